@@ -8,9 +8,11 @@
 A step is one EEMFlow inference forward (libeemflow_hip.so, HIP-graph replay) over one batch of
 synthetic event-voxel pairs already resident in HBM: BASELINE.json configs[1], 1280x720, batch 1.
 Ranks are independent replicas (frames shard over GPUs, no data-path collective): weak scaling.
-Rank 0 prints ONE JSON line with the whole-job frames/s, the roofline of the dominant kernel
-(per-kernel HIP-event timing via eemflow_time_kernels) and the CPU baseline (the oracle - the
-reference's PyTorch-CPU path restated - timed on this host's cores).
+Rank 0 prints ONE JSON line with the whole-job frames/s and ms_per_step.  With --full the line also
+holds the roofline of the dominant kernel (per-kernel HIP-event timing via eemflow_time_kernels),
+the CPU baseline (the oracle - the reference's PyTorch-CPU path restated - timed on this host's
+cores), the parity of the timed configuration against the oracle and the other rows.
+--dump-outputs DIR writes the flow of the last timed step as DIR/flow.npy.
 """
 import argparse
 import ctypes
@@ -76,8 +78,38 @@ def parse():
     p.add_argument("--rows-child", action="store_true",
                    help="internal: measure the other rows (E-RAFT, EEMFlow+, voxelizer, training steps) in THIS fresh process and print them as one JSON line")
     p.add_argument("--long-steps", type=int, default=400,
-                   help="a second, longer run of the same timed loop after the K steps (reported as value_long; 0 disables)")
+                   help="--full: a second, longer run of the same timed loop after the K steps (reported as value_long; 0 disables)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beyond the headline figure: the second timed run (value_long), per-kernel "
+                        "roofline tables, the CPU baseline and the parity of the timed configuration against the oracle, the other rows "
+                        "and the latency / pipeline rows.  Without it a run sets up, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                        "(float32 / float64, at most 64 MB in all: a fixed seeded sample of a larger output)")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000          # --dump-outputs: array bytes in all, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor or array} as out_dir/<name>.npy: float64 stays float64, everything else becomes float32.  Over the budget,
+    the budget is shared out smallest array first: an array within its share is written whole, a larger one as a sample of its
+    elements at fixed, seeded positions (flattened, in index order), so that two runs with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left = DUMP_BUDGET_BYTES
+    for i, name in enumerate(sorted(host, key=lambda n: host[n].nbytes)):
+        a = host[name]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, share // a.itemsize), replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def usable_cores():
@@ -634,6 +666,9 @@ def main_train(args):
     parallel.barrier(dev)
     value, slowest = parallel.aggregate_throughput(args.steps * B, elapsed, dev)
     ar_us = float(np.mean([a.elapsed_time(b) for a, b in evs])) * 1e3 if evs else 0.0
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        # the last step's flow, loss and flat gradient buffer (all-reduced) as the step left it
+        dump_outputs(args.dump_outputs, {"flow": flow, "grad": grad, "loss": np.array([loss], dtype=np.float64)})
     if rank == 0:
         flops = 3 * 14.583e9 * (H * W) / (720 * 1280)                   # ~3x the forward's direct-convolution count per sample
         line = {"metric": f"samples/sec, EEMFlow training step {W}x{H}, batch {B}/GPU, data parallel (BASELINE configs[3] shape)",
@@ -692,7 +727,8 @@ def main_eraft(args):
 
         def step(timed):
             opt.zero_grad()
-            loss, _ = sequence_loss(net(e1, e2, iters=iters)[1], gt, va, 0.8, metrics=False)
+            preds = net(e1, e2, iters=iters)[1]
+            loss, _ = sequence_loss(preds, gt, va, 0.8, metrics=False)
             loss.backward()
             have = [p for p in params if p.grad is not None]
             flat = torch.cat([p.grad.reshape(-1) for p in have])
@@ -711,12 +747,14 @@ def main_eraft(args):
             torch.nn.utils.clip_grad_norm_(net.parameters(), 1.0)
             opt.step()
             last["loss"] = loss
+            last["flow"] = preds[-1].detach()
     else:
         nparam = sum(p.numel() for p in net.parameters())
+        last = {}
 
         def step(timed):
             with torch.no_grad():
-                net(e1, e2, iters=iters)
+                last["flow"] = net(e1, e2, iters=iters)[1][-1]
 
     for _ in range(max(args.warmup, 1)):
         step(False)
@@ -730,6 +768,12 @@ def main_eraft(args):
     parallel.barrier(dev)
     value, slowest = parallel.aggregate_throughput(args.steps * B, elapsed, dev)
     ar_us = float(np.mean([a.elapsed_time(b) for a, b in evs])) * 1e3 if evs else 0.0
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        # the last step's final prediction (and, training, its loss)
+        outs = {"flow": last["flow"]}
+        if train:
+            outs["loss"] = np.array([float(last["loss"])], dtype=np.float64)
+        dump_outputs(args.dump_outputs, outs)
     if rank == 0:
         ms_per_step = slowest * 1e3 / args.steps
         gflop = ERAFT_GFLOP_PER_FRAME_640x480_12IT * (H * W) / (480 * 640) * iters / 12 * (3 if train else 1)     # ~3x forward per training sample
@@ -882,15 +926,17 @@ def main():
         return dst
 
     def timed(nsteps):
-        """nsteps frames through the loop, bracketed as the contract says; returns (elapsed s, HIP-event ms, host enqueue s)."""
+        """nsteps frames through the loop, bracketed as the contract says; returns (elapsed s, HIP-event ms, host enqueue s, the last
+        step's flow tensor)."""
         torch.cuda.synchronize(dev)
         parallel.barrier(dev)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         counter[0] = 0
         t0 = time.perf_counter()
         ev0.record(stream)
+        last = None
         for _ in range(nsteps):
-            step()
+            last = step()
         flush()                                          # a last, shorter call when CO does not divide nsteps
         enq = time.perf_counter() - t0                   # host time to hand the steps to the streams (reported; < elapsed = GPU-bound)
         for st in streams[1:]:
@@ -899,17 +945,18 @@ def main():
         torch.cuda.synchronize(dev)
         el = time.perf_counter() - t0
         parallel.barrier(dev)
-        return el, ev0.elapsed_time(ev1), enq
+        return el, ev0.elapsed_time(ev1), enq, last
 
     # Clock / runtime pre-heat (untimed, reported as "preheat_steps"): the contexts have just been built on an idle GPU, and the first
     # milliseconds after that run at ramping clocks with cold graph-launch paths (20 timed steps after 5 warm-up steps read 6 % lower than
     # after 100).  Every call size the loops below will issue (CO, and the remainders of the step counts) is captured here, on every
     # chain.  Then the W warm-up steps the caller asked for, then the timed region.
+    long_steps = args.long_steps if args.full else 0
     for _ in range(args.preheat):
         step()
     flush()
     if CO > 1:
-        for r in sorted({args.steps % CO, args.warmup % CO, args.long_steps % CO} - {0}):
+        for r in sorted({args.steps % CO, args.warmup % CO, long_steps % CO} - {0}):
             for _ in range(NS):
                 for _ in range(r):
                     step()
@@ -919,14 +966,35 @@ def main():
     for _ in range(args.warmup):
         step()
     flush()
-    elapsed, gpu_ms, enqueue_s = timed(args.steps)
+    elapsed, gpu_ms, enqueue_s, last_flow = timed(args.steps)
     value, slowest = parallel.aggregate_throughput(args.steps * B, elapsed, dev)
+    if rank == 0 and args.dump_outputs and last_flow is not None:
+        # the flow the last timed step's frame received (input pair (K - 1) mod --rotate-pairs), before anything below reuses its buffer
+        dump_outputs(args.dump_outputs, {"flow": last_flow})
+    ms_per_step = slowest * 1e3 / args.steps
+    line = {
+        "metric": baseline_metric(),
+        "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"EEMFlow inference, HREM {W}x{H} dt1, batch={B} per GPU (BASELINE configs[1]); "
+                               "synthetic 20%-dense voxel pairs resident in HBM, seeded Kaiming weights",
+                   "height": H, "width": W, "batch_per_gpu": B, "hip_graph": not args.no_graph, "streams_per_gpu": NS,
+                   "coalesced_frames": CO, "frames_in_flight_hint": args.frames_in_flight or NS, "preheat_steps": args.preheat,
+                   "input_pairs_rotated": n_rot, "input_bytes_rotated": n_rot * 2 * e1.numel() * 4,
+                   "parallelism": f"replicas x{world}: frames sharded over ranks, no data-path collective"},
+        "gpu_ms_per_step_hip_events": round(gpu_ms / args.steps, 4),
+        "host_enqueue_ms_per_step": round(enqueue_s * 1e3 / args.steps, 4),
+        "full": args.full,
+    }
     value_long = None
-    if args.long_steps > 0:
-        el_long, _, _ = timed(args.long_steps)
-        value_long, _ = parallel.aggregate_throughput(args.long_steps * B, el_long, dev)
+    if long_steps > 0:
+        el_long, _, _, _ = timed(long_steps)
+        value_long, _ = parallel.aggregate_throughput(long_steps * B, el_long, dev)
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(line), flush=True)
+    if rank == 0 and args.full:
         # ---- per-kernel roofline, measured live with HIP events on the launch stream, in the launch configuration of the timed loop
         # (frames_in_flight = streams: persistent encoder kernels on fewer blocks) and in the single-frame configuration (full grids)
         def kernel_table(frames_in_flight, nb=B, chain=True):
@@ -1065,7 +1133,6 @@ def main():
             _, cpu_small = cpu_baseline(sd_np, s1, s2, min(3.0, args.cpu_seconds))
             extra["cpu_baseline_346x260"] = cpu_small
 
-        ms_per_step = slowest * 1e3 / args.steps
         # the robust number: the frame's direct-convolution FLOPs at the fp32 MFMA peak (its ceiling with the direct algorithm on that
         # pipe) over the measured time per step of one GPU
         ceiling_ms = total_gflop / PEAK_MFMA_F32_TFLOPS                    # GFLOP of one step (its whole batch) / (TFLOP/s) = ms
@@ -1078,26 +1145,14 @@ def main():
             roof["frame_hbm_mbytes"] = tr_now["_encoder_mb_per_frame"]
             roof["frame_hbm_gbs"] = round(tr_now["_encoder_mb_per_frame"] / 1e3 / (ms_per_step * 1e-3), 1)
             roof["frame_hbm_frac"] = round(roof["frame_hbm_gbs"] / PEAK_HBM_GBS, 4)
-        line = {
-            "metric": baseline_metric(),
-            "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"EEMFlow inference, HREM {W}x{H} dt1, batch={B} per GPU (BASELINE configs[1]); "
-                                   "synthetic 20%-dense voxel pairs resident in HBM, seeded Kaiming weights",
-                       "height": H, "width": W, "batch_per_gpu": B, "hip_graph": not args.no_graph, "streams_per_gpu": NS,
-                       "coalesced_frames": CO, "frames_in_flight_hint": args.frames_in_flight or NS, "preheat_steps": args.preheat,
-                       "input_pairs_rotated": n_rot, "input_bytes_rotated": n_rot * 2 * e1.numel() * 4,
-                       "parallelism": f"replicas x{world}: frames sharded over ranks, no data-path collective"},
+        line.update({
             "roofline": roof, "roofline_single_frame_launch": roof_single, "cpu_baseline": cpu,
             "value_long": None if value_long is None else round(value_long, 2), "value_long_steps": args.long_steps,
-            "gpu_ms_per_step_hip_events": round(gpu_ms / args.steps, 4),
-            "host_enqueue_ms_per_step": round(enqueue_s * 1e3 / args.steps, 4),
             "schedule_sum_us": round(sum_us, 1), "schedule_frames_per_launch": CO * B, "frame_gflop": round(total_gflop, 3),
             "frame_tflops": round(total_gflop / ms_per_step, 2),
             "encoder_tflops_in_kernel": round(enc_tflops, 2),
             "kernels": kernels, **extra,
-        }
+        })
         # The other rows are measured in a FRESH child process (its own HIP context; this one idles meanwhile): in this process, behind the
         # batch-10 workspaces of the main loop, whichever of them comes late runs slower ON THE GPU with the host enqueue unchanged -
         # single-stream E-RAFT 178 -> 70 frames/s behind the pipeline section, or the E-RAFT training step 94 -> 112 ms when the rows come

@@ -113,8 +113,17 @@ def test_decoder_winograd_streams_follow_the_optimizer_steps(monkeypatch):
         weights[mode] = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     fresh = {k: torch.as_tensor(v).cpu() for k, v in sd.items()}
     moved = max(float((weights["1"][k] - fresh[k]).abs().max()) for k in fresh)
-    drift = max(float((weights["1"][k] - weights["0"][k]).abs().max()) for k in fresh)
-    assert moved > 1e-3 and drift < 1e-2 * moved                                    # both forms train the same model
+    drifts = sorted(((float((weights["1"][k] - weights["0"][k]).abs().max()), k) for k in fresh), reverse=True)
+    # Both forms train the same model.  LeakyReLU is not differentiable at 0 (test_gradients_vs_oracle_autograd): a pconv3_1 pixel that
+    # the two forms' roundings - and the weight gradients' atomics, from run to run - put on different sides of 0 changes some of that
+    # layer's weight gradients, and AdamW turns them into steps of another size (measured: 3.7e-4 = 15 % of moved on pconv3_1.0.weight;
+    # without such a pixel the drift is 0.6 % of moved).  So: every tensor within 1 % of moved except at most one layer's weight / bias
+    # pair, which is not a decoder's conv1 / conv5 (the layers the two forms compute) and stays within half of moved.
+    assert moved > 1e-3 and all(d < 1e-2 * moved for d, _ in drifts[2:]), (moved, drifts[:4])
+    for d, k in drifts[:2]:
+        assert d < 1e-2 * moved or (d < 0.5 * moved and ".conv1." not in k and ".conv5." not in k), (moved, d, k)
+    if drifts[1][0] >= 1e-2 * moved:
+        assert drifts[0][1].rsplit(".", 1)[0] == drifts[1][1].rsplit(".", 1)[0], (moved, drifts[:2])
     assert float((flows["1"] - flows["0"]).abs().max()) < 5e-2 * max(1.0, float(flows["0"].abs().max()))
 
 

@@ -4,8 +4,8 @@ tag=${1:-ab}; var=${2:-EEM_NO_STAGGER}
 out=gpurun_out/$tag; mkdir -p $out
 for v in "" 1; do
   if [ -z "$v" ]; then unset $var; n=default; else export $var=$v; n=${var}_$v; fi
-  timeout 300 python3 bench.py --steps 300 --warmup 30 --cpu-seconds 0 --no-other-rows > $out/bench_$n.json 2> $out/err_$n.txt
-  timeout 300 python3 bench.py --steps 300 --warmup 30 --cpu-seconds 0 --no-other-rows --streams 1 > $out/bench_s1_$n.json 2>> $out/err_$n.txt
+  timeout 300 python3 bench.py --full --steps 300 --warmup 30 --cpu-seconds 0 --no-other-rows > $out/bench_$n.json 2> $out/err_$n.txt
+  timeout 300 python3 bench.py --full --steps 300 --warmup 30 --cpu-seconds 0 --no-other-rows --streams 1 > $out/bench_s1_$n.json 2>> $out/err_$n.txt
   python3 - <<P
 import json
 for f in ("$out/bench_$n.json", "$out/bench_s1_$n.json"):

@@ -5,7 +5,7 @@ run() {  # co ns hint
   local hint=""
   [ "$3" != "0" ] && hint="--frames-in-flight $3"
   for rep in 1 2 3; do
-  python bench.py --steps 20 --warmup 5 --coalesce $1 --streams $2 $hint --cpu-seconds 0 --no-side-rows --no-other-rows 2>/dev/null |
+  python bench.py --full --steps 20 --warmup 5 --coalesce $1 --streams $2 $hint --cpu-seconds 0 --no-side-rows --no-other-rows 2>/dev/null |
     python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('co $1 ns $2 hint $3 : value(20)', d['value'], ' value_long(400)', d['value_long'])"
   done
 }

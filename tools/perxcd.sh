@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: tuning sweeps with four frames in flight (env overrides of the persistent grid sizes / stride-2 tilings)
-run() { python3 bench.py --steps 600 --warmup 40 --cpu-seconds 0 --no-other-rows --no-side-rows --streams ${NSTR:-4} 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --steps 600 --warmup 40 --cpu-seconds 0 --no-other-rows --no-side-rows --streams ${NSTR:-4} 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['value'], 'fps', ' '.join(str(k['us']) for k in d['kernels'][:8]))"; }
 run base

@@ -5,7 +5,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for c in FETCH_SIZE WRITE_SIZE; do
-  env "$@" timeout 300 rocprofv3 --pmc $c --output-format csv -d $out/$c -- python3 bench.py --steps 20 --warmup 10 --long-steps 0 --preheat 10 --cpu-seconds 0 --no-graph --streams 1 --coalesce $co --kernel-reps 2 --no-other-rows --no-side-rows > /dev/null 2> $out/$c.err
+  env "$@" timeout 300 rocprofv3 --pmc $c --output-format csv -d $out/$c -- python3 bench.py --full --steps 20 --warmup 10 --long-steps 0 --preheat 10 --cpu-seconds 0 --no-graph --streams 1 --coalesce $co --kernel-reps 2 --no-other-rows --no-side-rows > /dev/null 2> $out/$c.err
 done
 python3 - <<P
 import csv, glob, collections

@@ -8,7 +8,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for fuse in 1 0; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    EEM_FUSE12=$fuse timeout 300 rocprofv3 --pmc $c --output-format csv -d $out/f$fuse/$c -- python3 bench.py --steps 5 --warmup 2 --long-steps 0 --preheat 4 --cpu-seconds 0 --no-graph --streams 1 --coalesce 1 --frames-in-flight 4 --kernel-reps 3 --no-other-rows --no-side-rows > /dev/null 2> $out/f${fuse}_$c.err
+    EEM_FUSE12=$fuse timeout 300 rocprofv3 --pmc $c --output-format csv -d $out/f$fuse/$c -- python3 bench.py --full --steps 5 --warmup 2 --long-steps 0 --preheat 4 --cpu-seconds 0 --no-graph --streams 1 --coalesce 1 --frames-in-flight 4 --kernel-reps 3 --no-other-rows --no-side-rows > /dev/null 2> $out/f${fuse}_$c.err
   done
 done
 python3 - <<P

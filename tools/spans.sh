@@ -6,5 +6,5 @@ export EEM_LIB_PATH="$(cd "$(dirname "$0")/.." && pwd)/eemflow_amd/libeemflow_hi
 [ -f "$EEM_LIB_PATH" ] || { echo "build the diagnostic library first" >&2; exit 1; }
 for s in 1 2 3 4; do
   echo "== $s frame(s) in flight (eager launches)"
-  EEM_SPANS=1 python3 bench.py --steps 400 --warmup 30 --preheat 50 --cpu-seconds 0 --no-other-rows --no-side-rows --no-graph --streams $s --frames-in-flight 4 "$@" 2>&1 >/dev/null | grep EEM_SPANS | tail -$s
+  EEM_SPANS=1 python3 bench.py --full --steps 400 --warmup 30 --preheat 50 --cpu-seconds 0 --no-other-rows --no-side-rows --no-graph --streams $s --frames-in-flight 4 "$@" 2>&1 >/dev/null | grep EEM_SPANS | tail -$s
 done
