@@ -40,6 +40,10 @@ _SIGNATURES = {
     "eemflow_forward_many": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_void_p]),
+    "eemflow_forward_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "eemflow_stream_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "eemflow_stream_pending": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "eemflow_time_kernels": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KernelStat),
                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),

@@ -56,7 +56,7 @@ extern "C" void eemflow_destroy(eemflow_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     drop_graph(c);
-    DevBuf* bufs[] = {&c->a1, &c->f11, &c->a2, &c->b2, &c->f12, &c->a3, &c->b3, &c->f13, &c->flowcat, &c->coarse,
+    DevBuf* bufs[] = {&c->a1, &c->f11, &c->a2, &c->b2, &c->f12, &c->a3, &c->b3, &c->f13, &c->flowcat, &c->coarse, &c->carry,
                       &c->padded, &c->fuse_scratch, &c->g_a1, &c->g_f11, &c->g_a2, &c->g_b2, &c->g_f12, &c->g_a3, &c->g_b3, &c->g_f13,
                       &c->g_flowcat, &c->g_coarse, &c->g_flow, &c->ups_tmp, &c->grad_flat, &c->adam_m, &c->adam_v, &c->scalars};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
@@ -327,16 +327,28 @@ extern "C" int eemflow_set_frames_in_flight(eemflow_ctx* c, int n) {
     return EEM_OK;
 }
 
+// A stream call (eemflow_forward_stream): `batch` flows of consecutive windows, whose nframes new windows are e1[0 .. nframes-1]
+struct StreamCall {
+    int carry_in, slot_in, slot_out;
+};
+
 // One forward of `batch` samples.  nframes == 0: events1 / events2 / flow are contiguous [batch, ...] tensors (e1[0], e2[0], out[0]).
 // nframes == batch >= 1 (eemflow_forward_many): every sample is its own single-frame buffer triple {e1[i], e2[i], out[i]}; the two
 // launches that touch caller memory find them through the io table's per-frame triples, everything between is the batch-n chain.
+// sc != NULL (eemflow_forward_stream): nframes windows e1[i] (e2[i] NULL) in the triples' first slots, flow i < batch in the third
 static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, const float* const* e2, float* const* out, int batch,
-                          int in_h, int in_w, int out_h, int out_w, void* stream) {
+                          int in_h, int in_w, int out_h, int out_w, void* stream, const StreamCall* sc = nullptr) {
     EEM_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     Shape s;
-    int rc = compute_shape(c, batch, in_h, in_w, out_h, out_w, &s);
+    int rc = compute_shape(c, batch, in_h, in_w, out_h, out_w, &s, sc ? nframes : -1);
     if (rc != EEM_OK) return rc;
+    if (sc) {
+        s.stream = 1; s.carry_in = sc->carry_in; s.slot_in = sc->slot_in; s.slot_out = sc->slot_out;
+        const unsigned long moved = g_realloc_events;
+        if ((rc = ensure(c->carry, 2 * 112 * (size_t)s.gh * s.gw)) != EEM_OK) return rc;
+        if (g_realloc_events != moved) drop_graph(c);                 // the cached stream graphs point into the carry slots
+    }
     const int nptr = nframes > 0 ? 3 * nframes : 3;
     const void* want[3 * EEM_MAX_COALESCE];
     uintptr_t bits = 0;
@@ -362,7 +374,7 @@ static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, c
 
     c->workspace_overwritten();
     c->last_e1 = e1[0]; c->last_e2 = e2[0]; c->last_io_frames = nframes;
-    if ((rc = ensure_forward_wino(c, batch, st)) != EEM_OK) return rc;          // outside any capture
+    if ((rc = ensure_forward_wino(c, s.enc_batch, st)) != EEM_OK) return rc;    // outside any capture
     if (!c->use_graph || c->enc0_generic) {                           // (the generic first layer pads through the caller's pointers: no io table)
         if ((rc = alloc_workspace(c, s)) != EEM_OK) return rc;
         c->last = s;
@@ -376,8 +388,9 @@ static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, c
         c->cur_io_frames = 0;
         return rc;
     }
-    const eemflow_ctx::Key key = {batch, in_h, in_w, out_h, out_w, {c->pad[0], c->pad[1], c->pad[2], c->pad[3]}, aligned, nframes,
-                                  c->deferred_norm ? 1 : 0};
+    eemflow_ctx::Key key = {batch, in_h, in_w, out_h, out_w, {c->pad[0], c->pad[1], c->pad[2], c->pad[3]}, aligned, nframes,
+                            c->deferred_norm ? 1 : 0};
+    if (sc) { key.stream_nvol = nframes; key.stream_carry = sc->carry_in; key.stream_slot = sc->slot_out; }
     eemflow_ctx::GraphEntry* ent = nullptr;
     for (eemflow_ctx::GraphEntry& g : c->graphs)
         if (g.key == key) ent = &g;
@@ -464,6 +477,68 @@ extern "C" int eemflow_forward_many(eemflow_ctx* c, int nframes, const float* co
                     "eemflow_forward_many: frame %d: buffers must be 16-byte aligned (torch allocations are)", i);
     }
     return forward_common(c, nframes, e1, e2, out, nframes, in_h, in_w, out_h, out_w, stream);
+}
+
+// Consecutive windows of one event stream (test_mvsec.py:580-597 walks a sequence with stride 1; MVSEC.py:115-116 builds sample i from
+// windows i and i + 1): every window is encoded ONCE - the call's nvol new windows as one encoder batch - and the last one's pooled maps
+// are carried to the next call, where they stand in for the older window of its first pair.  Flow p is bitwise what eemflow_forward_many
+// gives for that pair (same kernels; the carried maps are the values the correlation read from the partial sums).
+extern "C" int eemflow_forward_stream(eemflow_ctx* c, int nvol, const float* const* volumes, float* const* flow_out, int nflow, int in_h,
+                                      int in_w, int out_h, int out_w, void* stream) {
+    EEM_REQUIRE(c && volumes, "eemflow_forward_stream: NULL argument");
+    EEM_REQUIRE(nvol >= 1 && nvol <= EEM_STREAM_MAX_VOLUMES, "eemflow_forward_stream: 1..%d volumes per call; got %d", EEM_STREAM_MAX_VOLUMES, nvol);
+    EEM_REQUIRE(c->weights_loaded, "eemflow_forward_stream: no weights loaded");
+    EEM_REQUIRE(c->have_pad, "eemflow_forward_stream: call eemflow_set_image_size first");
+    EEM_REQUIRE(in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, "eemflow_forward_stream: bad sizes");
+    EEM_REQUIRE(!c->enc0_generic, "eemflow_forward_stream: built for the 5-bin first layer (n_first_channels == 5)");
+    if (c->stream_pending) {
+        EEM_REQUIRE(c->stream_wver == c->weights_version, "eemflow_forward_stream: the weights changed since the carried window was encoded; "
+                    "call eemflow_stream_reset to start a new stream");
+        EEM_REQUIRE(c->stream_h == in_h && c->stream_w == in_w && memcmp(c->stream_pad, c->pad, sizeof(c->pad)) == 0,
+                    "eemflow_forward_stream: the carried window is %dx%d, this call's volumes are %dx%d (or the padding changed); "
+                    "call eemflow_stream_reset to start a new stream", c->stream_h, c->stream_w, in_h, in_w);
+    }
+    const int want = c->stream_pending ? nvol : nvol - 1;
+    EEM_REQUIRE(nflow == want, "eemflow_forward_stream: %d volumes %s give %d flows; nflow = %d", nvol,
+                c->stream_pending ? "after the carried window" : "with no carried window", want, nflow);
+    EEM_REQUIRE(nflow == 0 || flow_out, "eemflow_forward_stream: flow_out is NULL");
+    for (int i = 0; i < nvol; ++i) {
+        EEM_REQUIRE(volumes[i], "eemflow_forward_stream: volume %d is NULL", i);
+        EEM_REQUIRE(((uintptr_t)volumes[i] & 15) == 0, "eemflow_forward_stream: volume %d: buffers must be 16-byte aligned (torch allocations are)", i);
+    }
+    for (int i = 0; i < nflow; ++i) {
+        EEM_REQUIRE(flow_out[i], "eemflow_forward_stream: flow %d is NULL", i);
+        EEM_REQUIRE(((uintptr_t)flow_out[i] & 15) == 0, "eemflow_forward_stream: flow %d: buffers must be 16-byte aligned (torch allocations are)", i);
+    }
+    const float* none[EEM_MAX_COALESCE] = {};
+    float* outs[EEM_MAX_COALESCE] = {};
+    for (int i = 0; i < nflow; ++i) outs[i] = flow_out[i];
+    StreamCall sc;
+    sc.carry_in = c->stream_pending ? 1 : 0;
+    sc.slot_in = c->stream_slot;
+    sc.slot_out = c->stream_pending ? 1 - c->stream_slot : 0;
+    c->stream_pending = false;                                   // (a failed call leaves no carry behind)
+    const int rc = forward_common(c, nvol, volumes, none, outs, nflow, in_h, in_w, out_h, out_w, stream, &sc);
+    c->have_last = false;                                        // the workspace holds windows, not a forward's pairs (eemflow_get_stage)
+    if (rc != EEM_OK) return rc;
+    c->stream_pending = true;
+    c->stream_slot = sc.slot_out;
+    c->stream_wver = c->weights_version;
+    c->stream_h = in_h; c->stream_w = in_w;
+    memcpy(c->stream_pad, c->pad, sizeof(c->pad));
+    return EEM_OK;
+}
+
+extern "C" int eemflow_stream_reset(eemflow_ctx* c) {
+    EEM_REQUIRE(c, "eemflow_stream_reset: NULL context");
+    c->stream_pending = false;
+    return EEM_OK;
+}
+
+extern "C" int eemflow_stream_pending(eemflow_ctx* c, int* out) {
+    EEM_REQUIRE(c && out, "eemflow_stream_pending: NULL argument");
+    *out = c->stream_pending ? 1 : 0;
+    return EEM_OK;
 }
 
 // Graph-cache statistics of a context: captures (stream captures + instantiations), replays, io-table rewrites.

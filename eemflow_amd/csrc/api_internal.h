@@ -41,6 +41,13 @@ struct Shape {
     // fused stage pooling (fast path): partial-sum buffer dims per stage, fuse[k] = conv epilogue pools stage k
     bool fuse[3] = {false, false, false};
     int prow[3] = {0, 0, 0}, pcol[3] = {0, 0, 0}, th[3] = {0, 0, 0};
+    // the encoder's batch: nimg images, the first nimg0 of them from events1; enc_batch is the sample count its per-batch policies see
+    // (f4_mask, the block walks).  A forward: 2 * batch, batch, batch.  A stream call (eemflow_forward_stream): the nvol new windows,
+    // all from the per-frame table, and nvol / 2 - the sample count whose forward encodes as many images
+    int nimg = 0, nimg0 = 0, enc_batch = 0;
+    // stream call: `batch` pairs of consecutive windows; carry_in: pair 0 starts at the carried window, read from carry slot
+    // `slot_in`; the last window's finished maps go to slot `slot_out`
+    int stream = 0, carry_in = 0, slot_in = 0, slot_out = 0;
 };
 
 }  // namespace
@@ -165,6 +172,16 @@ struct eemflow_ctx {
     const float* last_e1 = nullptr;                      // the last forward's caller buffers (contiguous form) / its io-table form
     const float* last_e2 = nullptr;
     int last_io_frames = 0;
+    // bumped by every change of the device-resident weights (refresh_wino): what a carried stream window was encoded with
+    long weights_version = 0;
+    // eemflow_forward_stream: the last window's finished pooled maps, 16 + 32 + 64 channels on the 1/64 grid, in one of two slots
+    // (a call reads one and writes the other).  Owned by the context, apart from the shared workspace: forward / forward_many /
+    // forward_train between two stream calls leave it alone
+    DevBuf carry;
+    bool stream_pending = false;
+    int stream_slot = 0;                                 // the slot holding the carried window
+    long stream_wver = 0;                                // weights_version it was encoded with
+    int stream_h = 0, stream_w = 0, stream_pad[4] = {0, 0, 0, 0};
     int frames_in_flight = 1;                            // eemflow_set_frames_in_flight: >= 3 shrinks the persistent encoder grids
     // eemflow_set_deferred_input_norm: the event volumes handed to forward / forward_many are RAW voxel grids with their normalisation
     // record behind them (eemflow_voxelize*, normalize = 2); pconv1_1 normalises as it reads
@@ -174,10 +191,13 @@ struct eemflow_ctx {
         int aligned16;                                   // all three caller buffers 16-byte aligned (kernel selection depends on it)
         int io_frames;                                   // 0: one batch in contiguous tensors; n: n single-frame buffer triples (eemflow_forward_many)
         int deferred_norm;
+        int stream_nvol = 0;                             // eemflow_forward_stream: windows per call (0: a forward), carry present, carry slot
+        int stream_carry = 0, stream_slot = 0;           // written (the slot read is the other one)
         bool operator==(const Key& o) const {
             return batch == o.batch && in_h == o.in_h && in_w == o.in_w && out_h == o.out_h && out_w == o.out_w &&
                    pad[0] == o.pad[0] && pad[1] == o.pad[1] && pad[2] == o.pad[2] && pad[3] == o.pad[3] && aligned16 == o.aligned16 &&
-                   io_frames == o.io_frames && deferred_norm == o.deferred_norm;
+                   io_frames == o.io_frames && deferred_norm == o.deferred_norm && stream_nvol == o.stream_nvol &&
+                   stream_carry == o.stream_carry && stream_slot == o.stream_slot;
         }
     };
     struct GraphEntry {
@@ -224,6 +244,7 @@ int refresh_wino(eemflow_ctx* c, hipStream_t) {
     for (int l = 0; l < ENC_NUM; ++l) c->s2r_ok[l] = false;
     for (int l = 0; l < ENC_NUM; ++l) c->bx3_ok[l] = false;
     c->dec_wnc_ok = false;
+    c->weights_version += 1;
     return EEM_OK;
 }
 // The packed forms a launch can actually take (the opt-in kernels' switches are read per launch - conv_s2r.hip, conv_bx3.hip - and so are
@@ -343,8 +364,12 @@ void drop_graph(eemflow_ctx* c) {
     c->graphs.clear();
 }
 
-int compute_shape(eemflow_ctx* c, int batch, int in_h, int in_w, int out_h, int out_w, Shape* s) {
+// nimg >= 0: a stream call's encoder batch of nimg windows (Shape::nimg); -1: a forward's 2 * batch
+int compute_shape(eemflow_ctx* c, int batch, int in_h, int in_w, int out_h, int out_w, Shape* s, int nimg = -1) {
     s->batch = batch; s->in_h = in_h; s->in_w = in_w; s->out_h = out_h; s->out_w = out_w;
+    s->nimg = nimg >= 0 ? nimg : 2 * batch;
+    s->nimg0 = nimg >= 0 ? nimg : batch;
+    s->enc_batch = nimg >= 0 ? nimg / 2 : batch;
     s->hp = in_h + c->pad[2] + c->pad[3];
     s->wp = in_w + c->pad[0] + c->pad[1];
     auto half = [](int v) { return (v - 1) / 2 + 1; };          // conv k3 s2 p1
@@ -366,7 +391,7 @@ int compute_shape(eemflow_ctx* c, int batch, int in_h, int in_w, int out_h, int 
         const EncLayerDesc& d = kEncLayers[last[k]];
         int th, tw, pk;
         const bool wino = c->use_wino && c->enc_wino[last[k]] && wino_supported(d.cin, d.cout, d.stride, ws[k]);
-        if (wino) wino_tile(d.cin, c->layer_f4(d.cin, batch) ? 1 : 0, &th, &tw, &pk);
+        if (wino) wino_tile(d.cin, c->layer_f4(d.cin, s->enc_batch) ? 1 : 0, &th, &tw, &pk);
         else enc2_tile(d.cin, d.cout, &th, &tw, &pk);
         s->fuse[k] = (wino || (c->enc_has2[last[k]] && enc2_supported(d.cin, d.cout, d.stride, ws[k]))) && pk == ks[k];
         s->th[k] = th;
@@ -386,7 +411,7 @@ int alloc_workspace(eemflow_ctx* c, const Shape& s) {
 }
 
 int alloc_workspace_raw(eemflow_ctx* c, const Shape& s) {
-    const size_t n2 = 2 * (size_t)s.batch, B = s.batch, g = (size_t)s.gh * s.gw;
+    const size_t n2 = (size_t)s.nimg, B = s.batch, g = (size_t)s.gh * s.gw;
     int rc;
 #define ENS(buf, n) if ((rc = ensure(buf, n)) != EEM_OK) return rc
     ENS(c->a1, n2 * 16 * s.h1 * s.w1);  ENS(c->f11, n2 * 16 * s.h1 * s.w1);
@@ -681,7 +706,7 @@ static int span_mark(eemflow_ctx* c, int i, hipStream_t st) {
 int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const float* e2, Hook& hk, const void* const* io,
                   const float* prepadded, bool may_skip_store) {
     int rc;
-    const int n2 = 2 * s.batch;
+    const int n2 = s.nimg;
     struct Step { int layer; const char* name; const float* in; float* out; int hin, win, hout, wout; };
     const Step steps[ENC_NUM] = {
         {ENC_1_1, "enc.pconv1_1 5->16 s2 +pad", nullptr, c->a1.p, s.hp, s.wp, s.h1, s.w1},
@@ -726,7 +751,7 @@ int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const
         a.wpk2 = c->enc_has2[sp.layer] ? c->arena + c->enc_w2[sp.layer] : nullptr;
         a.wwino = nullptr;
         a.wino_f4 = 0;
-        if (c->use_wino && c->enc_wino[sp.layer] && (rc = ensure_wino(c, sp.layer, 0, s.batch, hk.st, &a.wwino, &a.wino_f4)) != EEM_OK) return rc;
+        if (c->use_wino && c->enc_wino[sp.layer] && (rc = ensure_wino(c, sp.layer, 0, s.enc_batch, hk.st, &a.wwino, &a.wino_f4)) != EEM_OK) return rc;
         a.ws2r = nullptr;
         if (c->enc_s2r[sp.layer] && s2r_wanted() && (rc = ensure_s2r(c, sp.layer, hk.st, &a.ws2r)) != EEM_OK) return rc;
         a.wbx3 = nullptr;
@@ -735,7 +760,7 @@ int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const
         a.trash = c->zero_page + 256;
         a.bias = c->arena + c->enc_b[sp.layer];
         a.out = sp.out;
-        a.nimg = n2; a.nimg0 = sp.layer == ENC_1_1 ? s.batch : n2;
+        a.nimg = n2; a.nimg0 = sp.layer == ENC_1_1 ? s.nimg0 : n2;
         a.hin = sp.hin; a.win = sp.win; a.hout = sp.hout; a.wout = sp.wout;
         a.hraw = sp.layer == ENC_1_1 ? s.in_h : sp.hin;
         a.wraw = sp.layer == ENC_1_1 ? s.in_w : sp.win;
@@ -756,14 +781,14 @@ int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const
         a.no_store = 0;
         {   // batched chains (EEM_ZIGZAG=<layer mask>, experiment): this layer walks the images back to front
             static const int zz = [] { const char* e = getenv("EEM_ZIGZAG"); return e ? atoi(e) : 0; }();
-            a.reverse = (s.batch >= 2 && ((zz >> sp.layer) & 1)) ? 1 : 0;
+            a.reverse = (s.enc_batch >= 2 && ((zz >> sp.layer) & 1)) ? 1 : 0;
             // ... or in COLUMNS (EEM_COLWALK=<layer mask>; default: the two 64-channel layers of a batched chain).  Measured at ten frames
             // per launch (rocprofv3 FETCH_SIZE): the 32-pixel-wide tiles of the 64-channel layers fetch 22.3 MB per frame in row order
             // and 10.8 / 10.3 in column order (a tile row touches three cache lines for one of payload, and in row order the neighbour
             // that shares two of them comes a whole tile later); 32 channels 29.0 -> 32.2 (worse), 16 channels unchanged; frame rate the
             // same within noise either way - those layers are bound by their transforms, not their bytes
             static const int cw = [] { const char* e = getenv("EEM_COLWALK"); return e ? atoi(e) : (1 << ENC_3_2) | (1 << ENC_3_3); }();
-            if (s.batch >= 2 && ((cw >> sp.layer) & 1)) a.reverse = 2;
+            if (s.enc_batch >= 2 && ((cw >> sp.layer) & 1)) a.reverse = 2;
             // ... or INTERLEAVED (EEM_WALK3=<layer mask>, round 6): an XCD's blocks take every G-th tile of its range, so neighbouring
             // tiles are in flight together (conv_wino4.hip)
             // Measured at ten frames per launch (profiles/r06_walk3.txt): FETCH_SIZE per frame pconv1_2 49.5 -> 32.8 MB (31.5 of input),
@@ -771,7 +796,7 @@ int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const
             // 10 290 -> 10 500 frames/s over 400 steps.  Default for every stride-1 layer of a batched chain (supersedes the column walk).
             static const int w3 = [] { const char* e = getenv("EEM_WALK3");
                                        return e ? atoi(e) : (1 << ENC_1_2) | (1 << ENC_2_2) | (1 << ENC_2_3) | (1 << ENC_3_2) | (1 << ENC_3_3); }();
-            if (s.batch >= 2 && ((w3 >> sp.layer) & 1)) a.reverse = 3;
+            if (s.enc_batch >= 2 && ((w3 >> sp.layer) & 1)) a.reverse = 3;
             static const int nts = [] { const char* e = getenv("EEM_NT_STORE"); return e ? atoi(e) : 0; }();
             a.nt_store = ((nts >> sp.layer) & 1) | ((nts >> 8) & 2);          // (bit 9, diagnostic builds: the weight-slice experiment of conv_wino4.hip)
         }
@@ -808,7 +833,7 @@ int run_enc12(eemflow_ctx* c, const Shape& s, const float* e1, const float* e2, 
     // launches it replaces, kept for the traffic it saves and as the record of that measurement
     const char* eon = getenv("EEM_FUSE12");
     const bool off = !(eon && eon[0] == '1');
-    if (off || c->deferred_norm || c->keep_stage_stores || c->enc0_generic || prepadded != nullptr || !c->use_wino || !c->enc_wino[ENC_1_2] ||
+    if (off || s.stream || c->deferred_norm || c->keep_stage_stores || c->enc0_generic || prepadded != nullptr || !c->use_wino || !c->enc_wino[ENC_1_2] ||
         !c->layer_f4(16, s.batch) || !s.fuse[0] || c->fuse_scratch.p == nullptr)
         return EEM_OK;
     int rc;
@@ -849,8 +874,8 @@ int run_forward(eemflow_ctx* c, const Shape& s, const float* e1, const float* e2
 int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const float* e2, float* out, Hook& hk,
                      const void* const* io, const float* prepadded) {
     int rc;
-    const int n2 = 2 * s.batch;
-    // ---- encoder (both event volumes as one batch; shared weights, EEMFlow.py:135-140)
+    const int n2 = s.nimg;
+    // ---- encoder (both event volumes as one batch; shared weights, EEMFlow.py:135-140; a stream call: its new windows)
     // pconv1_1 + pconv1_2 as one launch when nothing needs a1 itself (inference; the training forward keeps every activation)
     bool fused12 = false;
     if ((rc = run_enc12(c, s, e1, e2, hk, io, prepadded, &fused12)) != EEM_OK) return rc;
@@ -887,7 +912,42 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
             if (rc != EEM_OK) return rc;
         }
         if ((rc = span_mark(c, 1, hk.st)) != EEM_OK) return rc;
-        if (!no_fuse) {
+        if (s.stream) {
+            // consecutive windows: pair b compares window b - 1 + i2_off with the next one; the carried window's finished maps stand in for
+            // window -1, and the last window's finished maps become the next call's carry (the other slot: no launch reads what it writes)
+            EEM_REQUIRE(!no_fuse, "eemflow_forward_stream needs the fused tail head (EEM_NO_TAIL_FUSE is set)");
+            TailHeadStreamArgs sa;
+            memset(&sa, 0, sizeof(sa));
+            TailHeadArgs& ha = sa.base;
+            const size_t coff[3] = {0, 16 * g, 48 * g}, slot = 112 * g;
+            for (int k = 0; k < 3; ++k) {
+                PooledSrc& ps = ha.src[k];
+                if (s.fuse[k]) {
+                    const int rows = ks[k] / s.th[k];
+                    ps.base = c->ppart[k].p; ps.rows = rows; ps.rstride = s.pcol[k]; ps.ystride = rows * s.pcol[k];
+                    ps.cstride = s.prow[k] * s.pcol[k]; ps.nstride = pc[k] * ps.cstride; ps.scale = 1.f / (float)(ks[k] * ks[k]);
+                } else {
+                    ps.base = c->pool[k].p; ps.rows = 1; ps.rstride = 0; ps.ystride = s.gw; ps.cstride = (int)g;
+                    ps.nstride = pc[k] * (int)g; ps.scale = 1.f;
+                }
+                PooledSrc& cs = sa.carry[k];
+                cs.base = s.carry_in ? c->carry.p + s.slot_in * slot + coff[k] : nullptr;
+                cs.rows = 1; cs.rstride = 0; cs.ystride = s.gw; cs.cstride = (int)g; cs.nstride = pc[k] * (int)g; cs.scale = 1.f;
+                ha.c[k] = pc[k];
+                ha.cat[k] = c->cat[k].p;
+                ha.pool_out[k] = c->carry.p + s.slot_out * slot + coff[k];
+                ha.rw[k] = c->arena + c->rconv[k].wpk;
+                ha.rb[k] = c->arena + c->rconv[k].bias;
+            }
+            ha.batch = s.batch; ha.gh = s.gh; ha.gw = s.gw; ha.ntaps = kNTaps; ha.cat_ctotal = kDecIn;
+            sa.i2_off = s.carry_in ? 0 : 1;
+            sa.pool_img = s.nimg - 1;
+            const double fl = 2.0 * s.batch * g * (kNTaps * (16 + 32 + 64) + 16.0 * 9 * (16 + 32 + 64));
+            rc = hk.run("tail head: stream pool+corr53+rconv", fl, 4.0 * (fin_elems + 3.0 * s.batch * g * kDecIn),
+                        [&](hipStream_t st) { return tail_head_stream_launch(sa, kTaps53, st); });
+            if (rc != EEM_OK) return rc;
+            if (s.batch == 0) return EEM_OK;                 // a first call of one window: nothing to decode, the carry is written
+        } else if (!no_fuse) {
             TailHeadArgs ha;
             memset(&ha, 0, sizeof(ha));
             for (int k = 0; k < 3; ++k) {

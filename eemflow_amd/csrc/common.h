@@ -358,6 +358,17 @@ struct TailHeadArgs {
     int tap[TAIL_HEAD_MAX_TAPS]; // filled by the launcher from taps_host: the selected taps of the 9x9 window (EEMFlow.py:14-23)
 };
 int tail_head_launch(const TailHeadArgs& a, const int* taps_host, hipStream_t stream);
+// The head of a stream of consecutive windows (eemflow_forward_stream): `base.src` holds this call's images 0..nimg-1 and pair b compares
+// image i2 - 1 with image i2 = b + i2_off (i2_off 1: the pairs (0, 1), (1, 2), ...; 0: pair 0 starts at the carried window).  An image
+// index below 0 is the carried window, read from `carry` (finished maps [c][gh][gw]: rows 1, scale 1 - the value the pooled-map role
+// wrote, bitwise).  The pooled-map role writes image `pool_img` alone, [c][gh][gw] into base.pool_out[k]: the next call's carry.
+struct TailHeadStreamArgs {
+    TailHeadArgs base;
+    PooledSrc carry[3];
+    int i2_off;
+    int pool_img;
+};
+int tail_head_stream_launch(const TailHeadStreamArgs& a, const int* taps_host, hipStream_t stream);
 struct TailUpArgs {
     const float* flowcat;        // the three decoders' flows [B][6][g]
     const float* wo;             // out_conv weight [2][6], bias [2] (state_dict layout)

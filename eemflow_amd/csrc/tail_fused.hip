@@ -35,8 +35,9 @@ __device__ __forceinline__ float pooled_load(const PooledSrc& s, const float* ch
 // by blockIdx.y, so everything a block needs from the launch arguments - its stage's source, its tap - is ONE batch of scalar
 // loads issued at its first instruction, and its operand loads are the second and last round trip before the stores (see
 // tail_conv_kernel in tail.hip for what a round trip costs beside other frames' kernels).
-template <int CG, int ROWS>
-__device__ __forceinline__ void rconv_role(const TailHeadArgs& a, int k, int blk, f32x4 (*part)[64]) {
+// STREAM (tail_head_stream_kernel): the pair's first image is image b + i2_off - 1 of the call, or - below 0 - the carried window
+template <int CG, int ROWS, bool STREAM>
+__device__ __forceinline__ void rconv_role(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int k, int blk, f32x4 (*part)[64]) {
     // one block = 16 pixels x 16 couts of one (scale, sample); wave t = filter tap t (see tail_conv_kernel)
     const int lane = threadIdx.x & 63;
     const int t = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -57,13 +58,17 @@ __device__ __forceinline__ void rconv_role(const TailHeadArgs& a, int k, int blk
     const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
     const bool valid = pvalid && yy >= 0 && yy < gh && xx >= 0 && xx < gw;
     const float* wp = rw + (size_t)t * CG * 64 + lane;
-    const float* img = src.base + (size_t)b * src.nstride;                 // events1 half: image b
+    const int i1 = STREAM ? b + i2_off - 1 : b;
+    const bool from_carry = STREAM && i1 < 0;
+    const PooledSrc csrc = STREAM ? carry[k] : src;                         // (values, not references: no copy of the arguments in scratch)
+    const float* img = from_carry ? csrc.base : src.base + (size_t)i1 * src.nstride;   // events1 half: image b
     float av[CG], bv[CG];
 #pragma unroll
     for (int q = 0; q < CG; ++q) {
         const int c = q * 4 + gq;
         av[q] = wp[(size_t)q * 64];
-        bv[q] = (valid && c < cin) ? pooled_load<ROWS>(src, img + (size_t)c * src.cstride, yy, xx) : 0.f;
+        if (from_carry) bv[q] = (valid && c < cin) ? pooled_load<1>(csrc, img + (size_t)c * csrc.cstride, yy, xx) : 0.f;
+        else bv[q] = (valid && c < cin) ? pooled_load<ROWS>(src, img + (size_t)c * src.cstride, yy, xx) : 0.f;
     }
     float bs[4] = {0.f, 0.f, 0.f, 0.f};
     if (t == 0) {
@@ -92,8 +97,8 @@ __device__ __forceinline__ void rconv_role(const TailHeadArgs& a, int k, int blk
 
 // a wave = one (sample, tap, 16-pixel tile): four adjacent lanes share one output and split its channels (see corr_kernel);
 // NC = channels per lane (cin / 4): all 2 * NC * ROWS loads of a lane are issued before the first product
-template <int NC, int ROWS>
-__device__ __forceinline__ void corr_role(const TailHeadArgs& a, int k) {
+template <int NC, int ROWS, bool STREAM>
+__device__ __forceinline__ void corr_role(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int k) {
     const PooledSrc src = a.src[k];
     const int tap = a.tap[blockIdx.y];
     float* cat = a.cat[k];
@@ -113,20 +118,26 @@ __device__ __forceinline__ void corr_role(const TailHeadArgs& a, int k) {
     const int yy = y + tap / 9 - 4, xx = x + tap % 9 - 4;
     float s = 0.f;
     if (live && yy >= 0 && yy < gh && xx >= 0 && xx < gw) {
-        const float* i1 = src.base + (size_t)b * src.nstride;
-        const float* i2 = src.base + (size_t)(batch + b) * src.nstride;
+        // image 2 of pair b: the events2 half of a forward, or the window after image 1 in a stream (image 1 below 0: the carry)
+        const int n2 = STREAM ? b + i2_off : batch + b;
+        const bool from_carry = STREAM && n2 == 0;
+        const PooledSrc csrc = STREAM ? carry[k] : src;
+        const float* i1 = from_carry ? csrc.base : src.base + (size_t)(STREAM ? n2 - 1 : b) * src.nstride;
+        const float* i2 = src.base + (size_t)n2 * src.nstride;
         if (cin == NC * 4) {
             float u[NC], v[NC];
 #pragma unroll
             for (int i = 0; i < NC; ++i) {
-                u[i] = pooled_load<ROWS>(src, i1 + (size_t)(sub + 4 * i) * src.cstride, y, x);
+                u[i] = from_carry ? pooled_load<1>(csrc, i1 + (size_t)(sub + 4 * i) * csrc.cstride, y, x)
+                                  : pooled_load<ROWS>(src, i1 + (size_t)(sub + 4 * i) * src.cstride, y, x);
                 v[i] = pooled_load<ROWS>(src, i2 + (size_t)(sub + 4 * i) * src.cstride, yy, xx);
             }
 #pragma unroll
             for (int i = 0; i < NC; ++i) s = fmaf(u[i], v[i], s);
         } else {
             for (int c = sub; c < cin; c += 4)
-                s = fmaf(pooled_load<0>(src, i1 + (size_t)c * src.cstride, y, x), pooled_load<0>(src, i2 + (size_t)c * src.cstride, yy, xx), s);
+                s = fmaf(from_carry ? pooled_load<1>(csrc, i1 + (size_t)c * csrc.cstride, y, x) : pooled_load<0>(src, i1 + (size_t)c * src.cstride, y, x),
+                         pooled_load<0>(src, i2 + (size_t)c * src.cstride, yy, xx), s);
         }
     }
     s = dpp_add<0xB1>(s);
@@ -134,33 +145,34 @@ __device__ __forceinline__ void corr_role(const TailHeadArgs& a, int k) {
     if (live && sub == 0) cat[((size_t)b * a.cat_ctotal + blockIdx.y) * g + p] = s / (float)cin;
 }
 
-__global__ __launch_bounds__(576) void tail_head_kernel(TailHeadArgs a) {
+template <bool STREAM>
+__device__ __forceinline__ void tail_head_body(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int pool_img) {
     __shared__ f32x4 part[9][64];
     const int role = blockIdx.z;
     const int blk = blockIdx.y * a.grid_x + blockIdx.x;
     if (role < 3) {
         const int rows = a.src[role].rows;                                // 16, 32, 64 input channels (EEMFlow.py:96-98)
-        if (role == 0) { if (rows == 4) rconv_role<4, 4>(a, 0, blk, part); else if (rows == 1) rconv_role<4, 1>(a, 0, blk, part); else rconv_role<4, 0>(a, 0, blk, part); }
-        else if (role == 1) { if (rows == 2) rconv_role<8, 2>(a, 1, blk, part); else if (rows == 1) rconv_role<8, 1>(a, 1, blk, part); else rconv_role<8, 0>(a, 1, blk, part); }
-        else { if (rows == 1) rconv_role<16, 1>(a, 2, blk, part); else rconv_role<16, 0>(a, 2, blk, part); }
+        if (role == 0) { if (rows == 4) rconv_role<4, 4, STREAM>(a, carry, i2_off, 0, blk, part); else if (rows == 1) rconv_role<4, 1, STREAM>(a, carry, i2_off, 0, blk, part); else rconv_role<4, 0, STREAM>(a, carry, i2_off, 0, blk, part); }
+        else if (role == 1) { if (rows == 2) rconv_role<8, 2, STREAM>(a, carry, i2_off, 1, blk, part); else if (rows == 1) rconv_role<8, 1, STREAM>(a, carry, i2_off, 1, blk, part); else rconv_role<8, 0, STREAM>(a, carry, i2_off, 1, blk, part); }
+        else { if (rows == 1) rconv_role<16, 1, STREAM>(a, carry, i2_off, 2, blk, part); else rconv_role<16, 0, STREAM>(a, carry, i2_off, 2, blk, part); }
         return;
     }
     if (role < 6) {
         const int k = role - 3, rows = a.src[k].rows;
-        if (k == 0) { if (rows == 4) corr_role<4, 4>(a, 0); else if (rows == 1) corr_role<4, 1>(a, 0); else corr_role<4, 0>(a, 0); }
-        else if (k == 1) { if (rows == 2) corr_role<8, 2>(a, 1); else if (rows == 1) corr_role<8, 1>(a, 1); else corr_role<8, 0>(a, 1); }
-        else { if (rows == 1) corr_role<16, 1>(a, 2); else corr_role<16, 0>(a, 2); }
+        if (k == 0) { if (rows == 4) corr_role<4, 4, STREAM>(a, carry, i2_off, 0); else if (rows == 1) corr_role<4, 1, STREAM>(a, carry, i2_off, 0); else corr_role<4, 0, STREAM>(a, carry, i2_off, 0); }
+        else if (k == 1) { if (rows == 2) corr_role<8, 2, STREAM>(a, carry, i2_off, 1); else if (rows == 1) corr_role<8, 1, STREAM>(a, carry, i2_off, 1); else corr_role<8, 0, STREAM>(a, carry, i2_off, 1); }
+        else { if (rows == 1) corr_role<16, 1, STREAM>(a, carry, i2_off, 2); else corr_role<16, 0, STREAM>(a, carry, i2_off, 2); }
         return;
     }
-    // pooled maps [2B][C][gh][gw] as a side output
+    // pooled maps [2B][C][gh][gw] as a side output (STREAM: image pool_img alone, [C][gh][gw])
     const int g = a.gh * a.gw;
     int idx = blk * 576 + threadIdx.x;
     for (int k = 0; k < 3; ++k) {
-        const int total = 2 * a.batch * a.c[k] * g;
+        const int total = (STREAM ? 1 : 2 * a.batch) * a.c[k] * g;
         if (idx < total) {
             if (a.pool_out[k] == nullptr) return;
             const int nc = idx / g;
-            const int n = nc / a.c[k], c = nc - n * a.c[k];
+            const int n = STREAM ? pool_img : nc / a.c[k], c = STREAM ? nc : nc - n * a.c[k];
             const int pp = idx - nc * g;
             const int y = pp / a.gw, x = pp - y * a.gw;
             const float* cb = a.src[k].base + (size_t)n * a.src[k].nstride + (size_t)c * a.src[k].cstride;
@@ -171,6 +183,12 @@ __global__ __launch_bounds__(576) void tail_head_kernel(TailHeadArgs a) {
         }
         idx -= total;
     }
+}
+
+__global__ __launch_bounds__(576) void tail_head_kernel(TailHeadArgs a) { tail_head_body<false>(a, nullptr, 0, 0); }
+
+__global__ __launch_bounds__(576) void tail_head_stream_kernel(TailHeadStreamArgs a) {
+    tail_head_body<true>(a.base, a.carry, a.i2_off, a.pool_img);
 }
 
 // ------------------------------------------------------------------------------------------------ conv7 + out_conv + upsample
@@ -260,22 +278,44 @@ __global__ __launch_bounds__(256) void tail_up_kernel(TailUpArgs a) {
 
 }  // namespace
 
-int tail_head_launch(const TailHeadArgs& a0, const int* taps_host, hipStream_t stream) {
-    TailHeadArgs a = a0;
+// the launch box of the head (grid_x, filled in), its taps; pool_imgs: images of the pooled-map role
+static int tail_head_prepare(TailHeadArgs& a, const int* taps_host, int pool_imgs) {
     EEM_REQUIRE(a.ntaps >= 1 && a.ntaps <= TAIL_HEAD_MAX_TAPS, "tail_head_launch: ntaps=%d", a.ntaps);
     for (int i = 0; i < a.ntaps; ++i) a.tap[i] = taps_host[i];
     const int g = a.gh * a.gw;
     const int nblk_rconv = ceil_div(g, 16) * a.batch;                     // per stage
     const int nblk_corr = ceil_div(ceil_div(g, 16) * a.batch, 9);         // per stage and tap: nine (sample, pixel tile) waves per block
     long pool_elems = 0;
-    for (int k = 0; k < 3; ++k) pool_elems += (long)2 * a.batch * a.c[k] * g;
+    for (int k = 0; k < 3; ++k) pool_elems += (long)pool_imgs * a.c[k] * g;
     const int nblk_pool = (int)((pool_elems + 575) / 576);
     // a box of grid_x x ntaps blocks per role: correlation uses (x, tap), the other roles count it row by row
     a.grid_x = nblk_corr;
     if (ceil_div(nblk_rconv, a.ntaps) > a.grid_x) a.grid_x = ceil_div(nblk_rconv, a.ntaps);
     if (ceil_div(nblk_pool, a.ntaps) > a.grid_x) a.grid_x = ceil_div(nblk_pool, a.ntaps);
     EEM_NOTE_GRID(a.grid_x * a.ntaps * 7, 576);
+    return EEM_OK;
+}
+
+int tail_head_launch(const TailHeadArgs& a0, const int* taps_host, hipStream_t stream) {
+    TailHeadArgs a = a0;
+    const int rc = tail_head_prepare(a, taps_host, 2 * a.batch);
+    if (rc != EEM_OK) return rc;
     hipLaunchKernelGGL(tail_head_kernel, dim3(a.grid_x, a.ntaps, 7), dim3(576), 0, stream, a);
+    EEM_HIP_CHECK(hipGetLastError());
+    return EEM_OK;
+}
+
+int tail_head_stream_launch(const TailHeadStreamArgs& a0, const int* taps_host, hipStream_t stream) {
+    TailHeadStreamArgs a = a0;
+    EEM_REQUIRE(a.i2_off == 0 || a.i2_off == 1, "tail_head_stream_launch: i2_off=%d", a.i2_off);
+    EEM_REQUIRE(a.pool_img >= 0 && a.base.batch >= 0, "tail_head_stream_launch: pool_img=%d batch=%d", a.pool_img, a.base.batch);
+    for (int k = 0; k < 3; ++k) {
+        EEM_REQUIRE(a.base.pool_out[k] != nullptr, "tail_head_stream_launch: stage %d has no carry output", k);
+        EEM_REQUIRE(a.i2_off == 1 || (a.carry[k].base != nullptr && a.carry[k].rows == 1), "tail_head_stream_launch: stage %d: carried maps missing", k);
+    }
+    const int rc = tail_head_prepare(a.base, taps_host, 1);
+    if (rc != EEM_OK) return rc;
+    hipLaunchKernelGGL(tail_head_stream_kernel, dim3(a.base.grid_x, a.base.ntaps, 7), dim3(576), 0, stream, a);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }

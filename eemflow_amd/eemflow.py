@@ -138,9 +138,13 @@ class EEMFlow(nn.Module):
         self._layout_loaded = False
         self.use_graph = True
         self.frames_in_flight = 1       # >= 3: this module is one of several replicas kept busy on separate streams (throughput over latency)
+        self._stream_prev = None        # forward_stream: the caller's tensor of the window the context carries (events1 of the next pair)
 
     # ------------------------------------------------------------------ reference interface
     def change_imagesize(self, img_size):
+        old = getattr(self, "image_size", None)
+        if old is not None and tuple(int(v) for v in old) != tuple(int(v) for v in img_size):
+            self.reset_stream()                                  # a carried window of another size cannot start the next pair
         self.image_size = img_size
         self.image_padder = InputPadder(img_size, mode='chairs', eval_pad_rate=64)
 
@@ -236,6 +240,71 @@ class EEMFlow(nn.Module):
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().eemflow_forward_many(ctx, n, p1, p2, po, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev)))
         return [((frames[i][0], frames[i][1]), [flows[i]]) for i in range(n)]
+
+    MAX_STREAM = 16                     # EEM_STREAM_MAX_VOLUMES of include/eemflow_hip.h
+
+    def forward_stream(self, volumes, deferred_norm=False):
+        """Flow along a stream of CONSECUTIVE event windows, each window encoded once (the MVSEC evaluation walks a sequence this way:
+        sample i is windows i and i + 1, loader/MVSEC.py:115-116).  `volumes` are 1..16 [1, C, H, W] tensors in time order, on one
+        device with one shape.  Returns one `((events1, events2), [flow])` per pair of neighbouring windows - flow [1, 2, H, W] (the
+        `forward` rule for the output size), bitwise what `forward_many` gives for those pairs.  The last window is carried to the next
+        call, whose first pair starts at it: a call after a carried window returns len(volumes) pairs (events1 of the first is the
+        previous call's last tensor), otherwise len(volumes) - 1.  `reset_stream()` drops the carried window; `change_imagesize` to a
+        new size does too.  After a weight change (optimizer step, load_state_dict) the next call raises until `reset_stream()`.
+        Inference only (no autograd graph is recorded).  deferred_norm: as in `forward_many`."""
+        vols = list(volumes)
+        if not 1 <= len(vols) <= self.MAX_STREAM:
+            raise ValueError(f"forward_stream: 1..{self.MAX_STREAM} volumes per call, got {len(vols)}")
+        if not hasattr(self, "image_padder"):
+            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
+        keep, shape = [], None
+        for v in vols:
+            if not v.is_cuda:
+                raise _lib.EEMFlowHipError("EEMFlow.forward_stream: inputs must be CUDA (ROCm) tensors - this implementation has no CPU path")
+            v = v.contiguous().float()
+            if v.dim() != 4 or v.shape[0] != 1 or v.shape[1] != self.n_first_channels:
+                raise ValueError(f"forward_stream: every volume is a (1,{self.n_first_channels},H,W) tensor, got {tuple(v.shape)}")
+            if shape is not None and (v.shape != shape or v.device != keep[0].device):
+                raise ValueError("forward_stream: all volumes of a call share one shape and one device")
+            if deferred_norm:
+                from .voxelizer import has_norm_record
+                if not has_norm_record(v):
+                    raise ValueError("forward_stream(deferred_norm=True): every volume needs its four-float record behind it "
+                                     "(voxelize with normalize='deferred')")
+            shape = v.shape
+            keep.append(v)
+        dev = keep[0].device
+        h, w = int(shape[2]), int(shape[3])
+        out_size = (16, 16) if (self.training and self.out_mesh_size) else (h, w)
+        L = _lib.lib()
+        ctx = self._context(dev)
+        pending = ctypes.c_int()
+        _lib.check(L.eemflow_stream_pending(ctx, ctypes.byref(pending)))
+        carried = self._stream_prev if (pending.value and self._stream_prev is not None) else None
+        if carried is None and pending.value:
+            _lib.check(L.eemflow_stream_reset(ctx))               # (no tensor to name as events1: start over)
+        _lib.check(L.eemflow_set_deferred_input_norm(ctx, 1 if deferred_norm else 0))
+        n = len(keep)
+        nflow = n if carried is not None else n - 1
+        flows = [torch.empty(1, 2, out_size[0], out_size[1], device=dev, dtype=torch.float32) for _ in range(nflow)]
+        pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
+        po = (ctypes.c_void_p * max(nflow, 1))(*[f.data_ptr() for f in flows])
+        with torch.cuda.device(dev):
+            rc = L.eemflow_forward_stream(ctx, n, pv, po, nflow, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev))
+        if rc != 0:
+            msg = L.eemflow_last_error().decode("utf-8", "replace")
+            if "eemflow_stream_reset" in msg:
+                raise _lib.EEMFlowHipError(f"EEMFlow.forward_stream: {msg} - call reset_stream() on the module")
+            raise _lib.EEMFlowHipError(msg)
+        older = ([carried] if carried is not None else []) + vols[:-1]
+        self._stream_prev = vols[-1]
+        return [((older[i], vols[i + 1 - (1 if carried is not None else 0)]), [flows[i]]) for i in range(nflow)]
+
+    def reset_stream(self):
+        """Drop the window `forward_stream` carries: its next call starts a new stream (len(volumes) - 1 pairs)."""
+        self._stream_prev = None
+        if getattr(self, "_ctx", None) is not None:
+            _lib.check(_lib.lib().eemflow_stream_reset(self._ctx))
 
     # ------------------------------------------------------------------ HIP context plumbing
     def _flat_weights(self, device=None):

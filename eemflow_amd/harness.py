@@ -77,6 +77,34 @@ def _device_of(model):
     return next(model.parameters()).device
 
 
+def stream_plan(n_samples, n):
+    """The calls of a stride-1 walk over a sequence of n_samples samples (n_samples + 1 consecutive windows) by EEMFlow.forward_stream, at
+    most n windows per call: [(first_window, windows, first_sample, flows)].  The first call carries nothing in (its windows - 1 flows); every
+    later one starts at the window the call before carried (as many flows as windows).  Every window is in one call, every sample one flow."""
+    n = max(2, min(int(n), 16))
+    plan, w = [], 0
+    while n_samples > 0 and w <= n_samples:
+        cnt = min(n, n_samples + 1 - w)
+        plan.append((w, cnt, max(w - 1, 0), cnt if w > 0 else cnt - 1))
+        w += cnt
+    return plan
+
+
+def stream_chunks(dataset, model, n, dev):
+    """Walk the dataset's current sequence window by window: each window read and voxelized once (dataset.get_windows), each call's
+    windows through ONE model.forward_stream, the stream reset at the start.  Yields (sample indices, their targets, their flows) per call."""
+    model.reset_stream()
+    carry_target = None
+    for w0, cnt, s0, nflow in stream_plan(len(dataset), n):
+        vols, targets = dataset.get_windows(w0, cnt)
+        outs = model.forward_stream([v.to(dev)[None].float() for v in vols])
+        pair_targets = ([carry_target] if w0 > 0 else []) + list(targets[:cnt - 1])
+        carry_target = targets[cnt - 1]
+        if len(outs) != nflow or len(pair_targets) != nflow:
+            raise RuntimeError(f"stream_chunks: windows {w0}..{w0 + cnt - 1} gave {len(outs)} flows for {nflow} samples")
+        yield list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]
+
+
 class TestRaftEvents:
     """Evaluation loop of test_mvsec.py:538-671 on a dataset object (HREMEventFlow-like: change_test_sequence, __len__,
     __getitem__ -> sample dict)."""
@@ -94,19 +122,33 @@ class TestRaftEvents:
         _, preds = model(events1=e1, events2=e2)
         return preds[-1]
 
-    def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1):
+    def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0):
         """The evaluation loop of test_mvsec.py:580-597.  It reads the LAST prediction of every sample only (run_network, :1455): a
-        model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call."""
+        model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call.
+        stream = n > 0 (stride 1, a model with forward_stream - EEMFlow - and a dataset of consecutive windows with get_windows -
+        MvsecEventFlow / _dt4): each sequence is walked window by window, every window read and voxelized once, up to n per call
+        (stream_plan), each call's windows through ONE model.forward_stream - sample i's flow is windows i and i + 1, the encoder runs
+        once per window instead of twice.  Same per-sample lines in the same order; frames_in_flight, loader_threads and coalesce do
+        not apply."""
+        if stream:
+            if stride != 1:
+                raise ValueError(f"stream= walks consecutive windows: it needs stride == 1 (got stride={stride}, whose samples share no window)")
+            if not getattr(self.dataset, "consecutive_windows", False) or not hasattr(self.dataset, "get_windows"):
+                raise ValueError(f"stream= needs a dataset whose sample i is windows i and i + 1 (consecutive_windows, get_windows: MvsecEventFlow, "
+                                 f"MvsecEventFlow_dt4); {type(self.dataset).__name__}'s samples are separate event files (HREM: events1.npz / "
+                                 f"events2.npz) that share no window")
+            if not hasattr(model, "forward_stream"):
+                raise ValueError("stream= needs a model with forward_stream (EEMFlow)")
         had = getattr(model, "final_only", None)
         if had is not None:
             model.final_only = True
         try:
-            return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce)
+            return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce, stream)
         finally:
             if had is not None:
                 model.final_only = had
 
-    def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1):
+    def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0):
         """coalesce > 1 (a model with forward_many - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset with get_samples): that many samples are read, voxelized by
         ONE voxelizer launch sequence and handed to ONE model.forward_many call - n independent batch-1 samples riding a batch-n chain of
         launches, every sample in its own tensors; raw volumes with a normalisation record (HREMEventFlow(deferred_norm=True)) are
@@ -128,6 +170,8 @@ class TestRaftEvents:
         mean_aee, mean_out, aee_list, out_list = 0., 0., [], []
         nfl = max(1, int(frames_in_flight))
         co = max(1, int(coalesce))
+        if stream:
+            nfl, co, loader_threads = 1, 0, 0                    # (co = 0: neither the coalesced nor the one-sample loop below runs)
         if co > 1:
             if not (hasattr(model, "forward_many") and hasattr(self.dataset, "get_samples")):
                 raise ValueError("coalesce > 1 needs a model with forward_many (EEMFlow, EEMFlow_cdc, ERAFT) and a dataset with get_samples (HREMEventFlow)")
@@ -174,6 +218,15 @@ class TestRaftEvents:
                     for idx in itertools.islice(ahead, 2 * loader_threads):
                         futures.append(pool.submit(load, idx))
                 count = 0
+                for chunk, targets, f_ests in (stream_chunks(self.dataset, model, stream, dev) if stream else ()):
+                    f_gts = [t_['flow'].to(dev)[None].float() for t_ in targets]
+                    evs_ = [t_['event_valid'].to(dev).sum(0) for t_ in targets] if (sparse and all('event_valid' in t_ for t_ in targets)) else None
+                    all_sums = flow_error_sums_many(f_gts, f_ests, evs_, is_car=self.is_car,
+                                                    evaluation_type="sparse" if evs_ is not None else "dense")
+                    for i_, idx in enumerate(chunk):
+                        pending.append((idx, 0, all_sums[i_], (targets[i_], f_ests[i_], f_gts[i_], evs_[i_] if evs_ is not None else None)))
+                    while pending:
+                        retire()
                 for c0 in (range(0, len(indices), co) if co > 1 else ()):
                     chunk = indices[c0:c0 + co]
                     k = count % nfl
@@ -195,7 +248,7 @@ class TestRaftEvents:
                             pending.append((idx, k, all_sums[i_], (sample, f_ests[i_], f_gts[i_], evs_[i_] if evs_ is not None else None)))
                     while len(pending) >= nfl * co:
                         retire()
-                for idx in (indices if co == 1 else ()):
+                for idx in (indices if co == 1 else ()):      # (co == 0: the stream walk above)
                     k = count % nfl
                     count += 1
                     with torch.cuda.stream(streams[k]):

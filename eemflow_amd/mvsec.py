@@ -87,6 +87,9 @@ class MvsecEventFlow(torch.utils.data.Dataset):
     image_height = 260
     frames_per_volume = 1
     flow_dir = 'flowgt_dt1'
+    # sample i is windows i and i + 1 of one sequence (MVSEC.py:115-116, :247-251): a stride-1 walk can encode every window once
+    # (harness.TestRaftEvents.test_multi_sequence(stream=n), EEMFlow.forward_stream)
+    consecutive_windows = True
 
     def __init__(self, args, train=True, root=None, device=None, to_cpu=False, augmentor=None, events_reader=None,
                  valid_time_index=None):
@@ -162,6 +165,39 @@ class MvsecEventFlow(torch.utils.data.Dataset):
             out['event_valid'] = torch.from_numpy(event_mask(old.get_sequence_only(), self.image_height,
                                                              self.image_width)).unsqueeze(dim=0)
         return out
+
+    def _window_paths(self, j):
+        """The event files of window j: event_volume_old of sample j, event_volume_new of sample j - 1."""
+        n = len(self.event_list)
+        return [self.event_list[(j + i) % n] for i in range(self.frames_per_volume)]
+
+    def get_windows(self, first, count):
+        """Windows first .. first + count - 1 of the sequence, each read and voxelized once (ONE voxelizer launch sequence for all), and
+        the evaluation targets of the samples that start at them: returns (volumes, targets) - volumes[i] the [C, 256, 256] volume of window
+        first + i, cropped as __getitem__ crops it; targets[i] the dict of sample first + i ('idx', 'flow', 'valid', 'event_valid', the
+        same values as __getitem__ gives), None past the last sample (the last window only ends a sample).  Evaluation datasets only."""
+        if self.type != 'val':
+            raise ValueError("get_windows: evaluation datasets only (train=False); training samples are augmented pair by pair")
+        if first < 0 or count < 1 or first + count > len(self) + 1:
+            raise ValueError(f"get_windows: windows {first}..{first + count - 1} of a sequence of {len(self)} samples ({len(self) + 1} windows)")
+        seqs = [self._sequence(self._window_paths(j)) for j in range(first, first + count)]
+        vols = self.voxel.many(seqs)
+        crop = (256, 256)                                                                       # MVSEC.py:52,193-197
+        volumes, targets = [], []
+        for i, j in enumerate(range(first, first + count)):
+            vol = vols[i].cpu() if self.to_cpu else vols[i]
+            volumes.append(center_crop(vol, crop))
+            if j >= len(self):
+                targets.append(None)
+                continue
+            flow = np.load(self.flow_list[j])
+            if flow.shape[-1] == 2:
+                flow = flow.transpose(2, 0, 1)
+            fl = center_crop(torch.from_numpy(np.ascontiguousarray(flow)), crop)
+            ev = torch.from_numpy(event_mask(seqs[i].get_sequence_only(), self.image_height, self.image_width)).unsqueeze(dim=0)
+            targets.append({'idx': self.names[j], 'flow': fl, 'valid': (fl[0].abs() < 1000) & (fl[1].abs() < 1000),
+                            'event_valid': center_crop(ev, crop)})
+        return volumes, targets
 
     def __getitem__(self, idx):
         sample = self.get_sample(idx % len(self))

@@ -110,6 +110,33 @@ int eemflow_forward(eemflow_ctx* ctx, const float* events1, const float* events2
 int eemflow_forward_many(eemflow_ctx* ctx, int nframes, const float* const* events1, const float* const* events2,
                          float* const* flow_out, int in_h, int in_w, int out_h, int out_w, void* stream);
 
+/* Volumes per eemflow_forward_stream call: the per-frame pointer table of eemflow_forward_many holds 16 frames. */
+#define EEM_STREAM_MAX_VOLUMES 16
+
+/* Flow along a stream of CONSECUTIVE event windows, each window encoded once.  volumes[j] (j < nvol, 1..EEM_STREAM_MAX_VOLUMES) are
+ * [1][C][in_h][in_w] windows in time order and flow_out[p] [1][2][out_h][out_w] tensors (HOST arrays of 16-byte aligned device
+ * pointers, as in eemflow_forward_many).  Flow p is the flow from the older window of pair p to the newer one: with a window carried
+ * from the previous call the pairs are (carried, v0), (v0, v1), ... and nflow == nvol; with none, (v0, v1), ... and nflow == nvol - 1
+ * (flow_out may then be NULL for nvol == 1).  Any other nflow is an error.  Afterwards the context carries v[nvol-1]: its three pooled
+ * feature maps (16 + 32 + 64 channels on the 1/64 grid), in context-owned memory that forward / forward_many / training calls leave
+ * alone.  Flow p is bitwise eemflow_forward_many on the pairs in the same encoder form (EEM_WINO4_LAYERS / f4 policy: the call
+ * counts as nvol / 2 samples).  A carried window made with other weights (eemflow_load_weights, eemflow_update_weights, an
+ * optimizer step) or at another input size is refused with an error: call eemflow_stream_reset.  eemflow_set_deferred_input_norm
+ * applies as in eemflow_forward_many.  One stream per context; eemflow_get_stage has nothing to read after a stream call.
+ * Replaces: the evaluation loop over consecutive samples of a sequence (test_mvsec.py:580-597 at stride 1, samples built by
+ * loader/MVSEC.py:115-116 from windows i and i + 1), which runs EEMFlow.forward's encoder (model/EEMFlow/EEMFlow.py:135-154) on
+ * every window twice. */
+int eemflow_forward_stream(eemflow_ctx* ctx, int nvol, const float* const* volumes, float* const* flow_out, int nflow, int in_h,
+                           int in_w, int out_h, int out_w, void* stream);
+
+/* Drop the carried window: the next eemflow_forward_stream call starts a new stream.
+ * Replaces: the start of a sequence in test_mvsec.py:580-597 (dataset.change_test_sequence). */
+int eemflow_stream_reset(eemflow_ctx* ctx);
+
+/* *out = 1 when a window is carried for the next eemflow_forward_stream call, else 0.
+ * Replaces: nothing in the reference (it has no stream state); the query behind EEMFlow.forward_stream's bookkeeping. */
+int eemflow_stream_pending(eemflow_ctx* ctx, int* out);
+
 /* Per-kernel timing of the forward schedule: the schedule runs `reps` + 1 times as the chain it is (eagerly, the first pass warms and
  * is not counted) with a pair of HIP events around EVERY launch, recorded on `stream` (the stream the kernels run on); `ms` is the
  * average per launch - each kernel measured behind its producer, as it runs in a forward.  `flops` / `bytes` are the ALGORITHMIC
