@@ -1,0 +1,211 @@
+"""fp64 STAGE CHECKER for the EEMFlow inference path.  TEST INFRASTRUCTURE ONLY (never imported by eemflow_amd/).
+
+Every stage the library exposes (eemflow_get_stage) is compared with an fp64 evaluation of THAT ONE stage on the GPU's own input
+to it, and the error is measured in units of fp32 rounding of the stage's own sums:
+
+    z = (got - ref) / (u * mag),   u = 2^-24,   mag = the same sum over absolute values (sum |w x| + |b| for a convolution)
+
+so a correct fp32 kernel gives |z| of a few units whatever the layer's scale, and an error confined to one tile is seen at the
+tile instead of being averaged away by the 32 x 32 pooling in front of the flow.  `check` asserts four statistics of z against a
+form's `Limits`: max |z|, rms(z), |mean(z)| and the least-squares slope of (got - ref) against ref in units of u (a wrong divisor
+or an off-by-rounding transform constant is a scale error: small per element, large in the slope).
+
+The decoders' inner layers are not exposed: `check_decoder` holds the GPU's error on a decoder to a multiple of what the fp32 CPU
+oracle's error is on the same input (both against fp64).
+"""
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import eemflow_oracle as O
+
+U = 2.0 ** -24
+LEAKY = float(np.float32(0.1))          # LeakyReLU(0.1) of an fp32 model: the slope is the float nearest 0.1
+MAG_FLOOR = 1e-7                        # mag is floored at this fraction of its largest value (an all-zero window is not 0 / 0)
+
+
+@dataclass(frozen=True)
+class Limits:
+    max_z: float        # max |z|
+    rms_z: float        # sqrt(mean z^2)
+    mean_z: float       # |mean z|
+    slope_u: float      # |slope of (got - ref) on ref| / u
+
+
+# One limit set per form family, calibrated on an MI355X (the measured worst cases are in tests/test_gpu_stage_fp64.py's docstring;
+# the path is bitwise repeatable, so they are deterministic for the committed seeds): max|z| 2x and rms(z) 1.5x the worst value seen
+# across all cases, |mean z| and the slope 2x, each rounded down to two digits (up for mean and slope).
+LIMITS = {
+    "enc1": Limits(9.9, 0.54, 0.15, 0.72),      # pconv1_1: conv_enc1.hip, the generic kernel, the fused and deferred forms
+    "direct": Limits(20.0, 0.98, 0.22, 1.9),    # fp32 MFMA direct convolutions (stride 2, EEM_WINO=0, rconv)
+    "bx3": Limits(14.0, 0.68, 0.15, 2.4),       # three-piece bf16 products (conv_bx3.hip)
+    "wino2": Limits(8.9, 0.47, 0.04, 0.56),     # Winograd F(2x2,3x3)
+    "wino4": Limits(430.0, 3.1, 0.18, 2.3),     # Winograd F(4x4,3x3): transform entries up to 8, the worst at C = 16 (K = 144)
+    "pool": Limits(7.0, 1.2, 0.28, 0.5),        # average pooling (fused epilogue partial sums or the pooling kernel)
+    "corr": Limits(7.6, 1.1, 0.07, 3.8),        # 53-tap local correlation
+    "out_conv": Limits(4.9, 1.1, 0.34, 1.4),    # the 1x1 6 -> 2 output conv
+    "upsample": Limits(99.0, 1.0, 0.27, 2.8),   # bilinear, align_corners=False
+}
+KAPPA_DEC = 6.4                                  # decoders: GPU error <= KAPPA_DEC x the fp32 CPU oracle's (rms and max); 2x the worst
+
+LOG = []            # every check's statistics, in order: {"name", "form", "max_z", "rms_z", "mean_z", "slope_u", ...}
+
+
+def _d(t):
+    return torch.as_tensor(t).detach().cpu().double()
+
+
+def leaky(x):
+    return torch.where(x >= 0, x, LEAKY * x)
+
+
+# ----------------------------------------------------------------------------------------------------------- stage references
+def conv_ref(x, w, b, stride=1, groups=1, act=True, padding=1):
+    """`convrelu` (EEMFlow.py:26-30; zero padding 1) in fp64: (ref, mag) with mag = conv(|x|, |w|) + |b|."""
+    x, w = _d(x), _d(w)
+    b = _d(b) if b is not None else None
+    ref = F.conv2d(x, w, b, stride=stride, padding=padding, groups=groups)
+    mag = F.conv2d(x.abs(), w.abs(), b.abs() if b is not None else None, stride=stride, padding=padding, groups=groups)
+    return (leaky(ref) if act else ref), mag
+
+
+def normalise_ref(v, record):
+    """loader_utils.py:527-535 as the deferred form applies it: (v - mean) / sd on the non-zero voxels, from the record
+    {mean, sd, scale, any} the voxelizer wrote (scale 0: mean subtracted only; any 0: nothing to do) - in fp64."""
+    v = _d(v)
+    mean, sd, scale, anyv = (float(r) for r in _d(record))
+    if anyv == 0:
+        return v
+    out = v - mean
+    if scale != 0:
+        out = out / sd
+    return torch.where(v != 0, out, v)
+
+
+def first_layer_ref(events, pad, w, b, records=None):
+    """pconv1_1 on the replicate-padded input (image_utils.py:129-140, EEMFlow.py:75,135): events [N, 5, H, W] as the caller
+    handed them; `records` (one per image) selects the deferred-normalisation form, which normalises before the padding."""
+    x = _d(events)
+    if records is not None:
+        x = torch.stack([normalise_ref(x[i], records[i]) for i in range(x.shape[0])])
+    return conv_ref(O.replicate_pad(x, pad), w, b, stride=2)
+
+
+def avg_pool_ref(f, k):
+    f = _d(f)
+    return F.avg_pool2d(f, k, k), F.avg_pool2d(f.abs(), k, k)
+
+
+def corr53_ref(x, y):
+    """(1/C) sum_c x y over the 53 taps, zero outside the image; mag = (1/C) sum_c |x y|."""
+    x, y = _d(x), _d(y)
+    return O.local_corr53(x, y), O.local_corr53(x.abs(), y.abs())
+
+
+def out_conv_ref(x, w, b):
+    return conv_ref(x, w, b, act=False, padding=0)
+
+
+def upsample_ref(coarse, size):
+    """Bilinear, align_corners=False.  mag = interpolated |coarse| + the term of the fp32 source coordinate: an error of u times a
+    coordinate (up to the map's height / width) moves the sample along the map's slope between the two rows / columns it reads."""
+    c = _d(coarse)
+    h, w = c.shape[-2:]
+    gy, gx = torch.zeros_like(c), torch.zeros_like(c)
+    gy[..., :-1, :] = (c[..., 1:, :] - c[..., :-1, :]).abs()
+    gx[..., :, :-1] = (c[..., :, 1:] - c[..., :, :-1]).abs()
+    mag = O.upsample_flow(c.abs(), size) + h * O.upsample_flow(gy, size) + w * O.upsample_flow(gx, size)
+    return O.upsample_flow(c, size), mag
+
+
+# ----------------------------------------------------------------------------------------------------------------- the checks
+class StageError(AssertionError):
+    pass
+
+
+def stats(got, ref, mag):
+    """The four statistics of z = (got - ref) / (u mag) and the worst element's flat index."""
+    g = _d(got)
+    if g.shape != ref.shape:
+        raise StageError(f"shape {tuple(g.shape)} against the reference's {tuple(ref.shape)}")
+    d = g - ref
+    floor = max(float(mag.max()) * MAG_FLOOR, 1e-300) if mag.numel() else 1.0
+    z = d / (U * mag.clamp_min(floor))
+    zf = z.reshape(-1)
+    bad = ~torch.isfinite(zf)
+    worst = int(torch.nonzero(bad)[0]) if bool(bad.any()) else int(zf.abs().argmax())
+    rr = float((ref * ref).sum())
+    return {"max_z": float(zf.abs().max()) if not bool(bad.any()) else float("inf"),
+            "rms_z": float(zf.pow(2).mean().sqrt()),
+            "mean_z": float(zf.mean()),
+            "slope_u": float((d * ref).sum()) / rr / U if rr > 0 else 0.0,
+            "worst": worst, "z": z, "n": zf.numel()}
+
+
+def where(shape, flat, tile=None):
+    """(image, channel, y, x) of a flat index into an NCHW tensor, with its tile in a (rows, cols) tiling."""
+    idx = np.unravel_index(flat, tuple(shape))
+    s = "(image %d, channel %d, y %d, x %d)" % tuple(int(i) for i in idx) if len(shape) == 4 else str(tuple(int(i) for i in idx))
+    if tile is not None and len(shape) == 4:
+        th, tw = tile
+        y, x = int(idx[2]), int(idx[3])
+        s += f", tile (row {y // th}, col {x // tw}) of {th}x{tw} at offset ({y % th}, {x % tw}); {shape[2]}x{shape[3]} map = " \
+             f"{-(-shape[2] // th)}x{-(-shape[3] // tw)} tiles"
+    return s
+
+
+def check(name, got, ref, mag, limits, tile=None, form=None):
+    """Assert the four statistics of z against `limits` (a Limits or a key of LIMITS); on failure name the worst element."""
+    lim = LIMITS[limits] if isinstance(limits, str) else limits
+    st = stats(got, ref, mag)
+    rec = {"name": name, "form": form or (limits if isinstance(limits, str) else "?"),
+           **{k: st[k] for k in ("max_z", "rms_z", "mean_z", "slope_u", "n")}}
+    LOG.append(rec)
+    fails = []
+    if not st["max_z"] <= lim.max_z:
+        fails.append(f"max|z| {st['max_z']:.3g} > {lim.max_z}")
+    if not st["rms_z"] <= lim.rms_z:
+        fails.append(f"rms(z) {st['rms_z']:.3g} > {lim.rms_z}")
+    if not abs(st["mean_z"]) <= lim.mean_z:
+        fails.append(f"|mean(z)| {abs(st['mean_z']):.3g} > {lim.mean_z}")
+    if not abs(st["slope_u"]) <= lim.slope_u:
+        fails.append(f"|slope| {abs(st['slope_u']):.3g} u > {lim.slope_u} u")
+    if fails:
+        w = st["worst"]
+        g, r, m = _d(got).reshape(-1)[w], ref.reshape(-1)[w], mag.reshape(-1)[w]
+        raise StageError(f"{name} [{rec['form']}]: " + "; ".join(fails) +
+                         f".  Worst element {where(ref.shape, w, tile)}: z {float(st['z'].reshape(-1)[w]):.4g}, got {float(g):.9g}, "
+                         f"ref {float(r):.9g}, mag {float(m):.4g}  (max|z| {st['max_z']:.3g}, rms {st['rms_z']:.3g}, "
+                         f"mean {st['mean_z']:.3g}, slope {st['slope_u']:.3g} u over {st['n']} values)")
+    return rec
+
+
+def decoder_refs(sd, k, x, groups=5):
+    """Decoder k (EEMFlow.py:59-69) on the decoders' input x, in fp64 and in fp32 (the CPU oracle)."""
+    pre = f"decoder_{k}."
+    w = {key: v for key, v in sd.items() if key.startswith(pre)}
+    ref64 = O.decoder({key: _d(v) for key, v in w.items()}, pre, _d(x), groups)
+    ref32 = O.decoder({key: torch.as_tensor(v).detach().cpu().float() for key, v in w.items()}, pre,
+                      torch.as_tensor(x).detach().cpu().float(), groups)
+    return ref64, ref32
+
+
+def check_decoder(name, got, ref64, ref32, kappa=None):
+    """rms and max of the GPU's error <= kappa x those of the fp32 CPU oracle's error on the same input, plus an absolute floor
+    of one unit of fp32 rounding at the largest output."""
+    kappa = KAPPA_DEC if kappa is None else kappa
+    eg = _d(got) - ref64
+    ec = _d(ref32) - ref64
+    floor = U * float(ref64.abs().max())
+    rg, rc = float(eg.pow(2).mean().sqrt()), float(ec.pow(2).mean().sqrt())
+    mg, mc = float(eg.abs().max()), float(ec.abs().max())
+    rec = {"name": name, "form": "decoder", "rms_ratio": rg / max(rc, 1e-300), "max_ratio": mg / max(mc, 1e-300),
+           "rms_gpu": rg, "rms_cpu": rc, "max_gpu": mg, "max_cpu": mc, "n": eg.numel()}
+    LOG.append(rec)
+    if not (rg <= kappa * rc + floor and mg <= kappa * mc + floor):
+        w = int(eg.abs().reshape(-1).argmax())
+        raise StageError(f"{name} [decoder]: GPU error rms {rg:.3g} / max {mg:.3g} against the fp32 CPU oracle's {rc:.3g} / {mc:.3g} "
+                         f"(kappa {kappa}, floor {floor:.3g}); worst element {where(ref64.shape, w)}")
+    return rec
