@@ -101,6 +101,14 @@ _SIGNATURES = {
                                          ctypes.c_int, ctypes.c_int, _c_float_p, ctypes.c_void_p]),
     "eraft_convex_upsample": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              _c_float_p, ctypes.c_void_p]),
+    "eraft_forward_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                            ctypes.c_void_p]),
+    "eraft_stream_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "eraft_stream_pending": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    "eraft_forward_interpolate_scratch": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "eraft_forward_interpolate": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_size_t, ctypes.c_void_p]),
     "eemplus_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "eemplus_destroy": (None, [ctypes.c_void_p]),
     "eemplus_load_weights": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int]),

@@ -88,6 +88,15 @@ struct eraft_ctx {
     bool final_only = false;       // eraft_set_final_only: only the last iteration's prediction leaves the forward
     Buf f2l[3];                    // avg-pooled fmap2, levels 1..3 (alt_corr)
     bool stages_valid = false;
+    int fmap_imgs = 0;             // images in `fmap` after the last forward (2B; nflow + 1 after a stream call)
+    unsigned long wver = 0;        // bumped by every eraft_load_weights
+    // eraft_forward_stream: the carry - the last window's padded volume and feature map, the last pair's flow_low - in memory of its
+    // own (forward / forward_many / the operator-level calls reuse the workspace, never these), and the last call's per-pair flow_low
+    Buf carry_pad, carry_fmap, carry_flow, sflow, finit, fi_ws;
+    bool carry_on = false, carry_has_flow = false;
+    int carry_h = 0, carry_w = 0, carry_padv[4] = {0, 0, 0, 0};
+    unsigned long carry_wver = 0;
+    int stream_pairs = 0;          // > 0: the last forward was a stream call of that many pairs ("flow_low" reads sflow)
 };
 
 namespace {
@@ -405,7 +414,8 @@ int build_feature_pyramid(eraft_ctx* c, const float* f2, int batch, int ch, int 
 // flow_dst (optional): the lookup launch also writes flow = coords - flow_c0 there (resident-volume form; the on-the-fly form
 // keeps the separate launch)
 int run_lookup(eraft_ctx* c, const float* coords, float* out, int out_ctotal, int batch, int h, int w, hipStream_t st,
-               const float* flow_c0 = nullptr, float* flow_dst = nullptr, int flow_ctotal = 0, int flow_coff = 0, hipEvent_t done_ev = nullptr) {
+               const float* flow_c0 = nullptr, float* flow_dst = nullptr, int flow_ctotal = 0, int flow_coff = 0, hipEvent_t done_ev = nullptr,
+               size_t pair = 0) {
     if (c->alt_corr) {
         if (flow_dst) {
             const int rcf = er_flow_launch(flow_c0, coords, flow_dst, flow_ctotal, flow_coff, batch, h * w, st);
@@ -424,7 +434,7 @@ int run_lookup(eraft_ctx* c, const float* coords, float* out, int out_ctotal, in
         return rca;
     }
     LookupArgs la;
-    for (int l = 0; l < 4; ++l) { la.pyr[l] = c->pyr[l].p; la.ph[l] = c->ph[l]; la.pw[l] = c->pw[l]; }
+    for (int l = 0; l < 4; ++l) { la.pyr[l] = c->pyr[l].p + pair * h * w * c->ph[l] * c->pw[l]; la.ph[l] = c->ph[l]; la.pw[l] = c->pw[l]; }
     la.coords = coords; la.out = out; la.batch = batch; la.h = h; la.w = w; la.out_ctotal = out_ctotal;
     la.coords0 = flow_c0; la.flow_dst = flow_dst; la.flow_ctotal = flow_ctotal; la.flow_coff = flow_coff;
     return er_lookup_launch(la, st, done_ev);
@@ -455,7 +465,8 @@ extern "C" void eraft_destroy(eraft_ctx* c) {
                   &c->pyr[0], &c->pyr[1], &c->pyr[2], &c->pyr[3], &c->c0, &c->c1, &c->c1b, &c->corr, &c->cor1, &c->corflo, &c->flo1,
                   &c->motion, &c->z, &c->rh, &c->fhid, &c->delta, &c->mhid, &c->mask, &c->st_corr0, &c->st_net1, &c->st_mask1,
                   &c->st_delta1, &c->zeros, &c->many_out, &c->f2l[0], &c->f2l[1], &c->f2l[2], &c->czr[0], &c->czr[1], &c->cq[0], &c->cq[1],
-                  &c->s2[0], &c->s2[1], &c->s2[2], &c->s2[3], &c->s2[4]};
+                  &c->s2[0], &c->s2[1], &c->s2[2], &c->s2[3], &c->s2[4], &c->carry_pad, &c->carry_fmap, &c->carry_flow, &c->sflow,
+                  &c->finit, &c->fi_ws};
     for (Buf* b : all) if (b->p) (void)hipFree(b->p);
     if (c->nstat) (void)hipFree(c->nstat);
     if (c->side) (void)hipStreamDestroy(c->side);
@@ -575,28 +586,45 @@ extern "C" int eraft_load_weights(eraft_ctx* c, const float* flat, size_t nfloat
     }
     c->cin0 = n_first_channels;
     c->loaded = true;
+    ++c->wver;
     return EEM_OK;
 }
 
+// eraft_forward_stream's windows.  Slot j of `padded` / `fmap` is window j - 1 with a carried window (slot 0: the carry), window j
+// without; pair p reads slots p and p + 1, and `batch` is the number of pairs.
+struct StreamPlan {
+    const float* const* vols;
+    int nvol;
+    bool carried;                  // slot 0 comes from the carry
+    bool warm;                     // the pairs' loops one after another at batch 1, each from the previous pair's interpolated flow_low
+    const float* flow_prev;        // warm: flow_low of the pair before pair 0 (the previous call's last), or NULL: pair 0 starts cold
+    float* const* flow_out;        // warm: each pair's predictions, written by its loop
+};
+
 // frames == 0: e1 / e2 / out are eraft_forward's batched tensors.  frames = n > 0 (eraft_forward_many): e1v / e2v hold n pointers to single
-// samples, read by the pad launches; `out` is the context's staging buffer for the batched predictions.
+// samples, read by the pad launches; `out` is the context's staging buffer for the batched predictions.  sp (eraft_forward_stream): the
+// windows come from sp->vols and the carry, `batch` pairs of neighbouring slots.
 static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, const float* const* e1v, const float* const* e2v, int frames,
-                              int batch, int in_h, int in_w, const int pad[4], int iters, const float* flow_init, float* out, hipStream_t st) {
+                              int batch, int in_h, int in_w, const int pad[4], int iters, const float* flow_init, float* out, hipStream_t st,
+                              const StreamPlan* sp = nullptr) {
     const int B = batch, hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
+    const int nimg = sp ? B + 1 : 2 * B;                                 // images in `padded` / `fmap`
+    const int nfn = sp ? sp->nvol : 2 * B;                               // images through the feature network
+    const int s0 = sp && sp->carried ? 1 : 0;                            // the first slot the feature network writes
     EEM_REQUIRE(hp % 8 == 0 && wp % 8 == 0, "eraft_forward: padded size %dx%d must be a multiple of 8", hp, wp);
     const int h8 = hp / 8, w8 = wp / 8;
     const size_t g = (size_t)h8 * w8;
     int rc;
     // ---- workspace
-    const size_t big = (size_t)2 * B * 64 * ((hp + 1) / 2) * ((wp + 1) / 2);
+    const size_t big = (size_t)std::max(nfn, 2 * B) * 64 * ((hp + 1) / 2) * ((wp + 1) / 2);
 #define ENS(b, n) if ((rc = ensure(b, n)) != EEM_OK) return rc
-    ENS(c->padded, (size_t)2 * B * c->cin0 * hp * wp);
+    ENS(c->padded, (size_t)nimg * c->cin0 * hp * wp);
     for (int i = 0; i < 5; ++i) ENS(c->s[i], big);
     {   // scratch of the large-plane instance norm: the first stage has the most (planes x chunks)
         const int hw1 = ((hp + 1) / 2) * ((wp + 1) / 2);
-        size_t need = er_instnorm_scratch_doubles(2 * B * 64, hw1);
-        need = std::max(need, er_instnorm_scratch_doubles(2 * B * 96, hw1 / 4));
-        need = std::max(need, er_instnorm_scratch_doubles(2 * B * 128, hw1 / 16));
+        size_t need = er_instnorm_scratch_doubles(nfn * 64, hw1);
+        need = std::max(need, er_instnorm_scratch_doubles(nfn * 96, hw1 / 4));
+        need = std::max(need, er_instnorm_scratch_doubles(nfn * 128, hw1 / 16));
         if (need > c->nstat_cap) {
             if (c->nstat) EEM_HIP_CHECK(hipFree(c->nstat));
             c->nstat = nullptr; c->nstat_cap = 0;
@@ -604,14 +632,33 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             c->nstat_cap = need;
         }
     }
-    ENS(c->fmap, (size_t)2 * B * 256 * g);
+    ENS(c->fmap, (size_t)nimg * 256 * g);
     ENS(c->net[0], B * 128 * g); ENS(c->net[1], B * 128 * g); ENS(c->net[2], B * 128 * g); ENS(c->inp, B * 128 * g);
     ENS(c->c0, B * 2 * g); ENS(c->c1, B * 2 * g); ENS(c->c1b, B * 2 * g); ENS(c->corr, B * kCorrPad * g); ENS(c->cor1, B * 256 * g);
     ENS(c->corflo, B * 256 * g); ENS(c->flo1, B * 128 * g); ENS(c->motion, B * 128 * g); ENS(c->z, B * 256 * g);
     ENS(c->rh, B * 128 * g); ENS(c->fhid, B * 512 * g); ENS(c->delta, B * 2 * g); ENS(c->mhid, B * 256 * g);
     ENS(c->mask, B * 576 * g);
-    if (c->keep_stages) { ENS(c->st_corr0, B * 324 * g); ENS(c->st_net1, B * 128 * g); ENS(c->st_mask1, B * 576 * g); ENS(c->st_delta1, B * 2 * g); }
+    const bool keep = c->keep_stages && !sp;
+    if (keep) { ENS(c->st_corr0, B * 324 * g); ENS(c->st_net1, B * 128 * g); ENS(c->st_mask1, B * 576 * g); ENS(c->st_delta1, B * 2 * g); }
+    if (sp) {
+        ENS(c->sflow, (size_t)std::max(B, 1) * 2 * g); ENS(c->finit, 2 * g);
+        ENS(c->fi_ws, eraft_forward_interpolate_scratch(1, h8, w8));    // (ints)
+    }
 #undef ENS
+    const int cin0 = c->cin0;
+    const size_t img = (size_t)cin0 * hp * wp;
+    if (sp) {                                                            // the windows into slots s0.., the carried one into slot 0
+        if (sp->carried) EEM_HIP_CHECK(hipMemcpyAsync(c->padded.p, c->carry_pad.p, img * 4, hipMemcpyDeviceToDevice, st));
+        for (int j = 0; j < sp->nvol; ++j)
+            if ((rc = er_pad_launch(sp->vols[j], c->padded.p + (size_t)(s0 + j) * img, cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
+        if (B == 0) {                                                    // one window and no carry: its feature map for the carry, no pair
+            float* feat = nullptr;
+            if ((rc = run_encoder(c, c->fnet, c->padded.p, nfn, cin0, hp, wp, &feat, st)) != EEM_OK) return rc;
+            GConvArgs a = conv_args(c, c->fnet.conv2a, nfn, h8, w8, c->fmap.p, 256, 0, GACT_NONE);
+            set_seg(a, 0, feat, 128, 128, 0);
+            return gconv_launch(a, st);
+        }
+    }
     // Independent branches on the context's side stream (EEM_ERAFT_NO_OVERLAP=1, read per forward: everything on the caller's stream).
     // One forward at a time most launches of this model are 40 - 300 blocks for 256 CUs: the branches fill CUs the main chain leaves idle.
     const char* eno = getenv("EEM_ERAFT_NO_OVERLAP");
@@ -663,14 +710,13 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         if ((rc = ensure(c->czr[pass], (size_t)B * 256 * g)) != EEM_OK || (rc = ensure(c->cq[pass], (size_t)B * 128 * g)) != EEM_OK) return rc;
     // pad channels of the correlation buffer (never written by the lookup)
     EEM_HIP_CHECK(hipMemset2DAsync(c->corr.p + (size_t)324 * g, (size_t)kCorrPad * g * 4, 0, (size_t)(kCorrPad - 324) * g * 4, B, st));
-    const int cin0 = c->cin0;
     // ---- pad both event volumes into one batch (model/eraft.py:106-109)
     float* pad1 = c->padded.p;
     float* pad2 = c->padded.p + (size_t)B * cin0 * hp * wp;
-    if (frames == 0) {
+    if (sp) {
+    } else if (frames == 0) {
         if ((rc = er_pad2_launch(e1, e2, pad1, B * cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
     } else {
-        const size_t img = (size_t)cin0 * hp * wp;
         for (int i = 0; i < frames; ++i) {
             if ((rc = er_pad_launch(e1v[i], pad1 + (size_t)i * img, cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
             if ((rc = er_pad_launch(e2v[i], pad2 + (size_t)i * img, cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
@@ -687,15 +733,17 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     auto run_fnet = [&]() -> int {
         // ---- feature network on [image1; image2] (:116), then its 1x1 output conv
         float* feat = nullptr;
-        if ((rc = run_encoder(c, c->fnet, c->padded.p, 2 * B, cin0, hp, wp, &feat, st)) != EEM_OK) return rc;
+        if ((rc = run_encoder(c, c->fnet, c->padded.p + s0 * img, nfn, cin0, hp, wp, &feat, st)) != EEM_OK) return rc;
         {
-            GConvArgs a = conv_args(c, c->fnet.conv2a, 2 * B, h8, w8, c->fmap.p, 256, 0, GACT_NONE);
+            GConvArgs a = conv_args(c, c->fnet.conv2a, nfn, h8, w8, c->fmap.p + (size_t)s0 * 256 * g, 256, 0, GACT_NONE);
             set_seg(a, 0, feat, 128, 128, 0);
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
         }
-        // ---- all-pairs correlation pyramid (:121)
-        if (c->alt_corr) rc = build_feature_pyramid(c, c->fmap.p + (size_t)B * 256 * g, B, 256, h8, w8, st);
-        else rc = build_pyramid(c, c->fmap.p, c->fmap.p + (size_t)B * 256 * g, B, 256, h8, w8, st);
+        if (s0) EEM_HIP_CHECK(hipMemcpyAsync(c->fmap.p, c->carry_fmap.p, 256 * g * 4, hipMemcpyDeviceToDevice, st));
+        // ---- all-pairs correlation pyramid (:121); the stream's pair p: slots p and p + 1 of one buffer
+        const size_t f2off = (size_t)(sp ? 1 : B) * 256 * g;
+        if (c->alt_corr) rc = build_feature_pyramid(c, c->fmap.p + f2off, B, 256, h8, w8, st);
+        else rc = build_pyramid(c, c->fmap.p, c->fmap.p + f2off, B, 256, h8, w8, st);
         if (rc != EEM_OK) return rc;
         return EEM_OK;
     };
@@ -732,6 +780,10 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     // final_only: the predictions of iterations 0 .. iters - 2 are never formed - their mask head (the 3x3 128 -> 256 and 1x1 256 -> 576
     // convs) and convex upsampling are not launched; the hidden state and coords1 go through the same launches with the same operands,
     // so the one prediction that leaves is bit for bit the last of the full list (tests/test_eraft_hip.py)
+    // warm stream: the pairs' loops one after another at batch 1 (LB), each on its slice of the batch-B context buffers and pyramids
+    const bool warm = sp && sp->warm;
+    int LB = warm ? 1 : B;
+    float* lout = out;
     float* c1p = c->c1.p;
     float* c1q = c->c1b.p;
     // lagged schedule: the prediction of iteration i - mask head and convex upsampling - goes onto the SIDE stream behind the flow branch of
@@ -748,24 +800,40 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         // (work queued on the side stream AFTER a join(): the guard joins it again if a later launch of this iteration fails and the
         // function returns early - `out`, the hidden state and coords1 are still being used over there)
         if (sd != st) guard.forked = true;
-        GConvArgs m = conv_args(c, c->mk0, B, h8, w8, c->mhid.p, 256, 0, GACT_RELU);
+        GConvArgs m = conv_args(c, c->mk0, LB, h8, w8, c->mhid.p, 256, 0, GACT_RELU);
         set_seg(m, 0, pend.hidden, 128, 128, 0);
         int r2 = gconv_launch(m, sd);
         if (r2 != EEM_OK) return r2;
-        m = conv_args(c, c->mk2, B, h8, w8, c->mask.p, 576, 0, GACT_NONE);
+        m = conv_args(c, c->mk2, LB, h8, w8, c->mask.p, 576, 0, GACT_NONE);
         set_seg(m, 0, c->mhid.p, 256, 256, 0);
         m.out_scale = 0.25f;
         if ((r2 = gconv_launch(m, sd)) != EEM_OK) return r2;
         // :155-157 the convex upsampling of coords1 - coords0
-        return er_convex_up_launch(c->c0.p, pend.c1, c->mask.p, out + (size_t)pend.oi * B * 2 * in_h * in_w, B, h8, w8, pad[2], pad[0], in_h,
+        return er_convex_up_launch(c->c0.p, pend.c1, c->mask.p, lout + (size_t)pend.oi * LB * 2 * in_h * in_w, LB, h8, w8, pad[2], pad[0], in_h,
                                    in_w, sd);
     };
+    const float* c1last = nullptr;
+    for (int pr = 0; pr < (warm ? B : 1); ++pr) {
+    const size_t lp = pr;                                                // (0 unless warm)
+    if (warm) {
+        // pair pr from coords0 + forward_interpolate(flow_low of pair pr - 1) (model/eraft.py:134-137), on the device
+        lout = sp->flow_out[pr];
+        c1p = c->c1.p; c1q = c->c1b.p;
+        const float* prev = pr ? c->sflow.p + (lp - 1) * 2 * g : sp->flow_prev;
+        if (prev && (rc = eraft_forward_interpolate(prev, c->finit.p, 1, h8, w8, (int*)c->fi_ws.p, c->fi_ws.cap, st)) != EEM_OK) return rc;
+        if ((rc = er_coords_init_launch(c->c0.p, c->c1.p, prev ? c->finit.p : nullptr, 1, h8, w8, st)) != EEM_OK) return rc;
+    }
+    const int B = LB;                                                    // (the loop's batch)
+    float* const netb[2] = {c->net[0].p + lp * 128 * g, c->net[1].p};   // the pair's initial hidden state in netb[0]
+    float* const czr_l[2] = {c->czr[0].p + lp * 256 * g, c->czr[1].p + lp * 256 * g};
+    float* const cq_l[2] = {c->cq[0].p + lp * 128 * g, c->cq[1].p + lp * 128 * g};
+    float* const inp_l = c->inp.p + lp * 128 * g;
     for (int it = 0; it < iters; ++it) {
-        const bool emit = !c->final_only || it == iters - 1 || (it == 0 && c->keep_stages);   // (mask1 is a kept stage)
+        const bool emit = !c->final_only || it == iters - 1 || (it == 0 && keep);   // (mask1 is a kept stage)
         // the hidden state alternates between two buffers, with a third between the GRU's passes: the state an iteration leaves is read
         // by its lagging mask head during the next iteration and overwritten only in the one after
-        float* nin = c->net[it & 1].p;
-        float* net = c->net[(it + 1) & 1].p;                               // (the state this iteration leaves)
+        float* nin = netb[it & 1];
+        float* net = netb[(it + 1) & 1];                                   // (the state this iteration leaves)
         // coords1 lives in two buffers: iteration `it` reads c1[it & 1], the convex-upsampling launch at its end writes the updated
         // coordinates into the other one
         // EEM_ERAFT_NO_FUSE=1 (read per forward): the separate flow / coords1 += delta launches, for A/B runs and the equality test
@@ -779,9 +847,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         const char* efr = getenv("EEM_ERAFT_FORK_RECORD");
         const bool fork_by_launch = fuse_small && overlap && !(efr && efr[0] == '1');
         if (fuse_small) {
-            if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st, c->c0.p, c->motion.p, 128, 126, fork_by_launch ? c->fork_ev : nullptr)) != EEM_OK) return rc;
+            if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st, c->c0.p, c->motion.p, 128, 126, fork_by_launch ? c->fork_ev : nullptr, lp)) != EEM_OK) return rc;
         } else {
-            if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st)) != EEM_OK) return rc;
+            if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st, nullptr, nullptr, 0, 0, nullptr, lp)) != EEM_OK) return rc;
             if ((rc = er_flow_launch(c->c0.p, c1cur, c->motion.p, 128, 126, B, (int)g, st)) != EEM_OK) return rc;
         }
         // motion encoder (model/update.py:73-81): the flow branch convf1 -> convf2 on the side stream beside the correlation branch
@@ -841,10 +909,10 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                 if (use_pre) {
                     a = conv_args(c, c->gzr_hm[pass], B, h8, w8, c->z.p, 256, 0, GACT_SIGMOID);
                     set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, c->motion.p, 128, 128, 0);
-                    a.pre = c->czr[pass].p; a.pre_ctotal = 256; a.pre_coff = 0;
+                    a.pre = czr_l[pass]; a.pre_ctotal = 256; a.pre_coff = 0;
                 } else {
                     a = conv_args(c, c->gzr[pass], B, h8, w8, c->z.p, 256, 0, GACT_SIGMOID);
-                    set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, c->inp.p, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
+                    set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
                 }
                 // r leaves the launch as r * h (GEPI_ZR); EEM_ERAFT_NO_ZR=1: the separate elementwise launch
                 const char* enz = getenv("EEM_ERAFT_NO_ZR");
@@ -854,20 +922,20 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                 if (!zr_epi && (rc = er_mul_channels_launch(c->rh.p, c->z.p, 256, 128, hcur, B, 128, (long)g, st)) != EEM_OK) return rc;
             } else {
                 a = conv_args(c, c->gz[pass], B, h8, w8, c->z.p, 128, 0, GACT_SIGMOID);
-                set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, c->inp.p, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
+                set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
                 a = conv_args(c, c->gr[pass], B, h8, w8, c->rh.p, 128, 0, GACT_SIGMOID);
-                set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, c->inp.p, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
+                set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
                 a.epi = GEPI_MUL; a.e0 = hcur; a.e0_ctotal = 128; a.e0_coff = 0;
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
             }
             if (use_pre) {
                 a = conv_args(c, c->gq_hm[pass], B, h8, w8, hnext, 128, 0, GACT_TANH);
                 set_seg(a, 0, c->rh.p, 128, 128, 0); set_seg(a, 1, c->motion.p, 128, 128, 0);
-                a.pre = c->cq[pass].p; a.pre_ctotal = 128; a.pre_coff = 0;
+                a.pre = cq_l[pass]; a.pre_ctotal = 128; a.pre_coff = 0;
             } else {
                 a = conv_args(c, c->gq[pass], B, h8, w8, hnext, 128, 0, GACT_TANH);
-                set_seg(a, 0, c->rh.p, 128, 128, 0); set_seg(a, 1, c->inp.p, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
+                set_seg(a, 0, c->rh.p, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
             }
             a.epi = GEPI_GRU; a.e0 = hcur; a.e0_ctotal = 128; a.e0_coff = 0; a.e1 = c->z.p; a.e1_ctotal = stack ? 256 : 128; a.e1_coff = 0;
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
@@ -892,7 +960,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             }
             if (emit) {
                 pend.on = true; pend.c1 = c1nxt; pend.hidden = net; pend.oi = c->final_only ? 0 : it;
-                if (it == iters - 1 || (it == 0 && c->keep_stages)) {        // nothing follows / the kept stages are copied on `st`
+                if (it == iters - 1 || (it == 0 && keep)) {                  // nothing follows / the kept stages are copied on `st`
                     if ((rc = fork()) != EEM_OK || (rc = side_mask()) != EEM_OK || (rc = join()) != EEM_OK) return rc;
                 }
             }
@@ -936,16 +1004,16 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             // :149 coords1 = coords1 + delta_flow and :155-157 the convex upsampling of coords1 - coords0, one launch
             const int oi = c->final_only ? 0 : it;
             if (fuse_small) {
-                if ((rc = er_convex_up_launch(c->c0.p, c1cur, c->mask.p, out + (size_t)oi * B * 2 * in_h * in_w, B, h8, w8, pad[2],
+                if ((rc = er_convex_up_launch(c->c0.p, c1cur, c->mask.p, lout + (size_t)oi * B * 2 * in_h * in_w, B, h8, w8, pad[2],
                                               pad[0], in_h, in_w, st, c->delta.p, c1nxt)) != EEM_OK) return rc;
                 float* t = c1p; c1p = c1q; c1q = t;
             } else {
                 if ((rc = er_axpy_launch(c->c1.p, c->delta.p, (long)B * 2 * g, st)) != EEM_OK) return rc;
-                if ((rc = er_convex_up_launch(c->c0.p, c->c1.p, c->mask.p, out + (size_t)oi * B * 2 * in_h * in_w, B, h8, w8, pad[2],
+                if ((rc = er_convex_up_launch(c->c0.p, c->c1.p, c->mask.p, lout + (size_t)oi * B * 2 * in_h * in_w, B, h8, w8, pad[2],
                                               pad[0], in_h, in_w, st)) != EEM_OK) return rc;
             }
         }
-        if (it == 0 && c->keep_stages) {
+        if (it == 0 && keep) {
             EEM_HIP_CHECK(hipMemcpy2DAsync(c->st_corr0.p, 324 * g * 4, c->corr.p, kCorrPad * g * 4, 324 * g * 4, B,
                                            hipMemcpyDeviceToDevice, st));
             EEM_HIP_CHECK(hipMemcpyAsync(c->st_net1.p, net, B * 128 * g * 4, hipMemcpyDeviceToDevice, st));
@@ -955,10 +1023,16 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     }
     {
         const char* enf = getenv("EEM_ERAFT_NO_FUSE");
-        c->c1last = !(enf && enf[0] == '1') ? c1p : c->c1.p;
+        c1last = !(enf && enf[0] == '1') ? c1p : c->c1.p;
     }
+    // the stream's flow_low of every pair (the next pair's warm start, the carry, eraft_get_stage)
+    if (sp && (rc = er_flow_launch(c->c0.p, c1last, c->sflow.p + lp * 2 * g, 2, 0, B, (int)g, st)) != EEM_OK) return rc;
+    }
+    c->c1last = c1last;
     c->B = B; c->h8 = h8; c->w8 = w8; c->have_last = true;
-    c->stages_valid = c->keep_stages;
+    c->stages_valid = keep;
+    c->fmap_imgs = nimg;
+    c->stream_pairs = sp ? B : 0;
     return EEM_OK;
 }
 
@@ -992,6 +1066,78 @@ extern "C" int eraft_forward_many(eraft_ctx* c, int n, const float* const* event
     for (int i = 0; i < n; ++i)                                          // [nout][n][2][H][W] -> sample i's [nout][1][2][H][W]
         EEM_HIP_CHECK(hipMemcpy2DAsync(flow_out[i], per * 4, c->many_out.p + (size_t)i * per, (size_t)n * per * 4, per * 4, nout,
                                        hipMemcpyDeviceToDevice, st));
+    return EEM_OK;
+}
+
+// Consecutive windows, each through the feature network once (include/eemflow_hip.h).  Cold: one batch-nflow chain as
+// eraft_forward_many, the pairs' feature maps read in place from one buffer.  Warm: the same encoders and pyramids, then the pairs'
+// update loops at batch 1 one after another, each from the interpolated flow_low of the pair before.
+extern "C" int eraft_forward_stream(eraft_ctx* c, int nvol, const float* const* volumes, int in_h, int in_w, const int pad[4], int iters,
+                                    int warm_start, float* const* flow_out, int nflow, void* stream) {
+    EEM_REQUIRE(c && volumes && pad, "eraft_forward_stream: NULL argument");
+    EEM_REQUIRE(c->loaded, "eraft_forward_stream: no weights loaded");
+    EEM_REQUIRE(nvol >= 1 && nvol <= ERAFT_STREAM_MAX_VOLUMES && in_h >= 1 && in_w >= 1 && iters >= 1,
+                "eraft_forward_stream: nvol = %d (1..%d) windows of %dx%d, %d iterations", nvol, ERAFT_STREAM_MAX_VOLUMES, in_h, in_w, iters);
+    EEM_REQUIRE(!c->alt_corr, "eraft_forward_stream: alternate_corr is not supported - the stream reads every pair's all-pairs volume "
+                              "from one batch (eraft_set_alternate_corr(ctx, 0))");
+    for (int j = 0; j < nvol; ++j) EEM_REQUIRE(volumes[j], "eraft_forward_stream: NULL pointer for window %d", j);
+    const int hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
+    EEM_REQUIRE(hp % 8 == 0 && wp % 8 == 0, "eraft_forward_stream: padded size %dx%d must be a multiple of 8", hp, wp);
+    if (c->carry_on) {
+        EEM_REQUIRE(c->carry_wver == c->wver, "eraft_forward_stream: the weights changed since the carried window was encoded; "
+                    "call eraft_stream_reset to start a new stream");
+        EEM_REQUIRE(c->carry_h == in_h && c->carry_w == in_w && memcmp(c->carry_padv, pad, sizeof(c->carry_padv)) == 0,
+                    "eraft_forward_stream: the carried window is %dx%d (pad %d %d %d %d), this call's %dx%d (pad %d %d %d %d); call "
+                    "eraft_stream_reset to start a new stream", c->carry_h, c->carry_w, c->carry_padv[0], c->carry_padv[1], c->carry_padv[2],
+                    c->carry_padv[3], in_h, in_w, pad[0], pad[1], pad[2], pad[3]);
+    }
+    const int P = c->carry_on ? nvol : nvol - 1;
+    EEM_REQUIRE(nflow == P, "eraft_forward_stream: %d windows %s make %d pairs, nflow = %d", nvol,
+                c->carry_on ? "after the carried window" : "with no carried window", P, nflow);
+    if (P > 0) {
+        EEM_REQUIRE(flow_out, "eraft_forward_stream: flow_out is NULL");
+        for (int p = 0; p < P; ++p) EEM_REQUIRE(flow_out[p], "eraft_forward_stream: NULL output for pair %d", p);
+    }
+    EEM_HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t g = (size_t)(hp / 8) * (wp / 8), img = (size_t)c->cin0 * hp * wp;
+    int rc;
+    if ((rc = ensure(c->carry_pad, img)) != EEM_OK || (rc = ensure(c->carry_fmap, 256 * g)) != EEM_OK ||
+        (rc = ensure(c->carry_flow, 2 * g)) != EEM_OK) return rc;
+    const bool warm = warm_start != 0;
+    StreamPlan sp{volumes, nvol, c->carry_on, warm, warm && c->carry_on && c->carry_has_flow ? c->carry_flow.p : nullptr, flow_out};
+    c->carry_on = false;                                                 // (a failed call leaves no carry behind)
+    const int nout = c->final_only ? 1 : iters;
+    const size_t per = (size_t)2 * in_h * in_w;
+    if (P > 0 && !warm && (rc = ensure(c->many_out, (size_t)nout * P * per)) != EEM_OK) return rc;
+    if ((rc = eraft_forward_impl(c, nullptr, nullptr, nullptr, nullptr, 0, P, in_h, in_w, pad, iters, nullptr, warm ? nullptr : c->many_out.p,
+                                 st, &sp)) != EEM_OK) return rc;
+    if (P > 0 && !warm)
+        for (int p = 0; p < P; ++p)                                      // [nout][P][2][H][W] -> pair p's [nout][1][2][H][W]
+            EEM_HIP_CHECK(hipMemcpy2DAsync(flow_out[p], per * 4, c->many_out.p + (size_t)p * per, (size_t)P * per * 4, per * 4, nout,
+                                           hipMemcpyDeviceToDevice, st));
+    // the carry: the last window's padded volume and feature map (slot P), the last pair's flow_low
+    EEM_HIP_CHECK(hipMemcpyAsync(c->carry_pad.p, c->padded.p + (size_t)P * img, img * 4, hipMemcpyDeviceToDevice, st));
+    EEM_HIP_CHECK(hipMemcpyAsync(c->carry_fmap.p, c->fmap.p + (size_t)P * 256 * g, 256 * g * 4, hipMemcpyDeviceToDevice, st));
+    if (P > 0) EEM_HIP_CHECK(hipMemcpyAsync(c->carry_flow.p, c->sflow.p + (size_t)(P - 1) * 2 * g, 2 * g * 4, hipMemcpyDeviceToDevice, st));
+    c->carry_has_flow = P > 0;
+    c->carry_on = true;
+    c->carry_h = in_h; c->carry_w = in_w;
+    memcpy(c->carry_padv, pad, sizeof(c->carry_padv));
+    c->carry_wver = c->wver;
+    return EEM_OK;
+}
+
+extern "C" int eraft_stream_reset(eraft_ctx* c) {
+    EEM_REQUIRE(c, "eraft_stream_reset: NULL context");
+    c->carry_on = false;
+    c->carry_has_flow = false;
+    return EEM_OK;
+}
+
+extern "C" int eraft_stream_pending(eraft_ctx* c, int* out) {
+    EEM_REQUIRE(c && out, "eraft_stream_pending: NULL argument");
+    *out = c->carry_on ? 1 : 0;
     return EEM_OK;
 }
 
@@ -1031,13 +1177,13 @@ extern "C" int eraft_get_stage(eraft_ctx* c, const char* name, float* dst, size_
         eem_set_error("eraft_get_stage: '%s' is only kept after eraft_keep_stages(ctx, 1)", name);
         return EEM_ERR_STATE;
     }
-    if (nm == "fmap") { src = c->fmap.p; dims[0] = 2 * c->B; dims[1] = 256; }
+    if (nm == "fmap") { src = c->fmap.p; dims[0] = c->fmap_imgs; dims[1] = 256; }
     else if (nm == "inp") { src = c->inp.p; dims[0] = c->B; dims[1] = 128; }
     else if (nm == "corr0") { src = c->st_corr0.p; dims[0] = c->B; dims[1] = 324; }
     else if (nm == "net1") { src = c->st_net1.p; dims[0] = c->B; dims[1] = 128; }
     else if (nm == "mask1") { src = c->st_mask1.p; dims[0] = c->B; dims[1] = 576; }
     else if (nm == "delta1") { src = c->st_delta1.p; dims[0] = c->B; dims[1] = 2; }
-    else if (nm == "flow_low") { src = nullptr; dims[0] = c->B; dims[1] = 2; }
+    else if (nm == "flow_low") { src = c->stream_pairs ? c->sflow.p : nullptr; dims[0] = c->stream_pairs ? c->stream_pairs : c->B; dims[1] = 2; }
     else if (nm.size() == 4 && nm.compare(0, 3, "pyr") == 0 && nm[3] >= '0' && nm[3] <= '3') {
         const int l = nm[3] - '0';
         EEM_REQUIRE(!c->alt_corr && c->pyr[l].p, "eraft_get_stage: '%s' does not exist - the last forward computed the correlation on the fly", name);
@@ -1049,7 +1195,7 @@ extern "C" int eraft_get_stage(eraft_ctx* c, const char* name, float* dst, size_
     const size_t n = (size_t)dims[0] * dims[1] * dims[2] * dims[3];
     if (dst == nullptr) return EEM_OK;
     EEM_REQUIRE(cap >= n, "eraft_get_stage: '%s' needs %zu floats, buffer holds %zu", name, n, cap);
-    if (nm == "flow_low") {
+    if (nm == "flow_low" && !c->stream_pairs) {
         int rc = er_flow_launch(c->c0.p, c->c1last, dst, 2, 0, c->B, c->h8 * c->w8, (hipStream_t)stream);
         return rc;
     }
@@ -1065,6 +1211,7 @@ extern "C" int eraft_corr_lookup(eraft_ctx* c, const float* fmap1, const float* 
     int rc = build_pyramid(c, fmap1, fmap2, batch, ch, h, w, (hipStream_t)stream);
     if (rc != EEM_OK) return rc;
     c->B = batch; c->h8 = h; c->w8 = w; c->have_last = true;
+    c->stream_pairs = 0; c->fmap_imgs = 2 * batch;
     return run_lookup(c, coords, out, 324, batch, h, w, (hipStream_t)stream);
 }
 

@@ -168,8 +168,12 @@ class ERAFT(nn.Module):
         self.frames_in_flight = 1      # >= 3: one of several replicas kept busy on separate streams (eraft_set_frames_in_flight)
         self.final_only = False        # True (inference route): the returned list holds the last prediction only - what test_mvsec.py:1455 reads
         self.alternate_corr = False    # True (inference route): correlation features on the fly, no all-pairs volume (RAFT's alternate_corr)
+        self.warm_start = False        # True: forward_stream starts each pair from the previous pair's forward-interpolated flow_low
+        self._stream_prev = None
 
     def change_imagesize(self, img_size):
+        if tuple(img_size) != tuple(getattr(self, "image_size", ())):
+            self.reset_stream()
         self.image_size = img_size
         self.image_padder = InputPadder(img_size, mode='chairs')
 
@@ -185,6 +189,7 @@ class ERAFT(nn.Module):
         twin.frames_in_flight = self.frames_in_flight if frames_in_flight is None else frames_in_flight
         twin.final_only = getattr(self, "final_only", False)
         twin.alternate_corr = getattr(self, "alternate_corr", False)
+        twin.warm_start = getattr(self, "warm_start", False)
         return twin
 
     def freeze_bn(self):
@@ -290,6 +295,79 @@ class ERAFT(nn.Module):
             _lib.check(_lib.lib().eraft_forward_many(ctx, n, p1, p2, h, w, padc, iters, po, _lib.current_stream_ptr(dev)))
         return [((frames[i][0], frames[i][1]), [outs[i][k] for k in range(nout)]) for i in range(n)]
 
+    MAX_STREAM = 16                     # ERAFT_STREAM_MAX_VOLUMES of include/eemflow_hip.h
+
+    def forward_stream(self, volumes, iters=12):
+        """Flow along a stream of CONSECUTIVE event windows, each window through the feature network once (the MVSEC evaluation at
+        stride 1: sample i is windows i and i + 1).  `volumes` are 1..16 [1, C, H, W] tensors in time order, on one device with one
+        shape.  Returns one `((events1, events2), [predictions])` per pair of neighbouring windows - `iters` predictions, or the last
+        with `final_only`.  The last window is carried to the next call, whose first pair starts at it: a call after a carried window
+        returns len(volumes) pairs (events1 of the first is the previous call's last tensor), otherwise len(volumes) - 1.
+        warm_start = False: bitwise what `forward_many` gives for those pairs (in the same kernel forms).  warm_start = True (E-RAFT's
+        sequential mode): each pair starts from forward_interpolate(the previous pair's flow_low), across calls too; the first pair
+        after `reset_stream()` starts cold.  `change_imagesize` to a new size resets the stream; after a weight change
+        (load_state_dict, an optimizer step) the next call raises until `reset_stream()`.  Inference only (eval-mode BatchNorm, no
+        autograd); alternate_corr is refused."""
+        vols = list(volumes)
+        if not 1 <= len(vols) <= self.MAX_STREAM:
+            raise ValueError(f"forward_stream: 1..{self.MAX_STREAM} volumes per call, got {len(vols)}")
+        if not hasattr(self, "image_padder"):
+            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
+        keep, shape = [], None
+        for v in vols:
+            if not v.is_cuda:
+                raise _lib.EEMFlowHipError("ERAFT.forward_stream: inputs must be CUDA (ROCm) tensors - there is no CPU path")
+            v = v.contiguous().float()
+            if v.dim() != 4 or v.shape[0] != 1 or v.shape[1] != self.n_first_channels:
+                raise ValueError(f"forward_stream: every volume is a (1,{self.n_first_channels},H,W) tensor, got {tuple(v.shape)}")
+            if shape is not None and (v.shape != shape or v.device != keep[0].device):
+                raise ValueError("forward_stream: all volumes of a call share one shape and one device")
+            shape = v.shape
+            keep.append(v)
+        if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
+            raise RuntimeError("forward_stream: inference only - BatchNorm is in train mode (call eval())")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("forward_stream: inference only - run it under torch.no_grad() (the stream records no autograd graph)")
+        if getattr(self, "alternate_corr", False):
+            raise ValueError("forward_stream: alternate_corr is not supported (the stream reads every pair's all-pairs volume)")
+        dev = keep[0].device
+        h, w = int(shape[2]), int(shape[3])
+        pad = self.image_padder._pad
+        if (h + pad[2] + pad[3]) % 8 or (w + pad[0] + pad[1]) % 8:
+            raise ValueError("forward_stream: the padded size must be a multiple of 8 (eraft.py:83-94)")
+        L = _lib.lib()
+        ctx = self._context(dev)
+        pending = ctypes.c_int()
+        _lib.check(L.eraft_stream_pending(ctx, ctypes.byref(pending)))
+        carried = self._stream_prev if (pending.value and self._stream_prev is not None) else None
+        if carried is None and pending.value:
+            _lib.check(L.eraft_stream_reset(ctx))                 # (no tensor to name as events1: start over)
+        n = len(keep)
+        nflow = n if carried is not None else n - 1
+        nout = 1 if getattr(self, "final_only", False) else iters
+        outs = [torch.empty(nout, 1, 2, h, w, device=dev, dtype=torch.float32) for _ in range(nflow)]
+        pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
+        po = (ctypes.c_void_p * max(nflow, 1))(*[o.data_ptr() for o in outs])
+        padc = (ctypes.c_int * 4)(*pad)
+        with torch.cuda.device(dev):
+            rc = L.eraft_forward_stream(ctx, n, pv, h, w, padc, iters, 1 if getattr(self, "warm_start", False) else 0, po, nflow,
+                                        _lib.current_stream_ptr(dev))
+        if rc != 0:
+            msg = L.eemflow_last_error().decode("utf-8", "replace")
+            if "eraft_stream_reset" in msg:
+                raise _lib.EEMFlowHipError(f"ERAFT.forward_stream: {msg} - call reset_stream() on the module")
+            raise _lib.EEMFlowHipError(msg)
+        older = ([carried] if carried is not None else []) + vols[:-1]
+        newer = vols if carried is not None else vols[1:]
+        self._stream_prev = vols[-1]
+        return [((older[i], newer[i]), [outs[i][k] for k in range(nout)]) for i in range(nflow)]
+
+    def reset_stream(self):
+        """Drop the window (and flow) `forward_stream` carries: its next call starts a new stream, cold, with len(volumes) - 1 pairs."""
+        self._stream_prev = None
+        if getattr(self, "_ctx", None) is not None:
+            _lib.check(_lib.lib().eraft_stream_reset(self._ctx))
+
     # ------------------------------------------------------------------ differentiable route (eemflow_amd/ops.py)
     def _norm(self, norm, x, relu):
         return apply_norm(norm, x, relu)
@@ -371,6 +449,29 @@ class ERAFT(nn.Module):
             self._release()
         except Exception:
             pass
+
+
+def forward_interpolate(flow):
+    """forward_interpolate_pytorch (utils/image_utils.py:53-84) on the GPU, bit for bit the reference function on the CPU at one thread:
+    flow [B, 2, h, w] (or [2, h, w]) fp32 CUDA tensor -> a new [B, 2, h, w] tensor, each source splatted to its four floor / ceil
+    landing cells in the reference's order and summation order.  E-RAFT's warm start: `forward(e1, e2, flow_init=forward_interpolate(
+    model.stage("flow_low")))`."""
+    if not flow.is_cuda:
+        raise _lib.EEMFlowHipError("forward_interpolate: a CUDA (ROCm) tensor is required - there is no CPU path")
+    f = flow.detach().contiguous().float()
+    if f.dim() == 3:
+        f = f.unsqueeze(0)
+    if f.dim() != 4 or f.shape[1] != 2:
+        raise ValueError(f"forward_interpolate: expected a (B,2,h,w) flow, got {tuple(flow.shape)}")
+    b, _, h, w = (int(x) for x in f.shape)
+    L = _lib.lib()
+    need = L.eraft_forward_interpolate_scratch(b, h, w)
+    scratch = torch.empty(need, device=f.device, dtype=torch.int32)
+    out = torch.empty_like(f)
+    with torch.cuda.device(f.device):
+        _lib.check(L.eraft_forward_interpolate(f.data_ptr(), out.data_ptr(), b, h, w, scratch.data_ptr(), need,
+                                               _lib.current_stream_ptr(f.device)))
+    return out
 
 
 # ---------------------------------------------------------------------- BasicEncoder's operator chain (module level: BasicEncoder.forward and ERAFT share it)

@@ -365,6 +365,47 @@ int eraft_convex_upsample_bwd(const float* flow, const float* mask, const float*
 int eraft_convex_upsample(eraft_ctx* ctx, const float* flow, const float* mask, int batch, int h, int w, float* out,
                           void* stream);
 
+/* Forward interpolation of a low-resolution flow, E-RAFT's warm start: flow [batch][2][h][w] -> out [batch][2][h][w] (out must not
+ * alias flow).  Bit for bit the reference function on the CPU at one thread: each cell adds its four-pass contributions (floor / ceil
+ * landing cells in the reference's order) in source order in fp32 and divides by the weight sum + 1e-15f; cells no source reaches are
+ * 0.  `scratch` is device memory of at least eraft_forward_interpolate_scratch(batch, h, w) ints (3 h w + (h + 1)(w + 1) per sample).
+ * One workgroup per sample.
+ * Replaces: forward_interpolate_pytorch (utils/image_utils.py:53-84, with grid_sample_values :11-51). */
+int eraft_forward_interpolate(const float* flow, float* out, int batch, int h, int w, int* scratch, size_t scratch_ints, void* stream);
+size_t eraft_forward_interpolate_scratch(int batch, int h, int w);
+
+/* Windows per eraft_forward_stream call. */
+#define ERAFT_STREAM_MAX_VOLUMES 16
+
+/* E-RAFT along a stream of CONSECUTIVE event windows, each window through the feature network once.  volumes[j] (j < nvol,
+ * 1..ERAFT_STREAM_MAX_VOLUMES) are [1][C][in_h][in_w] windows in time order (a HOST array of device pointers); pair p is (window
+ * p - 1, window p), window -1 being the one carried from the previous call: nflow == nvol with a carried window, nvol - 1 without
+ * (flow_out may then be NULL for nvol == 1).  flow_out[p] is [iters][1][2][in_h][in_w], or [1][1][2][in_h][in_w] after
+ * eraft_set_final_only, as in eraft_forward_many.  The feature network runs once over the nvol new windows; the context network over
+ * each pair's first window (model/eraft.py:126); the correlation volumes of all pairs come from one buffer of feature maps.
+ * warm_start = 0: one batch-nflow update loop, bitwise eraft_forward_many on the same pairs in the same kernel forms (the feature network
+ * runs nvol images here, 2 nflow there).  warm_start = 1 (E-RAFT's sequential mode): pair p starts from coords0 +
+ * eraft_forward_interpolate(flow_low of pair p - 1) (model/eraft.py:134-137), pair -1 being the previous call's last pair; the first
+ * pair after eraft_stream_reset starts cold.  The pairs' loops then run one after another at batch 1, the interpolation between them
+ * on the device.  Afterwards the context carries the last window's feature map and padded volume and the last pair's flow_low, in
+ * memory that eraft_forward / eraft_forward_many / eraft_get_stage and the operator-level calls leave alone.  A call with other weights
+ * (eraft_load_weights) or another size or pad than the carry's is refused with an error: call eraft_stream_reset.
+ * eraft_get_stage("flow_low") afterwards is [nflow][2][h/8][w/8]: every pair's low-resolution flow.  eraft_set_alternate_corr(1) is
+ * refused: the stream needs the all-pairs volume.  eraft_keep_stages does not apply.
+ * Replaces: the evaluation loop over consecutive samples at stride 1 (test_mvsec.py:580-597), which runs ERAFT.forward's feature
+ * network (model/eraft.py:116) on every window twice; with warm_start, that loop with flow_init = forward_interpolate_pytorch(the
+ * previous pair's coords1 - coords0), which model/eraft.py:48-49,125-128 leaves commented out. */
+int eraft_forward_stream(eraft_ctx* ctx, int nvol, const float* const* volumes, int in_h, int in_w, const int pad[4], int iters,
+                         int warm_start, float* const* flow_out, int nflow, void* stream);
+
+/* Drop the carried window and flow: the next eraft_forward_stream call starts a new stream (cold).
+ * Replaces: the start of a sequence in test_mvsec.py:580-597 (dataset.change_test_sequence). */
+int eraft_stream_reset(eraft_ctx* ctx);
+
+/* *out = 1 when a window is carried for the next eraft_forward_stream call, else 0.
+ * Replaces: nothing in the reference (it has no stream state); the query behind ERAFT.forward_stream's bookkeeping. */
+int eraft_stream_pending(eraft_ctx* ctx, int* out);
+
 /* ------------------------------------------------------------------------------------------------
  * EEMFlow+ (EEMFlow_cdc, model/EEMFlow/EEMFlow+.py + cdc_utils.py): the coarse-to-fine bilinear flow-warp loop.
  * ---------------------------------------------------------------------------------------------- */
