@@ -28,6 +28,7 @@ _SIGNATURES = {
                                              _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
     "eemflow_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
                                         ctypes.c_void_p]),
+    "eemflow_backward_forms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
     "eemflow_sequence_loss": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                              _c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
     "eemflow_set_image_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int * 4)]),

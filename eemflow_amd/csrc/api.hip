@@ -587,6 +587,48 @@ extern "C" int eemflow_time_kernels(eemflow_ctx* c, const float* e1, const float
     return EEM_OK;
 }
 
+// The training buffers eemflow_get_stage reads after a training forward (activations) and after its backward (gradients, "g_" names;
+// include/eemflow_hip.h says what each holds): false if `nm` is none of them
+static bool train_stage_of(eemflow_ctx* c, const std::string& nm, const float** src, int dims[4]) {
+    const Shape& s = c->last;
+    const int n2 = 2 * s.batch, B = s.batch;
+    auto set = [&](const DevBuf& b, int n, int ch, int h, int w) { *src = b.p; dims[0] = n; dims[1] = ch; dims[2] = h; dims[3] = w; return true; };
+    const bool g = nm.compare(0, 2, "g_") == 0;
+    const std::string base = g ? nm.substr(2) : nm;
+    // per-stage names "<name>_k", k = 1..3
+    int k = -1;
+    std::string stem = base;
+    if (base.size() >= 3 && base[base.size() - 2] == '_' && base.back() >= '1' && base.back() <= '3') {
+        k = base.back() - '1';
+        stem = base.substr(0, base.size() - 2);
+    }
+    const int pc[3] = {16, 32, 64};
+    if (k >= 0) {
+        if (stem == "ta") return set(g ? c->g_ta[k] : c->ta[k], B, kDecW, s.gh, s.gw);
+        if (stem == "tb") return set(g ? c->g_tb[k] : c->tb[k], B, kDecW, s.gh, s.gw);
+        if (stem == "tc") return set(g ? c->g_tc[k] : c->tc[k], B, kDecW, s.gh, s.gw);
+        if (stem == "td") return set(g ? c->g_td[k] : c->td[k], B, kDecW, s.gh, s.gw);
+        if (stem == "t64") return set(g ? c->g_t64[k] : c->t64[k], B, 64, s.gh, s.gw);
+        if (stem == "t32") return set(g ? c->g_t32[k] : c->t32[k], B, 32, s.gh, s.gw);
+        if (g && stem == "cat") return set(c->g_cat[k], B, kDecIn, s.gh, s.gw);
+        if (g && stem == "pool") return set(c->g_pool[k], n2, pc[k], s.gh, s.gw);
+        return false;
+    }
+    if (!g) return nm == "padded" && set(c->padded, n2, c->cin0, s.hp, s.wp);
+    if (base == "flow") return set(c->g_flow, B, 2, s.out_h, s.out_w);
+    if (base == "coarse") return set(c->g_coarse, B, 2, s.gh, s.gw);
+    if (base == "flowcat") return set(c->g_flowcat, B, 6, s.gh, s.gw);
+    if (base == "f13") return set(c->g_f13, n2, 64, s.h3, s.w3);
+    if (base == "b3") return set(c->g_b3, n2, 64, s.h3, s.w3);
+    if (base == "a3") return set(c->g_a3, n2, 64, s.h3, s.w3);
+    if (base == "f12") return set(c->g_f12, n2, 32, s.h2, s.w2);
+    if (base == "b2") return set(c->g_b2, n2, 32, s.h2, s.w2);
+    if (base == "a2") return set(c->g_a2, n2, 32, s.h2, s.w2);
+    if (base == "f11") return set(c->g_f11, n2, 16, s.h1, s.w1);
+    if (base == "a1") return set(c->g_a1, n2, 16, s.h1, s.w1);
+    return false;
+}
+
 extern "C" int eemflow_get_stage(eemflow_ctx* c, const char* name, float* dst, size_t cap, int dims[4], void* stream) {
     EEM_REQUIRE(c && name && dims, "eemflow_get_stage: NULL argument");
     EEM_REQUIRE(c->have_last, "eemflow_get_stage: no forward has run");
@@ -610,6 +652,16 @@ extern "C" int eemflow_get_stage(eemflow_ctx* c, const char* name, float* dst, s
         src = c->pool[k].p; dims[0] = n2; dims[1] = pc[k]; dims[2] = s.gh; dims[3] = s.gw;
     } else if (nm.size() == 5 && nm.compare(0, 4, "cat_") == 0 && nm[4] >= '1' && nm[4] <= '3') {
         src = c->cat[nm[4] - '1'].p; dims[0] = s.batch; dims[1] = kDecIn; dims[2] = s.gh; dims[3] = s.gw;
+    } else if (train_stage_of(c, nm, &src, dims)) {
+        // the training buffers belong to the forward whose activations the workspace holds - or to none
+        EEM_REQUIRE(c->have_train_fwd, "eemflow_get_stage: '%s' is a training buffer, and the workspace does not hold a training forward "
+                    "(none has run, or an inference, forward_many or stream call has reused the workspace since)", name);
+        if (nm.compare(0, 2, "g_") == 0) {
+            EEM_REQUIRE(c->bwd_serial == c->train_serial, "eemflow_get_stage: '%s' is stale - no eemflow_backward / eemflow_forward_backward "
+                        "has run for the current training forward", name);
+            EEM_REQUIRE(nm != "g_flow" || c->bwd_fused_loss, "eemflow_get_stage: 'g_flow' is written by eemflow_forward_backward's loss "
+                        "only (eemflow_backward reads the caller's d loss / d flow)");
+        }
     } else {
         eem_set_error("eemflow_get_stage: unknown stage '%s'", name);
         return EEM_ERR_ARG;

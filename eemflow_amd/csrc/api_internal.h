@@ -125,6 +125,14 @@ struct eemflow_ctx {
     // every entry point that writes the shared workspace without keeping the activations calls this: a pending backward then finds a
     // newer serial and its caller recomputes the forward (eemflow.py) instead of differentiating somebody else's activations
     void workspace_overwritten() { have_train_fwd = false; train_serial += 1; }
+    // eemflow_get_stage("g_...") / eemflow_backward_forms: the train_serial whose backward last filled the gradient buffers (-1: none;
+    // they are current while it equals train_serial), whether that was eemflow_forward_backward's (g_flow = d loss / d flow), and the
+    // kernel form each layer's gradients took in it as "<layer>.<what>=<form>;" text (a fixed buffer: no allocation per step)
+    long bwd_serial = -1;
+    bool bwd_fused_loss = false;
+    static constexpr int kFormsCap = 4096;
+    char bwd_forms[kFormsCap] = {};
+    int bwd_forms_len = 0;
     // backward pass: weight / bias gradients are leaves of the chain of data gradients, so they run on this context-owned side stream
     // (fork: an event after the gradient they read; join: the caller's stream waits for the last one before backward returns)
     hipStream_t wstream = nullptr;

@@ -22,6 +22,10 @@ struct WgradArgs {
     int xsc[3] = {0, 0, 0};
 };
 
+// the kernel form the last weight-gradient, pool-backward or upsample-backward launch of this thread took (a string literal, set on the
+// host at the dispatch point; eemflow_backward_forms reports it)
+extern thread_local const char* tr_last_form;
+
 int tr_loss_launch(const float* flow, const float* gt, const float* valid, float* dflow, int batch, int hw, float weight,
                    double* stats, hipStream_t st);
 int tr_upsample_bwd_launch(const float* d, float* tmp, float* out, int nc, int oh, int ow, int h, int w, hipStream_t st);

@@ -4,6 +4,8 @@
 // Data gradients of the convolutions reuse gconv (transposed weights, transposed stride, LeakyReLU' gate).
 #include "train.h"
 
+thread_local const char* tr_last_form = "";
+
 namespace {
 
 inline unsigned nblocks(long n) { return (unsigned)((n + 255) / 256); }
@@ -501,7 +503,9 @@ int tr_loss_launch(const float* flow, const float* gt, const float* valid, float
 
 int tr_upsample_bwd_launch(const float* d, float* tmp, float* out, int nc, int oh, int ow, int h, int w, hipStream_t st) {
     const char* ex = getenv("EEM_UPBWD_THREADS");                     // (=1, read per call: the thread-per-target form, for the equality test)
-    if (ow >= 64 && ow <= 8192 && !(ex && ex[0] == '1'))
+    const bool rows = ow >= 64 && ow <= 8192 && !(ex && ex[0] == '1');
+    tr_last_form = rows ? "rows" : "threads";
+    if (rows)
         hipLaunchKernelGGL(upbwd_x_rows_kernel, dim3((unsigned)(((long)nc * oh + 3) / 4)), dim3(256), 4 * ow * sizeof(float), st, d, tmp, (long)nc * oh, ow, w);
     else
         hipLaunchKernelGGL(upbwd_x_kernel, dim3(nblocks((long)nc * oh * w)), dim3(256), 0, st, d, tmp, (long)nc * oh, ow, w);
@@ -512,7 +516,9 @@ int tr_upsample_bwd_launch(const float* d, float* tmp, float* out, int nc, int o
 
 int tr_pool_bwd_launch(const float* dpool, float* g, long nc, int h, int w, int k, int gh, int gw, int accumulate, const float* gate,
                        hipStream_t st) {
-    if ((w & 3) == 0 && (k & 3) == 0 && (((uintptr_t)g | (uintptr_t)gate) & 15) == 0)
+    const bool vec4 = (w & 3) == 0 && (k & 3) == 0 && (((uintptr_t)g | (uintptr_t)gate) & 15) == 0;
+    tr_last_form = vec4 ? "poolbwd4" : "poolbwd";
+    if (vec4)
         hipLaunchKernelGGL(poolbwd4_kernel, dim3(nblocks(nc * h * (w / 4))), dim3(256), 0, st, dpool, g, nc, h, w, k, gh, gw, accumulate, gate);
     else
         hipLaunchKernelGGL(poolbwd_kernel, dim3(nblocks(nc * h * w)), dim3(256), 0, st, dpool, g, nc, h, w, k, gh, gw, accumulate, gate);
@@ -614,6 +620,7 @@ int tr_wgrad_launch_batch(const WgradArgs* jobs, int njobs, hipStream_t st) {
                     EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_small_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                     small_attr = true;
                 }
+                tr_last_form = "small";
                 if (a0.k == 3) hipLaunchKernelGGL((wgrad_small_kernel<3>), dim3(w, nchunk, njobs), dim3(256), lb, st, b, ipt);
                 else hipLaunchKernelGGL((wgrad_small_kernel<1>), dim3(w, nchunk, njobs), dim3(256), lb, st, b, ipt);
                 EEM_HIP_CHECK(hipGetLastError());
@@ -622,6 +629,7 @@ int tr_wgrad_launch_batch(const WgradArgs* jobs, int njobs, hipStream_t st) {
         }
     }
     dim3 grid(workers, nchunk, njobs);
+    tr_last_form = "generic";
     const WgradArgs& a = jobs[0];
     const int kh = a.kh ? a.kh : a.k, kw = a.kh ? a.kw : a.k;
 #define WG_CASE(KH_, KW_, S_)                                                                                                   \
@@ -732,6 +740,7 @@ int wgrad_few_launch(const WgradArgs& a, hipStream_t st) {
     if (a.cout <= 2) hipLaunchKernelGGL((wgrad_few_kernel<2>), dim3(a.cin, splits), dim3(256), 0, st, a, per_block);
     else if (a.cout <= 4) hipLaunchKernelGGL((wgrad_few_kernel<4>), dim3(a.cin, splits), dim3(256), 0, st, a, per_block);
     else hipLaunchKernelGGL((wgrad_few_kernel<8>), dim3(a.cin, splits), dim3(256), 0, st, a, per_block);
+    tr_last_form = "few";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }

@@ -28,12 +28,27 @@ int side_stream(eemflow_ctx* c, hipStream_t st, hipStream_t* out) {
     return EEM_OK;
 }
 
+const char* const kEncNames[ENC_NUM] = {"pconv1_1", "pconv1_2", "pconv2_1", "pconv2_2", "pconv2_3", "pconv3_1", "pconv3_2", "pconv3_3"};
+
 struct Bwd {
     eemflow_ctx* c;
     hipStream_t st;
     float* grad;           // flat gradient buffer
     hipStream_t wst;       // stream of the weight / bias gradient launches (the context's side stream, or st)
     bool grad_zeroed = false;   // the forward's prologue cleared `grad` on the side stream (forward_train_impl)
+
+    // "<layer>.<what>=<form>;" into the context's record of this backward (eemflow_backward_forms); a full buffer keeps what fits
+    void note(const char* layer, const char* what, const char* form) {
+        const int room = eemflow_ctx::kFormsCap - c->bwd_forms_len;
+        const int n = snprintf(c->bwd_forms + c->bwd_forms_len, room, "%s.%s=%s;", layer, what, form);
+        if (n > 0 && n < room) c->bwd_forms_len += n;
+        else c->bwd_forms[c->bwd_forms_len] = 0;
+    }
+    // the layers of the queued weight gradients (one note per layer, however many decoders / groups it has)
+    void note_queue(const char* const* names, int n, const char* form) {
+        for (int i = 0; i < n; ++i)
+            if (i == 0 || strcmp(names[i], names[i - 1]) != 0) note(names[i], "wgrad", form);
+    }
 
     // the side stream picks up after everything queued on st so far (the gradient a weight-gradient launch reads is complete)
     int fork() {
@@ -81,12 +96,14 @@ struct Bwd {
     // queued variant: the weight gradients of one tail layer (all decoders / groups) go out as ONE launch (flush_wgrads)
     WgradArgs wq[WGRAD_MAX_JOBS];
     BiasJob bq[WGRAD_MAX_JOBS];
+    const char* wq_name[WGRAD_MAX_JOBS];
     int nwq = 0;
     // round 6: the 3x3 convs of the tail are collected over ALL its layers and leave as ONE launch when the tail's chain is through
     // (flush_tail; wgrad_tail.hip) - their operands are the tail's activations and gradients, each in a buffer of its own
     std::vector<WgradArgs> tq;
+    std::vector<const char*> tq_name;
     bool tail_one_launch = false;
-    int wgrad_q(const ConvRef& r, const float* x, int x_ctotal, int x_coff, const float* dy, const float* y_gate, int g_ctotal,
+    int wgrad_q(const char* name, const ConvRef& r, const float* x, int x_ctotal, int x_coff, const float* dy, const float* y_gate, int g_ctotal,
                 int g_coff, int g_cmul, int n, int hin, int win, int hout, int wout) {
         if (tail_one_launch && r.k == 3) {
             WgradArgs w;
@@ -96,8 +113,10 @@ struct Bwd {
             w.n = n; w.hin = hin; w.win = win; w.hout = hout; w.wout = wout; w.k = 3; w.stride = r.stride; w.pad = 1;
             w.zero_page = nullptr;
             tq.push_back(w);
+            tq_name.push_back(name);
             return EEM_OK;
         }
+        wq_name[nwq] = name;
         WgradArgs& w = wq[nwq++];
         w.x = x; w.x_ctotal = x_ctotal; w.x_coff = x_coff; w.cin = r.cin;
         w.g = dy; w.gate = y_gate; w.g_ctotal = g_ctotal; w.g_coff = g_coff; w.g_cmul = g_cmul; w.cout = r.cout;
@@ -113,6 +132,7 @@ struct Bwd {
         if (nwq == 0) return EEM_OK;
         int rc = fork();
         if (rc == EEM_OK) rc = tr_wgrad_launch_batch(wq, nwq, wst);
+        if (rc == EEM_OK) note_queue(wq_name, nwq, tr_last_form);
         if (rc == EEM_OK) rc = tr_bias_grad_launch_batch(bq, nwq, wst);
         nwq = 0;
         return rc;
@@ -121,16 +141,19 @@ struct Bwd {
         if (tq.empty()) return flush_wgrads();
         int rc = fork();
         if (rc == EEM_OK) rc = wgrad_tail_launch(tq.data(), (int)tq.size(), n, h, w, wst);
+        if (rc == EEM_OK) note_queue(tq_name.data(), (int)tq_name.size(), tr_last_form);
         tq.clear();
+        tq_name.clear();
         if (rc == EEM_OK && nwq > 0) {                   // (the deferred ones, behind the same fork)
             rc = tr_wgrad_launch_batch(wq, nwq, wst);
+            if (rc == EEM_OK) note_queue(wq_name, nwq, tr_last_form);
             if (rc == EEM_OK) rc = tr_bias_grad_launch_batch(bq, nwq, wst);
             nwq = 0;
         }
         return rc;
     }
     // weight + bias gradient of a conv layer into the flat buffer
-    int wgrad(const ConvRef& r, const float* x, int x_ctotal, int x_coff, const float* dy, const float* y_gate, int g_ctotal,
+    int wgrad(const char* name, const ConvRef& r, const float* x, int x_ctotal, int x_coff, const float* dy, const float* y_gate, int g_ctotal,
               int g_coff, int g_cmul, int n, int hin, int win, int hout, int wout) {
         WgradArgs w;
         w.x = x; w.x_ctotal = x_ctotal; w.x_coff = x_coff; w.cin = r.cin;
@@ -140,11 +163,14 @@ struct Bwd {
         w.zero_page = c->zero_page; w.db = grad + r.b;
         int rc = fork();
         if (rc != EEM_OK) return rc;
-        if (wgrad_ring_supported(w) && wgrad_ring_preferred(w)) return wgrad_ring_launch(w, wst);   // weight and bias gradient in one kernel
-        if (wgrad_enc_supported(w)) return wgrad_enc_launch(w, wst);
-        rc = tr_wgrad_launch(w, wst);
-        if (rc != EEM_OK) return rc;
-        return tr_bias_grad_launch(dy, y_gate, g_ctotal, g_coff, g_cmul, r.cout, n, hout * wout, grad + r.b, wst);
+        if (wgrad_ring_supported(w) && wgrad_ring_preferred(w)) rc = wgrad_ring_launch(w, wst);   // weight and bias gradient in one kernel
+        else if (wgrad_enc_supported(w)) rc = wgrad_enc_launch(w, wst);
+        else if ((rc = tr_wgrad_launch(w, wst)) == EEM_OK) {
+            note(name, "wgrad", tr_last_form);
+            return tr_bias_grad_launch(dy, y_gate, g_ctotal, g_coff, g_cmul, r.cout, n, hout * wout, grad + r.b, wst);
+        }
+        if (rc == EEM_OK) note(name, "wgrad", tr_last_form);
+        return rc;
     }
 };
 
@@ -186,8 +212,12 @@ static int backward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const 
     if (rs != EEM_OK) return rs;
     Bwd bw{c, st, grad_out, wst};
     bw.grad_zeroed = grad_zeroed;
+    c->bwd_serial = -1;                              // (the gradient buffers are being rewritten)
+    c->bwd_forms_len = 0;
+    c->bwd_forms[0] = 0;
     const int rc = backward_chain(c, s, e1, e2, dflow, grad_out, st, bw);
     const int rj = bw.join();                        // also after an error: nothing of this pass stays behind on the side stream
+    if (rc == EEM_OK && rj == EEM_OK) c->bwd_serial = c->train_serial;
     return rc != EEM_OK ? rc : rj;
 }
 
@@ -199,6 +229,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
     if (!bw.grad_zeroed) EEM_HIP_CHECK(hipMemsetAsync(grad_out, 0, c->nflat * sizeof(float), st));
     // ---- upsample backward (EEMFlow.py:118-120)
     if ((rc = tr_upsample_bwd_launch(dflow, c->ups_tmp.p, c->g_coarse.p, B * 2, s.out_h, s.out_w, s.gh, s.gw, st)) != EEM_OK) return rc;
+    bw.note("upsample", "bwd", tr_last_form);
     // ---- the 1/64-grid tail, last layer first.  Weight / bias gradients: one launch per conv.  Data gradients: the
     // same conv layer of all three decoders (and all five groups) as the jobs of ONE tail_conv_kernel launch - a 9-way
     // K split per block like the forward, instead of 60 register-gather launches of 32 blocks each.
@@ -207,12 +238,13 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
     const int gh = s.gh, gw = s.gw;
     TailConvLaunch TL;
     TL.batch = B; TL.h = gh; TL.w = gw;
-    auto run_jobs = [&](int ksize) {
+    auto run_jobs = [&](int ksize, const char* layer) {
         TL.ksize = ksize;
         // this layer's weight gradients: one launch - or, with the tail's 3x3 layers leaving as one launch at the end (flush_tail), the
         // few others (the 1x1 out_conv) wait for that launch's fork: one event record less in the chain (~7 us each)
         int r = bw.tail_one_launch ? EEM_OK : bw.flush_wgrads();
         if (r == EEM_OK) r = tail_conv_launch(TL, st);
+        if (r == EEM_OK) bw.note(layer, "dgrad", "tail_conv");
         TL.njobs = 0;
         return r;
     };
@@ -225,54 +257,55 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
         bw.tail_one_launch = wgrad_tail_supported(&probe, 1, B, gh, gw);
     }
     // out_conv (1x1, no activation)
-    if ((rc = bw.wgrad_q(c->t_outc, c->flowcat.p, 6, 0, c->g_coarse.p, nullptr, 2, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+    if ((rc = bw.wgrad_q("out_conv", c->t_outc, c->flowcat.p, 6, 0, c->g_coarse.p, nullptr, 2, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
     TL.job[TL.njobs++] = bw.djob(c->t_outc, c->g_coarse.p, nullptr, 2, 0, 1, c->g_flowcat.p, 6, 0);
-    if ((rc = run_jobs(1)) != EEM_OK) return rc;
+    if ((rc = run_jobs(1, "out_conv")) != EEM_OK) return rc;
     // conv7: 32 -> 2, no activation; its output gradient is channels [2k, 2k+2) of g_flowcat
     for (int k = 0; k < 3; ++k) {
-        if ((rc = bw.wgrad_q(c->t_dconv7[k], c->t32[k].p, 32, 0, c->g_flowcat.p, nullptr, 6, 2 * k, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+        if ((rc = bw.wgrad_q("conv7", c->t_dconv7[k], c->t32[k].p, 32, 0, c->g_flowcat.p, nullptr, 6, 2 * k, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
         TL.job[TL.njobs++] = bw.djob(c->t_dconv7[k], c->g_flowcat.p, nullptr, 6, 2 * k, 1, c->g_t32[k].p, 32, 0);
     }
-    if ((rc = run_jobs(3)) != EEM_OK) return rc;
+    if ((rc = run_jobs(3, "conv7")) != EEM_OK) return rc;
     // conv6: 64 -> 32 (gate = its output t32)
     for (int k = 0; k < 3; ++k) {
-        if ((rc = bw.wgrad_q(c->t_dconv6[k], c->t64[k].p, 64, 0, c->g_t32[k].p, c->t32[k].p, 32, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+        if ((rc = bw.wgrad_q("conv6", c->t_dconv6[k], c->t64[k].p, 64, 0, c->g_t32[k].p, c->t32[k].p, 32, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
         TL.job[TL.njobs++] = bw.djob(c->t_dconv6[k], c->g_t32[k].p, c->t32[k].p, 32, 0, 1, c->g_t64[k].p, 64, 0);
     }
-    if ((rc = run_jobs(3)) != EEM_OK) return rc;
+    if ((rc = run_jobs(3, "conv6")) != EEM_OK) return rc;
     // conv5: 100 -> 64, input = td (shuffled output of conv4)
     for (int k = 0; k < 3; ++k) {
-        if ((rc = bw.wgrad_q(c->t_dconv5[k], c->td[k].p, kDecW, 0, c->g_t64[k].p, c->t64[k].p, 64, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+        if ((rc = bw.wgrad_q("conv5", c->t_dconv5[k], c->td[k].p, kDecW, 0, c->g_t64[k].p, c->t64[k].p, 64, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
         TL.job[TL.njobs++] = bw.djob(c->t_dconv5[k], c->g_t64[k].p, c->t64[k].p, 64, 0, 1, c->g_td[k].p, kDecW, 0);
     }
-    if ((rc = run_jobs(3)) != EEM_OK) return rc;
+    if ((rc = run_jobs(3, "conv5")) != EEM_OK) return rc;
 
     // conv4, conv3, conv2: grouped + channel shuffle; group g's output channel j lives at j*G + g of the shuffled
     // tensor, its inputs are channels [g*per, (g+1)*per) of the previous activation
     for (int layer = 2; layer >= 0; --layer) {
+        static const char* const gname[3] = {"conv2", "conv3", "conv4"};
         for (int k = 0; k < 3; ++k) {
             float* act[4] = {c->ta[k].p, c->tb[k].p, c->tc[k].p, c->td[k].p};
             float* gact[4] = {c->g_ta[k].p, c->g_tb[k].p, c->g_tc[k].p, c->g_td[k].p};
             for (int gi = 0; gi < G; ++gi) {
                 const ConvRef& r = c->t_dgroup[k][layer][gi];
-                if ((rc = bw.wgrad_q(r, act[layer], kDecW, gi * per, gact[layer + 1], act[layer + 1], kDecW, gi, G, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+                if ((rc = bw.wgrad_q(gname[layer], r, act[layer], kDecW, gi * per, gact[layer + 1], act[layer + 1], kDecW, gi, G, B, gh, gw, gh, gw)) != EEM_OK) return rc;
                 TL.job[TL.njobs++] = bw.djob(r, gact[layer + 1], act[layer + 1], kDecW, gi, G, gact[layer], kDecW, gi * per);
             }
         }
-        if ((rc = run_jobs(3)) != EEM_OK) return rc;
+        if ((rc = run_jobs(3, gname[layer])) != EEM_OK) return rc;
     }
     // conv1: 69 -> 100, input = cat_k
     for (int k = 0; k < 3; ++k) {
-        if ((rc = bw.wgrad_q(c->t_dconv1[k], c->cat[k].p, kDecIn, 0, c->g_ta[k].p, c->ta[k].p, kDecW, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+        if ((rc = bw.wgrad_q("conv1", c->t_dconv1[k], c->cat[k].p, kDecIn, 0, c->g_ta[k].p, c->ta[k].p, kDecW, 0, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
         TL.job[TL.njobs++] = bw.djob(c->t_dconv1[k], c->g_ta[k].p, c->ta[k].p, kDecW, 0, 1, c->g_cat[k].p, kDecIn, 0);
     }
-    if ((rc = run_jobs(3)) != EEM_OK) return rc;
+    if ((rc = run_jobs(3, "conv1")) != EEM_OK) return rc;
     // rconv_k: pooled features of events1 -> channels [53, 69) of cat_k (gate = those channels)
     for (int k = 0; k < 3; ++k) {
-        if ((rc = bw.wgrad_q(c->t_rconv[k], c->pool[k].p, pc[k], 0, c->g_cat[k].p, c->cat[k].p, kDecIn, kNTaps, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
+        if ((rc = bw.wgrad_q("rconv", c->t_rconv[k], c->pool[k].p, pc[k], 0, c->g_cat[k].p, c->cat[k].p, kDecIn, kNTaps, 1, B, gh, gw, gh, gw)) != EEM_OK) return rc;
         TL.job[TL.njobs++] = bw.djob(c->t_rconv[k], c->g_cat[k].p, c->cat[k].p, kDecIn, kNTaps, 1, c->g_pool[k].p, pc[k], 0);
     }
-    if ((rc = run_jobs(3)) != EEM_OK) return rc;
+    if ((rc = run_jobs(3, "rconv")) != EEM_OK) return rc;
     // every 3x3 weight gradient of the tail: one launch on the side stream (three launches beside the chain - after conv5, after the
     // grouped layers, here - measured 178 us of kernels for 99 and a slower step: the chain's own launches wait behind their blocks)
     if ((rc = bw.flush_tail(B, gh, gw)) != EEM_OK) return rc;
@@ -283,6 +316,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
             cj[k] = CorrBwdJob{c->g_cat[k].p, c->pool[k].p, c->pool[k].p + (size_t)B * pc[k] * g, c->g_pool[k].p,
                                c->g_pool[k].p + (size_t)B * pc[k] * g, kDecIn, pc[k]};
         if ((rc = tr_corr_bwd_launch_jobs(cj, 3, B, gh, gw, c->taps, kNTaps, st)) != EEM_OK) return rc;      // one launch for the three stages
+        bw.note("corr", "bwd", "corrbwd");
     }
     // ---- encoder (EEMFlow.py:135-154): both event volumes as one batch of 2B images; c->padded holds them replicate-padded since the
     // forward (forward_train_impl), which read its first layer from there
@@ -300,6 +334,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
     // pre-activation, so weight/bias gradients read them as they are and the stride-1 data gradients run on the
     // encoder's own fast conv kernels (W^T, zero bias, no activation, epilogue gate = the next layer's output).
     if ((rc = tr_pool_bwd_launch(c->g_pool[2].p, c->g_f13.p, (long)n2 * 64, s.h3, s.w3, 8, s.gh, s.gw, 0, c->f13.p, st)) != EEM_OK) return rc;
+    bw.note("pool_3", "bwd", tr_last_form);
     for (const L& l : ls) {
         const ConvRef& r = c->t_enc[l.layer];
         if (!l.gx) {
@@ -308,12 +343,12 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
             static const bool side = [] { const char* e = getenv("EEM_WGRAD_LAST_SIDE"); return e && e[0] == '1'; }();
             hipStream_t keep = bw.wst;
             if (!side) bw.wst = st;
-            rc = bw.wgrad(r, l.x, l.xc, 0, l.gy, nullptr, r.cout, 0, 1, n2, l.hin, l.win, l.hout, l.wout);
+            rc = bw.wgrad(kEncNames[l.layer], r, l.x, l.xc, 0, l.gy, nullptr, r.cout, 0, 1, n2, l.hin, l.win, l.hout, l.wout);
             bw.wst = keep;
             if (rc != EEM_OK) return rc;
             continue;
         }
-        if ((rc = bw.wgrad(r, l.x, l.xc, 0, l.gy, nullptr, r.cout, 0, 1, n2, l.hin, l.win, l.hout, l.wout)) != EEM_OK) return rc;
+        if ((rc = bw.wgrad(kEncNames[l.layer], r, l.x, l.xc, 0, l.gy, nullptr, r.cout, 0, 1, n2, l.hin, l.win, l.hout, l.wout)) != EEM_OK) return rc;
         if (r.fast_dgrad) {
             EncConvArgs a;
             memset(&a, 0, sizeof(a));
@@ -333,6 +368,8 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
                 if (w3 && n2 >= 4) a.reverse = 3;
             }
             if ((rc = enc_conv_launch(r.cout, r.cin, 1, a, st)) != EEM_OK) return rc;
+            // (enc_conv_launch's order: the Winograd kernels when the weights are there and the width allows, else a direct kernel)
+            bw.note(kEncNames[l.layer], "dgrad", a.wwino && wino_supported(r.cout, r.cin, 1, a.win) ? (a.wino_f4 ? "wino4" : "wino2") : "direct");
         } else {
             // stride-2 layers read a stage output, which also feeds the pooling
             const bool first = l.layer == ENC_2_1;
@@ -343,14 +380,27 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
             d.n = n2; d.cin = r.cin; d.cout = r.cout; d.hin = l.hin; d.win = l.win; d.hout = l.hout; d.wout = l.wout;
             if ((l.layer == ENC_2_1 || l.layer == ENC_3_1) && dgrad_s2_supported(d)) {
                 if ((rc = dgrad_s2_launch(d, st)) != EEM_OK) return rc;      // conv^T + pooling branch + gate in one kernel
+                bw.note(kEncNames[l.layer], "dgrad", "dgrad_s2");
                 continue;
             }
             if ((rc = bw.dgrad(r, l.gy, nullptr, r.cout, 0, 1, n2, l.hout, l.wout, l.hin, l.win, l.gx, r.cin, 0)) != EEM_OK) return rc;
+            bw.note(kEncNames[l.layer], "dgrad", "gconv");
             // stride-2 layers read a stage output, which also feeds the pooling: add that branch, then gate
             if (l.layer == ENC_3_1 && (rc = tr_pool_bwd_launch(c->g_pool[1].p, c->g_f12.p, (long)n2 * 32, s.h2, s.w2, 16, s.gh, s.gw, 1, c->f12.p, st)) != EEM_OK) return rc;
             if (l.layer == ENC_2_1 && (rc = tr_pool_bwd_launch(c->g_pool[0].p, c->g_f11.p, (long)n2 * 16, s.h1, s.w1, 32, s.gh, s.gw, 1, c->f11.p, st)) != EEM_OK) return rc;
+            bw.note(l.layer == ENC_3_1 ? "pool_2" : "pool_1", "bwd", tr_last_form);
         }
     }
+    return EEM_OK;
+}
+
+// The kernel form of every layer's gradients in the last backward, as "<layer>.<what>=<form>;" text (recorded on the host at the dispatch
+// points of backward_impl)
+extern "C" int eemflow_backward_forms(eemflow_ctx* c, char* dst, size_t cap) {
+    EEM_REQUIRE(c && dst, "eemflow_backward_forms: NULL argument");
+    EEM_REQUIRE(c->bwd_forms_len > 0, "eemflow_backward_forms: no backward has run on this context");
+    EEM_REQUIRE(cap > (size_t)c->bwd_forms_len, "eemflow_backward_forms: %d characters, buffer holds %zu", c->bwd_forms_len + 1, cap);
+    memcpy(dst, c->bwd_forms, (size_t)c->bwd_forms_len + 1);
     return EEM_OK;
 }
 
@@ -437,6 +487,7 @@ extern "C" int eemflow_backward(eemflow_ctx* c, int64_t serial, const float* e1,
     EEM_REQUIRE(serial == c->train_serial, "eemflow_backward: the activations of forward %lld were overwritten by forward %lld "
                 "(one forward per backward and context; run eemflow_forward_train again)", (long long)serial, (long long)c->train_serial);
     EEM_HIP_CHECK(hipSetDevice(c->device));
+    c->bwd_fused_loss = false;
     return backward_impl(c, c->train_shape, e1, e2, dflow, grad_out, (hipStream_t)stream);
 }
 
@@ -497,6 +548,7 @@ extern "C" int eemflow_forward_backward(eemflow_ctx* c, const float* e1, const f
         EEM_HIP_CHECK(hipEventRecord(c->stats_ev, c->cstream));
         c->stats_pending = true;
     }
+    c->bwd_fused_loss = true;
     if ((rc = backward_impl(c, s, e1, e2, c->g_flow.p, grad_out, st, zero.done)) != EEM_OK) return rc;
     if (stats_out) {
         double hst[5];

@@ -411,11 +411,14 @@ int launch_wide(const WgradArgs& a, hipStream_t st) {
 template <int MT, int S>
 int launch_tw(const WgradArgs& a, hipStream_t st) {
     static const bool mt1 = [] { const char* e = getenv("EEM_WGRAD_BX3_MT1"); return e && e[0] == '1'; }();     // (measurement)
+    const bool tw32 = a.wout % 32 == 0 || a.wout >= 256;
     if ((MT >= 2 || mt1) && use_bx3()) {                             // (one 16-cout tile per wave: the splits cost what the multiplies save)
-        if (a.wout % 32 == 0 || a.wout >= 256) return launch<MT, S, 32, 16, 3, 3, true>(a, st);
+        tr_last_form = tw32 ? "enc_bx3_tw32" : "enc_bx3_tw16";
+        if (tw32) return launch<MT, S, 32, 16, 3, 3, true>(a, st);
         return launch<MT, S, 16, 16, 3, 3, true>(a, st);
     }
-    if (a.wout % 32 == 0 || a.wout >= 256) return launch<MT, S, 32, 16>(a, st);
+    tr_last_form = tw32 ? "enc_fp32_tw32" : "enc_fp32_tw16";
+    if (tw32) return launch<MT, S, 32, 16>(a, st);
     return launch<MT, S, 16, 16>(a, st);
 }
 
@@ -459,7 +462,10 @@ int wgrad_enc_launch(const WgradArgs& a, hipStream_t st) {
         if (mt == 2) return launch_tw<2, 1>(a, st);
         return launch_tw<4, 1>(a, st);
     }
-    if (mt == 1 && a.cin <= 5 && (a.wout % 32 == 0 || a.wout >= 256)) return launch<1, 2, 32, 5>(a, st);   // pconv1_1
+    if (mt == 1 && a.cin <= 5 && (a.wout % 32 == 0 || a.wout >= 256)) {     // pconv1_1
+        tr_last_form = "enc_fp32_tw32_c5";
+        return launch<1, 2, 32, 5>(a, st);
+    }
     if (mt == 1) return launch_tw<1, 2>(a, st);
     if (mt == 2) return launch_tw<2, 2>(a, st);
     return launch_tw<4, 2>(a, st);

@@ -526,23 +526,26 @@ int wgrad_ring_launch(const WgradArgs& a, hipStream_t st) {
     if (const char* e = getenv("EEM_WGRAD_RING_BLOCK")) {
         const int v = atoi(e);
         if (a.stride == 1 && kh == 3 && (a.kh ? a.kw : a.k) == 3) {
-            if (v == 6464) return launch_ring<Cfg64x64>(a, st);
-            if (v == 3232) return launch_ring<Cfg32x32>(a, st);
-            if (v == 1616) return launch_ring<Cfg16x16>(a, st);
+            if (v == 6464) { tr_last_form = "ring_6464"; return launch_ring<Cfg64x64>(a, st); }
+            if (v == 3232) { tr_last_form = "ring_3232"; return launch_ring<Cfg32x32>(a, st); }
+            if (v == 1616) { tr_last_form = "ring_1616"; return launch_ring<Cfg16x16>(a, st); }
         }
     }
     if (a.stride == 2) {
-        if (a.cout <= 32 && a.cin <= 16) return launch_ring<Cfg32x16s2>(a, st);
-        if (a.cout <= 64 && a.cin <= 32) return launch_ring<Cfg64x32s2>(a, st);
+        if (a.cout <= 32 && a.cin <= 16) { tr_last_form = "ring_s2_3216"; return launch_ring<Cfg32x16s2>(a, st); }
+        if (a.cout <= 64 && a.cin <= 32) { tr_last_form = "ring_s2_6432"; return launch_ring<Cfg64x32s2>(a, st); }
+        tr_last_form = "ring_s2_6464";
         return launch_ring<Cfg64x64s2>(a, st);
     }
+    tr_last_form = "ring_wide";
     if (kh == 5) {
         const char* e = getenv("EEM_WGRAD_RING_51");                 // (measurement: 6464 = 64 input channels per block, strips of <= 64)
         if (e && atoi(e) == 6464) return launch_ring<Cfg64x64r51>(a, st);
         return a.wout > 64 ? launch_ring<Cfg64x32r51>(a, st) : launch_ring<Cfg64x64r51>(a, st);
     }
     if (kh == 1) return launch_ring<Cfg64x64r15>(a, st);
-    if (a.cout <= 16 && a.cin <= 16) return launch_ring<Cfg16x16>(a, st);
-    if (a.cout <= 32 && a.cin <= 32) return launch_ring<Cfg32x32>(a, st);
+    if (a.cout <= 16 && a.cin <= 16) { tr_last_form = "ring_1616"; return launch_ring<Cfg16x16>(a, st); }
+    if (a.cout <= 32 && a.cin <= 32) { tr_last_form = "ring_3232"; return launch_ring<Cfg32x32>(a, st); }
+    tr_last_form = "ring_6464";
     return launch_ring<Cfg64x64>(a, st);
 }

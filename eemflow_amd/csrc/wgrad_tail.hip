@@ -240,6 +240,7 @@ int wgrad_tail_launch(const WgradArgs* jobs, int njobs, int n, int h, int w, hip
         raised = true;
     }
     static const int dbg = [] { const char* e = getenv("EEM_TW_DBG"); return e ? atoi(e) : 0; }();     // measurement: 1 no atomics, 2 no k-loop, 4 no G staging
+    tr_last_form = "wgrad_tail";
     hipLaunchKernelGGL(wgrad_tail_kernel, dim3((unsigned)hb.size()), dim3(256), lds_bytes, st, tc->djobs, tc->dblocks, n, h, w, ipt, gp, dbg);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

@@ -357,6 +357,12 @@ class EEMFlow(nn.Module):
                                            _lib.current_stream_ptr(self._ctx_device)))
         return out
 
+    def backward_forms(self):
+        """{"<layer>.<wgrad | dgrad | bwd>": kernel form} of the last backward (see eemflow_backward_forms)."""
+        buf = ctypes.create_string_buffer(8192)
+        _lib.check(_lib.lib().eemflow_backward_forms(self._ctx, buf, len(buf)))
+        return dict(kv.split("=", 1) for kv in buf.value.decode().split(";") if kv)
+
     def _release(self):
         if self._ctx is not None:
             _lib.lib().eemflow_destroy(self._ctx)

@@ -162,7 +162,21 @@ int eemflow_time_kernels(eemflow_ctx* ctx, const float* events1, const float* ev
 /* Copy an intermediate of the LAST forward into dst (device).  Names: "f11","f12","f13" (stage
  * outputs, images 0..B-1 = events1, B..2B-1 = events2), "pool_1".."pool_3", "cat_1".."cat_3"
  * ([cv(53) | r(16)]), "flow_1".."flow_3" (as channels 0-1, 2-3, 4-5 of "flowcat"), "flowcat",
- * "coarse".  dims_out = [n, c, h, w].  For parity tests against the oracle's stage tensors. */
+ * "coarse".  dims_out = [n, c, h, w].  For parity tests against the oracle's stage tensors.
+ *
+ * While the workspace holds a training forward (eemflow_forward_train / eemflow_forward_backward, and no inference, forward_many
+ * or stream call since), also: "padded" ([2B][n_first_channels][hp][wp]: both event volumes replicate-padded, events1 first) and
+ * the decoders' activations "ta_k", "tb_k", "tc_k", "td_k" ([B][100][gh][gw]: conv1's output, then conv2, conv3, conv4's outputs
+ * after the channel shuffle), "t64_k", "t32_k" (conv5, conv6), k = 1..3.
+ * After eemflow_backward / eemflow_forward_backward for THAT forward, the gradient buffers "g_<name>" (the call fails while no
+ * backward has run for the current training forward):
+ *   tail, d loss / d the stored tensor: "g_flow" ([B][2][out_h][out_w], the loss kernel's d loss / d flow; eemflow_forward_backward
+ *   only), "g_coarse", "g_flowcat", "g_t32_k", "g_t64_k", "g_td_k", "g_tc_k", "g_tb_k", "g_ta_k" (before the LeakyReLU' of the
+ *   tensor's own layer: d loss / d its output), "g_cat_k" ([B][69][gh][gw]), "g_pool_k" ([2B][16 / 32 / 64][gh][gw]: the pooled
+ *   maps of both volumes, events1 first);
+ *   encoder, d loss / d the PRE-activation of the layer that produced the tensor (LeakyReLU' of its stored output applied; for the
+ *   stage outputs f11 / f12 / f13 with the pooling branch added before that): "g_f13", "g_b3", "g_a3", "g_f12", "g_b2", "g_a2",
+ *   "g_f11", "g_a1" ([2B][C][h][w] like the activations).  pconv1_1 gets no data gradient. */
 int eemflow_get_stage(eemflow_ctx* ctx, const char* name, float* dst, size_t dst_capacity_floats,
                       int dims_out[4], void* stream);
 
@@ -239,6 +253,13 @@ int eemflow_forward_train(eemflow_ctx* ctx, const float* events1, const float* e
                           float* flow_out, int out_h, int out_w, int64_t* serial_out, void* stream);
 int eemflow_backward(eemflow_ctx* ctx, int64_t serial, const float* events1, const float* events2, const float* dflow,
                      float* grad_out, void* stream);
+
+/* The kernel each layer's gradients took in the last backward of this context, as "<layer>.<what>=<form>;" text, e.g.
+ * "upsample.bwd=rows;out_conv.wgrad=small;out_conv.dgrad=tail_conv;...;conv7.wgrad=wgrad_tail;...;pconv3_1.dgrad=dgrad_s2;
+ * pconv2_2.wgrad=enc_bx3_tw16;...".  Layers: upsample, out_conv, conv1 .. conv7 (all decoders and groups of a layer share one
+ * launch), rconv, corr, pool_1 .. pool_3, pconv1_1 .. pconv3_3.  Recorded on the host at dispatch (no synchronisation).  Fails
+ * before any backward and when `capacity` (bytes, terminating zero included) is too small. */
+int eemflow_backward_forms(eemflow_ctx* ctx, char* dst, size_t capacity);
 
 /* One term of sequence_loss and its gradient: weight * mean over batch*2*h*w of valid*|flow - gt| with
  * valid = (valid >= 0.5) & (|gt| < 400).  dflow_out [batch][2][h][w] = d term / d flow.  stats6 (DEVICE, 6 doubles, added
