@@ -1,5 +1,5 @@
-// C ABI of libeemflow_hip.so (declared in include/eemflow_hip.h): context, weight packing,
-// workspace management, the forward schedule and its HIP-graph cache.
+// C ABI of libeemflow_hip.so (declared in include/eemflow_hip.h): context, weight packing, the entry points and
+// their HIP-graph cache.  Workspace management: workspace.hip; the forward schedule: schedule.hip (both declared in ctx.h).
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "api_internal.h"
+#include "ctx.h"
 #include <mutex>
 
 // ------------------------------------------------------------------------------- errors

@@ -2,7 +2,7 @@
 // activation kept, sequence loss, the full backward pass into one flat gradient buffer (state_dict order - the
 // buffer a data-parallel job all-reduces over RCCL), then gradient clipping + AdamW on the device-resident
 // weights and the re-pack of every MFMA weight layout.
-#include "api_internal.h"
+#include "ctx.h"
 #include "eraft_kernels.h"
 #include "train.h"
 
@@ -363,7 +363,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
             a.hin = l.hout; a.win = l.wout; a.hout = l.hin; a.wout = l.win; a.hraw = l.hout; a.wraw = l.wout;
             a.act = 0;
             a.gate = l.x;                                        // -> gradient w.r.t. the previous conv's pre-activation
-            {   // (the interleaved tile walk of the batched forward chains, api_internal.h; EEM_WALK3_TRAIN=0 keeps the contiguous ranges)
+            {   // (the interleaved tile walk of the batched forward chains, schedule.hip enc_walk; EEM_WALK3_TRAIN=0 keeps the contiguous ranges)
                 static const bool w3 = [] { const char* e = getenv("EEM_WALK3_TRAIN"); return !(e && e[0] == '0'); }();
                 if (w3 && n2 >= 4) a.reverse = 3;
             }

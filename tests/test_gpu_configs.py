@@ -77,7 +77,7 @@ def test_c3_training_step_mvsec_346x260_batch32_vs_oracle():
 
 
 def test_c4_training_hrem_1280x720_batch8_vs_oracle(monkeypatch):
-    # the encoder's Winograd form follows the batch (F(4x4,3x3) on every stride-1 layer from batch 4 on, csrc/api_internal.h
+    # the encoder's Winograd form follows the batch (F(4x4,3x3) on every stride-1 layer from batch 4 on, csrc/ctx.h
     # f4_mask); the shard identities below compare batch 8 with batches of 2, so the form is pinned (read when the weights load)
     monkeypatch.setenv("EEM_WINO4_LAYERS", "7")
     monkeypatch.setenv("EEM_DEC_WNC", "1")           # (the decoders' wide convs too: Winograd kernel from four samples per launch on)
@@ -178,7 +178,7 @@ def test_dp_equivalence_two_shards_one_gpu(b, h, w, monkeypatch):
     """Rank r of a 2-rank job holds samples [r*b/2, (r+1)*b/2).  parallel.average_gradients computes (g0 + g1) / 2 (SUM all-reduce,
     / world); that must be the gradient of the reference's mean over the GLOBAL batch (train_mvsec.py:215), and the replicas' clip +
     AdamW on it must track the single-process step.  The Winograd form is pinned: by default it follows the per-launch batch
-    (f4_mask, csrc/api_internal.h), and this test compares launches of b with launches of b/2."""
+    (f4_mask, csrc/ctx.h), and this test compares launches of b with launches of b/2."""
     monkeypatch.setenv("EEM_WINO4_LAYERS", "7")
     e1, e2 = (torch.from_numpy(a).to(DEV) for a in synthetic_voxel_pair(131, b, h, w))
     gt, valid = (torch.from_numpy(a).to(DEV) for a in synthetic_gt(132, b, h, w))

@@ -64,7 +64,7 @@ SWITCHES = ("EEM_WINO", "EEM_WINO4_LAYERS", "EEM_NO_ENC1", "EEM_BX3_S1", "EEM_NO
 
 
 def forms_of(env, batch, fif):
-    """The form every encoder stage takes under these switches (api_internal.h f4_mask / bx3_wanted, conv_enc.hip's dispatch)."""
+    """The form every encoder stage takes under these switches (ctx.h f4_mask, schedule.hip bx3_wanted, conv_enc.hip's dispatch)."""
     def s1(c):
         if env.get("EEM_WINO") == "0":
             return "direct"
