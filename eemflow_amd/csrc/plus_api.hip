@@ -78,6 +78,17 @@ struct eemplus_ctx {
     hipEvent_t ev_fork = nullptr, ev_lvl[7] = {};
     int B = 0, hl[7] = {0}, wl[7] = {0};
     bool have_last = false;
+    unsigned long wver = 0;              // bumped by every eemplus_load_weights (the stream's carry records it)
+    // the pyramid the levels of the last call read (level_units, run_level, eemplus_level): levels 2..6 at fb[l], pair b's feature_1 image b
+    // and its feature_2 image b + f2off - the forward's f[l] with f2off = B, or the stream's sf[l] with f2off = 1
+    float* fb[7] = {};
+    int f2off = 0;
+    // eemplus_forward_stream: levels 2..6 of its windows, one image per window, image 0 the window carried in.  forward / forward_many
+    // leave these alone; the carried window sits in image carry_slot until the next stream call moves it to image 0
+    PBuf sf[7];
+    bool carry_on = false;
+    int carry_slot = 0, carry_h = 0, carry_w = 0, carry_pad[4] = {0, 0, 0, 0}, carry_cin = 0;
+    unsigned long carry_wver = 0;
 };
 
 namespace {
@@ -359,6 +370,7 @@ extern "C" void eemplus_destroy(eemplus_ctx* c) {
         if (c->a2_l[l].p) (void)hipFree(c->a2_l[l].p);
         if (c->cat_l[l].p) (void)hipFree(c->cat_l[l].p);
         if (c->f[l].p) (void)hipFree(c->f[l].p);
+        if (c->sf[l].p) (void)hipFree(c->sf[l].p);
         if (c->fup[l].p) (void)hipFree(c->fup[l].p);
         if (c->finit[l].p) (void)hipFree(c->finit[l].p);
         if (c->flow[l].p) (void)hipFree(c->flow[l].p);
@@ -375,6 +387,7 @@ extern "C" int eemplus_load_weights(eemplus_ctx* c, const float* flat, size_t nf
     EEM_REQUIRE(n_first_channels >= 1 && n_first_channels <= 64, "eemplus_load_weights: n_first_channels=%d", n_first_channels);
     EEM_REQUIRE(groups == 3 || groups == 1, "eemplus_load_weights: groups must be 3 (reference default) or 1, got %d", groups);
     EEM_HIP_CHECK(hipSetDevice(c->device));
+    ++c->wver;                                                     // (a stream's carried window is stale from here on, whatever follows)
     Cur cur{flat, flat + nfloats};
     Pk pk;
     c->zero_off = pk.push(4096);
@@ -469,8 +482,8 @@ static int level_units(eemplus_ctx* c, int l, int B, hipStream_t st, bool skip_r
     int rc;
     const int C[7] = {0, 16, 32, 64, 64, 64, 64};
     const int h = c->hl[l], w = c->wl[l];
-    const float* f1 = c->f[l].p;
-    const float* f2 = c->f[l].p + (size_t)B * C[l] * h * w;
+    const float* f1 = c->fb[l];
+    const float* f2 = c->fb[l] + (size_t)c->f2off * C[l] * h * w;
     if (l <= 5) {
         // (the coarse levels: both projections - the same weights on the two feature maps - as the two jobs of ONE small-grid launch)
         static const bool no_tail = [] { const char* e = getenv("EEM_PLUS_NO_TAIL"); return e && e[0] == '1'; }();
@@ -505,8 +518,8 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
     int rc;
     const int C[7] = {0, 16, 32, 64, 64, 64, 64};
     const int* hl = c->hl; const int* wl = c->wl;
-    auto f1 = [&](int k) { return c->f[k].p; };
-    auto f2 = [&](int k) { return c->f[k].p + (size_t)B * C[k] * hl[k] * wl[k]; };
+    auto f1 = [&](int k) { return (const float*)c->fb[k]; };
+    auto f2 = [&](int k) { return (const float*)c->fb[k] + (size_t)c->f2off * C[k] * hl[k] * wl[k]; };
     const int h = hl[l], w = wl[l], hc = hl[l + 1], wc = wl[l + 1];
     const size_t g = (size_t)h * w;
     if ((rc = level_buffers(c, l, B)) != EEM_OK ||
@@ -595,13 +608,67 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
 // One forward over `batch` samples.  frames == 0: events1 / events2 / flow_out are the batched tensors of eemplus_forward.  frames = n > 0
 // (eemplus_forward_many): e1v / e2v / outv hold n pointers to single samples - the pad launches read each sample from its own tensor and
 // the five full-resolution predictions of sample i go to outv[i] [5][1][2][in_h][in_w]; everything between runs as the batch-n chain.
+// sp (eemplus_forward_stream): the encoder runs over the stream's nvol windows alone, into the stream's pyramid (stream_pyramid) after
+// the carried window; pair p reads image p as feature_1 and image p + 1 as feature_2.  batch = frames = the pairs (0: encode and carry).
+struct PlusStream { const float* const* vols; int nvol; bool carried; };
+
+// The stream's levels 2..6 for `nimg` images of this call's geometry, the carried window (image c->carry_slot) moved to image 0 by ONE
+// launch - within the buffers, or from the old ones into grown ones (freed once the move is through).
+static int stream_pyramid(eemplus_ctx* c, int nimg, bool carried, hipStream_t st) {
+    const int C[7] = {0, 16, 32, 64, 64, 64, 64};
+    size_t need[7] = {0};
+    bool grow = false;
+    for (int l = 2; l <= 6; ++l) {
+        need[l] = (size_t)nimg * C[l] * c->hl[l] * c->wl[l];
+        grow = grow || need[l] > c->sf[l].cap;
+    }
+    PBuf old[7];
+    if (grow) {
+        for (int l = 2; l <= 6; ++l) {
+            old[l] = c->sf[l];
+            c->sf[l] = PBuf();
+            const size_t cap = need[l] > old[l].cap ? need[l] : old[l].cap;
+            hipError_t e = hipMalloc(&c->sf[l].p, cap * sizeof(float));
+            if (e != hipSuccess) {                               // (levels 2 .. l hold new buffers: back to the old ones)
+                for (int k = 2; k <= l; ++k) { if (c->sf[k].p) (void)hipFree(c->sf[k].p); c->sf[k] = old[k]; }
+                eem_set_error("eemplus_forward_stream: %s", hipGetErrorString(e));
+                return EEM_ERR_HIP;
+            }
+            c->sf[l].cap = cap;
+        }
+    }
+    if (carried && (grow || c->carry_slot != 0)) {
+        PlCarryJobs J;
+        J.njobs = 5;
+        for (int l = 2; l <= 6; ++l) {
+            const size_t img = (size_t)C[l] * c->hl[l] * c->wl[l];
+            J.src[l - 2] = (grow ? old[l].p : c->sf[l].p) + (size_t)c->carry_slot * img;
+            J.dst[l - 2] = c->sf[l].p;
+            J.n4[l - 2] = (long)(img / 4);
+        }
+        const int rc = pl_carry_launch(J, st);
+        if (rc != EEM_OK) return rc;
+    }
+    if (grow) {
+        EEM_HIP_CHECK(hipStreamSynchronize(st));
+        for (int l = 2; l <= 6; ++l) if (old[l].p) EEM_HIP_CHECK(hipFree(old[l].p));
+    }
+    c->carry_slot = 0;
+    return EEM_OK;
+}
+
 static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, const float* const* e1v, const float* const* e2v, int frames,
-                             int batch, int in_h, int in_w, const int pad[4], float* out, float* const* outv, hipStream_t st) {
-    const int B = batch, n2 = 2 * batch, hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
+                             int batch, int in_h, int in_w, const int pad[4], float* out, float* const* outv, hipStream_t st,
+                             const PlusStream* sp = nullptr) {
+    const int B = batch, n2 = sp ? sp->nvol : 2 * batch, hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
     int rc;
-    // ---- pad, encoder on both volumes (EEMFlow+.py:162-169)
+    // ---- pad, encoder on both volumes (EEMFlow+.py:162-169); the stream: on its new windows (n2 = nvol images)
     if ((rc = pensure(c->padded, (size_t)n2 * c->cin0 * hp * wp)) != EEM_OK) return rc;
-    if (frames == 0) {
+    if (sp) {
+        const size_t img = (size_t)c->cin0 * hp * wp;
+        for (int i = 0; i < sp->nvol; ++i)
+            if ((rc = er_pad_launch(sp->vols[i], c->padded.p + (size_t)i * img, c->cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
+    } else if (frames == 0) {
         if ((rc = er_pad2_launch(e1, e2, c->padded.p, B * c->cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
     } else {
         const size_t img = (size_t)c->cin0 * hp * wp;
@@ -616,8 +683,16 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
     for (int l = 4; l <= 6; ++l) { hl[l] = hl[l - 1] / 2; wl[l] = wl[l - 1] / 2; }
     EEM_REQUIRE(hl[6] >= 1 && wl[6] >= 1, "eemplus_forward: padded input %dx%d is too small for the 6-level pyramid", hp, wp);
     const int C[7] = {0, 16, 32, 64, 64, 64, 64};
-    for (int l = 1; l <= 6; ++l)
+    for (int l = 1; l <= (sp ? 1 : 6); ++l)
         if ((rc = pensure(c->f[l], (size_t)n2 * C[l] * hl[l] * wl[l])) != EEM_OK) return rc;
+    // where the encoder and the pooling write levels 2..6: the forward's pyramid, or the stream's after the carried window
+    float* fo[7] = {nullptr, c->f[1].p};
+    if (sp) {
+        if ((rc = stream_pyramid(c, (sp->carried ? 1 : 0) + sp->nvol, sp->carried, st)) != EEM_OK) return rc;
+        for (int l = 2; l <= 6; ++l) fo[l] = c->sf[l].p + (sp->carried ? (size_t)C[l] * hl[l] * wl[l] : 0);
+    } else {
+        for (int l = 2; l <= 6; ++l) fo[l] = c->f[l].p;
+    }
     // scratch for the two-conv stages: reuse `dense` (large) and `cat`
     {
         const size_t s1 = (size_t)n2 * 16 * hl[1] * wl[1], s2 = (size_t)n2 * 32 * hl[2] * wl[2], s3 = (size_t)n2 * 64 * hl[3] * wl[3];
@@ -627,8 +702,8 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
         struct EStep { const float* in; float* out; int hin, win, hout, wout; };
         const EStep es[8] = {{c->padded.p, t0, hp, wp, hl[1], wl[1]},     {t0, c->f[1].p, hl[1], wl[1], hl[1], wl[1]},
                              {c->f[1].p, t0, hl[1], wl[1], hl[2], wl[2]}, {t0, t1, hl[2], wl[2], hl[2], wl[2]},
-                             {t1, c->f[2].p, hl[2], wl[2], hl[2], wl[2]}, {c->f[2].p, t0, hl[2], wl[2], hl[3], wl[3]},
-                             {t0, t1, hl[3], wl[3], hl[3], wl[3]},        {t1, c->f[3].p, hl[3], wl[3], hl[3], wl[3]}};
+                             {t1, fo[2], hl[2], wl[2], hl[2], wl[2]},     {fo[2], t0, hl[2], wl[2], hl[3], wl[3]},
+                             {t0, t1, hl[3], wl[3], hl[3], wl[3]},        {t1, fo[3], hl[3], wl[3], hl[3], wl[3]}};
         for (int i = 0; i < 8; ++i) {
             const PLayer& L = c->enc[i];
             if (c->enc_fast) {
@@ -653,10 +728,16 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
         }
     }
     // avg_pool2d(2,2) x3 (:170-175), one launch
-    if ((rc = er_pool2x3_launch(c->f[3].p, c->f[4].p, c->f[5].p, c->f[6].p, (long)n2 * 64, hl[3], wl[3], st)) != EEM_OK) return rc;
+    if ((rc = er_pool2x3_launch(fo[3], fo[4], fo[5], fo[6], (long)n2 * 64, hl[3], wl[3], st)) != EEM_OK) return rc;
 
-    auto f1 = [&](int l) { return c->f[l].p; };
-    auto f2 = [&](int l) { return c->f[l].p + (size_t)B * C[l] * hl[l] * wl[l]; };
+    for (int l = 2; l <= 6; ++l) c->fb[l] = sp ? c->sf[l].p : c->f[l].p;
+    c->f2off = sp ? 1 : B;
+    if (B == 0) {                                   // (the stream's first window alone: encoded for the carry, no pair to run)
+        c->B = 0; c->have_last = false;
+        return EEM_OK;
+    }
+    auto f1 = [&](int l) { return (const float*)c->fb[l]; };
+    auto f2 = [&](int l) { return (const float*)c->fb[l] + (size_t)c->f2off * C[l] * hl[l] * wl[l]; };
     // ---- what the levels compute from the pyramid alone (level_units), on a side stream beside the coarse levels' chain: OPT-IN
     // (EEM_PLUS_SIDE=1, read per forward).  Measured at 1280x720 over 40 forwards: 841 - 866 frames/s against 884 - 891 in the chain - the
     // fork's event record and the five waits cost the chain more than the ~75 us of launches they take out of it, and a forward that
@@ -735,6 +816,56 @@ extern "C" int eemplus_forward_many(eemplus_ctx* c, int n, const float* const* e
     for (int i = 0; i < n; ++i) EEM_REQUIRE(events1[i] && events2[i] && flow_out[i], "eemplus_forward_many: NULL pointer for sample %d", i);
     EEM_HIP_CHECK(hipSetDevice(c->device));
     return plus_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream);
+}
+
+// Consecutive windows, each through the encoder once (include/eemflow_hip.h): one batch-nflow chain as eemplus_forward_many, the pairs'
+// feature maps read in place from the stream's pyramid, whose image 0 is the window carried from the call before.
+extern "C" int eemplus_forward_stream(eemplus_ctx* c, int n, const float* const* volumes, int in_h, int in_w, const int pad[4],
+                                      float* const* flow_out, int nflow, void* stream) {
+    EEM_REQUIRE(c && volumes && pad, "eemplus_forward_stream: NULL argument");
+    EEM_REQUIRE(c->loaded, "eemplus_forward_stream: no weights loaded");
+    EEM_REQUIRE(n >= 1 && n <= EEM_STREAM_MAX_VOLUMES && in_h >= 1 && in_w >= 1, "eemplus_forward_stream: n = %d (1..%d) windows of %dx%d", n,
+                EEM_STREAM_MAX_VOLUMES, in_h, in_w);
+    for (int j = 0; j < n; ++j) EEM_REQUIRE(volumes[j], "eemplus_forward_stream: NULL pointer for window %d", j);
+    if (c->carry_on) {
+        EEM_REQUIRE(c->carry_wver == c->wver && c->carry_cin == c->cin0, "eemplus_forward_stream: the weights changed since the carried window "
+                    "was encoded; call eemplus_stream_reset to start a new stream");
+        EEM_REQUIRE(c->carry_h == in_h && c->carry_w == in_w && memcmp(c->carry_pad, pad, sizeof(c->carry_pad)) == 0,
+                    "eemplus_forward_stream: the carried window is %dx%d (pad %d %d %d %d), this call's %dx%d (pad %d %d %d %d); call "
+                    "eemplus_stream_reset to start a new stream", c->carry_h, c->carry_w, c->carry_pad[0], c->carry_pad[1], c->carry_pad[2],
+                    c->carry_pad[3], in_h, in_w, pad[0], pad[1], pad[2], pad[3]);
+    }
+    const int P = c->carry_on ? n : n - 1;
+    EEM_REQUIRE(nflow == P, "eemplus_forward_stream: %d windows %s make %d pairs, nflow = %d", n,
+                c->carry_on ? "after the carried window" : "with no carried window", P, nflow);
+    if (P > 0) {
+        EEM_REQUIRE(flow_out, "eemplus_forward_stream: flow_out is NULL");
+        for (int p = 0; p < P; ++p) EEM_REQUIRE(flow_out[p], "eemplus_forward_stream: NULL output for pair %d", p);
+    }
+    EEM_HIP_CHECK(hipSetDevice(c->device));
+    const PlusStream sp{volumes, n, c->carry_on};
+    c->carry_on = false;                                                 // (a call that fails from here on leaves no carry behind)
+    const int rc = plus_forward_impl(c, nullptr, nullptr, nullptr, nullptr, P, P, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream, &sp);
+    if (rc != EEM_OK) return rc;
+    c->carry_on = true;
+    c->carry_slot = P;                                                   // the last window: image P of the stream's pyramid
+    c->carry_h = in_h; c->carry_w = in_w;
+    memcpy(c->carry_pad, pad, sizeof(c->carry_pad));
+    c->carry_cin = c->cin0;
+    c->carry_wver = c->wver;
+    return EEM_OK;
+}
+
+extern "C" int eemplus_stream_reset(eemplus_ctx* c) {
+    EEM_REQUIRE(c, "eemplus_stream_reset: NULL context");
+    c->carry_on = false;
+    return EEM_OK;
+}
+
+extern "C" int eemplus_stream_pending(eemplus_ctx* c, int* out) {
+    EEM_REQUIRE(c && out, "eemplus_stream_pending: NULL argument");
+    *out = c->carry_on ? 1 : 0;
+    return EEM_OK;
 }
 
 extern "C" int eemplus_set_frames_in_flight(eemplus_ctx* c, int n) {

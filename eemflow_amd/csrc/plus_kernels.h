@@ -22,5 +22,14 @@ int pl_copy_channels_launch(const float* src, int s_ctotal, int s_coff, float* d
 // doubling of the coarse flow (into fc_scaled, a second buffer) + WarpingLayer_no_div(x, flow_init) as one launch (h x w >= 2 hc x wc)
 int pl_warp_blend_warp_launch(const float* flow_init, const float* xout, float* out, float* cat, int cat_ctotal, int cat_coff, const float* f2,
                               float* fw, int c2, int batch, int h, int w, hipStream_t st);
+// eemplus_forward_stream's carried window: dst[k][0 .. 4 n4[k]) = src[k][...] for njobs (1..5) disjoint, 16-byte-aligned pairs, one launch
+#define PL_CARRY_MAX_JOBS 5
+struct PlCarryJobs {
+    const float* src[PL_CARRY_MAX_JOBS];
+    float* dst[PL_CARRY_MAX_JOBS];
+    long n4[PL_CARRY_MAX_JOBS];
+    int njobs;
+};
+int pl_carry_launch(const PlCarryJobs& J, hipStream_t st);
 int pl_upflow_warp_launch(const float* fc, float* fc_scaled, int hc, int wc, float* fi, const float* x, float* out, int out_ctotal, int out_coff,
                           int batch, int c, int h, int w, hipStream_t st);

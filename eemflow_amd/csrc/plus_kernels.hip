@@ -240,7 +240,33 @@ __global__ __launch_bounds__(256) void copy_channels_kernel(const float* __restr
     dst[((size_t)b * d_ctotal + d_coff + ch) * hw + p] = src ? src[((size_t)b * s_ctotal + s_coff + ch) * hw + p] : 0.f;
 }
 
+// eemplus_forward_stream's carry: up to five buffers moved as one grid-stride pass of float4s; element i belongs to the first job whose
+// prefix end exceeds it.  src and dst of a job do not overlap.
+__global__ __launch_bounds__(256) void carry_kernel(PlCarryJobs J, long total4) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
+        int k = 0;
+        long base = 0;
+        while (k < J.njobs - 1 && i >= base + J.n4[k]) { base += J.n4[k]; ++k; }
+        reinterpret_cast<float4*>(J.dst[k])[i - base] = reinterpret_cast<const float4*>(J.src[k])[i - base];
+    }
+}
+
 }  // namespace
+
+int pl_carry_launch(const PlCarryJobs& J, hipStream_t st) {
+    EEM_REQUIRE(J.njobs >= 1 && J.njobs <= PL_CARRY_MAX_JOBS, "pl_carry_launch: %d jobs (1..%d)", J.njobs, PL_CARRY_MAX_JOBS);
+    long total4 = 0;
+    for (int k = 0; k < J.njobs; ++k) {
+        EEM_REQUIRE(J.src[k] && J.dst[k] && J.n4[k] >= 0 && ((uintptr_t)J.src[k] & 15) == 0 && ((uintptr_t)J.dst[k] & 15) == 0,
+                    "pl_carry_launch: job %d needs 16-byte-aligned buffers", k);
+        total4 += J.n4[k];
+    }
+    if (total4 == 0) return EEM_OK;
+    const long want = (total4 + 255) / 256;
+    hipLaunchKernelGGL(carry_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, J, total4);
+    EEM_HIP_CHECK(hipGetLastError());
+    return EEM_OK;
+}
 
 int pl_warp_launch(const float* x, const float* flow, int flow_ctotal, float* out, int out_ctotal, int out_coff, int batch, int c, int h,
                    int w, int mode, hipStream_t st) {

@@ -110,8 +110,12 @@ class EEMFlow_cdc(nn.Module):  # noqa: N801
         self._ctx = None
         self._ctx_device = None
         self._weights_version = None
+        self._stream_prev = None        # forward_stream: the caller's tensor of the window the context carries (events1 of the next pair)
 
     def change_imagesize(self, img_size):
+        old = getattr(self, "image_size", None)
+        if old is not None and tuple(int(v) for v in old) != tuple(int(v) for v in img_size):
+            self.reset_stream()                                  # a carried window of another size cannot start the next pair
         self.image_size = img_size
         self.image_padder = InputPadder(img_size, mode='chairs', eval_pad_rate=64)
 
@@ -202,6 +206,65 @@ class EEMFlow_cdc(nn.Module):  # noqa: N801
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().eemplus_forward_many(ctx, n, p1, p2, h, w, padc, po, _lib.current_stream_ptr(dev)))
         return [((frames[i][0], frames[i][1]), [outs[i][k] for k in range(5)]) for i in range(n)]
+
+    MAX_STREAM = 16                     # EEM_STREAM_MAX_VOLUMES of include/eemflow_hip.h
+
+    def forward_stream(self, volumes):
+        """Flow along a stream of CONSECUTIVE event windows, each window padded and encoded once (the MVSEC evaluation walks a sequence
+        this way: sample i is windows i and i + 1, loader/MVSEC.py:115-116).  `volumes` are 1..16 [1, C, H, W] tensors in time order, on
+        one device with one shape.  Returns one `((events1, events2), [flow6 .. flow2 at full resolution])` per pair of neighbouring
+        windows, bitwise what `forward_many` gives for those pairs once the kernel forms that follow the encoder's image count are pinned
+        (include/eemflow_hip.h, eemplus_forward_stream).  The last window is carried to the next call, whose first pair starts at it: a
+        call after a carried window returns len(volumes) pairs (events1 of the first is the previous call's last tensor), otherwise
+        len(volumes) - 1.  `reset_stream()` drops the carried window; `change_imagesize` to a new size does too.  After a weight change
+        (optimizer step, load_state_dict) the next call raises until `reset_stream()`.  Inference only (no autograd graph is recorded)."""
+        vols = list(volumes)
+        if not 1 <= len(vols) <= self.MAX_STREAM:
+            raise ValueError(f"forward_stream: 1..{self.MAX_STREAM} volumes per call, got {len(vols)}")
+        if not hasattr(self, "image_padder"):
+            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
+        keep, shape = [], None
+        for v in vols:
+            if not v.is_cuda:
+                raise _lib.EEMFlowHipError("EEMFlow_cdc.forward_stream: inputs must be CUDA (ROCm) tensors - there is no CPU path")
+            v = v.contiguous().float()
+            if v.dim() != 4 or v.shape[0] != 1 or v.shape[1] != self.n_first_channels:
+                raise ValueError(f"forward_stream: every volume is a (1,{self.n_first_channels},H,W) tensor, got {tuple(v.shape)}")
+            if shape is not None and (v.shape != shape or v.device != keep[0].device):
+                raise ValueError("forward_stream: all volumes of a call share one shape and one device")
+            shape = v.shape
+            keep.append(v)
+        dev = keep[0].device
+        h, w = int(shape[2]), int(shape[3])
+        L = _lib.lib()
+        ctx = self._context(dev)
+        pending = ctypes.c_int()
+        _lib.check(L.eemplus_stream_pending(ctx, ctypes.byref(pending)))
+        carried = self._stream_prev if (pending.value and self._stream_prev is not None) else None
+        if carried is None and pending.value:
+            _lib.check(L.eemplus_stream_reset(ctx))               # (no tensor to name as events1: start over)
+        n = len(keep)
+        nflow = n if carried is not None else n - 1
+        outs = [torch.empty(5, 1, 2, h, w, device=dev, dtype=torch.float32) for _ in range(nflow)]
+        pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
+        po = (ctypes.c_void_p * max(nflow, 1))(*[o.data_ptr() for o in outs])
+        padc = (ctypes.c_int * 4)(*self.image_padder._pad)
+        with torch.cuda.device(dev):
+            rc = L.eemplus_forward_stream(ctx, n, pv, h, w, padc, po, nflow, _lib.current_stream_ptr(dev))
+        if rc != 0:
+            msg = L.eemflow_last_error().decode("utf-8", "replace")
+            if "eemplus_stream_reset" in msg:
+                raise _lib.EEMFlowHipError(f"EEMFlow_cdc.forward_stream: {msg} - call reset_stream() on the module")
+            raise _lib.EEMFlowHipError(msg)
+        older = ([carried] if carried is not None else []) + vols[:-1]
+        self._stream_prev = vols[-1]
+        return [((older[i], vols[i + 1 - (1 if carried is not None else 0)]), [outs[i][k] for k in range(5)]) for i in range(nflow)]
+
+    def reset_stream(self):
+        """Drop the window `forward_stream` carries: its next call starts a new stream (len(volumes) - 1 pairs)."""
+        self._stream_prev = None
+        if getattr(self, "_ctx", None) is not None:
+            _lib.check(_lib.lib().eemplus_stream_reset(self._ctx))
 
     # ------------------------------------------------------------------ differentiable route (eemflow_amd/ops.py)
     def _lrelu_conv(self, seq, *xs):

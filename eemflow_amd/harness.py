@@ -78,9 +78,10 @@ def _device_of(model):
 
 
 def stream_plan(n_samples, n):
-    """The calls of a stride-1 walk over a sequence of n_samples samples (n_samples + 1 consecutive windows) by EEMFlow.forward_stream, at
-    most n windows per call: [(first_window, windows, first_sample, flows)].  The first call carries nothing in (its windows - 1 flows); every
-    later one starts at the window the call before carried (as many flows as windows).  Every window is in one call, every sample one flow."""
+    """The calls of a stride-1 walk over a sequence of n_samples samples (n_samples + 1 consecutive windows) by forward_stream (EEMFlow,
+    EEMFlow_cdc, ERAFT), at most n windows per call: [(first_window, windows, first_sample, flows)].  The first call carries nothing in (its
+    windows - 1 flows); every later one starts at the window the call before carried (as many flows as windows).  Every window is in one
+    call, every sample one flow."""
     n = max(2, min(int(n), 16))
     plan, w = [], 0
     while n_samples > 0 and w <= n_samples:
@@ -125,8 +126,8 @@ class TestRaftEvents:
     def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0):
         """The evaluation loop of test_mvsec.py:580-597.  It reads the LAST prediction of every sample only (run_network, :1455): a
         model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call.
-        stream = n > 0 (stride 1, a model with forward_stream - EEMFlow, ERAFT - and a dataset of consecutive windows with get_windows -
-        MvsecEventFlow / _dt4): each sequence is walked window by window, every window read and voxelized once, up to n per call
+        stream = n > 0 (stride 1, a model with forward_stream - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset of consecutive windows with
+        get_windows - MvsecEventFlow / _dt4): each sequence is walked window by window, every window read and voxelized once, up to n per call
         (stream_plan), each call's windows through ONE model.forward_stream - sample i's flow is windows i and i + 1, the encoder runs
         once per window instead of twice.  Same per-sample lines in the same order; frames_in_flight, loader_threads and coalesce do
         not apply.  An ERAFT with warm_start = True is E-RAFT's warm-start evaluation: each sequence starts cold (reset_stream), every
@@ -139,7 +140,8 @@ class TestRaftEvents:
                                  f"MvsecEventFlow_dt4); {type(self.dataset).__name__}'s samples are separate event files (HREM: events1.npz / "
                                  f"events2.npz) that share no window")
             if not hasattr(model, "forward_stream"):
-                raise ValueError(f"stream= needs a model with forward_stream (EEMFlow, ERAFT); {type(model).__name__} has none")
+                raise ValueError(f"stream= needs a model with forward_stream (EEMFlow, ERAFT); {type(model).__name__} has none "
+                                 f"(EEMFlow_cdc has one too)")
         had = getattr(model, "final_only", None)
         if had is not None:
             model.final_only = True

@@ -452,6 +452,29 @@ int eemplus_forward(eemplus_ctx* ctx, const float* events1, const float* events2
 int eemplus_forward_many(eemplus_ctx* ctx, int n, const float* const* events1, const float* const* events2, int in_h, int in_w,
                          const int pad[4], float* const* flow_out, void* stream);
 
+/* EEMFlow+ along a stream of CONSECUTIVE event windows, each window padded and encoded once.  volumes[j] (j < n,
+ * 1..EEM_STREAM_MAX_VOLUMES) are [1][C][in_h][in_w] windows in time order (a HOST array of device pointers); pair p is (window p - 1,
+ * window p), window -1 being the one carried from the previous call: nflow == n with a carried window, n - 1 without (flow_out may then
+ * be NULL for n == 1: the window is encoded and carried, no flow is formed).  Any other nflow is an error.  flow_out[p] is
+ * [5][1][2][in_h][in_w] - flow6 .. flow2 at full resolution, as in eemplus_forward_many.  The encoder and the three poolings run over the n
+ * new windows; pair p's feature_1 is image p of the pyramid and its feature_2 image p + 1.  Pair p is bitwise eemplus_forward_many on the
+ * same pairs in one call, once the kernel forms that follow the encoder's image count (n here, 2 nflow there) are pinned.  Afterwards the
+ * context carries the last window's pyramid levels 2..6 in memory that eemplus_forward / eemplus_forward_many leave alone; the next call
+ * moves it to image 0 with one launch.  A carry made with other weights (eemplus_load_weights) or at another size or pad is refused with
+ * an error: call eemplus_stream_reset.  eemplus_get_stage (batch nflow) and eemplus_level read the last call's pyramid, stream or not.
+ * Replaces: the evaluation loop over consecutive samples at stride 1 (test_mvsec.py:580-597, samples built by loader/MVSEC.py:115-116
+ * from windows i and i + 1), which runs EEMFlow_cdc.forward's encoder (model/EEMFlow/EEMFlow+.py:162-175) on every window twice. */
+int eemplus_forward_stream(eemplus_ctx* ctx, int n, const float* const* volumes, int in_h, int in_w, const int pad[4],
+                           float* const* flow_out, int nflow, void* stream);
+
+/* Drop the carried window: the next eemplus_forward_stream call starts a new stream.
+ * Replaces: the start of a sequence in test_mvsec.py:580-597 (dataset.change_test_sequence). */
+int eemplus_stream_reset(eemplus_ctx* ctx);
+
+/* *out = 1 when a window is carried for the next eemplus_forward_stream call, else 0.
+ * Replaces: nothing in the reference (it has no stream state); the query behind EEMFlow_cdc.forward_stream's bookkeeping. */
+int eemplus_stream_pending(eemplus_ctx* ctx, int* out);
+
 /* Intermediates of the LAST forward: "flow2".."flow6" (low-resolution level flows, incl. the in-place doubling
  * the reference applies to flow3..flow6), "flow_up2".."flow_up5" and "flow_init2".."flow_init5" (cdc_model's upsampled
  * input flow of each level). */
