@@ -10,5 +10,6 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 from .eemflow import EEMFlow            # noqa: F401
+from .metrics import fb_check          # noqa: F401
 from .padder import InputPadder         # noqa: F401
 from .voxelizer import EventSequence, EventSequenceToVoxelGrid_Pytorch   # noqa: F401

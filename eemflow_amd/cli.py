@@ -71,6 +71,13 @@ def build_parser():
         q.add_argument('--coalesce', default=1, type=int,
                        help='evaluation, EEMFlow: samples voxelized by one launch sequence and handed to one forward_many call (not in the '
                             'reference; 10 with --frames_in_flight 2 suits one MI355X); the volumes then stay raw and pconv1_1 normalises them')
+        if not train:
+            q.add_argument('--stream', default=0, type=int,
+                           help='evaluation: walk each sequence window by window, up to N windows per forward_stream call (not in the reference; '
+                                'needs a dataset of consecutive windows - HREM samples are separate files and are refused)')
+            q.add_argument('--fb_check', nargs=2, type=float, default=None, metavar=('A1', 'A2'),
+                           help='evaluation, EEMFlow with --stream: run the stream bidirectionally and add the forward-backward consistency '
+                                'share and the AEE over the consistent pixels to every line (threshold A1 * (|fw| + |bw|) + A2)')
     common(sub.add_parser('train', help='train_EEMFlow_HREM.py'), True)
     common(sub.add_parser('test', help='test_EEMFlow_HREM.py'), False)
     return p
@@ -177,6 +184,8 @@ def train(args):
 
 def test(args):
     from . import harness
+    if args.fb_check is not None and not args.stream:
+        raise SystemExit("--fb_check needs --stream N (the backward flow comes from the bidirectional stream)")
     from .hrem import HREMEventFlow
     config = load_config(args.config)
     model = build_model(args.model_name, config, training=False)
@@ -195,8 +204,13 @@ def test(args):
     model = model.to(dev)
     sequences = [args.test_sequence] if args.test_sequence else list(test_set.nori_list.keys())
     ev = harness.TestRaftEvents(test_set, tuple(config["val_img_size"]), logger=logger)
+    extra = {}
+    if args.stream:
+        extra["stream"] = args.stream
+    if args.fb_check is not None:
+        extra["fb_check"] = tuple(args.fb_check)
     return ev.test_multi_sequence(model, start_epoch + 1, sequence_list=sequences, stride=1, frames_in_flight=args.frames_in_flight,
-                                  loader_threads=args.loader_threads, coalesce=coalesce)
+                                  loader_threads=args.loader_threads, coalesce=coalesce, **extra)
 
 
 def main(argv=None):

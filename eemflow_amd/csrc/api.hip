@@ -328,14 +328,16 @@ extern "C" int eemflow_set_frames_in_flight(eemflow_ctx* c, int n) {
 }
 
 // A stream call (eemflow_forward_stream): `batch` flows of consecutive windows, whose nframes new windows are e1[0 .. nframes-1]
+// (bidir: `batch` counts both directions - flows [0, batch / 2) older -> newer, [batch / 2, batch) newer -> older)
 struct StreamCall {
-    int carry_in, slot_in, slot_out;
+    int carry_in, slot_in, slot_out, bidir;
 };
 
 // One forward of `batch` samples.  nframes == 0: events1 / events2 / flow are contiguous [batch, ...] tensors (e1[0], e2[0], out[0]).
 // nframes == batch >= 1 (eemflow_forward_many): every sample is its own single-frame buffer triple {e1[i], e2[i], out[i]}; the two
 // launches that touch caller memory find them through the io table's per-frame triples, everything between is the batch-n chain.
 // sc != NULL (eemflow_forward_stream): nframes windows e1[i] (e2[i] NULL) in the triples' first slots, flow i < batch in the third
+// (a bidirectional call has more flows than windows: max(nframes, batch) triples, the arrays NULL-padded to that length)
 static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, const float* const* e2, float* const* out, int batch,
                           int in_h, int in_w, int out_h, int out_w, void* stream, const StreamCall* sc = nullptr) {
     EEM_HIP_CHECK(hipSetDevice(c->device));
@@ -344,15 +346,16 @@ static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, c
     int rc = compute_shape(c, batch, in_h, in_w, out_h, out_w, &s, sc ? nframes : -1);
     if (rc != EEM_OK) return rc;
     if (sc) {
-        s.stream = 1; s.carry_in = sc->carry_in; s.slot_in = sc->slot_in; s.slot_out = sc->slot_out;
+        s.stream = 1; s.carry_in = sc->carry_in; s.slot_in = sc->slot_in; s.slot_out = sc->slot_out; s.bidir = sc->bidir;
         const unsigned long moved = g_realloc_events;
         if ((rc = ensure(c->carry, 2 * 112 * (size_t)s.gh * s.gw)) != EEM_OK) return rc;
         if (g_realloc_events != moved) drop_graph(c);                 // the cached stream graphs point into the carry slots
     }
-    const int nptr = nframes > 0 ? 3 * nframes : 3;
+    const int ntab = sc && batch > nframes ? batch : nframes;        // triples of the per-frame table
+    const int nptr = ntab > 0 ? 3 * ntab : 3;
     const void* want[3 * EEM_MAX_COALESCE];
     uintptr_t bits = 0;
-    for (int i = 0; i < (nframes > 0 ? nframes : 1); ++i) {
+    for (int i = 0; i < (ntab > 0 ? ntab : 1); ++i) {
         want[3 * i] = e1[i]; want[3 * i + 1] = e2[i]; want[3 * i + 2] = out[i];
         bits |= (uintptr_t)e1[i] | (uintptr_t)e2[i] | (uintptr_t)out[i];
     }
@@ -362,7 +365,7 @@ static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, c
         bool same = c->io_host_n == nptr && c->io_stream == stream;
         for (int i = 0; same && i < nptr; ++i) same = c->io_host[i] == want[i];
         if (same) return EEM_OK;
-        const int r = nframes > 0 ? io_table_many_launch(c->io_table, nframes, e1, e2, out, st)
+        const int r = nframes > 0 ? io_table_many_launch(c->io_table, ntab, e1, e2, out, st)
                                   : io_table_launch(c->io_table, e1[0], e2[0], out[0], st);
         if (r != EEM_OK) return r;
         for (int i = 0; i < nptr; ++i) c->io_host[i] = want[i];
@@ -390,7 +393,7 @@ static int forward_common(eemflow_ctx* c, int nframes, const float* const* e1, c
     }
     eemflow_ctx::Key key = {batch, in_h, in_w, out_h, out_w, {c->pad[0], c->pad[1], c->pad[2], c->pad[3]}, aligned, nframes,
                             c->deferred_norm ? 1 : 0};
-    if (sc) { key.stream_nvol = nframes; key.stream_carry = sc->carry_in; key.stream_slot = sc->slot_out; }
+    if (sc) { key.stream_nvol = nframes; key.stream_carry = sc->carry_in; key.stream_slot = sc->slot_out; key.stream_bidir = sc->bidir; }
     eemflow_ctx::GraphEntry* ent = nullptr;
     for (eemflow_ctx::GraphEntry& g : c->graphs)
         if (g.key == key) ent = &g;
@@ -483,42 +486,56 @@ extern "C" int eemflow_forward_many(eemflow_ctx* c, int nframes, const float* co
 // windows i and i + 1): every window is encoded ONCE - the call's nvol new windows as one encoder batch - and the last one's pooled maps
 // are carried to the next call, where they stand in for the older window of its first pair.  Flow p is bitwise what eemflow_forward_many
 // gives for that pair (same kernels; the carried maps are the values the correlation read from the partial sums).
-extern "C" int eemflow_forward_stream(eemflow_ctx* c, int nvol, const float* const* volumes, float* const* flow_out, int nflow, int in_h,
-                                      int in_w, int out_h, int out_w, void* stream) {
-    EEM_REQUIRE(c && volumes, "eemflow_forward_stream: NULL argument");
-    EEM_REQUIRE(nvol >= 1 && nvol <= EEM_STREAM_MAX_VOLUMES, "eemflow_forward_stream: 1..%d volumes per call; got %d", EEM_STREAM_MAX_VOLUMES, nvol);
-    EEM_REQUIRE(c->weights_loaded, "eemflow_forward_stream: no weights loaded");
-    EEM_REQUIRE(c->have_pad, "eemflow_forward_stream: call eemflow_set_image_size first");
-    EEM_REQUIRE(in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, "eemflow_forward_stream: bad sizes");
-    EEM_REQUIRE(!c->enc0_generic, "eemflow_forward_stream: built for the 5-bin first layer (n_first_channels == 5)");
+// bidir (eemflow_forward_stream_bidir): the tail runs over 2 * nflow pairs, the second half with the two windows'
+// roles exchanged (the pooled maps of a window do not depend on which side of a pair it sits on), flows [nflow, 2 nflow) into flow_bw.
+static int forward_stream_impl(eemflow_ctx* c, int nvol, const float* const* volumes, float* const* flow_out, float* const* flow_bw, int bidir,
+                               int nflow, int in_h, int in_w, int out_h, int out_w, void* stream) {
+    const int maxvol = bidir ? EEM_STREAM_BIDIR_MAX_VOLUMES : EEM_STREAM_MAX_VOLUMES;
+    const char* fn = bidir ? "eemflow_forward_stream_bidir" : "eemflow_forward_stream";
+    EEM_REQUIRE(c && volumes, "%s: NULL argument", fn);
+    EEM_REQUIRE(nvol >= 1 && nvol <= maxvol, "%s: 1..%d volumes per call; got %d", fn, maxvol, nvol);
+    EEM_REQUIRE(c->weights_loaded, "%s: no weights loaded", fn);
+    EEM_REQUIRE(c->have_pad, "%s: call eemflow_set_image_size first", fn);
+    EEM_REQUIRE(in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, "%s: bad sizes", fn);
+    EEM_REQUIRE(!c->enc0_generic, "%s: built for the 5-bin first layer (n_first_channels == 5)", fn);
     if (c->stream_pending) {
-        EEM_REQUIRE(c->stream_wver == c->weights_version, "eemflow_forward_stream: the weights changed since the carried window was encoded; "
-                    "call eemflow_stream_reset to start a new stream");
+        EEM_REQUIRE(c->stream_wver == c->weights_version, "%s: the weights changed since the carried window was encoded; "
+                    "call eemflow_stream_reset to start a new stream", fn);
         EEM_REQUIRE(c->stream_h == in_h && c->stream_w == in_w && memcmp(c->stream_pad, c->pad, sizeof(c->pad)) == 0,
-                    "eemflow_forward_stream: the carried window is %dx%d, this call's volumes are %dx%d (or the padding changed); "
-                    "call eemflow_stream_reset to start a new stream", c->stream_h, c->stream_w, in_h, in_w);
+                    "%s: the carried window is %dx%d, this call's volumes are %dx%d (or the padding changed); "
+                    "call eemflow_stream_reset to start a new stream", fn, c->stream_h, c->stream_w, in_h, in_w);
     }
     const int want = c->stream_pending ? nvol : nvol - 1;
-    EEM_REQUIRE(nflow == want, "eemflow_forward_stream: %d volumes %s give %d flows; nflow = %d", nvol,
+    EEM_REQUIRE(nflow == want, "%s: %d volumes %s give %d flows; nflow = %d", fn, nvol,
                 c->stream_pending ? "after the carried window" : "with no carried window", want, nflow);
-    EEM_REQUIRE(nflow == 0 || flow_out, "eemflow_forward_stream: flow_out is NULL");
+    EEM_REQUIRE(nflow == 0 || flow_out, "%s: %s is NULL", fn, bidir ? "flow_fw_out" : "flow_out");
+    EEM_REQUIRE(nflow == 0 || !bidir || flow_bw, "%s: flow_bw_out is NULL", fn);
     for (int i = 0; i < nvol; ++i) {
-        EEM_REQUIRE(volumes[i], "eemflow_forward_stream: volume %d is NULL", i);
-        EEM_REQUIRE(((uintptr_t)volumes[i] & 15) == 0, "eemflow_forward_stream: volume %d: buffers must be 16-byte aligned (torch allocations are)", i);
+        EEM_REQUIRE(volumes[i], "%s: volume %d is NULL", fn, i);
+        EEM_REQUIRE(((uintptr_t)volumes[i] & 15) == 0, "%s: volume %d: buffers must be 16-byte aligned (torch allocations are)", fn, i);
     }
-    for (int i = 0; i < nflow; ++i) {
-        EEM_REQUIRE(flow_out[i], "eemflow_forward_stream: flow %d is NULL", i);
-        EEM_REQUIRE(((uintptr_t)flow_out[i] & 15) == 0, "eemflow_forward_stream: flow %d: buffers must be 16-byte aligned (torch allocations are)", i);
-    }
+    const float* vols[EEM_MAX_COALESCE] = {};
     const float* none[EEM_MAX_COALESCE] = {};
     float* outs[EEM_MAX_COALESCE] = {};
-    for (int i = 0; i < nflow; ++i) outs[i] = flow_out[i];
+    for (int i = 0; i < nvol; ++i) vols[i] = volumes[i];
+    for (int i = 0; i < nflow; ++i) {
+        outs[i] = flow_out[i];
+        if (bidir) outs[nflow + i] = flow_bw[i];
+    }
+    const int nout = bidir ? 2 * nflow : nflow;                  // (<= EEM_MAX_COALESCE: a bidirectional call takes at most 8 volumes)
+    for (int i = 0; i < nout; ++i) {
+        const char* dir = !bidir ? "flow" : i < nflow ? "forward flow" : "backward flow";
+        const int k = i < nflow ? i : i - nflow;
+        EEM_REQUIRE(outs[i], "%s: %s %d is NULL", fn, dir, k);
+        EEM_REQUIRE(((uintptr_t)outs[i] & 15) == 0, "%s: %s %d: buffers must be 16-byte aligned (torch allocations are)", fn, dir, k);
+    }
     StreamCall sc;
+    sc.bidir = bidir;
     sc.carry_in = c->stream_pending ? 1 : 0;
     sc.slot_in = c->stream_slot;
     sc.slot_out = c->stream_pending ? 1 - c->stream_slot : 0;
     c->stream_pending = false;                                   // (a failed call leaves no carry behind)
-    const int rc = forward_common(c, nvol, volumes, none, outs, nflow, in_h, in_w, out_h, out_w, stream, &sc);
+    const int rc = forward_common(c, nvol, vols, none, outs, nout, in_h, in_w, out_h, out_w, stream, &sc);
     c->have_last = false;                                        // the workspace holds windows, not a forward's pairs (eemflow_get_stage)
     if (rc != EEM_OK) return rc;
     c->stream_pending = true;
@@ -527,6 +544,18 @@ extern "C" int eemflow_forward_stream(eemflow_ctx* c, int nvol, const float* con
     c->stream_h = in_h; c->stream_w = in_w;
     memcpy(c->stream_pad, c->pad, sizeof(c->pad));
     return EEM_OK;
+}
+
+extern "C" int eemflow_forward_stream(eemflow_ctx* c, int nvol, const float* const* volumes, float* const* flow_out, int nflow, int in_h,
+                                      int in_w, int out_h, int out_w, void* stream) {
+    return forward_stream_impl(c, nvol, volumes, flow_out, nullptr, 0, nflow, in_h, in_w, out_h, out_w, stream);
+}
+
+// Both directions of every pair of the stream: the backward flow (newer -> older window) reads the same pooled maps as the forward one,
+// so it costs the tail alone - the encoder still runs once per new window.
+extern "C" int eemflow_forward_stream_bidir(eemflow_ctx* c, int nvol, const float* const* volumes, float* const* flow_fw_out,
+                                            float* const* flow_bw_out, int nflow, int in_h, int in_w, int out_h, int out_w, void* stream) {
+    return forward_stream_impl(c, nvol, volumes, flow_fw_out, flow_bw_out, 1, nflow, in_h, in_w, out_h, out_w, stream);
 }
 
 extern "C" int eemflow_stream_reset(eemflow_ctx* c) {

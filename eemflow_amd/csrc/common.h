@@ -362,11 +362,14 @@ int tail_head_launch(const TailHeadArgs& a, const int* taps_host, hipStream_t st
 // image i2 - 1 with image i2 = b + i2_off (i2_off 1: the pairs (0, 1), (1, 2), ...; 0: pair 0 starts at the carried window).  An image
 // index below 0 is the carried window, read from `carry` (finished maps [c][gh][gw]: rows 1, scale 1 - the value the pooled-map role
 // wrote, bitwise).  The pooled-map role writes image `pool_img` alone, [c][gh][gw] into base.pool_out[k]: the next call's carry.
+// nfw: pairs b < nfw run in that (forward) direction; nfw == base.batch for eemflow_forward_stream.  A bidirectional call
+// (eemflow_forward_stream_bidir) has base.batch == 2 * nfw: pair nfw + q is pair q with the two windows' roles exchanged.
 struct TailHeadStreamArgs {
     TailHeadArgs base;
     PooledSrc carry[3];
     int i2_off;
     int pool_img;
+    int nfw;
 };
 int tail_head_stream_launch(const TailHeadStreamArgs& a, const int* taps_host, hipStream_t stream);
 struct TailUpArgs {

@@ -47,6 +47,8 @@ struct Shape {
     // stream call: `batch` pairs of consecutive windows; carry_in: pair 0 starts at the carried window, read from carry slot
     // `slot_in`; the last window's finished maps go to slot `slot_out`
     int stream = 0, carry_in = 0, slot_in = 0, slot_out = 0;
+    // bidirectional stream call (eemflow_forward_stream_bidir): `batch` = 2 x the pairs, the second half with the windows exchanged
+    int bidir = 0;
 };
 
 struct eemflow_ctx {
@@ -198,11 +200,12 @@ struct eemflow_ctx {
         int deferred_norm;
         int stream_nvol = 0;                             // eemflow_forward_stream: windows per call (0: a forward), carry present, carry slot
         int stream_carry = 0, stream_slot = 0;           // written (the slot read is the other one)
+        int stream_bidir = 0;                            // eemflow_forward_stream_bidir: both directions of every pair
         bool operator==(const Key& o) const {
             return batch == o.batch && in_h == o.in_h && in_w == o.in_w && out_h == o.out_h && out_w == o.out_w &&
                    pad[0] == o.pad[0] && pad[1] == o.pad[1] && pad[2] == o.pad[2] && pad[3] == o.pad[3] && aligned16 == o.aligned16 &&
                    io_frames == o.io_frames && deferred_norm == o.deferred_norm && stream_nvol == o.stream_nvol &&
-                   stream_carry == o.stream_carry && stream_slot == o.stream_slot;
+                   stream_carry == o.stream_carry && stream_slot == o.stream_slot && stream_bidir == o.stream_bidir;
         }
     };
     struct GraphEntry {

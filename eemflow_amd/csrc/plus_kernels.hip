@@ -4,6 +4,7 @@
 // nw + ne + sw + se, so the coordinate and weight arithmetic follows ATen's CPU grid sampler operation by
 // operation (separate multiplies and adds, same association).
 #include "plus_kernels.h"
+#include "warp_px.h"
 
 namespace {
 
@@ -12,56 +13,18 @@ inline unsigned nblocks(long n) { return (unsigned)((n + 255) / 256); }
 // mode 0: align_corners=True (EEMFlow_cdc.warp); 1: align_corners=False (torch_warp);
 // 2: align_corners=False + `grid_sample(ones) >= 1` mask (WarpingLayer_no_div)
 constexpr int kWarpCh = 4;
-// one pixel of a warp: the flow (fx, fy) of pixel p, the channels [ch0, ch0 + kWarpCh) of x
+// one pixel of a warp: the flow (fx, fy) of pixel p, the channels [ch0, ch0 + kWarpCh) of x (taps, gather and sum: warp_px.h)
 __device__ __forceinline__ void warp_px(const float* __restrict__ x, float fx, float fy, float* __restrict__ out, int out_ctotal, int out_coff,
                                         int b, int c, int h, int w, int p, int mode, int ch0) {
     const int hw = h * w;
-    const int py = p / w, px = p - py * w;
-    const float vx = (float)px + fx;
-    const float vy = (float)py + fy;
-    const float xn = 2.0f * vx / (float)max(w - 1, 1) - 1.0f;
-    const float yn = 2.0f * vy / (float)max(h - 1, 1) - 1.0f;
-    float ix, iy;
-    if (mode == 0) {
-        ix = (xn + 1.f) * ((float)(w - 1) / 2.f);
-        iy = (yn + 1.f) * ((float)(h - 1) / 2.f);
-    } else {
-        ix = (xn + 1.f) * ((float)w / 2.f) - 0.5f;
-        iy = (yn + 1.f) * ((float)h / 2.f) - 0.5f;
-    }
-    const float xw = floorf(ix), yn0 = floorf(iy);
-    const float wgt_w = ix - xw, wgt_e = 1.f - wgt_w, wgt_n = iy - yn0, wgt_s = 1.f - wgt_n;
-    const float nw = wgt_s * wgt_e, ne = wgt_s * wgt_w, sw = wgt_n * wgt_e, se = wgt_n * wgt_w;
-    // the float -> int conversion must not overflow for wild flows
-    const float cx = fminf(fmaxf(xw, -2.f), (float)w + 1.f), cy = fminf(fmaxf(yn0, -2.f), (float)h + 1.f);
-    const int x0 = (int)cx, y0 = (int)cy;
-    const bool in_w = x0 >= 0 && x0 < w, in_e = x0 + 1 >= 0 && x0 + 1 < w;
-    const bool in_n = y0 >= 0 && y0 < h, in_s = y0 + 1 >= 0 && y0 + 1 < h;
-    float m = 1.f;
-    if (mode == 2) {
-        const float ones = (((in_n && in_w ? 1.f : 0.f) * nw + (in_n && in_e ? 1.f : 0.f) * ne) + (in_s && in_w ? 1.f : 0.f) * sw) +
-                           (in_s && in_e ? 1.f : 0.f) * se;
-        m = ones >= 1.0f ? 1.f : 0.f;
-    }
-    const int o_nw = (in_n && in_w) ? y0 * w + x0 : -1, o_ne = (in_n && in_e) ? y0 * w + x0 + 1 : -1;
-    const int o_sw = (in_s && in_w) ? (y0 + 1) * w + x0 : -1, o_se = (in_s && in_e) ? (y0 + 1) * w + x0 + 1 : -1;
+    const WarpTaps t = warp_taps(fx, fy, h, w, p, mode);
     float v[kWarpCh][4];
 #pragma unroll
-    for (int i = 0; i < kWarpCh; ++i) {
-        const float* s = x + ((size_t)b * c + min(ch0 + i, c - 1)) * hw;
-        // (unconditional loads from clamped offsets, the bounds applied to the values: a load in one arm of a lane-dependent
-        // conditional is a branch followed by s_waitcnt vmcnt(0) - sixteen dependent round trips instead of one)
-        const float a0 = s[max(o_nw, 0)], a1 = s[max(o_ne, 0)], a2 = s[max(o_sw, 0)], a3 = s[max(o_se, 0)];
-        v[i][0] = o_nw >= 0 ? a0 : 0.f;
-        v[i][1] = o_ne >= 0 ? a1 : 0.f;
-        v[i][2] = o_sw >= 0 ? a2 : 0.f;
-        v[i][3] = o_se >= 0 ? a3 : 0.f;
-    }
+    for (int i = 0; i < kWarpCh; ++i) warp_gather(x + ((size_t)b * c + min(ch0 + i, c - 1)) * hw, t, v[i]);
 #pragma unroll
     for (int i = 0; i < kWarpCh; ++i) {
         if (ch0 + i >= c) break;
-        const float r = ((v[i][0] * nw + v[i][1] * ne) + v[i][2] * sw) + v[i][3] * se;
-        out[((size_t)b * out_ctotal + out_coff + ch0 + i) * hw + p] = r * m;
+        out[((size_t)b * out_ctotal + out_coff + ch0 + i) * hw + p] = warp_sum(v[i], t) * t.m;
     }
 }
 

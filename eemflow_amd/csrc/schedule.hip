@@ -490,6 +490,7 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
             ha.batch = s.batch; ha.gh = s.gh; ha.gw = s.gw; ha.ntaps = kNTaps; ha.cat_ctotal = kDecIn;
             sa.i2_off = s.carry_in ? 0 : 1;
             sa.pool_img = s.nimg - 1;
+            sa.nfw = s.bidir ? s.batch / 2 : s.batch;             // bidirectional: pairs nfw .. 2 nfw - 1 are the first nfw, roles exchanged
             const double fl = 2.0 * s.batch * g * (kNTaps * (16 + 32 + 64) + 16.0 * 9 * (16 + 32 + 64));
             rc = hk.run("tail head: stream pool+corr53+rconv", fl, 4.0 * (fin_elems + 3.0 * s.batch * g * kDecIn),
                         [&](hipStream_t st) { return tail_head_stream_launch(sa, kTaps53, st); });

@@ -35,9 +35,10 @@ __device__ __forceinline__ float pooled_load(const PooledSrc& s, const float* ch
 // by blockIdx.y, so everything a block needs from the launch arguments - its stage's source, its tap - is ONE batch of scalar
 // loads issued at its first instruction, and its operand loads are the second and last round trip before the stores (see
 // tail_conv_kernel in tail.hip for what a round trip costs beside other frames' kernels).
-// STREAM (tail_head_stream_kernel): the pair's first image is image b + i2_off - 1 of the call, or - below 0 - the carried window
+// STREAM (tail_head_stream_kernel): the pair's first image is image b + i2_off - 1 of the call, or - below 0 - the carried window;
+// pairs b >= nfw (a bidirectional call) are pairs b - nfw with the two windows' roles exchanged
 template <int CG, int ROWS, bool STREAM>
-__device__ __forceinline__ void rconv_role(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int k, int blk, f32x4 (*part)[64]) {
+__device__ __forceinline__ void rconv_role(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int nfw, int k, int blk, f32x4 (*part)[64]) {
     // one block = 16 pixels x 16 couts of one (scale, sample); wave t = filter tap t (see tail_conv_kernel)
     const int lane = threadIdx.x & 63;
     const int t = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -58,7 +59,7 @@ __device__ __forceinline__ void rconv_role(const TailHeadArgs& a, const PooledSr
     const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
     const bool valid = pvalid && yy >= 0 && yy < gh && xx >= 0 && xx < gw;
     const float* wp = rw + (size_t)t * CG * 64 + lane;
-    const int i1 = STREAM ? b + i2_off - 1 : b;
+    const int i1 = !STREAM ? b : b < nfw ? b + i2_off - 1 : b - nfw + i2_off;   // (a backward pair starts at its newer window)
     const bool from_carry = STREAM && i1 < 0;
     const PooledSrc csrc = STREAM ? carry[k] : src;                         // (values, not references: no copy of the arguments in scratch)
     const float* img = from_carry ? csrc.base : src.base + (size_t)i1 * src.nstride;   // events1 half: image b
@@ -98,7 +99,7 @@ __device__ __forceinline__ void rconv_role(const TailHeadArgs& a, const PooledSr
 // a wave = one (sample, tap, 16-pixel tile): four adjacent lanes share one output and split its channels (see corr_kernel);
 // NC = channels per lane (cin / 4): all 2 * NC * ROWS loads of a lane are issued before the first product
 template <int NC, int ROWS, bool STREAM>
-__device__ __forceinline__ void corr_role(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int k) {
+__device__ __forceinline__ void corr_role(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int nfw, int k) {
     const PooledSrc src = a.src[k];
     const int tap = a.tap[blockIdx.y];
     float* cat = a.cat[k];
@@ -118,26 +119,31 @@ __device__ __forceinline__ void corr_role(const TailHeadArgs& a, const PooledSrc
     const int yy = y + tap / 9 - 4, xx = x + tap % 9 - 4;
     float s = 0.f;
     if (live && yy >= 0 && yy < gh && xx >= 0 && xx < gw) {
-        // image 2 of pair b: the events2 half of a forward, or the window after image 1 in a stream (image 1 below 0: the carry)
-        const int n2 = STREAM ? b + i2_off : batch + b;
-        const bool from_carry = STREAM && n2 == 0;
+        // image 2 of pair b: the events2 half of a forward, or the window after image 1 in a stream (image 1 below 0: the carry);
+        // a stream's backward pair b >= nfw is forward pair b - nfw with the two windows exchanged (image 2 below 0: the carry)
+        const bool bwd = STREAM && b >= nfw;
+        const int newer = STREAM ? (bwd ? b - nfw : b) + i2_off : batch + b;
+        const int n1 = !STREAM ? b : bwd ? newer : newer - 1;
+        const int n2 = bwd ? newer - 1 : newer;
+        const bool carry1 = STREAM && n1 < 0, carry2 = STREAM && n2 < 0;
         const PooledSrc csrc = STREAM ? carry[k] : src;
-        const float* i1 = from_carry ? csrc.base : src.base + (size_t)(STREAM ? n2 - 1 : b) * src.nstride;
-        const float* i2 = src.base + (size_t)n2 * src.nstride;
+        const float* i1 = carry1 ? csrc.base : src.base + (size_t)n1 * src.nstride;
+        const float* i2 = carry2 ? csrc.base : src.base + (size_t)n2 * src.nstride;
         if (cin == NC * 4) {
             float u[NC], v[NC];
 #pragma unroll
             for (int i = 0; i < NC; ++i) {
-                u[i] = from_carry ? pooled_load<1>(csrc, i1 + (size_t)(sub + 4 * i) * csrc.cstride, y, x)
-                                  : pooled_load<ROWS>(src, i1 + (size_t)(sub + 4 * i) * src.cstride, y, x);
-                v[i] = pooled_load<ROWS>(src, i2 + (size_t)(sub + 4 * i) * src.cstride, yy, xx);
+                u[i] = carry1 ? pooled_load<1>(csrc, i1 + (size_t)(sub + 4 * i) * csrc.cstride, y, x)
+                              : pooled_load<ROWS>(src, i1 + (size_t)(sub + 4 * i) * src.cstride, y, x);
+                v[i] = carry2 ? pooled_load<1>(csrc, i2 + (size_t)(sub + 4 * i) * csrc.cstride, yy, xx)
+                              : pooled_load<ROWS>(src, i2 + (size_t)(sub + 4 * i) * src.cstride, yy, xx);
             }
 #pragma unroll
             for (int i = 0; i < NC; ++i) s = fmaf(u[i], v[i], s);
         } else {
             for (int c = sub; c < cin; c += 4)
-                s = fmaf(from_carry ? pooled_load<1>(csrc, i1 + (size_t)c * csrc.cstride, y, x) : pooled_load<0>(src, i1 + (size_t)c * src.cstride, y, x),
-                         pooled_load<0>(src, i2 + (size_t)c * src.cstride, yy, xx), s);
+                s = fmaf(carry1 ? pooled_load<1>(csrc, i1 + (size_t)c * csrc.cstride, y, x) : pooled_load<0>(src, i1 + (size_t)c * src.cstride, y, x),
+                         carry2 ? pooled_load<1>(csrc, i2 + (size_t)c * csrc.cstride, yy, xx) : pooled_load<0>(src, i2 + (size_t)c * src.cstride, yy, xx), s);
         }
     }
     s = dpp_add<0xB1>(s);
@@ -146,22 +152,22 @@ __device__ __forceinline__ void corr_role(const TailHeadArgs& a, const PooledSrc
 }
 
 template <bool STREAM>
-__device__ __forceinline__ void tail_head_body(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int pool_img) {
+__device__ __forceinline__ void tail_head_body(const TailHeadArgs& a, const PooledSrc* carry, int i2_off, int nfw, int pool_img) {
     __shared__ f32x4 part[9][64];
     const int role = blockIdx.z;
     const int blk = blockIdx.y * a.grid_x + blockIdx.x;
     if (role < 3) {
         const int rows = a.src[role].rows;                                // 16, 32, 64 input channels (EEMFlow.py:96-98)
-        if (role == 0) { if (rows == 4) rconv_role<4, 4, STREAM>(a, carry, i2_off, 0, blk, part); else if (rows == 1) rconv_role<4, 1, STREAM>(a, carry, i2_off, 0, blk, part); else rconv_role<4, 0, STREAM>(a, carry, i2_off, 0, blk, part); }
-        else if (role == 1) { if (rows == 2) rconv_role<8, 2, STREAM>(a, carry, i2_off, 1, blk, part); else if (rows == 1) rconv_role<8, 1, STREAM>(a, carry, i2_off, 1, blk, part); else rconv_role<8, 0, STREAM>(a, carry, i2_off, 1, blk, part); }
-        else { if (rows == 1) rconv_role<16, 1, STREAM>(a, carry, i2_off, 2, blk, part); else rconv_role<16, 0, STREAM>(a, carry, i2_off, 2, blk, part); }
+        if (role == 0) { if (rows == 4) rconv_role<4, 4, STREAM>(a, carry, i2_off, nfw, 0, blk, part); else if (rows == 1) rconv_role<4, 1, STREAM>(a, carry, i2_off, nfw, 0, blk, part); else rconv_role<4, 0, STREAM>(a, carry, i2_off, nfw, 0, blk, part); }
+        else if (role == 1) { if (rows == 2) rconv_role<8, 2, STREAM>(a, carry, i2_off, nfw, 1, blk, part); else if (rows == 1) rconv_role<8, 1, STREAM>(a, carry, i2_off, nfw, 1, blk, part); else rconv_role<8, 0, STREAM>(a, carry, i2_off, nfw, 1, blk, part); }
+        else { if (rows == 1) rconv_role<16, 1, STREAM>(a, carry, i2_off, nfw, 2, blk, part); else rconv_role<16, 0, STREAM>(a, carry, i2_off, nfw, 2, blk, part); }
         return;
     }
     if (role < 6) {
         const int k = role - 3, rows = a.src[k].rows;
-        if (k == 0) { if (rows == 4) corr_role<4, 4, STREAM>(a, carry, i2_off, 0); else if (rows == 1) corr_role<4, 1, STREAM>(a, carry, i2_off, 0); else corr_role<4, 0, STREAM>(a, carry, i2_off, 0); }
-        else if (k == 1) { if (rows == 2) corr_role<8, 2, STREAM>(a, carry, i2_off, 1); else if (rows == 1) corr_role<8, 1, STREAM>(a, carry, i2_off, 1); else corr_role<8, 0, STREAM>(a, carry, i2_off, 1); }
-        else { if (rows == 1) corr_role<16, 1, STREAM>(a, carry, i2_off, 2); else corr_role<16, 0, STREAM>(a, carry, i2_off, 2); }
+        if (k == 0) { if (rows == 4) corr_role<4, 4, STREAM>(a, carry, i2_off, nfw, 0); else if (rows == 1) corr_role<4, 1, STREAM>(a, carry, i2_off, nfw, 0); else corr_role<4, 0, STREAM>(a, carry, i2_off, nfw, 0); }
+        else if (k == 1) { if (rows == 2) corr_role<8, 2, STREAM>(a, carry, i2_off, nfw, 1); else if (rows == 1) corr_role<8, 1, STREAM>(a, carry, i2_off, nfw, 1); else corr_role<8, 0, STREAM>(a, carry, i2_off, nfw, 1); }
+        else { if (rows == 1) corr_role<16, 1, STREAM>(a, carry, i2_off, nfw, 2); else corr_role<16, 0, STREAM>(a, carry, i2_off, nfw, 2); }
         return;
     }
     // pooled maps [2B][C][gh][gw] as a side output (STREAM: image pool_img alone, [C][gh][gw])
@@ -185,10 +191,10 @@ __device__ __forceinline__ void tail_head_body(const TailHeadArgs& a, const Pool
     }
 }
 
-__global__ __launch_bounds__(576) void tail_head_kernel(TailHeadArgs a) { tail_head_body<false>(a, nullptr, 0, 0); }
+__global__ __launch_bounds__(576) void tail_head_kernel(TailHeadArgs a) { tail_head_body<false>(a, nullptr, 0, 0, 0); }
 
 __global__ __launch_bounds__(576) void tail_head_stream_kernel(TailHeadStreamArgs a) {
-    tail_head_body<true>(a.base, a.carry, a.i2_off, a.pool_img);
+    tail_head_body<true>(a.base, a.carry, a.i2_off, a.nfw, a.pool_img);
 }
 
 // ------------------------------------------------------------------------------------------------ conv7 + out_conv + upsample
@@ -309,6 +315,7 @@ int tail_head_stream_launch(const TailHeadStreamArgs& a0, const int* taps_host, 
     TailHeadStreamArgs a = a0;
     EEM_REQUIRE(a.i2_off == 0 || a.i2_off == 1, "tail_head_stream_launch: i2_off=%d", a.i2_off);
     EEM_REQUIRE(a.pool_img >= 0 && a.base.batch >= 0, "tail_head_stream_launch: pool_img=%d batch=%d", a.pool_img, a.base.batch);
+    EEM_REQUIRE(a.nfw == a.base.batch || 2 * a.nfw == a.base.batch, "tail_head_stream_launch: nfw=%d batch=%d", a.nfw, a.base.batch);
     for (int k = 0; k < 3; ++k) {
         EEM_REQUIRE(a.base.pool_out[k] != nullptr, "tail_head_stream_launch: stage %d has no carry output", k);
         EEM_REQUIRE(a.i2_off == 1 || (a.carry[k].base != nullptr && a.carry[k].rows == 1), "tail_head_stream_launch: stage %d: carried maps missing", k);

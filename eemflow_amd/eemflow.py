@@ -242,8 +242,9 @@ class EEMFlow(nn.Module):
         return [((frames[i][0], frames[i][1]), [flows[i]]) for i in range(n)]
 
     MAX_STREAM = 16                     # EEM_STREAM_MAX_VOLUMES of include/eemflow_hip.h
+    MAX_STREAM_BIDIR = 8                # EEM_STREAM_BIDIR_MAX_VOLUMES
 
-    def forward_stream(self, volumes, deferred_norm=False):
+    def forward_stream(self, volumes, deferred_norm=False, bidirectional=False, fb_check=None):
         """Flow along a stream of CONSECUTIVE event windows, each window encoded once (the MVSEC evaluation walks a sequence this way:
         sample i is windows i and i + 1, loader/MVSEC.py:115-116).  `volumes` are 1..16 [1, C, H, W] tensors in time order, on one
         device with one shape.  Returns one `((events1, events2), [flow])` per pair of neighbouring windows - flow [1, 2, H, W] (the
@@ -251,10 +252,23 @@ class EEMFlow(nn.Module):
         call, whose first pair starts at it: a call after a carried window returns len(volumes) pairs (events1 of the first is the
         previous call's last tensor), otherwise len(volumes) - 1.  `reset_stream()` drops the carried window; `change_imagesize` to a
         new size does too.  After a weight change (optimizer step, load_state_dict) the next call raises until `reset_stream()`.
-        Inference only (no autograd graph is recorded).  deferred_norm: as in `forward_many`."""
+        Inference only (no autograd graph is recorded).  deferred_norm: as in `forward_many`.
+        bidirectional=True: both directions of every pair for the price of the forward one plus the 1/64-grid tail (the encoder still
+        runs once per window) - each item is `((events1, events2), [flow_fw], [flow_bw])`, flow_bw the flow from events2 to events1,
+        bitwise `forward_many` on the swapped pair.  At most 8 volumes per call (both directions share the 16-frame pointer table).
+        Calls with and without it may alternate on one stream.
+        fb_check=(alpha1, alpha2) or (alpha1, alpha2, 'all' | 'obj' | 'out') (needs bidirectional=True): a fourth element
+        `(mask_fw, mask_bw)`, the forward-backward consistency masks of `eemflow_amd.metrics.fb_check` ([1, 1, H, W], 1 = consistent),
+        by one more launch on the same stream."""
         vols = list(volumes)
-        if not 1 <= len(vols) <= self.MAX_STREAM:
-            raise ValueError(f"forward_stream: 1..{self.MAX_STREAM} volumes per call, got {len(vols)}")
+        if fb_check is not None and not bidirectional:
+            raise ValueError("forward_stream: fb_check needs bidirectional=True (the check compares the two directions' flows)")
+        if fb_check is not None:
+            from .metrics import fb_check_args
+            fb_check = fb_check_args(*fb_check)
+        max_vols = self.MAX_STREAM_BIDIR if bidirectional else self.MAX_STREAM
+        if not 1 <= len(vols) <= max_vols:
+            raise ValueError(f"forward_stream: 1..{max_vols} volumes per call{' with bidirectional=True' if bidirectional else ''}, got {len(vols)}")
         if not hasattr(self, "image_padder"):
             raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
         keep, shape = [], None
@@ -289,8 +303,14 @@ class EEMFlow(nn.Module):
         flows = [torch.empty(1, 2, out_size[0], out_size[1], device=dev, dtype=torch.float32) for _ in range(nflow)]
         pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
         po = (ctypes.c_void_p * max(nflow, 1))(*[f.data_ptr() for f in flows])
+        if bidirectional:
+            flows_bw = [torch.empty_like(f) for f in flows]
+            pb = (ctypes.c_void_p * max(nflow, 1))(*[f.data_ptr() for f in flows_bw])
         with torch.cuda.device(dev):
-            rc = L.eemflow_forward_stream(ctx, n, pv, po, nflow, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev))
+            if bidirectional:
+                rc = L.eemflow_forward_stream_bidir(ctx, n, pv, po, pb, nflow, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev))
+            else:
+                rc = L.eemflow_forward_stream(ctx, n, pv, po, nflow, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev))
         if rc != 0:
             msg = L.eemflow_last_error().decode("utf-8", "replace")
             if "eemflow_stream_reset" in msg:
@@ -298,7 +318,14 @@ class EEMFlow(nn.Module):
             raise _lib.EEMFlowHipError(msg)
         older = ([carried] if carried is not None else []) + vols[:-1]
         self._stream_prev = vols[-1]
-        return [((older[i], vols[i + 1 - (1 if carried is not None else 0)]), [flows[i]]) for i in range(nflow)]
+        pairs = [(older[i], vols[i + 1 - (1 if carried is not None else 0)]) for i in range(nflow)]
+        if not bidirectional:
+            return [(pairs[i], [flows[i]]) for i in range(nflow)]
+        if fb_check is None or nflow == 0:
+            return [(pairs[i], [flows[i]], [flows_bw[i]]) for i in range(nflow)]
+        from .metrics import fb_check_many
+        masks = fb_check_many(flows, flows_bw, *fb_check)
+        return [(pairs[i], [flows[i]], [flows_bw[i]], masks[i]) for i in range(nflow)]
 
     def reset_stream(self):
         """Drop the window `forward_stream` carries: its next call starts a new stream (len(volumes) - 1 pairs)."""

@@ -91,19 +91,29 @@ def stream_plan(n_samples, n):
     return plan
 
 
-def stream_chunks(dataset, model, n, dev):
+def stream_chunks(dataset, model, n, dev, fb_check=None):
     """Walk the dataset's current sequence window by window: each window read and voxelized once (dataset.get_windows), each call's
-    windows through ONE model.forward_stream, the stream reset at the start.  Yields (sample indices, their targets, their flows) per call."""
+    windows through ONE model.forward_stream, the stream reset at the start.  Yields (sample indices, their targets, their flows) per call.
+    fb_check = (alpha1, alpha2[, 'all' | 'obj' | 'out']): the stream runs bidirectionally (EEMFlow; at most 8 windows per call) and a
+    fourth element follows, the samples' forward consistency masks (mask_fw of forward_stream(fb_check=...))."""
     model.reset_stream()
     carry_target = None
+    if fb_check is not None:
+        n = min(int(n), getattr(model, "MAX_STREAM_BIDIR", 8))
     for w0, cnt, s0, nflow in stream_plan(len(dataset), n):
         vols, targets = dataset.get_windows(w0, cnt)
-        outs = model.forward_stream([v.to(dev)[None].float() for v in vols])
+        if fb_check is not None:
+            outs = model.forward_stream([v.to(dev)[None].float() for v in vols], bidirectional=True, fb_check=tuple(fb_check))
+        else:
+            outs = model.forward_stream([v.to(dev)[None].float() for v in vols])
         pair_targets = ([carry_target] if w0 > 0 else []) + list(targets[:cnt - 1])
         carry_target = targets[cnt - 1]
         if len(outs) != nflow or len(pair_targets) != nflow:
             raise RuntimeError(f"stream_chunks: windows {w0}..{w0 + cnt - 1} gave {len(outs)} flows for {nflow} samples")
-        yield list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]
+        if fb_check is not None:
+            yield list(range(s0, s0 + nflow)), pair_targets, [o[1][-1] for o in outs], [o[3][0] for o in outs]
+        else:
+            yield list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]
 
 
 class TestRaftEvents:
@@ -123,7 +133,8 @@ class TestRaftEvents:
         _, preds = model(events1=e1, events2=e2)
         return preds[-1]
 
-    def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0):
+    def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
+                            fb_check=None):
         """The evaluation loop of test_mvsec.py:580-597.  It reads the LAST prediction of every sample only (run_network, :1455): a
         model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call.
         stream = n > 0 (stride 1, a model with forward_stream - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset of consecutive windows with
@@ -131,7 +142,16 @@ class TestRaftEvents:
         (stream_plan), each call's windows through ONE model.forward_stream - sample i's flow is windows i and i + 1, the encoder runs
         once per window instead of twice.  Same per-sample lines in the same order; frames_in_flight, loader_threads and coalesce do
         not apply.  An ERAFT with warm_start = True is E-RAFT's warm-start evaluation: each sequence starts cold (reset_stream), every
-        later sample from the previous sample's forward-interpolated flow."""
+        later sample from the previous sample's forward-interpolated flow.
+        fb_check = (alpha1, alpha2[, 'all' | 'obj' | 'out']) (needs stream > 0 and a model whose forward_stream is bidirectional:
+        EEMFlow): the stream runs in both directions and every per-sample line gains two fields - `fb consistent`, the share of pixels
+        the forward-backward check (metrics.fb_check) keeps, and `AEE consistent`, the AEE over those pixels alone (the mask as the
+        event image of the sparse flow_error).  Without it the lines are unchanged."""
+        if fb_check is not None:
+            if not stream:
+                raise ValueError("fb_check= needs stream= (the backward flow comes from the bidirectional stream)")
+            if not hasattr(model, "MAX_STREAM_BIDIR"):
+                raise ValueError(f"fb_check= needs a model whose forward_stream takes bidirectional=True (EEMFlow); {type(model).__name__} has none")
         if stream:
             if stride != 1:
                 raise ValueError(f"stream= walks consecutive windows: it needs stride == 1 (got stride={stride}, whose samples share no window)")
@@ -146,12 +166,14 @@ class TestRaftEvents:
         if had is not None:
             model.final_only = True
         try:
-            return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce, stream)
+            extra = {"fb_check": fb_check} if fb_check is not None else {}
+            return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce, stream, **extra)
         finally:
             if had is not None:
                 model.final_only = had
 
-    def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0):
+    def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
+                             fb_check=None):
         """coalesce > 1 (a model with forward_many - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset with get_samples): that many samples are read, voxelized by
         ONE voxelizer launch sequence and handed to ONE model.forward_many call - n independent batch-1 samples riding a batch-n chain of
         launches, every sample in its own tensors; raw volumes with a normalisation record (HREMEventFlow(deferred_norm=True)) are
@@ -196,6 +218,7 @@ class TestRaftEvents:
                 iters, n_points = 0, 0
                 self.dataset.change_test_sequence(sequence)
                 pending = collections.deque()
+                fb_extra = {}                                    # fb_check: sample -> (consistent share, sums over the consistent pixels)
 
                 def retire():
                     nonlocal iters, n_points
@@ -205,8 +228,12 @@ class TestRaftEvents:
                     for name, v in (("aee", aee), ("sum", s_ee), ("aee_gt", aee_gt), ("sum_gt", s_gt), ("p1", p1), ("p3", p3)):
                         acc[name] += v
                     iters += 1
-                    print('{:05d} / {:05d}  AEE: {:2.6f}  meanAEE:{:2.6f} 3 - mean %AEE: {:.6f}'.format(
-                        idx + 1, len(self.dataset), aee, acc["aee"] / iters, 1. - acc["p3"] / iters))
+                    line = '{:05d} / {:05d}  AEE: {:2.6f}  meanAEE:{:2.6f} 3 - mean %AEE: {:.6f}'.format(
+                        idx + 1, len(self.dataset), aee, acc["aee"] / iters, 1. - acc["p3"] / iters)
+                    if idx in fb_extra:
+                        share, sums_fb = fb_extra.pop(idx)
+                        line += '  fb consistent: {:.6f}  AEE consistent: {:2.6f}'.format(float(share), flow_error_from_sums(sums_fb)[0])
+                    print(line)
 
                 indices = [idx for idx in range(len(self.dataset)) if idx % stride == 0]
                 futures = collections.deque()
@@ -221,11 +248,17 @@ class TestRaftEvents:
                     for idx in itertools.islice(ahead, 2 * loader_threads):
                         futures.append(pool.submit(load, idx))
                 count = 0
-                for chunk, targets, f_ests in (stream_chunks(self.dataset, model, stream, dev) if stream else ()):
+                for chunk, targets, f_ests, *fb_masks in (stream_chunks(self.dataset, model, stream, dev, fb_check) if stream else ()):
                     f_gts = [t_['flow'].to(dev)[None].float() for t_ in targets]
                     evs_ = [t_['event_valid'].to(dev).sum(0) for t_ in targets] if (sparse and all('event_valid' in t_ for t_ in targets)) else None
                     all_sums = flow_error_sums_many(f_gts, f_ests, evs_, is_car=self.is_car,
                                                     evaluation_type="sparse" if evs_ is not None else "dense")
+                    if fb_masks:
+                        # the consistent pixels as the event image of the sparse statistics (of a sparse evaluation: those with events too)
+                        cons = [m_[0, 0] if evs_ is None else m_[0, 0] * (evs_[i_] > 0).float() for i_, m_ in enumerate(fb_masks[0])]
+                        sums_fb = flow_error_sums_many(f_gts, f_ests, cons, is_car=self.is_car, evaluation_type="sparse")
+                        for i_, idx in enumerate(chunk):
+                            fb_extra[idx] = (fb_masks[0][i_].mean(), sums_fb[i_])
                     for i_, idx in enumerate(chunk):
                         pending.append((idx, 0, all_sums[i_], (targets[i_], f_ests[i_], f_gts[i_], evs_[i_] if evs_ is not None else None)))
                     while pending:

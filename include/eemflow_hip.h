@@ -129,6 +129,24 @@ int eemflow_forward_many(eemflow_ctx* ctx, int nframes, const float* const* even
 int eemflow_forward_stream(eemflow_ctx* ctx, int nvol, const float* const* volumes, float* const* flow_out, int nflow, int in_h,
                            int in_w, int out_h, int out_w, void* stream);
 
+/* Volumes per eemflow_forward_stream_bidir call: its 2 * nflow flows share the 16 frames of the per-frame pointer table. */
+#define EEM_STREAM_BIDIR_MAX_VOLUMES 8
+
+/* eemflow_forward_stream with BOTH directions of every pair: flow_fw_out[p] is the flow from the older to the newer window of pair p
+ * (what eemflow_forward_stream gives), flow_bw_out[p] the flow from the newer to the older one.  The encoder runs once per new window,
+ * exactly as in eemflow_forward_stream: the pooled maps of a window do not depend on which side of a pair it sits on, so the tail
+ * (correlation, rconv, decoders, out_conv, upsample) runs over 2 * nflow pairs, the second half with the two windows' roles exchanged -
+ * 0.4 % of a frame's MACs per extra flow.  nvol is 1..EEM_STREAM_BIDIR_MAX_VOLUMES.  Windows, the carried window, the nflow rule, the
+ * weight-version and size refusals, eemflow_stream_reset and eemflow_set_deferred_input_norm are those of eemflow_forward_stream, and
+ * the two calls share the context's one stream state: either may follow the other with the carry intact.
+ * In the same encoder and decoder forms (EEM_WINO4_LAYERS; EEM_DEC_WNC - the decoders' kernel choice follows the batch, here
+ * 2 * nflow) flow_fw_out[p] is bitwise eemflow_forward_many on (v_p, v_p+1) and flow_bw_out[p] bitwise eemflow_forward_many on
+ * (v_p+1, v_p).
+ * Replaces: two passes of the evaluation loop (test_mvsec.py:580-597), the second with events1 / events2 exchanged, as the input of
+ * occ_check_model (utils_luo/tools.py:1148): four runs of EEMFlow.forward's encoder (model/EEMFlow/EEMFlow.py:135-154) per pair. */
+int eemflow_forward_stream_bidir(eemflow_ctx* ctx, int nvol, const float* const* volumes, float* const* flow_fw_out,
+                                 float* const* flow_bw_out, int nflow, int in_h, int in_w, int out_h, int out_w, void* stream);
+
 /* Drop the carried window: the next eemflow_forward_stream call starts a new stream.
  * Replaces: the start of a sequence in test_mvsec.py:580-597 (dataset.change_test_sequence). */
 int eemflow_stream_reset(eemflow_ctx* ctx);
@@ -210,6 +228,20 @@ int eemflow_flow_error(const float* flow_gt, const float* flow_pred, const float
  * Replaces: n calls of Test.flow_error in the evaluation loop (test_mvsec.py:580-597 -> :291-346). */
 int eemflow_flow_error_many(int n, const float* const* flow_gt, const float* const* flow_pred, const float* const* event_img, int h,
                             int w, int max_row, double* out5n, void* stream);
+
+/* Forward-backward consistency masks of n (1..16) bidirectional flow pairs of one image size by ONE launch: flow_fw[i], flow_bw[i]
+ * ([1][2][h][w]) and mask_fw_out[i], mask_bw_out[i] ([1][1][h][w], 1.0 = consistent, 0.0 = occluded / unreliable) are HOST arrays of
+ * device pointers.  With len(x) = sqrt(x_u^2 + x_v^2):
+ *     thresh  = alpha1 * (len(fw) + len(bw)) + alpha2
+ *     mask_fw = len(fw + torch_warp(bw, fw)) < thresh,   mask_bw = len(bw + torch_warp(fw, bw)) < thresh
+ * torch_warp is eemplus_warp's mode 1 (the same device routine: normalised by W - 1 / H - 1, sampled with align_corners=False and zero
+ * padding - half a pixel off, as the reference is).  mode 0 ('all'): these masks; 1 ('obj'): a pixel whose target x + flow leaves
+ * [0, W-1] x [0, H-1] is forced to 1; 2 ('out'): the outgoing mask alone (1 inside, 0 leaving).  A mask is a valid `event_img` of
+ * eemflow_flow_error: the statistics over the consistent pixels.
+ * Replaces: occ_check_model.__call__ (utils_luo/tools.py:1148-1220, :1273-1309; occ_type 'for_back_check', scale 1) on
+ * tensor_tools.torch_warp (utils_luo/tools.py:2262-2306). */
+int eemflow_fb_check_many(int n, const float* const* flow_fw, const float* const* flow_bw, float* const* mask_fw_out,
+                          float* const* mask_bw_out, int h, int w, float alpha1, float alpha2, int mode, void* stream);
 
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
