@@ -23,6 +23,10 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 void eem_set_error(const char* fmt, ...);
 
+// name of the kernel instantiation this thread's last convolution launch chose (gconv.hip; eemop_last_conv_form reports it): a test
+// observable - one pointer store on the host per launch
+extern thread_local const char* eem_conv_form;
+
 #define EEM_HIP_CHECK(expr)                                                            \
     do {                                                                               \
         hipError_t _e = (expr);                                                        \

@@ -171,6 +171,8 @@ static int stem7_launch_t(const GConvArgs& a, hipStream_t stream) {
     }
     static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
     const int grid = ntiles < cus ? ntiles : cus;       // one resident block per CU, each walks tiles blockIdx.x, + grid, ...
+    static const char* const names[5] = {"stem7_c1", "stem7_c2", "stem7_c3", "stem7_c4", "stem7_c5"};
+    eem_conv_form = names[CIN - 1];
     hipLaunchKernelGGL((stem7_kernel<CIN>), dim3(grid), dim3(256), lds_bytes, stream, a, reinterpret_cast<const f32x4*>(a.wstem), tiles_x, tiles_y);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

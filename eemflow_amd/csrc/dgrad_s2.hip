@@ -388,6 +388,7 @@ int launch_wide(const DgradS2Args& a, hipStream_t st) {
         EEM_HIP_CHECK(hipFuncSetAttribute((const void*)dgrad_s2w_kernel<CO, K1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised = true;
     }
+    eem_conv_form = CO == 96 ? (K1 ? "dgrad_s2w_96_1x1" : "dgrad_s2w_96_3x3") : (K1 ? "dgrad_s2w_128_1x1" : "dgrad_s2w_128_3x3");
     hipLaunchKernelGGL((dgrad_s2w_kernel<CO, K1>), dim3(gx, citiles), dim3(256), lds_bytes, st, a, tiles_x, tiles_y);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

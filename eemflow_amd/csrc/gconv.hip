@@ -255,6 +255,8 @@ __global__ __launch_bounds__(SPLITK ? SPLITK * 64 : 256) void gconv_kernel(GConv
 
 }  // namespace
 
+thread_local const char* eem_conv_form = "";
+
 size_t gconv_packed_floats(int cout, const int* cs, int nseg, int kh, int kw) {
     int cps = 0;
     for (int s = 0; s < nseg; ++s) cps += (cs[s] + 1) / 2;
@@ -570,14 +572,23 @@ int fewout_launch(const GConvArgs& a, hipStream_t stream) {
         // EEM_FEWOUT_WIDE=0 (read per call: the equality test flips it): the 64-pixel form for the small launches too
         const char* ew = getenv("EEM_FEWOUT_WIDE");
         if (small && a.seg[0].c <= 256 && !(ew && ew[0] == '0')) {
+            eem_conv_form = "fewout_wide2";
             hipLaunchKernelGGL((fewout_wide_kernel<2>), dim3((unsigned)((n + 31) / 32)), dim3(1024), 0, stream, a, (a.seg[0].c + 31) / 32);
-        } else if (small) hipLaunchKernelGGL((fewout_kernel<16, 2, 2>), dim3(blocks), dim3(1024), 0, stream, a, (a.seg[0].c + 15) / 16);
-        else hipLaunchKernelGGL((fewout_kernel<8, 1, 2>), dim3(blocks), dim3(512), 0, stream, a, (a.seg[0].c + 7) / 8);
+        } else if (small) {
+            eem_conv_form = "fewout_k16_c2";
+            hipLaunchKernelGGL((fewout_kernel<16, 2, 2>), dim3(blocks), dim3(1024), 0, stream, a, (a.seg[0].c + 15) / 16);
+        } else {
+            eem_conv_form = "fewout_k8_c2";
+            hipLaunchKernelGGL((fewout_kernel<8, 1, 2>), dim3(blocks), dim3(512), 0, stream, a, (a.seg[0].c + 7) / 8);
+        }
     } else if (a.cout <= 4 && !small) {                               // EEMFlow+'s mask estimator tail 184 -> 3 (cdc_utils.py:151)
+        eem_conv_form = "fewout_k8_c4";
         hipLaunchKernelGGL((fewout_kernel<8, 1, 4>), dim3(blocks), dim3(512), 0, stream, a, (a.seg[0].c + 7) / 8);
     } else if (small) {
+        eem_conv_form = "fewout_k16_c8";
         hipLaunchKernelGGL((fewout_kernel<16, 2, 8>), dim3(blocks), dim3(1024), 0, stream, a, (a.seg[0].c + 15) / 16);
     } else {
+        eem_conv_form = "fewout_k8_c8";
         hipLaunchKernelGGL((fewout_kernel<8, 1, 8>), dim3(blocks), dim3(512), 0, stream, a, (a.seg[0].c + 7) / 8);
     }
     EEM_HIP_CHECK(hipGetLastError());
@@ -610,6 +621,7 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
         if (!off && a.nseg == 1 && a.seg[0].c <= (shape7 ? taps_maxc : 2) && (shape7 || shape3) && a.tstride <= 1 && a.epi == GEPI_PLAIN && a.pre == nullptr && a.seg[0].gate == nullptr &&
             a.seg[0].cmul <= 1) {
             dim3 grid(ceil_div(hwo, 128), cot, a.n);
+            eem_conv_form = shape7 ? "taps_7x7" : "taps_3x3";
             if (shape7) hipLaunchKernelGGL((gconv_taps_kernel<7, 7>), grid, dim3(256), 0, stream, a);
             else hipLaunchKernelGGL((gconv_taps_kernel<3, 3>), grid, dim3(256), 0, stream, a);
             EEM_HIP_CHECK(hipGetLastError());
@@ -619,10 +631,12 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
     if (maxpairs <= 4) {                                             // short batches for few-channel inputs
         if (waves22 >= 2048 && cot >= 2) {
             dim3 grid(ceil_div(hwo, 256), ceil_div(cot, 2), a.n);
+            eem_conv_form = maxpairs <= 1 ? "generic_2x2_b1" : "generic_2x2_b4";
             if (maxpairs <= 1) hipLaunchKernelGGL((gconv_kernel<2, 2, false, 1>), grid, dim3(256), 0, stream, a);
             else hipLaunchKernelGGL((gconv_kernel<2, 2, false, 4>), grid, dim3(256), 0, stream, a);
         } else {
             dim3 grid(ceil_div(hwo, 128), cot, a.n);
+            eem_conv_form = maxpairs <= 1 ? "generic_1x1_b1" : "generic_1x1_b4";
             if (maxpairs <= 1) hipLaunchKernelGGL((gconv_kernel<1, 1, false, 1>), grid, dim3(256), 0, stream, a);
             else hipLaunchKernelGGL((gconv_kernel<1, 1, false, 4>), grid, dim3(256), 0, stream, a);
         }
@@ -631,9 +645,11 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
     }
     if (waves22 >= 2048 && cot >= 2) {
         dim3 grid(ceil_div(hwo, 256), ceil_div(cot, 2), a.n);
+        eem_conv_form = "generic_2x2";
         hipLaunchKernelGGL((gconv_kernel<2, 2>), grid, dim3(256), 0, stream, a);
     } else if ((long)ceil_div(hwo, 64) * cot * a.n >= 2048) {
         dim3 grid(ceil_div(hwo, 256), cot, a.n);
+        eem_conv_form = "generic_2x1";
         hipLaunchKernelGGL((gconv_kernel<2, 1>), grid, dim3(256), 0, stream, a);
     } else {
         int ksteps = 0;
@@ -652,11 +668,13 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
             static const int force = [] { const char* e = getenv("EEM_SPLITK_WAVES"); return e ? atoi(e) : 0; }();
             int skw = tiles <= 64 && batches >= 32 ? 16 : tiles <= 160 && batches >= 16 ? 8 : 4;
             if (force) skw = force;
+            eem_conv_form = skw == 16 ? "generic_splitk16" : skw == 8 ? "generic_splitk8" : "generic_splitk4";
             if (skw == 16) hipLaunchKernelGGL((gconv_kernel<1, 1, 16>), grid, dim3(1024), 0, stream, a);
             else if (skw == 8) hipLaunchKernelGGL((gconv_kernel<1, 1, 8>), grid, dim3(512), 0, stream, a);
             else hipLaunchKernelGGL((gconv_kernel<1, 1, 4>), grid, dim3(256), 0, stream, a);
         } else {
             dim3 grid(ceil_div(hwo, 128), cot, a.n);
+            eem_conv_form = "generic_1x1";
             hipLaunchKernelGGL((gconv_kernel<1, 1>), grid, dim3(256), 0, stream, a);
         }
     }

@@ -363,6 +363,15 @@ __global__ __launch_bounds__(256 * KG, (KG > 1 || S > 1 || (THT != 2 && THT != 4
 #endif
 }
 
+// eem_conv_form of an instantiation: filter shape, tile rows, cout tiles per block, K groups (stride 2: "_s2")
+struct G16Name {
+    char s[48];
+    G16Name(int kh, int kw, int th, int wm, int kg, int stride) {
+        if (stride == 2) snprintf(s, sizeof(s), "gconv16_%dx%d_s2", kh, kw);
+        else snprintf(s, sizeof(s), "gconv16_%dx%d_th%d_wm%d_kg%d", kh, kw, th, wm, kg);
+    }
+};
+
 template <int KH, int KW, int THT, int WM>
 int launch_wm(const GConvArgs& a, const float* wpk16, const float* zero_page, hipStream_t stream) {
     using C = G16Cfg<KH, KW, THT>;
@@ -377,6 +386,8 @@ int launch_wm(const GConvArgs& a, const float* wpk16, const float* zero_page, hi
     const int nchunks = cin / 16;
     const long blocks = (long)grid.x * grid.y * grid.z;
     const bool two = nchunks >= 4 && (kg_env ? kg_env == 2 : (blocks <= cus && a.in_flight < 3));
+    static const G16Name names[2] = {G16Name(KH, KW, THT, WM, 1, 1), G16Name(KH, KW, THT, WM, 2, 1)};   // (written once per instantiation)
+    eem_conv_form = names[two].s;
     if (two) hipLaunchKernelGGL((gconv16_kernel<KH, KW, THT, WM, 2>), grid, dim3(512), 0, stream, a, wpk16, zero_page, tiles_x, nchunks);
     else hipLaunchKernelGGL((gconv16_kernel<KH, KW, THT, WM, 1>), grid, dim3(256), 0, stream, a, wpk16, zero_page, tiles_x, nchunks);
     EEM_HIP_CHECK(hipGetLastError());
@@ -398,6 +409,8 @@ int launch_s2(const GConvArgs& a, const float* wpk16, const float* zero_page, hi
     for (int s = 0; s < a.nseg; ++s) cin += a.seg[s].c;
     const int tiles_x = ceil_div(a.wout, C::TW), tiles_y = ceil_div(a.hout, C::TH);
     dim3 grid(tiles_x * tiles_y, ceil_div(a.cout, 64), a.n);
+    static const G16Name name(KH, KW, 4, 4, 1, 2);
+    eem_conv_form = name.s;
     hipLaunchKernelGGL((gconv16_kernel<KH, KW, 4, 4, 1, 2>), grid, dim3(256), 0, stream, a, wpk16, zero_page, tiles_x, cin / 16);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

@@ -351,6 +351,8 @@ int gb_launch_t(const GConvArgs& a, hipStream_t stream) {
 #ifdef EEM_DIAG
     { static int once = [] { const char* e = getenv("EEM_GB_DBG"); int v = e ? atoi(e) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gb_dbg), &v, sizeof v); return v; }(); (void)once; }
 #endif
+    static const struct Name { char s[32]; Name() { snprintf(s, sizeof(s), "gconvb_%dx%d_th%d", KH, KW, THT); } } name;   // eem_conv_form
+    eem_conv_form = name.s;
     hipLaunchKernelGGL((gconvb_kernel<KH, KW, THT, RING>), grid, dim3(768), 0, stream, a, reinterpret_cast<const u32x4*>(a.wpkb), tiles_x, cin / 32);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

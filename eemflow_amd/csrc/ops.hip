@@ -585,6 +585,20 @@ int plan_bwd(int cout, int cin, int ci0, int cic, int kh, int kw, Plan** out) {
     return EEM_OK;
 }
 
+// eem_conv_form of a weight gradient: the kernels' own names (tr_last_form) with what the launch functions dispatch on behind it; the
+// per-segment calls of eemop_conv2d_bwd_weight_cat are joined with '+'
+thread_local char t_wgrad_form[256];
+thread_local bool t_wgrad_join = false;           // the next name is appended to t_wgrad_form
+
+void wgrad_form(const char* fmt, int a = 0, int b = 0, int c = 0) {
+    size_t at = t_wgrad_join ? strlen(t_wgrad_form) : 0;
+    if (at && at + 1 < sizeof(t_wgrad_form)) t_wgrad_form[at++] = '+';
+    char f[96];
+    snprintf(f, sizeof(f), "wgrad_%s%s", tr_last_form, fmt);
+    snprintf(t_wgrad_form + at, sizeof(t_wgrad_form) - at, f, a, b, c);
+    eem_conv_form = t_wgrad_form;
+}
+
 }  // namespace
 
 // ================================================================================================ packed-weight cache
@@ -615,6 +629,12 @@ extern "C" int eemop_pack_forget(long long token) {
 }
 
 // ================================================================================================ convolution
+extern "C" int eemop_last_conv_form(char* buf, int cap) {
+    EEM_REQUIRE(buf && cap >= 1, "eemop_last_conv_form: bad arguments");
+    snprintf(buf, (size_t)cap, "%s", eem_conv_form);
+    return EEM_OK;
+}
+
 extern "C" int eemop_conv2d_fwd(const float* x0, int c0, const float* x1, int c1, const float* x2, int c2, const float* w,
                                 const float* bias, int n, int hin, int win, int cout, int kh, int kw, int stride, int ph, int pw, int act,
                                 float out_scale, float* out, int out_ctotal, int out_coff, void* stream) {
@@ -673,7 +693,13 @@ extern "C" int eemop_conv2d_bwd_data(const float* dy, const float* w, int n, int
     a.tstride = stride;
     a.act = GACT_NONE; a.epi = GEPI_PLAIN; a.out_scale = 1.f;
     if ((rc = pack_for(pl, w, a, st)) != EEM_OK) return rc;
-    return gconv_launch(a, st);
+    rc = gconv_launch(a, st);
+    if (stride == 2) {                            // the transposed form is an arithmetic of its own (a quarter of the taps per output)
+        thread_local char t2_form[64];
+        snprintf(t2_form, sizeof(t2_form), "dgrad_t2_%s", eem_conv_form);
+        eem_conv_form = t2_form;
+    }
+    return rc;
 }
 
 // dw [cout][cin][kh][kw] += dy (x) x for the input-channel slice [ci0, ci0 + cic) (x is that slice: [n][cic][hin][win]);
@@ -703,10 +729,18 @@ extern "C" int eemop_conv2d_bwd_weight(const float* x, const float* dy, int n, i
         float* zp = nullptr;
         if ((rc = scratch_get(g_scratch[1], 1024, &zp)) != EEM_OK) return rc;
         a.zero_page = zp;
-        if (wgrad_ring_supported(a) && wgrad_ring_preferred(a)) return wgrad_ring_launch(a, st);
-        if (wgrad_few_supported(a)) return wgrad_few_launch(a, st);                          // (<= 8 couts: the flow heads)
-        if (kh == 3 && kw == 3 && wgrad_enc_supported(a)) return wgrad_enc_launch(a, st);   // (16 / 32 / 64 couts on blocks of their own height)
-        if (wgrad_wide_supported(a)) return wgrad_wide_launch(a, st);
+        if (wgrad_ring_supported(a) && wgrad_ring_preferred(a)) { rc = wgrad_ring_launch(a, st); wgrad_form(""); return rc; }
+        if (wgrad_few_supported(a)) {                                                        // (<= 8 couts: the flow heads)
+            rc = wgrad_few_launch(a, st);
+            wgrad_form("_c%d", cout <= 2 ? 2 : cout <= 4 ? 4 : 8);
+            return rc;
+        }
+        if (kh == 3 && kw == 3 && wgrad_enc_supported(a)) {                                  // (16 / 32 / 64 couts on blocks of their own height)
+            rc = wgrad_enc_launch(a, st);
+            wgrad_form("_c%d_s%d", cout, stride);
+            return rc;
+        }
+        if (wgrad_wide_supported(a)) { rc = wgrad_wide_launch(a, st); wgrad_form("_%dx%d", kh, kw); return rc; }
     }
     for (int c0 = 0; c0 < cout; c0 += 128) {                     // the kernel holds at most 128 couts per block
         WgradArgs a;
@@ -718,6 +752,7 @@ extern "C" int eemop_conv2d_bwd_weight(const float* x, const float* dy, int n, i
         a.kh = kh; a.kw = kw; a.ph = ph; a.pw = pw; a.dw_cin = cin; a.dw_coff = ci0;
         if ((rc = tr_wgrad_launch_batch(&a, 1, st)) != EEM_OK) return rc;
     }
+    wgrad_form(db ? "_%dx%d_s%d_bias" : "_%dx%d_s%d", kh, kw, stride);             // ("generic" + the bias-gradient kernel)
     if (db) return tr_bias_grad_launch(dy, nullptr, cout, 0, 1, cout, n, hout * wout, db, st);
     return EEM_OK;
 }
@@ -750,11 +785,13 @@ extern "C" int eemop_conv2d_bwd_weight_cat(const float* x0, int c0, const float*
         int rc = scratch_get(g_scratch[1], 1024, &zp);
         if (rc != EEM_OK) return rc;
         a.zero_page = zp;
-        if (wgrad_ring_supported(a) && wgrad_ring_preferred(a)) return wgrad_ring_launch(a, st);
+        if (wgrad_ring_supported(a) && wgrad_ring_preferred(a)) { rc = wgrad_ring_launch(a, st); wgrad_form("_cat%d", nseg); return rc; }
     }
     int ci0 = 0;
     for (int s = 0; s < nseg; ++s) {
+        t_wgrad_join = s > 0;
         const int rc = eemop_conv2d_bwd_weight(xs[s], dy, n, hin, win, cin, ci0, cs[s], cout, kh, kw, stride, ph, pw, dw, s == 0 ? db : nullptr, stream);
+        t_wgrad_join = false;
         if (rc != EEM_OK) return rc;
         ci0 += cs[s];
     }

@@ -400,11 +400,14 @@ static bool use_bx3() {
 // stride-1 layers of any width with 3x3, 1x5, 5x1 or 1x1 filters (E-RAFT's residual stacks, update block and heads): 64-cout chunks
 template <int KH, int KW>
 int launch_wide(const WgradArgs& a, hipStream_t st) {
+    const bool tw32 = a.wout % 32 == 0 || a.wout >= 256;
     if (use_bx3()) {
-        if (a.wout % 32 == 0 || a.wout >= 256) return launch<4, 1, 32, 16, KH, KW, true>(a, st);
+        tr_last_form = tw32 ? "wide_bx3_tw32" : "wide_bx3_tw16";
+        if (tw32) return launch<4, 1, 32, 16, KH, KW, true>(a, st);
         return launch<4, 1, 16, 16, KH, KW, true>(a, st);
     }
-    if (a.wout % 32 == 0 || a.wout >= 256) return launch<4, 1, 32, 16, KH, KW>(a, st);
+    tr_last_form = tw32 ? "wide_fp32_tw32" : "wide_fp32_tw16";
+    if (tw32) return launch<4, 1, 32, 16, KH, KW>(a, st);
     return launch<4, 1, 16, 16, KH, KW>(a, st);
 }
 

@@ -537,13 +537,13 @@ int wgrad_ring_launch(const WgradArgs& a, hipStream_t st) {
         tr_last_form = "ring_s2_6464";
         return launch_ring<Cfg64x64s2>(a, st);
     }
-    tr_last_form = "ring_wide";
     if (kh == 5) {
         const char* e = getenv("EEM_WGRAD_RING_51");                 // (measurement: 6464 = 64 input channels per block, strips of <= 64)
-        if (e && atoi(e) == 6464) return launch_ring<Cfg64x64r51>(a, st);
-        return a.wout > 64 ? launch_ring<Cfg64x32r51>(a, st) : launch_ring<Cfg64x64r51>(a, st);
+        const bool c64 = (e && atoi(e) == 6464) || a.wout <= 64;
+        tr_last_form = c64 ? "ring_wide_5x1_6464" : "ring_wide_5x1_6432";
+        return c64 ? launch_ring<Cfg64x64r51>(a, st) : launch_ring<Cfg64x32r51>(a, st);
     }
-    if (kh == 1) return launch_ring<Cfg64x64r15>(a, st);
+    if (kh == 1) { tr_last_form = "ring_wide_1x5"; return launch_ring<Cfg64x64r15>(a, st); }
     if (a.cout <= 16 && a.cin <= 16) { tr_last_form = "ring_1616"; return launch_ring<Cfg16x16>(a, st); }
     if (a.cout <= 32 && a.cin <= 32) { tr_last_form = "ring_3232"; return launch_ring<Cfg32x32>(a, st); }
     tr_last_form = "ring_6464";

@@ -582,6 +582,11 @@ int eemop_conv2d_bwd_weight(const float* x, const float* dy, int n, int hin, int
  * Replaces: autograd of nn.Conv2d w.r.t. its weight and bias for the convs of model/update.py:33-60,63-81 whose input is a torch.cat. */
 int eemop_conv2d_bwd_weight_cat(const float* x0, int c0, const float* x1, int c1, const float* x2, int c2, const float* dy, int n, int hin,
                                 int win, int cout, int kh, int kw, int stride, int ph, int pw, float* dw, float* db, void* stream);
+/* TEST OBSERVABLE: the name of the kernel instantiation that the calling thread's most recent eemop_conv2d_* call launched, e.g.
+ * "gconv16_3x3_th3_wm4_kg1" (filter, tile rows, 16-cout tiles per block, K groups), "gconvb_1x5_th6", "generic_splitk8",
+ * "fewout_k8_c4", "stem7_c5", "dgrad_s2w_128_3x3", "wgrad_enc_bx3_tw16_c32_s2", "wgrad_generic_7x7_s2_bias"; a weight gradient served by
+ * one launch per input segment reports the segments' names joined with '+'.  A host-side pointer store per launch; "" before any. */
+int eemop_last_conv_form(char* buf, int cap);
 /* out = scale * dy * act'(y) for y = act(pre): kind 1 ReLU, 2 sigmoid, 3 tanh, 0 identity.  Replaces: autograd of F.relu /
  * torch.sigmoid / torch.tanh (model/update.py:14,45-47,54-56,74-79,95; model/eraft.py:130-131) and of the 0.25 mask scale (:105). */
 int eemop_act_bwd(const float* dy, const float* y, long long n, int kind, float scale, float* out, void* stream);

@@ -323,3 +323,138 @@ def check_decoder(name, got, ref64, ref32, kappa=None):
         raise StageError(f"{name} [decoder]: GPU error rms {rg:.3g} / max {mg:.3g} against the fp32 CPU oracle's {rc:.3g} / {mc:.3g} "
                          f"(kappa {kappa}, floor {floor:.3g}); worst element {where(ref64.shape, w)}")
     return rec
+
+
+# ------------------------------------------------------------------------------------- the operator-level ABI (eemop_conv2d_*)
+# tests/test_gpu_ops_fp64.py and tests/test_fp64_bounds_ops.py: every kernel form behind eemop_conv2d_fwd / _bwd_data / _bwd_weight /
+# _bwd_weight_cat, named by eemop_last_conv_form, against the references above.  What that ABI adds to them: non-square filters and
+# paddings (conv_ref & co. take padding as a pair), channel-concatenated inputs, input-channel slices, out_scale and three epilogues.
+ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 4         # the ABI's `act` codes that are sums' roundings (sigmoid / tanh are left out: see the tests)
+
+
+def op_conv_ref(xs, w, b, stride=1, padding=(1, 1), act=ACT_NONE, out_scale=1.0):
+    """out_scale * act(conv2d(cat(xs, 1), w) + b) in fp64 with mag = |out_scale| (conv(|x|, |w|) + |b|): the pre-activation's mag for
+    every epilogue (ReLU and LeakyReLU never enlarge an error of their argument)."""
+    x = torch.cat([_d(t) for t in xs], 1)
+    pre, mag = conv_ref(x, w, b, stride=stride, act=False, padding=tuple(padding))
+    ref = {ACT_NONE: pre, ACT_RELU: pre.clamp_min(0.0), ACT_LEAKY: leaky(pre)}[act]
+    s = float(np.float32(out_scale))
+    return ref * s, mag * abs(s)
+
+
+def op_dgrad_ref(dy, w, in_hw, stride=1, padding=(1, 1), ci0=0, cic=None):
+    """dx of the input-channel slice [ci0, ci0 + cic) for dy w.r.t. the conv's pre-activation (this ABI's contract: the caller has
+    applied the activation's gate, eemop_act_bwd, to dy already - from the stored output, as `gate` does)."""
+    w = _d(w)
+    cic = w.shape[1] - ci0 if cic is None else cic
+    return conv_dgrad_ref(dy, w[:, ci0:ci0 + cic], in_hw, stride=stride, padding=tuple(padding))
+
+
+def op_wgrad_ref(xs, dy, wshape, stride=1, padding=(1, 1), ci0=0):
+    """(dW, mag, db, mag) of a conv over cat(xs, 1), as the columns [ci0, ci0 + sum c_s) of a zero dW of shape `wshape` (the ABI writes
+    an input-channel slice into a wider dw; the other columns must stay what they were)."""
+    x = torch.cat([_d(t) for t in xs], 1)
+    cout, cin, kh, kw = wshape
+    c = x.shape[1]
+    dw, mw, db, mb = conv_wgrad_ref(x, dy, (cout, c, kh, kw), stride=stride, padding=tuple(padding))
+    full, fmag = torch.zeros(*wshape, dtype=torch.float64), torch.zeros(*wshape, dtype=torch.float64)
+    full[:, ci0:ci0 + c], fmag[:, ci0:ci0 + c] = dw, mw
+    return full, fmag, db, mb
+
+
+def seeded_conv(seed, cin, cout, k, stride=1, padding=None):
+    """(w, b) of an nn.Conv2d with its default initialisation under `seed` (the global generator is left as it was); k = (kh, kw)."""
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        conv = torch.nn.Conv2d(cin, cout, tuple(k), stride=stride, padding=tuple(padding) if padding is not None else (k[0] // 2, k[1] // 2))
+    return conv.weight.detach().clone(), conv.bias.detach().clone()
+
+
+def random_sign(shape, generator, scale=1.0):
+    """Upstream gradients as the training fp64 tests make them: unit-normal magnitudes, so an adjoint's terms cancel like a real
+    backward's (|ref| ~ mag / sqrt(K))."""
+    return torch.randn(*shape, generator=generator) * scale
+
+
+# Form name (eemop_last_conv_form) -> family of LIMITS, by the form's arithmetic; no limit is fitted to these kernels.  A stride-1 data
+# gradient is a forward launch on transposed weights (ops.hip: plan_bwd) and reports - and is held to - the forward kernel's name and
+# family.  A name joined with '+' (one weight-gradient launch per input segment) is looked up part by part.
+def _form_families():
+    t = {}
+    for k in ("1x1", "3x3", "1x5", "5x1"):
+        # fp32 MFMA, LDS-tiled: tile rows x (16-cout tiles per block) x K groups.  16 couts: 4-row tiles only; 32 couts: 2 or 4 rows, and
+        # its 4-row form is chosen from 2048 blocks on - more than the 256 a second K group is given
+        for th, wm in [(2, 4), (3, 4), (4, 4), (5, 4), (6, 4), (2, 2), (4, 2), (4, 1)]:
+            for kg in (1, 2):
+                if not ((th, wm) == (4, 2) and kg == 2):
+                    t[f"gconv16_{k}_th{th}_wm{wm}_kg{kg}"] = "direct"
+        for th in (2, 4, 6, 8):
+            t[f"gconvb_{k}_th{th}"] = "bx3"                       # bf16 matrix pipe, operands as three exact pieces
+    t.update({"gconv16_3x3_s2": "direct", "gconv16_1x1_s2": "direct"})
+    # (conv_stem7.hip names its launches "stem7_c<cin>", but only eraft_forward hands it its packing: this ABI serves the stems on taps_7x7)
+    t.update({"taps_7x7": "direct", "taps_3x3": "direct"})
+    t.update({f"fewout_{v}": "direct" for v in ("wide2", "k16_c2", "k8_c2", "k8_c4", "k16_c8", "k8_c8")})     # vector-pipe FMA
+    generic = ("generic_2x2_b1", "generic_2x2_b4", "generic_1x1_b1", "generic_1x1_b4", "generic_2x2", "generic_2x1", "generic_1x1",
+               "generic_splitk4", "generic_splitk8", "generic_splitk16")
+    t.update({g: "direct" for g in generic})
+    return t
+
+
+FORM_FAMILY = _form_families()
+# the transposed generic form (tstride = 2: the data gradient of a stride-2 conv the parity kernel refuses) and the parity kernel
+FORM_FAMILY.update({f"dgrad_t2_{g}": "dgrad_gconv" for g in FORM_FAMILY if g.startswith("generic_")})
+FORM_FAMILY.update({f"dgrad_s2w_{c}_{k}": "dgrad_s2" for c in (96, 128) for k in ("3x3", "1x1")})
+# weight gradients, by kernel
+FORM_FAMILY.update({f"wgrad_ring_{v}": "wgrad_ring" for v in ("s2_6464", "s2_6432", "s2_3216", "6464", "3232", "1616", "wide_1x5",
+                                                                "wide_5x1_6464", "wide_5x1_6432")})
+# (the one-launch form of eemop_conv2d_bwd_weight_cat: every ring block shape over two or three input segments)
+FORM_FAMILY.update({f"{f}_cat{n}": "wgrad_ring" for f in list(FORM_FAMILY) if f.startswith("wgrad_ring_") for n in (2, 3)})
+FORM_FAMILY.update({f"wgrad_few_c{c}": "wgrad_batched" for c in (2, 4, 8)})
+for _c_ in (16, 32, 64):
+    for _s_ in (1, 2):
+        for _tw_ in (16, 32):
+            FORM_FAMILY[f"wgrad_enc_fp32_tw{_tw_}_c{_c_}_s{_s_}"] = "wgrad_fp32"
+            if _c_ > 16:                                                # (one 16-cout tile per wave stays on the fp32 MFMA)
+                FORM_FAMILY[f"wgrad_enc_bx3_tw{_tw_}_c{_c_}_s{_s_}"] = "wgrad_bx3"
+FORM_FAMILY["wgrad_enc_fp32_tw32_c5_c16_s2"] = "wgrad_fp32"           # (<= 5 input channels: EEMFlow's first layer)
+for _k_ in ("3x3", "1x5", "5x1", "1x1"):
+    for _tw_ in (16, 32):
+        FORM_FAMILY[f"wgrad_wide_bx3_tw{_tw_}_{_k_}"] = "wgrad_bx3"
+        FORM_FAMILY[f"wgrad_wide_fp32_tw{_tw_}_{_k_}"] = "wgrad_fp32"
+for _k_ in ("3x3_s1", "3x3_s2", "1x1_s1", "1x1_s2", "1x5_s1", "5x1_s1", "7x7_s1", "7x7_s2"):
+    FORM_FAMILY[f"wgrad_generic_{_k_}"] = "wgrad_batched"             # train.hip's batched kernel ...
+    FORM_FAMILY[f"wgrad_generic_{_k_}_bias"] = "wgrad_batched"        # ... and the bias-gradient kernel behind it
+# Forms held to check_decoder's criterion (KAPPA_DEC x the error of torch's fp32 CPU evaluation of the same operation on the same inputs,
+# plus one unit of fp32 rounding) in place of a family's SLOPE, each with its reason; max|z|, rms(z) and |mean z| stay the family's
+# (FORM_KAPPA_FAMILY: only the statistic the reason is about is waived).
+_T2_SPLIT = ("the dispatch gives it launches of at most %d tiles of 32 pixels x 32 channels (at most %d values) of sums of >= %d terms that "
+             "cancel: there the slope is the ratio of two noises - torch's own fp32 data gradient of the case reads %s u against dgrad_gconv's "
+             "0.031 u, its max|z|, rms and mean inside the family.  The arithmetic is the transposed generic kernel's, which "
+             "dgrad_t2_generic_splitk4 holds to dgrad_gconv at launches of a million values")
+FORM_KAPPA = {
+    "dgrad_t2_generic_splitk8": _T2_SPLIT % (160, 163840, 256, "0.040"),
+    "dgrad_t2_generic_splitk16": _T2_SPLIT % (64, 65536, 512, "0.091"),
+}
+FORM_KAPPA_FAMILY = {_f_: FORM_FAMILY.pop(_f_) for _f_ in FORM_KAPPA}
+
+
+def form_family(name):
+    """Family of a form name; the parts of a '+'-joined name must agree.  KeyError for the forms of FORM_KAPPA."""
+    fams = {FORM_FAMILY[part] for part in name.split("+")}
+    if len(fams) != 1:
+        raise KeyError(f"{name}: segments of different families {sorted(fams)}")
+    return fams.pop()
+
+
+def check_form(name, form, got, ref, mag, tile=None, ref32=None):
+    """`check` under the family of the form that ran; for a form of FORM_KAPPA `check_decoder` against ref32, (a function returning)
+    torch's fp32 CPU evaluation of the same operation on the same inputs."""
+    if form in FORM_KAPPA:
+        if ref32 is None:
+            raise StageError(f"{name} [{form}]: this form is held to the fp32 CPU evaluation's error, which the caller did not pass")
+        fam = LIMITS[FORM_KAPPA_FAMILY[form]]
+        check(name, got, ref, mag, Limits(fam.max_z, fam.rms_z, fam.mean_z, float("inf")), tile=tile, form=form)     # all but the slope
+        rec = check_decoder(name, got, ref, ref32() if callable(ref32) else ref32)
+        rec["form"] = form
+        return rec
+    return check(name, got, ref, mag, form_family(form), tile=tile, form=form)

@@ -12,6 +12,15 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+def last_conv_form():
+    """Name of the kernel instantiation the last eemop_conv2d_* call of this thread launched."""
+    import ctypes
+    from eemflow_amd import _lib
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.lib().eemop_last_conv_form(buf, len(buf)))
+    return buf.value.decode()
+
+
 def rel(a, b):
     a, b = a.detach().cpu().double(), b.detach().cpu().double()
     return float((a - b).abs().max() / (b.abs().max() + 1e-12))
@@ -100,8 +109,10 @@ def test_few_output_conv_vs_torch_and_generic_kernel(monkeypatch, cin, cout, h, 
     convd = conv.to(DEV)
     with torch.no_grad():
         few = ops.conv2d(convd, x.to(DEV), act=ops.ACT_LEAKY).cpu()
+        assert last_conv_form().startswith("fewout_")
         monkeypatch.setenv("EEM_NO_FEWOUT", "1")
         gen = ops.conv2d(convd, x.to(DEV), act=ops.ACT_LEAKY).cpu()
+        assert last_conv_form().startswith("generic_")
     scale = float(ref.abs().max())
     assert float((few - ref).abs().max()) < 2e-5 * max(scale, 1.0) * (cin / 32) ** 0.5
     assert float((gen - ref).abs().max()) < 2e-5 * max(scale, 1.0) * (cin / 32) ** 0.5
@@ -119,8 +130,10 @@ def test_sixteen_output_conv_on_the_lds_tiled_kernel(monkeypatch):
     convd = conv.to(DEV)
     with torch.no_grad():
         tiled = ops.conv2d(convd, x.to(DEV), act=ops.ACT_LEAKY).cpu()
+        assert last_conv_form() == "gconv16_3x3_th4_wm1_kg1"
         monkeypatch.setenv("EEM_NO_GCONV16", "1")
         gen = ops.conv2d(convd, x.to(DEV), act=ops.ACT_LEAKY).cpu()
+        assert last_conv_form().startswith("generic_")
     assert float((tiled - ref).abs().max()) < 1e-4 and float((gen - ref).abs().max()) < 1e-4
     assert not torch.equal(tiled, gen)
 
