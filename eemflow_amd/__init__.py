@@ -12,4 +12,5 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 from .eemflow import EEMFlow            # noqa: F401
 from .metrics import fb_check          # noqa: F401
 from .padder import InputPadder         # noqa: F401
+from .viz import ImageWriter, event_image, event_image_many, flow_to_image, flow_to_image_many   # noqa: F401
 from .voxelizer import EventSequence, EventSequenceToVoxelGrid_Pytorch   # noqa: F401

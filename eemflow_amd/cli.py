@@ -7,7 +7,9 @@ Same flags and defaults as the reference scripts (`--lr --wd --train_iters --val
 --start-epoch --num_workers --test_only --test_sequence ...`), the `lr{lr}_we{wd}` run folder, `config.json` / `train.log` /
 `lasted_ckpt.pth.tar` in it, checkpoint loading with 'module.' stripping.  Added: `--data_root` (the reference hard-wires its own
 repository path), `--save_root`, `--checkpoint`, `--config` (a JSON like the reference's config/a_meshflow.json; its training and
-loader defaults are built in).  Dropped: visualisation, xlsx export, git metadata, nn.DataParallel (one process per GPU:
+loader defaults are built in), `test`: `--vis_events --print_epe --visualize_every` (the keywords of the reference's evaluation loop
+that its script leaves at their defaults; `-v` writes the flow images under the run's save folder).  Dropped: the key-map, warped-image
+and HSV visualisations, xlsx export, git metadata, nn.DataParallel (one process per GPU:
 launch with torchrun for data parallelism; see eemflow_amd.parallel).  Only the models built here are accepted: EEMFlow (trained by
 the fused step inside the library), `eraft` (train_EEMFlow_HREM.py:30-32) and `EEMFlow+` (both trained through the reference's own
 statement sequence on the operator-level autograd route, train_mvsec.py:241-258).
@@ -44,7 +46,9 @@ def build_parser():
     sub = p.add_subparsers(dest="command", required=True)
 
     def common(q, train):
-        q.add_argument('-v', '--visualize', action='store_true', help='accepted for compatibility; visualisation is not built')
+        q.add_argument('-v', '--visualize', action='store_true',
+                       help='evaluation: write the colour-wheel images of every estimated and ground-truth flow as JPEG files under '
+                            '<save folder>/<sequence>/test/ (train: accepted, the training loop writes no images)')
         q.add_argument('-n', '--num_workers', default=0, type=int, help='host threads that read and voxelize samples ahead (the reference: DataLoader worker processes); 0 = in the loop')
         q.add_argument('--train_iters', default=6000000 if train else 1000000, type=int, metavar='N', help='number of total iterations')
         q.add_argument('-se', '--start-epoch', action='store_true', help='restart from lasted_ckpt.pth.tar of the run folder')
@@ -72,6 +76,9 @@ def build_parser():
                        help='evaluation, EEMFlow: samples voxelized by one launch sequence and handed to one forward_many call (not in the '
                             'reference; 10 with --frames_in_flight 2 suits one MI355X); the volumes then stay raw and pconv1_1 normalises them')
         if not train:
+            q.add_argument('--vis_events', action='store_true', help='with -v: also the red / blue images of both event volumes, their density in the file name')
+            q.add_argument('--print_epe', action='store_true', help="with -v: the sample's AEE in the name of the estimated flow's file")
+            q.add_argument('--visualize_every', default=1, type=int, metavar='N', help='with -v: every N-th sample only (the reference: every sample)')
             q.add_argument('--stream', default=0, type=int,
                            help='evaluation: walk each sequence window by window, up to N windows per forward_stream call (not in the reference; '
                                 'needs a dataset of consecutive windows - HREM samples are separate files and are refused)')
@@ -186,6 +193,10 @@ def test(args):
     from . import harness
     if args.fb_check is not None and not args.stream:
         raise SystemExit("--fb_check needs --stream N (the backward flow comes from the bidirectional stream)")
+    if (args.vis_events or args.print_epe or args.visualize_every != 1) and not args.visualize:
+        raise SystemExit("--vis_events / --print_epe / --visualize_every qualify -v (--visualize)")
+    if args.visualize_every < 1:
+        raise SystemExit("--visualize_every N: N >= 1")
     from .hrem import HREMEventFlow
     config = load_config(args.config)
     model = build_model(args.model_name, config, training=False)
@@ -209,6 +220,9 @@ def test(args):
         extra["stream"] = args.stream
     if args.fb_check is not None:
         extra["fb_check"] = tuple(args.fb_check)
+    if args.visualize:
+        extra.update(visualize_map=True, vis_events=args.vis_events, print_epe=args.print_epe, visualize_every=args.visualize_every,
+                     save_path=save_path)
     return ev.test_multi_sequence(model, start_epoch + 1, sequence_list=sequences, stride=1, frames_in_flight=args.frames_in_flight,
                                   loader_threads=args.loader_threads, coalesce=coalesce, **extra)
 

@@ -20,6 +20,7 @@ nn.DataParallel.  Unlike the reference, save_checkpoint can also store the step 
 """
 import collections
 import itertools
+import os
 import sys
 
 import torch
@@ -91,29 +92,38 @@ def stream_plan(n_samples, n):
     return plan
 
 
-def stream_chunks(dataset, model, n, dev, fb_check=None):
+def stream_chunks(dataset, model, n, dev, fb_check=None, with_volumes=False):
     """Walk the dataset's current sequence window by window: each window read and voxelized once (dataset.get_windows), each call's
     windows through ONE model.forward_stream, the stream reset at the start.  Yields (sample indices, their targets, their flows) per call.
     fb_check = (alpha1, alpha2[, 'all' | 'obj' | 'out']): the stream runs bidirectionally (EEMFlow; at most 8 windows per call) and a
-    fourth element follows, the samples' forward consistency masks (mask_fw of forward_stream(fb_check=...))."""
+    fourth element follows, the samples' forward consistency masks (mask_fw of forward_stream(fb_check=...)).
+    with_volumes: a last element follows, the samples' (event_volume_old, event_volume_new) as the [1, C, H, W] device tensors the
+    model was given (sample i is windows i and i + 1; the last window of a call is kept for the next call's first sample)."""
     model.reset_stream()
     carry_target = None
+    carry_volume = None
     if fb_check is not None:
         n = min(int(n), getattr(model, "MAX_STREAM_BIDIR", 8))
     for w0, cnt, s0, nflow in stream_plan(len(dataset), n):
         vols, targets = dataset.get_windows(w0, cnt)
+        vols = [v.to(dev)[None].float() for v in vols]
         if fb_check is not None:
-            outs = model.forward_stream([v.to(dev)[None].float() for v in vols], bidirectional=True, fb_check=tuple(fb_check))
+            outs = model.forward_stream(vols, bidirectional=True, fb_check=tuple(fb_check))
         else:
-            outs = model.forward_stream([v.to(dev)[None].float() for v in vols])
+            outs = model.forward_stream(vols)
         pair_targets = ([carry_target] if w0 > 0 else []) + list(targets[:cnt - 1])
         carry_target = targets[cnt - 1]
         if len(outs) != nflow or len(pair_targets) != nflow:
             raise RuntimeError(f"stream_chunks: windows {w0}..{w0 + cnt - 1} gave {len(outs)} flows for {nflow} samples")
+        tail = ()
+        if with_volumes:
+            seq = ([carry_volume] if w0 > 0 else []) + vols
+            carry_volume = vols[-1]
+            tail = ([(seq[i], seq[i + 1]) for i in range(nflow)],)
         if fb_check is not None:
-            yield list(range(s0, s0 + nflow)), pair_targets, [o[1][-1] for o in outs], [o[3][0] for o in outs]
+            yield (list(range(s0, s0 + nflow)), pair_targets, [o[1][-1] for o in outs], [o[3][0] for o in outs]) + tail
         else:
-            yield list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]
+            yield (list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]) + tail
 
 
 class TestRaftEvents:
@@ -134,7 +144,7 @@ class TestRaftEvents:
         return preds[-1]
 
     def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
-                            fb_check=None):
+                            fb_check=None, visualize_map=False, vis_events=False, print_epe=False, visualize_every=1, save_path=None):
         """The evaluation loop of test_mvsec.py:580-597.  It reads the LAST prediction of every sample only (run_network, :1455): a
         model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call.
         stream = n > 0 (stride 1, a model with forward_stream - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset of consecutive windows with
@@ -146,7 +156,22 @@ class TestRaftEvents:
         fb_check = (alpha1, alpha2[, 'all' | 'obj' | 'out']) (needs stream > 0 and a model whose forward_stream is bidirectional:
         EEMFlow): the stream runs in both directions and every per-sample line gains two fields - `fb consistent`, the share of pixels
         the forward-backward check (metrics.fb_check) keeps, and `AEE consistent`, the AEE over those pixels alone (the mask as the
-        event image of the sparse flow_error).  Without it the lines are unchanged."""
+        event image of the sparse flow_error).  Without it the lines are unchanged.
+        visualize_map (the reference's keyword, test_mvsec.py:618-637; all four loops): every visualize_every-th sample (the reference:
+        every one) is written as JPEG files under <save_path>/<sequence>/test/ (the reference's self.save_path is per sequence, :576):
+        <idx>_flow_est.jpg - <idx>_flow_est_<AEE:.3f>.jpg with print_epe - and <idx>_flow_gt.jpg, the colour-wheel images of the
+        estimated and the ground-truth flow (viz.flow_to_image), and with vis_events <idx>_events1_<density:.3f>.jpg and
+        <idx>_events2_..., the red / blue images of both event volumes (viz.event_image); idx is the number the sample's line carries.
+        Per chunk all estimated flows go through one conversion call and all ground truths through one more, on the chunk's stream;
+        the files are encoded by an ImageWriter's threads behind the evaluation.  The key-map images (emap1/2), warp_img and the HSV
+        variant are not built.  Off (the default): lines, numbers and launches are unchanged."""
+        if visualize_map:
+            if not save_path:
+                raise ValueError("visualize_map= needs save_path= (the images go to <save_path>/<sequence>/test/)")
+            if int(visualize_every) < 1:
+                raise ValueError(f"visualize_every must be >= 1, got {visualize_every}")
+        elif vis_events or print_epe:
+            raise ValueError("vis_events= / print_epe= qualify visualize_map=True")
         if fb_check is not None:
             if not stream:
                 raise ValueError("fb_check= needs stream= (the backward flow comes from the bidirectional stream)")
@@ -167,13 +192,18 @@ class TestRaftEvents:
             model.final_only = True
         try:
             extra = {"fb_check": fb_check} if fb_check is not None else {}
+            if visualize_map:
+                extra["visualize"] = dict(vis_events=bool(vis_events), print_epe=bool(print_epe), every=int(visualize_every), save_path=save_path)
             return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce, stream, **extra)
         finally:
             if had is not None:
                 model.final_only = had
+            writer = self.__dict__.pop("_viz_writer", None)
+            if writer is not None:                               # an error left the loop early: the encoder threads still stop
+                writer.close(reraise=False)
 
     def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
-                             fb_check=None):
+                             fb_check=None, visualize=None):
         """coalesce > 1 (a model with forward_many - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset with get_samples): that many samples are read, voxelized by
         ONE voxelizer launch sequence and handed to ONE model.forward_many call - n independent batch-1 samples riding a batch-n chain of
         launches, every sample in its own tensors; raw volumes with a normalisation record (HREMEventFlow(deferred_norm=True)) are
@@ -219,12 +249,45 @@ class TestRaftEvents:
                 self.dataset.change_test_sequence(sequence)
                 pending = collections.deque()
                 fb_extra = {}                                    # fb_check: sample -> (consistent share, sums over the consistent pixels)
+                viz_images = {}                                  # visualize: sample -> its images, converted on the chunk's stream
+                writer = None
+                if visualize is not None:
+                    from . import viz
+                    writer = self._viz_writer = viz.ImageWriter(os.path.join(visualize["save_path"], sequence, "test"))
+
+                def convert(chunk, f_ests, f_gts, volumes, norms=None):
+                    """The chunk's images: ONE conversion call for the estimated flows, one for the ground truths (and one for the
+                    event volumes), on the current stream; volumes: per sample (event_volume_old, event_volume_new) [1, C, H, W]."""
+                    sel = [i_ for i_, idx in enumerate(chunk) if idx % visualize["every"] == 0]
+                    if not sel:
+                        return
+                    est = viz.flow_to_image_many([f_ests[i_].contiguous().float() for i_ in sel])
+                    gt = viz.flow_to_image_many([f_gts[i_].contiguous().float() for i_ in sel])
+                    ev = dens = None
+                    if visualize["vis_events"]:
+                        flat = [volumes[i_][j_] for j_ in (0, 1) for i_ in sel]
+                        recs = [norms[i_][j_] for j_ in (0, 1) for i_ in sel] if norms is not None else None
+                        ev, dens = viz.event_image_many([v_ if recs is not None else v_.contiguous().float() for v_ in flat], recs)
+                    for q_, i_ in enumerate(sel):
+                        viz_images[chunk[i_]] = (est[q_], gt[q_]) + ((ev[q_], ev[len(sel) + q_], dens[q_::len(sel)]) if ev is not None else ())
+
+                def submit(idx, aee):
+                    """test_mvsec.py:618-637: the file names carry the number of the sample's line."""
+                    est, gt, *events = viz_images.pop(idx)
+                    writer.submit('{:d}_flow_est_{:.3f}.jpg'.format(idx + 1, aee) if visualize["print_epe"] else '{:d}_flow_est.jpg'.format(idx + 1), est)
+                    writer.submit('{:d}_flow_gt.jpg'.format(idx + 1), gt)
+                    if events:
+                        d1, d2 = events[2].tolist()
+                        writer.submit('{:d}_events1_{:.3f}.jpg'.format(idx + 1, d1), events[0])
+                        writer.submit('{:d}_events2_{:.3f}.jpg'.format(idx + 1, d2), events[1])
 
                 def retire():
                     nonlocal iters, n_points
                     idx, k, sums, keep = pending.popleft()
                     with torch.cuda.stream(streams[k]):
                         aee, p1, p3, n_points, s_ee, aee_gt, s_gt = flow_error_from_sums(sums)
+                        if idx in viz_images:
+                            submit(idx, aee)
                     for name, v in (("aee", aee), ("sum", s_ee), ("aee_gt", aee_gt), ("sum_gt", s_gt), ("p1", p1), ("p3", p3)):
                         acc[name] += v
                     iters += 1
@@ -248,7 +311,9 @@ class TestRaftEvents:
                     for idx in itertools.islice(ahead, 2 * loader_threads):
                         futures.append(pool.submit(load, idx))
                 count = 0
-                for chunk, targets, f_ests, *fb_masks in (stream_chunks(self.dataset, model, stream, dev, fb_check) if stream else ()):
+                with_vols = {"with_volumes": True} if (visualize is not None and visualize["vis_events"]) else {}
+                for chunk, targets, f_ests, *fb_masks in (stream_chunks(self.dataset, model, stream, dev, fb_check, **with_vols) if stream else ()):
+                    vol_pairs = fb_masks.pop() if with_vols else None
                     f_gts = [t_['flow'].to(dev)[None].float() for t_ in targets]
                     evs_ = [t_['event_valid'].to(dev).sum(0) for t_ in targets] if (sparse and all('event_valid' in t_ for t_ in targets)) else None
                     all_sums = flow_error_sums_many(f_gts, f_ests, evs_, is_car=self.is_car,
@@ -259,6 +324,8 @@ class TestRaftEvents:
                         sums_fb = flow_error_sums_many(f_gts, f_ests, cons, is_car=self.is_car, evaluation_type="sparse")
                         for i_, idx in enumerate(chunk):
                             fb_extra[idx] = (fb_masks[0][i_].mean(), sums_fb[i_])
+                    if visualize is not None:
+                        convert(chunk, f_ests, f_gts, vol_pairs)
                     for i_, idx in enumerate(chunk):
                         pending.append((idx, 0, all_sums[i_], (targets[i_], f_ests[i_], f_gts[i_], evs_[i_] if evs_ is not None else None)))
                     while pending:
@@ -280,6 +347,12 @@ class TestRaftEvents:
                         evs_ = [s_['event_valid'].to(dev).sum(0) for s_ in samples] if (sparse and all('event_valid' in s_ for s_ in samples)) else None
                         all_sums = flow_error_sums_many(f_gts, f_ests, evs_, is_car=self.is_car,        # the chunk's statistics by one launch
                                                         evaluation_type="sparse" if evs_ is not None else "dense")
+                        if visualize is not None:
+                            norms = None
+                            if deferred and visualize["vis_events"]:     # raw volumes: their records normalise them inside the kernel
+                                from .voxelizer import norm_record
+                                norms = [(norm_record(a_), norm_record(b_)) for a_, b_ in frames]
+                            convert(chunk, f_ests, f_gts, frames, norms)
                         for i_, (idx, sample) in enumerate(zip(chunk, samples)):
                             pending.append((idx, k, all_sums[i_], (sample, f_ests[i_], f_gts[i_], evs_[i_] if evs_ is not None else None)))
                     while len(pending) >= nfl * co:
@@ -299,11 +372,17 @@ class TestRaftEvents:
                         f_gt = sample['flow'].to(dev)[None].float()
                         ev = sample['event_valid'].to(dev).sum(0) if ('event_valid' in sample and sparse) else None
                         sums = flow_error_sums(f_gt, f_est, ev, is_car=self.is_car, evaluation_type="sparse" if ev is not None else "dense")
+                        if visualize is not None and idx % visualize["every"] == 0:
+                            vols_ = [(sample['event_volume_old'].to(dev)[None], sample['event_volume_new'].to(dev)[None])] if visualize["vis_events"] else None
+                            convert([idx], [f_est], [f_gt], vols_)
                     pending.append((idx, k, sums, (sample, f_est, f_gt, ev)))     # the tensors stay alive until the sample retires
                     while len(pending) >= nfl:
                         retire()
                 while pending:
                     retire()
+                if writer is not None:
+                    writer.close()                               # joins the encoders; a worker's error surfaces here
+                    del self._viz_writer
                 iters = max(iters, 1)
                 self.logger.write_line("-------------------test_sequence_{:s}------------------".format(sequence), True)
                 self.logger.write_line(

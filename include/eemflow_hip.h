@@ -243,6 +243,29 @@ int eemflow_flow_error_many(int n, const float* const* flow_gt, const float* con
 int eemflow_fb_check_many(int n, const float* const* flow_fw, const float* const* flow_bw, float* const* mask_fw_out,
                           float* const* mask_bw_out, int h, int w, float alpha1, float alpha2, int mode, void* stream);
 
+/* Colour images of n (1..16) flow fields of one size by two launches: flow[i] ([2][h][w] fp32) and image_out[i] ([h][w][3] bytes, RGB,
+ * or BGR with bgr != 0) are HOST arrays of device pointers.  The Middlebury colour wheel, normalised by each frame's own maximum radius:
+ * |u| or |v| > 1e7 is unknown (black, not part of the maximum); maxrad is the fp32 maximum of sqrt(u*u + v*v), or -1 when the frame
+ * holds a NaN; the divisor is (double)maxrad + 2^-52 and the normalised components, radius, angle and wheel interpolation are fp64;
+ * rad <= 1 fades towards white, rad > 1 is darkened by 0.75; NaN pixels are black; a byte is floor(255 * col).
+ * stats (device, n x 4 doubles, initialised by the call): [i][0] receives frame i's divisor, [i][1] is its reduction cell.
+ * Stream-ordered, no host synchronisation, no allocation.
+ * Replaces: tensor_tools.flow_to_image_dmax (utils_luo/tools.py:2385-2523) as Test.visualize_optical_flow_light calls it in the
+ * evaluation loop (test_mvsec.py:618-629). */
+int eemflow_flow_to_image_many(int n, const float* const* flow, uint8_t* const* image_out, double* stats, int h, int w, int bgr,
+                               void* stream);
+
+/* Red / blue event images of n (1..16) event volumes of one size by two launches: volume[i] ([bins][h][w] fp32) and image_out[i]
+ * ([h][w][3] bytes) are HOST arrays of device pointers.  s = the channel sum (fp32, channel order); white background, s <= mean(s) - 0.2
+ * is [255, 0, 0], s >= mean(s) + 0.2 is [0, 0, 255] (painted last); the mean is taken in fp64 and rounded to fp32 once.  norm: NULL
+ * (normalised volumes) or a HOST array of device pointers to each raw grid's record {mean, sd, scale, any} (eemflow_voxelize with
+ * normalize = 2): non-zero voxels are normalised as the first convolution does before they are summed.
+ * stats (device, n x 4 doubles, initialised by the call): [i][0] receives the density count(s > 0.1) / (h*w), [i][1] the sum of s,
+ * [i][2] the count.  bgr != 0 writes the channels in reverse order.  Stream-ordered, no host synchronisation, no allocation.
+ * Replaces: Test.vis_map_RGB (test_mvsec.py:175-233), up to the array it hands to cv2.imwrite. */
+int eemflow_event_image_many(int n, const float* const* volume, const float* const* norm, int bins, int h, int w,
+                             uint8_t* const* image_out, double* stats, int bgr, void* stream);
+
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
  * receive, per event, the int64 flat index x + y*w + bin*w*h of the left / right temporal vote, or -1
