@@ -362,6 +362,10 @@ struct TailHeadArgs {
     int tap[TAIL_HEAD_MAX_TAPS]; // filled by the launcher from taps_host: the selected taps of the 9x9 window (EEMFlow.py:14-23)
 };
 int tail_head_launch(const TailHeadArgs& a, const int* taps_host, hipStream_t stream);
+// the same launch with every pooled value formed once per block and the correlation / rconv operands read from LDS (batched calls;
+// bitwise tail_head_launch's outputs).  Supported: fused partial sums with rows 4 / 2 / 1 of 16 / 32 / 64 channels, 53 taps, <= 240 cells
+bool tail_head_lds_supported(const TailHeadArgs& a);
+int tail_head_lds_launch(const TailHeadArgs& a, const int* taps_host, hipStream_t stream);
 // The head of a stream of consecutive windows (eemflow_forward_stream): `base.src` holds this call's images 0..nimg-1 and pair b compares
 // image i2 - 1 with image i2 = b + i2_off (i2_off 1: the pairs (0, 1), (1, 2), ...; 0: pair 0 starts at the carried window).  An image
 // index below 0 is the carried window, read from `carry` (finished maps [c][gh][gw]: rows 1, scale 1 - the value the pooled-map role

@@ -19,6 +19,8 @@
 //   EEM_S2R            per launch (s2r_wanted; conv_s2r.hip)    off       1: the stride-2 layers on conv_s2r.hip
 //   EEM_BX3_S1         per launch (bx3_wanted; conv_bx3.hip)    0         <mask>: stride-1 layers on conv_bx3.hip (bit 0: C = 32, 1: C = 64)
 //   EEM_DEC_WNC        per call (dec_wnc_wanted)                unset     0: off, 1: at every batch, unset: from batch 4 on
+//   EEM_TAIL_HEAD_LDS  per schedule build (tail_head_lds_wanted) unset    0: tail_head_kernel always, 1: the LDS form wherever it is
+//                                                                         supported, unset: from four frames per launch on
 //   EEM_FUSE12         per schedule build (run_enc12) and per   off       1: pconv1_1 + pconv1_2 as one launch (a cached graph keeps
 //                      alloc_workspace (its block scratch)                the form it was captured with)
 //   EEM_ZIGZAG         once per process (enc_walk)              0         <layer mask>: images back to front
@@ -52,6 +54,16 @@ bool dec_wnc_wanted(const eemflow_ctx* c, int gw, int batch) {
     const char* e = getenv("EEM_DEC_WNC");
     if (c->dec_wnc == nullptr || gw % 4 != 0 || (e && e[0] == '0')) return false;
     return (e && e[0] == '1') || batch >= 4;
+}
+// The tail head's LDS form (tail_fused.hip: every pooled value formed once per block, correlation and rconv operands from LDS) for
+// batched launches that are no stream call, where the launch supports the shapes (tail_head_lds_supported: the three stages' fused
+// partial sums, kTaps53 - the only list this schedule passes -, at most 240 cells), from four frames per launch on - the decoders' rule:
+// one frame alone is 21 blocks that each pay the chunk walk where tail_head_kernel's gathers are all in flight at once.  The two forms'
+// outputs are bitwise equal.  EEM_TAIL_HEAD_LDS (read per schedule build): 0 never, 1 wherever it is supported, unset: by batch.
+static bool tail_head_lds_wanted(const Shape& s, const TailHeadArgs& ha) {
+    const char* e = getenv("EEM_TAIL_HEAD_LDS");
+    if (s.stream || !tail_head_lds_supported(ha) || (e && e[0] == '0')) return false;
+    return (e && e[0] == '1') || s.batch >= 4;
 }
 
 // The order in which a layer's blocks walk its tiles, its non-temporal stores and its grid under several frames in flight: the fields
@@ -509,8 +521,10 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
             }
             ha.batch = s.batch; ha.gh = s.gh; ha.gw = s.gw; ha.ntaps = kNTaps; ha.cat_ctotal = kDecIn;
             const double fl = 2.0 * s.batch * g * (kNTaps * (16 + 32 + 64) + 16.0 * 9 * (16 + 32 + 64));
-            rc = hk.run("tail head: pool+corr53+rconv", fl, 4.0 * (fin_elems + 3.0 * s.batch * g * kDecIn),
-                        [&](hipStream_t st) { return tail_head_launch(ha, kTaps53, st); });
+            const bool lds_form = tail_head_lds_wanted(s, ha);
+            rc = hk.run("tail head: pool+corr53+rconv", fl, 4.0 * (fin_elems + 3.0 * s.batch * g * kDecIn), [&](hipStream_t st) {
+                return lds_form ? tail_head_lds_launch(ha, kTaps53, st) : tail_head_launch(ha, kTaps53, st);
+            });
             if (rc != EEM_OK) return rc;
         } else {
             if (nf) {

@@ -197,6 +197,237 @@ __global__ __launch_bounds__(576) void tail_head_stream_kernel(TailHeadStreamArg
     tail_head_body<true>(a.base, a.carry, a.i2_off, a.nfw, a.pool_img);
 }
 
+// ------------------------------------------------------------------------------------------------ tail head, LDS form
+// The same launch for batched calls (tail_head_lds_wanted, schedule.hip).  tail_head_kernel fetches a pooled value once per tap that
+// reaches it - 128 four-byte gathers per (pixel, tap) - and a third of its grid exits at once; at ten frames per launch that is
+// 6 678 blocks and 49 M lane loads for 0.5 M pooled values.  Here a block owns one (frame, stage) and either a group of THL_TG taps
+// (correlation) or THL_RT pixel tiles (rconv); thread p owns cell p of the 1/64 grid.  The block walks the stage's channels in chunks
+// of CH: every thread requests the partial sums of its own cell for the NEXT chunk into registers, pools the current ones by
+// pooled_load's expression and puts them in LDS ([CH][THL_G] floats, 7.5 KB), and all neighbours' values - the correlation's second
+// image, the rconv's B operands - come from there.  The correlation's first image is the thread's own cell and stays in registers.
+// Tap group 0 also writes the finished pooled maps.  Every block has work.  131 VGPRs, no scratch.
+// Measured at ten frames per launch (profiles/r07_tail_head.txt): 35.3 -> 18.1 us alone, 270 blocks for 6 678.  What is left is the
+// chain of round trips - 4 / 4 / 8 chunks per stage, each waiting for its partial sums; the same time with the requests issued
+// after the barriers, with 9 / 14 / 18 taps per block, with two tiles per rconv wave, and with the blocks of a (frame, stage) on one XCD.
+// Bitwise tail_head_kernel: four fmaf chains over c = r (mod 4) in ascending order carried across chunks, (s0 + s1) + (s2 + s3),
+// a true division by cin; the rconv's MFMA sequence per tap over ascending channel groups, taps added 0..8, bias, LeakyReLU.
+constexpr int THL_G = 240;          // cells the LDS chunk is sized for (1280x720: 12 x 20)
+constexpr int THL_TG = 11;          // taps per correlation block (53 taps: five blocks)
+constexpr int THL_RT = 4;           // 16-pixel tiles per rconv block: one per wave
+constexpr int THL_THREADS = 256;    // >= THL_G
+constexpr int THL_TPW = THL_RT / (THL_THREADS / 64);
+
+// buffer loads: the image (or the weights) as the resource, the lane's cell as the one vector offset, channel and row in the scalar
+// offset - a load's address costs no vector registers, and 32 of them are in flight per thread
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t thl_rsrc(const float* base, int floats) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, floats * 4, 0x00020000);
+}
+template <int CH, int ROWS>
+__device__ __forceinline__ void thl_request(const PooledSrc& s, __amdgpu_buffer_rsrc_t img, int cell, int c0, float (&r)[CH * ROWS]) {
+#pragma unroll
+    for (int q = 0; q < CH; ++q)
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i)
+            r[q * ROWS + i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(img, cell, ((c0 + q) * s.cstride + i * s.rstride) * 4, 0));
+}
+template <int ROWS>
+__device__ __forceinline__ float thl_pool(const float* r, float scale) {    // pooled_load's sum order
+    float v = r[0];
+#pragma unroll
+    for (int i = 1; i < ROWS; ++i) v += r[i];
+    return v * scale;
+}
+
+template <int CIN, int CH, int ROWS>
+__device__ __forceinline__ void thl_corr(const TailHeadArgs& a, int k, int b, int tg, float* lds) {
+    const PooledSrc src = a.src[k];
+    float* cat = a.cat[k];
+    float* pool_out = tg == 0 ? a.pool_out[k] : nullptr;
+    const int gw = a.gw, gh = a.gh, batch = a.batch, ntaps = a.ntaps;
+    const float cinf = (float)a.c[k];
+    const int g = gh * gw;
+    const int p = threadIdx.x;
+    const bool live = p < g;
+    const int pc = live ? p : 0;                                          // idle lanes follow cell 0 and store nothing
+    const int y = pc / gw, x = pc - y * gw;
+    const int cell = 4 * (y * src.ystride + x);
+    const __amdgpu_buffer_rsrc_t c1 = thl_rsrc(src.base + (size_t)b * src.nstride, src.nstride);
+    const __amdgpu_buffer_rsrc_t c2 = thl_rsrc(src.base + (size_t)(batch + b) * src.nstride, src.nstride);
+    constexpr int NR = CH * ROWS;
+    float ru[NR], rv[NR];
+    thl_request<CH, ROWS>(src, c1, cell, 0, ru);
+    thl_request<CH, ROWS>(src, c2, cell, 0, rv);
+    const int t0 = tg * THL_TG;
+    int idx[THL_TG];
+    unsigned ok_mask = 0;
+#pragma unroll
+    for (int t = 0; t < THL_TG; ++t) {
+        const int tap = a.tap[t0 + t < ntaps ? t0 + t : 0];
+        const int yy = y + tap / 9 - 4, xx = x + tap % 9 - 4;
+        const bool ok = live && t0 + t < ntaps && yy >= 0 && yy < gh && xx >= 0 && xx < gw;
+        idx[t] = ok ? yy * gw + xx : pc;                                  // an out-of-grid tap reads a cell that exists; its sum is dropped
+        ok_mask |= (ok ? 1u : 0u) << t;
+    }
+    float acc[THL_TG][4];
+#pragma unroll
+    for (int t = 0; t < THL_TG; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[t][r] = 0.f;
+    const __amdgpu_buffer_rsrc_t po1 = thl_rsrc(pool_out ? pool_out + (size_t)b * CIN * g : nullptr, pool_out ? CIN * g : 0);
+    const __amdgpu_buffer_rsrc_t po2 = thl_rsrc(pool_out ? pool_out + (size_t)(batch + b) * CIN * g : nullptr, pool_out ? CIN * g : 0);
+#pragma unroll 1
+    for (int c0 = 0; c0 < CIN; c0 += CH) {
+        float u[CH], v[CH];
+#pragma unroll
+        for (int q = 0; q < CH; ++q) {
+            u[q] = thl_pool<ROWS>(ru + q * ROWS, src.scale);
+            v[q] = thl_pool<ROWS>(rv + q * ROWS, src.scale);
+        }
+        if (c0 + CH < CIN) {                                              // in flight while this chunk is consumed
+            thl_request<CH, ROWS>(src, c1, cell, c0 + CH, ru);
+            thl_request<CH, ROWS>(src, c2, cell, c0 + CH, rv);
+        }
+        if (c0) __syncthreads();                                          // the last chunk's readers are done
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < CH; ++q) lds[q * THL_G + p] = v[q];
+            if (pool_out) {
+#pragma unroll
+                for (int q = 0; q < CH; ++q) {
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(u[q]), po1, p * 4, (c0 + q) * g * 4, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[q]), po2, p * 4, (c0 + q) * g * 4, 0);
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < THL_TG; ++t)
+#pragma unroll
+            for (int q = 0; q < CH; ++q) acc[t][q & 3] = fmaf(u[q], lds[q * THL_G + idx[t]], acc[t][q & 3]);
+    }
+    if (!live) return;
+#pragma unroll
+    for (int t = 0; t < THL_TG; ++t) {
+        const float s = (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
+        if (t0 + t < ntaps) cat[((size_t)b * a.cat_ctotal + t0 + t) * g + p] = ((ok_mask >> t) & 1u) ? s / cinf : 0.f;
+    }
+}
+
+// wave w of rconv block rb = pixel tiles rb * THL_RT + THL_TPW w ..., all nine filter taps of each: an accumulator per (tile, tap),
+// carried over the chunks
+template <int CIN, int CH, int ROWS>
+__device__ __forceinline__ void thl_rconv(const TailHeadArgs& a, int k, int b, int rblk, float* lds) {
+    const PooledSrc src = a.src[k];
+    const float* rw = a.rw[k];
+    const float* rb = a.rb[k];
+    float* cat = a.cat[k];
+    const int gw = a.gw, gh = a.gh;
+    const int g = gh * gw;
+    const int p = threadIdx.x;
+    const bool live = p < g;
+    const int pc = live ? p : 0;
+    const int y = pc / gw, x = pc - y * gw;
+    const int cell = 4 * (y * src.ystride + x);
+    const __amdgpu_buffer_rsrc_t c1 = thl_rsrc(src.base + (size_t)b * src.nstride, src.nstride);   // events1 half: image b
+    const __amdgpu_buffer_rsrc_t wr = thl_rsrc(rw, 9 * CIN * 16);
+    constexpr int NR = CH * ROWS, QN = CH / 4, CG = CIN / 4;
+    float ru[NR];
+    thl_request<CH, ROWS>(src, c1, cell, 0, ru);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = lane & 15, gq = lane >> 4;
+    float awn[QN][9];
+#pragma unroll
+    for (int qq = 0; qq < QN; ++qq)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) awn[qq][t] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wr, lane * 4, (t * CG + qq) * 256, 0));
+    const int ptiles = ceil_div(g, 16);
+    const int tile0 = rblk * THL_RT + wave * THL_TPW;
+    int py[THL_TPW], px[THL_TPW], pp[THL_TPW];
+    bool pv[THL_TPW];
+#pragma unroll
+    for (int m = 0; m < THL_TPW; ++m) {
+        pp[m] = (tile0 + m) * 16 + j;
+        pv[m] = tile0 + m < ptiles && pp[m] < g;
+        py[m] = pp[m] / gw;
+        px[m] = pp[m] - py[m] * gw;
+    }
+    f32x4 acc[THL_TPW][9];
+#pragma unroll
+    for (int m = 0; m < THL_TPW; ++m)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int c0 = 0; c0 < CIN; c0 += CH) {
+        float u[CH], aw[QN][9];
+#pragma unroll
+        for (int q = 0; q < CH; ++q) u[q] = thl_pool<ROWS>(ru + q * ROWS, src.scale);
+#pragma unroll
+        for (int qq = 0; qq < QN; ++qq)
+#pragma unroll
+            for (int t = 0; t < 9; ++t) aw[qq][t] = awn[qq][t];
+        if (c0 + CH < CIN) {
+            thl_request<CH, ROWS>(src, c1, cell, c0 + CH, ru);
+#pragma unroll
+            for (int qq = 0; qq < QN; ++qq)
+#pragma unroll
+                for (int t = 0; t < 9; ++t) awn[qq][t] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wr, lane * 4, (t * CG + (c0 + CH) / 4 + qq) * 256, 0));
+        }
+        if (c0) __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < CH; ++q) lds[q * THL_G + p] = u[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int qq = 0; qq < QN; ++qq)
+#pragma unroll
+            for (int m = 0; m < THL_TPW; ++m)
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int yy = py[m] + t / 3 - 1, xx = px[m] + t % 3 - 1;
+                    const bool ok = pv[m] && yy >= 0 && yy < gh && xx >= 0 && xx < gw;
+                    const float bv = lds[(qq * 4 + gq) * THL_G + (ok ? yy * gw + xx : 0)];
+                    acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[qq][t], ok ? bv : 0.f, acc[m][t], 0, 0, 0);
+                }
+    }
+    float bs[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bs[r] = rb[gq * 4 + r];
+#pragma unroll
+    for (int m = 0; m < THL_TPW; ++m) {
+        f32x4 s = acc[m][0];
+#pragma unroll
+        for (int t = 1; t < 9; ++t) s += acc[m][t];                       // tail_head_kernel's order
+        if (pv[m]) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int co = gq * 4 + r;
+                float v = s[r] + bs[r];
+                v = v > 0.f ? v : 0.1f * v;
+                cat[((size_t)b * a.cat_ctotal + a.ntaps + co) * g + pp[m]] = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(THL_THREADS, 3) void tail_head_lds_kernel(TailHeadArgs a) {
+    __shared__ float lds[8 * THL_G];
+    const int ntg = ceil_div(a.ntaps, THL_TG);
+    const int per = ntg + ceil_div(ceil_div(a.gh * a.gw, 16), THL_RT);    // blocks of one (frame, stage)
+    const int fs = blockIdx.x / per, r = blockIdx.x - fs * per;
+    const int b = fs / 3, k = fs - 3 * b;
+    if (r < ntg) {
+        if (k == 0) thl_corr<16, 4, 4>(a, 0, b, r, lds);
+        else if (k == 1) thl_corr<32, 8, 2>(a, 1, b, r, lds);
+        else thl_corr<64, 8, 1>(a, 2, b, r, lds);
+    } else {
+        if (k == 0) thl_rconv<16, 4, 4>(a, 0, b, r - ntg, lds);
+        else if (k == 1) thl_rconv<32, 8, 2>(a, 1, b, r - ntg, lds);
+        else thl_rconv<64, 8, 1>(a, 2, b, r - ntg, lds);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ conv7 + out_conv + upsample
 // F.interpolate(mode='bilinear', align_corners=False): src = max(scale*(dst+0.5)-0.5, 0)   (same arithmetic as upsample_kernel)
 __device__ __forceinline__ void src_index2(float scale, int dst, int in_size, int& i0, int& i1, float& l1) {
@@ -307,6 +538,29 @@ int tail_head_launch(const TailHeadArgs& a0, const int* taps_host, hipStream_t s
     const int rc = tail_head_prepare(a, taps_host, 2 * a.batch);
     if (rc != EEM_OK) return rc;
     hipLaunchKernelGGL(tail_head_kernel, dim3(a.grid_x, a.ntaps, 7), dim3(576), 0, stream, a);
+    EEM_HIP_CHECK(hipGetLastError());
+    return EEM_OK;
+}
+
+// the LDS form takes the fused partial sums of the three stages as the encoder's pooling epilogues leave them (rows 4 / 2 / 1 of
+// 16 / 32 / 64 channels), the 53 taps, and a grid whose cells one block's threads and one LDS chunk hold
+bool tail_head_lds_supported(const TailHeadArgs& a) {
+    static const int kRows[3] = {4, 2, 1}, kCin[3] = {16, 32, 64};
+    if (a.batch < 1 || a.gh < 1 || a.gw < 1 || a.gh * a.gw > THL_G || a.ntaps != 53) return false;
+    for (int k = 0; k < 3; ++k)
+        if (a.src[k].rows != kRows[k] || a.c[k] != kCin[k]) return false;
+    return true;
+}
+
+int tail_head_lds_launch(const TailHeadArgs& a0, const int* taps_host, hipStream_t stream) {
+    TailHeadArgs a = a0;
+    EEM_REQUIRE(tail_head_lds_supported(a), "tail_head_lds_launch: batch=%d grid=%dx%d ntaps=%d rows=%d/%d/%d", a.batch, a.gh, a.gw, a.ntaps,
+                a.src[0].rows, a.src[1].rows, a.src[2].rows);
+    for (int i = 0; i < a.ntaps; ++i) a.tap[i] = taps_host[i];
+    const int per = ceil_div(a.ntaps, THL_TG) + ceil_div(ceil_div(a.gh * a.gw, 16), THL_RT);
+    const int blocks = a.batch * 3 * per;
+    EEM_NOTE_GRID(blocks, THL_THREADS);
+    hipLaunchKernelGGL(tail_head_lds_kernel, dim3(blocks), dim3(THL_THREADS), 0, stream, a);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
