@@ -8,7 +8,8 @@ Same flags and defaults as the reference scripts (`--lr --wd --train_iters --val
 `lasted_ckpt.pth.tar` in it, checkpoint loading with 'module.' stripping.  Added: `--data_root` (the reference hard-wires its own
 repository path), `--save_root`, `--checkpoint`, `--config` (a JSON like the reference's config/a_meshflow.json; its training and
 loader defaults are built in), `test`: `--vis_events --print_epe --visualize_every` (the keywords of the reference's evaluation loop
-that its script leaves at their defaults; `-v` writes the flow images under the run's save folder).  Dropped: the key-map, warped-image
+that its script leaves at their defaults; `-v` writes the flow images under the run's save folder), `--fwl` (the flow warp loss of
+Test.inference_img_warp_loss, test_mvsec.py:753-852, as a field of every evaluation line).  Dropped: the key-map, warped-image
 and HSV visualisations, xlsx export, git metadata, nn.DataParallel (one process per GPU:
 launch with torchrun for data parallelism; see eemflow_amd.parallel).  Only the models built here are accepted: EEMFlow (trained by
 the fused step inside the library), `eraft` (train_EEMFlow_HREM.py:30-32) and `EEMFlow+` (both trained through the reference's own
@@ -76,6 +77,9 @@ def build_parser():
                        help='evaluation, EEMFlow: samples voxelized by one launch sequence and handed to one forward_many call (not in the '
                             'reference; 10 with --frames_in_flight 2 suits one MI355X); the volumes then stay raw and pconv1_1 normalises them')
         if not train:
+            q.add_argument('--fwl', action='store_true',
+                           help='evaluation: add the flow warp loss of every sample - the variance of the image of its events warped by the '
+                                'estimated flow over the variance of the event-count image, no ground truth needed - to every line')
             q.add_argument('--vis_events', action='store_true', help='with -v: also the red / blue images of both event volumes, their density in the file name')
             q.add_argument('--print_epe', action='store_true', help="with -v: the sample's AEE in the name of the estimated flow's file")
             q.add_argument('--visualize_every', default=1, type=int, metavar='N', help='with -v: every N-th sample only (the reference: every sample)')
@@ -211,7 +215,7 @@ def test(args):
     dev = torch.device(args.device)
     coalesce = args.coalesce if args.model_name == 'EEMFlow' else 1      # (forward_many is EEMFlow's)
     test_set = HREMEventFlow(args=config["data_loader"]["test"]["args"], train=False, root=args.data_root, device=dev,
-                             deferred_norm=coalesce > 1)
+                             deferred_norm=coalesce > 1, with_events=args.fwl)
     model = model.to(dev)
     sequences = [args.test_sequence] if args.test_sequence else list(test_set.nori_list.keys())
     ev = harness.TestRaftEvents(test_set, tuple(config["val_img_size"]), logger=logger)
@@ -220,6 +224,8 @@ def test(args):
         extra["stream"] = args.stream
     if args.fb_check is not None:
         extra["fb_check"] = tuple(args.fb_check)
+    if args.fwl:
+        extra["fwl"] = True
     if args.visualize:
         extra.update(visualize_map=True, vis_events=args.vis_events, print_epe=args.print_epe, visualize_every=args.visualize_every,
                      save_path=save_path)

@@ -144,7 +144,7 @@ class TestRaftEvents:
         return preds[-1]
 
     def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
-                            fb_check=None, visualize_map=False, vis_events=False, print_epe=False, visualize_every=1, save_path=None):
+                            fb_check=None, visualize_map=False, vis_events=False, print_epe=False, visualize_every=1, save_path=None, fwl=False):
         """The evaluation loop of test_mvsec.py:580-597.  It reads the LAST prediction of every sample only (run_network, :1455): a
         model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call.
         stream = n > 0 (stride 1, a model with forward_stream - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset of consecutive windows with
@@ -164,7 +164,16 @@ class TestRaftEvents:
         <idx>_events2_..., the red / blue images of both event volumes (viz.event_image); idx is the number the sample's line carries.
         Per chunk all estimated flows go through one conversion call and all ground truths through one more, on the chunk's stream;
         the files are encoded by an ImageWriter's threads behind the evaluation.  The key-map images (emap1/2), warp_img and the HSV
-        variant are not built.  Off (the default): lines, numbers and launches are unchanged."""
+        variant are not built.  Off (the default): lines, numbers and launches are unchanged.
+        fwl (all four loops; a dataset built with with_events=True): the flow warp loss of every sample's last prediction - the
+        variance of the image of the old window's events warped by the flow over the variance of their count image
+        (eemflow_amd.iwe.fwl_many, t_ref="end"; the measure of Test.inference_img_warp_loss, test_mvsec.py:753-852, which needs no
+        ground truth) - by ONE fwl_many call per chunk on the chunk's stream.  Every per-sample line gains
+        '  FWL: {:2.6f}  meanFWL:{:2.6f}' (NaN samples - a constant count image - are left out of the mean) and every sequence one
+        summary line "Mean FWL: {:.6f}".  Off (the default): lines, numbers and launches are unchanged."""
+        if fwl and not getattr(self.dataset, "with_events", False):
+            raise ValueError(f"fwl= needs a dataset whose samples carry their events (with_events=True: MvsecEventFlow, MvsecEventFlow_dt4, "
+                             f"HREMEventFlow); {type(self.dataset).__name__} was built without")
         if visualize_map:
             if not save_path:
                 raise ValueError("visualize_map= needs save_path= (the images go to <save_path>/<sequence>/test/)")
@@ -192,6 +201,8 @@ class TestRaftEvents:
             model.final_only = True
         try:
             extra = {"fb_check": fb_check} if fb_check is not None else {}
+            if fwl:
+                extra["fwl"] = True
             if visualize_map:
                 extra["visualize"] = dict(vis_events=bool(vis_events), print_epe=bool(print_epe), every=int(visualize_every), save_path=save_path)
             return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce, stream, **extra)
@@ -203,7 +214,7 @@ class TestRaftEvents:
                 writer.close(reraise=False)
 
     def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
-                             fb_check=None, visualize=None):
+                             fb_check=None, visualize=None, fwl=False):
         """coalesce > 1 (a model with forward_many - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset with get_samples): that many samples are read, voxelized by
         ONE voxelizer launch sequence and handed to ONE model.forward_many call - n independent batch-1 samples riding a batch-n chain of
         launches, every sample in its own tensors; raw volumes with a normalisation record (HREMEventFlow(deferred_norm=True)) are
@@ -250,6 +261,17 @@ class TestRaftEvents:
                 pending = collections.deque()
                 fb_extra = {}                                    # fb_check: sample -> (consistent share, sums over the consistent pixels)
                 viz_images = {}                                  # visualize: sample -> its images, converted on the chunk's stream
+                fwl_extra = {}                                   # fwl: sample -> its flow warp loss (a 0-dim device tensor)
+                fwl_count = 0
+
+                def warp_loss(chunk, carriers, f_ests):
+                    """The chunk's flow warp losses by ONE fwl_many call on the current stream; carriers: the samples (or stream
+                    targets), each with its 'events' and 'events_offset'."""
+                    from .iwe import fwl_many     # (the package's attribute `iwe` is the one-job function, not the module)
+                    vals = fwl_many([c_['events'] for c_ in carriers], [f_[0].contiguous().float() for f_ in f_ests],
+                                        offset=carriers[0]['events_offset'])
+                    for i_, idx in enumerate(chunk):
+                        fwl_extra[idx] = vals[i_]
                 writer = None
                 if visualize is not None:
                     from . import viz
@@ -282,10 +304,11 @@ class TestRaftEvents:
                         writer.submit('{:d}_events2_{:.3f}.jpg'.format(idx + 1, d2), events[1])
 
                 def retire():
-                    nonlocal iters, n_points
+                    nonlocal iters, n_points, fwl_count
                     idx, k, sums, keep = pending.popleft()
                     with torch.cuda.stream(streams[k]):
                         aee, p1, p3, n_points, s_ee, aee_gt, s_gt = flow_error_from_sums(sums)
+                        fwl_val = float(fwl_extra.pop(idx)) if idx in fwl_extra else None
                         if idx in viz_images:
                             submit(idx, aee)
                     for name, v in (("aee", aee), ("sum", s_ee), ("aee_gt", aee_gt), ("sum_gt", s_gt), ("p1", p1), ("p3", p3)):
@@ -296,6 +319,11 @@ class TestRaftEvents:
                     if idx in fb_extra:
                         share, sums_fb = fb_extra.pop(idx)
                         line += '  fb consistent: {:.6f}  AEE consistent: {:2.6f}'.format(float(share), flow_error_from_sums(sums_fb)[0])
+                    if fwl_val is not None:
+                        if fwl_val == fwl_val:                   # NaN (a constant count image) stays out of the mean
+                            acc["fwl"] += fwl_val
+                            fwl_count += 1
+                        line += '  FWL: {:2.6f}  meanFWL:{:2.6f}'.format(fwl_val, acc["fwl"] / fwl_count if fwl_count else float("nan"))
                     print(line)
 
                 indices = [idx for idx in range(len(self.dataset)) if idx % stride == 0]
@@ -324,6 +352,8 @@ class TestRaftEvents:
                         sums_fb = flow_error_sums_many(f_gts, f_ests, cons, is_car=self.is_car, evaluation_type="sparse")
                         for i_, idx in enumerate(chunk):
                             fb_extra[idx] = (fb_masks[0][i_].mean(), sums_fb[i_])
+                    if fwl:
+                        warp_loss(chunk, targets, f_ests)
                     if visualize is not None:
                         convert(chunk, f_ests, f_gts, vol_pairs)
                     for i_, idx in enumerate(chunk):
@@ -347,6 +377,8 @@ class TestRaftEvents:
                         evs_ = [s_['event_valid'].to(dev).sum(0) for s_ in samples] if (sparse and all('event_valid' in s_ for s_ in samples)) else None
                         all_sums = flow_error_sums_many(f_gts, f_ests, evs_, is_car=self.is_car,        # the chunk's statistics by one launch
                                                         evaluation_type="sparse" if evs_ is not None else "dense")
+                        if fwl:
+                            warp_loss(chunk, samples, f_ests)
                         if visualize is not None:
                             norms = None
                             if deferred and visualize["vis_events"]:     # raw volumes: their records normalise them inside the kernel
@@ -372,6 +404,8 @@ class TestRaftEvents:
                         f_gt = sample['flow'].to(dev)[None].float()
                         ev = sample['event_valid'].to(dev).sum(0) if ('event_valid' in sample and sparse) else None
                         sums = flow_error_sums(f_gt, f_est, ev, is_car=self.is_car, evaluation_type="sparse" if ev is not None else "dense")
+                        if fwl:
+                            warp_loss([idx], [sample], [f_est])
                         if visualize is not None and idx % visualize["every"] == 0:
                             vols_ = [(sample['event_volume_old'].to(dev)[None], sample['event_volume_new'].to(dev)[None])] if visualize["vis_events"] else None
                             convert([idx], [f_est], [f_gt], vols_)
@@ -390,6 +424,8 @@ class TestRaftEvents:
                     "3 - mean %AEE: {:.6f}, # pts: {:.6f}".format(acc["aee"] / iters, acc["sum"] / iters, acc["aee_gt"] / iters,
                                                                   acc["sum_gt"] / iters, 1. - acc["p1"] / iters,
                                                                   1. - acc["p3"] / iters, n_points), True)
+                if fwl:
+                    self.logger.write_line("Mean FWL: {:.6f}".format(acc["fwl"] / fwl_count if fwl_count else float("nan")), True)
                 mean_aee += acc["aee"] / iters
                 mean_out += 1. - acc["p3"] / iters
                 aee_list.append(acc["aee"] / iters)

@@ -138,14 +138,18 @@ class HREMEventFlow(torch.utils.data.Dataset):
     image_width = 1280
     image_height = 720
 
-    def __init__(self, args, train=True, root=None, device=None, to_cpu=False, augmentor=None, deferred_norm=False):
-        """deferred_norm (evaluation, GPU-resident samples): the event volumes stay RAW with their normalisation record behind them
+    def __init__(self, args, train=True, root=None, device=None, to_cpu=False, augmentor=None, deferred_norm=False, with_events=False):
+        """with_events: every sample also carries 'events', the OLD event set's (N,4) float64 device tensor [t, x, y, p] - uploaded once,
+        the voxelizer reads the same tensor - and 'events_offset' = (0, 0) (HREM frames are not cropped): what eemflow_amd.iwe.fwl_many
+        takes beside the predicted flow.
+        deferred_norm (evaluation, GPU-resident samples): the event volumes stay RAW with their normalisation record behind them
         (voxelizer normalize='deferred') for a model that normalises as it reads - EEMFlow.forward_many(..., deferred_norm=True),
         which harness.TestRaftEvents.test_multi_sequence(coalesce=...) calls when the samples say so (`sample['deferred_norm']`)."""
         super().__init__()
         if deferred_norm and (train or to_cpu):
             raise ValueError("deferred_norm is the evaluation route with samples resident on the GPU (train=False, to_cpu=False)")
         self.deferred_norm = bool(deferred_norm)
+        self.with_events = bool(with_events)
         self.input_type = 'events'
         self.type = 'train' if train else 'val'
         self.evaluation_type = args['eval_type']
@@ -199,6 +203,9 @@ class HREMEventFlow(torch.utils.data.Dataset):
         params = {'height': self.image_height, 'width': self.image_width}
         seqs = [EventSequence(None, params, features=get_compressed_events(sample[key]), timestamp_multiplier=1e6,
                               convert_to_relative=True) for key in ('event0', 'event1')]
+        if self.with_events:
+            seqs[0].features = torch.from_numpy(np.ascontiguousarray(seqs[0].features.astype('float'))).to(self.device)
+            out['events'], out['events_offset'] = seqs[0].features, (0, 0)
         return out, seqs
 
     def _attach(self, out, old, new):

@@ -92,8 +92,13 @@ class MvsecEventFlow(torch.utils.data.Dataset):
     consecutive_windows = True
 
     def __init__(self, args, train=True, root=None, device=None, to_cpu=False, augmentor=None, events_reader=None,
-                 valid_time_index=None):
+                 valid_time_index=None, with_events=False):
+        """with_events: every sample (and every target of get_windows) also carries 'events', the OLD window's (N,4) float64 device
+        tensor [t, x, y, p] - uploaded once, the voxelizer reads the same tensor - and 'events_offset', (ox, oy) of the evaluation
+        crop in event coordinates (the centre crop's left / top; (0, 0) for un-cropped training samples): what eemflow_amd.iwe.fwl_many
+        takes beside the predicted flow."""
         super().__init__()
+        self.with_events = bool(with_events)
         self.input_type = 'events'
         self.type = 'train' if train else 'val'
         self.evaluation_type = args['eval_type']
@@ -147,6 +152,19 @@ class MvsecEventFlow(torch.utils.data.Dataset):
         return EventSequence(None, {'height': self.image_height, 'width': self.image_width}, features=feats,
                              timestamp_multiplier=1e6, convert_to_relative=True)
 
+    def _upload(self, seq):
+        """with_events: the sequence's events move to the device once (the voxelizer takes device-resident features); returns the host array."""
+        host = seq.features
+        if self.with_events:
+            seq.features = torch.from_numpy(np.ascontiguousarray(host.astype('float'))).to(self.device)
+        return host
+
+    def _crop_offset(self):
+        """(ox, oy) of center_crop's 256 x 256 evaluation window (its left and top)."""
+        if self.type != 'val':
+            return (0, 0)
+        return (int(round((self.image_width - 256) / 2.0)), int(round((self.image_height - 256) / 2.0)))
+
     def get_sample(self, idx):
         flow = np.load(self.flow_list[idx])
         if flow.shape[-1] == 2:
@@ -156,13 +174,16 @@ class MvsecEventFlow(torch.utils.data.Dataset):
         n = len(self.event_list)
         old = self._sequence([self.event_list[idx + i] for i in range(k)])                      # MVSEC.py:119,247
         new = self._sequence([self.event_list[(idx + i + 1) % n] for i in range(k)])            # :120,251
+        old_host = self._upload(old)
         vol_old, vol_new = self.voxel.pair(old, new)              # both volumes in one three-launch sequence
+        if self.with_events:
+            out['events'], out['events_offset'] = old.features, self._crop_offset()
         if self.to_cpu:
             vol_new, vol_old = vol_new.cpu(), vol_old.cpu()
         out['event_volume_new'] = out['d_event_volume_new'] = vol_new
         out['event_volume_old'] = out['d_event_volume_old'] = vol_old
         if self.type == 'val':
-            out['event_valid'] = torch.from_numpy(event_mask(old.get_sequence_only(), self.image_height,
+            out['event_valid'] = torch.from_numpy(event_mask(old_host, self.image_height,
                                                              self.image_width)).unsqueeze(dim=0)
         return out
 
@@ -181,6 +202,7 @@ class MvsecEventFlow(torch.utils.data.Dataset):
         if first < 0 or count < 1 or first + count > len(self) + 1:
             raise ValueError(f"get_windows: windows {first}..{first + count - 1} of a sequence of {len(self)} samples ({len(self) + 1} windows)")
         seqs = [self._sequence(self._window_paths(j)) for j in range(first, first + count)]
+        hosts = [self._upload(s) for s in seqs]
         vols = self.voxel.many(seqs)
         crop = (256, 256)                                                                       # MVSEC.py:52,193-197
         volumes, targets = [], []
@@ -194,9 +216,11 @@ class MvsecEventFlow(torch.utils.data.Dataset):
             if flow.shape[-1] == 2:
                 flow = flow.transpose(2, 0, 1)
             fl = center_crop(torch.from_numpy(np.ascontiguousarray(flow)), crop)
-            ev = torch.from_numpy(event_mask(seqs[i].get_sequence_only(), self.image_height, self.image_width)).unsqueeze(dim=0)
+            ev = torch.from_numpy(event_mask(hosts[i], self.image_height, self.image_width)).unsqueeze(dim=0)
             targets.append({'idx': self.names[j], 'flow': fl, 'valid': (fl[0].abs() < 1000) & (fl[1].abs() < 1000),
                             'event_valid': center_crop(ev, crop)})
+            if self.with_events:
+                targets[-1]['events'], targets[-1]['events_offset'] = seqs[i].features, self._crop_offset()
         return volumes, targets
 
     def __getitem__(self, idx):

@@ -266,6 +266,28 @@ int eemflow_flow_to_image_many(int n, const float* const* flow, uint8_t* const* 
 int eemflow_event_image_many(int n, const float* const* volume, const float* const* norm, int bins, int h, int w,
                              uint8_t* const* image_out, double* stats, int bgr, void* stream);
 
+/* Warped positions of n events under a flow: events [n][4] f64 (t, x, y, p) on the device, flow [2][h][w] fp32 (NULL: zero flow) ->
+ * warped_xy [n][2] f64.  In unfused fp64: xe = x - ox, ye = y - oy; (u, v) = the bilinear sample of the flow at (xe, ye) in pixel
+ * coordinates (grid_sample with align_corners=True and zero padding: a neighbour outside the frame contributes 0);
+ * tau = (t - t0) * scale; xw = xe + u * tau, yw = ye + v * tau.  With ox = oy = 0 and scale = 1 this is the reference's function.
+ * Replaces: warp_events_flow_torch (utils_luo/event_utils.py:9-51), as Test.inference_img_warp_loss calls it (test_mvsec.py:753-852). */
+int eemflow_warp_events(const double* events, int64_t n, const float* flow, int h, int w, double t0, double scale, double ox, double oy,
+                        double* warped_xy, void* stream);
+
+/* Images of warped events of k (1..32) jobs of one frame size by ONE launch sequence: events[i] ([n[i]][4] f64, time-sorted; n[i] may be
+ * 0), flows[i] ([2][h][w] fp32; a NULL entry, or flows == NULL, is the zero flow), t0[i], scale[i] and iwe[i] ([2][h][w] fp32) are HOST
+ * arrays, read before the call returns.  Every event is warped as eemflow_warp_events warps it and votes bilinearly - weights
+ * (1-gx)(1-gy), gx(1-gy), (1-gx)gy, gx gy around (floor(yw), floor(xw)) - into channel 0 (p > 0) or 1; a target outside the frame is
+ * dropped on its own, an event with a non-finite warped position is dropped whole and counted.  Every cell is the fp64 sum of its votes
+ * rounded to fp32 once, and every cell is written.  moments (device, k x 4 doubles): {h*w, sum S, sum S^2, dropped} with
+ * S = iwe[0] + iwe[1] of the stored values, summed in a fixed order - the flow warp loss is var(S under the flow) / var(S under zero
+ * flow).  EEM_IWE_DIRECT=1 (read per call) takes the direct atomic form instead of the binned one.  Stream-ordered, no host
+ * synchronisation; scratch is owned by the library.
+ * Replaces: warp_events_flow_torch (utils_luo/event_utils.py:9-51) and the image / variance-ratio part of Test.inference_img_warp_loss
+ * (test_mvsec.py:753-852, the ratio at :821-824). */
+int eemflow_iwe_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                     const double* scale, double ox, double oy, int h, int w, float* const* iwe, double* moments, void* stream);
+
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
  * receive, per event, the int64 flat index x + y*w + bin*w*h of the left / right temporal vote, or -1
