@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .padder import InputPadder
+from ._hipmodel import HipModel, ptr_table
 from .weights import CORR_TAPS_53, eemflow_param_shapes
 
 
@@ -102,7 +102,22 @@ class _EEMFlowFunction(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
-class EEMFlow(nn.Module):
+def _needs_norm_record(method):
+    """The per-tensor check of `method`(deferred_norm=True)."""
+    from .voxelizer import has_norm_record
+
+    def check(v):
+        if not has_norm_record(v):
+            raise ValueError(f"{method}(deferred_norm=True): every volume needs its four-float record behind it "
+                             "(voxelize with normalize='deferred')")
+    return check
+
+
+class EEMFlow(HipModel, nn.Module):
+    _ABI = "eemflow"
+    _PADDER = dict(mode='chairs', eval_pad_rate=64)
+    MAX_STREAM_BIDIR = 8                # forward_stream(bidirectional=True): both directions share the 16-frame pointer table
+
     def __init__(self, config, groups=5, n_first_channels=5, out_mesh_size=False):
         super().__init__()
         self.groups = groups
@@ -132,33 +147,12 @@ class EEMFlow(nn.Module):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
         assert list(self.state_dict().keys()) == list(eemflow_param_shapes(n_first_channels, groups).keys())
-        self._ctx = None
-        self._ctx_device = None
-        self._weights_version = None
-        self._layout_loaded = False
+        self._layout_loaded = False     # the context holds the packed weight layout: changed values reach it device to device
         self.use_graph = True
-        self.frames_in_flight = 1       # >= 3: this module is one of several replicas kept busy on separate streams (throughput over latency)
-        self._stream_prev = None        # forward_stream: the caller's tensor of the window the context carries (events1 of the next pair)
 
     # ------------------------------------------------------------------ reference interface
-    def change_imagesize(self, img_size):
-        old = getattr(self, "image_size", None)
-        if old is not None and tuple(int(v) for v in old) != tuple(int(v) for v in img_size):
-            self.reset_stream()                                  # a carried window of another size cannot start the next pair
-        self.image_size = img_size
-        self.image_padder = InputPadder(img_size, mode='chairs', eval_pad_rate=64)
-
-    def replicate(self, frames_in_flight=None):
-        """A second module with the same weights, device, image size and mode and a context of its own: what keeps one more frame
-        in flight on another HIP stream (harness.TestRaftEvents(frames_in_flight=...))."""
-        twin = EEMFlow("", groups=self.groups, n_first_channels=self.n_first_channels, out_mesh_size=self.out_mesh_size)
-        twin.load_state_dict(self.state_dict())
-        twin = twin.to(next(self.parameters()).device)
-        if hasattr(self, "image_size"):
-            twin.change_imagesize(self.image_size)
-        twin.train(self.training)
-        twin.frames_in_flight = self.frames_in_flight if frames_in_flight is None else frames_in_flight
-        return twin
+    def _twin(self):
+        return EEMFlow("", groups=self.groups, n_first_channels=self.n_first_channels, out_mesh_size=self.out_mesh_size)
 
     def upsample_flow(self, flow, orig_size):
         if not flow.is_cuda:
@@ -172,33 +166,28 @@ class EEMFlow(nn.Module):
                 _lib.current_stream_ptr(flow.device)))
         return out
 
+    def _out_size(self, h, w):
+        return (16, 16) if (self.training and self.out_mesh_size) else (h, w)      # EEMFlow.py:126-130
+
     def forward(self, events1, events2):
-        if not (events1.is_cuda and events2.is_cuda):
-            raise _lib.EEMFlowHipError(
-                "EEMFlow.forward: inputs must be CUDA (ROCm) tensors - this implementation has no CPU path")
+        self._require_cuda("forward", events1, events2)
         if not hasattr(self, "image_padder"):
             raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        input_size = events1.shape[-2:]
-        if self.training and self.out_mesh_size:
-            out_size = (16, 16)                                  # EEMFlow.py:126-130
-        else:
-            out_size = tuple(int(v) for v in input_size)
         e1 = events1.contiguous().float()
         e2 = events2.contiguous().float()
         if e1.shape != e2.shape or e1.dim() != 4 or e1.shape[1] != self.n_first_channels:
             raise ValueError(f"expected two (B,{self.n_first_channels},H,W) tensors, got {tuple(e1.shape)} and {tuple(e2.shape)}")
+        b, _, h, w = e1.shape
+        out_size = self._out_size(int(h), int(w))
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             flow = _EEMFlowFunction.apply(self, e1, e2, out_size, *self.parameters())
             return (events1, events2), [flow]
         ctx = self._context(e1.device)
-        b, _, h, w = e1.shape
         flow = torch.empty(b, 2, out_size[0], out_size[1], device=e1.device, dtype=torch.float32)
         with torch.cuda.device(e1.device):
             _lib.check(_lib.lib().eemflow_forward(ctx, e1.data_ptr(), e2.data_ptr(), b, h, w, flow.data_ptr(),
                                                   out_size[0], out_size[1], _lib.current_stream_ptr(e1.device)))
         return (events1, events2), [flow]
-
-    MAX_COALESCE = 16
 
     def forward_many(self, frames, deferred_norm=False):
         """Several INDEPENDENT samples of the evaluation loop (test_mvsec.py:580-597: one `model(events1, events2)` per sample at batch 1)
@@ -208,41 +197,16 @@ class EEMFlow(nn.Module):
         deferred_norm=True: the frames are RAW voxel grids with their normalisation record behind them (the voxelizer's
         normalize="deferred"); pconv1_1 applies loader_utils.py:527-535's (v - mean) / sd as it reads them."""
         frames = list(frames)
-        if not 1 <= len(frames) <= self.MAX_COALESCE:
-            raise ValueError(f"forward_many: 1..{self.MAX_COALESCE} frames per call, got {len(frames)}")
-        if not hasattr(self, "image_padder"):
-            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        keep, shape = [], None
-        for a, b in frames:
-            if not (a.is_cuda and b.is_cuda):
-                raise _lib.EEMFlowHipError("EEMFlow.forward_many: inputs must be CUDA (ROCm) tensors - this implementation has no CPU path")
-            a, b = a.contiguous().float(), b.contiguous().float()
-            if a.shape != b.shape or a.dim() != 4 or a.shape[0] != 1 or a.shape[1] != self.n_first_channels:
-                raise ValueError(f"forward_many: every frame is two (1,{self.n_first_channels},H,W) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
-            if shape is not None and a.shape != shape:
-                raise ValueError("forward_many: all frames of a call share one shape")
-            if deferred_norm:
-                from .voxelizer import has_norm_record
-                if not (has_norm_record(a) and has_norm_record(b)):
-                    raise ValueError("forward_many(deferred_norm=True): every volume needs its four-float record behind it "
-                                     "(voxelize with normalize='deferred')")
-            shape = a.shape
-            keep.append((a, b))
-        dev = keep[0][0].device
-        h, w = int(shape[2]), int(shape[3])
-        out_size = (16, 16) if (self.training and self.out_mesh_size) else (h, w)
+        keep, dev, h, w = self._check_frames(frames, _needs_norm_record("forward_many") if deferred_norm else None)
+        out_size = self._out_size(h, w)
         ctx = self._context(dev)
         _lib.check(_lib.lib().eemflow_set_deferred_input_norm(ctx, 1 if deferred_norm else 0))
         n = len(keep)
         flows = [torch.empty(1, 2, out_size[0], out_size[1], device=dev, dtype=torch.float32) for _ in range(n)]
-        arr = ctypes.c_void_p * n
-        p1, p2, po = arr(*[a.data_ptr() for a, _ in keep]), arr(*[b.data_ptr() for _, b in keep]), arr(*[f.data_ptr() for f in flows])
+        p1, p2, po = ptr_table([a for a, _ in keep]), ptr_table([b for _, b in keep]), ptr_table(flows)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().eemflow_forward_many(ctx, n, p1, p2, po, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev)))
         return [((frames[i][0], frames[i][1]), [flows[i]]) for i in range(n)]
-
-    MAX_STREAM = 16                     # EEM_STREAM_MAX_VOLUMES of include/eemflow_hip.h
-    MAX_STREAM_BIDIR = 8                # EEM_STREAM_BIDIR_MAX_VOLUMES
 
     def forward_stream(self, volumes, deferred_norm=False, bidirectional=False, fb_check=None):
         """Flow along a stream of CONSECUTIVE event windows, each window encoded once (the MVSEC evaluation walks a sequence this way:
@@ -266,59 +230,26 @@ class EEMFlow(nn.Module):
         if fb_check is not None:
             from .metrics import fb_check_args
             fb_check = fb_check_args(*fb_check)
-        max_vols = self.MAX_STREAM_BIDIR if bidirectional else self.MAX_STREAM
-        if not 1 <= len(vols) <= max_vols:
-            raise ValueError(f"forward_stream: 1..{max_vols} volumes per call{' with bidirectional=True' if bidirectional else ''}, got {len(vols)}")
-        if not hasattr(self, "image_padder"):
-            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        keep, shape = [], None
-        for v in vols:
-            if not v.is_cuda:
-                raise _lib.EEMFlowHipError("EEMFlow.forward_stream: inputs must be CUDA (ROCm) tensors - this implementation has no CPU path")
-            v = v.contiguous().float()
-            if v.dim() != 4 or v.shape[0] != 1 or v.shape[1] != self.n_first_channels:
-                raise ValueError(f"forward_stream: every volume is a (1,{self.n_first_channels},H,W) tensor, got {tuple(v.shape)}")
-            if shape is not None and (v.shape != shape or v.device != keep[0].device):
-                raise ValueError("forward_stream: all volumes of a call share one shape and one device")
-            if deferred_norm:
-                from .voxelizer import has_norm_record
-                if not has_norm_record(v):
-                    raise ValueError("forward_stream(deferred_norm=True): every volume needs its four-float record behind it "
-                                     "(voxelize with normalize='deferred')")
-            shape = v.shape
-            keep.append(v)
-        dev = keep[0].device
-        h, w = int(shape[2]), int(shape[3])
-        out_size = (16, 16) if (self.training and self.out_mesh_size) else (h, w)
+        keep, dev, h, w = self._check_volumes(vols, self.MAX_STREAM_BIDIR if bidirectional else self.MAX_STREAM,
+                                              " with bidirectional=True" if bidirectional else "",
+                                              _needs_norm_record("forward_stream") if deferred_norm else None)
+        out_size = self._out_size(h, w)
         L = _lib.lib()
         ctx = self._context(dev)
-        pending = ctypes.c_int()
-        _lib.check(L.eemflow_stream_pending(ctx, ctypes.byref(pending)))
-        carried = self._stream_prev if (pending.value and self._stream_prev is not None) else None
-        if carried is None and pending.value:
-            _lib.check(L.eemflow_stream_reset(ctx))               # (no tensor to name as events1: start over)
-        _lib.check(L.eemflow_set_deferred_input_norm(ctx, 1 if deferred_norm else 0))
         n = len(keep)
-        nflow = n if carried is not None else n - 1
+        carried, nflow = self._stream_begin(ctx, n)
+        _lib.check(L.eemflow_set_deferred_input_norm(ctx, 1 if deferred_norm else 0))
         flows = [torch.empty(1, 2, out_size[0], out_size[1], device=dev, dtype=torch.float32) for _ in range(nflow)]
-        pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
-        po = (ctypes.c_void_p * max(nflow, 1))(*[f.data_ptr() for f in flows])
+        pv, po = ptr_table(keep), ptr_table(flows)
         if bidirectional:
             flows_bw = [torch.empty_like(f) for f in flows]
-            pb = (ctypes.c_void_p * max(nflow, 1))(*[f.data_ptr() for f in flows_bw])
+            pb = ptr_table(flows_bw)
         with torch.cuda.device(dev):
             if bidirectional:
                 rc = L.eemflow_forward_stream_bidir(ctx, n, pv, po, pb, nflow, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev))
             else:
                 rc = L.eemflow_forward_stream(ctx, n, pv, po, nflow, h, w, out_size[0], out_size[1], _lib.current_stream_ptr(dev))
-        if rc != 0:
-            msg = L.eemflow_last_error().decode("utf-8", "replace")
-            if "eemflow_stream_reset" in msg:
-                raise _lib.EEMFlowHipError(f"EEMFlow.forward_stream: {msg} - call reset_stream() on the module")
-            raise _lib.EEMFlowHipError(msg)
-        older = ([carried] if carried is not None else []) + vols[:-1]
-        self._stream_prev = vols[-1]
-        pairs = [(older[i], vols[i + 1 - (1 if carried is not None else 0)]) for i in range(nflow)]
+        pairs = self._stream_end(rc, vols, carried)
         if not bidirectional:
             return [(pairs[i], [flows[i]]) for i in range(nflow)]
         if fb_check is None or nflow == 0:
@@ -326,12 +257,6 @@ class EEMFlow(nn.Module):
         from .metrics import fb_check_many
         masks = fb_check_many(flows, flows_bw, *fb_check)
         return [(pairs[i], [flows[i]], [flows_bw[i]], masks[i]) for i in range(nflow)]
-
-    def reset_stream(self):
-        """Drop the window `forward_stream` carries: its next call starts a new stream (len(volumes) - 1 pairs)."""
-        self._stream_prev = None
-        if getattr(self, "_ctx", None) is not None:
-            _lib.check(_lib.lib().eemflow_stream_reset(self._ctx))
 
     # ------------------------------------------------------------------ HIP context plumbing
     def _flat_weights(self, device=None):
@@ -343,60 +268,32 @@ class EEMFlow(nn.Module):
         version counter the staleness check reads)."""
         self._weights_version = None
 
-    def _weights_fingerprint(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def _context(self, device):
+    def _load_weights(self, device):
         L = _lib.lib()
-        if self._ctx is None or self._ctx_device != device:
-            self._release()
-            handle = ctypes.c_void_p()
-            _lib.check(L.eemflow_create(device.index if device.index is not None else torch.cuda.current_device(),
-                                        ctypes.byref(handle)))
-            self._ctx, self._ctx_device, self._weights_version, self._layout_loaded = handle, device, None, False
-        fp = self._weights_fingerprint()
-        if fp != self._weights_version:
-            if self._layout_loaded and all(p.device == device for p in self.parameters()):
-                flat = self._flat_weights(device).contiguous()          # e.g. after optimizer.step(): device to device
-                with torch.cuda.device(device):
-                    _lib.check(L.eemflow_update_weights(self._ctx, flat.data_ptr(), flat.numel(), _lib.current_stream_ptr(device)))
-            else:
-                flat = self._flat_weights().contiguous()
-                _lib.check(L.eemflow_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels, self.groups))
-                self._layout_loaded = True
-            self._weights_version = fp
+        if self._layout_loaded and all(p.device == device for p in self.parameters()):
+            flat = self._flat_weights(device).contiguous()          # e.g. after optimizer.step(): device to device
+            with torch.cuda.device(device):
+                _lib.check(L.eemflow_update_weights(self._ctx, flat.data_ptr(), flat.numel(), _lib.current_stream_ptr(device)))
+        else:
+            flat = self._flat_weights().contiguous()
+            _lib.check(L.eemflow_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels, self.groups))
+            self._layout_loaded = True
+
+    def _configure(self):
+        L = _lib.lib()
         pad = (ctypes.c_int * 4)()
         _lib.check(L.eemflow_set_image_size(self._ctx, int(self.image_size[0]), int(self.image_size[1]), ctypes.byref(pad)))
         assert list(pad) == self.image_padder._pad
         _lib.check(L.eemflow_use_graph(self._ctx, 1 if self.use_graph else 0))
         _lib.check(L.eemflow_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
         _lib.check(L.eemflow_set_deferred_input_norm(self._ctx, 0))       # (forward_many(deferred_norm=True) turns it on for its call)
-        return self._ctx
 
-    def stage(self, name):
-        """Intermediate tensor of the last forward (parity tests): see eemflow_get_stage."""
-        L = _lib.lib()
-        dims = (ctypes.c_int * 4)()
-        _lib.check(L.eemflow_get_stage(self._ctx, name.encode(), None, 0, ctypes.byref(dims), None))
-        out = torch.empty(*list(dims), device=self._ctx_device, dtype=torch.float32)
-        with torch.cuda.device(self._ctx_device):
-            _lib.check(L.eemflow_get_stage(self._ctx, name.encode(), out.data_ptr(), out.numel(), ctypes.byref(dims),
-                                           _lib.current_stream_ptr(self._ctx_device)))
-        return out
+    def _release(self):
+        super()._release()
+        self._layout_loaded = False                              # (the packed layout went with the context)
 
     def backward_forms(self):
         """{"<layer>.<wgrad | dgrad | bwd>": kernel form} of the last backward (see eemflow_backward_forms)."""
         buf = ctypes.create_string_buffer(8192)
         _lib.check(_lib.lib().eemflow_backward_forms(self._ctx, buf, len(buf)))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";") if kv)
-
-    def _release(self):
-        if self._ctx is not None:
-            _lib.lib().eemflow_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass

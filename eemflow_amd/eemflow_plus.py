@@ -14,8 +14,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._hipmodel import HipModel, ptr_table
 from .eemflow import convrelu
-from .padder import InputPadder
 from .weights import CORR_TAPS_53
 
 
@@ -66,7 +66,10 @@ class cdc_model(nn.Module):  # noqa: N801  (reference class name)
                                                   conv(16, 32, kernel_size=3, stride=1, dilation=1), conv(32, 32, stride=2))
 
 
-class EEMFlow_cdc(nn.Module):  # noqa: N801
+class EEMFlow_cdc(HipModel, nn.Module):  # noqa: N801
+    _ABI = "eemplus"
+    _PADDER = dict(mode='chairs', eval_pad_rate=64)
+
     def __init__(self, config, groups=3, n_first_channels=15, args=None):
         super().__init__()
         self.args = args
@@ -107,55 +110,22 @@ class EEMFlow_cdc(nn.Module):  # noqa: N801
                                        conv(64, 32, kernel_size=1, stride=1, dilation=1),
                                        conv(64, 32, kernel_size=1, stride=1, dilation=1),
                                        conv(64, 32, kernel_size=1, stride=1, dilation=1)])
-        self._ctx = None
-        self._ctx_device = None
-        self._weights_version = None
-        self._stream_prev = None        # forward_stream: the caller's tensor of the window the context carries (events1 of the next pair)
 
-    def change_imagesize(self, img_size):
-        old = getattr(self, "image_size", None)
-        if old is not None and tuple(int(v) for v in old) != tuple(int(v) for v in img_size):
-            self.reset_stream()                                  # a carried window of another size cannot start the next pair
-        self.image_size = img_size
-        self.image_padder = InputPadder(img_size, mode='chairs', eval_pad_rate=64)
-
-    def replicate(self, frames_in_flight=None):
-        """A second module with the same weights, device, image size and mode and a context of its own: what keeps one more frame
-        in flight on another HIP stream (harness.TestRaftEvents(frames_in_flight=...))."""
-        twin = EEMFlow_cdc("", groups=self.groups, n_first_channels=self.n_first_channels, args=self.args)
-        twin.load_state_dict(self.state_dict())
-        twin = twin.to(next(self.parameters()).device)
-        if hasattr(self, "image_size"):
-            twin.change_imagesize(self.image_size)
-        twin.train(self.training)
-        twin.frames_in_flight = getattr(self, "frames_in_flight", 1) if frames_in_flight is None else frames_in_flight
-        return twin
+    def _twin(self):
+        return EEMFlow_cdc("", groups=self.groups, n_first_channels=self.n_first_channels, args=self.args)
 
     def _flat_weights(self):
         return torch.cat([v.detach().reshape(-1).to(torch.float32).cpu() for v in self.state_dict().values()])
 
-    def _fingerprint(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+    def _load_weights(self, device):
+        flat = self._flat_weights().contiguous()
+        _lib.check(_lib.lib().eemplus_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels, self.groups))
 
-    def _context(self, device):
-        L = _lib.lib()
-        if self._ctx is None or self._ctx_device != device:
-            self._release()
-            handle = ctypes.c_void_p()
-            _lib.check(L.eemplus_create(device.index if device.index is not None else torch.cuda.current_device(),
-                                        ctypes.byref(handle)))
-            self._ctx, self._ctx_device, self._weights_version = handle, device, None
-        fp = self._fingerprint()
-        if fp != self._weights_version:
-            flat = self._flat_weights().contiguous()
-            _lib.check(L.eemplus_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels, self.groups))
-            self._weights_version = fp
-        _lib.check(L.eemplus_set_frames_in_flight(self._ctx, max(1, int(getattr(self, "frames_in_flight", 1)))))
-        return self._ctx
+    def _configure(self):
+        _lib.check(_lib.lib().eemplus_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
 
     def forward(self, events1, events2):
-        if not (events1.is_cuda and events2.is_cuda):
-            raise _lib.EEMFlowHipError("EEMFlow_cdc.forward: inputs must be CUDA (ROCm) tensors - there is no CPU path")
+        self._require_cuda("forward", events1, events2)
         if not hasattr(self, "image_padder"):
             raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
         e1, e2 = events1.contiguous().float(), events2.contiguous().float()
@@ -172,42 +142,21 @@ class EEMFlow_cdc(nn.Module):  # noqa: N801
                                                   _lib.current_stream_ptr(e1.device)))
         return (events1, events2), [out[i] for i in range(5)]
 
-    MAX_COALESCE = 16
-
     def forward_many(self, frames):
         """Several INDEPENDENT samples of the evaluation loop (test_mvsec.py:580-597: one `model(events1, events2)` per sample at batch 1)
         as one batch-n chain of launches, each sample staying in its own tensors: `frames` is a sequence of (events1, events2) pairs of
         [1, C, H, W] tensors; returns one `((events1, events2), [flow6 .. flow2 at full resolution])` per sample, bitwise what `forward`
         gives for the samples stacked into one batch.  Inference only."""
         frames = list(frames)
-        if not 1 <= len(frames) <= self.MAX_COALESCE:
-            raise ValueError(f"forward_many: 1..{self.MAX_COALESCE} frames per call, got {len(frames)}")
-        if not hasattr(self, "image_padder"):
-            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        keep, shape = [], None
-        for a, b in frames:
-            if not (a.is_cuda and b.is_cuda):
-                raise _lib.EEMFlowHipError("EEMFlow_cdc.forward_many: inputs must be CUDA (ROCm) tensors - there is no CPU path")
-            a, b = a.contiguous().float(), b.contiguous().float()
-            if a.shape != b.shape or a.dim() != 4 or a.shape[0] != 1 or a.shape[1] != self.n_first_channels:
-                raise ValueError(f"forward_many: every frame is two (1,{self.n_first_channels},H,W) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
-            if shape is not None and a.shape != shape:
-                raise ValueError("forward_many: all frames of a call share one shape")
-            shape = a.shape
-            keep.append((a, b))
-        dev = keep[0][0].device
-        h, w = int(shape[2]), int(shape[3])
+        keep, dev, h, w = self._check_frames(frames)
         ctx = self._context(dev)
         n = len(keep)
         outs = [torch.empty(5, 1, 2, h, w, device=dev, dtype=torch.float32) for _ in range(n)]
-        arr = ctypes.c_void_p * n
-        p1, p2, po = arr(*[a.data_ptr() for a, _ in keep]), arr(*[b.data_ptr() for _, b in keep]), arr(*[o.data_ptr() for o in outs])
+        p1, p2, po = ptr_table([a for a, _ in keep]), ptr_table([b for _, b in keep]), ptr_table(outs)
         padc = (ctypes.c_int * 4)(*self.image_padder._pad)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().eemplus_forward_many(ctx, n, p1, p2, h, w, padc, po, _lib.current_stream_ptr(dev)))
         return [((frames[i][0], frames[i][1]), [outs[i][k] for k in range(5)]) for i in range(n)]
-
-    MAX_STREAM = 16                     # EEM_STREAM_MAX_VOLUMES of include/eemflow_hip.h
 
     def forward_stream(self, volumes):
         """Flow along a stream of CONSECUTIVE event windows, each window padded and encoded once (the MVSEC evaluation walks a sequence
@@ -219,52 +168,17 @@ class EEMFlow_cdc(nn.Module):  # noqa: N801
         len(volumes) - 1.  `reset_stream()` drops the carried window; `change_imagesize` to a new size does too.  After a weight change
         (optimizer step, load_state_dict) the next call raises until `reset_stream()`.  Inference only (no autograd graph is recorded)."""
         vols = list(volumes)
-        if not 1 <= len(vols) <= self.MAX_STREAM:
-            raise ValueError(f"forward_stream: 1..{self.MAX_STREAM} volumes per call, got {len(vols)}")
-        if not hasattr(self, "image_padder"):
-            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        keep, shape = [], None
-        for v in vols:
-            if not v.is_cuda:
-                raise _lib.EEMFlowHipError("EEMFlow_cdc.forward_stream: inputs must be CUDA (ROCm) tensors - there is no CPU path")
-            v = v.contiguous().float()
-            if v.dim() != 4 or v.shape[0] != 1 or v.shape[1] != self.n_first_channels:
-                raise ValueError(f"forward_stream: every volume is a (1,{self.n_first_channels},H,W) tensor, got {tuple(v.shape)}")
-            if shape is not None and (v.shape != shape or v.device != keep[0].device):
-                raise ValueError("forward_stream: all volumes of a call share one shape and one device")
-            shape = v.shape
-            keep.append(v)
-        dev = keep[0].device
-        h, w = int(shape[2]), int(shape[3])
-        L = _lib.lib()
+        keep, dev, h, w = self._check_volumes(vols, self.MAX_STREAM)
         ctx = self._context(dev)
-        pending = ctypes.c_int()
-        _lib.check(L.eemplus_stream_pending(ctx, ctypes.byref(pending)))
-        carried = self._stream_prev if (pending.value and self._stream_prev is not None) else None
-        if carried is None and pending.value:
-            _lib.check(L.eemplus_stream_reset(ctx))               # (no tensor to name as events1: start over)
         n = len(keep)
-        nflow = n if carried is not None else n - 1
+        carried, nflow = self._stream_begin(ctx, n)
         outs = [torch.empty(5, 1, 2, h, w, device=dev, dtype=torch.float32) for _ in range(nflow)]
-        pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
-        po = (ctypes.c_void_p * max(nflow, 1))(*[o.data_ptr() for o in outs])
+        pv, po = ptr_table(keep), ptr_table(outs)
         padc = (ctypes.c_int * 4)(*self.image_padder._pad)
         with torch.cuda.device(dev):
-            rc = L.eemplus_forward_stream(ctx, n, pv, h, w, padc, po, nflow, _lib.current_stream_ptr(dev))
-        if rc != 0:
-            msg = L.eemflow_last_error().decode("utf-8", "replace")
-            if "eemplus_stream_reset" in msg:
-                raise _lib.EEMFlowHipError(f"EEMFlow_cdc.forward_stream: {msg} - call reset_stream() on the module")
-            raise _lib.EEMFlowHipError(msg)
-        older = ([carried] if carried is not None else []) + vols[:-1]
-        self._stream_prev = vols[-1]
-        return [((older[i], vols[i + 1 - (1 if carried is not None else 0)]), [outs[i][k] for k in range(5)]) for i in range(nflow)]
-
-    def reset_stream(self):
-        """Drop the window `forward_stream` carries: its next call starts a new stream (len(volumes) - 1 pairs)."""
-        self._stream_prev = None
-        if getattr(self, "_ctx", None) is not None:
-            _lib.check(_lib.lib().eemplus_stream_reset(self._ctx))
+            rc = _lib.lib().eemplus_forward_stream(ctx, n, pv, h, w, padc, po, nflow, _lib.current_stream_ptr(dev))
+        pairs = self._stream_end(rc, vols, carried)
+        return [(pairs[i], [outs[i][k] for k in range(5)]) for i in range(nflow)]
 
     # ------------------------------------------------------------------ differentiable route (eemflow_amd/ops.py)
     def _lrelu_conv(self, seq, *xs):
@@ -364,24 +278,3 @@ class EEMFlow_cdc(nn.Module):  # noqa: N801
             _lib.check(_lib.lib().eemplus_level(self._ctx, int(l), fi.data_ptr(), up.data_ptr(), out.data_ptr(),
                                                 _lib.current_stream_ptr(fi.device)))
         return up, out
-
-    def stage(self, name):
-        L = _lib.lib()
-        dims = (ctypes.c_int * 4)()
-        _lib.check(L.eemplus_get_stage(self._ctx, name.encode(), None, 0, ctypes.byref(dims), None))
-        out = torch.empty(*list(dims), device=self._ctx_device, dtype=torch.float32)
-        with torch.cuda.device(self._ctx_device):
-            _lib.check(L.eemplus_get_stage(self._ctx, name.encode(), out.data_ptr(), out.numel(), ctypes.byref(dims),
-                                           _lib.current_stream_ptr(self._ctx_device)))
-        return out
-
-    def _release(self):
-        if self._ctx is not None:
-            _lib.lib().eemplus_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass

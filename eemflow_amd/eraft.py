@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .padder import InputPadder
+from ._hipmodel import HipModel, ptr_table
 
 
 class ResidualBlock(nn.Module):
@@ -148,7 +148,11 @@ def get_args():
     return Namespace(small=False, dropout=False, mixed_precision=False, clip=1.0)
 
 
-class ERAFT(nn.Module):
+class ERAFT(HipModel, nn.Module):
+    _ABI = "eraft"
+    _PADDER = dict(mode='chairs')
+    _REPLICATED = ("final_only", "alternate_corr", "warm_start")
+
     def __init__(self, config, n_first_channels=5):
         super().__init__()
         args = get_args()
@@ -161,36 +165,13 @@ class ERAFT(nn.Module):
         self.fnet = BasicEncoder(output_dim=256, norm_fn='instance', dropout=0, n_first_channels=n_first_channels)
         self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn='batch', dropout=0, n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.args, hidden_dim=hdim)
-        self._ctx = None
-        self._ctx_device = None
-        self._weights_version = None
         self.keep_stages = False       # True: the first iteration's corr0 / net1 / mask1 / delta1 stay readable through stage()
-        self.frames_in_flight = 1      # >= 3: one of several replicas kept busy on separate streams (eraft_set_frames_in_flight)
         self.final_only = False        # True (inference route): the returned list holds the last prediction only - what test_mvsec.py:1455 reads
         self.alternate_corr = False    # True (inference route): correlation features on the fly, no all-pairs volume (RAFT's alternate_corr)
         self.warm_start = False        # True: forward_stream starts each pair from the previous pair's forward-interpolated flow_low
-        self._stream_prev = None
 
-    def change_imagesize(self, img_size):
-        if tuple(img_size) != tuple(getattr(self, "image_size", ())):
-            self.reset_stream()
-        self.image_size = img_size
-        self.image_padder = InputPadder(img_size, mode='chairs')
-
-    def replicate(self, frames_in_flight=None):
-        """A second module with the same weights, device, image size and mode and a context of its own: what keeps one more frame
-        in flight on another HIP stream (harness.TestRaftEvents(frames_in_flight=...))."""
-        twin = ERAFT("", n_first_channels=self.n_first_channels)
-        twin.load_state_dict(self.state_dict())
-        twin = twin.to(next(self.parameters()).device)
-        if hasattr(self, "image_size"):
-            twin.change_imagesize(self.image_size)
-        twin.train(self.training)
-        twin.frames_in_flight = self.frames_in_flight if frames_in_flight is None else frames_in_flight
-        twin.final_only = getattr(self, "final_only", False)
-        twin.alternate_corr = getattr(self, "alternate_corr", False)
-        twin.warm_start = getattr(self, "warm_start", False)
-        return twin
+    def _twin(self):
+        return ERAFT("", n_first_channels=self.n_first_channels)
 
     def freeze_bn(self):
         for m in self.modules():
@@ -203,31 +184,22 @@ class ERAFT(nn.Module):
         return torch.cat([v.detach().reshape(-1).to(torch.float32).cpu()
                           for k, v in self.state_dict().items() if not k.endswith("num_batches_tracked")])
 
-    def _fingerprint(self):
+    def _weights_fingerprint(self):
         return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
-    def _context(self, device):
+    def _load_weights(self, device):
+        flat = self._flat_weights().contiguous()
+        _lib.check(_lib.lib().eraft_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels))
+
+    def _configure(self):
         L = _lib.lib()
-        if self._ctx is None or self._ctx_device != device:
-            self._release()
-            handle = ctypes.c_void_p()
-            _lib.check(L.eraft_create(device.index if device.index is not None else torch.cuda.current_device(),
-                                      ctypes.byref(handle)))
-            self._ctx, self._ctx_device, self._weights_version = handle, device, None
-        fp = self._fingerprint()
-        if fp != self._weights_version:
-            flat = self._flat_weights().contiguous()
-            _lib.check(L.eraft_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels))
-            self._weights_version = fp
         _lib.check(L.eraft_keep_stages(self._ctx, 1 if self.keep_stages else 0))
-        _lib.check(L.eraft_set_frames_in_flight(self._ctx, max(1, int(getattr(self, "frames_in_flight", 1)))))
-        _lib.check(L.eraft_set_alternate_corr(self._ctx, 1 if getattr(self, "alternate_corr", False) else 0))
-        _lib.check(L.eraft_set_final_only(self._ctx, 1 if getattr(self, "final_only", False) else 0))
-        return self._ctx
+        _lib.check(L.eraft_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
+        _lib.check(L.eraft_set_alternate_corr(self._ctx, 1 if self.alternate_corr else 0))
+        _lib.check(L.eraft_set_final_only(self._ctx, 1 if self.final_only else 0))
 
     def forward(self, events1, events2, iters=12, flow_init=None, upsample=True, normal=False):
-        if not (events1.is_cuda and events2.is_cuda):
-            raise _lib.EEMFlowHipError("ERAFT.forward: inputs must be CUDA (ROCm) tensors - there is no CPU path")
+        self._require_cuda("forward", events1, events2)
         if not hasattr(self, "image_padder"):
             raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
         e1, e2 = events1.contiguous().float(), events2.contiguous().float()
@@ -244,7 +216,7 @@ class ERAFT(nn.Module):
             # autograd route; also taken without gradients while BatchNorm is in train(): batch statistics, running-stat update
             return (events1, events2), self._forward_ops(e1, e2, iters, flow_init)
         ctx = self._context(e1.device)
-        nout = 1 if getattr(self, "final_only", False) else iters
+        nout = 1 if self.final_only else iters
         out = torch.empty(nout, b, 2, h, w, device=e1.device, dtype=torch.float32)
         fi = None
         if flow_init is not None:
@@ -256,46 +228,25 @@ class ERAFT(nn.Module):
                                                 _lib.current_stream_ptr(e1.device)))
         return (events1, events2), [out[i] for i in range(nout)]
 
-    MAX_COALESCE = 16
-
     def forward_many(self, frames, iters=12):
         """Several INDEPENDENT samples of the evaluation loop (test_mvsec.py:580-597: one `model(events1, events2)` per sample at batch 1)
         as one batch-n forward, each sample staying in its own tensors: `frames` is a sequence of (events1, events2) pairs of [1, C, H, W]
         tensors; returns one `((events1, events2), [predictions])` per sample - `iters` predictions, or the last one with `final_only` -
         bitwise what `forward` gives for the samples stacked into one batch.  Inference only, no flow_init."""
         frames = list(frames)
-        if not 1 <= len(frames) <= self.MAX_COALESCE:
-            raise ValueError(f"forward_many: 1..{self.MAX_COALESCE} frames per call, got {len(frames)}")
-        if not hasattr(self, "image_padder"):
-            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        keep, shape = [], None
-        for a, b in frames:
-            if not (a.is_cuda and b.is_cuda):
-                raise _lib.EEMFlowHipError("ERAFT.forward_many: inputs must be CUDA (ROCm) tensors - there is no CPU path")
-            a, b = a.contiguous().float(), b.contiguous().float()
-            if a.shape != b.shape or a.dim() != 4 or a.shape[0] != 1 or a.shape[1] != self.n_first_channels:
-                raise ValueError(f"forward_many: every frame is two (1,{self.n_first_channels},H,W) tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
-            if shape is not None and a.shape != shape:
-                raise ValueError("forward_many: all frames of a call share one shape")
-            shape = a.shape
-            keep.append((a, b))
-        dev = keep[0][0].device
-        h, w = int(shape[2]), int(shape[3])
+        keep, dev, h, w = self._check_frames(frames)
         pad = self.image_padder._pad
         if (h + pad[2] + pad[3]) % 8 or (w + pad[0] + pad[1]) % 8:
             raise ValueError("forward_many: the padded size must be a multiple of 8 (eraft.py:83-94)")
         ctx = self._context(dev)
         n = len(keep)
-        nout = 1 if getattr(self, "final_only", False) else iters
+        nout = 1 if self.final_only else iters
         outs = [torch.empty(nout, 1, 2, h, w, device=dev, dtype=torch.float32) for _ in range(n)]
-        arr = ctypes.c_void_p * n
-        p1, p2, po = arr(*[a.data_ptr() for a, _ in keep]), arr(*[b.data_ptr() for _, b in keep]), arr(*[o.data_ptr() for o in outs])
+        p1, p2, po = ptr_table([a for a, _ in keep]), ptr_table([b for _, b in keep]), ptr_table(outs)
         padc = (ctypes.c_int * 4)(*pad)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().eraft_forward_many(ctx, n, p1, p2, h, w, padc, iters, po, _lib.current_stream_ptr(dev)))
         return [((frames[i][0], frames[i][1]), [outs[i][k] for k in range(nout)]) for i in range(n)]
-
-    MAX_STREAM = 16                     # ERAFT_STREAM_MAX_VOLUMES of include/eemflow_hip.h
 
     def forward_stream(self, volumes, iters=12):
         """Flow along a stream of CONSECUTIVE event windows, each window through the feature network once (the MVSEC evaluation at
@@ -309,64 +260,28 @@ class ERAFT(nn.Module):
         (load_state_dict, an optimizer step) the next call raises until `reset_stream()`.  Inference only (eval-mode BatchNorm, no
         autograd); alternate_corr is refused."""
         vols = list(volumes)
-        if not 1 <= len(vols) <= self.MAX_STREAM:
-            raise ValueError(f"forward_stream: 1..{self.MAX_STREAM} volumes per call, got {len(vols)}")
-        if not hasattr(self, "image_padder"):
-            raise AttributeError("call change_imagesize(img_size) before forward (as the reference requires)")
-        keep, shape = [], None
-        for v in vols:
-            if not v.is_cuda:
-                raise _lib.EEMFlowHipError("ERAFT.forward_stream: inputs must be CUDA (ROCm) tensors - there is no CPU path")
-            v = v.contiguous().float()
-            if v.dim() != 4 or v.shape[0] != 1 or v.shape[1] != self.n_first_channels:
-                raise ValueError(f"forward_stream: every volume is a (1,{self.n_first_channels},H,W) tensor, got {tuple(v.shape)}")
-            if shape is not None and (v.shape != shape or v.device != keep[0].device):
-                raise ValueError("forward_stream: all volumes of a call share one shape and one device")
-            shape = v.shape
-            keep.append(v)
+        keep, dev, h, w = self._check_volumes(vols, self.MAX_STREAM)
         if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
             raise RuntimeError("forward_stream: inference only - BatchNorm is in train mode (call eval())")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("forward_stream: inference only - run it under torch.no_grad() (the stream records no autograd graph)")
-        if getattr(self, "alternate_corr", False):
+        if self.alternate_corr:
             raise ValueError("forward_stream: alternate_corr is not supported (the stream reads every pair's all-pairs volume)")
-        dev = keep[0].device
-        h, w = int(shape[2]), int(shape[3])
         pad = self.image_padder._pad
         if (h + pad[2] + pad[3]) % 8 or (w + pad[0] + pad[1]) % 8:
             raise ValueError("forward_stream: the padded size must be a multiple of 8 (eraft.py:83-94)")
-        L = _lib.lib()
         ctx = self._context(dev)
-        pending = ctypes.c_int()
-        _lib.check(L.eraft_stream_pending(ctx, ctypes.byref(pending)))
-        carried = self._stream_prev if (pending.value and self._stream_prev is not None) else None
-        if carried is None and pending.value:
-            _lib.check(L.eraft_stream_reset(ctx))                 # (no tensor to name as events1: start over)
         n = len(keep)
-        nflow = n if carried is not None else n - 1
-        nout = 1 if getattr(self, "final_only", False) else iters
+        carried, nflow = self._stream_begin(ctx, n)
+        nout = 1 if self.final_only else iters
         outs = [torch.empty(nout, 1, 2, h, w, device=dev, dtype=torch.float32) for _ in range(nflow)]
-        pv = (ctypes.c_void_p * n)(*[v.data_ptr() for v in keep])
-        po = (ctypes.c_void_p * max(nflow, 1))(*[o.data_ptr() for o in outs])
+        pv, po = ptr_table(keep), ptr_table(outs)
         padc = (ctypes.c_int * 4)(*pad)
         with torch.cuda.device(dev):
-            rc = L.eraft_forward_stream(ctx, n, pv, h, w, padc, iters, 1 if getattr(self, "warm_start", False) else 0, po, nflow,
-                                        _lib.current_stream_ptr(dev))
-        if rc != 0:
-            msg = L.eemflow_last_error().decode("utf-8", "replace")
-            if "eraft_stream_reset" in msg:
-                raise _lib.EEMFlowHipError(f"ERAFT.forward_stream: {msg} - call reset_stream() on the module")
-            raise _lib.EEMFlowHipError(msg)
-        older = ([carried] if carried is not None else []) + vols[:-1]
-        newer = vols if carried is not None else vols[1:]
-        self._stream_prev = vols[-1]
-        return [((older[i], newer[i]), [outs[i][k] for k in range(nout)]) for i in range(nflow)]
-
-    def reset_stream(self):
-        """Drop the window (and flow) `forward_stream` carries: its next call starts a new stream, cold, with len(volumes) - 1 pairs."""
-        self._stream_prev = None
-        if getattr(self, "_ctx", None) is not None:
-            _lib.check(_lib.lib().eraft_stream_reset(self._ctx))
+            rc = _lib.lib().eraft_forward_stream(ctx, n, pv, h, w, padc, iters, 1 if self.warm_start else 0, po, nflow,
+                                                 _lib.current_stream_ptr(dev))
+        pairs = self._stream_end(rc, vols, carried)
+        return [(pairs[i], [outs[i][k] for k in range(nout)]) for i in range(nflow)]
 
     # ------------------------------------------------------------------ differentiable route (eemflow_amd/ops.py)
     def _norm(self, norm, x, relu):
@@ -428,27 +343,6 @@ class ERAFT(nn.Module):
             coords1 = ops.Add.apply(coords1, delta, 1)
             preds.append(ops.ConvexUpsample.apply(ops.Add.apply(coords1, coords0, -1), mask, tuple(pad)))
         return preds
-
-    def stage(self, name):
-        L = _lib.lib()
-        dims = (ctypes.c_int * 4)()
-        _lib.check(L.eraft_get_stage(self._ctx, name.encode(), None, 0, ctypes.byref(dims), None))
-        out = torch.empty(*list(dims), device=self._ctx_device, dtype=torch.float32)
-        with torch.cuda.device(self._ctx_device):
-            _lib.check(L.eraft_get_stage(self._ctx, name.encode(), out.data_ptr(), out.numel(), ctypes.byref(dims),
-                                         _lib.current_stream_ptr(self._ctx_device)))
-        return out
-
-    def _release(self):
-        if self._ctx is not None:
-            _lib.lib().eraft_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
 
 def forward_interpolate(flow):
