@@ -9,6 +9,7 @@ import os as _os
 # it; the variable is read at the runtime's first call.  A value the user exported wins.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
+from .augmentor import AugPlan, apply_host, augment_many   # noqa: F401
 from .eemflow import EEMFlow            # noqa: F401
 from .iwe import fwl, fwl_many, iwe, iwe_many, warp_events   # noqa: F401
 from .metrics import fb_check          # noqa: F401

@@ -17,6 +17,13 @@ class KernelStat(ctypes.Structure):
                 ("ms", ctypes.c_float), ("blocks", ctypes.c_int), ("pipe", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
+class AugPlanC(ctypes.Structure):
+    """eemflow_aug_plan of include/eemflow_hip.h."""
+    _fields_ = [("scale_x", ctypes.c_double), ("scale_y", ctypes.c_double), ("resized", ctypes.c_int), ("RH", ctypes.c_int),
+                ("RW", ctypes.c_int), ("hflip", ctypes.c_int), ("vflip", ctypes.c_int), ("y0", ctypes.c_int), ("x0", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
 _SIGNATURES = {
     "eemflow_abi_version": (ctypes.c_int, []),
     "eemflow_last_error": (ctypes.c_char_p, []),
@@ -92,6 +99,10 @@ _SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_void_p]),
     "eemflow_voxelize_many": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
+    "eemflow_augment_many": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(AugPlanC), ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
+                                            ctypes.c_void_p]),
     "eemflow_forward_backward": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_float_p,
                                                 _c_float_p, ctypes.POINTER(ctypes.c_double * 5), ctypes.c_void_p]),

@@ -9,7 +9,9 @@ Same flags and defaults as the reference scripts (`--lr --wd --train_iters --val
 repository path), `--save_root`, `--checkpoint`, `--config` (a JSON like the reference's config/a_meshflow.json; its training and
 loader defaults are built in), `test`: `--vis_events --print_epe --visualize_every` (the keywords of the reference's evaluation loop
 that its script leaves at their defaults; `-v` writes the flow images under the run's save folder), `--fwl` (the flow warp loss of
-Test.inference_img_warp_loss, test_mvsec.py:753-852, as a field of every evaluation line).  Dropped: the key-map, warped-image
+Test.inference_img_warp_loss, test_mvsec.py:753-852, as a field of every evaluation line), `train`: `--device_batches` (beside `--num_workers`: every batch voxelized, flipped and assembled
+on the GPU by the threaded loader, the event volumes never copied through host memory; the same batches under the same numpy seed).
+Dropped: the key-map, warped-image
 and HSV visualisations, xlsx export, git metadata, nn.DataParallel (one process per GPU:
 launch with torchrun for data parallelism; see eemflow_amd.parallel).  Only the models built here are accepted: EEMFlow (trained by
 the fused step inside the library), `eraft` (train_EEMFlow_HREM.py:30-32) and `EEMFlow+` (both trained through the reference's own
@@ -51,6 +53,11 @@ def build_parser():
                        help='evaluation: write the colour-wheel images of every estimated and ground-truth flow as JPEG files under '
                             '<save folder>/<sequence>/test/ (train: accepted, the training loop writes no images)')
         q.add_argument('-n', '--num_workers', default=0, type=int, help='host threads that read and voxelize samples ahead (the reference: DataLoader worker processes); 0 = in the loop')
+        if train:
+            q.add_argument('--device_batches', action='store_true',
+                           help='build every training batch on the GPU: voxelized, flipped and assembled without a copy of the event volumes '
+                                'through host memory (implies the threaded loader with at least one thread; same batches as the host route '
+                                'under the same numpy seed, and reproducible for any --num_workers)')
         q.add_argument('--train_iters', default=6000000 if train else 1000000, type=int, metavar='N', help='number of total iterations')
         q.add_argument('-se', '--start-epoch', action='store_true', help='restart from lasted_ckpt.pth.tar of the run folder')
         q.add_argument('-be', '--best_epe', default=1e5, type=float)
@@ -156,10 +163,10 @@ def train(args):
     torch.cuda.set_device(dev)
     train_set = HREMEventFlow(args=config["data_loader"]["train"]["args"], train=True, root=args.data_root, device=dev)
     sampler = torch.utils.data.distributed.DistributedSampler(train_set, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
-    if args.num_workers > 0:             # the reference's worker count: here host threads that read / inflate / voxelize samples ahead
+    if args.num_workers > 0 or args.device_batches:   # the reference's worker count: here host threads that read / inflate / voxelize samples ahead
         from .loader import ThreadedBatchLoader
         loader = ThreadedBatchLoader(train_set, per_rank_batch(args.batch_size, world), shuffle=sampler is None, sampler=sampler,
-                                     threads=args.num_workers, drop_last=True)
+                                     threads=max(1, args.num_workers), drop_last=True, device_batches=args.device_batches)
     else:
         loader = torch.utils.data.DataLoader(train_set, batch_size=per_rank_batch(args.batch_size, world), shuffle=sampler is None,
                                              sampler=sampler, num_workers=0, drop_last=True)

@@ -460,7 +460,11 @@ def _target_like(pred, flow_gt, valid):
 
 
 class TrainRaftEvents:
-    """Training loop of train_mvsec.py:229-286 (one process per GPU; batches are this rank's shard)."""
+    """Training loop of train_mvsec.py:229-286 (one process per GPU; batches are this rank's shard).
+
+    A loader that assembles its batches on the device (loader.ThreadedBatchLoader(device_batches=True)) needs nothing else here: the
+    loops' `batch[key].to(dev).float()` returns the very tensor when it is float32 and already on `dev` (Tensor.to and Tensor.float
+    return self when nothing changes; tests/test_gpu_augment.py holds the data pointers equal), so no copy is made."""
 
     def __init__(self, loader, image_size, lr=1e-4, wdecay=5e-5, epsilon=1e-8, num_steps=1000000, clip=1.0, gamma=0.8,
                  logger=None, print_freq=100, engine="fused", mixed_precision=True, start_iteration=0):

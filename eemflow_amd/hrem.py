@@ -238,6 +238,58 @@ class HREMEventFlow(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         return self._finish(self.get_sample(idx % len(self)))
 
+    # ---------------------------------------------------------------------------------------- batches assembled on the device
+    def _check_device_batches(self):
+        if self.type != 'train':
+            raise ValueError("get_batch: training datasets only (train=True); evaluation samples are not augmented - get_samples serves them")
+        if self.augmentor is not None and not hasattr(self.augmentor, "draw"):
+            raise ValueError("get_batch: the augmentor is a callable without draw(): its samples keep the host route (dataset[i])")
+
+    def draw_plans(self, idxs):
+        """One AugPlan per sample, drawn from numpy.random in sample order - the draws `[self[i] for i in idxs]` would make."""
+        from .augmentor import AugPlan
+        self._check_device_batches()
+        h, w = self.image_height, self.image_width
+        return [self.augmentor.draw(h, w, without_resize=True) if self.augmentor is not None else AugPlan(h, w) for _ in idxs]
+
+    def read_sample(self, idx):
+        """The host part of sample idx (files, mesh flow): what get_batch takes as `reads`, so that a loader can read ahead on threads."""
+        return self._read(idx % len(self))
+
+    def get_batch(self, idxs, plans=None, reads=None):
+        """The stacked batch of `[self[i] for i in idxs]` - the same keys, dtypes, shapes and bits - with every tensor on the device and
+        the event volumes never on the host: the samples are voxelized in groups of up to 16 (voxel.many) and each group is flipped
+        straight into the batch tensors by one launch (augmentor.augment_many).  As on the host route the mesh flow is returned
+        un-augmented and `event_valid` is the un-augmented old volume's bin sum.  plans: the samples' AugPlans (default: drawn here, in
+        sample order); reads: their read_sample results (default: read here).  Training datasets only."""
+        from .augmentor import AUGMENT_MAX, augment_many
+        self._check_device_batches()
+        idxs = list(idxs)
+        if plans is None:
+            plans = self.draw_plans(idxs)
+        if reads is None:
+            reads = [self.read_sample(i) for i in idxs]
+        n, dev = len(idxs), self.device
+        h, w = self.image_height, self.image_width
+        old = torch.empty(n, self.num_bins, h, w, device=dev)
+        new = torch.empty_like(old)
+        event_valid = torch.empty(n, 1, h, w, device=dev)
+        for i0 in range(0, n, AUGMENT_MAX):
+            k = min(AUGMENT_MAX, n - i0)
+            vols = self.voxel.many([s for _, seqs in reads[i0:i0 + k] for s in seqs])
+            for j in range(k):
+                torch.sum(vols[2 * j], dim=0, out=event_valid[i0 + j, 0])
+            augment_many(plans[i0:i0 + k], vols[0::2], vols[1::2], None, out=(old[i0:i0 + k], new[i0:i0 + k], None, None))
+        outs = [out for out, _ in reads]
+        flow = torch.stack([o['flow'] for o in outs]).float().to(dev)
+        batch = {'names': [o['names'] for o in outs], 'flow': flow,
+                 'fflow': torch.stack([o['fflow'] for o in outs]).to(dev),
+                 'valid': torch.ones(n, *flow.shape[2:], device=dev)}
+        if self.with_events:
+            batch['events'], batch['events_offset'] = [o['events'] for o in outs], [o['events_offset'] for o in outs]
+        batch['event_volume_old'], batch['event_volume_new'], batch['event_valid'] = old, new, event_valid
+        return batch
+
     def _finish(self, sample):
         if self.type == 'train':
             if self.augmentor is not None:

@@ -6,6 +6,14 @@ inflating the event and flow files.  Those release the GIL, so threads do: `Thre
 that builds samples ahead (each on its thread's current stream) and hands finished batches to the training loop in the
 sampler's order, a HIP event ordering every batch behind the launches that produced it.  Same iteration protocol as the
 DataLoader it replaces: iterable of dicts of stacked tensors, `len()`, `.dataset`, `.sampler`, drop_last.
+
+`device_batches=True` (datasets with `get_batch`: the training splits of hrem.HREMEventFlow and mvsec.MvsecEventFlow) builds a whole
+batch per pool task instead - voxelized by one launch sequence per 16 samples and augmented straight into the batch tensors on the
+GPU, so the event volumes never visit host memory.  The augmentation plans of a batch are drawn (`dataset.draw_plans`) on the
+consumer thread when the batch is submitted, in the sampler's order: a run seeded with numpy.random.seed is reproducible for any
+thread count, which the per-sample route (draws made by whichever worker runs first) is not.  The samples' files are still read by
+separate pool tasks (`dataset.read_sample`), submitted ahead of the batch's own task, so the pool's FIFO order rules out a task
+waiting for one that cannot start.
 """
 import collections
 import concurrent.futures
@@ -14,7 +22,11 @@ import torch
 
 
 class ThreadedBatchLoader:
-    def __init__(self, dataset, batch_size, shuffle=False, sampler=None, threads=4, drop_last=True, ahead=2, seed=0):
+    def __init__(self, dataset, batch_size, shuffle=False, sampler=None, threads=4, drop_last=True, ahead=2, seed=0, device_batches=False):
+        if device_batches and not hasattr(dataset, "get_batch"):
+            raise ValueError("ThreadedBatchLoader: device_batches=True needs a dataset with get_batch (a training split of "
+                             f"HREMEventFlow / MvsecEventFlow), got {type(dataset).__name__}")
+        self.device_batches = bool(device_batches)
         self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
         self.shuffle, self.drop_last, self.threads, self.ahead = shuffle, drop_last, max(1, int(threads)), max(1, int(ahead))
         self._epoch, self._seed = 0, seed
@@ -80,6 +92,18 @@ class ThreadedBatchLoader:
             return sample, ready, sdev
         return sample, None, None
 
+    def _batch(self, idxs, plans, reads):
+        """One pool task of the device route: the whole batch, built (and its hand-over event recorded) under the dataset's device."""
+        kw = {} if reads is None else {"reads": [f.result() for f in reads]}
+        dev = getattr(self.dataset, "device", None)
+        if torch.cuda.is_available() and dev is not None and torch.device(dev).type == "cuda":
+            with torch.cuda.device(dev):
+                batch = self.dataset.get_batch(idxs, plans, **kw)
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(dev))
+            return batch, ready, torch.device(dev)
+        return self.dataset.get_batch(idxs, plans, **kw), None, None
+
     def __iter__(self):
         idx = self._indices()
         self._epoch += 1
@@ -93,7 +117,13 @@ class ThreadedBatchLoader:
 
         def submit():
             b = next(todo, None)
-            if b is not None:
+            if b is None:
+                return
+            if self.device_batches:
+                plans = self.dataset.draw_plans(b) if hasattr(self.dataset, "draw_plans") else None      # here: in the sampler's order
+                reads = [pool.submit(self.dataset.read_sample, i) for i in b] if hasattr(self.dataset, "read_sample") else None
+                queue.append((reads or []) + [pool.submit(self._batch, b, plans, reads)])
+            else:
                 queue.append([pool.submit(self._sample, i) for i in b])
         for _ in range(self.ahead):
             submit()
@@ -101,6 +131,12 @@ class ThreadedBatchLoader:
             while queue:
                 futures = queue.popleft()
                 submit()
+                if self.device_batches:
+                    batch, ready, sdev = futures[-1].result()
+                    if ready is not None:
+                        torch.cuda.current_stream(sdev).wait_event(ready)
+                    yield batch
+                    continue
                 samples = []
                 for f in futures:
                     sample, ready, sdev = f.result()

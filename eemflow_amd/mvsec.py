@@ -223,6 +223,77 @@ class MvsecEventFlow(torch.utils.data.Dataset):
                 targets[-1]['events'], targets[-1]['events_offset'] = seqs[i].features, self._crop_offset()
         return volumes, targets
 
+    # ---------------------------------------------------------------------------------------- batches assembled on the device
+    def _batch_augmentor(self):
+        if self.type != 'train':
+            raise ValueError("get_batch: training datasets only (train=True); evaluation samples are centre-cropped - get_windows serves them")
+        aug = self.dense_augmentor if self.dense_augmentor is not None else self.augmentor
+        if aug is not None and not hasattr(aug, "draw"):
+            raise ValueError("get_batch: the augmentor is a callable without draw(): its samples keep the host route (dataset[i])")
+        return aug
+
+    def draw_plans(self, idxs):
+        """One AugPlan per sample, drawn from numpy.random in sample order - the draws `[self[i] for i in idxs]` would make."""
+        from .augmentor import AugPlan
+        aug = self._batch_augmentor()
+        h, w = self.image_height, self.image_width
+        return [aug.draw(h, w) if aug is not None else AugPlan(h, w) for _ in idxs]
+
+    def read_sample(self, idx):
+        """The host part of sample idx (its flow and two event sequences, as get_sample reads them): what get_batch takes as `reads`,
+        so that a loader can read ahead on threads."""
+        idx = idx % len(self)
+        flow = np.load(self.flow_list[idx])
+        if flow.shape[-1] == 2:
+            flow = flow.transpose(2, 0, 1)
+        flow = np.ascontiguousarray(flow)
+        if flow.dtype not in (np.float32, np.float64):
+            flow = flow.astype(np.float64)                        # what the host's `flow * [-1.0, 1.0]` / .float() make of it
+        k, n = self.frames_per_volume, len(self.event_list)
+        old = self._sequence([self.event_list[idx + i] for i in range(k)])
+        new = self._sequence([self.event_list[(idx + i + 1) % n] for i in range(k)])
+        self._upload(old)
+        return {'idx': self.names[idx], 'flow': torch.from_numpy(flow)}, (old, new)
+
+    def get_batch(self, idxs, plans=None, reads=None):
+        """The stacked batch of `[self[i] for i in idxs]` - the same keys, dtypes, shapes and bits - with every tensor on the device and
+        the event volumes never on the host: the samples are voxelized in groups of up to 16 (voxel.many) and each group is rescaled /
+        flipped / cropped straight into the batch tensors by one launch (augmentor.augment_many), flow and `valid` with them.  With
+        'aug_params' the d_event_volume_* keys are the event_volume_* tensors themselves (the host route passes the same arrays twice);
+        with a caller's FlowAugmentor, or none, they are the un-augmented volumes, as the host route leaves them.  plans: the samples'
+        AugPlans (default: drawn here, in sample order); reads: their read_sample results (default: read here).  Training datasets only."""
+        from .augmentor import AUGMENT_MAX, augment_many
+        self._batch_augmentor()
+        idxs = list(idxs)
+        if plans is None:
+            plans = self.draw_plans(idxs)
+        if reads is None:
+            reads = [self.read_sample(i) for i in idxs]
+        n, dev = len(idxs), self.device
+        ch, cw = plans[0].crop
+        old = torch.empty(n, self.num_bins, ch, cw, device=dev)
+        new = torch.empty_like(old)
+        flow = torch.empty(n, 2, ch, cw, device=dev)
+        valid = torch.empty(n, ch, cw, device=dev)
+        raw_old, raw_new = [], []
+        for i0 in range(0, n, AUGMENT_MAX):
+            k = min(AUGMENT_MAX, n - i0)
+            vols = self.voxel.many([s for _, seqs in reads[i0:i0 + k] for s in seqs])
+            flows = [out['flow'].to(dev) for out, _ in reads[i0:i0 + k]]
+            augment_many(plans[i0:i0 + k], vols[0::2], vols[1::2], flows,
+                         out=(old[i0:i0 + k], new[i0:i0 + k], flow[i0:i0 + k], valid[i0:i0 + k]))
+            raw_old += vols[0::2]
+            raw_new += vols[1::2]
+        batch = {'idx': [out['idx'] for out, _ in reads], 'flow': flow, 'valid': valid}
+        if self.with_events:
+            batch['events'] = [seqs[0].features for _, seqs in reads]
+            batch['events_offset'] = [self._crop_offset() for _ in reads]
+        dense = self.dense_augmentor is not None
+        batch['event_volume_new'], batch['event_volume_old'] = new, old
+        batch['d_event_volume_new'] = new if dense else torch.stack(raw_new)
+        batch['d_event_volume_old'] = old if dense else torch.stack(raw_old)
+        return batch
+
     def __getitem__(self, idx):
         sample = self.get_sample(idx % len(self))
         if self.type == 'train':

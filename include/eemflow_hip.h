@@ -313,6 +313,34 @@ int eemflow_voxelize_pair(const double* events1, int64_t n1, const double* event
 int eemflow_voxelize_many(int nsets, const double* const* events, const int64_t* n_events, int bins, int h, int w, int normalize,
                           float* const* grids, void* stream);
 
+/* Augmentation of n (1..EEMFLOW_AUGMENT_MAX) training samples of one source size and one output size by ONE launch, written into the
+ * batch tensors: vol_old[i], vol_new[i] ([C][H][W] fp32), flow[i] ([2][H][W]; fp64 with flow_f64 != 0, else fp32; a NULL entry, or
+ * flow == NULL, is a sample without flow: HREM's mesh flow is returned un-augmented by the reference) and plans[i] are HOST arrays, read
+ * before the call returns.  Destinations (device): out_old, out_new [n][C][ch][cw], out_flow [n][2][ch][cw], out_valid [n][ch][cw], all
+ * fp32; sample i fills slice i; the last two may be NULL when no sample has a flow, and are left untouched for a sample without one.
+ * Output pixel (r, c) reads the resized (or original) RH x RW image at (y0 + r, x0 + c), mirrored first (vflip: row RH-1-row, hflip:
+ * column RW-1-column): resize, then flips, then crop, as the host does.  Resized: RH = round(H * scale_y), RW = round(W * scale_x) (ties
+ * to even); destination index d samples the source at (d + 0.5) / scale - 0.5, the two neighbours clamped, blended as
+ * top = v00*(1-tx) + v01*tx, bot = v10*(1-tx) + v11*tx, out = top*(1-ty) + bot*ty in unfused fp64 and rounded to the source's type.
+ * Flow: that sample, times (scale_x, scale_y) in fp64 when resized, times -1 on u for hflip and on v for vflip, rounded to fp32 once.
+ * valid = 1 where both written components are finite and their fp32 norm is > 0 (both squares underflowing to 0 counts as 0), else 0.
+ * Stream-ordered, no host synchronisation, no allocation: the plans travel as kernel arguments.
+ * Replaces: FlowAugmentor.spatial_transform / spatial_transform_no_resize and DenseSparseAugmentor.spatial_transform
+ * (utils/augumentor.py:158-257,389-419) on HWC numpy copies of the volumes, at the call sites loader/HREM.py:252 and
+ * loader/MVSEC.py:170-187 (with the valid mask of MVSEC.py:185). */
+#define EEMFLOW_AUGMENT_MAX 16
+typedef struct eemflow_aug_plan {
+    double scale_x, scale_y;   /* used when resized != 0 */
+    int resized;
+    int RH, RW;                /* size of the image the crop is taken from: the source's when not resized */
+    int hflip, vflip;
+    int y0, x0;                /* top-left corner of the crop */
+    int reserved;
+} eemflow_aug_plan;
+int eemflow_augment_many(int n, const float* const* vol_old, const float* const* vol_new, const void* const* flow, int flow_f64,
+                         const eemflow_aug_plan* plans, int C, int H, int W, int ch, int cw, float* out_old, float* out_new,
+                         float* out_flow, float* out_valid, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training step of EEMFlow (train_mvsec.py:229-258).  Weights live on the device in state_dict order; one
  * flat gradient buffer in the same order is what a data-parallel job all-reduces (RCCL) between the two calls.
