@@ -11,7 +11,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 from .augmentor import AugPlan, apply_host, augment_many   # noqa: F401
 from .eemflow import EEMFlow            # noqa: F401
-from .iwe import fwl, fwl_many, iwe, iwe_many, warp_events   # noqa: F401
+from .iwe import contrast_many, fwl, fwl_loss, fwl_many, iwe, iwe_many, warp_events   # noqa: F401
 from .metrics import fb_check          # noqa: F401
 from .padder import InputPadder         # noqa: F401
 from .viz import ImageWriter, event_image, event_image_many, flow_to_image, flow_to_image_many   # noqa: F401

@@ -66,8 +66,36 @@ class AugPlan:
     def astuple(self):
         return (self.resized, float(self.scale_x), float(self.scale_y), self.RH, self.RW, self.hflip, self.vflip, self.y0, self.x0, self.crop)
 
+    def event_map(self, h, w):
+        """(ax, bx, ay, by): where an event at (x, y) of the h x w source frame lies in the augmented frame, x' = ax * x + bx and
+        y' = ay * y + by - resize, then flip, then crop, in apply_host's order.  The resize is x' = (x + 0.5) * scale_x - 0.5, the
+        inverse of the sample position (d + 0.5) / f - 0.5 that resize_linear uses; the horizontal flip x' = RW - 1 - x'; the crop
+        x' -= x0; the same in y.  What eemflow_amd.iwe takes as `maps=`."""
+        if not self.resized and (int(h), int(w)) != (self.RH, self.RW):
+            raise ValueError(f"AugPlan.event_map: the plan was drawn for a {self.RH}x{self.RW} frame, not {h}x{w}")
+        ax = ay = 1.0
+        bx = by = 0.0
+        if self.resized:
+            ax, bx = float(self.scale_x), 0.5 * float(self.scale_x) - 0.5
+            ay, by = float(self.scale_y), 0.5 * float(self.scale_y) - 0.5
+        if self.hflip:
+            ax, bx = -ax, (self.RW - 1) - bx
+        if self.vflip:
+            ay, by = -ay, (self.RH - 1) - by
+        return ax, bx - self.x0, ay, by - self.y0
+
     def __repr__(self):
         return "AugPlan(resized=%r, scale_x=%r, scale_y=%r, RH=%d, RW=%d, hflip=%r, vflip=%r, y0=%d, x0=%d, crop=%r)" % self.astuple()
+
+
+def event_map_after_offset(plan, offset, h, w):
+    """The event map of a dataset sample: the dataset's own events_offset (ox, oy) first, x - ox, then the plan's map on the h x w frame;
+    plan=None gives the pure offset map (1, -ox, 1, -oy)."""
+    ox, oy = float(offset[0]), float(offset[1])
+    if plan is None:
+        return (1.0, -ox, 1.0, -oy)
+    ax, bx, ay, by = plan.event_map(h, w)
+    return (ax, bx - ax * ox, ay, by - ay * oy)
 
 
 def apply_host(plan, *arrays):

@@ -58,6 +58,13 @@ def build_parser():
                            help='build every training batch on the GPU: voxelized, flipped and assembled without a copy of the event volumes '
                                 'through host memory (implies the threaded loader with at least one thread; same batches as the host route '
                                 'under the same numpy seed, and reproducible for any --num_workers)')
+            q.add_argument('--contrast_weight', default=0.0, type=float, metavar='W',
+                           help='add W times the contrast term - minus the mean flow warp loss of the batch under the last prediction, no '
+                                'ground truth needed - to the loss (not in the reference; the samples then carry their events, every model '
+                                'trains through the autograd engine and EEMFlow predicts at the full frame; needs --device_batches or an '
+                                'un-augmented dataset)')
+            q.add_argument('--self_supervised', action='store_true',
+                           help='with --contrast_weight: train on the contrast term alone, the ground-truth flow is not read')
         q.add_argument('--train_iters', default=6000000 if train else 1000000, type=int, metavar='N', help='number of total iterations')
         q.add_argument('-se', '--start-epoch', action='store_true', help='restart from lasted_ckpt.pth.tar of the run folder')
         q.add_argument('-be', '--best_epe', default=1e5, type=float)
@@ -105,13 +112,13 @@ def load_config(path):
     return json.load(open(path)) if path else copy.deepcopy(DEFAULT_CONFIG)
 
 
-def build_model(name, config, training):
+def build_model(name, config, training, mesh=True):
     if name == "EEMFlow":
         from .eemflow import EEMFlow
         # HREM's training target is the 16x16 mesh flow (HREM.py:254-255); the reference script builds the model without
         # out_mesh_size and its loss then meets a full-resolution prediction.  Training here predicts at mesh size
         # (EEMFlow.py:126-132), evaluation at full resolution against the upsampled mesh flow (HREM.py:264-267).
-        return EEMFlow(config=config, n_first_channels=5, out_mesh_size=training)
+        return EEMFlow(config=config, n_first_channels=5, out_mesh_size=training and mesh)   # (mesh=False: the contrast term needs the full frame)
     if name == "eraft":                                             # train_EEMFlow_HREM.py:30-32 / test_EEMFlow_HREM.py
         from .eraft import ERAFT
         split = 'train' if training else 'test'
@@ -135,6 +142,8 @@ def per_rank_batch(batch_size, world):
 def train(args):
     from . import harness, parallel
     from .hrem import HREMEventFlow
+    if getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0:
+        raise SystemExit("--self_supervised needs a --contrast_weight: there is no other loss")
     # one process per GPU under torchrun: every rank trains on its shard of the samples, the trainer all-reduces the flat gradient
     # (RCCL), rank 0 writes the logs and checkpoints
     rank, local_rank, world = parallel.init_distributed()
@@ -143,7 +152,8 @@ def train(args):
         # this rank's host threads (the loader's workers inherit the mask) on the CPUs next to its GPU
         parallel.pin_host_threads_to_gpu_numa(parallel.local_device_index(local_rank))
     config = load_config(args.config)
-    model = build_model(args.model_name, config, training=True)
+    contrast = float(getattr(args, "contrast_weight", 0.0))
+    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0)
     config["train"]["lr"] = args.lr                                                  # train_EEMFlow_HREM.py:56-59
     config["train"]["wdecay"] = args.wd
     config["train"]["num_steps"] = args.train_iters
@@ -161,8 +171,15 @@ def train(args):
     logger = harness.Logger(os.path.join(save_path, 'train.log') if rank == 0 else None, verbose=rank == 0)
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
-    train_set = HREMEventFlow(args=config["data_loader"]["train"]["args"], train=True, root=args.data_root, device=dev)
+    train_set = HREMEventFlow(args=config["data_loader"]["train"]["args"], train=True, root=args.data_root, device=dev,
+                              with_events=contrast != 0.0)
+    if contrast != 0.0 and train_set.augmentor is not None and not args.device_batches:
+        # the host route flips the volumes without telling where the events went; get_batch hands out batch['events_map']
+        raise SystemExit("--contrast_weight with an augmented dataset needs --device_batches: only batches assembled on the device carry "
+                         "the event map of their augmentation")
     sampler = torch.utils.data.distributed.DistributedSampler(train_set, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
+    if contrast != 0.0:
+        args.device_batches = True                                   # (un-augmented: get_batch all the same - it stacks nothing ragged)
     if args.num_workers > 0 or args.device_batches:   # the reference's worker count: here host threads that read / inflate / voxelize samples ahead
         from .loader import ThreadedBatchLoader
         loader = ThreadedBatchLoader(train_set, per_rank_batch(args.batch_size, world), shuffle=sampler is None, sampler=sampler,
@@ -184,10 +201,11 @@ def train(args):
     # HREM training samples here are the un-cropped frames, so the padder is sized from the first batch itself (image_size=None).
     # EEMFlow: the fused step inside the library; E-RAFT / EEMFlow+: the reference's statement sequence over the operator-level
     # autograd route (their data-parallel exchange is the flat-gradient all-reduce in TrainRaftEvents._train_iters_autograd)
-    engine = "fused" if args.model_name == "EEMFlow" else "autograd"
+    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 else "autograd"     # (the fused trainer has no contrast term)
     tr = harness.TrainRaftEvents(loader, None, lr=tcfg["lr"], wdecay=tcfg["wdecay"], epsilon=tcfg["epsilon"],
                                  num_steps=tcfg["num_steps"], clip=tcfg["clip"], gamma=tcfg["gamma"], logger=logger,
-                                 start_iteration=start_iteration, engine=engine, mixed_precision=tcfg.get("mixed_precision", True))
+                                 start_iteration=start_iteration, engine=engine, mixed_precision=tcfg.get("mixed_precision", True),
+                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False))
     for epoch in range(start_epoch, max(args.train_iters // args.val_iters, 1)):
         if sampler is not None:
             sampler.set_epoch(epoch)

@@ -2,9 +2,10 @@
 // warp_events_flow_torch, utils_luo/event_utils.py:9-51; the loop around it Test.inference_img_warp_loss, test_mvsec.py:753-852, whose
 // variance-ratio form of the flow warp loss sits at :821-824).
 //
-// Per job: events [n][4] f64 (t, x, y, p), time-sorted; a flow [2][h][w] fp32 or NULL (zero flow); scalars t0, scale, ox, oy.  All
-// arithmetic is fp64 and unfused (this file is built with -ffp-contract=off):
-//   warp        xe = x - ox, ye = y - oy; (u, v) = the bilinear sample of the flow at (xe, ye) in pixel coordinates - x0 = floor(xe),
+// Per job: events [n][4] f64 (t, x, y, p), time-sorted; a flow [2][h][w] fp32 or NULL (zero flow); scalars t0, scale and an affine event
+// map (ax, bx, ay, by) - an offset (ox, oy) is (1, -ox, 1, -oy), the same bits.  All arithmetic is fp64 and unfused (this file is built
+// with -ffp-contract=off; the per-event functions live in iwe_shared.h, which the gradient, iwe_grad.hip, includes too):
+//   warp        xe = ax * x + bx, ye = ay * y + by; (u, v) = the bilinear sample of the flow at (xe, ye) in pixel coordinates - x0 = floor(xe),
 //               fx = xe - x0, the four neighbours weighted (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy and summed in that order, a
 //               neighbour outside [0, w-1] x [0, h-1] contributing 0 (grid_sample, align_corners=True, zero padding);
 //               tau = (t - t0) * scale; xw = xe + u * tau, yw = ye + v * tau
@@ -43,124 +44,9 @@
 // launch, one job after the other).
 #include <string.h>
 
-#include "common.h"
-
-#include <algorithm>
-#include <cstdlib>
-#include <mutex>
+#include "iwe_shared.h"
 
 namespace {
-
-constexpr int IWE_MAX_JOBS = 32;
-constexpr int VT = 1024;                 // threads per binning block (also the maximum number of bands + 1)
-constexpr unsigned NONE = 0xffffffffu;
-
-// ------------------------------------------------------------------------------------------------ per-event arithmetic
-// bilinear sample of both flow channels at (xe, ye), pixel coordinates, zero padding; a NULL flow is the zero flow
-__device__ __forceinline__ void iwe_sample(const float* __restrict__ flow, double xe, double ye, int h, int w, double& u, double& v) {
-    u = 0.0;
-    v = 0.0;
-    if (!flow) return;
-    if (!(xe > -1.0 && xe < (double)w && ye > -1.0 && ye < (double)h)) return;     // every neighbour outside (also NaN coordinates)
-    const double xf = floor(xe), yf = floor(ye);
-    const double fx = xe - xf, fy = ye - yf;
-    const int x0 = (int)xf, y0 = (int)yf;                                          // -1 .. w-1, -1 .. h-1
-    const bool xl = x0 >= 0, xr = x0 + 1 <= w - 1, yt = y0 >= 0, yb = y0 + 1 <= h - 1;
-    const double w00 = (1.0 - fx) * (1.0 - fy), w01 = fx * (1.0 - fy), w10 = (1.0 - fx) * fy, w11 = fx * fy;
-    const long hw = (long)h * w;
-    const long o = (long)y0 * w + x0;
-    const double u00 = (xl && yt) ? w00 * (double)flow[o] : 0.0, v00 = (xl && yt) ? w00 * (double)flow[hw + o] : 0.0;
-    const double u01 = (xr && yt) ? w01 * (double)flow[o + 1] : 0.0, v01 = (xr && yt) ? w01 * (double)flow[hw + o + 1] : 0.0;
-    const double u10 = (xl && yb) ? w10 * (double)flow[o + w] : 0.0, v10 = (xl && yb) ? w10 * (double)flow[hw + o + w] : 0.0;
-    const double u11 = (xr && yb) ? w11 * (double)flow[o + w + 1] : 0.0, v11 = (xr && yb) ? w11 * (double)flow[hw + o + w + 1] : 0.0;
-    u = ((u00 + u01) + u10) + u11;
-    v = ((v00 + v01) + v10) + v11;
-}
-
-struct IweEvent {
-    double xw, yw;
-    int c;
-};
-
-__device__ __forceinline__ IweEvent iwe_warp(const double* __restrict__ ev, long i, const float* __restrict__ flow, double t0, double scale,
-                                             double ox, double oy, int h, int w) {
-    const double t = ev[i * 4 + 0], x = ev[i * 4 + 1], y = ev[i * 4 + 2], p = ev[i * 4 + 3];
-    const double xe = x - ox, ye = y - oy;
-    double u, v;
-    iwe_sample(flow, xe, ye, h, w, u, v);
-    const double tau = (t - t0) * scale;
-    IweEvent e;
-    e.xw = xe + u * tau;
-    e.yw = ye + v * tau;
-    e.c = p > 0.0 ? 0 : 1;
-    return e;
-}
-
-// the votes of a warped event: rows Y0, Y0 + 1 and columns X0, X0 + 1 with weights wy[dy] * wx[dx]
-struct IweVotes {
-    int X0, Y0;
-    double gx, gy;
-    bool finite, inside;     // inside: at least one of the four targets can be in the frame
-};
-
-__device__ __forceinline__ IweVotes iwe_votes(const IweEvent& e, int h, int w) {
-    IweVotes q;
-    q.finite = isfinite(e.xw) && isfinite(e.yw);
-    q.inside = q.finite && e.xw > -1.0 && e.xw < (double)w && e.yw > -1.0 && e.yw < (double)h;
-    q.X0 = q.Y0 = 0;
-    q.gx = q.gy = 0.0;
-    if (q.inside) {
-        const double xf = floor(e.xw), yf = floor(e.yw);
-        q.X0 = (int)xf;
-        q.Y0 = (int)yf;
-        q.gx = e.xw - xf;
-        q.gy = e.yw - yf;
-    }
-    return q;
-}
-
-// ------------------------------------------------------------------------------------------------ block helpers
-// sums of two values over the block, by a fixed tree (wave shuffles, then the waves' sums in order; sh: 2 * NT / 64 doubles): the same
-// bits whatever the schedule.  Every thread of the block calls it; the results are valid in thread 0.
-template <int NT>
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* sh) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a += __shfl_down(a, d);
-        b += __shfl_down(b, d);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                               // (sh may still be read from a call before)
-    if (lane == 0) { sh[2 * wave] = a; sh[2 * wave + 1] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = b = 0.0;
-        for (int k = 0; k < NT / 64; ++k) { a += sh[2 * k]; b += sh[2 * k + 1]; }
-    }
-}
-
-// exclusive prefix sum over the block's VT threads (sh: VT / 64 words)
-__device__ __forceinline__ unsigned block_exscan(unsigned v, unsigned* sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(x, d);
-        if (lane >= d) x += t;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    unsigned before = 0;
-#pragma unroll
-    for (int k = 0; k < VT / 64; ++k) before += k < wave ? sh[k] : 0u;
-    return before + x - v;
-}
-
-struct IwePlan {
-    int rows;                // image rows per band
-    int nb;                  // bands
-    int cells;               // fp64 cells of a band: 2 * rows * w
-};
 
 // One job of a launch: blockIdx.y picks it (one frame size and plan, its own events, flow, slabs, run table, partials and image)
 struct IweJob {
@@ -172,11 +58,12 @@ struct IweJob {
     double* part;            // [parts][2]: (sum S, sum S^2) of a band (binned) or of a finishing block (direct)
     double* dropped;         // [nblk]: events with a non-finite warped position, per binning block (direct: one slot)
     double t0, scale;
+    IweMap map;              // xe = ax * x + bx, ye = ay * y + by
     long n;
     int nblk;                // binning blocks (slabs) of this job
     int pad;
 };
-struct IweJobs { IweJob j[IWE_MAX_JOBS]; };      // 88 bytes each: 2.8 KB of kernel arguments at 32 jobs
+struct IweJobs { IweJob j[IWE_MAX_JOBS]; };      // 120 bytes each: 3.8 KB of kernel arguments at 32 jobs
 
 __device__ __forceinline__ unsigned iwe_fix(double wgt) { return (unsigned)(wgt * 2147483648.0 + 0.5); }       // wgt in [0, 1]
 
@@ -184,7 +71,7 @@ __device__ __forceinline__ unsigned iwe_fix(double wgt) { return (unsigned)(wgt 
 // Block `blk` owns the slab recs[blk * S .. (blk + 1) * S) (S = 2 * 1024 * EPT records): its row records sorted by band, and row
 // `blk` of the run table: run_start[blk][b] = offset of band b's run inside the slab, run_start[blk][nb] = the slab's fill.
 template <int EPT>
-__global__ __launch_bounds__(VT) void iwe_bin_kernel(IweJobs jobs, int h, int w, double ox, double oy, IwePlan pl) {
+__global__ __launch_bounds__(VT) void iwe_bin_kernel(IweJobs jobs, int h, int w, IwePlan pl) {
     const IweJob& J = jobs.j[blockIdx.y];
     if ((int)blockIdx.x >= J.nblk) return;                         // a shorter event set of the launch
     const double* __restrict__ ev = J.ev;
@@ -207,7 +94,7 @@ __global__ __launch_bounds__(VT) void iwe_bin_kernel(IweJobs jobs, int h, int w,
         const long i = ((long)blockIdx.x * EPT + k) * VT + tid;
         band[2 * k] = band[2 * k + 1] = NONE;
         if (i < n) {
-            const IweEvent e = iwe_warp(ev, i, flow, t0, scale, ox, oy, h, w);
+            const IweEvent e = iwe_warp(ev, i, flow, t0, scale, J.map, h, w);
             const IweVotes q = iwe_votes(e, h, w);
             if (!q.finite) ++drop;
             if (q.inside) {
@@ -324,11 +211,11 @@ __global__ __launch_bounds__(256) void iwe_moments_kernel(IweJobs jobs, int npar
 
 // ------------------------------------------------------------------------------------------------ direct form
 __global__ __launch_bounds__(256) void iwe_direct_kernel(const double* __restrict__ ev, long n, const float* __restrict__ flow, double t0,
-                                                         double scale, double ox, double oy, int h, int w, double* __restrict__ acc,
+                                                         double scale, IweMap map, int h, int w, double* __restrict__ acc,
                                                          unsigned long long* __restrict__ ndrop) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const IweEvent e = iwe_warp(ev, i, flow, t0, scale, ox, oy, h, w);
+    const IweEvent e = iwe_warp(ev, i, flow, t0, scale, map, h, w);
     const IweVotes q = iwe_votes(e, h, w);
     if (!q.finite) atomicAdd(ndrop, 1ull);
     if (!q.inside) return;
@@ -371,15 +258,12 @@ __global__ __launch_bounds__(256) void iwe_warp_kernel(const double* __restrict_
                                                        double scale, double ox, double oy, int h, int w, double* __restrict__ xy) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const IweEvent e = iwe_warp(ev, i, flow, t0, scale, ox, oy, h, w);
+    const IweEvent e = iwe_warp(ev, i, flow, t0, scale, IweMap{1.0, -ox, 1.0, -oy}, h, w);
     xy[2 * i] = e.xw;
     xy[2 * i + 1] = e.yw;
 }
 
 // ------------------------------------------------------------------------------------------------ host
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline long iwe_blocks(long n, int ept) { return (n + (long)VT * ept - 1) / ((long)VT * ept); }
-constexpr long IWE_MAX_BLOCKS = 4096;                              // 16.7 M events at 4 per thread; beyond: direct form
 inline int iwe_ept(long n) {
     const char* e = getenv("EEM_IWE_EPT");                         // events per binning thread, 1 / 2 / 4 (read per call: the tests run all three)
     const int forced = e ? atoi(e) : 0;
@@ -390,28 +274,6 @@ inline int iwe_ept(long n) {
 }
 constexpr int IWE_DIRECT_PARTS = 256;
 
-bool iwe_direct_forced() {
-    const char* e = getenv("EEM_IWE_DIRECT");                      // read per call: the tests run both forms in one process
-    return e && e[0] == '1';
-}
-
-// the band layout of an h x w frame, or false: the direct form serves it
-bool iwe_plan(long nmax, int h, int w, IwePlan* pl) {
-    if (iwe_direct_forced() || iwe_blocks(nmax, 4) > IWE_MAX_BLOCKS) return false;
-    // 9216 fp64 cells (72 KB) per band: two blocks per CU; a frame wider than that still gets one-row bands up to 150 KB of LDS
-    long rows = 9216 / (2L * w);
-    if (rows < 1) {
-        if (2L * w > 19200) return false;                      // 150 KB of fp64 cells beside the static tables
-        rows = 1;
-    }
-    const long spread = std::max(1L, (h + 239L) / 240);            // small frames: still up to a few hundred bands
-    rows = std::min(rows, spread);
-    if ((h + rows - 1) / rows > VT - 1) return false;              // thread nb of a binning block holds the slab's fill
-    pl->rows = (int)rows;
-    pl->nb = (int)((h + rows - 1) / rows);
-    pl->cells = (int)(2 * rows * w);
-    return true;
-}
 
 struct IweLayout { size_t recs, table, part, dropped, total; };
 
@@ -427,7 +289,7 @@ IweLayout iwe_layout_binned(long n, int ept, const IwePlan& pl) {
 }
 
 template <int EPT>
-int launch_bin(const IweJobs& jobs, int njobs, long nblk_max, int h, int w, double ox, double oy, const IwePlan& pl, hipStream_t stream) {
+int launch_bin(const IweJobs& jobs, int njobs, long nblk_max, int h, int w, const IwePlan& pl, hipStream_t stream) {
     constexpr int stage_bytes = 2 * VT * EPT * 12;
     if (stage_bytes > 32 * 1024) {
         static bool raised = false;
@@ -436,7 +298,7 @@ int launch_bin(const IweJobs& jobs, int njobs, long nblk_max, int h, int w, doub
             raised = true;
         }
     }
-    hipLaunchKernelGGL((iwe_bin_kernel<EPT>), dim3((unsigned)nblk_max, njobs), dim3(VT), stage_bytes, stream, jobs, h, w, ox, oy, pl);
+    hipLaunchKernelGGL((iwe_bin_kernel<EPT>), dim3((unsigned)nblk_max, njobs), dim3(VT), stage_bytes, stream, jobs, h, w, pl);
     return EEM_OK;
 }
 
@@ -453,7 +315,7 @@ size_t iwe_scratch_bytes(int k, const int64_t* n, int h, int w) {
 }
 
 int iwe_launch(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0, const double* scale,
-               double ox, double oy, int h, int w, float* const* iwe, double* moments, char* scratch, hipStream_t stream) {
+               const double (*maps)[4], int h, int w, float* const* iwe, double* moments, char* scratch, hipStream_t stream) {
     long nmax = 0;
     for (int i = 0; i < k; ++i) nmax = std::max(nmax, (long)n[i]);
     const long hw = (long)h * w;
@@ -471,7 +333,8 @@ int iwe_launch(int k, const double* const* events, const int64_t* n, const float
             EEM_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)2 * hw * 8 + 8, stream));
             if (n[i] > 0)
                 hipLaunchKernelGGL(iwe_direct_kernel, dim3((unsigned)((n[i] + 255) / 256)), dim3(256), 0, stream, events[i], (long)n[i],
-                                   flows ? flows[i] : nullptr, t0[i], scale[i], ox, oy, h, w, acc, ndrop);
+                                   flows ? flows[i] : nullptr, t0[i], scale[i],
+                                   IweMap{maps[i][0], maps[i][1], maps[i][2], maps[i][3]}, h, w, acc, ndrop);
             hipLaunchKernelGGL(iwe_direct_finish_kernel, dim3(parts), dim3(256), 0, stream, acc, ndrop, iwe[i], hw, part, dropped);
             IweJobs one;
             memset(&one, 0, sizeof(one));
@@ -498,6 +361,7 @@ int iwe_launch(int k, const double* const* events, const int64_t* n, const float
         J.dropped = reinterpret_cast<double*>(q + l.dropped);
         J.t0 = t0[i];
         J.scale = scale[i];
+        J.map = IweMap{maps[i][0], maps[i][1], maps[i][2], maps[i][3]};
         J.n = (long)n[i];
         J.nblk = (int)iwe_blocks((long)n[i], ept);
         nblk_max = std::max(nblk_max, (long)J.nblk);
@@ -506,9 +370,9 @@ int iwe_launch(int k, const double* const* events, const int64_t* n, const float
     if (nblk_max > 0) {
         int rc;
         switch (ept) {
-            case 1: rc = launch_bin<1>(jobs, k, nblk_max, h, w, ox, oy, pl, stream); break;
-            case 2: rc = launch_bin<2>(jobs, k, nblk_max, h, w, ox, oy, pl, stream); break;
-            default: rc = launch_bin<4>(jobs, k, nblk_max, h, w, ox, oy, pl, stream); break;
+            case 1: rc = launch_bin<1>(jobs, k, nblk_max, h, w, pl, stream); break;
+            case 2: rc = launch_bin<2>(jobs, k, nblk_max, h, w, pl, stream); break;
+            default: rc = launch_bin<4>(jobs, k, nblk_max, h, w, pl, stream); break;
         }
         if (rc != EEM_OK) return rc;
     }
@@ -535,10 +399,7 @@ int iwe_launch(int k, const double* const* events, const int64_t* n, const float
     return EEM_OK;
 }
 
-// Scratch arenas (record slabs, run tables, partials; the direct form's fp64 image), grown on demand and owned by the library: one per
-// (device, stream) for up to eight streams, so that chunks in flight on different streams do not wait for each other; a ninth stream
-// takes over the least recently used arena after waiting for the kernels that last used it.  The lock is held over the launches and
-// the event record, so a take-over always sees the event of the arena's last user.
+// the arenas that iwe_shared.h describes
 struct Arena { void* p = nullptr; size_t cap = 0; int dev = -1; hipEvent_t done = nullptr; void* stream = nullptr; unsigned long used = 0; };
 Arena g_arenas[8];
 unsigned long g_tick = 0;
@@ -546,16 +407,9 @@ std::mutex g_arena_lock;
 
 }  // namespace
 
-extern "C" int eemflow_iwe_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
-                                const double* scale, double ox, double oy, int h, int w, float* const* iwe, double* moments, void* stream) {
-    EEM_REQUIRE(k >= 1 && k <= IWE_MAX_JOBS, "eemflow_iwe_many: 1..%d jobs per call; got %d", IWE_MAX_JOBS, k);
-    EEM_REQUIRE(events && n && t0 && scale && iwe && moments, "eemflow_iwe_many: NULL argument");
-    EEM_REQUIRE(h >= 1 && w >= 1 && (long)h * w <= (1L << 30), "eemflow_iwe_many: bad size %dx%d", h, w);
-    for (int i = 0; i < k; ++i) {
-        EEM_REQUIRE(n[i] >= 0 && n[i] < (1LL << 40), "eemflow_iwe_many: job %d has n=%ld events", i, (long)n[i]);
-        EEM_REQUIRE((events[i] || n[i] == 0) && iwe[i], "eemflow_iwe_many: job %d has a NULL buffer", i);
-    }
-    std::lock_guard<std::mutex> guard(g_arena_lock);
+std::mutex& iwe_arena_lock() { return g_arena_lock; }
+
+int iwe_arena_take(size_t need, void* stream, char** scratch, void** token) {
     int dev = 0;
     EEM_HIP_CHECK(hipGetDevice(&dev));
     Arena* ar = nullptr;
@@ -568,7 +422,6 @@ extern "C" int eemflow_iwe_many(int k, const double* const* events, const int64_
         ar->stream = stream;
     }
     ar->used = ++g_tick;
-    const size_t need = iwe_scratch_bytes(k, n, h, w);
     if (ar->p == nullptr || ar->dev != dev || ar->cap < need) {
         if (ar->p) {                                                             // hipFree synchronises with work using it
             int cur = dev;
@@ -582,9 +435,42 @@ extern "C" int eemflow_iwe_many(int k, const double* const* events, const int64_
         if (!ar->done) EEM_HIP_CHECK(hipEventCreateWithFlags(&ar->done, hipEventDisableTiming));
         ar->dev = dev;
     }
-    const int rc = iwe_launch(k, events, n, flows, t0, scale, ox, oy, h, w, iwe, moments, (char*)ar->p, (hipStream_t)stream);
-    if (rc == EEM_OK) EEM_HIP_CHECK(hipEventRecord(ar->done, (hipStream_t)stream));
+    *scratch = (char*)ar->p;
+    *token = ar;
+    return EEM_OK;
+}
+
+int iwe_arena_done(void* token, void* stream) {
+    EEM_HIP_CHECK(hipEventRecord(static_cast<Arena*>(token)->done, (hipStream_t)stream));
+    return EEM_OK;
+}
+
+extern "C" int eemflow_iwe_map_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                                    const double* scale, const double (*maps)[4], int h, int w, float* const* iwe, double* moments,
+                                    void* stream) {
+    EEM_REQUIRE(k >= 1 && k <= IWE_MAX_JOBS, "eemflow_iwe_many: 1..%d jobs per call; got %d", IWE_MAX_JOBS, k);
+    EEM_REQUIRE(events && n && t0 && scale && maps && iwe && moments, "eemflow_iwe_many: NULL argument");
+    EEM_REQUIRE(h >= 1 && w >= 1 && (long)h * w <= (1L << 30), "eemflow_iwe_many: bad size %dx%d", h, w);
+    for (int i = 0; i < k; ++i) {
+        EEM_REQUIRE(n[i] >= 0 && n[i] < (1LL << 40), "eemflow_iwe_many: job %d has n=%ld events", i, (long)n[i]);
+        EEM_REQUIRE((events[i] || n[i] == 0) && iwe[i], "eemflow_iwe_many: job %d has a NULL buffer", i);
+    }
+    std::lock_guard<std::mutex> guard(g_arena_lock);
+    char* scratch = nullptr;
+    void* token = nullptr;
+    int rc = iwe_arena_take(iwe_scratch_bytes(k, n, h, w), stream, &scratch, &token);
+    if (rc != EEM_OK) return rc;
+    rc = iwe_launch(k, events, n, flows, t0, scale, maps, h, w, iwe, moments, scratch, (hipStream_t)stream);
+    if (rc == EEM_OK) rc = iwe_arena_done(token, stream);
     return rc;
+}
+
+extern "C" int eemflow_iwe_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                                const double* scale, double ox, double oy, int h, int w, float* const* iwe, double* moments, void* stream) {
+    EEM_REQUIRE(k >= 1 && k <= IWE_MAX_JOBS, "eemflow_iwe_many: 1..%d jobs per call; got %d", IWE_MAX_JOBS, k);
+    double maps[IWE_MAX_JOBS][4];
+    for (int i = 0; i < k; ++i) { maps[i][0] = 1.0; maps[i][1] = -ox; maps[i][2] = 1.0; maps[i][3] = -oy; }
+    return eemflow_iwe_map_many(k, events, n, flows, t0, scale, maps, h, w, iwe, moments, stream);
 }
 
 extern "C" int eemflow_warp_events(const double* events, int64_t n, const float* flow, int h, int w, double t0, double scale, double ox,

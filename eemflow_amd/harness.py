@@ -27,7 +27,7 @@ import torch
 
 from .metrics import flow_error, flow_error_from_sums, flow_error_sums, flow_error_sums_many
 from . import parallel
-from .train import EEMFlowTrainer, sequence_loss
+from .train import EEMFlowTrainer, contrast_loss, sequence_loss
 
 
 class Logger:
@@ -464,12 +464,25 @@ class TrainRaftEvents:
 
     A loader that assembles its batches on the device (loader.ThreadedBatchLoader(device_batches=True)) needs nothing else here: the
     loops' `batch[key].to(dev).float()` returns the very tensor when it is float32 and already on `dev` (Tensor.to and Tensor.float
-    return self when nothing changes; tests/test_gpu_augment.py holds the data pointers equal), so no copy is made."""
+    return self when nothing changes; tests/test_gpu_augment.py holds the data pointers equal), so no copy is made.
+
+    contrast_weight / supervised (the autograd engine only): the loss is sequence_loss + contrast_weight * train.contrast_loss(last
+    prediction, batch['events'], batch['events_map']) - minus the mean flow warp loss of the batch, the ground-truth-free contrast
+    term; supervised=False trains on the contrast term alone and reads neither batch['flow'] nor batch['valid'].  The batches must
+    carry their events (a dataset built with with_events=True; get_batch adds 'events_map', batches without it use 'events_offset'),
+    and the prediction must be at the event frame's size (not out_mesh_size)."""
 
     def __init__(self, loader, image_size, lr=1e-4, wdecay=5e-5, epsilon=1e-8, num_steps=1000000, clip=1.0, gamma=0.8,
-                 logger=None, print_freq=100, engine="fused", mixed_precision=True, start_iteration=0):
+                 logger=None, print_freq=100, engine="fused", mixed_precision=True, start_iteration=0, contrast_weight=0.0,
+                 supervised=True):
         if engine not in ("fused", "autograd"):
             raise ValueError("engine must be 'fused' or 'autograd'")
+        self.contrast_weight, self.supervised = float(contrast_weight), bool(supervised)
+        if engine == "fused" and (self.contrast_weight != 0.0 or not self.supervised):
+            raise ValueError("TrainRaftEvents: the contrast term (contrast_weight != 0, supervised=False) is honoured by engine='autograd' "
+                             "only - the fused trainer has no contrast term")
+        if not self.supervised and self.contrast_weight == 0.0:
+            raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight")
         self.loader, self.image_size = loader, image_size
         self.opt = dict(lr=lr, wdecay=wdecay, epsilon=epsilon, num_steps=num_steps, clip=clip, gamma=gamma)
         self.logger = logger or Logger()
@@ -503,11 +516,18 @@ class TrainRaftEvents:
         done = 0
         for batch in self.loader:
             self.optimizer.zero_grad()
+            if self.contrast_weight != 0.0:
+                self._contrast_inputs(batch)                       # (before any GPU work: a loader without events fails at once)
             e1 = batch['event_volume_old'].to(dev).float()
             e2 = batch['event_volume_new'].to(dev).float()
             _, flow_list = model(e1, e2)
-            flow_gt, valid = _target_like(flow_list[-1], batch['flow'].to(dev).float(), batch['valid'].to(dev).float())
-            loss, metrics = sequence_loss(flow_list, flow_gt, valid, self.opt["gamma"])
+            if self.supervised:
+                flow_gt, valid = _target_like(flow_list[-1], batch['flow'].to(dev).float(), batch['valid'].to(dev).float())
+                loss, metrics = sequence_loss(flow_list, flow_gt, valid, self.opt["gamma"])
+            else:
+                loss, metrics = 0.0, {"epe": float("nan")}
+            if self.contrast_weight != 0.0:
+                loss = loss + self.contrast_weight * self._contrast_term(flow_list[-1], batch, e1)
             self.scaler.scale(loss).backward()
             if parallel.exchange_active():
                 # the still-SCALED gradients are exchanged, then unscaled: an overflow on one rank reaches every rank through the
@@ -533,6 +553,26 @@ class TrainRaftEvents:
             if val_iters is not None and done >= val_iters:
                 break
         return model
+
+    @staticmethod
+    def _contrast_inputs(batch):
+        """(event sets, maps) of a batch for the contrast term: 'events_map' where get_batch made one, else the pure offset maps."""
+        if 'events' not in batch:
+            raise ValueError("TrainRaftEvents: contrast_weight needs batches that carry their events - build the dataset with "
+                             "with_events=True (its get_batch / samples then have 'events')")
+        maps = batch.get('events_map')
+        if maps is None:
+            maps = [(1.0, -float(o[0]), 1.0, -float(o[1])) for o in batch.get('events_offset', [(0, 0)] * len(batch['events']))]
+        return list(batch['events']), list(maps)
+
+    @classmethod
+    def _contrast_term(cls, flow_pred, batch, volume):
+        """train.contrast_loss of the last prediction on the batch's events (float32, as the supervised loss is)."""
+        events, maps = cls._contrast_inputs(batch)
+        if tuple(flow_pred.shape[-2:]) != tuple(volume.shape[-2:]):
+            raise ValueError(f"TrainRaftEvents: the contrast term needs the prediction at the event frame's size {tuple(volume.shape[-2:])}, "
+                             f"got {tuple(flow_pred.shape[-2:])} - a model with out_mesh_size=True predicts the mesh flow")
+        return contrast_loss(flow_pred, events, maps).float()
 
     def train_iters(self, model, start_epoch=0, val_iters=None):
         if self.image_size is None:                              # padder sized from the data (cli: un-cropped HREM frames)

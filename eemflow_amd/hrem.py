@@ -261,8 +261,10 @@ class HREMEventFlow(torch.utils.data.Dataset):
         the event volumes never on the host: the samples are voxelized in groups of up to 16 (voxel.many) and each group is flipped
         straight into the batch tensors by one launch (augmentor.augment_many).  As on the host route the mesh flow is returned
         un-augmented and `event_valid` is the un-augmented old volume's bin sum.  plans: the samples' AugPlans (default: drawn here, in
-        sample order); reads: their read_sample results (default: read here).  Training datasets only."""
-        from .augmentor import AUGMENT_MAX, augment_many
+        sample order); reads: their read_sample results (default: read here).  With with_events=True the batch also carries 'events_map',
+        one (ax, bx, ay, by) per sample: the sample's plan (AugPlan.event_map) behind its events_offset, the pure offset map for a None
+        plan - where the events lie in the augmented frame (eemflow_amd.iwe's maps=).  Training datasets only."""
+        from .augmentor import AUGMENT_MAX, augment_many, event_map_after_offset
         self._check_device_batches()
         idxs = list(idxs)
         if plans is None:
@@ -287,6 +289,7 @@ class HREMEventFlow(torch.utils.data.Dataset):
                  'valid': torch.ones(n, *flow.shape[2:], device=dev)}
         if self.with_events:
             batch['events'], batch['events_offset'] = [o['events'] for o in outs], [o['events_offset'] for o in outs]
+            batch['events_map'] = [event_map_after_offset(p, o['events_offset'], h, w) for p, o in zip(plans, outs)]
         batch['event_volume_old'], batch['event_volume_new'], batch['event_valid'] = old, new, event_valid
         return batch
 

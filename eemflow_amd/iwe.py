@@ -20,8 +20,18 @@ t0 = t_last and scale = -1/T: xw = xe + u * (t_last - t) / T, every event is car
 t0 = t_first with the same scale: xw = xe - u * (t - t_first) / T, every event is carried back to the window's start.
 
 moments rows are {H*W, sum S, sum S^2, dropped} with S = iwe[0] + iwe[1]; var = sum S^2 / n - (sum S / n)^2;
-FWL = var(IWE under the flow) / var(IWE under zero flow), NaN when the denominator is 0.  CUDA tensors only: there is no CPU path, and
-no gradient.  EEM_IWE_DIRECT=1 takes the library's direct atomic form instead of the binned one.
+FWL = var(IWE under the flow) / var(IWE under zero flow), NaN when the denominator is 0.  CUDA tensors only: there is no CPU path.
+EEM_IWE_DIRECT=1 takes the library's direct atomic form instead of the binned one.
+
+GRADIENT (contrast maximisation).  `contrast_many` returns the variances and is differentiable with respect to the flows; `fwl_loss` is
+minus the mean FWL of a batch, the self-supervised training objective (train.contrast_loss applies it to a prediction).  The backward
+is the library's eemflow_iwe_grad_many (csrc/iwe_grad.hip): with G = 2 (S - mean) / (H W) per cell - the fp32 rounding of the stored
+image taken as the identity - an event hands d var / d xw = sum over its in-frame targets of G * wy[dy] * (dx ? +1 : -1) (and the same
+in y) times w_k * tau to each in-frame sample neighbour k of (xe, ye).  `iwe`, `iwe_many`, `fwl` and `fwl_many` build no graph.
+
+EVENT MAPS.  `maps=` gives one affine map (ax, bx, ay, by) per event set in place of `offset`: xe = ax * x + bx, ye = ay * y + by - where
+the events of an augmented (resized, flipped, cropped) sample lie in its frame (AugPlan.event_map; the datasets' get_batch hands them
+out as batch['events_map']).  offset = (ox, oy) is the map (1, -ox, 1, -oy), bit for bit.
 """
 import ctypes
 
@@ -198,3 +208,144 @@ def fwl_many(event_sets, flows, t_ref="end", offset=(0, 0)):
 def fwl(events, flow, t_ref="end", offset=(0, 0)):
     """The one-job form of fwl_many: a 0-dim float64 device tensor."""
     return fwl_many([events], [flow], t_ref=t_ref, offset=offset)[0]
+
+
+# ------------------------------------------------------------------------------------------------ gradient: contrast maximisation
+def _maps(name, maps, offset, k):
+    if maps is None:
+        ox, oy = _offset(name, offset)
+        return [(1.0, -ox, 1.0, -oy)] * k
+    maps = list(maps)
+    if len(maps) != k:
+        raise ValueError(f"{name}: one map (ax, bx, ay, by) per event set; got {len(maps)} maps for {k} sets")
+    out = []
+    for m in maps:
+        try:
+            ax, bx, ay, by = m
+            out.append((float(ax), float(bx), float(ay), float(by)))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: a map is (ax, bx, ay, by)") from None
+    return out
+
+
+def _map_table(maps):
+    return (ctypes.c_double * (4 * len(maps)))(*[v for m in maps for v in m])
+
+
+def _launch_maps(event_sets, flows, t0s, scales, maps, h, w, dev):
+    """_launch with one event map per job (eemflow_iwe_map_many)."""
+    k = len(event_sets)
+    images = [torch.empty(2, h, w, device=dev, dtype=torch.float32) for _ in range(k)]
+    moments = torch.empty(k, 4, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        for i0 in range(0, k, MAX_JOBS_PER_CALL):
+            c = min(MAX_JOBS_PER_CALL, k - i0)
+            ptr = ctypes.c_void_p * c
+            dbl = ctypes.c_double * c
+            _lib.check(_lib.lib().eemflow_iwe_map_many(
+                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
+                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
+                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
+                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), _map_table(maps[i0:i0 + c]), h, w,
+                ptr(*[t.data_ptr() for t in images[i0:i0 + c]]), moments[i0:].data_ptr(), _lib.current_stream_ptr(dev)))
+    return images, moments
+
+
+def iwe_grad_many(event_sets, flows, t0s, scales, maps, images, moments, coef):
+    """coef[i] * d var_i / d flows[i] for the jobs of a forward (`_launch_maps`' arguments, its images and moments): a list with one
+    (2,H,W) float32 tensor per job, None where the flow is None.  coef is a (k,) float64 device tensor; one eemflow_iwe_grad_many call
+    per 32 jobs on the current stream, no host synchronisation."""
+    k = len(event_sets)
+    dev = moments.device
+    h, w = images[0].shape[1], images[0].shape[2]
+    coef = coef.detach().to(torch.float64).contiguous()
+    moments = moments.contiguous()
+    grads = [torch.empty(2, h, w, device=dev, dtype=torch.float32) if f is not None else None for f in flows]
+    with torch.cuda.device(dev):
+        for i0 in range(0, k, MAX_JOBS_PER_CALL):
+            c = min(MAX_JOBS_PER_CALL, k - i0)
+            if all(f is None for f in flows[i0:i0 + c]):
+                continue
+            ptr = ctypes.c_void_p * c
+            dbl = ctypes.c_double * c
+            _lib.check(_lib.lib().eemflow_iwe_grad_many(
+                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
+                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
+                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
+                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), _map_table(maps[i0:i0 + c]), h, w,
+                ptr(*[t.data_ptr() for t in images[i0:i0 + c]]), moments[i0:].data_ptr(), coef[i0:].data_ptr(),
+                ptr(*[g.data_ptr() if g is not None else None for g in grads[i0:i0 + c]]), _lib.current_stream_ptr(dev)))
+    return grads
+
+
+class _Contrast(torch.autograd.Function):
+    """(k,) variances of the images of warped events of k jobs; backward: one eemflow_iwe_grad_many call per 32 jobs."""
+
+    @staticmethod
+    def forward(ctx, job, *flows):
+        event_sets, slots, t0s, scales, maps, h, w, dev = job
+        full = [None] * len(event_sets)                            # the flow (or None: zero flow) of every job
+        for i, f in zip(slots, flows):
+            full[i] = f.detach()
+        images, moments = _launch_maps(event_sets, full, t0s, scales, maps, h, w, dev)
+        ctx.job, ctx.full, ctx.images, ctx.moments = job, full, images, moments
+        var = variance(moments)
+        ctx.mark_non_differentiable(moments)
+        return var, moments
+
+    @staticmethod
+    def backward(ctx, gvar, _gmoments):
+        event_sets, slots, t0s, scales, maps, h, w, dev = ctx.job
+        wanted = [None] * len(event_sets)                          # a flow that needs no gradient is skipped like a zero flow
+        for q, i in enumerate(slots):
+            if ctx.needs_input_grad[1 + q]:
+                wanted[i] = ctx.full[i]
+        grads = iwe_grad_many(event_sets, wanted, t0s, scales, maps, ctx.images, ctx.moments, gvar)
+        return (None,) + tuple(grads[i] if wanted[i] is not None else None for i in slots)
+
+
+def _contrast(name, event_sets, flows, t_ref, offset, maps):
+    event_sets, flows, dev, h, w = _check_sets(name, event_sets, flows, None)
+    maps = _maps(name, maps, offset, len(event_sets))
+    event_sets = [e.detach() for e in event_sets]
+    t0s, scales = _time_refs(name, event_sets, t_ref, dev)
+    return event_sets, flows, t0s, scales, maps, h, w, dev
+
+
+def _variances(event_sets, flows, t0s, scales, maps, h, w, dev):
+    slots = [i for i, f in enumerate(flows) if f is not None]
+    var, moments = _Contrast.apply((event_sets, slots, t0s, scales, maps, h, w, dev), *[flows[i] for i in slots])
+    return var, moments
+
+
+def contrast_many(event_sets, flows, t_ref="end", offset=(0, 0), maps=None):
+    """Variance of the image of warped events of every event set under its (2,H,W) float32 flow (None: zero flow, at least one flow
+    names the frame): a (k,) float64 device tensor, differentiable with respect to every flow that requires grad - the contrast that
+    contrast maximisation raises.  A flow may be a view pred[i] of a (B,2,H,W) prediction: autograd adds the gradients back into the
+    batch tensor.  maps: one (ax, bx, ay, by) per set in place of `offset`.  One library call per 32 jobs forward, one backward."""
+    job = _contrast("contrast_many", event_sets, flows, t_ref, offset, maps)
+    return _variances(*job)[0]
+
+
+def fwl_loss(event_sets, flows, t_ref="end", offset=(0, 0), maps=None):
+    """Minus the mean over the samples of var(IWE under the flow) / var(IWE under zero flow): a 0-dim float64 device tensor to minimise,
+    differentiable with respect to the flows.  As in fwl_many each set rides the launch twice, 16 sets per library call.  A sample whose
+    zero-flow variance is 0 or not finite is left out of the mean and gets a zero gradient; with every sample left out the loss is 0.
+    No host synchronisation beyond the timestamps' copy."""
+    event_sets, flows = list(event_sets), list(flows)
+    if any(f is None for f in flows):
+        raise ValueError("fwl_loss: every event set needs its flow (zero flow is the denominator)")
+    event_sets, flows, t0s, scales, maps, h, w, dev = _contrast("fwl_loss", event_sets, flows, t_ref, offset, maps)
+    half = MAX_JOBS_PER_CALL // 2
+    total = torch.zeros((), device=dev, dtype=torch.float64)
+    count = torch.zeros((), device=dev, dtype=torch.float64)
+    for i0 in range(0, len(event_sets), half):
+        sl = slice(i0, i0 + half)
+        c = len(event_sets[sl])
+        var, _ = _variances(event_sets[sl] * 2, flows[sl] + [None] * c, t0s[sl] * 2, scales[sl] * 2, maps[sl] * 2, h, w, dev)
+        num, den = var[:c], var[c:]
+        ok = torch.isfinite(den) & (den != 0)
+        ratio = torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(num))
+        total = total + ratio.sum()
+        count = count + ok.sum()
+    return -total / count.clamp(min=1.0)

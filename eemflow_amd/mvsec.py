@@ -261,8 +261,10 @@ class MvsecEventFlow(torch.utils.data.Dataset):
         flipped / cropped straight into the batch tensors by one launch (augmentor.augment_many), flow and `valid` with them.  With
         'aug_params' the d_event_volume_* keys are the event_volume_* tensors themselves (the host route passes the same arrays twice);
         with a caller's FlowAugmentor, or none, they are the un-augmented volumes, as the host route leaves them.  plans: the samples'
-        AugPlans (default: drawn here, in sample order); reads: their read_sample results (default: read here).  Training datasets only."""
-        from .augmentor import AUGMENT_MAX, augment_many
+        AugPlans (default: drawn here, in sample order); reads: their read_sample results (default: read here).  With with_events=True the
+        batch also carries 'events_map', one (ax, bx, ay, by) per sample: the sample's plan (AugPlan.event_map) behind events_offset, the
+        pure offset map for a None plan - where the events lie in the augmented frame.  Training datasets only."""
+        from .augmentor import AUGMENT_MAX, augment_many, event_map_after_offset
         self._batch_augmentor()
         idxs = list(idxs)
         if plans is None:
@@ -288,6 +290,7 @@ class MvsecEventFlow(torch.utils.data.Dataset):
         if self.with_events:
             batch['events'] = [seqs[0].features for _, seqs in reads]
             batch['events_offset'] = [self._crop_offset() for _ in reads]
+            batch['events_map'] = [event_map_after_offset(p, self._crop_offset(), self.image_height, self.image_width) for p in plans]
         dense = self.dense_augmentor is not None
         batch['event_volume_new'], batch['event_volume_old'] = new, old
         batch['d_event_volume_new'] = new if dense else torch.stack(raw_new)

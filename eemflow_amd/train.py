@@ -82,6 +82,24 @@ def sequence_loss(flow_preds, flow_gt, valid, gamma=0.8, metrics=True):
     return loss, {"epe": st[1] / cnt, "1px": st[3] / cnt, "3px": st[4] / cnt, "5px": st[5] / cnt}
 
 
+def contrast_loss(flow_pred, events, maps=None):
+    """The contrast (flow-warp-loss) term of a (B,2,H,W) prediction: iwe.fwl_loss of the B samples' event sets (a list of (N,4) float64
+    device tensors) under flow_pred[i] - minus the mean of var(IWE under the flow) / var(IWE under zero flow), a differentiable 0-dim
+    float64 CUDA tensor; its backward is the library's IWE gradient (csrc/iwe_grad.hip) and lands in flow_pred.  maps: one
+    (ax, bx, ay, by) per sample, where its events lie in the prediction's frame (batch['events_map']); None: the identity."""
+    import importlib
+    fwl_loss = importlib.import_module(__package__ + ".iwe").fwl_loss      # (the package's attribute `iwe` is the one-job function)
+    if not torch.is_tensor(flow_pred) or flow_pred.dim() != 4 or flow_pred.shape[1] != 2:
+        raise ValueError("contrast_loss: the prediction is a (B,2,H,W) tensor")
+    if not flow_pred.is_cuda:
+        raise _lib.EEMFlowHipError("contrast_loss: CUDA (ROCm) tensors required - there is no CPU path")
+    events = list(events)
+    if len(events) != flow_pred.shape[0]:
+        raise ValueError(f"contrast_loss: one event set per sample; got {len(events)} sets for a batch of {flow_pred.shape[0]}")
+    pred = flow_pred.float().contiguous()
+    return fwl_loss(events, [pred[i] for i in range(pred.shape[0])], maps=maps)
+
+
 class EEMFlowTrainer:
     """One optimisation step per `step()` call; owns the flat gradient buffer and the schedule."""
 

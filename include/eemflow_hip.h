@@ -288,6 +288,30 @@ int eemflow_warp_events(const double* events, int64_t n, const float* flow, int 
 int eemflow_iwe_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
                      const double* scale, double ox, double oy, int h, int w, float* const* iwe, double* moments, void* stream);
 
+/* eemflow_iwe_many with an affine event map per job in place of the offset: maps (HOST, k x 4 doubles) holds (ax, bx, ay, by), and
+ * xe = ax * x + bx, ye = ay * y + by - what a resize, a flip and a crop of the frame do to event coordinates.  (1, -ox, 1, -oy) is the
+ * offset (ox, oy), bit for bit; eemflow_iwe_many calls this entry with that map.  The same kernels, the same image and moments.
+ * Replaces: warp_events_flow_torch (utils_luo/event_utils.py:9-51) and the image / variance-ratio part of Test.inference_img_warp_loss
+ * (test_mvsec.py:753-852), for events of an augmented sample (the reference augments frames only and has no such map). */
+int eemflow_iwe_map_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                         const double* scale, const double (*maps)[4], int h, int w, float* const* iwe, double* moments, void* stream);
+
+/* Gradient of var(S) of eemflow_iwe_map_many's images with respect to the flows, times a scalar per job: grads[i] ([2][h][w] fp32,
+ * HOST array of device pointers) = coef[i] * d var_i / d flows[i].  events, n, flows, t0, scale and maps are the forward's; a NULL
+ * flows[i] (zero flow) skips job i, whose grads[i] is not touched.  iwe (HOST array of device pointers) and moments (device, k x 4) are
+ * what the forward returned for the same jobs; coef is a DEVICE array of k doubles (the upstream gradient; -1 / var0 for the flow warp
+ * loss), so no host synchronisation is needed.  In unfused fp64, with the stored image's fp32 rounding taken as the identity:
+ * G = 2 (S - mean) / (h w) per cell; per event dX = sum over in-frame targets of G * wy[dy] * (dx ? +1 : -1), dY likewise with
+ * wx[dx] * (dy ? +1 : -1); every in-frame sample neighbour k of (xe, ye) receives coef * w_k * tau * dX in channel 0 and
+ * coef * w_k * tau * dY in channel 1.  Events the forward dropped whole add nothing.  Every cell of a gradient is written, an fp64 sum
+ * rounded to fp32 once; the binned form (default) rounds each contribution to fp32 first, the direct form (EEM_IWE_DIRECT=1, frames too
+ * wide for a band) does not.  The order of the sums is free: the last bits of the fp64 sums may differ from run to run.
+ * Replaces: loss.backward() through warp_events_flow_torch (utils_luo/event_utils.py:9-51) and the variance of the image of warped
+ * events (test_mvsec.py:821-824) - the reference evaluates this measure and never trains on it. */
+int eemflow_iwe_grad_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                          const double* scale, const double (*maps)[4], int h, int w, const float* const* iwe, const double* moments,
+                          const double* coef, float* const* grads, void* stream);
+
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
  * receive, per event, the int64 flat index x + y*w + bin*w*h of the left / right temporal vote, or -1
