@@ -11,6 +11,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 from .augmentor import AugPlan, apply_host, augment_many   # noqa: F401
 from .eemflow import EEMFlow            # noqa: F401
+from .events import pack_events_many, read_event_columns   # noqa: F401
 from .iwe import contrast_many, fwl, fwl_loss, fwl_many, iwe, iwe_many, warp_events   # noqa: F401
 from .metrics import fb_check          # noqa: F401
 from .padder import InputPadder         # noqa: F401

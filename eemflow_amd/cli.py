@@ -10,7 +10,8 @@ repository path), `--save_root`, `--checkpoint`, `--config` (a JSON like the ref
 loader defaults are built in), `test`: `--vis_events --print_epe --visualize_every` (the keywords of the reference's evaluation loop
 that its script leaves at their defaults; `-v` writes the flow images under the run's save folder), `--fwl` (the flow warp loss of
 Test.inference_img_warp_loss, test_mvsec.py:753-852, as a field of every evaluation line), `train`: `--device_batches` (beside `--num_workers`: every batch voxelized, flipped and assembled
-on the GPU by the threaded loader, the event volumes never copied through host memory; the same batches under the same numpy seed).
+on the GPU by the threaded loader, the event volumes never copied through host memory; the same batches under the same numpy seed), `train` and `test`: `--device_events` (HREM event sets prepared on the GPU from the npz columns,
+eemflow_amd.events; the same samples bit for bit).
 Dropped: the key-map, warped-image
 and HSV visualisations, xlsx export, git metadata, nn.DataParallel (one process per GPU:
 launch with torchrun for data parallelism; see eemflow_amd.parallel).  Only the models built here are accepted: EEMFlow (trained by
@@ -65,6 +66,10 @@ def build_parser():
                                 'un-augmented dataset)')
             q.add_argument('--self_supervised', action='store_true',
                            help='with --contrast_weight: train on the contrast term alone, the ground-truth flow is not read')
+        q.add_argument('--device_events', action='store_true',
+                       help='prepare the event sets on the GPU from the npz columns (HREM datasets: the columns are uploaded in their file '
+                            'dtypes and one launch per sample writes the float64 event tables; the same samples bit for bit, a set whose '
+                            'timestamps are not in order keeps the host route)')
         q.add_argument('--train_iters', default=6000000 if train else 1000000, type=int, metavar='N', help='number of total iterations')
         q.add_argument('-se', '--start-epoch', action='store_true', help='restart from lasted_ckpt.pth.tar of the run folder')
         q.add_argument('-be', '--best_epe', default=1e5, type=float)
@@ -139,6 +144,16 @@ def per_rank_batch(batch_size, world):
     return batch_size // world
 
 
+def device_events_kw(args, dataset_class):
+    """The dataset keyword of --device_events; only datasets that read HREM's npz columns take it (hrem.HREMEventFlow)."""
+    if not getattr(args, "device_events", False):
+        return {}
+    if not getattr(dataset_class, "supports_device_events", False):
+        raise SystemExit(f"--device_events prepares HREM event files (events1.npz / events2.npz columns) on the GPU: "
+                         f"{dataset_class.__name__} has no such route")
+    return {"device_events": True}
+
+
 def train(args):
     from . import harness, parallel
     from .hrem import HREMEventFlow
@@ -172,7 +187,7 @@ def train(args):
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
     train_set = HREMEventFlow(args=config["data_loader"]["train"]["args"], train=True, root=args.data_root, device=dev,
-                              with_events=contrast != 0.0)
+                              with_events=contrast != 0.0, **device_events_kw(args, HREMEventFlow))
     if contrast != 0.0 and train_set.augmentor is not None and not args.device_batches:
         # the host route flips the volumes without telling where the events went; get_batch hands out batch['events_map']
         raise SystemExit("--contrast_weight with an augmented dataset needs --device_batches: only batches assembled on the device carry "
@@ -240,7 +255,7 @@ def test(args):
     dev = torch.device(args.device)
     coalesce = args.coalesce if args.model_name == 'EEMFlow' else 1      # (forward_many is EEMFlow's)
     test_set = HREMEventFlow(args=config["data_loader"]["test"]["args"], train=False, root=args.data_root, device=dev,
-                             deferred_norm=coalesce > 1, with_events=args.fwl)
+                             deferred_norm=coalesce > 1, with_events=args.fwl, **device_events_kw(args, HREMEventFlow))
     model = model.to(dev)
     sequences = [args.test_sequence] if args.test_sequence else list(test_set.nori_list.keys())
     ev = harness.TestRaftEvents(test_set, tuple(config["val_img_size"]), logger=logger)

@@ -137,9 +137,15 @@ class HREMEventFlow(torch.utils.data.Dataset):
 
     image_width = 1280
     image_height = 720
+    supports_device_events = True
 
-    def __init__(self, args, train=True, root=None, device=None, to_cpu=False, augmentor=None, deferred_norm=False, with_events=False):
-        """with_events: every sample also carries 'events', the OLD event set's (N,4) float64 device tensor [t, x, y, p] - uploaded once,
+    def __init__(self, args, train=True, root=None, device=None, to_cpu=False, augmentor=None, deferred_norm=False, with_events=False,
+                 device_events=False):
+        """device_events: the event sets are prepared on the GPU from the npz columns (eemflow_amd.events: the columns go up in their
+        file dtypes, one launch per sample writes both (N,4) float64 tables) instead of in NumPy on the host; the same tensors, volumes
+        and `events` bit for bit.  A set whose raw timestamps are not in order keeps the host route; `event_routes` counts the sets
+        by route, {'device': n, 'host': m}.
+        with_events: every sample also carries 'events', the OLD event set's (N,4) float64 device tensor [t, x, y, p] - uploaded once,
         the voxelizer reads the same tensor - and 'events_offset' = (0, 0) (HREM frames are not cropped): what eemflow_amd.iwe.fwl_many
         takes beside the predicted flow.
         deferred_norm (evaluation, GPU-resident samples): the event volumes stay RAW with their normalisation record behind them
@@ -150,6 +156,8 @@ class HREMEventFlow(torch.utils.data.Dataset):
             raise ValueError("deferred_norm is the evaluation route with samples resident on the GPU (train=False, to_cpu=False)")
         self.deferred_norm = bool(deferred_norm)
         self.with_events = bool(with_events)
+        self.device_events = bool(device_events)
+        self.event_routes = {'device': 0, 'host': 0}
         self.input_type = 'events'
         self.type = 'train' if train else 'val'
         self.evaluation_type = args['eval_type']
@@ -201,6 +209,14 @@ class HREMEventFlow(torch.utils.data.Dataset):
                'fflow': torch.from_numpy(np.ascontiguousarray(fflow.transpose(2, 0, 1))),
                'valid': None}
         params = {'height': self.image_height, 'width': self.image_width}
+        if self.device_events:
+            from . import events as E
+            packed = E.pack_events_many([E.read_event_columns(sample[key]) for key in ('event0', 'event1')], 1e-9, 1e6, True,
+                                        device=self.device, counts=self.event_routes)
+            seqs = [E.device_sequence(t, params) for t in packed]     # handed to the voxelizer as device-resident features
+            if self.with_events:
+                out['events'], out['events_offset'] = packed[0], (0, 0)
+            return out, seqs
         seqs = [EventSequence(None, params, features=get_compressed_events(sample[key]), timestamp_multiplier=1e6,
                               convert_to_relative=True) for key in ('event0', 'event1')]
         if self.with_events:

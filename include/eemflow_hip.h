@@ -337,6 +337,31 @@ int eemflow_voxelize_pair(const double* events1, int64_t n1, const double* event
 int eemflow_voxelize_many(int nsets, const double* const* events, const int64_t* n_events, int bins, int h, int w, int normalize,
                           float* const* grids, void* stream);
 
+/* Event preparation: nsets (1..EEMFLOW_PACK_MAX) event sets, each given as its four COLUMNS on the device - t[k], x[k], y[k], p[k], n_events[k]
+ * elements each, of the dtype codes[4*k + 0..3] (EEMFLOW_PACK_*; a bool column is uploaded as u8) - packed by ONE launch into
+ * out[k] [n_events[k]][4] f64 (t, x, y, p): the table eemflow_voxelize, the IWE entry points and a loader's `events` take.  Every value
+ * is converted as NumPy's astype(float64) converts it (exact but for int64: round to nearest even); tt = ((double)t * scale_a) * scale_b
+ * as two separately rounded products; out[i][0] = tt[i] - tt[0] with relative != 0, else tt[i]; out[i][1..3] = x, y, p.  p arrives
+ * already as 2*p - 1, formed by the host in the column's own dtype.  The sets must be in time order already (the caller checks the raw
+ * t column; eemflow_amd/events.py keeps the host route for the others).  t, x, y, p, codes, n_events and out are HOST arrays, read
+ * before the call returns; column pointers are aligned to their elements, out[k] to 16 bytes.  A set with n_events[k] == 0 writes
+ * nothing; nsets outside 1..EEMFLOW_PACK_MAX or an unknown code is an error return before any launch.  Stream-ordered, no host
+ * synchronisation, no allocation: the job table travels as kernel arguments.
+ * Replaces: get_compressed_events (loader/loader_utils.py:26-37) and EventSequence.__init__ (loader/loader_utils.py:352-397) - the
+ * float64 table, the two timestamp scalings and absolute_time_to_relative, which the reference does in NumPy on the host. */
+#define EEMFLOW_PACK_MAX 32
+#define EEMFLOW_PACK_U8 0
+#define EEMFLOW_PACK_I8 1
+#define EEMFLOW_PACK_U16 2
+#define EEMFLOW_PACK_I16 3
+#define EEMFLOW_PACK_I32 4
+#define EEMFLOW_PACK_I64 5
+#define EEMFLOW_PACK_F32 6
+#define EEMFLOW_PACK_F64 7
+int eemflow_pack_events_many(int nsets, const void* const* t, const void* const* x, const void* const* y, const void* const* p,
+                             const int* codes, const int64_t* n_events, double scale_a, double scale_b, int relative,
+                             double* const* out, void* stream);
+
 /* Augmentation of n (1..EEMFLOW_AUGMENT_MAX) training samples of one source size and one output size by ONE launch, written into the
  * batch tensors: vol_old[i], vol_new[i] ([C][H][W] fp32), flow[i] ([2][H][W]; fp64 with flow_f64 != 0, else fp32; a NULL entry, or
  * flow == NULL, is a sample without flow: HREM's mesh flow is returned un-augmented by the reference) and plans[i] are HOST arrays, read
