@@ -230,10 +230,10 @@ extern "C" int eemflow_load_weights(eemflow_ctx* c, const float* flat, size_t nf
     int rc = repack_launch(c->flat, c->pack_idx, c->arena, (long)c->arena_floats, nullptr);
     if (rc != EEM_OK) return rc;
     {   // Winograd-domain weights for the stride-1 C->C layers
-        const char* e = getenv("EEM_WINO");
-        c->use_wino = !(e && atoi(e) == 0);
-        const char* e4 = getenv("EEM_WINO4_LAYERS");
-        c->f4_mask_env = (e && atoi(e) == 2) ? 0 : (e4 ? atoi(e4) & 7 : -1);
+        const int wino = sw_int<SW_EEM_WINO>();
+        c->use_wino = wino != 0;
+        const char* e4 = sw_raw<SW_EEM_WINO4_LAYERS>();
+        c->f4_mask_env = wino == 2 ? 0 : (e4 ? atoi(e4) & 7 : -1);
         size_t off = 0;
         for (int l = 0; l < ENC_NUM; ++l) {
             const EncLayerDesc& d = kEncLayers[l];

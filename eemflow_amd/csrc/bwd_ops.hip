@@ -22,7 +22,7 @@ struct LookupBwdArgs {
     int batch, h, w;
 };
 
-// adjoint of lookup_kernel: the 4 bilinear taps of (level, window position) scatter dout * weight
+// adjoint of lookup_tiled_kernel: the 4 bilinear taps of (level, window position) scatter dout * weight
 __global__ __launch_bounds__(256) void lookup_bwd_kernel(LookupBwdArgs a) {
     const int hw = a.h * a.w;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void lookup_bwd_kernel(LookupBwdArgs a) {
 // offset, 9 x 9 integer offsets) touch a 10 x 10 window of that map: a thread owns one row of the window and adds, cell by cell, the
 // <= 4 taps whose bilinear corners fall on the cell - plain read-modify-writes (no two threads share a cell), 10 consecutive floats
 // per thread, and dout read as full-width runs over p (the scatter form issues 4 atomics per (tap, pixel), each on another map:
-// 25 M atomics on distinct lines per call at batch 4, 0.95 ms).  A tap's corner and weight are evaluated with lookup_kernel's own
+// 25 M atomics on distinct lines per call at batch 4, 0.95 ms).  A tap's corner and weight are evaluated with lookup_tiled_kernel's own
 // arithmetic; only a corner that rounding moved by one cell beside an (almost) integer coordinate is not found - its weight is ~1e-7.
 __global__ __launch_bounds__(256) void lookup_bwd_rows_kernel(LookupBwdArgs a) {
     const int hw = a.h * a.w;
@@ -349,8 +349,7 @@ extern "C" int eraft_corr_lookup_bwd(const float* coords, const float* dout, int
         ph /= 2; pw /= 2;
     }
     a.coords = coords; a.dout = dout; a.batch = batch; a.h = h; a.w = w;
-    const char* sc = getenv("EEM_LOOKUP_BWD_SCATTER");            // read per call: the tests run both forms
-    if (sc && sc[0] == '1') hipLaunchKernelGGL(lookup_bwd_kernel, dim3(nblocks((long)batch * 324 * h * w)), dim3(256), 0, st, a);
+    if (sw_on<SW_EEM_LOOKUP_BWD_SCATTER>()) hipLaunchKernelGGL(lookup_bwd_kernel, dim3(nblocks((long)batch * 324 * h * w)), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(lookup_bwd_rows_kernel, dim3(nblocks((long)batch * 40 * h * w)), dim3(256), 0, st, a);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

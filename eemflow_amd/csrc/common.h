@@ -8,6 +8,7 @@
 
 #include <type_traits>
 
+#include "switch.h"
 #include "../../include/eemflow_hip.h"   // every definition of an entry point sees its declaration (default visibility; the build hides the rest)
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -103,13 +104,15 @@ __device__ static __forceinline__ float lane_group_sum(float v) {
 // Persistent encoder kernels launch one block per CU (32 per XCD) by default; EEM_ENC_PER_XCD_<tag> (or EEM_ENC_PER_XCD) lowers the cap:
 // fewer, longer blocks amortise the per-block prologue when several frames share the chip.
 static inline int enc_blocks_per_xcd(const char* tag, int dflt) {
-    char name[48];
-    snprintf(name, sizeof name, "EEM_ENC_PER_XCD_%s", tag);
-    const char* e = getenv(name);
-    if (!e) e = getenv("EEM_ENC_PER_XCD");
+    char suffix[32];
+    snprintf(suffix, sizeof suffix, "_%s", tag);
+    const char* e = sw_family<SW_EEM_ENC_PER_XCD>(suffix);
+    if (!e) e = sw_family<SW_EEM_ENC_PER_XCD>("");
     const int v = e ? atoi(e) : 0;
     return v > 0 ? v : dflt;
 }
+// EEM_BX3_S1 = mask of the stride-1 channel widths on conv_bx3.hip: 1 = 32, 2 = 64 (off by default: see the note at bx3_s1_kernel)
+static inline bool bx3_s1_wanted(int cin) { return (sw_int<SW_EEM_BX3_S1>() & (cin == 32 ? 1 : 2)) != 0; }
 struct TileCoord { int bx, by, n; };
 struct TileRange { int first, count; };
 __device__ static inline TileRange block_tile_range(int T, unsigned bid, unsigned nblocks) {
@@ -191,7 +194,7 @@ struct EncConvArgs {
     // walk the tiles from the LAST image to the first (conv_wino4.hip): in a batched chain a layer's input was written by the launch
     // before it, front to back, and is larger than the 256 MB Infinity Cache - read back to front, the part written last is still there
     int reverse = 0;
-    // feature-map stores as non-temporal stores (conv_wino4.hip; EEM_NT_STORE=<layer mask>, experiment): a batched chain's outputs stream
+    // feature-map stores as non-temporal stores (conv_wino4.hip; an experiment the schedule leaves off): a batched chain's outputs stream
     // through each XCD's 4 MB L2 beside the Winograd weights and halo rows the kernel re-reads
     int nt_store = 0;
     // persistent kernels: blocks per XCD (0 = one per CU).  The context lowers it when the application keeps several frames in flight
@@ -282,7 +285,7 @@ struct Enc12Args {
     int h1, w1;                  // a1 / f11 extent
     int tiles_x, tiles_y;        // filled by the launcher
     int dbg;                     // diagnostic builds (-DEEM_DIAG): phases switched off (EEM_E12_DBG)
-    int row_order;               // tiles in row order (x fastest) instead of the column walk (EEM_E12_ROW_ORDER=1: measurement)
+    int row_order;               // tiles in row order (x fastest) instead of the column walk (measurement; the launcher leaves it 0)
 };
 bool enc12_supported(const Enc12Args& a);
 int enc12_blocks(int nimg, int h1, int w1, int blocks_per_xcd);
@@ -320,10 +323,6 @@ int tail_conv_launch(const TailConvLaunch& l, hipStream_t stream);
 // avg-pool k x k (stride k, floor) of [n][c][h][w] -> [n][c][h/k][w/k]
 struct PoolJob { const float* in; float* out; int c, h, w, k; };
 int pool_launch(const PoolJob* jobs, int njobs, int nimg, hipStream_t stream);
-// sums the per-block partial sums written by the fused conv epilogue: out[n][c][gy][gx] =
-// (1/k^2) * sum_{i < rows} partial[n][c][gy*rows + i][gx], partial is [n][c][prows][pcols]
-struct PoolFinJob { const float* partial; float* out; int c, prows, pcols, rows, k; };
-int pool_finalize_launch(const PoolFinJob* jobs, int njobs, int nimg, int gh, int gw, hipStream_t stream);
 
 // 9x9 local correlation, selected taps, scaled by 1/C; writes channels [0,ntaps) of out
 struct CorrJob { const float* f1; const float* f2; float* out; int c, out_ctotal; };

@@ -15,7 +15,7 @@
 // ([k-step][piece][cout tile][lane][4 dwords], bx3_transform_launch) through a ring of three k-steps of global loads (L1 / L2 hits:
 // every block reads the same 27 / 108 KB).  Software pipeline: k-step s + 1's raw values are in registers when k-step s's MFMAs
 // issue, and their split sits between those MFMAs (pinned by sched_barrier; the scheduler's own order put the whole split in front).
-// pconv2_1 (16 -> 32): 40 KB of LDS, four blocks per CU, 17.0 -> 13.3 us; pconv3_1 (32 -> 64, EEM_NO_BX3_64=1 for conv_enc2.hip's
+// pconv2_1 (16 -> 32): 40 KB of LDS, four blocks per CU, 17.0 -> 13.3 us; pconv3_1 (32 -> 64, before: conv_enc2.hip's
 // kernel): 80 KB, two per CU, 14.5 -> 11.1 us.  What is left is not arithmetic: the tile's way in from HBM and the stores.
 // Measured and not kept: pconv2_1 as persistent blocks (weights stationary in 108 registers, two LDS stages, tile t + 1 streaming in under
 // tile t's MFMAs and tile t - 1's stores, counted waits; two blocks per CU): 14.1 us at two tiles per block, 17.2 at three on 150 CUs,
@@ -443,17 +443,8 @@ int bx3_transform_launch(const float* w, int cin, int cout, float* packed, hipSt
 }
 
 bool bx3_supported(int cin, int cout, int stride, const EncConvArgs& a) {
-    const char* off = getenv("EEM_NO_BX3");              // read per launch: the tests compare both kernels in one process
-    if (off && off[0] == '1') return false;
-    if (stride == 2 && cin == 32) {                       // pconv3_1: EEM_NO_BX3_64=1 keeps conv_enc2.hip's chunked kernel
-        const char* m = getenv("EEM_NO_BX3_64");
-        if (m && m[0] == '1') return false;
-    }
-    if (stride == 1) {                                    // EEM_BX3_S1 = mask of channel widths: 1 = 32, 2 = 64
-        const char* m = getenv("EEM_BX3_S1");
-        const int mask = m ? atoi(m) : 0;                 // off by default: see the note at bx3_s1_kernel
-        if (!(mask & (cin == 32 ? 1 : 2))) return false;
-    }
+    if (sw_on<SW_EEM_NO_BX3>()) return false;
+    if (stride == 1 && !bx3_s1_wanted(cin)) return false;
     return bx3_shape(cin, cout, stride) && a.wbx3 && a.gate == nullptr && a.pool_partial == nullptr && a.res == nullptr && (a.win & 3) == 0 &&
            (a.act == 0 || a.act == 1) && (((uintptr_t)a.in0) & 15) == 0 && (size_t)cin * a.hin * a.win * 4 < (1u << 31);
 }

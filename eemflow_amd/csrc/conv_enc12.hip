@@ -470,11 +470,11 @@ int enc12_launch(const Enc12Args& a0, int blocks, hipStream_t stream) {
                 "enc12_launch: NULL operand");
     Enc12Args a = a0;
 #ifdef EEM_DIAG
-    { const char* e = getenv("EEM_E12_DBG"); a.dbg = e ? atoi(e) : 0; }      // 1: no phase A, 2: no phase B, 4: A's stores to the trash page, 8: A without MFMAs
+    a.dbg = sw_int<SW_EEM_E12_DBG>();     // 1: no phase A, 2: no phase B, 4: A's stores to the trash page, 8: A without MFMAs
 #endif
     a.tiles_x = ceil_div(a.w1, TW);
     a.tiles_y = ceil_div(a.h1, TH);
-    { static const bool ro = [] { const char* e = getenv("EEM_E12_ROW_ORDER"); return e && e[0] == '1'; }(); a.row_order = ro ? 1 : 0; }
+    a.row_order = 0;
     EEM_NOTE_GRID(blocks, 512);
     hipLaunchKernelGGL(enc12_kernel, dim3(blocks), dim3(512), 0, stream, a);
     EEM_HIP_CHECK(hipGetLastError());

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(WAVES * 64) void enc_conv2_kernel(EncConvArgs a) {
     // ---- epilogue: LeakyReLU, [pooling], NCHW store; with POOLK also the stage pooling (EEMFlow.py:144-154) as
     // per-block partial sums: lanes reduce their pixels inside a window by shuffles, rows / tiles of the
     // block are summed through LDS in a fixed order (bitwise repeatable, no atomics), and one value per
-    // (channel, window) and block row-group goes to a small buffer that pool_finalize sums.
+    // (channel, window) and block row-group goes to a small buffer that the tail head sums.
     constexpr int SW = (POOLK > 0 && POOLK < C::NPIX) ? POOLK : C::NPIX;   // pixels per reduction slot
     constexpr int SLOTS = C::TW / SW;                                       // slots per block row
     float* red = lds;                                                       // [TH][COUT][SLOTS]
@@ -577,9 +577,9 @@ static const Variant* pick_variant(int cin, int cout) {
     else if (cin == 32 && cout == 64) { tab = kV32_64; n = sizeof(kV32_64) / sizeof(Variant); }
     else if (cin == 64 && cout == 64) { tab = kV64_64; n = sizeof(kV64_64) / sizeof(Variant); }
     if (!tab) return nullptr;
-    char name[32];
-    snprintf(name, sizeof(name), "EEM_V%d_%d", cin, cout);
-    const char* e = getenv(name);
+    char layer[32];
+    snprintf(layer, sizeof(layer), "%d_%d", cin, cout);
+    const char* e = sw_family<SW_EEM_V>(layer);
     int idx = e ? atoi(e) : 0;
     if (idx >= 100) {                            // 100 + i selects persistent variant i
         const Variant* pt = nullptr;

@@ -150,10 +150,8 @@ int s2_launch_t(const EncConvArgs& a0, hipStream_t stream) {
 
 // wpk2 must be conv_enc2.hip's packing with 8-channel chunks (its production variants of these two layers)
 bool s2_supported(int cin, int cout, int stride, const EncConvArgs& a) {
-    const char* off = getenv("EEM_NO_S2W");              // read per launch: the tests compare both kernels in one process
-    if (off && off[0] == '1') return false;
-    const char* e64 = getenv("EEM_S2W_64");
-    const bool also64 = e64 && e64[0] == '1';
+    if (sw_on<SW_EEM_NO_S2W>()) return false;
+    const bool also64 = sw_on<SW_EEM_S2W_64>();
     return stride == 2 && ((cin == 16 && cout == 32) || (also64 && cin == 32 && cout == 64)) && a.wpk2 && a.gate == nullptr &&
            a.pool_partial == nullptr && (a.win & 3) == 0 && (((uintptr_t)a.in0) & 15) == 0 && (size_t)cin * a.hin * a.win * 4 < (1u << 31);
 }

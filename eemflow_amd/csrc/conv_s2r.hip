@@ -11,7 +11,7 @@
 //   * bias rides in the accumulators (C operand of the first MFMA), LeakyReLU and the NCHW stores (64-byte runs per cout) follow.
 // MEASURED (round 3, 1280x720): 18.9 us for pconv2_1 and 15.7 us for pconv3_1 on full grids, against 17.3 / 14.6 us for the light-block
 // kernels of conv_s2.hip / conv_enc2.hip, and 7 720 against 7 900 frames/s with four frames in flight - so this kernel is OFF by
-// default (EEM_S2R=1, read per launch, turns it on; tests run both).  Software-pipelined B reads and two interleaved accumulator
+// default (EEM_S2R=1 turns it on; tests run both).  Software-pipelined B reads and two interleaved accumulator
 // streams changed nothing: with 4 / 8 k-steps per tile and one tile per block the launch is its prologue (DMA plan, first slice from
 // HBM) plus one slice latency per k-step, not the matrix pipe; the layers are also within 2x of their HBM floor (47 / 24 MB).
 #include <type_traits>
@@ -290,8 +290,7 @@ size_t s2r_packed_floats(int cin, int cout) { return (size_t)(cin / 4) * (cout /
 bool s2r_shape(int cin, int cout, int stride) { return stride == 2 && ((cin == 16 && cout == 32) || (cin == 32 && cout == 64)); }
 
 bool s2r_supported(int cin, int cout, int stride, const EncConvArgs& a) {
-    const char* on = getenv("EEM_S2R");                         // read per launch: the tests compare both kernels in one process
-    if (!(on && on[0] == '1')) return false;
+    if (!sw_on<SW_EEM_S2R>()) return false;
     return s2r_shape(cin, cout, stride) && a.ws2r != nullptr && a.gate == nullptr && a.pool_partial == nullptr && (a.win & 3) == 0 &&
            (((uintptr_t)a.in0) & 15) == 0 && (size_t)cin * a.hin * a.win * 4 < (1u << 31);
 }

@@ -151,8 +151,7 @@ void stem7_pack(const float* w, int cin, float* packed) {
 }
 
 bool stem7_supported(const GConvArgs& a) {
-    const char* e = getenv("EEM_NO_STEM7");                       // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_STEM7>()) return false;
     return a.wstem && a.nseg == 1 && a.seg[0].c >= 1 && a.seg[0].c <= ST_MAXC && a.cout == 64 && a.kh == 7 && a.kw == 7 && a.stride == 2 &&
            a.tstride <= 1 && a.pad_h == 3 && a.pad_w == 3 && a.groups <= 1 && a.epi == GEPI_PLAIN && a.pre == nullptr &&
            a.seg[0].gate == nullptr && a.seg[0].cmul <= 1 && a.out_cmul <= 1 && a.win % 4 == 0 && ((uintptr_t)a.seg[0].ptr & 15) == 0 &&

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
     auto dma_issue = [&]() {
         float* sbase = lds + dma_slot * K::STAGE;
 #ifdef EEM_DIAG
-        const char* usrc = wbase + (size_t)(a.nt_store & 2 ? 0 : dma_s) * (K::UP * 16);    // EEM_NT_STORE bit 1 (diag): every k-step reads slice 0's weights
+        const char* usrc = wbase + (size_t)(a.nt_store & 2 ? 0 : dma_s) * (K::UP * 16);    // nt_store bit 1 (diag; the schedule leaves it 0): every k-step reads slice 0's weights
 #else
         const char* usrc = wbase + (size_t)dma_s * (K::UP * 16);
 #endif

@@ -540,8 +540,7 @@ int wnc_pack_device_launch(const WncPackArgs& a, hipStream_t st) {
 }
 
 bool wnc_supported(const WncArgs& a) {
-    const char* e = getenv("EEM_NO_WNC");                   // read per call: a test runs both forms in one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_WNC>()) return false;
     if (a.njobs < 1 || a.njobs > WNC_MAX_JOBS || a.nchunks < 1 || a.nchunks > WNC_MAX_CHUNKS || a.n < 1) return false;
     if (a.cin < 32 || (a.cin + 31) / 32 != a.nchunks) return false;
     if (a.w % 4 || a.h < 1 || !a.zero_page || !a.trash || ((uintptr_t)a.zero_page & 15) || ((uintptr_t)a.trash & 7)) return false;
@@ -555,10 +554,7 @@ bool wnc_supported(const WncArgs& a) {
 }
 
 int wnc_launch(const WncArgs& a, hipStream_t st) {
-    // EEM_WNC_SMALL_MAXPX (read per call; 30000): maps below it take the 4 x 32 block tile, two blocks per CU
-    const char* m = getenv("EEM_WNC_SMALL_MAXPX");
-    const bool small = (long)a.h * a.w < (m ? atol(m) : 30000L);
-    if (small) {
+    if (wnc_small_map(a.h, a.w)) {
         using C = WncCfg<1, 2>;
         const int T = ceil_div(a.w, C::TW) * ceil_div(a.h, C::TH) * a.njobs * a.n;
         int per_xcd = ceil_div(T, 8);

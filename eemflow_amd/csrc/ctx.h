@@ -254,7 +254,7 @@ struct Hook {
     int run(const char* name, double flops, double bytes, F&& launch) {
 #ifdef EEM_DIAG
         if (skipped(name)) {                                  // EEM_SKIP_SPIN_US=<us>: one lane holds the launch's place in the stream for <us>
-            static const float spin = [] { const char* e = getenv("EEM_SKIP_SPIN_US"); return e ? (float)atof(e) : 0.f; }();
+            static const float spin = sw_float<SW_EEM_SKIP_SPIN_US>();
             return spin > 0.f ? spin_launch(spin, st) : EEM_OK;
         }
 #endif
@@ -325,7 +325,7 @@ int compute_shape(eemflow_ctx* c, int batch, int in_h, int in_w, int out_h, int 
 int alloc_workspace(eemflow_ctx* c, const Shape& s);
 
 // ------------------------------------------------------------------------------- schedule.hip
-// dispatch policy (its section there lists every environment switch the schedule reads)
+// dispatch policy (switches.def.h lists every environment switch the schedule reads)
 bool s2r_wanted();
 bool bx3_wanted(int l);
 bool dec_wnc_wanted(const eemflow_ctx* c, int gw, int batch);

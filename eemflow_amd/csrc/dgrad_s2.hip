@@ -397,8 +397,7 @@ int launch_wide(const DgradS2Args& a, hipStream_t st) {
 }  // namespace
 
 bool dgrad_s2_supported(const DgradS2Args& a) {
-    const char* e = getenv("EEM_NO_DGRAD_S2");                      // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_DGRAD_S2>()) return false;
     const bool shape = (a.cout == 32 && a.cin == 16) || (a.cout == 64 && a.cin == 32);
     return shape && a.zero_page && a.wout % 4 == 0 && a.win % 2 == 0 && a.hout == (a.hin + 1) / 2 && a.wout == (a.win + 1) / 2 &&
            ((uintptr_t)a.dy & 15) == 0 && ((uintptr_t)a.dx & 7) == 0 && (a.gate == nullptr || ((uintptr_t)a.gate & 7) == 0) &&
@@ -412,8 +411,7 @@ int dgrad_s2_launch(const DgradS2Args& a, hipStream_t st) {
 
 // wide layers: cout 96 or 128, any cin; k = 3 (pad 1) or k = 1 (pad 0): DgradS2Args::pool_k carries the kernel size here (no pooling branch)
 bool dgrad_s2w_supported(const DgradS2Args& a, int ksize) {
-    const char* e = getenv("EEM_NO_DGRAD_S2W");                     // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_DGRAD_S2W>()) return false;
     return (a.cout == 96 || a.cout == 128) && (ksize == 3 || ksize == 1) && a.zero_page && a.trash && a.gate == nullptr && a.dpool == nullptr &&
            a.wout % 4 == 0 && a.win % 2 == 0 && a.hout == (a.hin + 1) / 2 && a.wout == (a.win + 1) / 2 && ((uintptr_t)a.dy & 15) == 0 &&
            ((uintptr_t)a.dx & 7) == 0 && (size_t)a.cout * a.hout * a.wout * 4 < (1u << 31);

@@ -273,8 +273,7 @@ void set_seg(GConvArgs& a, int i, const float* ptr, int cch, int ctotal, int cof
 // act: 0 none (an InstanceNorm follows), 2 ReLU (eval BatchNorm folded into weights and shift).  From 128 tiles of 32x16 pixels on
 // (fewer leave most CUs without a block and the LDS-tiled kernel wins); EEM_ERAFT_NO_F4=1 keeps every conv on gconv.
 bool f4_eligible(const Layer& L, int n, int h, int w) {
-    const char* e = getenv("EEM_ERAFT_NO_F4");
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_ERAFT_NO_F4>()) return false;
     return L.has_f4 && w % 4 == 0 && (long)n * ((h + 15) / 16) * ((w + 31) / 32) >= 128;
 }
 int run_f4(eraft_ctx* c, const Layer& L, const float* x, int n, int h, int w, float* out, int act, const float* res, hipStream_t st) {
@@ -285,18 +284,14 @@ int run_f4(eraft_ctx* c, const Layer& L, const float* x, int n, int h, int w, fl
     a.bias = c->arena + L.shift; a.out = out;
     a.nimg = n; a.nimg0 = n; a.hin = h; a.win = w; a.hout = h; a.wout = w; a.hraw = h; a.wraw = w;
     a.act = act; a.res = res;
-    {   // the interleaved tile walk (conv_wino4.hip, round 6): neighbouring tiles in flight together; EEM_WALK3_ERAFT=0 keeps contiguous ranges
-        static const bool w3 = [] { const char* e = getenv("EEM_WALK3_ERAFT"); return !(e && e[0] == '0'); }();
-        if (w3) a.reverse = 3;
-    }
+    a.reverse = 3;                                        // the interleaved tile walk (conv_wino4.hip, round 6): neighbouring tiles in flight together
     return wino4_launch(64, a, st);
 }
 
 // A 96 -> 96 / 128 -> 128 3x3 conv of the encoder on the Winograd F(2x2,3x3) kernel (same contract as run_f4).  From 128 (tile, slice)
-// pairs on; EEM_ERAFT_NO_WNC=1 (read per call) keeps every conv on gconv.
+// pairs on; EEM_ERAFT_NO_WNC=1 keeps every conv on gconv.
 bool wnc_eligible(const Layer& L, int n, int h, int w) {
-    const char* e = getenv("EEM_ERAFT_NO_WNC");
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_ERAFT_NO_WNC>()) return false;
     return L.has_wnc && w % 4 == 0 && (long)n * ((h + 3) / 4) * ((w + 31) / 32) * (L.cout / 32) >= 128;
 }
 int run_wnc(eraft_ctx* c, const Layer& L, const float* x, int n, int h, int w, float* out, int act, const float* res, hipStream_t st,
@@ -319,13 +314,12 @@ int run_wnc(eraft_ctx* c, const Layer& L, const float* x, int n, int h, int w, f
     return wnc_launch(a, st);
 }
 
-// the motion encoder's three 3x3 convs (model/update.py:66-81) on the same kernel: EEM_ERAFT_WNC_UPD=<mask> (read per call; bit 0 convc2
+// the motion encoder's three 3x3 convs (model/update.py:66-81) on the same kernel: EEM_ERAFT_WNC_UPD=<mask> (bit 0 convc2
 // 256 -> 192, bit 1 convf2 128 -> 64, bit 2 conv 256 -> 126).  Measured at 640x480 x 12, batch 4, one box: none 289.5 frames/s, convf2 298.7
 // (it ran the LDS-tiled kernel's two-K-group form - 240 blocks - at 25 TFLOP/s beside convc2: 115 us), convc2 287, conv 296, all three 297;
 // batch 1 within 0.5 %: the default is convf2 alone
 bool wnc_upd(const Layer& L, int bit, int n, int h, int w) {
-    const char* e = getenv("EEM_ERAFT_WNC_UPD");
-    const int mask = e ? atoi(e) : 2;
+    const int mask = sw_int<SW_EEM_ERAFT_WNC_UPD>();
     return ((mask >> bit) & 1) && wnc_eligible(L, n, h, w);
 }
 
@@ -659,10 +653,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             return gconv_launch(a, st);
         }
     }
-    // Independent branches on the context's side stream (EEM_ERAFT_NO_OVERLAP=1, read per forward: everything on the caller's stream).
+    // Independent branches on the context's side stream (EEM_ERAFT_NO_OVERLAP=1: everything on the caller's stream).
     // One forward at a time most launches of this model are 40 - 300 blocks for 256 CUs: the branches fill CUs the main chain leaves idle.
-    const char* eno = getenv("EEM_ERAFT_NO_OVERLAP");
-    const bool overlap = !(eno && eno[0] == '1');
+    const bool overlap = !sw_on<SW_EEM_ERAFT_NO_OVERLAP>();
     if (overlap) {
         if (!c->side) {
             EEM_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
@@ -676,10 +669,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     // (model/eraft.py:141-157: the recurrence is net -> flow head -> coords1 -> lookup): it runs on the side stream beside the NEXT
     // iteration, which starts as soon as the flow head has updated coords1.  One forward at a time the update block's launches leave
     // most CUs idle (60x80 cells at batch 1 are 75 - 300 blocks): E-RAFT 640x480 x 12 batch 1 / 4: tools/bench_eraft.py, DESIGN.md 4b.
-    // EEM_ERAFT_NO_LAG=1 (read per forward): the mask head inside the iteration, as before.
-    const char* enl = getenv("EEM_ERAFT_NO_LAG");
-    const char* enf0 = getenv("EEM_ERAFT_NO_FUSE");
-    const bool lagged = overlap && !(enl && enl[0] == '1') && !(enf0 && enf0[0] == '1');
+    // EEM_ERAFT_NO_LAG=1: the mask head inside the iteration, as before.
+    const bool fuse_small = !sw_on<SW_EEM_ERAFT_NO_FUSE>();
+    const bool lagged = overlap && !sw_on<SW_EEM_ERAFT_NO_LAG>() && fuse_small;
     hipStream_t sd = overlap ? c->side : st;
     // fork: the side stream continues from here on the caller's stream; join: the caller's stream waits for the side stream's work so far
     // An error return between a fork and its join must not leave work queued on the side stream that the caller's stream never waits
@@ -727,9 +719,8 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     // (the feature network's launches are enqueued FIRST: it is the longer chain - two images, instance norms - and the host needs ~0.3 ms
     // to enqueue either network's ~45 launches; a forward that starts on an idle GPU - the first of a timed region, every forward of a loop
     // that reads each result - had the chip run the context network alone for that long before the feature network's first kernel arrived)
-    const char* enp = getenv("EEM_ERAFT_NO_PRE");
-    const char* ens0 = getenv("EEM_ERAFT_NO_STACK");
-    const bool use_pre = !(enp && enp[0] == '1') && !(ens0 && ens0[0] == '1');
+    const bool stack = !sw_on<SW_EEM_ERAFT_NO_STACK>();
+    const bool use_pre = !sw_on<SW_EEM_ERAFT_NO_PRE>() && stack;
     auto run_fnet = [&]() -> int {
         // ---- feature network on [image1; image2] (:116), then its 1x1 output conv
         float* feat = nullptr;
@@ -772,10 +763,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         }
         return EEM_OK;
     };
-    // EEM_ERAFT_CNET_FIRST=1 (read per forward): the order through round 6's first half
-    const char* ecf = getenv("EEM_ERAFT_CNET_FIRST");
-    if (ecf && ecf[0] == '1') { if ((rc = run_cnet()) != EEM_OK || (rc = run_fnet()) != EEM_OK) return rc; }
-    else if ((rc = run_fnet()) != EEM_OK || (rc = run_cnet()) != EEM_OK) return rc;
+    if ((rc = run_fnet()) != EEM_OK || (rc = run_cnet()) != EEM_OK) return rc;
     if ((rc = join()) != EEM_OK) return rc;                            // net, inp, the context parts of the GRU convs, coords
     // final_only: the predictions of iterations 0 .. iters - 2 are never formed - their mask head (the 3x3 128 -> 256 and 1x1 256 -> 576
     // convs) and convex upsampling are not launched; the hidden state and coords1 go through the same launches with the same operands,
@@ -836,16 +824,13 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         float* net = netb[(it + 1) & 1];                                   // (the state this iteration leaves)
         // coords1 lives in two buffers: iteration `it` reads c1[it & 1], the convex-upsampling launch at its end writes the updated
         // coordinates into the other one
-        // EEM_ERAFT_NO_FUSE=1 (read per forward): the separate flow / coords1 += delta launches, for A/B runs and the equality test
-        const char* enf = getenv("EEM_ERAFT_NO_FUSE");
-        const bool fuse_small = !(enf && enf[0] == '1');
+        // EEM_ERAFT_NO_FUSE=1: the separate flow / coords1 += delta launches, for A/B runs and the equality test
         float* c1cur = fuse_small ? c1p : c->c1.p;
         float* c1nxt = fuse_small ? c1q : c->c1.p;
         // :142 lookup; :144 flow = coords1 - coords0 into the motion features' last two channels (update.py:81), by the same launch
-        // (the fork of the flow branch below: the lookup's own completion signal is the event the side stream waits for - EEM_ERAFT_FORK_RECORD=1,
-        // read per forward: a hipEventRecord behind it, as through round 6's first half)
-        const char* efr = getenv("EEM_ERAFT_FORK_RECORD");
-        const bool fork_by_launch = fuse_small && overlap && !(efr && efr[0] == '1');
+        // (the fork of the flow branch below: the lookup's own completion signal is the event the side stream waits for, not a
+        // hipEventRecord behind it as through round 6's first half)
+        const bool fork_by_launch = fuse_small && overlap;
         if (fuse_small) {
             if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st, c->c0.p, c->motion.p, 128, 126, fork_by_launch ? c->fork_ev : nullptr, lp)) != EEM_OK) return rc;
         } else {
@@ -901,9 +886,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         // small elementwise launch), and the first convs of the flow head and the mask head.  One forward at a time at batch 1 these were
         // 200-block launches for 256 CUs each - one round of 5 / 6-row tiles now instead of two launches that each leave the chip
         // partly empty (an update iteration at 60x80: 490 -> 430 us, 121 -> 129 frames/s; + 1.5 % at batch 4 / 8, the same with
-        // frames in flight).  EEM_ERAFT_NO_STACK=1 (read per forward) keeps them apart.
-        const char* ens = getenv("EEM_ERAFT_NO_STACK");
-        const bool stack = !(ens && ens[0] == '1');
+        // frames in flight).  EEM_ERAFT_NO_STACK=1 keeps them apart.
         for (int pass = 0; pass < 2; ++pass) {
             if (stack) {
                 if (use_pre) {
@@ -915,8 +898,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                     set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
                 }
                 // r leaves the launch as r * h (GEPI_ZR); EEM_ERAFT_NO_ZR=1: the separate elementwise launch
-                const char* enz = getenv("EEM_ERAFT_NO_ZR");
-                const bool zr_epi = !(enz && enz[0] == '1');
+                const bool zr_epi = !sw_on<SW_EEM_ERAFT_NO_ZR>();
                 if (zr_epi) { a.epi = GEPI_ZR; a.split = 128; a.out2 = c->rh.p; a.out2_ctotal = 128; a.e0 = hcur; a.e0_ctotal = 128; a.e0_coff = 0; }
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
                 if (!zr_epi && (rc = er_mul_channels_launch(c->rh.p, c->z.p, 256, 128, hcur, B, 128, (long)g, st)) != EEM_OK) return rc;
@@ -1021,10 +1003,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             EEM_HIP_CHECK(hipMemcpyAsync(c->st_delta1.p, c->delta.p, B * 2 * g * 4, hipMemcpyDeviceToDevice, st));
         }
     }
-    {
-        const char* enf = getenv("EEM_ERAFT_NO_FUSE");
-        c1last = !(enf && enf[0] == '1') ? c1p : c->c1.p;
-    }
+    c1last = fuse_small ? c1p : c->c1.p;
     // the stream's flow_low of every pair (the next pair's warm start, the carry, eraft_get_stage)
     if (sp && (rc = er_flow_launch(c->c0.p, c1last, c->sflow.p + lp * 2 * g, 2, 0, B, (int)g, st)) != EEM_OK) return rc;
     }

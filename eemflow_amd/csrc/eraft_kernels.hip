@@ -475,26 +475,7 @@ __device__ __forceinline__ float sample_bilinear(const float* __restrict__ img, 
     return v00 * (1.f - tx) * (1.f - ty) + v01 * tx * (1.f - ty) + v10 * (1.f - tx) * ty + v11 * tx * ty;
 }
 
-__global__ __launch_bounds__(256) void lookup_kernel(LookupArgs a) {
-    const int hw = a.h * a.w;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)a.batch * 324 * hw) return;
-    const int p = idx % hw;
-    const int ch = (idx / hw) % 324;
-    const int b = idx / ((long)hw * 324);
-    const int lvl = ch / 81, k = ch - lvl * 81;
-    const int i = k / 9, jj = k - i * 9;
-    const float cx = a.coords[((size_t)b * 2 + 0) * hw + p], cy = a.coords[((size_t)b * 2 + 1) * hw + p];
-    const float sc = (float)(1 << lvl);
-    const float x = cx / sc + (float)(i - 4);          // the reference adds (dy[i], dx[j]) to (x, y)
-    const float y = cy / sc + (float)(jj - 4);
-    const float* img = a.pyr[lvl] + ((size_t)b * hw + p) * a.ph[lvl] * a.pw[lvl];
-    a.out[((size_t)b * a.out_ctotal + ch) * hw + p] = sample_bilinear<false>(img, a.ph[lvl], a.pw[lvl], x, y);
-    if (a.flow_dst != nullptr && ch < 2)
-        a.flow_dst[((size_t)b * a.flow_ctotal + a.flow_coff + ch) * hw + p] = (ch ? cy : cx) - a.coords0[((size_t)b * 2 + ch) * hw + p];
-}
-
-// The same lookup with both sides coalesced.  lookup_kernel above gives consecutive lanes consecutive PIXELS: its stores are
+// The correlation lookup with both sides coalesced.  A thread per (level, tap, pixel) with consecutive lanes on consecutive PIXELS stores
 // 256-byte runs but every lane samples a different pixel's correlation map (19 KB apart at level 0).  Here a block owns 64
 // consecutive pixels of one pyramid level; lanes walk the flattened (pixel, tap) pairs, so the 64 samples of an instruction
 // come from the 10x10 windows of one or two maps; the values pass through an LDS tile [tap][pixel] and leave as 256-byte runs.
@@ -528,7 +509,7 @@ __global__ __launch_bounds__(256) void lookup_tiled_kernel(LookupArgs a) {
     for (int item = tid; item < npx * 81; item += 256) {
         const int px = item / 81, k = item - px * 81;
         const int i = k / 9, jj = k - i * 9;
-        const float x = cxs[px] * inv + (float)(i - 4);          // as lookup_kernel: the reference adds (dy[i], dx[j]) to (x, y)
+        const float x = cxs[px] * inv + (float)(i - 4);          // the reference adds (dy[i], dx[j]) to (x, y)
         const float y = cys[px] * inv + (float)(jj - 4);
         tile[k][px] = sample_bilinear<FLAT>(maps + (size_t)px * ph * pw, ph, pw, x, y);
     }
@@ -544,7 +525,7 @@ __global__ __launch_bounds__(256) void lookup_tiled_kernel(LookupArgs a) {
 // volume.  avg_pool2d of the volume over its last two dimensions is the correlation with avg_pool2d of fmap2 (linear), so a pixel's
 // 81 taps at level l are bilinear samples of  corr_l(p, q) = <fmap1[:, p], pool^l(fmap2)[:, q]> / sqrt(C)  over the 10 x 10 integer
 // cells its window touches.  One block per (pixel, level): the fmap1 column in LDS, a thread per window cell (a C-long dot product,
-// cells of a window row are consecutive floats of a feature plane), then a thread per tap with lookup_kernel's own corner / weight
+// cells of a window row are consecutive floats of a feature plane), then a thread per tap with the lookup's own corner / weight
 // arithmetic on the 10 x 10 cells (cells outside the map hold 0; a corner that rounding moves out of the window beside an integer
 // coordinate carries a weight ~1e-7 and is dropped).  C * 100 reads per pixel, level and iteration instead of 81 x 4: this path trades
 // ~250x the lookup's memory traffic for not holding B * (HW)^2 * 4/3 floats - 829 MB per sample at 1280x720 - and is off by default.
@@ -747,11 +728,10 @@ int er_instnorm_launch(const float* x, float* out, const float* res, int planes,
 int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, int c, int hw, hipStream_t st) {
     const bool even = hw % 2 == 0 && ((uintptr_t)f1 & 7) == 0 && ((uintptr_t)f2 & 7) == 0 && ((uintptr_t)out & 7) == 0;
     dim3 grid(ceil_div(hw, 128), ceil_div(hw, 128), batch);
-    // the LDS-staged form where it applies (EEM_ALLPAIRS_L2=1, read per call: the form that feeds the MFMAs from L2)
-    const char* el2 = getenv("EEM_ALLPAIRS_L2");
+    // the LDS-staged form where it applies (EEM_ALLPAIRS_L2=1: the form that feeds the MFMAs from L2)
     static float* zero_pages[16] = {};                       // 256 bytes of zeros per device for the pieces past the last pixel (never freed)
     int dev = 0;
-    if (even && c % 16 == 0 && hw % 4 == 0 && (((uintptr_t)f1 | (uintptr_t)f2) & 15) == 0 && !(el2 && el2[0] == '1') &&
+    if (even && c % 16 == 0 && hw % 4 == 0 && (((uintptr_t)f1 | (uintptr_t)f2) & 15) == 0 && !sw_on<SW_EEM_ALLPAIRS_L2>() &&
         hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
         if (!zero_pages[dev]) {
             EEM_HIP_CHECK(hipMalloc(&zero_pages[dev], 256));
@@ -775,13 +755,12 @@ int er_pool2_launch(const float* in, float* out, long planes, int h, int w, hipS
     return EEM_OK;
 }
 
-// levels 1 .. 3 of a pyramid over `planes` planes of h x w in one launch (pool2x3_kernel); EEM_POOL_CHAIN=1 (read per call: the equality
+// levels 1 .. 3 of a pyramid over `planes` planes of h x w in one launch (pool2x3_kernel); EEM_POOL_CHAIN=1 (the equality
 // test flips it) or a level-3 map that would be empty: three er_pool2_launch
 int er_pool2x3_launch(const float* in, float* o1, float* o2, float* o3, long planes, int h, int w, hipStream_t st) {
     const int h1 = h / 2, w1 = w / 2, h2 = h1 / 2, w2 = w1 / 2, h3 = h2 / 2, w3 = w2 / 2;
-    const char* e = getenv("EEM_POOL_CHAIN");
     const long nblk = planes * ceil_div(h1, 4);
-    if ((e && e[0] == '1') || nblk >= (1L << 31) || h3 < 1 || w3 < 1) {
+    if (sw_on<SW_EEM_POOL_CHAIN>() || nblk >= (1L << 31) || h3 < 1 || w3 < 1) {
         int rc;
         if ((rc = er_pool2_launch(in, o1, planes, h, w, st)) != EEM_OK || (rc = er_pool2_launch(o1, o2, planes, h1, w1, st)) != EEM_OK) return rc;
         return er_pool2_launch(o2, o3, planes, h2, w2, st);
@@ -792,19 +771,17 @@ int er_pool2x3_launch(const float* in, float* o1, float* o2, float* o3, long pla
     return EEM_OK;
 }
 
-static const long flat_max = [] { const char* e = getenv("EEM_LOOKUP_FLAT_MAX"); return e ? atol(e) : 1024L; }();
+constexpr long kLookupFlatMax = 1024;                         // blocks of 64 pixels: smaller launches take the FLAT sampler and 16-pixel blocks
 // done_ev (optional): signalled when the launch completes - as the launch's own completion signal (hipExtLaunchKernelGGL's stop event),
 // not as a separate hipEventRecord: an event record behind a kernel is a barrier packet that costs the recording stream ~6 us before its
 // next kernel starts (tools/eraft_timeline.sh: the gap in front of convc1 in every iteration)
 int er_lookup_launch(const LookupArgs& a, hipStream_t st, hipEvent_t done_ev) {
-    static const bool plain = [] { const char* e = getenv("EEM_LOOKUP_PLAIN"); return e && e[0] == '1'; }();
     const long blocks64 = (long)ceil_div(a.h * a.w, 64) * 4 * a.batch;
-    // EEM_LOOKUP_PX=64|32|16 (read per call: the equality test flips it): the block's pixels; default 16 below EEM_LOOKUP_FLAT_MAX blocks of 64
-    const char* epx = getenv("EEM_LOOKUP_PX");
-    const int px = epx ? atoi(epx) : (blocks64 < flat_max ? 16 : 64);
+    // EEM_LOOKUP_PX=64|32|16 (the equality test flips it): the block's pixels; default 16 below kLookupFlatMax blocks of 64
+    const char* epx = sw_raw<SW_EEM_LOOKUP_PX>();
+    const int px = epx ? atoi(epx) : (blocks64 < kLookupFlatMax ? 16 : 64);
     const dim3 gt(ceil_div(a.h * a.w, px == 16 ? 16 : px == 32 ? 32 : 64), 4, a.batch);
-    if (plain) hipExtLaunchKernelGGL(lookup_kernel, dim3(blocks((long)a.batch * 324 * a.h * a.w)), dim3(256), 0, st, nullptr, done_ev, 0, a);
-    else if (blocks64 < flat_max) {
+    if (blocks64 < kLookupFlatMax) {
         if (px == 16) hipExtLaunchKernelGGL((lookup_tiled_kernel<true, 16>), gt, dim3(256), 0, st, nullptr, done_ev, 0, a);
         else if (px == 32) hipExtLaunchKernelGGL((lookup_tiled_kernel<true, 32>), gt, dim3(256), 0, st, nullptr, done_ev, 0, a);
         else hipExtLaunchKernelGGL((lookup_tiled_kernel<true, 64>), gt, dim3(256), 0, st, nullptr, done_ev, 0, a);

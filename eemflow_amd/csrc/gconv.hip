@@ -553,9 +553,8 @@ void fewout_pack(const float* w, int cout, int cin, int kh, int kw, float* packe
 }
 
 bool fewout_supported(const GConvArgs& a) {
-    static const long few_min_px = [] { const char* m = getenv("EEM_FEWOUT_MINPX"); return m ? atol(m) : 256L; }();
-    const char* e = getenv("EEM_NO_FEWOUT");                         // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    constexpr long few_min_px = 256;
+    if (sw_on<SW_EEM_NO_FEWOUT>()) return false;
     return a.wfew && a.nseg == 1 && a.cout <= 8 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.tstride <= 1 && a.pad_h == 1 && a.pad_w == 1 &&
            a.seg[0].cmul <= 1 && a.seg[0].gate == nullptr && a.pre == nullptr && (a.epi == GEPI_PLAIN || a.epi == GEPI_ADD || a.epi == GEPI_SUM2) && a.hout == a.hin && a.wout == a.win &&
            (long)a.hin * a.win >= few_min_px;                        // smaller maps: the split-K launch of the generic kernel
@@ -565,13 +564,12 @@ int fewout_launch(const GConvArgs& a, hipStream_t stream) {
     const long n = (long)a.n * a.hin * a.win;
     const unsigned blocks = (unsigned)((n + 63) / 64);
     // less than a wave per SIMD - or, for the layers of 3 .. 8 couts (EEMFlow+'s mask estimator tail at 96 x 160: 240 blocks), less than
-    // EEM_FEWOUT_SMALL_BLOCKS (read once; 512): a wave's time there is the number of its request round trips (22 channels, one ahead)
-    static const long small_blocks = [] { const char* e = getenv("EEM_FEWOUT_SMALL_BLOCKS"); return e ? atol(e) : 512L; }();
+    // EEM_FEWOUT_SMALL_BLOCKS: a wave's time there is the number of its request round trips (22 channels, one ahead)
+    const long small_blocks = sw_long_once<SW_EEM_FEWOUT_SMALL_BLOCKS>();
     const bool small = (blocks * 8 < 1024 || (a.cout > 2 && (long)blocks < small_blocks)) && a.seg[0].c >= 64;
     if (a.cout <= 2) {                                                // E-RAFT's flow head
-        // EEM_FEWOUT_WIDE=0 (read per call: the equality test flips it): the 64-pixel form for the small launches too
-        const char* ew = getenv("EEM_FEWOUT_WIDE");
-        if (small && a.seg[0].c <= 256 && !(ew && ew[0] == '0')) {
+        // EEM_FEWOUT_WIDE=0 (the equality test flips it): the 64-pixel form for the small launches too
+        if (small && a.seg[0].c <= 256 && sw_not0<SW_EEM_FEWOUT_WIDE>()) {
             eem_conv_form = "fewout_wide2";
             hipLaunchKernelGGL((fewout_wide_kernel<2>), dim3((unsigned)((n + 31) / 32)), dim3(1024), 0, stream, a, (a.seg[0].c + 31) / 32);
         } else if (small) {
@@ -612,12 +610,11 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
     int maxpairs = 0;
     for (int sgi = 0; sgi < a.nseg; ++sgi) maxpairs = std::max(maxpairs, (a.seg[sgi].c + 1) / 2);
     {
-        const char* e = getenv("EEM_NO_TAPS_KERNEL");                // read per call: a test flips it inside one process
-        const bool off = e && e[0] == '1';
+        const bool off = sw_on<SW_EEM_NO_TAPS_KERNEL>();
         const bool shape7 = a.kh == 7 && a.kw == 7, shape3 = a.kh == 3 && a.kw == 3;
         // (one pair only: with the 5-bin volumes' three pairs through a stride-2 7x7 the 2x2-tile batches of the generic kernel are
         // faster - measured, E-RAFT 122 -> 117 frames/s)
-        static const int taps_maxc = [] { const char* e = getenv("EEM_TAPS_MAXC"); return e ? atoi(e) : 6; }();   // 7x7: up to three channel pairs (the encoders' stems on 5-bin volumes; 2 = the flow conv only)
+        constexpr int taps_maxc = 6;   // 7x7: up to three channel pairs (the encoders' stems on 5-bin volumes; 2 = the flow conv only)
         if (!off && a.nseg == 1 && a.seg[0].c <= (shape7 ? taps_maxc : 2) && (shape7 || shape3) && a.tstride <= 1 && a.epi == GEPI_PLAIN && a.pre == nullptr && a.seg[0].gate == nullptr &&
             a.seg[0].cmul <= 1) {
             dim3 grid(ceil_div(hwo, 128), cot, a.n);
@@ -655,9 +652,8 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
         int ksteps = 0;
         for (int sgi = 0; sgi < a.nseg; ++sgi) ksteps += (a.seg[sgi].c + 1) / 2;
         ksteps *= a.kh * a.kw;
-        const char* esk = getenv("EEM_NO_SPLITK");                   // read per call: a test flips it inside one process
-        const bool no_splitk = esk && esk[0] == '1';
-        static const long splitk_max = [] { const char* e = getenv("EEM_SPLITK_MAX"); return e ? atol(e) : 512L; }();
+        const bool no_splitk = sw_on<SW_EEM_NO_SPLITK>();
+        const long splitk_max = sw_long_once<SW_EEM_SPLITK_MAX>();
         // deep single-cout-tile layers (E-RAFT's 256 -> 2 flow head) always split: one wave per 32 pixels would walk all of K
         const long plain_blocks = (long)ceil_div(hwo, 128) * cot * a.n;
         if (!no_splitk && ksteps >= 128 && (plain_blocks < splitk_max || (cot == 1 && ksteps >= 512 && plain_blocks < 4096))) {
@@ -665,9 +661,7 @@ int gconv_launch(const GConvArgs& a, hipStream_t stream) {
             // tiles that leave most of the chip empty: more waves per tile, fewer (latency-bound) batches per wave
             const long tiles = (long)grid.x * cot * a.n;
             const int batches = ksteps / 16;
-            static const int force = [] { const char* e = getenv("EEM_SPLITK_WAVES"); return e ? atoi(e) : 0; }();
-            int skw = tiles <= 64 && batches >= 32 ? 16 : tiles <= 160 && batches >= 16 ? 8 : 4;
-            if (force) skw = force;
+            const int skw = tiles <= 64 && batches >= 32 ? 16 : tiles <= 160 && batches >= 16 ? 8 : 4;
             eem_conv_form = skw == 16 ? "generic_splitk16" : skw == 8 ? "generic_splitk8" : "generic_splitk4";
             if (skw == 16) hipLaunchKernelGGL((gconv_kernel<1, 1, 16>), grid, dim3(1024), 0, stream, a);
             else if (skw == 8) hipLaunchKernelGGL((gconv_kernel<1, 1, 8>), grid, dim3(512), 0, stream, a);

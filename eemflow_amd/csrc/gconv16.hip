@@ -381,11 +381,10 @@ int launch_wm(const GConvArgs& a, const float* wpk16, const float* zero_page, hi
     const int ng = a.groups > 1 ? a.groups : 1;
     dim3 grid(tiles_x * tiles_y, ceil_div(a.cout, 16 * WM) * ng, a.n);
     // at most one block per CU: two K groups of four waves per tile (see the kernel's KG)
-    static const int kg_env = [] { const char* e = getenv("EEM_G16_KG"); return e ? atoi(e) : 0; }();
     static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
     const int nchunks = cin / 16;
     const long blocks = (long)grid.x * grid.y * grid.z;
-    const bool two = nchunks >= 4 && (kg_env ? kg_env == 2 : (blocks <= cus && a.in_flight < 3));
+    const bool two = nchunks >= 4 && blocks <= cus && a.in_flight < 3;
     static const G16Name names[2] = {G16Name(KH, KW, THT, WM, 1, 1), G16Name(KH, KW, THT, WM, 2, 1)};   // (written once per instantiation)
     eem_conv_form = names[two].s;
     if (two) hipLaunchKernelGGL((gconv16_kernel<KH, KW, THT, WM, 2>), grid, dim3(512), 0, stream, a, wpk16, zero_page, tiles_x, nchunks);
@@ -418,12 +417,9 @@ int launch_s2(const GConvArgs& a, const float* wpk16, const float* zero_page, hi
 
 template <int KH, int KW>
 int launch(const GConvArgs& a, const float* wpk16, const float* zero_page, hipStream_t stream) {
-    static const int th_env = [] { const char* e = getenv("EEM_G16_TH"); return e ? atoi(e) : 0; }();
     const auto blocks_of = [&](int th) { return (long)ceil_div(a.wout, 16) * ceil_div(a.hout, th) * ceil_div(a.cout, 64) * a.n * (a.groups > 1 ? a.groups : 1); };
     int th;
-    if (th_env) {
-        th = th_env;
-    } else if (a.in_flight >= 3) {
+    if (a.in_flight >= 3) {
         // with several frames in flight the other frames fill the CUs a short launch leaves idle, and what counts is CU time: 4-row tiles
         // read every weight fragment half as often (E-RAFT batch 4, three in flight: 168 -> 175 frames/s; one at a time 144 -> 138)
         th = blocks_of(4) < 512 ? 2 : 4;
@@ -494,8 +490,7 @@ void gconv16_pack(const float* w, int cout, const int* cs, int nseg, int kh, int
 }
 
 bool gconv16_supported(const GConvArgs& a) {
-    const char* e = getenv("EEM_NO_GCONV16");                    // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_GCONV16>()) return false;
     if (!a.wpk16 || !a.zero_page || a.tstride > 1 || a.pad_h != a.kh / 2 || a.pad_w != a.kw / 2) return false;
     int cs[3];
     for (int s = 0; s < a.nseg; ++s) {
@@ -506,14 +501,13 @@ bool gconv16_supported(const GConvArgs& a) {
     for (int s = 0; s < a.nseg; ++s) cin += cs[s];
     // measured on E-RAFT (640x480, batch 1 / 4) and EEMFlow+ (1280x720): shallow inputs and launches of a few dozen blocks
     // stay on the generic kernel's split-K form (128 blocks before the K groups and the tile-row choice, 12 with them)
-    static const int min_cin = [] { const char* m = getenv("EEM_G16_MINCIN"); return m ? atoi(m) : 32; }();
-    static const long min_blk = [] { const char* m = getenv("EEM_G16_MINBLK"); return m ? atol(m) : 12L; }();
+    constexpr int min_cin = 32;
+    constexpr long min_blk = 12;
     const long blocks = (long)ceil_div(a.wout, 16) * ceil_div(a.hout, 4) * ceil_div(a.cout, 64) * a.n * (a.groups > 1 ? a.groups : 1);
     if (cin < min_cin || blocks < min_blk) return false;
     if (a.groups > 1 && (a.nseg != 1 || a.epi != GEPI_PLAIN)) return false;
     if (a.stride == 2) {                                         // downsampling form: plain epilogues, one segment, no groups
-        const char* m = getenv("EEM_NO_G16_S2");                 // read per call, like EEM_NO_GCONV16
-        if ((m && m[0] == '1') || a.groups > 1 || a.pre || (a.epi != GEPI_PLAIN && a.epi != GEPI_ADD_RELU && a.epi != GEPI_ADD)) return false;
+        if (sw_on<SW_EEM_NO_G16_S2>() || a.groups > 1 || a.pre || (a.epi != GEPI_PLAIN && a.epi != GEPI_ADD_RELU && a.epi != GEPI_ADD)) return false;
         return gconv16_shape(a.cout, cs, a.nseg, a.kh, a.kw, 2) && a.win % 4 == 0 && a.hout == (a.hin + 2 * a.pad_h - a.kh) / 2 + 1 &&
                a.wout == (a.win + 2 * a.pad_w - a.kw) / 2 + 1 && (size_t)16 * a.hin * a.win * 4 < (1u << 31) &&
                (size_t)a.cout * a.hout * a.wout < (1u << 31);

@@ -349,7 +349,7 @@ int gb_launch_t(const GConvArgs& a, hipStream_t stream) {
     const int tiles_x = ceil_div(a.wout, C::TW), tiles_y = ceil_div(a.hout, C::TH);
     dim3 grid(tiles_x * tiles_y, ceil_div(a.cout, 128), a.n);
 #ifdef EEM_DIAG
-    { static int once = [] { const char* e = getenv("EEM_GB_DBG"); int v = e ? atoi(e) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gb_dbg), &v, sizeof v); return v; }(); (void)once; }
+    { static int once = [] { int v = sw_int<SW_EEM_GB_DBG>(); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gb_dbg), &v, sizeof v); return v; }(); (void)once; }
 #endif
     static const struct Name { char s[32]; Name() { snprintf(s, sizeof(s), "gconvb_%dx%d_th%d", KH, KW, THT); } } name;   // eem_conv_form
     eem_conv_form = name.s;
@@ -363,23 +363,19 @@ int gb_launch_t(const GConvArgs& a, hipStream_t stream) {
 // the work); its 128-cout convs are 160 blocks of 8 rows on 256 CUs or 200 of 6.  The count with the least (rounds x (rows + 2)), the
 // per-block prologue and epilogue counted as two rows (anything from one to six rows gives the same frame rates): E-RAFT 640x480 x 12
 // batch 4 245 -> 256 frames/s against tiles of 4 / 8 rows only, batch 1 162 -> 165; every forced height is slower than the choice
-// (EEM_GCONVB_TH = 2 / 4 / 6 / 8: 208 / 235 / 249 / 243 at batch 4).
+// (2 / 4 / 6 / 8 rows everywhere: 208 / 235 / 249 / 243 at batch 4).
 template <int KH, int KW>
 int gb_launch(const GConvArgs& a, hipStream_t stream) {
-    static const int th_env = [] { const char* e = getenv("EEM_GCONVB_TH"); return e ? atoi(e) : 0; }();
     static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
     const auto cost = [&](int th) { return (float)ceil_div(ceil_div(a.wout, 16) * ceil_div(a.hout, th) * ceil_div(a.cout, 128) * a.n, cus) * (float)(th + 2); };
-    int th = th_env;
-    if (th != 2 && th != 4 && th != 6 && th != 8) {
-        th = 8;
-        for (int t = 6; t >= 2; t -= 2)
-            if (cost(t) < cost(th) - 1e-3f) th = t;
-    }
+    int th = 8;
+    for (int t = 6; t >= 2; t -= 2)
+        if (cost(t) < cost(th) - 1e-3f) th = t;
 #ifdef EEM_DIAG
     // diagnostic builds, EEM_GCONVB_RING=3: the tiles of up to six rows request their weights two k-steps ahead (three slots).  Measured
     // (tools/gconvb_ring.sh): E-RAFT 640x480 x 12 batch 1 178.1 / 179.2 against 179.9 / 180.0 frames/s, batch 4 272.1 / 272.4 against
     // 275.5 / 275.6 - the weights' round trip is not what a k-step waits for
-    const char* rg = getenv("EEM_GCONVB_RING");
+    const char* rg = sw_raw<SW_EEM_GCONVB_RING>();
     if (rg && rg[0] == '3') {
         if (th == 2) return gb_launch_t<KH, KW, 2, 3>(a, stream);
         if (th == 4) return gb_launch_t<KH, KW, 4, 3>(a, stream);
@@ -488,8 +484,7 @@ void gconvb_pack(const float* w, int cout, const int* cs, int nseg, int kh, int 
 }
 
 bool gconvb_supported(const GConvArgs& a) {
-    const char* e = getenv("EEM_NO_GCONVB");                      // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_GCONVB>()) return false;
     if (!a.wpkb || !a.zero_page || a.tstride > 1 || a.stride != 1 || a.pad_h != a.kh / 2 || a.pad_w != a.kw / 2 || a.groups > 1 || a.out_cmul > 1) return false;
     int cs[3];
     for (int s = 0; s < a.nseg; ++s) {
@@ -499,15 +494,14 @@ bool gconvb_supported(const GConvArgs& a) {
     if (!gconvb_shape(a.cout, cs, a.nseg, a.kh, a.kw, a.stride)) return false;
     // 1x1: a k-step per chunk - the staging waves (one tile conversion per 48 MFMAs) set the pace: 72 us against gconv16's 45-63 at
     // E-RAFT's batch 4; EEM_GCONVB_1X1=1 sends them here all the same (tests)
-    if (a.kh == 1 && a.kw == 1) { const char* o = getenv("EEM_GCONVB_1X1"); if (!(o && o[0] == '1')) return false; }
+    if (a.kh == 1 && a.kw == 1 && !sw_on<SW_EEM_GCONVB_1X1>()) return false;
     if (a.win % 4 || a.wout % 4 || a.hout != a.hin || a.wout != a.win || ((uintptr_t)a.out & 15)) return false;
     if ((a.pre && ((uintptr_t)a.pre & 15)) || (a.epi != GEPI_PLAIN && ((uintptr_t)a.e0 & 15)) || (a.epi == GEPI_GRU && ((uintptr_t)a.e1 & 15)) ||
         (a.epi == GEPI_ZR && (((uintptr_t)a.out2 & 15) || a.split % 16)))
         return false;
     if ((size_t)a.cout * a.hin * a.win >= (1u << 30) || (size_t)32 * a.hin * a.win * 4 >= (1u << 31)) return false;
     // large tiles (128 pixels x 64 couts): launches that fill the chip with them; the others stay on gconv16.hip
-    const char* mb = getenv("EEM_GCONVB_MINBLK");                 // (read per call, like the switch above: the tests run small shapes through it)
-    const long min_blk = mb ? atol(mb) : 64L;
+    const long min_blk = sw_long<SW_EEM_GCONVB_MINBLK>();         // (the tests run small shapes through it)
     const long blocks = (long)ceil_div(a.wout, 16) * ceil_div(a.hout, 8) * ceil_div(a.cout, 128) * a.n;
     return blocks >= min_blk;
 }

@@ -37,7 +37,7 @@
 //                         block); one pass then rounds every cell to fp32 once, stores both channels and leaves the band's
 //                         (sum S, sum S^2).  9216 cells (72 KB) at most: 3 rows at w = 1280, 240 bands at 720 rows.
 //   3. iwe_moments_kernel one block per job adds the band partials and the binning blocks' drop counts in a fixed order.
-// Direct form (frames too wide for a one-row band, more than 16.7 M events, or EEM_IWE_DIRECT=1 - read per call): one thread per
+// Direct form (frames too wide for a one-row band, more than 16.7 M events, or EEM_IWE_DIRECT=1): one thread per
 // event adds its votes with global atomics.  The image's contract is an fp64 sum rounded once - a chain of fp32 atomic adds is off by
 // up to one rounding per vote, several ulps of the cell, where one ulp is allowed - so the direct form adds fp64 atomics into a zeroed
 // fp64 image in the scratch arena, and a finishing pass rounds, stores and takes the moments (memset + two launches + the moments
@@ -265,8 +265,7 @@ __global__ __launch_bounds__(256) void iwe_warp_kernel(const double* __restrict_
 
 // ------------------------------------------------------------------------------------------------ host
 inline int iwe_ept(long n) {
-    const char* e = getenv("EEM_IWE_EPT");                         // events per binning thread, 1 / 2 / 4 (read per call: the tests run all three)
-    const int forced = e ? atoi(e) : 0;
+    const int forced = sw_int<SW_EEM_IWE_EPT>();                   // events per binning thread, 1 / 2 / 4 (the tests run all three)
     if ((forced == 1 || forced == 2 || forced == 4) && iwe_blocks(n, forced) <= IWE_MAX_BLOCKS) return forced;
     int ept = 1;
     while (ept < 4 && iwe_blocks(n, ept) > 512) ept *= 2;

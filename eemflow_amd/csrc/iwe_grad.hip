@@ -23,7 +23,7 @@
 //                            the run table run_start[blk][band]: no global atomics.  A record of two zeros is not emitted.
 //   2. iwe_grad_band_kernel  one block per band: the band as fp64 LDS cells (ds_add_f64), 2^sgs adjacent lanes share a run; one pass
 //                            rounds every cell to fp32 once and stores it.
-// Direct form (frames too wide for a one-row band, more than 8.4 M events, or EEM_IWE_DIRECT=1 - read per call): one thread per event
+// Direct form (frames too wide for a one-row band, more than 8.4 M events, or EEM_IWE_DIRECT=1): one thread per event
 // adds its contributions, unrounded, with fp64 global atomics into a zeroed fp64 [2][h][w] image in the scratch arena; a finishing pass
 // rounds to fp32 (memset + two launches per job).  The order of the adds is free in both forms: the gradient is not bitwise
 // reproducible from run to run (its fp64 sums differ by their last bits, far below the fp32 it is rounded to).

@@ -159,10 +159,7 @@ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline long iwe_blocks(long n, int ept) { return (n + (long)VT * ept - 1) / ((long)VT * ept); }
 constexpr long IWE_MAX_BLOCKS = 4096;                              // 16.7 M events at 4 per thread; beyond: direct form
 
-inline bool iwe_direct_forced() {
-    const char* e = getenv("EEM_IWE_DIRECT");                      // read per call: the tests run both forms in one process
-    return e && e[0] == '1';
-}
+inline bool iwe_direct_forced() { return sw_on<SW_EEM_IWE_DIRECT>(); }
 
 // the band layout of an h x w frame for binning blocks of up to `ept_max` events per thread, or false: the direct form serves it
 inline bool iwe_plan(long nmax, int h, int w, IwePlan* pl, int ept_max = 4) {

@@ -711,7 +711,7 @@ extern "C" int eemop_conv2d_bwd_weight(const float* x, const float* dy, int n, i
     const int hout = (hin + 2 * ph - kh) / stride + 1, wout = (win + 2 * pw - kw) / stride + 1;
     int rc;
     {
-        static const bool log_calls = [] { const char* e = getenv("EEM_WGRAD_LOG"); return e && e[0] == '1'; }();
+        const bool log_calls = sw_on_once<SW_EEM_WGRAD_LOG>();
         if (log_calls)                                               // (measurement: the shapes a training step asks for, tools/wgrad_shapes.sh)
             fprintf(stderr, "WGRAD cic=%d cout=%d k=%dx%d s=%d n=%d hin=%d win=%d cin=%d ci0=%d db=%d\n", cic, cout, kh, kw, stride, n, hin, win, cin,
                     ci0, db != nullptr);
@@ -1001,8 +1001,7 @@ extern "C" int eemop_resize_ac_fwd(const float* in, float* out, int nc, int h, i
 extern "C" int eemop_resize_ac_bwd(const float* dout, float* dx, int nc, int h, int w, int oh, int ow, void* stream) {
     EEM_REQUIRE(dout && dx && nc >= 1, "eemop_resize_ac_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const char* e = getenv("EEM_RESIZE_BWD_SCATTER");              // read per call: the tests compare both forms in one process
-    if (!(e && e[0] == '1')) {
+    if (!sw_on<SW_EEM_RESIZE_BWD_SCATTER>()) {
         const long npix = (long)nc * h * w;
         hipLaunchKernelGGL(resize_ac_bwd_gather_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, st, dout, dx, h, w, oh, ow, npix);
         EEM_HIP_CHECK(hipGetLastError());

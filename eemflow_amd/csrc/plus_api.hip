@@ -143,23 +143,29 @@ void mk(Pk& pk, PLayer& L, const float* w, const float* b, int cin, int cout, in
 // launches of several jobs win - the decoder's first conv 25 -> 22 us, its grouped layers 16 -> 11, its 96 -> 64 conv 24 -> 16 - and the
 // one-job layers are level with the LDS-tiled kernel (120 blocks on 256 CUs); with four samples per call they win too, and so does
 // 48 x 80 (1 290 -> 1 374 frames/s).  What decides is how many (tile, job, sample) triples a launch has for the chip: from
-// EEM_PLUS_WNC_MINPAIRS (128) on.  EEM_PLUS_WNC_MINPX / EEM_PLUS_WNC_MINPX_JOBS, when set, replace that by the first rule - maps of at
+// kWncMinPairs on.  EEM_PLUS_WNC_MINPX / EEM_PLUS_WNC_MINPX_JOBS, when set, replace that by the first rule - maps of at
 // least so many pixels, for one-job launches / launches of several jobs (defaults 30000 / 10000; 0 sends every level through the kernel:
-// the tests).  All read per call.
+// the tests).
+constexpr long kWncMinPairs = 128;
 bool wnc_wanted(int h, int w, int njobs, int n) {
     if (w % 4) return false;
-    const char* m = getenv("EEM_PLUS_WNC_MINPX");
-    const char* mj = getenv("EEM_PLUS_WNC_MINPX_JOBS");
+    const char* m = sw_raw<SW_EEM_PLUS_WNC_MINPX>();
+    const char* mj = sw_raw<SW_EEM_PLUS_WNC_MINPX_JOBS>();
     const long px = (long)h * w;
     if (m || mj) {
         const long lim1 = m ? atol(m) : 30000L, limj = mj ? atol(mj) : 10000L;
         return px >= lim1 || (njobs >= 2 && px >= limj);
     }
-    const char* sm = getenv("EEM_WNC_SMALL_MAXPX");                 // (wnc_launch's choice of block tile: 4 x 32 below it, 4 x 64 from it on)
-    const int tw = px < (sm ? atol(sm) : 30000L) ? 32 : 64;
-    const char* mp = getenv("EEM_PLUS_WNC_MINPAIRS");
-    return (long)((h + 3) / 4) * ((w + tw - 1) / tw) * njobs * n >= (mp ? atol(mp) : 128L);
+    const int tw = wnc_small_map(h, w) ? 32 : 64;
+    return (long)((h + 3) / 4) * ((w + tw - 1) / tw) * njobs * n >= kWncMinPairs;
 }
+// The small-grid kernel of EEMFlow's tail on the coarse pyramid levels: maps of at most so many cells (single convs / the decoder's chain)
+constexpr long kConvTailMaxCells = 4096, kDecTailMaxCells = 4096;
+// EEM_PLUS_TAIL_MAXCIN: the widest layer the small-grid kernel takes - 100 keeps the dense estimator's four wide convs (128 .. 184
+// channels) on the LDS-tiled / few-cout kernels, as before round 5
+int tail_maxcin() { return sw_int<SW_EEM_PLUS_TAIL_MAXCIN>(); }
+// EEM_PLUS_NO_FUSE=1: the launches this file fuses - paired projections, rconv beside the mask estimator, warp + blend + copy - apart
+bool plus_fuse() { return !sw_on<SW_EEM_PLUS_NO_FUSE>(); }
 void wnc_common(eemplus_ctx* c, WncArgs& a, int cin, int n, int h, int w, int act) {
     memset(&a, 0, sizeof(a));
     a.nchunks = wnc_chunks(cin, a.chunk_off);
@@ -194,14 +200,8 @@ int conv(eemplus_ctx* c, const PLayer& L, const float* in, int in_ctotal, int in
         if (conv_wnc_args(c, L, in, in_ctotal, in_coff, n, hin, win, out, out_ctotal, out_coff, out_cmul, act, wa, policy_jobs)) return wnc_launch(wa, st);
     }
     // small maps (the coarse pyramid levels): the small-grid kernel of EEMFlow's tail
-    static const bool no_tail = [] { const char* e = getenv("EEM_PLUS_NO_TAIL"); return e && e[0] == '1'; }();
     const bool add_ok = add == nullptr || (out_ctotal == L.cout && out_coff == 0 && out_cmul <= 1);   // residual indexed like the output
-    // EEM_PLUS_TAIL_MAXCIN (read per call; 184): the widest layer the small-grid kernel takes - 100 keeps the dense estimator's four wide
-    // convs (128 .. 184 channels) on the LDS-tiled / few-cout kernels, as before round 5
-    const char* emc = getenv("EEM_PLUS_TAIL_MAXCIN");
-    const int tail_maxcin = emc ? atoi(emc) : 184;
-    static const long conv_tail_max = [] { const char* e = getenv("EEM_PLUS_CONV_TAIL_MAX"); return e ? atol(e) : 4096L; }();   // cells
-    if (!no_tail && L.has_tail && L.cin <= tail_maxcin && add_ok && (long)hin * win <= conv_tail_max && (act == GACT_LEAKY || act == GACT_NONE)) {
+    if (L.has_tail && L.cin <= tail_maxcin() && add_ok && (long)hin * win <= kConvTailMaxCells && (act == GACT_LEAKY || act == GACT_NONE)) {
         TailConvLaunch T;
         T.batch = n; T.h = hin; T.w = win; T.ksize = L.k; T.njobs = 1;
         TailConvJob& j = T.job[0];
@@ -244,9 +244,7 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
     const int G = c->groups, per = kDW / G;
     // coarse levels: every conv is a handful of 16x16 tiles - the small-grid kernel of EEMFlow's tail (one launch per layer,
     // the groups of a layer as jobs, K split over the waves of a block) instead of one generic-conv launch per group
-    static const bool no_tail = [] { const char* e = getenv("EEM_PLUS_NO_TAIL"); return e && e[0] == '1'; }();
-    static const long tail_max = [] { const char* e = getenv("EEM_PLUS_TAIL_MAX"); return e ? atol(e) : 4096L; }();
-    const bool small = !no_tail && (long)h * w <= tail_max && c->dec1[l].has_tail && c->decg[l][0][0].has_tail && c->dec5[l].has_tail &&
+    const bool small = (long)h * w <= kDecTailMaxCells && c->dec1[l].has_tail && c->decg[l][0][0].has_tail && c->dec5[l].has_tail &&
                        c->dec6[l].has_tail && G * 1 <= TAIL_MAX_JOBS;
     if (small) {
         auto job = [&](const PLayer& L, const float* in, int in_ctotal, int in_coff, float* out, int out_ctotal, int out_coff, int out_cmul) {
@@ -273,8 +271,7 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
         if ((rc = tail_conv_launch(L, st)) != EEM_OK) return rc;
     } else {
         if ((rc = conv(c, c->dec1[l], cat, kCat, 0, B, h, w, c->d[0].p, kDW, 0, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
-        const char* eng = getenv("EEM_PLUS_NO_GROUPED");             // read per forward: a test runs both forms in one process
-        const bool no_grouped = eng && eng[0] == '1';
+        const bool no_grouped = sw_on<SW_EEM_PLUS_NO_GROUPED>();
         for (int layer = 0; layer < 3; ++layer) {
             // the G groups of a layer as ONE launch of the LDS-tiled kernel when their packings lie at equal distances in the arena
             // (they do: same shapes, packed one after the other) and the launch qualifies
@@ -397,7 +394,7 @@ extern "C" int eemplus_load_weights(eemplus_ctx* c, const float* flat, size_t nf
         mk(pk, L, w, b, cin, cout, k, stride);
     };
     const int ec[8][3] = {{n_first_channels, 16, 2}, {16, 16, 1}, {16, 32, 2}, {32, 32, 1}, {32, 32, 1}, {32, 64, 2}, {64, 64, 1}, {64, 64, 1}};
-    c->enc_fast = n_first_channels == 5 && !getenv("EEM_PLUS_GENERIC_ENC");
+    c->enc_fast = n_first_channels == 5 && !sw_present<SW_EEM_PLUS_GENERIC_ENC>();
     for (int i = 0; i < 8; ++i) {
         const float* w = cur.p;
         layer(c->enc[i], ec[i][0], ec[i][1], 3, ec[i][2]);
@@ -486,11 +483,8 @@ static int level_units(eemplus_ctx* c, int l, int B, hipStream_t st, bool skip_r
     const float* f2 = c->fb[l] + (size_t)c->f2off * C[l] * h * w;
     if (l <= 5) {
         // (the coarse levels: both projections - the same weights on the two feature maps - as the two jobs of ONE small-grid launch)
-        static const bool no_tail = [] { const char* e = getenv("EEM_PLUS_NO_TAIL"); return e && e[0] == '1'; }();
-        static const long conv_tail_max = [] { const char* e = getenv("EEM_PLUS_CONV_TAIL_MAX"); return e ? atol(e) : 4096L; }();
         const PLayer& P = c->c1x1[l];
-        const char* epf0 = getenv("EEM_PLUS_NO_FUSE");
-        if (!no_tail && P.has_tail && (long)h * w <= conv_tail_max && !(epf0 && epf0[0] == '1')) {
+        if (P.has_tail && (long)h * w <= kConvTailMaxCells && plus_fuse()) {
             TailConvLaunch T;
             T.batch = B; T.h = h; T.w = w; T.ksize = P.k; T.njobs = 2;
             for (int q = 0; q < 2; ++q) {
@@ -532,26 +526,18 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
     float* const a2 = c->a2_l[l].p;
     float* const cat = c->cat_l[l].p;
     // coarse levels (small-grid kernel): rconv_l - 64 -> 32 over feature_1, the shape of the mask estimator's first conv - is the second
-    // job of that conv's launch instead of a launch of its own (EEM_PLUS_NO_FUSE=1, read per forward: apart)
-    bool rconv_rides = false;
-    {
-        static const bool no_tail = [] { const char* e = getenv("EEM_PLUS_NO_TAIL"); return e && e[0] == '1'; }();
-        static const long conv_tail_max = [] { const char* e = getenv("EEM_PLUS_CONV_TAIL_MAX"); return e ? atol(e) : 4096L; }();
-        const char* epf0 = getenv("EEM_PLUS_NO_FUSE");
-        const char* emc = getenv("EEM_PLUS_TAIL_MAXCIN");
-        rconv_rides = !units_done && !no_tail && !(epf0 && epf0[0] == '1') && (long)h * w <= conv_tail_max && c->de[0].has_tail &&
-                      c->rconv[l].has_tail && (emc ? atoi(emc) : 184) >= 64 && TAIL_MAX_JOBS >= 2 &&
-                      !(c->rconv[l].has_wnc && wnc_wanted(h, w, 1, B));      // (a map forced onto the Winograd kernel keeps rconv there)
-    }
+    // job of that conv's launch instead of a launch of its own (EEM_PLUS_NO_FUSE=1: apart)
+    const bool rconv_rides = !units_done && plus_fuse() && (long)h * w <= kConvTailMaxCells && c->de[0].has_tail &&
+                             c->rconv[l].has_tail && tail_maxcin() >= 64 && TAIL_MAX_JOBS >= 2 &&
+                             !(c->rconv[l].has_wnc && wnc_wanted(h, w, 1, B));      // (a map forced onto the Winograd kernel keeps rconv there)
     if (!units_done && (rc = level_units(c, l, B, st, rconv_rides)) != EEM_OK) return rc;
     // cdc_model.forward (cdc_utils.py:156-174)
     if (forced_init) {
         // teacher-forced level (eemplus_level): cdc_model's upsampled flow_init is supplied by the caller
         EEM_HIP_CHECK(hipMemcpyAsync(fi, forced_init, B * 2 * g * 4, hipMemcpyDeviceToDevice, st));
     }
-    // warp + blend + the copy of flow_up into the decoder's input as one launch (EEM_PLUS_NO_FUSE=1, read per forward: the separate launches)
-    const char* epf = getenv("EEM_PLUS_NO_FUSE");
-    const bool fuse3 = !(epf && epf[0] == '1');
+    // warp + blend + the copy of flow_up into the decoder's input as one launch (EEM_PLUS_NO_FUSE=1: the separate launches)
+    const bool fuse3 = plus_fuse();
     if (!forced_init && (hc != h || wc != w) && fuse3 && (size_t)h * w >= 2 * (size_t)hc * wc) {
         // upsampling, the coarse flow's doubling and the warp by the upsampled flow as ONE launch; the doubled coarse flow lands in a
         // second buffer (the launch's other threads still read the plain one) that takes the coarse flow's place from here on
@@ -739,13 +725,12 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
     auto f1 = [&](int l) { return (const float*)c->fb[l]; };
     auto f2 = [&](int l) { return (const float*)c->fb[l] + (size_t)c->f2off * C[l] * hl[l] * wl[l]; };
     // ---- what the levels compute from the pyramid alone (level_units), on a side stream beside the coarse levels' chain: OPT-IN
-    // (EEM_PLUS_SIDE=1, read per forward).  Measured at 1280x720 over 40 forwards: 841 - 866 frames/s against 884 - 891 in the chain - the
+    // (EEM_PLUS_SIDE=1).  Measured at 1280x720 over 40 forwards: 841 - 866 frames/s against 884 - 891 in the chain - the
     // fork's event record and the five waits cost the chain more than the ~75 us of launches they take out of it, and a forward that
     // starts on an idle GPU is held up by the host enqueueing the side stream's 12 launches first (tools/plus_timeline.sh).
     for (int l = 6; l >= 2; --l)
         if ((rc = level_buffers(c, l, B)) != EEM_OK) return rc;
-    const char* ens = getenv("EEM_PLUS_SIDE");
-    const bool side = ens && ens[0] == '1';
+    const bool side = sw_on<SW_EEM_PLUS_SIDE>();
     if (side) {
         if (!c->side) {
             EEM_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));

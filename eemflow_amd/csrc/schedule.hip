@@ -1,57 +1,30 @@
 // The EEMFlow forward schedule (declared in ctx.h): which kernel form every layer takes, and the chain of launches from the event
 // volumes to the flow - encoder, stage pooling / correlation / rconv, decoders, out_conv and upsample.  The inference entry points
 // (api.hip) and the training forward (train_api.hip) run this one copy.
-#include <stdlib.h>
-
 #include "ctx.h"
 
 // ------------------------------------------------------------------------------- dispatch policy
 // Everything that decides a kernel FORM (the tests mirror these predicates): eemflow_ctx::f4_mask / layer_f4 (ctx.h), s2r_wanted,
 // bx3_wanted, dec_wnc_wanted and enc_walk below.  The launchers apply further shape conditions of their own (conv_enc.hip's
 // dispatch, wnc_supported, tail_up_supported).
-//
-// Environment switches read by the schedule and the workspace, and WHEN (tests pin forms with setenv inside one process: only a
-// per-launch / per-call read follows them):
-//
-//   switch             read                                     default   effect
-//   EEM_WINO           at eemflow_load_weights (api.hip)        on        0: direct-convolution kernels; 2: Winograd, never F(4x4)
-//   EEM_WINO4_LAYERS   at eemflow_load_weights (api.hip)        unset     <mask>: f4_mask is always that mask (bit 0/1/2: C = 16/32/64)
-//   EEM_S2R            per launch (s2r_wanted; conv_s2r.hip)    off       1: the stride-2 layers on conv_s2r.hip
-//   EEM_BX3_S1         per launch (bx3_wanted; conv_bx3.hip)    0         <mask>: stride-1 layers on conv_bx3.hip (bit 0: C = 32, 1: C = 64)
-//   EEM_DEC_WNC        per call (dec_wnc_wanted)                unset     0: off, 1: at every batch, unset: from batch 4 on
-//   EEM_TAIL_HEAD_LDS  per schedule build (tail_head_lds_wanted) unset    0: tail_head_kernel always, 1: the LDS form wherever it is
-//                                                                         supported, unset: from four frames per launch on
-//   EEM_FUSE12         per schedule build (run_enc12) and per   off       1: pconv1_1 + pconv1_2 as one launch (a cached graph keeps
-//                      alloc_workspace (its block scratch)                the form it was captured with)
-//   EEM_ZIGZAG         once per process (enc_walk)              0         <layer mask>: images back to front
-//   EEM_COLWALK        once per process (enc_walk)              3_2, 3_3  <layer mask>: tiles in columns
-//   EEM_WALK3          once per process (enc_walk)              stride-1  <layer mask>: interleaved tile walk (supersedes the two above)
-//   EEM_NT_STORE       once per process (enc_walk)              0         <layer mask>: non-temporal output stores
-//   EEM_KEEP_F13       once per process (run_enc_layer)         off       1: inference writes f13 although only its pooling is read
-//   EEM_NO_TAIL_FUSE   once per process (run_forward_impl)      off       1: pool finalize, correlation, rconv, out_conv, upsample apart
-//   -DEEM_DIAG builds only:
-//   EEM_SKIP_KERNELS   once per process (Hook::skipped)         unset     "prefix;prefix": launches skipped by name (the flow is garbage)
-//   EEM_SKIP_SPIN_US   once per process and launch site         0         a skipped launch holds its place in the stream that long
-//                      (Hook::run, ctx.h)
-//   EEM_SPANS          once per process (spans_on)              off       1: encoder / tail chain spans to stderr every 64 frames
+// The environment switches these read, and WHEN, are rows of switches.def.h (tests pin forms with setenv inside one process: only a
+// per-call read follows them).
 //
 // The packed forms a launch can actually take (the opt-in kernels' switches are read per launch - conv_s2r.hip, conv_bx3.hip - and so are
 // these): after every optimizer step the packed copies are stale, and a transform nobody reads was six ~5 us launches in the chain of
 // a training step's forward
-bool s2r_wanted() { const char* on = getenv("EEM_S2R"); return on && on[0] == '1'; }
+bool s2r_wanted() { return sw_on<SW_EEM_S2R>(); }
 bool bx3_wanted(int l) {
     const EncLayerDesc& d = kEncLayers[l];
-    if (d.stride == 2) return true;
-    const char* m = getenv("EEM_BX3_S1");
-    return ((m ? atoi(m) : 0) & (d.cin == 32 ? 1 : 2)) != 0;
+    return d.stride == 2 || bx3_s1_wanted(d.cin);
 }
 // The decoders' conv1 / conv5 on the Winograd kernel: wanted for grids whose rows are 16-byte multiples (1280x720: 12 x 20 cells; MVSEC's
 // 5 x 6 stays on the small-grid kernel) from four samples per launch on - the rule of the encoder's F(4x4) forms (f4_mask): one frame alone
 // is three 20-us tiles per (decoder, slice) where the small-grid kernel needs 5 - 9 us (`latency_ms_b1` 0.192 -> 0.207 ms with the kernel
-// at every batch).  EEM_DEC_WNC (read per call): 0 off, 1 at every batch (tests that compare a batch with its shards pin the form), unset: by batch.
+// at every batch).  EEM_DEC_WNC: 0 off, 1 at every batch (tests that compare a batch with its shards pin the form), unset: by batch.
 // The training forward takes the same rule.
 bool dec_wnc_wanted(const eemflow_ctx* c, int gw, int batch) {
-    const char* e = getenv("EEM_DEC_WNC");
+    const char* e = sw_raw<SW_EEM_DEC_WNC>();
     if (c->dec_wnc == nullptr || gw % 4 != 0 || (e && e[0] == '0')) return false;
     return (e && e[0] == '1') || batch >= 4;
 }
@@ -59,9 +32,9 @@ bool dec_wnc_wanted(const eemflow_ctx* c, int gw, int batch) {
 // batched launches that are no stream call, where the launch supports the shapes (tail_head_lds_supported: the three stages' fused
 // partial sums, kTaps53 - the only list this schedule passes -, at most 240 cells), from four frames per launch on - the decoders' rule:
 // one frame alone is 21 blocks that each pay the chunk walk where tail_head_kernel's gathers are all in flight at once.  The two forms'
-// outputs are bitwise equal.  EEM_TAIL_HEAD_LDS (read per schedule build): 0 never, 1 wherever it is supported, unset: by batch.
+// outputs are bitwise equal.  EEM_TAIL_HEAD_LDS: 0 never, 1 wherever it is supported, unset: by batch.
 static bool tail_head_lds_wanted(const Shape& s, const TailHeadArgs& ha) {
-    const char* e = getenv("EEM_TAIL_HEAD_LDS");
+    const char* e = sw_raw<SW_EEM_TAIL_HEAD_LDS>();
     if (s.stream || !tail_head_lds_supported(ha) || (e && e[0] == '0')) return false;
     return (e && e[0] == '1') || s.batch >= 4;
 }
@@ -69,26 +42,24 @@ static bool tail_head_lds_wanted(const Shape& s, const TailHeadArgs& ha) {
 // The order in which a layer's blocks walk its tiles, its non-temporal stores and its grid under several frames in flight: the fields
 // reverse / nt_store / blocks_per_xcd of the layer's launch arguments
 static void enc_walk(const eemflow_ctx* c, const Shape& s, int layer, EncConvArgs& a) {
-    // batched chains (EEM_ZIGZAG=<layer mask>, experiment): this layer walks the images back to front
-    static const int zz = [] { const char* e = getenv("EEM_ZIGZAG"); return e ? atoi(e) : 0; }();
-    a.reverse = (s.enc_batch >= 2 && ((zz >> layer) & 1)) ? 1 : 0;
-    // ... or in COLUMNS (EEM_COLWALK=<layer mask>; default: the two 64-channel layers of a batched chain).  Measured at ten frames
+    a.reverse = 0;
+    // batched chains walk their tiles in COLUMNS (EEM_COLWALK=<layer mask>; default: the two 64-channel layers of a batched chain).  Measured at ten frames
     // per launch (rocprofv3 FETCH_SIZE): the 32-pixel-wide tiles of the 64-channel layers fetch 22.3 MB per frame in row order
     // and 10.8 / 10.3 in column order (a tile row touches three cache lines for one of payload, and in row order the neighbour
     // that shares two of them comes a whole tile later); 32 channels 29.0 -> 32.2 (worse), 16 channels unchanged; frame rate the
     // same within noise either way - those layers are bound by their transforms, not their bytes
-    static const int cw = [] { const char* e = getenv("EEM_COLWALK"); return e ? atoi(e) : (1 << ENC_3_2) | (1 << ENC_3_3); }();
+    static_assert(kSwitches[SW_EEM_COLWALK].dflt == ((1 << ENC_3_2) | (1 << ENC_3_3)), "switches.def.h: EEM_COLWALK's default");
+    const int cw = sw_int_once<SW_EEM_COLWALK>();
     if (s.enc_batch >= 2 && ((cw >> layer) & 1)) a.reverse = 2;
     // ... or INTERLEAVED (EEM_WALK3=<layer mask>, round 6): an XCD's blocks take every G-th tile of its range, so neighbouring
     // tiles are in flight together (conv_wino4.hip)
     // Measured at ten frames per launch (profiles/r06_walk3.txt): FETCH_SIZE per frame pconv1_2 49.5 -> 32.8 MB (31.5 of input),
     // pconv2_2 / 2_3 29.0 -> 17.0, pconv3_2 / 3_3 10.8 / 10.3 (column walk) -> 9.9 / 9.3; encoder 342 -> 299 MB per frame;
     // 10 290 -> 10 500 frames/s over 400 steps.  Default for every stride-1 layer of a batched chain (supersedes the column walk).
-    static const int w3 = [] { const char* e = getenv("EEM_WALK3");
-                               return e ? atoi(e) : (1 << ENC_1_2) | (1 << ENC_2_2) | (1 << ENC_2_3) | (1 << ENC_3_2) | (1 << ENC_3_3); }();
+    static_assert(kSwitches[SW_EEM_WALK3].dflt == ((1 << ENC_1_2) | (1 << ENC_2_2) | (1 << ENC_2_3) | (1 << ENC_3_2) | (1 << ENC_3_3)), "switches.def.h: EEM_WALK3's default");
+    const int w3 = sw_int_once<SW_EEM_WALK3>();
     if (s.enc_batch >= 2 && ((w3 >> layer) & 1)) a.reverse = 3;
-    static const int nts = [] { const char* e = getenv("EEM_NT_STORE"); return e ? atoi(e) : 0; }();
-    a.nt_store = ((nts >> layer) & 1) | ((nts >> 8) & 2);          // (bit 9, diagnostic builds: the weight-slice experiment of conv_wino4.hip)
+    a.nt_store = 0;
     // several frames in flight: kernels of different frames time-slice the CUs, so a block's prologue (DMA plan, first tile's
     // landing) is CU time another frame could use - fewer blocks with more tiles each (measured at 1280x720 with four in flight:
     // +3.5 % frames/s, +8 % single-frame latency; the 64-channel layers have one tile per CU and keep the full grid)
@@ -105,7 +76,7 @@ bool Hook::skipped(const char*) { return false; }
 #else
 bool Hook::skipped(const char* name) {
     static const std::string list = [] {
-        const char* e = getenv("EEM_SKIP_KERNELS");
+        const char* e = sw_raw_once<SW_EEM_SKIP_KERNELS>();
         if (e && e[0]) fprintf(stderr, "eemflow_hip: EEM_SKIP_KERNELS=\"%s\" is set - the launches it names are skipped and the flow is GARBAGE (diagnostic runs only)\n", e);
         return std::string(e ? e : "");
     }();
@@ -254,8 +225,7 @@ int run_decoders(eemflow_ctx* c, int k0, int k1, const float* const cat[3], int 
 
 static bool spans_on() {
 #ifdef EEM_DIAG
-    static const bool on = [] { const char* e = getenv("EEM_SPANS"); return e && e[0] == '1'; }();
-    return on;
+    return sw_on_once<SW_EEM_SPANS>();
 #else
     return false;                                        // EEM_SPANS is a diagnostic-build switch (-DEEM_DIAG)
 #endif
@@ -368,8 +338,7 @@ int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const
             if (s.fuse[k] && sp.layer == (k == 0 ? ENC_1_2 : k == 1 ? ENC_2_3 : ENC_3_3)) {
                 a.pool_partial = c->ppart[k].p;
                 a.pool_k = k == 0 ? 32 : k == 1 ? 16 : 8;
-                static const bool keep_f13 = [] { const char* e = getenv("EEM_KEEP_F13"); return e && e[0] == '1'; }();
-                if (k == 2 && may_skip_store && !keep_f13) a.no_store = 1;
+                if (k == 2 && may_skip_store) a.no_store = 1;
             }
         const double opix = (double)n2 * sp.hout * sp.wout;
         const double flops = 2.0 * opix * d.cout * d.cin * 9;
@@ -388,8 +357,7 @@ int run_enc12(eemflow_ctx* c, const Shape& s, const float* e1, const float* e2, 
     *done = false;
     // opt-in (EEM_FUSE12=1; read per schedule build - a cached graph keeps the form it was captured with): measured SLOWER than the two
     // launches it replaces, kept for the traffic it saves and as the record of that measurement
-    const char* eon = getenv("EEM_FUSE12");
-    const bool off = !(eon && eon[0] == '1');
+    const bool off = !sw_on<SW_EEM_FUSE12>();
     if (off || s.stream || c->deferred_norm || c->keep_stage_stores || c->enc0_generic || prepadded != nullptr || !c->use_wino || !c->enc_wino[ENC_1_2] ||
         !c->layer_f4(16, s.batch) || !s.fuse[0] || c->fuse_scratch.p == nullptr)
         return EEM_OK;
@@ -441,22 +409,19 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
         if ((rc = run_enc_layer(c, s, li, e1, e2, hk, io, prepadded, !c->keep_stage_stores)) != EEM_OK) return rc;
     c->f13_skipped = !c->keep_stage_stores;
     // ---- stage pooling to the common 1/64 grid (EEMFlow.py:144-154), 53-tap correlation and rconv into the decoders' input
-    // [cv | r] (EEMFlow.py:160-163).  Fused form (default): ONE launch whose correlation / rconv blocks read the conv epilogues'
+    // [cv | r] (EEMFlow.py:160-163).  ONE launch whose correlation / rconv blocks read the conv epilogues'
     // pooling partial sums directly and whose extra blocks write the finished pooled maps (tail_fused.hip).  Stages whose conv
-    // ran the generic kernel are pooled from the stored feature map first.  EEM_NO_TAIL_FUSE=1: the three separate launches.
+    // ran the generic kernel are pooled from the stored feature map first.
     const size_t g = (size_t)s.gh * s.gw;
     const int pc[3] = {16, 32, 64};
-    static const bool no_fuse = [] { const char* e = getenv("EEM_NO_TAIL_FUSE"); return e && e[0] == '1'; }();
     {
         const float* feat[3] = {c->f11.p, c->f12.p, c->f13.p};
         const int hs[3] = {s.h1, s.h2, s.h3}, ws[3] = {s.w1, s.w2, s.w3}, ks[3] = {32, 16, 8};
-        PoolFinJob fj[3];
         PoolJob pj[3];
-        int nf = 0, np = 0;
+        int np = 0;
         double fin_elems = 0, pool_elems = 0;
         for (int k = 0; k < 3; ++k) {
             if (s.fuse[k]) {
-                fj[nf++] = {c->ppart[k].p, c->pool[k].p, pc[k], s.prow[k], s.pcol[k], ks[k] / s.th[k], ks[k]};
                 fin_elems += (double)n2 * pc[k] * s.gh * s.gw * (ks[k] / s.th[k] + 1);
             } else {
                 pj[np++] = {feat[k], c->pool[k].p, pc[k], hs[k], ws[k], ks[k]};
@@ -483,7 +448,6 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
         if (s.stream) {
             // consecutive windows: pair b compares window b - 1 + i2_off with the next one; the carried window's finished maps stand in for
             // window -1, and the last window's finished maps become the next call's carry (the other slot: no launch reads what it writes)
-            EEM_REQUIRE(!no_fuse, "eemflow_forward_stream needs the fused tail head (EEM_NO_TAIL_FUSE is set)");
             TailHeadStreamArgs sa;
             memset(&sa, 0, sizeof(sa));
             TailHeadArgs& ha = sa.base;
@@ -508,7 +472,7 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
                         [&](hipStream_t st) { return tail_head_stream_launch(sa, kTaps53, st); });
             if (rc != EEM_OK) return rc;
             if (s.batch == 0) return EEM_OK;                 // a first call of one window: nothing to decode, the carry is written
-        } else if (!no_fuse) {
+        } else {
             TailHeadArgs ha;
             memset(&ha, 0, sizeof(ha));
             for (int k = 0; k < 3; ++k) {
@@ -526,32 +490,13 @@ int run_forward_impl(eemflow_ctx* c, const Shape& s, const float* e1, const floa
                 return lds_form ? tail_head_lds_launch(ha, kTaps53, st) : tail_head_launch(ha, kTaps53, st);
             });
             if (rc != EEM_OK) return rc;
-        } else {
-            if (nf) {
-                rc = hk.run("pool finalize (fused partials)", fin_elems, 4.0 * fin_elems, [&](hipStream_t st) {
-                    return pool_finalize_launch(fj, nf, n2, s.gh, s.gw, st);
-                });
-                if (rc != EEM_OK) return rc;
-            }
-            CorrJob cj[3];
-            for (int k = 0; k < 3; ++k)
-                cj[k] = {c->pool[k].p, c->pool[k].p + (size_t)s.batch * pc[k] * g, c->cat[k].p, pc[k], kDecIn};
-            rc = hk.run("local_corr 9x9 (53 taps)", 2.0 * s.batch * g * kNTaps * (16 + 32 + 64),
-                        4.0 * s.batch * g * (2.0 * (16 + 32 + 64) + 3.0 * kNTaps),
-                        [&](hipStream_t st) { return corr_launch(cj, 3, s.batch, s.gh, s.gw, c->taps, kNTaps, st); });
-            if (rc != EEM_OK) return rc;
-            TailConvLaunch L0;
-            L0.batch = s.batch; L0.h = s.gh; L0.w = s.gw; L0.ksize = 3; L0.njobs = 0;
-            for (int k = 0; k < 3; ++k)
-                L0.job[L0.njobs++] = make_job(c, c->rconv[k], c->pool[k].p, pc[k], 0, c->cat[k].p, kDecIn, kNTaps, 1, 1);
-            if ((rc = run_tail(hk, "rconv {16,32,64}->16", L0)) != EEM_OK) return rc;
         }
     }
     TailConvLaunch L;
     L.batch = s.batch; L.h = s.gh; L.w = s.gw; L.ksize = 3; L.njobs = 0;
     // ---- decoders, out_conv, upsample (EEMFlow.py:164-181)
     const float* cats[3] = {c->cat[0].p, c->cat[1].p, c->cat[2].p};
-    const bool fuse_up = !no_fuse && tail_up_supported(s.gh, s.gw, s.out_h, s.out_w);
+    const bool fuse_up = tail_up_supported(s.gh, s.gw, s.out_h, s.out_w);
     if ((rc = run_decoders(c, 0, 3, cats, s.batch, s.gh, s.gw, c->flowcat.p, 6, 0, hk)) != EEM_OK) return rc;
     if (fuse_up) {
         // out_conv + bilinear upsample in one launch; `coarse` is its side output

@@ -40,29 +40,6 @@ __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
     if (lane == 0) jb.out[((size_t)o * oh + oy) * ow + ox] = s / (float)kk;
 }
 
-struct PoolFinArgs {
-    PoolFinJob job[3];
-    int njobs, nimg, gh, gw;
-};
-
-__global__ __launch_bounds__(256) void pool_finalize_kernel(PoolFinArgs a) {
-    int idx = blockIdx.x * 256 + threadIdx.x;
-    const int g = a.gh * a.gw;
-    for (int ji = 0; ji < a.njobs; ++ji) {
-        const PoolFinJob jb = a.job[ji];
-        const int total = a.nimg * jb.c * g;
-        if (idx < total) {
-            const int gx = idx % a.gw, gy = (idx / a.gw) % a.gh, nc = idx / g;
-            const float* src = jb.partial + ((size_t)nc * jb.prows + (size_t)gy * jb.rows) * jb.pcols + gx;
-            float s = 0.f;
-            for (int i = 0; i < jb.rows; ++i) s += src[(size_t)i * jb.pcols];
-            jb.out[idx] = s / (float)(jb.k * jb.k);
-            return;
-        }
-        idx -= total;
-    }
-}
-
 // ------------------------------------------------------------------------------- local correlation
 struct CorrArgs {
     CorrJob job[3];
@@ -464,18 +441,6 @@ int pool_launch(const PoolJob* jobs, int njobs, int nimg, hipStream_t stream) {
     return EEM_OK;
 }
 
-int pool_finalize_launch(const PoolFinJob* jobs, int njobs, int nimg, int gh, int gw, hipStream_t stream) {
-    EEM_REQUIRE(njobs >= 1 && njobs <= 3, "pool_finalize_launch: njobs=%d", njobs);
-    PoolFinArgs a;
-    a.njobs = njobs; a.nimg = nimg; a.gh = gh; a.gw = gw;
-    int total = 0;
-    for (int i = 0; i < njobs; ++i) { a.job[i] = jobs[i]; total += nimg * jobs[i].c * gh * gw; }
-    if (total == 0) return EEM_OK;
-    hipLaunchKernelGGL(pool_finalize_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, stream, a);
-    EEM_HIP_CHECK(hipGetLastError());
-    return EEM_OK;
-}
-
 int corr_launch(const CorrJob* jobs, int njobs, int batch, int h, int w, const int* taps_dev, int ntaps,
                 hipStream_t stream) {
     EEM_REQUIRE(njobs >= 1 && njobs <= 3, "corr_launch: njobs=%d", njobs);
@@ -484,10 +449,9 @@ int corr_launch(const CorrJob* jobs, int njobs, int batch, int h, int w, const i
     a.njobs = njobs; a.batch = batch; a.h = h; a.w = w; a.ntaps = ntaps; a.taps = taps_dev;
     const long total = (long)njobs * batch * ntaps * h * w;
     if (total == 0) return EEM_OK;
-    static const bool plain = [] { const char* e = getenv("EEM_CORR_PLAIN"); return e && e[0] == '1'; }();
     bool c8 = true;
     for (int i = 0; i < njobs; ++i) c8 = c8 && jobs[i].c % 8 == 0;
-    if (!plain && ntaps == 53 && c8 && (long)h * w >= 8192) {                  // below: the tile's chain of eight chunks (~18 us whatever the map) loses to the direct kernel
+    if (ntaps == 53 && c8 && (long)h * w >= 8192) {                  // below: the tile's chain of eight chunks (~18 us whatever the map) loses to the direct kernel
         // (ntaps == 53 is EEMFlow's list, EEMFlow.py:14-23: every caller passes a device copy of that table - api.hip, plus_api.hip,
         // ops.hip - and the tiled kernel has it compiled in)
         const int tiles_x = ceil_div(w, 16);
@@ -548,34 +512,26 @@ int tail_conv_launch(const TailConvLaunch& l, hipStream_t stream) {
         return EEM_OK;
     }
     // narrow layers of a batched chain: five pixel tiles per block (tail_conv_multi_kernel; EEM_NO_TAIL_MULTI=1: the one-tile kernel)
-    // (EEM_TAIL_MULTI_MAXCG: the widest layer, in 4-channel groups, that takes it.  5 = the grouped convs: 19.2 -> 13.4 us per launch of
+    // (kMultiMaxCg: the widest layer, in 4-channel groups, that takes it.  5 = the grouped convs: 19.2 -> 13.4 us per launch of
     // ten frames; the wider layers with two or three tiles per block measured 25.1 -> 23.5 (conv1), 19.9 -> 21.7 (conv5), 3.7 -> 4.7 (conv7))
-    static const int multi_maxcg = [] { const char* e = getenv("EEM_TAIL_MULTI_MAXCG"); return e ? atoi(e) : 5; }();
-    bool multi_ok = l.ksize == 3 && max_cg <= multi_maxcg && ceil_div(l.h * l.w, 16) * l.batch >= 40;
+    constexpr int kMultiMaxCg = 5;
+    bool multi_ok = l.ksize == 3 && max_cg <= kMultiMaxCg && ceil_div(l.h * l.w, 16) * l.batch >= 40;
     for (int i = 0; i < l.njobs && multi_ok; ++i) {
         const TailConvJob& jb = l.job[i];
         const long span = ((long)(l.batch - 1) * jb.in_ctotal + jb.in_coff + (jb.cin - 1) * (jb.in_cmul > 1 ? jb.in_cmul : 1) + 1) * l.h * l.w * 4;
         multi_ok = jb.gate == nullptr && span < 0x7f000000L;
     }
-    { const char* e = getenv("EEM_NO_TAIL_MULTI"); if (e && e[0] == '1') multi_ok = false; }
+    if (sw_on<SW_EEM_NO_TAIL_MULTI>()) multi_ok = false;
     dim3 grid(ceil_div(l.h * l.w, 16) * l.batch, ceil_div(max_cout, 16), l.njobs);
     EEM_NOTE_GRID(grid.x * grid.y * grid.z, 64 * l.ksize * l.ksize);
     if (l.ksize == 1) {
         if (max_cg <= 2) tail_launch_t<1, 2>(l, grid, stream);
         else tail_launch_t<1, 25>(l, grid, stream);
     } else if (multi_ok) {
-        auto go = [&](auto cg_tag, auto pt_tag) {
-            constexpr int CG = decltype(cg_tag)::value, PT = decltype(pt_tag)::value;
-            dim3 gm(ceil_div((int)grid.x, PT), grid.y, grid.z);
-            EEM_NOTE_GRID(gm.x * gm.y * gm.z, 576);
-            hipLaunchKernelGGL((tail_conv_multi_kernel<CG, PT>), gm, dim3(576), 0, stream, l);
-        };
-        using std::integral_constant;
-        if (max_cg <= 5) go(integral_constant<int, 5>{}, integral_constant<int, 5>{});
-        else if (max_cg <= 8) go(integral_constant<int, 8>{}, integral_constant<int, 3>{});
-        else if (max_cg <= 16) go(integral_constant<int, 16>{}, integral_constant<int, 2>{});
-        else if (max_cg <= 18) go(integral_constant<int, 18>{}, integral_constant<int, 2>{});
-        else go(integral_constant<int, 25>{}, integral_constant<int, 2>{});
+        constexpr int PT = 5;                                          // pixel tiles per block
+        dim3 gm(ceil_div((int)grid.x, PT), grid.y, grid.z);
+        EEM_NOTE_GRID(gm.x * gm.y * gm.z, 576);
+        hipLaunchKernelGGL((tail_conv_multi_kernel<kMultiMaxCg, PT>), gm, dim3(576), 0, stream, l);
     } else if (max_cg <= 5) tail_launch_t<3, 5>(l, grid, stream);
     else if (max_cg <= 8) tail_launch_t<3, 8>(l, grid, stream);
     else if (max_cg <= 16) tail_launch_t<3, 16>(l, grid, stream);
@@ -608,8 +564,8 @@ static __global__ void spin_code_kernel(long ticks) {            // the same wai
 }
 
 int spin_launch(float us, hipStream_t stream) {
-    static const int blocks = [] { const char* e = getenv("EEM_SKIP_SPIN_BLOCKS"); return e ? atoi(e) : 1; }();    // x 576 threads
-    static const bool code = [] { const char* e = getenv("EEM_SKIP_SPIN_CODE"); return e && e[0] == '1'; }();
+    const int blocks = sw_int_once<SW_EEM_SKIP_SPIN_BLOCKS>();    // x 576 threads
+    const bool code = sw_on_once<SW_EEM_SKIP_SPIN_CODE>();
     const long ticks = (long)(us * 100.f);
     const dim3 g(blocks), b(blocks > 1 ? 576 : 64);
     if (code) hipLaunchKernelGGL(spin_code_kernel, g, b, 0, stream, ticks);

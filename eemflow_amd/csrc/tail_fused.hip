@@ -1,7 +1,7 @@
 // Two fused launches of EEMFlow's 1/64-grid tail (EEMFlow.py:144-181).  The tail is latency-bound: 13 launches of 3-8 us
 // each for 0.3 GFLOP, every one paying a kernel boundary plus a memory round trip.  These two take five of them away:
 //
-//   tail_head_kernel   stage pooling finish + 9x9 local correlation (53 taps) + rconv_k   (was: pool_finalize, corr, rconv)
+//   tail_head_kernel   stage pooling finish + 9x9 local correlation (53 taps) + rconv_k   (once three launches: pool finalize, corr, rconv)
 //       Nothing in it waits for anything else in it: the correlation and the rconv input gathers read the conv epilogues'
 //       pooling PARTIAL sums directly (2-4 loads per pooled value, all in flight) instead of a finished pooled map; the
 //       pooled maps themselves are still written, by extra blocks of the same launch (parity tests and the training

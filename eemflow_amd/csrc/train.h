@@ -53,7 +53,7 @@ int wgrad_enc_launch(const WgradArgs& a, hipStream_t st);
 bool wgrad_wide_supported(const WgradArgs& a);
 int wgrad_wide_launch(const WgradArgs& a, hipStream_t st);
 // round 6: the same jobs on LDS rings that run ahead of the MFMAs (wgrad_ring.hip: one 8-wave block per CU walks a run of output rows,
-// G staged once for up to 64 input channels); EEM_NO_WGRAD_RING=1 (read per call) keeps the kernels above
+// G staged once for up to 64 input channels); EEM_NO_WGRAD_RING=1 keeps the kernels above
 bool wgrad_ring_supported(const WgradArgs& a);            // 3x3 (stride 1 / 2), 1x5, 5x1 (stride 1); cin, cout >= 16; honours kh / kw / dw_cin / dw_coff
 int wgrad_ring_launch(const WgradArgs& a, hipStream_t st);
 bool wgrad_ring_preferred(const WgradArgs& a);            // the shapes where it is the faster kernel (measured; EEM_WGRAD_RING=all / none)

@@ -502,8 +502,7 @@ int tr_loss_launch(const float* flow, const float* gt, const float* valid, float
 }
 
 int tr_upsample_bwd_launch(const float* d, float* tmp, float* out, int nc, int oh, int ow, int h, int w, hipStream_t st) {
-    const char* ex = getenv("EEM_UPBWD_THREADS");                     // (=1, read per call: the thread-per-target form, for the equality test)
-    const bool rows = ow >= 64 && ow <= 8192 && !(ex && ex[0] == '1');
+    const bool rows = ow >= 64 && ow <= 8192 && !sw_on<SW_EEM_UPBWD_THREADS>();     // (=1: the thread-per-target form, for the equality test)
     tr_last_form = rows ? "rows" : "threads";
     if (rows)
         hipLaunchKernelGGL(upbwd_x_rows_kernel, dim3((unsigned)(((long)nc * oh + 3) / 4)), dim3(256), 4 * ow * sizeof(float), st, d, tmp, (long)nc * oh, ow, w);
@@ -597,8 +596,7 @@ int tr_wgrad_launch_batch(const WgradArgs* jobs, int njobs, hipStream_t st) {
     {
         const WgradArgs& a0 = jobs[0];
         const int hw0 = a0.hout * a0.wout;
-        const char* es = getenv("EEM_NO_WGRAD_SMALL");
-        bool small = !(es && es[0] == '1') && a0.kh == 0 && a0.dw_cin == 0 && a0.stride == 1 && hw0 * 2 <= WG_PX && a0.hin == a0.hout && a0.win == a0.wout;
+        bool small = !sw_on<SW_EEM_NO_WGRAD_SMALL>() && a0.kh == 0 && a0.dw_cin == 0 && a0.stride == 1 && hw0 * 2 <= WG_PX && a0.hin == a0.hout && a0.win == a0.wout;
         for (int i = 1; i < njobs; ++i)
             small = small && jobs[i].hout == a0.hout && jobs[i].wout == a0.wout && jobs[i].n == a0.n && jobs[i].hin == a0.hin &&
                     jobs[i].win == a0.win;
@@ -723,8 +721,7 @@ __global__ __launch_bounds__(256) void wgrad_few_kernel(WgradArgs a, int per_blo
 }
 
 bool wgrad_few_supported(const WgradArgs& a) {
-    const char* e = getenv("EEM_NO_WGRAD_FEW");                       // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_WGRAD_FEW>()) return false;
     const int kh = a.kh ? a.kh : a.k, kw = a.kh ? a.kw : a.k, ph = a.kh ? a.ph : a.pad, pw = a.kh ? a.pw : a.pad;
     return kh == 3 && kw == 3 && ph == 1 && pw == 1 && a.stride == 1 && a.cout >= 1 && a.cout <= 8 && a.gate == nullptr && a.g_cmul == 1 &&
            a.nxseg == 0 && a.hin == a.hout && a.win == a.wout;

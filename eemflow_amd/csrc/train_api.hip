@@ -12,12 +12,10 @@ namespace {
 
 typedef eemflow_ctx::ConvRef ConvRef;
 
-// The context's side stream (weight gradients; the prologue of a training forward), or `st` itself under EEM_NO_WGRAD_STREAM=1 (read per
-// call: the tests run both forms)
+// The context's side stream (weight gradients; the prologue of a training forward), or `st` itself under EEM_NO_WGRAD_STREAM=1
 int side_stream(eemflow_ctx* c, hipStream_t st, hipStream_t* out) {
-    const char* off = getenv("EEM_NO_WGRAD_STREAM");
     *out = st;
-    if (off && off[0] == '1') return EEM_OK;
+    if (sw_on<SW_EEM_NO_WGRAD_STREAM>()) return EEM_OK;
     if (!c->wstream) {
         EEM_HIP_CHECK(hipStreamCreateWithFlags(&c->wstream, hipStreamNonBlocking));
         for (hipEvent_t& e : c->wev) EEM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -250,7 +248,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
     };
     TL.njobs = 0;
     {
-        // one launch for the tail's 3x3 weight gradients when the map fits a K part (wgrad_tail.hip; EEM_NO_WGRAD_TAIL=1, read per call)
+        // one launch for the tail's 3x3 weight gradients when the map fits a K part (wgrad_tail.hip; EEM_NO_WGRAD_TAIL=1)
         WgradArgs probe;
         probe.k = 3; probe.kh = 0; probe.stride = 1; probe.pad = 1; probe.hin = probe.hout = gh; probe.win = probe.wout = gw; probe.n = B;
         probe.cin = probe.cout = 16;
@@ -340,7 +338,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
         if (!l.gx) {
             // the first layer has no data gradient: its weight gradient follows the chain on st, where its operand was produced, and runs
             // beside pconv1_2's on the side stream instead of behind it (EEM_WGRAD_LAST_SIDE=1: the round-5 order, for measurements)
-            static const bool side = [] { const char* e = getenv("EEM_WGRAD_LAST_SIDE"); return e && e[0] == '1'; }();
+            const bool side = sw_on_once<SW_EEM_WGRAD_LAST_SIDE>();
             hipStream_t keep = bw.wst;
             if (!side) bw.wst = st;
             rc = bw.wgrad(kEncNames[l.layer], r, l.x, l.xc, 0, l.gy, nullptr, r.cout, 0, 1, n2, l.hin, l.win, l.hout, l.wout);
@@ -364,7 +362,7 @@ static int backward_chain(eemflow_ctx* c, const Shape& s, const float* e1, const
             a.act = 0;
             a.gate = l.x;                                        // -> gradient w.r.t. the previous conv's pre-activation
             {   // (the interleaved tile walk of the batched forward chains, schedule.hip enc_walk; EEM_WALK3_TRAIN=0 keeps the contiguous ranges)
-                static const bool w3 = [] { const char* e = getenv("EEM_WALK3_TRAIN"); return !(e && e[0] == '0'); }();
+                const bool w3 = sw_not0_once<SW_EEM_WALK3_TRAIN>();
                 if (w3 && n2 >= 4) a.reverse = 3;
             }
             if ((rc = enc_conv_launch(r.cout, r.cin, 1, a, st)) != EEM_OK) return rc;
@@ -429,7 +427,7 @@ static int forward_train_impl(eemflow_ctx* c, const float* e1, const float* e2, 
     // chain.  EEM_TRAIN_SIDE_PREP=0 keeps them on st (measurements).
     hipStream_t wst;
     if ((rc = side_stream(c, st, &wst)) != EEM_OK) return rc;
-    static const bool side_prep = [] { const char* e = getenv("EEM_TRAIN_SIDE_PREP"); return !(e && e[0] == '0'); }();
+    const bool side_prep = sw_not0_once<SW_EEM_TRAIN_SIDE_PREP>();
     if (wst != st && side_prep) {
         hipEvent_t e = c->wev[c->wev_next++ % eemflow_ctx::kWEvents];
         EEM_HIP_CHECK(hipEventRecord(e, st));                 // (behind the previous step: its backward read these weight forms, its optimizer the gradient)
@@ -455,7 +453,7 @@ static int forward_train_impl(eemflow_ctx* c, const float* e1, const float* e2, 
     }
     Hook hk;
     hk.st = st;
-    static const bool no_prepad = [] { const char* e = getenv("EEM_NO_PREPAD_FWD"); return e && e[0] == '1'; }();
+    const bool no_prepad = sw_on_once<SW_EEM_NO_PREPAD_FWD>();
     c->keep_stage_stores = true;                          // the backward pass reads every activation, f13 included
     rc = run_forward(c, s, e1, e2, flow_out, hk, nullptr, no_prepad ? nullptr : c->padded.p);
     c->keep_stage_stores = false;
@@ -529,9 +527,8 @@ extern "C" int eemflow_forward_backward(eemflow_ctx* c, const float* e1, const f
     // kernel (an event), while the backward runs - eemflow_train_stats_wait then returns as soon as the host has enqueued the optimizer
     // step, and the next step's launches queue up behind a GPU that is still busy (round 5: the copy sat behind the whole backward, the
     // host woke up when the GPU was already idle, and ~100 us per step passed before the next forward's first launch).
-    // EEM_TRAIN_LATE_STATS=1 (read per call) keeps round 5's order.
-    const char* late = getenv("EEM_TRAIN_LATE_STATS");
-    if (!stats_out && !(late && late[0] == '1')) {
+    // EEM_TRAIN_LATE_STATS=1 keeps round 5's order.
+    if (!stats_out && !sw_on<SW_EEM_TRAIN_LATE_STATS>()) {
         if (!c->stats_host) {
             EEM_HIP_CHECK(hipHostMalloc((void**)&c->stats_host, 8 * sizeof(double), hipHostMallocDefault));
             EEM_HIP_CHECK(hipEventCreateWithFlags(&c->stats_ev, hipEventDisableTiming));

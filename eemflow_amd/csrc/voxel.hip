@@ -553,11 +553,11 @@ void launch_bin(const VoxJobs& jobs, int njobs, long nblk_max, int bins, int h, 
 bool make_plan(int64_t n, int bins, int h, int w, const double* events, VoxPlan* pl, int* lds_bytes) {
     const long hw = (long)h * w;
     if (bins > 64 || vox_blocks(n, 8) > VOX_MAX_BLOCKS || hw >= (1L << 31) || ((uintptr_t)events & 15)) return false;
-    const char* e = getenv("EEM_VOX_DIRECT");
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_VOX_DIRECT>()) return false;
     // 9216 fp64 cells (72 KB) per band by default -> vox_band_kernel<1024>, two blocks per CU; EEM_VOX_BAND_FLOATS=<cells> picks another
     // band size (<= 3072 cells: 256-thread blocks, <= 5120: 512) - 2304 .. 18432 cells measure the same within 3 % at 2e5 and 2e6 events
-    static const long band_floats = [] { const char* b = getenv("EEM_VOX_BAND_FLOATS"); const long v = b ? atol(b) : 0; return v >= 256 ? v : 9216L; }();
+    const long band_env = sw_long_once<SW_EEM_VOX_BAND_FLOATS>();
+    const long band_floats = band_env >= 256 ? band_env : 9216L;
     long band_px = (band_floats / bins) & ~3L;
     if (band_px < 64) band_px = 64;
     const long spread = ((hw + 511) / 512 + 3) & ~3L;              // small images: still a few hundred bands
@@ -615,10 +615,7 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
     VoxJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     if (planned) {
-        static const int ept_env = [] { const char* e = getenv("EEM_VOX_EPT"); return e ? atoi(e) : 0; }();
-        int ept = ept_env;
-        if ((ept != 1 && ept != 2 && ept != 4 && ept != 8) || vox_blocks((long)nmax, ept) > std::max(512L, vox_blocks((long)nmax, 8) + 1))
-            ept = vox_ept((long)nmax);                                 // the run table is sized for these block counts
+        const int ept = vox_ept((long)nmax);                           // the run table is sized for these block counts
         // one EPT for both jobs (the longer set's): the shorter one's slabs are the same size, it just fills fewer of them
         long nblk_max = 0;
         for (int k = 0; k < njobs; ++k) {
@@ -652,15 +649,13 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
         const int vec4 = (pl.band_px % 4 == 0 && pl.hw % 4 == 0 && aligned) ? 1 : 0;
         // Few events per voxel: accumulating the bands twice (16 B per vote from L2 / HBM each time) is cheaper than the normalisation's
         // read + write of the whole grid - a moments-only launch, then a launch that stores the bands already normalised
-        const char* tp = getenv("EEM_VOX_TWOPASS");                  // read per call: the tests run both forms in one process
-        const long two_pass_ratio = tp ? atol(tp) : 0L;
-        // lanes per run: the smallest power of two >= EEM_VOX_RUN_LANES_X10 / 10 (default 4.0 for sparse sets, else 1.7 - the rule through round 5) x the mean run length
+        const long two_pass_ratio = sw_long<SW_EEM_VOX_TWOPASS>();   // (the tests run both forms in one process)
+        // lanes per run: the smallest power of two >= 4.0 for sparse sets, else 1.7 (the rule through round 5), x the mean run length
         // (slab events / bands), 4 .. 64: a run longer than its lanes costs its block a dependent round trip in the clean-up loop, and with
         // 196 runs of mean length 2 per band and four lanes each nearly every block had one (stamps: 3 700 cycles in the adds)
         // (sparse sets only - mean run below 4 records: at 2e6 events per grid the wider runs idle more lanes than they save, 53.0 against
         // 50.6 us per sample)
-        static const long lanes_env = [] { const char* e = getenv("EEM_VOX_RUN_LANES_X10"); const long v = e ? atol(e) : 0; return v >= 10 ? v : 0L; }();
-        const long lanes_x10 = lanes_env ? lanes_env : ((long)VT * ept < 4L * pl.nb ? 40L : 17L);
+        const long lanes_x10 = (long)VT * ept < 4L * pl.nb ? 40L : 17L;
         int sgs = 2;
         while (sgs < 6 && (1 << sgs) * 10L * pl.nb < lanes_x10 * VT * ept) ++sgs;
         auto band = [&](int with_moments, int mode) {

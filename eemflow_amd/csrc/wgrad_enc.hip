@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void wgrad_enc_kernel(WgradArgs a, int tiles_x
 
     // tiles: an XCD owns a contiguous range; its resident blocks take every gb-th tile of it (interleaved, round 6: the tiles whose halo
     // rows / columns overlap are then in flight together and meet in the XCD's L2 - this kernel is bound by its operands' way in since its
-    // products run as bf16 pieces).  An EXPERIMENT (EEM_WGRAD_WALK=1): measured at no difference; default each block a contiguous sub-range
+    // products run as bf16 pieces).  An EXPERIMENT (flags bit 0, which the launcher leaves clear): measured at no difference; default each block a contiguous sub-range
     TileRange tr_ = block_tile_range(tiles_x * tiles_y * a.n, blockIdx.x, gridDim.x);
     int walk_stride = 1;
     if (walk) {
@@ -375,7 +375,7 @@ int launch(const WgradArgs& a, hipStream_t st) {
     const int need = (ceil_div(T, 8)) * 8;
     if (gx > need) gx = need;
 #ifdef EEM_DIAG
-    { static int once = [] { const char* e = getenv("EEM_WG_DBG"); int v = e ? atoi(e) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg_dbg), &v, sizeof v); return v; }(); (void)once; }
+    { static int once = [] { int v = sw_int<SW_EEM_WG_DBG>(); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg_dbg), &v, sizeof v); return v; }(); (void)once; }
 #endif
     static bool raised = false;
     if (!raised) {
@@ -383,19 +383,16 @@ int launch(const WgradArgs& a, hipStream_t st) {
                                           160 * 1024));
         raised = true;
     }
-    static const int walk = [] { const char* e = getenv("EEM_WGRAD_WALK"); return e ? atoi(e) : 0; }();     // (measured: no difference, profiles/r06_wgwalk.txt - its operands come out of L2 / MALL either way)
-    const char* eb = getenv("EEM_WGRAD_BURST");                 // (=1, read per call: a tile's requests in one block behind the barrier, the form through round 6's first half)
-    const int flags = (walk & 1) | ((eb && eb[0] == '1') ? 2 : 0);
+    // bit 0, the other tile walk, stays clear (measured: no difference, profiles/r06_wgwalk.txt - its operands come out of L2 / MALL either way);
+    // bit 1 (EEM_WGRAD_BURST=1): a tile's requests in one block behind the barrier, the form through round 6's first half
+    const int flags = sw_on<SW_EEM_WGRAD_BURST>() ? 2 : 0;
     hipLaunchKernelGGL((wgrad_enc_kernel<MT, S, TW, CP, KH, KW, BX>), dim3(gx, chunks, cochunks), dim3(256), lds_bytes, st, a, tiles_x, tiles_y, flags);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
-// EEM_NO_WGRAD_BX3=1 (read per call): the fp32 MFMA form of every launch
-static bool use_bx3() {
-    const char* e = getenv("EEM_NO_WGRAD_BX3");
-    return !(e && e[0] == '1');
-}
+// EEM_NO_WGRAD_BX3=1: the fp32 MFMA form of every launch
+static bool use_bx3() { return !sw_on<SW_EEM_NO_WGRAD_BX3>(); }
 
 // stride-1 layers of any width with 3x3, 1x5, 5x1 or 1x1 filters (E-RAFT's residual stacks, update block and heads): 64-cout chunks
 template <int KH, int KW>
@@ -413,7 +410,7 @@ int launch_wide(const WgradArgs& a, hipStream_t st) {
 
 template <int MT, int S>
 int launch_tw(const WgradArgs& a, hipStream_t st) {
-    static const bool mt1 = [] { const char* e = getenv("EEM_WGRAD_BX3_MT1"); return e && e[0] == '1'; }();     // (measurement)
+    static const bool mt1 = sw_on<SW_EEM_WGRAD_BX3_MT1>();     // (measurement)
     const bool tw32 = a.wout % 32 == 0 || a.wout >= 256;
     if ((MT >= 2 || mt1) && use_bx3()) {                             // (one 16-cout tile per wave: the splits cost what the multiplies save)
         tr_last_form = tw32 ? "enc_bx3_tw32" : "enc_bx3_tw16";
@@ -428,8 +425,7 @@ int launch_tw(const WgradArgs& a, hipStream_t st) {
 }  // namespace
 
 bool wgrad_enc_supported(const WgradArgs& a) {
-    const char* e = getenv("EEM_NO_WGRAD_ENC");                      // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_WGRAD_ENC>()) return false;
     return a.zero_page && a.gate == nullptr && a.k == 3 && a.pad == 1 && (a.stride == 1 || a.stride == 2) &&
            (a.cout == 16 || a.cout == 32 || a.cout == 64) && a.g_cmul == 1 && (a.cin <= 16 || a.cin % 16 == 0) &&
            a.wout % 4 == 0 && a.win % 4 == 0 && ((uintptr_t)a.g & 15) == 0 && ((uintptr_t)a.x & 15) == 0 &&
@@ -439,8 +435,7 @@ bool wgrad_enc_supported(const WgradArgs& a) {
 
 // a.kh / a.kw (0: a.k), a.ph / a.pw, a.dw_cin / a.dw_coff as in train.h
 bool wgrad_wide_supported(const WgradArgs& a) {
-    const char* e = getenv("EEM_NO_WGRAD_WIDE");                     // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_WGRAD_WIDE>()) return false;
     const int kh = a.kh ? a.kh : a.k, kw = a.kh ? a.kw : a.k;
     const int ph = a.kh ? a.ph : a.pad, pw = a.kh ? a.pw : a.pad;
     const bool shape = (kh == 3 && kw == 3) || (kh == 1 && kw == 5) || (kh == 5 && kw == 1) || (kh == 1 && kw == 1);

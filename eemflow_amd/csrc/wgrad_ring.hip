@@ -455,7 +455,7 @@ int launch_ring(const WgradArgs& a, hipStream_t st) {
         return EEM_ERR_ARG;
     }
 #ifdef EEM_DIAG
-    { static int once = [] { const char* e = getenv("EEM_WG_DBG"); int v = e ? atoi(e) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wr_dbg), &v, sizeof v); return v; }(); (void)once; }
+    { static int once = [] { int v = sw_int<SW_EEM_WG_DBG>(); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wr_dbg), &v, sizeof v); return v; }(); (void)once; }
 #endif
     static bool raised = false;
     if (!raised) {
@@ -479,8 +479,7 @@ using Cfg64x32r51 = RingCfg<4, 2, 1, 5, 1, 2, 2, 2, 96>;     // ... (5, 1) with 
 using Cfg64x64s2 = RingCfg<4, 4, 2, 3, 3, 2, 2, 1, 48>;      // the encoders' downsampling convs (model/extractor.py layer2 / layer3)
 
 bool common_ok(const WgradArgs& a) {
-    const char* e = getenv("EEM_NO_WGRAD_RING");                      // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_WGRAD_RING>()) return false;
     if (a.nxseg > 0) {
         for (int sgi = 0; sgi < a.nxseg; ++sgi)
             if (!a.xs[sgi] || ((uintptr_t)a.xs[sgi] & 15) || a.xsc[sgi] < 1) return false;
@@ -511,9 +510,9 @@ bool wgrad_ring_supported(const WgradArgs& a) {
 // heads, 34 against 50 at a GRU conv's input segment - and in the E-RAFT step (81.4 ms against 82.7 with every wide layer on the rings);
 // against the tile kernel's fp32 form the rings had won that step (89.5 against 93.8 ms).  What the rings buy - a third of the staged
 // bytes per product - is what the bf16-piece multiply would need next: that kernel is now bound by its operands' way in.
-// EEM_WGRAD_RING=all / none overrides (read per call).
+// EEM_WGRAD_RING=all / none overrides.
 bool wgrad_ring_preferred(const WgradArgs& a) {
-    if (const char* e = getenv("EEM_WGRAD_RING")) {
+    if (const char* e = sw_raw<SW_EEM_WGRAD_RING>()) {
         if (e[0] == 'a') return true;
         if (e[0] == 'n') return false;
     }
@@ -522,8 +521,8 @@ bool wgrad_ring_preferred(const WgradArgs& a) {
 
 int wgrad_ring_launch(const WgradArgs& a, hipStream_t st) {
     const int kh = a.kh ? a.kh : a.k;
-    // EEM_WGRAD_RING_BLOCK=<couts><cins> (read per call; measurement): the block extent of stride-1 3x3 layers - 6464, 3232 or 1616
-    if (const char* e = getenv("EEM_WGRAD_RING_BLOCK")) {
+    // EEM_WGRAD_RING_BLOCK=<couts><cins> (measurement): the block extent of stride-1 3x3 layers - 6464, 3232 or 1616
+    if (const char* e = sw_raw<SW_EEM_WGRAD_RING_BLOCK>()) {
         const int v = atoi(e);
         if (a.stride == 1 && kh == 3 && (a.kh ? a.kw : a.k) == 3) {
             if (v == 6464) { tr_last_form = "ring_6464"; return launch_ring<Cfg64x64>(a, st); }
@@ -538,8 +537,7 @@ int wgrad_ring_launch(const WgradArgs& a, hipStream_t st) {
         return launch_ring<Cfg64x64s2>(a, st);
     }
     if (kh == 5) {
-        const char* e = getenv("EEM_WGRAD_RING_51");                 // (measurement: 6464 = 64 input channels per block, strips of <= 64)
-        const bool c64 = (e && atoi(e) == 6464) || a.wout <= 64;
+        const bool c64 = sw_int<SW_EEM_WGRAD_RING_51>() == 6464 || a.wout <= 64;   // (measurement: 6464 = 64 input channels per block, strips of <= 64)
         tr_last_form = c64 ? "ring_wide_5x1_6464" : "ring_wide_5x1_6432";
         return c64 ? launch_ring<Cfg64x64r51>(a, st) : launch_ring<Cfg64x32r51>(a, st);
     }

@@ -173,8 +173,7 @@ thread_local TailCache g_tail_cache[4];              // a few contexts per threa
 }  // namespace
 
 bool wgrad_tail_supported(const WgradArgs* jobs, int njobs, int n, int h, int w) {
-    const char* e = getenv("EEM_NO_WGRAD_TAIL");                      // read per call: a test flips it inside one process
-    if (e && e[0] == '1') return false;
+    if (sw_on<SW_EEM_NO_WGRAD_TAIL>()) return false;
     if (njobs < 1 || njobs > 30000 || h * w > TW_MAXPX || n < 1) return false;
     for (int i = 0; i < njobs; ++i) {
         const WgradArgs& a = jobs[i];
@@ -239,7 +238,7 @@ int wgrad_tail_launch(const WgradArgs* jobs, int njobs, int n, int h, int w, hip
         EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised = true;
     }
-    static const int dbg = [] { const char* e = getenv("EEM_TW_DBG"); return e ? atoi(e) : 0; }();     // measurement: 1 no atomics, 2 no k-loop, 4 no G staging
+    const int dbg = sw_int_once<SW_EEM_TW_DBG>();    // measurement: 1 no atomics, 2 no k-loop, 4 no G staging
     tr_last_form = "wgrad_tail";
     hipLaunchKernelGGL(wgrad_tail_kernel, dim3((unsigned)hb.size()), dim3(256), lds_bytes, st, tc->djobs, tc->dblocks, n, h, w, ipt, gp, dbg);
     EEM_HIP_CHECK(hipGetLastError());

@@ -37,6 +37,8 @@ size_t wnc_packed_floats(int cin, int m16);
 void wnc_pack(const float* w, int cout, int cin, int co0, int m16, float* packed);
 bool wnc_supported(const WncArgs& a);
 int wnc_launch(const WncArgs& a, hipStream_t st);
+// wnc_launch's choice of block tile: maps below EEM_WNC_SMALL_MAXPX cells take 4 x 32 (two blocks per CU), the others 4 x 64
+inline bool wnc_small_map(int h, int w) { return (long)h * w < sw_long<SW_EEM_WNC_SMALL_MAXPX>(); }
 
 // The same packing on the device, for weights that change there (a training step, eemflow_update_weights): job j writes wnc_pack(w, cout,
 // cin, co0, m16)'s stream to `packed` - the very expression, shared with the host function - and the slice's 32 (m16: 16) biases, zero

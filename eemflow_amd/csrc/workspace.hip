@@ -191,8 +191,7 @@ int alloc_workspace_raw(eemflow_ctx* c, const Shape& s) {
     ENS(c->flowcat, B * 6 * g);  ENS(c->coarse, B * 2 * g);
     if (c->enc0_generic) { ENS(c->padded, n2 * c->cin0 * (size_t)s.hp * s.wp); }
     else {                                                   // block scratch of the OPT-IN fused first two layers only (41 MB)
-        const char* eon = getenv("EEM_FUSE12");
-        if (eon && eon[0] == '1') { ENS(c->fuse_scratch, enc12_scratch_floats(256)); }
+        if (sw_on<SW_EEM_FUSE12>()) { ENS(c->fuse_scratch, enc12_scratch_floats(256)); }
     }
 #undef ENS
     return EEM_OK;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of an environment switch on the bench (GPU box): tools/ab.sh <tag> VAR  -> bench lines with VAR unset / VAR=1
-tag=${1:-ab}; var=${2:-EEM_NO_STAGGER}
+tag=${1:-ab}; var=${2:?usage: tools/ab.sh <tag> VAR}
 out=gpurun_out/$tag; mkdir -p $out
 for v in "" 1; do
   if [ -z "$v" ]; then unset $var; n=default; else export $var=$v; n=${var}_$v; fi
