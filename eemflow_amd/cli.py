@@ -66,6 +66,15 @@ def build_parser():
                                 'un-augmented dataset)')
             q.add_argument('--self_supervised', action='store_true',
                            help='with --contrast_weight: train on the contrast term alone, the ground-truth flow is not read')
+            q.add_argument('--smooth_weight', default=0.0, type=float, metavar='W',
+                           help='add W times the edge-aware smoothness of the last prediction, weighted by the edges of the old event '
+                                'volume, to the loss (Loss_tools.edge_aware_smoothness_order1/2 of the reference; every model then '
+                                'trains through the autograd engine; a mesh-size prediction is regularised unweighted)')
+            q.add_argument('--smooth_order', default=1, type=int, choices=(1, 2), help='with --smooth_weight: first or second differences')
+            q.add_argument('--smooth_constant', default=1.0, type=float, metavar='A', help='with --smooth_weight: the factor on the image differences')
+            q.add_argument('--smooth_weight_type', default='gauss', choices=('gauss', 'exp'), help='with --smooth_weight: exp(-mean g^2) or exp(-mean |g|)')
+            q.add_argument('--smooth_error', default='L1', choices=('L1', 'abs_robust'), help='with --smooth_weight: |d| or (|d| + 0.01)^0.4')
+            q.add_argument('--smooth_all', action='store_true', help='with --smooth_weight: all predictions under the sequence loss\'s gamma, not the last alone')
         q.add_argument('--device_events', action='store_true',
                        help='prepare the event sets on the GPU from the npz columns (HREM datasets: the columns are uploaded in their file '
                             'dtypes and one launch per sample writes the float64 event tables; the same samples bit for bit, a set whose '
@@ -154,6 +163,13 @@ def device_events_kw(args, dataset_class):
     return {"device_events": True}
 
 
+def smooth_kw(args):
+    """TrainRaftEvents' smoothness arguments of the --smooth_* flags."""
+    return dict(smooth_weight=float(getattr(args, "smooth_weight", 0.0)), smooth_order=int(getattr(args, "smooth_order", 1)),
+                smooth_constant=float(getattr(args, "smooth_constant", 1.0)), smooth_weight_type=getattr(args, "smooth_weight_type", "gauss"),
+                smooth_error=getattr(args, "smooth_error", "L1"), smooth_all=bool(getattr(args, "smooth_all", False)))
+
+
 def train(args):
     from . import harness, parallel
     from .hrem import HREMEventFlow
@@ -216,11 +232,12 @@ def train(args):
     # HREM training samples here are the un-cropped frames, so the padder is sized from the first batch itself (image_size=None).
     # EEMFlow: the fused step inside the library; E-RAFT / EEMFlow+: the reference's statement sequence over the operator-level
     # autograd route (their data-parallel exchange is the flat-gradient all-reduce in TrainRaftEvents._train_iters_autograd)
-    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 else "autograd"     # (the fused trainer has no contrast term)
+    smooth = float(getattr(args, "smooth_weight", 0.0))
+    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has neither term)
     tr = harness.TrainRaftEvents(loader, None, lr=tcfg["lr"], wdecay=tcfg["wdecay"], epsilon=tcfg["epsilon"],
                                  num_steps=tcfg["num_steps"], clip=tcfg["clip"], gamma=tcfg["gamma"], logger=logger,
                                  start_iteration=start_iteration, engine=engine, mixed_precision=tcfg.get("mixed_precision", True),
-                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False))
+                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args))
     for epoch in range(start_epoch, max(args.train_iters // args.val_iters, 1)):
         if sampler is not None:
             sampler.set_epoch(epoch)

@@ -27,7 +27,7 @@ import torch
 
 from .metrics import flow_error, flow_error_from_sums, flow_error_sums, flow_error_sums_many
 from . import parallel
-from .train import EEMFlowTrainer, contrast_loss, sequence_loss
+from .train import EEMFlowTrainer, contrast_loss, sequence_loss, smoothness_loss
 
 
 class Logger:
@@ -470,11 +470,19 @@ class TrainRaftEvents:
     prediction, batch['events'], batch['events_map']) - minus the mean flow warp loss of the batch, the ground-truth-free contrast
     term; supervised=False trains on the contrast term alone and reads neither batch['flow'] nor batch['valid'].  The batches must
     carry their events (a dataset built with with_events=True; get_batch adds 'events_map', batches without it use 'events_offset'),
-    and the prediction must be at the event frame's size (not out_mesh_size)."""
+    and the prediction must be at the event frame's size (not out_mesh_size).
+
+    smooth_weight (the autograd engine only): smooth_weight * train.smoothness_loss(predictions, batch['event_volume_old'] as the
+    model received it) is added to the loss - the edge-aware smoothness regulariser of order smooth_order with smooth_constant,
+    smooth_weight_type ('gauss', 'exp') and smooth_error ('L1', 'abs_robust'); of the last prediction, or with smooth_all=True of all
+    predictions under the engine's gamma.  A prediction at mesh size (out_mesh_size=True) has no edge image of its size and is
+    regularised unweighted (img=None).  supervised=False still needs a contrast_weight: smoothness alone is minimised by a constant
+    flow.  With smooth_weight == 0 nothing is computed and nothing changes."""
 
     def __init__(self, loader, image_size, lr=1e-4, wdecay=5e-5, epsilon=1e-8, num_steps=1000000, clip=1.0, gamma=0.8,
                  logger=None, print_freq=100, engine="fused", mixed_precision=True, start_iteration=0, contrast_weight=0.0,
-                 supervised=True):
+                 supervised=True, smooth_weight=0.0, smooth_order=1, smooth_constant=1.0, smooth_weight_type="gauss", smooth_error="L1",
+                 smooth_all=False):
         if engine not in ("fused", "autograd"):
             raise ValueError("engine must be 'fused' or 'autograd'")
         self.contrast_weight, self.supervised = float(contrast_weight), bool(supervised)
@@ -483,6 +491,14 @@ class TrainRaftEvents:
                              "only - the fused trainer has no contrast term")
         if not self.supervised and self.contrast_weight == 0.0:
             raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight")
+        self.smooth_weight, self.smooth_all = float(smooth_weight), bool(smooth_all)
+        self.smooth_kw = dict(order=smooth_order, constant=smooth_constant, weight_type=smooth_weight_type, error_type=smooth_error)
+        if self.smooth_weight != 0.0:
+            if engine == "fused":
+                raise ValueError("TrainRaftEvents: the smoothness term (smooth_weight != 0) is honoured by engine='autograd' only - the "
+                                 "fused trainer has no smoothness term")
+            from .smooth import _settings
+            _settings("TrainRaftEvents", smooth_order, smooth_constant, smooth_weight_type, smooth_error)
         self.loader, self.image_size = loader, image_size
         self.opt = dict(lr=lr, wdecay=wdecay, epsilon=epsilon, num_steps=num_steps, clip=clip, gamma=gamma)
         self.logger = logger or Logger()
@@ -528,6 +544,8 @@ class TrainRaftEvents:
                 loss, metrics = 0.0, {"epe": float("nan")}
             if self.contrast_weight != 0.0:
                 loss = loss + self.contrast_weight * self._contrast_term(flow_list[-1], batch, e1)
+            if self.smooth_weight != 0.0:
+                loss = loss + self.smooth_weight * self._smooth_term(flow_list, e1)
             self.scaler.scale(loss).backward()
             if parallel.exchange_active():
                 # the still-SCALED gradients are exchanged, then unscaled: an overflow on one rank reaches every rank through the
@@ -573,6 +591,12 @@ class TrainRaftEvents:
             raise ValueError(f"TrainRaftEvents: the contrast term needs the prediction at the event frame's size {tuple(volume.shape[-2:])}, "
                              f"got {tuple(flow_pred.shape[-2:])} - a model with out_mesh_size=True predicts the mesh flow")
         return contrast_loss(flow_pred, events, maps).float()
+
+    def _smooth_term(self, flow_list, volume):
+        """train.smoothness_loss of the predictions against the old event volume (float32, as the supervised loss is); a prediction
+        at another size than the volume (the mesh flow) is regularised unweighted."""
+        img = volume if tuple(flow_list[-1].shape[-2:]) == tuple(volume.shape[-2:]) else None
+        return smoothness_loss(flow_list, img, gamma=self.opt["gamma"] if self.smooth_all else None, **self.smooth_kw).float()
 
     def train_iters(self, model, start_epoch=0, val_iters=None):
         if self.image_size is None:                              # padder sized from the data (cli: un-cropped HREM frames)

@@ -100,6 +100,24 @@ def contrast_loss(flow_pred, events, maps=None):
     return fwl_loss(events, [pred[i] for i in range(pred.shape[0])], maps=maps)
 
 
+def smoothness_loss(flow_preds, img, gamma=None, **kw):
+    """The edge-aware smoothness term of a model's predictions (a list of (B,2,H,W) tensors, the last one final) against the shared
+    edge image `img` ((B,C,H,W), in training the old event volume; None: unweighted): smooth.smoothness_loss of the last prediction
+    with gamma=None, else sum_i gamma^(n-1-i) * L_i over all n predictions - one library call forward and one backward per 16
+    predictions, img read and its weights taken once per tile for all of them.  A differentiable 0-dim float64 CUDA tensor;
+    **kw: order, constant, weight_type, error_type of smooth.smoothness_many."""
+    from .smooth import smoothness_many
+    flow_preds = list(flow_preds)
+    if len(flow_preds) < 1:
+        raise ValueError("smoothness_loss: at least one prediction")
+    if gamma is None:
+        return smoothness_many([flow_preds[-1].float()], img, **kw)[0]
+    n = len(flow_preds)
+    losses = smoothness_many([f.float() for f in flow_preds], img, **kw)
+    weights = torch.tensor([float(gamma) ** (n - 1 - i) for i in range(n)], dtype=torch.float64).to(losses.device, non_blocking=True)
+    return (losses * weights).sum()
+
+
 class EEMFlowTrainer:
     """One optimisation step per `step()` call; owns the flat gradient buffer and the schedule."""
 

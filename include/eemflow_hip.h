@@ -312,6 +312,33 @@ int eemflow_iwe_grad_many(int k, const double* const* events, const int64_t* n, 
                           const double* scale, const double (*maps)[4], int h, int w, const float* const* iwe, const double* moments,
                           const double* coef, float* const* grads, void* stream);
 
+/* Edge-aware smoothness loss of k (1..16) predictions of one shape, and its gradient, by one launch: pred[i] ([B][2][H][W] fp32,
+ * contiguous), img[i] ([B][C][H][W] fp32, any C >= 1; a NULL entry, or img == NULL, means every weight is 1) and grad[i] ([B][2][H][W]
+ * fp32) are HOST arrays of device pointers, read before the call returns.  For s = order in {1, 2} and both axes (axis 2 = rows, the
+ * reference's `x`; axis 3 = columns), in unfused fp64 on the fp32 inputs: d = p[i] - p[i+1] (order 1) or (p[i] - p[i+1]) - (p[i+1] -
+ * p[i+2]) (order 2); g_c = constant * (img_c[i] - img_c[i+s]) and w = exp(-mean_c f(g_c)) with f(g) = g * g (weight_type 0, 'gauss')
+ * or |g| (1, 'exp'), one weight per (b, i, j) for both flow channels; e(d) = |d| (error_type 0, 'L1') or (|d| + 0.01)^0.4 (1,
+ * 'abs_robust'); L = mean over the B*2*(H-s)*W axis-2 terms of e(d) * w + mean over the B*2*H*(W-s) axis-3 terms.
+ * loss (device, k doubles; may be NULL) receives L per job - block partial sums go to scratch (device,
+ * eemflow_smoothness_scratch_doubles(k, B, H, W) doubles) and are added in a fixed order, so a loss is bitwise the same from run to
+ * run.  grad (may be NULL) receives grad[i] = coef[i] * dL_i / dpred_i, every cell written: the fp64 sum over the terms that touch the
+ * cell of c * e'(d) * w / N_axis (c = +1, -1 or +1, -2, +1; e' = sign(d) with sign(0) = 0, or 0.4 e(d) / (|d| + 0.01) sign(d)), times
+ * coef, rounded to fp32 once - a gather without atomics, bitwise reproducible.  coef is a DEVICE array of k doubles (the upstream
+ * gradient; NULL: 1), so nothing visits the host.  img receives no gradient.  Consecutive jobs that name one img pointer read it and
+ * compute the weights once per tile; their results are bitwise those of one-job calls.  Stream-ordered, no host synchronisation, no
+ * allocation.  Errors: k out of range, H <= s or W <= s (the reference would take the mean of an empty tensor), unknown order or
+ * enum values, neither loss nor grad.  Non-finite inputs propagate.
+ * Replaces: Loss_tools.edge_aware_smoothness_order1 (utils_luo/tools.py:3008-3047), Loss_tools.edge_aware_smoothness_order2
+ * (utils_luo/tools.py:3049-3090) and Loss_tools.flow_smooth_delta (utils_luo/tools.py:3092-3110; order 1, L1, no img), and their
+ * autograd. */
+int eemflow_smoothness_many(int k, const float* const* pred, const float* const* img, int B, int C, int H, int W, int order,
+                            int weight_type, int error_type, double constant, const double* coef, double* loss, float* const* grad,
+                            double* scratch, void* stream);
+
+/* Doubles of scratch that eemflow_smoothness_many needs for k jobs of shape [B][2][H][W] (0 for arguments it would refuse).
+ * Replaces: nothing in the reference (torch.mean owns its temporaries). */
+size_t eemflow_smoothness_scratch_doubles(int k, int B, int H, int W);
+
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
  * receive, per event, the int64 flat index x + y*w + bin*w*h of the left / right temporal vote, or -1
