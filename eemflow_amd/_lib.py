@@ -133,6 +133,9 @@ _SIGNATURES = {
     "eraft_forward": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.POINTER(ctypes.c_int * 4), ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_void_p]),
     "eraft_keep_stages": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "eraft_record_stages": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]),
+    "eraft_last_form": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
+    "eraft_stage_list": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "eraft_set_frames_in_flight": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "eraft_forward_many": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),

@@ -27,6 +27,12 @@ int ensure(Buf& b, size_t floats) {
     return EEM_OK;
 }
 
+struct StageRec {                 // one recorded launch output: [dims] floats at rec_buf + off
+    std::string name, form;
+    int dims[4];
+    size_t off;
+};
+
 struct Layer {                    // one convolution, weights packed for gconv
     size_t wpk = 0, wpk16 = 0, wpkb = 0, wfew = 0, wstem = 0, scale = 0, shift = 0;
     bool hasb = false, has_stem = false;
@@ -97,6 +103,15 @@ struct eraft_ctx {
     int carry_h = 0, carry_w = 0, carry_padv[4] = {0, 0, 0, 0};
     unsigned long carry_wver = 0;
     int stream_pairs = 0;          // > 0: the last forward was a stream call of that many pairs ("flow_low" reads sflow)
+    // eraft_record_stages (the fp64 stage tests): a device copy of every launch's output whose name starts with one of `rec_prefix`,
+    // filed with the kernel form that wrote it.  The copies live in one arena sized by the forward before: a forward whose records do
+    // not fit only measures them and is run again (eraft_forward / eraft_forward_many) with the arena grown before its first fork
+    bool rec_on = false;
+    std::vector<std::string> rec_prefix;
+    int rec_iters = 0;             // update iterations 0 .. rec_iters - 1 are recorded
+    std::vector<StageRec> rec;
+    Buf rec_buf;
+    size_t rec_used = 0, rec_need = 0;
 };
 
 namespace {
@@ -269,6 +284,26 @@ void set_seg(GConvArgs& a, int i, const float* ptr, int cch, int ctotal, int cof
     a.seg[i].ptr = ptr; a.seg[i].c = cch; a.seg[i].ctotal = ctotal; a.seg[i].coff = coff;
 }
 
+// The stage recorder (eraft_ctx::rec_on): `src` is [n][src_ctotal][h * w], of which the channels [src_coff, src_coff + ch) are copied on
+// `st`, the stream of the launch that has just written them.  It launches no kernel; with the recorder off no call site gets here.
+int rec_stage(eraft_ctx* c, const char* name, const char* form, const float* src, int n, int ch, int h, int w, hipStream_t st,
+              int src_ctotal = 0, int src_coff = 0) {
+    bool wanted = false;
+    for (const std::string& p : c->rec_prefix) wanted = wanted || strncmp(name, p.c_str(), p.size()) == 0;
+    if (!wanted) return EEM_OK;
+    const size_t hw = (size_t)h * w, cnt = (size_t)n * ch * hw, off = c->rec_used;
+    c->rec_used += (cnt + 63) & ~(size_t)63;
+    if (c->rec_used > c->rec_buf.cap) return EEM_OK;                     // measured only: the forward runs again with the arena grown
+    float* dst = c->rec_buf.p + off;
+    if (src_ctotal == 0 || src_ctotal == ch)
+        EEM_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * 4, hipMemcpyDeviceToDevice, st));
+    else
+        EEM_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)ch * hw * 4, src + (size_t)src_coff * hw, (size_t)src_ctotal * hw * 4, (size_t)ch * hw * 4, n,
+                                       hipMemcpyDeviceToDevice, st));
+    c->rec.push_back(StageRec{name, form ? form : "", {n, ch, h, w}, off});
+    return EEM_OK;
+}
+
 // A 64 -> 64 3x3 conv of the encoder on the Winograd F(4x4,3x3) kernel: out = act(conv(x) + shift) [then relu(res + .)];
 // act: 0 none (an InstanceNorm follows), 2 ReLU (eval BatchNorm folded into weights and shift).  From 128 tiles of 32x16 pixels on
 // (fewer leave most CUs without a block and the LDS-tiled kernel wins); EEM_ERAFT_NO_F4=1 keeps every conv on gconv.
@@ -324,9 +359,18 @@ bool wnc_upd(const Layer& L, int bit, int n, int h, int w) {
 }
 
 // BasicEncoder forward on `n` images [n][cin0][hp][wp]; result of the residual stack in *feat ([n][128][hp/8][wp/8]).
-int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0, int hp, int wp, float** feat, hipStream_t st, Buf* sc = nullptr) {
+// tag ("fnet." / "cnet."; NULL: the recorder is off): every launch's output is recorded as <tag>conv1, <tag>norm1, <tag>layer<l>.<r>.conv1 ...
+int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0, int hp, int wp, float** feat, hipStream_t st, Buf* sc = nullptr,
+                const char* tag = nullptr) {
     int rc;
     if (!sc) sc = c->s;
+    char rname[64];
+    const char* wform = "";                                              // the form of the conv launch just made
+    auto recl = [&](int l, int r, const char* what, const char* form, const float* p, int ch, int hh, int ww) -> int {
+        if (l < 0) snprintf(rname, sizeof(rname), "%s%s", tag, what);
+        else snprintf(rname, sizeof(rname), "%slayer%d.%d.%s", tag, l + 1, r, what);
+        return rec_stage(c, rname, form, p, n, ch, hh, ww, st);
+    };
     float* X = sc[0].p; float* R = sc[1].p; float* Y = sc[2].p; float* D = sc[3].p; float* O = sc[4].p;
     int h = hp, w = wp;
     {   // conv1 7x7 s2 + norm1 + relu
@@ -334,7 +378,9 @@ int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0,
         set_seg(a, 0, x, cin0, cin0, 0);
         if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
         h = a.hout; w = a.wout;
+        if (tag && (rc = recl(-1, 0, "conv1", eem_conv_form, E.batch_norm ? X : R, 64, h, w)) != EEM_OK) return rc;
         if (!E.batch_norm && (rc = er_instnorm_launch(R, X, nullptr, n * 64, h * w, 1, st, c->nstat, c->nstat_cap)) != EEM_OK) return rc;
+        if (tag && !E.batch_norm && (rc = recl(-1, 0, "norm1", er_last_form, X, 64, h, w)) != EEM_OK) return rc;
     }
     const int dims[3] = {64, 96, 128};
     int in_planes = 64, bi = 0;
@@ -345,30 +391,36 @@ int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0,
             // y = relu(norm1(conv1(x)))
             GConvArgs a1 = conv_args(c, bk.conv1, n, h, w, E.batch_norm ? Y : R, planes, 0, E.batch_norm ? GACT_RELU : GACT_NONE);
             set_seg(a1, 0, X, cin, cin, 0);
-            if (f4_eligible(bk.conv1, n, h, w)) rc = run_f4(c, bk.conv1, X, n, h, w, E.batch_norm ? Y : R, E.batch_norm ? 2 : 0, nullptr, st);
-            else if (wnc_eligible(bk.conv1, n, h, w)) rc = run_wnc(c, bk.conv1, X, n, h, w, E.batch_norm ? Y : R, E.batch_norm ? 2 : 0, nullptr, st);
-            else rc = gconv_launch(a1, st);
+            if (f4_eligible(bk.conv1, n, h, w)) { rc = run_f4(c, bk.conv1, X, n, h, w, E.batch_norm ? Y : R, E.batch_norm ? 2 : 0, nullptr, st); wform = "f4"; }
+            else if (wnc_eligible(bk.conv1, n, h, w)) { rc = run_wnc(c, bk.conv1, X, n, h, w, E.batch_norm ? Y : R, E.batch_norm ? 2 : 0, nullptr, st); wform = "wnc"; }
+            else { rc = gconv_launch(a1, st); wform = eem_conv_form; }
             if (rc != EEM_OK) return rc;
             const int ho = a1.hout, wo = a1.wout;
+            if (tag && (rc = recl(l, r, "conv1", wform, E.batch_norm ? Y : R, planes, ho, wo)) != EEM_OK) return rc;
             if (!E.batch_norm && (rc = er_instnorm_launch(R, Y, nullptr, n * planes, ho * wo, 1, st, c->nstat, c->nstat_cap)) != EEM_OK) return rc;
+            if (tag && !E.batch_norm && (rc = recl(l, r, "norm1", er_last_form, Y, planes, ho, wo)) != EEM_OK) return rc;
             // shortcut
             const float* res = X;
             if (bk.has_down) {
                 GConvArgs ad = conv_args(c, bk.down, n, h, w, E.batch_norm ? D : R, planes, 0, GACT_NONE);
                 set_seg(ad, 0, X, cin, cin, 0);
                 if ((rc = gconv_launch(ad, st)) != EEM_OK) return rc;
+                if (tag && (rc = recl(l, r, "down", eem_conv_form, E.batch_norm ? D : R, planes, ho, wo)) != EEM_OK) return rc;
                 if (!E.batch_norm && (rc = er_instnorm_launch(R, D, nullptr, n * planes, ho * wo, 0, st, c->nstat, c->nstat_cap)) != EEM_OK) return rc;
+                if (tag && !E.batch_norm && (rc = recl(l, r, "norm3", er_last_form, D, planes, ho, wo)) != EEM_OK) return rc;
                 res = D;
             }
             // out = relu(res + relu(norm2(conv2(y))))
             GConvArgs a2 = conv_args(c, bk.conv2, n, ho, wo, E.batch_norm ? O : R, planes, 0, E.batch_norm ? GACT_RELU : GACT_NONE);
             set_seg(a2, 0, Y, planes, planes, 0);
             if (E.batch_norm) { a2.epi = GEPI_ADD_RELU; a2.e0 = res; a2.e0_ctotal = planes; a2.e0_coff = 0; }
-            if (f4_eligible(bk.conv2, n, ho, wo)) rc = run_f4(c, bk.conv2, Y, n, ho, wo, E.batch_norm ? O : R, E.batch_norm ? 2 : 0, E.batch_norm ? res : nullptr, st);
-            else if (wnc_eligible(bk.conv2, n, ho, wo)) rc = run_wnc(c, bk.conv2, Y, n, ho, wo, E.batch_norm ? O : R, E.batch_norm ? 2 : 0, E.batch_norm ? res : nullptr, st);
-            else rc = gconv_launch(a2, st);
+            if (f4_eligible(bk.conv2, n, ho, wo)) { rc = run_f4(c, bk.conv2, Y, n, ho, wo, E.batch_norm ? O : R, E.batch_norm ? 2 : 0, E.batch_norm ? res : nullptr, st); wform = "f4"; }
+            else if (wnc_eligible(bk.conv2, n, ho, wo)) { rc = run_wnc(c, bk.conv2, Y, n, ho, wo, E.batch_norm ? O : R, E.batch_norm ? 2 : 0, E.batch_norm ? res : nullptr, st); wform = "wnc"; }
+            else { rc = gconv_launch(a2, st); wform = eem_conv_form; }
             if (rc != EEM_OK) return rc;
+            if (tag && (rc = recl(l, r, "conv2", wform, E.batch_norm ? O : R, planes, ho, wo)) != EEM_OK) return rc;
             if (!E.batch_norm && (rc = er_instnorm_launch(R, O, res, n * planes, ho * wo, 1, st, c->nstat, c->nstat_cap)) != EEM_OK) return rc;
+            if (tag && !E.batch_norm && (rc = recl(l, r, "norm2", er_last_form, O, planes, ho, wo)) != EEM_OK) return rc;
             float* t = X; X = O; O = t;
             h = ho; w = wo;
             if (r == 0) in_planes = planes;
@@ -377,7 +429,7 @@ int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0,
     return EEM_OK;
 }
 
-int build_pyramid(eraft_ctx* c, const float* f1, const float* f2, int batch, int ch, int h, int w, hipStream_t st) {
+int build_pyramid(eraft_ctx* c, const float* f1, const float* f2, int batch, int ch, int h, int w, hipStream_t st, bool recd = false) {
     int rc;
     const size_t hw = (size_t)h * w;
     c->ph[0] = h; c->pw[0] = w;
@@ -387,11 +439,18 @@ int build_pyramid(eraft_ctx* c, const float* f1, const float* f2, int batch, int
         if ((rc = ensure(c->pyr[l], (size_t)batch * hw * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
     }
     if ((rc = er_allpairs_launch(f1, f2, c->pyr[0].p, batch, ch, (int)hw, st)) != EEM_OK) return rc;
-    return er_pool2x3_launch(c->pyr[0].p, c->pyr[1].p, c->pyr[2].p, c->pyr[3].p, (long)batch * hw, h, w, st);
+    if (recd && (rc = rec_stage(c, "pyr0", er_last_form, c->pyr[0].p, (int)(batch * hw), 1, h, w, st)) != EEM_OK) return rc;
+    if ((rc = er_pool2x3_launch(c->pyr[0].p, c->pyr[1].p, c->pyr[2].p, c->pyr[3].p, (long)batch * hw, h, w, st)) != EEM_OK) return rc;
+    if (recd)
+        for (int l = 1; l < 4; ++l) {
+            const char nm[5] = {'p', 'y', 'r', (char)('0' + l), 0};
+            if ((rc = rec_stage(c, nm, er_last_form, c->pyr[l].p, (int)(batch * hw), 1, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
+        }
+    return EEM_OK;
 }
 
 // alt_corr: the level sizes and the avg_pool2d(2) chain of fmap2 itself (pooling the volume's last two dimensions = pooling fmap2)
-int build_feature_pyramid(eraft_ctx* c, const float* f2, int batch, int ch, int h, int w, hipStream_t st) {
+int build_feature_pyramid(eraft_ctx* c, const float* f2, int batch, int ch, int h, int w, hipStream_t st, bool recd = false) {
     int rc;
     c->ph[0] = h; c->pw[0] = w;
     for (int l = 1; l < 4; ++l) { c->ph[l] = c->ph[l - 1] / 2; c->pw[l] = c->pw[l - 1] / 2; }
@@ -400,6 +459,8 @@ int build_feature_pyramid(eraft_ctx* c, const float* f2, int batch, int ch, int 
         EEM_REQUIRE(c->ph[l] >= 1 && c->pw[l] >= 1, "correlation pyramid level %d is empty for a %dx%d feature map", l, h, w);
         if ((rc = ensure(c->f2l[l - 1], (size_t)batch * ch * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
         if ((rc = er_pool2_launch(src, c->f2l[l - 1].p, (long)batch * ch, c->ph[l - 1], c->pw[l - 1], st)) != EEM_OK) return rc;
+        const char nm[5] = {'f', '2', 'l', (char)('0' + l), 0};
+        if (recd && (rc = rec_stage(c, nm, er_last_form, c->f2l[l - 1].p, batch, ch, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
         src = c->f2l[l - 1].p;
     }
     return EEM_OK;
@@ -460,7 +521,7 @@ extern "C" void eraft_destroy(eraft_ctx* c) {
                   &c->motion, &c->z, &c->rh, &c->fhid, &c->delta, &c->mhid, &c->mask, &c->st_corr0, &c->st_net1, &c->st_mask1,
                   &c->st_delta1, &c->zeros, &c->many_out, &c->f2l[0], &c->f2l[1], &c->f2l[2], &c->czr[0], &c->czr[1], &c->cq[0], &c->cq[1],
                   &c->s2[0], &c->s2[1], &c->s2[2], &c->s2[3], &c->s2[4], &c->carry_pad, &c->carry_fmap, &c->carry_flow, &c->sflow,
-                  &c->finit, &c->fi_ws};
+                  &c->finit, &c->fi_ws, &c->rec_buf};
     for (Buf* b : all) if (b->p) (void)hipFree(b->p);
     if (c->nstat) (void)hipFree(c->nstat);
     if (c->side) (void)hipStreamDestroy(c->side);
@@ -634,6 +695,11 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     ENS(c->mask, B * 576 * g);
     const bool keep = c->keep_stages && !sp;
     if (keep) { ENS(c->st_corr0, B * 324 * g); ENS(c->st_net1, B * 128 * g); ENS(c->st_mask1, B * 576 * g); ENS(c->st_delta1, B * 2 * g); }
+    // the stage recorder (a stream call records nothing): its arena, sized by the forward before (see eraft_ctx)
+    const bool recd = c->rec_on && !sp;
+    c->rec.clear();
+    c->rec_used = 0;
+    if (recd) ENS(c->rec_buf, c->rec_need);
     if (sp) {
         ENS(c->sflow, (size_t)std::max(B, 1) * 2 * g); ENS(c->finit, 2 * g);
         ENS(c->fi_ws, eraft_forward_interpolate_scratch(1, h8, w8));    // (ints)
@@ -641,6 +707,14 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
 #undef ENS
     const int cin0 = c->cin0;
     const size_t img = (size_t)cin0 * hp * wp;
+    char rname[48];
+#define REC(...) if (recd && (rc = rec_stage(c, __VA_ARGS__)) != EEM_OK) return rc
+    // (inside the update loop: iteration `it`'s stage `what`, a [B][ch][h8][w8] slice, on stream `strm`)
+#define RECIT(what, form, src, ch, strm, ctotal, coff)                                                              \
+    if (recd && it < c->rec_iters) {                                                                                \
+        snprintf(rname, sizeof(rname), "it%d.%s", it, what);                                                        \
+        if ((rc = rec_stage(c, rname, form, src, B, ch, h8, w8, strm, ctotal, coff)) != EEM_OK) return rc;          \
+    }
     if (sp) {                                                            // the windows into slots s0.., the carried one into slot 0
         if (sp->carried) EEM_HIP_CHECK(hipMemcpyAsync(c->padded.p, c->carry_pad.p, img * 4, hipMemcpyDeviceToDevice, st));
         for (int j = 0; j < sp->nvol; ++j)
@@ -714,6 +788,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             if ((rc = er_pad_launch(e2v[i], pad2 + (size_t)i * img, cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
         }
     }
+    REC("pad", er_last_form, c->padded.p, nimg, cin0, hp, wp, st);
     float* cfeat = nullptr;
     if ((rc = fork()) != EEM_OK) return rc;                            // (the padded volumes are on their way)
     // (the feature network's launches are enqueued FIRST: it is the longer chain - two images, instance norms - and the host needs ~0.3 ms
@@ -724,30 +799,33 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     auto run_fnet = [&]() -> int {
         // ---- feature network on [image1; image2] (:116), then its 1x1 output conv
         float* feat = nullptr;
-        if ((rc = run_encoder(c, c->fnet, c->padded.p + s0 * img, nfn, cin0, hp, wp, &feat, st)) != EEM_OK) return rc;
+        if ((rc = run_encoder(c, c->fnet, c->padded.p + s0 * img, nfn, cin0, hp, wp, &feat, st, nullptr, recd ? "fnet." : nullptr)) != EEM_OK) return rc;
         {
             GConvArgs a = conv_args(c, c->fnet.conv2a, nfn, h8, w8, c->fmap.p + (size_t)s0 * 256 * g, 256, 0, GACT_NONE);
             set_seg(a, 0, feat, 128, 128, 0);
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+            REC("fmap", eem_conv_form, c->fmap.p, nimg, 256, h8, w8, st);
         }
         if (s0) EEM_HIP_CHECK(hipMemcpyAsync(c->fmap.p, c->carry_fmap.p, 256 * g * 4, hipMemcpyDeviceToDevice, st));
         // ---- all-pairs correlation pyramid (:121); the stream's pair p: slots p and p + 1 of one buffer
         const size_t f2off = (size_t)(sp ? 1 : B) * 256 * g;
-        if (c->alt_corr) rc = build_feature_pyramid(c, c->fmap.p + f2off, B, 256, h8, w8, st);
-        else rc = build_pyramid(c, c->fmap.p, c->fmap.p + f2off, B, 256, h8, w8, st);
+        if (c->alt_corr) rc = build_feature_pyramid(c, c->fmap.p + f2off, B, 256, h8, w8, st, recd);
+        else rc = build_pyramid(c, c->fmap.p, c->fmap.p + f2off, B, 256, h8, w8, st, recd);
         if (rc != EEM_OK) return rc;
         return EEM_OK;
     };
     auto run_cnet = [&]() -> int {
         // ---- context network on image1 (:126-131): net = tanh(first half), inp = relu(second half)
-        if ((rc = run_encoder(c, c->cnet, pad1, B, cin0, hp, wp, &cfeat, sd, overlap ? c->s2 : nullptr)) != EEM_OK) return rc;
+        if ((rc = run_encoder(c, c->cnet, pad1, B, cin0, hp, wp, &cfeat, sd, overlap ? c->s2 : nullptr, recd ? "cnet." : nullptr)) != EEM_OK) return rc;
         {
             GConvArgs a = conv_args(c, c->cnet.conv2a, B, h8, w8, c->net[0].p, 128, 0, GACT_TANH);
             set_seg(a, 0, cfeat, 128, 128, 0);
             if ((rc = gconv_launch(a, sd)) != EEM_OK) return rc;
+            REC("net0", eem_conv_form, c->net[0].p, B, 128, h8, w8, sd);
             GConvArgs b2 = conv_args(c, c->cnet.conv2b, B, h8, w8, c->inp.p, 128, 0, GACT_RELU);
             set_seg(b2, 0, cfeat, 128, 128, 0);
             if ((rc = gconv_launch(b2, sd)) != EEM_OK) return rc;
+            REC("inp", eem_conv_form, c->inp.p, B, 128, h8, w8, sd);
         }
         if ((rc = er_coords_init_launch(c->c0.p, c->c1.p, flow_init, B, h8, w8, sd)) != EEM_OK) return rc;
         // the context features' part of the GRU convs, once per forward (see eraft_ctx)
@@ -756,9 +834,11 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                 GConvArgs a = conv_args(c, c->gzr_c[pass], B, h8, w8, c->czr[pass].p, 256, 0, GACT_NONE);
                 set_seg(a, 0, c->inp.p, 128, 128, 0);
                 if ((rc = gconv_launch(a, sd)) != EEM_OK) return rc;
+                REC(pass ? "czr1" : "czr0", eem_conv_form, c->czr[pass].p, B, 256, h8, w8, sd);
                 a = conv_args(c, c->gq_c[pass], B, h8, w8, c->cq[pass].p, 128, 0, GACT_NONE);
                 set_seg(a, 0, c->inp.p, 128, 128, 0);
                 if ((rc = gconv_launch(a, sd)) != EEM_OK) return rc;
+                REC(pass ? "cq1" : "cq0", eem_conv_form, c->cq[pass].p, B, 128, h8, w8, sd);
             }
         }
         return EEM_OK;
@@ -781,7 +861,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     // (three rotating buffers) and coords1 buffer iteration i + 2 overwrites.  Measured against a third stream that started the mask
     // head right behind the GRU (two event records per iteration on the chain's stream): 196.0 against 192.4 frames/s at batch 1, 283.3
     // against 277.2 at batch 4.
-    struct { bool on = false; const float* c1 = nullptr; const float* hidden = nullptr; int oi = 0; } pend;
+    struct { bool on = false; const float* c1 = nullptr; const float* hidden = nullptr; int oi = 0, it = 0; } pend;
     auto side_mask = [&]() -> int {
         if (!pend.on) return EEM_OK;
         pend.on = false;
@@ -792,13 +872,23 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         set_seg(m, 0, pend.hidden, 128, 128, 0);
         int r2 = gconv_launch(m, sd);
         if (r2 != EEM_OK) return r2;
+        const bool recp = recd && pend.it < c->rec_iters;
+        char pname[48];
+        auto recs = [&](const char* what, const char* form, const float* src, int ch, int hh, int ww) -> int {
+            snprintf(pname, sizeof(pname), "it%d.%s", pend.it, what);
+            return rec_stage(c, pname, form, src, LB, ch, hh, ww, sd);
+        };
+        if (recp && (r2 = recs("mhid", eem_conv_form, c->mhid.p, 256, h8, w8)) != EEM_OK) return r2;
         m = conv_args(c, c->mk2, LB, h8, w8, c->mask.p, 576, 0, GACT_NONE);
         set_seg(m, 0, c->mhid.p, 256, 256, 0);
         m.out_scale = 0.25f;
         if ((r2 = gconv_launch(m, sd)) != EEM_OK) return r2;
+        if (recp && (r2 = recs("mask", eem_conv_form, c->mask.p, 576, h8, w8)) != EEM_OK) return r2;
         // :155-157 the convex upsampling of coords1 - coords0
-        return er_convex_up_launch(c->c0.p, pend.c1, c->mask.p, lout + (size_t)pend.oi * LB * 2 * in_h * in_w, LB, h8, w8, pad[2], pad[0], in_h,
-                                   in_w, sd);
+        float* po = lout + (size_t)pend.oi * LB * 2 * in_h * in_w;
+        if ((r2 = er_convex_up_launch(c->c0.p, pend.c1, c->mask.p, po, LB, h8, w8, pad[2], pad[0], in_h, in_w, sd)) != EEM_OK) return r2;
+        if (recp && (r2 = recs("pred", er_last_form, po, 2, in_h, in_w)) != EEM_OK) return r2;
+        return EEM_OK;
     };
     const float* c1last = nullptr;
     for (int pr = 0; pr < (warm ? B : 1); ++pr) {
@@ -831,11 +921,16 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         // (the fork of the flow branch below: the lookup's own completion signal is the event the side stream waits for, not a
         // hipEventRecord behind it as through round 6's first half)
         const bool fork_by_launch = fuse_small && overlap;
+        RECIT("coords1_in", "", c1cur, 2, st, 0, 0);
         if (fuse_small) {
             if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st, c->c0.p, c->motion.p, 128, 126, fork_by_launch ? c->fork_ev : nullptr, lp)) != EEM_OK) return rc;
+            RECIT("corr", er_last_form, c->corr.p, 324, st, kCorrPad, 0);
+            RECIT("flow", c->alt_corr ? "flow" : er_last_form, c->motion.p, 2, st, 128, 126);
         } else {
             if ((rc = run_lookup(c, c1cur, c->corr.p, kCorrPad, B, h8, w8, st, nullptr, nullptr, 0, 0, nullptr, lp)) != EEM_OK) return rc;
+            RECIT("corr", er_last_form, c->corr.p, 324, st, kCorrPad, 0);
             if ((rc = er_flow_launch(c->c0.p, c1cur, c->motion.p, 128, 126, B, (int)g, st)) != EEM_OK) return rc;
+            RECIT("flow", er_last_form, c->motion.p, 2, st, 128, 126);
         }
         // motion encoder (model/update.py:73-81): the flow branch convf1 -> convf2 on the side stream beside the correlation branch
         // the 324 correlation features live in a 336-channel buffer (12 zero channels, zero weight columns) so that the
@@ -852,32 +947,40 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         GConvArgs a = conv_args(c, c->convf1, B, h8, w8, c->flo1.p, 128, 0, GACT_RELU);
         set_seg(a, 0, c->motion.p, 2, 128, 126);
         if ((rc = gconv_launch(a, sd)) != EEM_OK) return rc;
+        RECIT("flo1", eem_conv_form, c->flo1.p, 128, sd, 0, 0);
         if (wnc_upd(c->convf2, 1, B, h8, w8)) {
             if ((rc = run_wnc(c, c->convf2, c->flo1.p, B, h8, w8, c->corflo.p, 2, nullptr, sd, 256, 192)) != EEM_OK) return rc;
+            RECIT("corflo.f", "wnc", c->corflo.p, 64, sd, 256, 192);
         } else {
             a = conv_args(c, c->convf2, B, h8, w8, c->corflo.p, 256, 192, GACT_RELU);
             set_seg(a, 0, c->flo1.p, 128, 128, 0);
             if ((rc = gconv_launch(a, sd)) != EEM_OK) return rc;
+            RECIT("corflo.f", eem_conv_form, c->corflo.p, 64, sd, 256, 192);
         }
         a = conv_args(c, c->convc1, B, h8, w8, c->cor1.p, 256, 0, GACT_RELU);
         set_seg(a, 0, c->corr.p, kCorrPad, kCorrPad, 0);
         if (!gconv16_supported(a)) { a.wpk16 = nullptr; set_seg(a, 0, c->corr.p, 324, kCorrPad, 0); }
         if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+        RECIT("cor1", eem_conv_form, c->cor1.p, 256, st, 0, 0);
         if (wnc_upd(c->convc2, 0, B, h8, w8)) {
             if ((rc = run_wnc(c, c->convc2, c->cor1.p, B, h8, w8, c->corflo.p, 2, nullptr, st, 256, 0)) != EEM_OK) return rc;
+            RECIT("corflo.c", "wnc", c->corflo.p, 192, st, 256, 0);
         } else {
             a = conv_args(c, c->convc2, B, h8, w8, c->corflo.p, 256, 0, GACT_RELU);
             set_seg(a, 0, c->cor1.p, 256, 256, 0);
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+            RECIT("corflo.c", eem_conv_form, c->corflo.p, 192, st, 256, 0);
         }
         if ((rc = join()) != EEM_OK) return rc;
         if (lagged && (rc = side_mask()) != EEM_OK) return rc;             // (the previous iteration's prediction, behind the join event)
         if (wnc_upd(c->conv, 2, B, h8, w8)) {
             if ((rc = run_wnc(c, c->conv, c->corflo.p, B, h8, w8, c->motion.p, 2, nullptr, st, 128, 0)) != EEM_OK) return rc;
+            RECIT("motion", "wnc", c->motion.p, 126, st, 128, 0);
         } else {
             a = conv_args(c, c->conv, B, h8, w8, c->motion.p, 128, 0, GACT_RELU);
             set_seg(a, 0, c->corflo.p, 256, 256, 0);
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+            RECIT("motion", eem_conv_form, c->motion.p, 126, st, 128, 0);
         }
         // SepConvGRU (model/update.py:43-60): horizontal then vertical pass
         float* hcur = nin;
@@ -888,6 +991,10 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         // partly empty (an update iteration at 60x80: 490 -> 430 us, 121 -> 129 frames/s; + 1.5 % at batch 4 / 8, the same with
         // frames in flight).  EEM_ERAFT_NO_STACK=1 keeps them apart.
         for (int pass = 0; pass < 2; ++pass) {
+            const char* const gz_n = pass ? "gru1.z" : "gru0.z";
+            const char* const gr_n = pass ? "gru1.r" : "gru0.r";
+            const char* const grh_n = pass ? "gru1.rh" : "gru0.rh";
+            const char* const gh_n = pass ? "gru1.h" : "gru0.h";
             if (stack) {
                 if (use_pre) {
                     a = conv_args(c, c->gzr_hm[pass], B, h8, w8, c->z.p, 256, 0, GACT_SIGMOID);
@@ -901,15 +1008,21 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                 const bool zr_epi = !sw_on<SW_EEM_ERAFT_NO_ZR>();
                 if (zr_epi) { a.epi = GEPI_ZR; a.split = 128; a.out2 = c->rh.p; a.out2_ctotal = 128; a.e0 = hcur; a.e0_ctotal = 128; a.e0_coff = 0; }
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT(gz_n, eem_conv_form, c->z.p, 128, st, 256, 0);
+                if (zr_epi) { RECIT(grh_n, eem_conv_form, c->rh.p, 128, st, 0, 0); }
+                else { RECIT(gr_n, eem_conv_form, c->z.p, 128, st, 256, 128); }
                 if (!zr_epi && (rc = er_mul_channels_launch(c->rh.p, c->z.p, 256, 128, hcur, B, 128, (long)g, st)) != EEM_OK) return rc;
+                if (!zr_epi) { RECIT(grh_n, er_last_form, c->rh.p, 128, st, 0, 0); }
             } else {
                 a = conv_args(c, c->gz[pass], B, h8, w8, c->z.p, 128, 0, GACT_SIGMOID);
                 set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT(gz_n, eem_conv_form, c->z.p, 128, st, 0, 0);
                 a = conv_args(c, c->gr[pass], B, h8, w8, c->rh.p, 128, 0, GACT_SIGMOID);
                 set_seg(a, 0, hcur, 128, 128, 0); set_seg(a, 1, inp_l, 128, 128, 0); set_seg(a, 2, c->motion.p, 128, 128, 0);
                 a.epi = GEPI_MUL; a.e0 = hcur; a.e0_ctotal = 128; a.e0_coff = 0;
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT(grh_n, eem_conv_form, c->rh.p, 128, st, 0, 0);
             }
             if (use_pre) {
                 a = conv_args(c, c->gq_hm[pass], B, h8, w8, hnext, 128, 0, GACT_TANH);
@@ -921,6 +1034,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             }
             a.epi = GEPI_GRU; a.e0 = hcur; a.e0_ctotal = 128; a.e0_coff = 0; a.e1 = c->z.p; a.e1_ctotal = stack ? 256 : 128; a.e1_coff = 0;
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+            RECIT(gh_n, eem_conv_form, hnext, 128, st, 0, 0);
             hcur = hnext; hnext = net;
         }
         // after two passes the new hidden state is in `net`
@@ -929,19 +1043,24 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             a = conv_args(c, c->fh1, B, h8, w8, c->fhid.p, 256, 0, GACT_RELU);
             set_seg(a, 0, net, 128, 128, 0);
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+            RECIT("fhid", eem_conv_form, c->fhid.p, 256, st, 0, 0);
             // the flow head's last conv leaves delta_flow and :149 coords1 + delta_flow (the other coords1 buffer) in one launch
             a = conv_args(c, c->fh2, B, h8, w8, c->delta.p, 2, 0, GACT_NONE);
             set_seg(a, 0, c->fhid.p, 256, 256, 0);
             a.epi = GEPI_SUM2; a.e0 = c1cur; a.e0_ctotal = 2; a.e0_coff = 0; a.out2 = c1nxt; a.out2_ctotal = 2;
             if (fewout_supported(a)) {
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT("delta", eem_conv_form, c->delta.p, 2, st, 0, 0);
+                RECIT("coords1_out", eem_conv_form, c1nxt, 2, st, 0, 0);
             } else {                                                         // (maps of less than 256 cells: the generic kernel, then the sum)
                 a.epi = GEPI_PLAIN; a.e0 = nullptr; a.out2 = nullptr;
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT("delta", eem_conv_form, c->delta.p, 2, st, 0, 0);
                 if ((rc = er_sum_launch(c1nxt, c1cur, c->delta.p, (long)B * 2 * g, st)) != EEM_OK) return rc;
+                RECIT("coords1_out", er_last_form, c1nxt, 2, st, 0, 0);
             }
             if (emit) {
-                pend.on = true; pend.c1 = c1nxt; pend.hidden = net; pend.oi = c->final_only ? 0 : it;
+                pend.on = true; pend.c1 = c1nxt; pend.hidden = net; pend.oi = c->final_only ? 0 : it; pend.it = it;
                 if (it == iters - 1 || (it == 0 && keep)) {                  // nothing follows / the kept stages are copied on `st`
                     if ((rc = fork()) != EEM_OK || (rc = side_mask()) != EEM_OK || (rc = join()) != EEM_OK) return rc;
                 }
@@ -954,15 +1073,19 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                 a = conv_args(c, c->heads1, B, h8, w8, c->fhid.p, 512, 0, GACT_RELU);
                 set_seg(a, 0, net, 128, 128, 0);
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT("fhid", eem_conv_form, c->fhid.p, 256, st, 512, 0);
+                RECIT("mhid", eem_conv_form, c->fhid.p, 256, st, 512, 256);
                 mh = c->fhid.p; head_ct = 512; mh_off = 256;
             } else {
                 a = conv_args(c, c->fh1, B, h8, w8, c->fhid.p, 256, 0, GACT_RELU);
                 set_seg(a, 0, net, 128, 128, 0);
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT("fhid", eem_conv_form, c->fhid.p, 256, st, 0, 0);
                 if (emit) {
                     a = conv_args(c, c->mk0, B, h8, w8, c->mhid.p, 256, 0, GACT_RELU);
                     set_seg(a, 0, net, 128, 128, 0);
                     if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                    RECIT("mhid", eem_conv_form, c->mhid.p, 256, st, 0, 0);
                 }
             }
             if (!emit) {
@@ -970,7 +1093,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
                 a = conv_args(c, c->fh2, B, h8, w8, c->delta.p, 2, 0, GACT_NONE);
                 set_seg(a, 0, c->fhid.p, 256, head_ct, 0);
                 if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                RECIT("delta", eem_conv_form, c->delta.p, 2, st, 0, 0);
                 if ((rc = er_axpy_launch(c1cur, c->delta.p, (long)B * 2 * g, st)) != EEM_OK) return rc;
+                RECIT("coords1_out", er_last_form, c1cur, 2, st, 0, 0);
                 continue;
             }
             // the flow head's last conv (256 -> 2) beside the mask head's (256 -> 576)
@@ -978,21 +1103,29 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             a = conv_args(c, c->fh2, B, h8, w8, c->delta.p, 2, 0, GACT_NONE);
             set_seg(a, 0, c->fhid.p, 256, head_ct, 0);
             if ((rc = gconv_launch(a, sd)) != EEM_OK) return rc;
+            RECIT("delta", eem_conv_form, c->delta.p, 2, sd, 0, 0);
             a = conv_args(c, c->mk2, B, h8, w8, c->mask.p, 576, 0, GACT_NONE);
             set_seg(a, 0, mh, 256, head_ct, mh_off);
             a.out_scale = 0.25f;
             if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+            RECIT("mask", eem_conv_form, c->mask.p, 576, st, 0, 0);
             if ((rc = join()) != EEM_OK) return rc;
             // :149 coords1 = coords1 + delta_flow and :155-157 the convex upsampling of coords1 - coords0, one launch
             const int oi = c->final_only ? 0 : it;
             if (fuse_small) {
                 if ((rc = er_convex_up_launch(c->c0.p, c1cur, c->mask.p, lout + (size_t)oi * B * 2 * in_h * in_w, B, h8, w8, pad[2],
                                               pad[0], in_h, in_w, st, c->delta.p, c1nxt)) != EEM_OK) return rc;
+                RECIT("coords1_out", er_last_form, c1nxt, 2, st, 0, 0);
                 float* t = c1p; c1p = c1q; c1q = t;
             } else {
                 if ((rc = er_axpy_launch(c->c1.p, c->delta.p, (long)B * 2 * g, st)) != EEM_OK) return rc;
+                RECIT("coords1_out", er_last_form, c->c1.p, 2, st, 0, 0);
                 if ((rc = er_convex_up_launch(c->c0.p, c->c1.p, c->mask.p, lout + (size_t)oi * B * 2 * in_h * in_w, B, h8, w8, pad[2],
                                               pad[0], in_h, in_w, st)) != EEM_OK) return rc;
+            }
+            if (recd && it < c->rec_iters) {
+                snprintf(rname, sizeof(rname), "it%d.pred", it);
+                if ((rc = rec_stage(c, rname, er_last_form, lout + (size_t)oi * B * 2 * in_h * in_w, B, 2, in_h, in_w, st)) != EEM_OK) return rc;
             }
         }
         if (it == 0 && keep) {
@@ -1012,6 +1145,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     c->stages_valid = keep;
     c->fmap_imgs = nimg;
     c->stream_pairs = sp ? B : 0;
+    if (recd) c->rec_need = std::max(c->rec_need, c->rec_used);
+#undef REC
+#undef RECIT
     return EEM_OK;
 }
 
@@ -1021,7 +1157,11 @@ extern "C" int eraft_forward(eraft_ctx* c, const float* e1, const float* e2, int
     EEM_REQUIRE(c->loaded, "eraft_forward: no weights loaded");
     EEM_REQUIRE(batch >= 1 && in_h >= 1 && in_w >= 1 && iters >= 1, "eraft_forward: bad sizes");
     EEM_HIP_CHECK(hipSetDevice(c->device));
-    return eraft_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, iters, flow_init, out, (hipStream_t)stream);
+    int rc = eraft_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, iters, flow_init, out, (hipStream_t)stream);
+    // the stage recorder's arena was too small: that forward measured it; the same forward again, with the arena grown, fills it
+    if (rc == EEM_OK && c->rec_on && c->rec_used > c->rec_buf.cap)
+        rc = eraft_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, iters, flow_init, out, (hipStream_t)stream);
+    return rc;
 }
 
 // n independent samples of the evaluation loop (test_mvsec.py:580-597: one model(events1, events2) per sample at batch 1), each in its
@@ -1042,6 +1182,8 @@ extern "C" int eraft_forward_many(eraft_ctx* c, int n, const float* const* event
     int rc = ensure(c->many_out, (size_t)nout * n * per);
     if (rc != EEM_OK) return rc;
     if ((rc = eraft_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, iters, nullptr, c->many_out.p, st)) != EEM_OK) return rc;
+    if (c->rec_on && c->rec_used > c->rec_buf.cap &&                      // (the recorder's arena has grown: see eraft_forward)
+        (rc = eraft_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, iters, nullptr, c->many_out.p, st)) != EEM_OK) return rc;
     for (int i = 0; i < n; ++i)                                          // [nout][n][2][H][W] -> sample i's [nout][1][2][H][W]
         EEM_HIP_CHECK(hipMemcpy2DAsync(flow_out[i], per * 4, c->many_out.p + (size_t)i * per, (size_t)n * per * 4, per * 4, nout,
                                        hipMemcpyDeviceToDevice, st));
@@ -1127,6 +1269,48 @@ extern "C" int eraft_keep_stages(eraft_ctx* c, int enable) {
     return EEM_OK;
 }
 
+// The stage recorder (include/eemflow_hip.h): prefixes = comma-separated name prefixes, NULL = off.
+extern "C" int eraft_record_stages(eraft_ctx* c, const char* prefixes, int iterations) {
+    EEM_REQUIRE(c, "eraft_record_stages: NULL context");
+    EEM_REQUIRE(prefixes == nullptr || iterations >= 0, "eraft_record_stages: iterations = %d", iterations);
+    c->rec_prefix.clear();
+    c->rec_on = prefixes != nullptr;
+    c->rec_iters = prefixes ? iterations : 0;
+    if (prefixes) {
+        const std::string all(prefixes);
+        size_t i = 0;
+        while (i <= all.size()) {
+            size_t j = all.find(',', i);
+            if (j == std::string::npos) j = all.size();
+            c->rec_prefix.push_back(all.substr(i, j - i));                   // (an empty prefix matches every name)
+            i = j + 1;
+        }
+    }
+    return EEM_OK;
+}
+
+// The form of the last er_*_launch of this thread (the operator-level calls that go straight to one: eemop_replicate_pad, ...).
+extern "C" int eraft_last_form(char* buf, int cap) {
+    EEM_REQUIRE(buf && cap > 0, "eraft_last_form: NULL buffer");
+    snprintf(buf, (size_t)cap, "%s", er_last_form);
+    return EEM_OK;
+}
+
+extern "C" int eraft_stage_list(eraft_ctx* c, char* buf, size_t cap, size_t* need) {
+    EEM_REQUIRE(c && need, "eraft_stage_list: NULL argument");
+    std::string s;
+    for (const StageRec& r : c->rec) {
+        char line[160];
+        snprintf(line, sizeof(line), "%s %s %d %d %d %d\n", r.name.c_str(), r.form.empty() ? "-" : r.form.c_str(), r.dims[0], r.dims[1], r.dims[2], r.dims[3]);
+        s += line;
+    }
+    *need = s.size() + 1;
+    if (buf == nullptr) return EEM_OK;
+    EEM_REQUIRE(cap >= s.size() + 1, "eraft_stage_list: the list needs %zu bytes, the buffer holds %zu", s.size() + 1, cap);
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return EEM_OK;
+}
+
 // The evaluation loop reads flow_list[-1] only (test_mvsec.py:1455): with this switch the forward writes that one prediction.
 extern "C" int eraft_set_final_only(eraft_ctx* c, int enable) {
     EEM_REQUIRE(c, "eraft_set_final_only: NULL context");
@@ -1168,8 +1352,15 @@ extern "C" int eraft_get_stage(eraft_ctx* c, const char* name, float* dst, size_
         EEM_REQUIRE(!c->alt_corr && c->pyr[l].p, "eraft_get_stage: '%s' does not exist - the last forward computed the correlation on the fly", name);
         src = c->pyr[l].p; dims[0] = c->B * c->h8 * c->w8; dims[1] = 1; dims[2] = c->ph[l]; dims[3] = c->pw[l];
     } else {
-        eem_set_error("eraft_get_stage: unknown stage '%s'", name);
-        return EEM_ERR_ARG;
+        const StageRec* hit = nullptr;                                       // a name of the stage recorder (eraft_record_stages)
+        for (const StageRec& r : c->rec)
+            if (r.name == nm) { hit = &r; break; }
+        if (!hit) {
+            eem_set_error("eraft_get_stage: unknown stage '%s'", name);
+            return EEM_ERR_ARG;
+        }
+        src = c->rec_buf.p + hit->off;
+        for (int i = 0; i < 4; ++i) dims[i] = hit->dims[i];
     }
     const size_t n = (size_t)dims[0] * dims[1] * dims[2] * dims[3];
     if (dst == nullptr) return EEM_OK;
@@ -1187,11 +1378,21 @@ extern "C" int eraft_corr_lookup(eraft_ctx* c, const float* fmap1, const float* 
                                  int h, int w, float* out, void* stream) {
     EEM_REQUIRE(c && fmap1 && fmap2 && coords && out, "eraft_corr_lookup: NULL argument");
     EEM_HIP_CHECK(hipSetDevice(c->device));
-    int rc = build_pyramid(c, fmap1, fmap2, batch, ch, h, w, (hipStream_t)stream);
+    int rc;
+    c->rec.clear();
+    c->rec_used = 0;
+    if (c->rec_on) {                                                     // the recorder: "pyr0" .. "pyr3" and "corr", each with the form that ran
+        size_t need = (size_t)batch * 324 * h * w + 64 * 5;
+        for (int l = 0, ph = h, pw = w; l < 4; ++l, ph /= 2, pw /= 2) need += (size_t)batch * h * w * ph * pw;
+        if ((rc = ensure(c->rec_buf, need)) != EEM_OK) return rc;
+    }
+    rc = build_pyramid(c, fmap1, fmap2, batch, ch, h, w, (hipStream_t)stream, c->rec_on);
     if (rc != EEM_OK) return rc;
     c->B = batch; c->h8 = h; c->w8 = w; c->have_last = true;
     c->stream_pairs = 0; c->fmap_imgs = 2 * batch;
-    return run_lookup(c, coords, out, 324, batch, h, w, (hipStream_t)stream);
+    if ((rc = run_lookup(c, coords, out, 324, batch, h, w, (hipStream_t)stream)) != EEM_OK) return rc;
+    if (c->rec_on) rc = rec_stage(c, "corr", er_last_form, out, batch, 324, h, w, (hipStream_t)stream);
+    return rc;
 }
 
 // ERAFT.upsample_flow (model/eraft.py:83-94): flow [B][2][h][w], mask [B][576][h][w] -> out [B][2][8h][8w]

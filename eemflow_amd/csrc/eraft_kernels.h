@@ -3,6 +3,10 @@
 #pragma once
 #include "common.h"
 
+// the kernel form the last er_*_launch of this thread took ("instnorm_reg5", "allpairs_lds", "lookup_flat16", ...): what a stage
+// recorder files beside a launch's output, as eem_conv_form does for the convolutions
+extern thread_local const char* er_last_form;
+
 // F.pad(mode='replicate') of [nc][h][w] -> [nc][h+top+bottom][w+left+right]   (utils/image_utils.py:139-140)
 int er_pad_launch(const float* in, float* out, int nc, int h, int w, int left, int right, int top, int bottom, hipStream_t st);
 // both event volumes of a sample (in0 -> planes [0, nc), in1 -> [nc, 2 nc) of out) as one launch

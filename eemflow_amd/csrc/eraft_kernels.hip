@@ -203,6 +203,21 @@ __global__ __launch_bounds__(1024) void instnorm_apply_kernel(const float* __res
     }
 }
 
+// The all-pairs kernels add their C products in runs of kApRun channels: the MFMA accumulators hold one run and are then added to a
+// second set.  Feature maps have a per-channel mean, so the C products of a value mostly share a sign, and ONE chain of C / 2 MFMA
+// accumulations rounds every partial sum of a steadily growing total: rms error 0.29 sqrt(C / 3) = 2.7 u of sum |terms| at C = 256
+// (measured 2.84 by tests/test_gpu_eraft_stage_fp64.py) against 0.6 - 0.7 u in runs of 32.  All three kernels cut the runs at the same
+// channels and add in the same order: their results stay bit for bit the same.
+constexpr int kApRun = 32;
+__device__ __forceinline__ void ap_flush(f32x16 (&tot)[2][2], f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { tot[s][t][r] += acc[s][t][r]; acc[s][t][r] = 0.f; }
+}
+
 // D[p1][p2] tiles of 64x64 per wave on v_mfma_f32_32x32x2_f32; both operands are read with unit stride along
 // the pixel index (A[i=p1][k=c] = f1[c][p1], B[k=c][j=p2] = f2[c][p2]) and each accumulator register is a
 // 128-B run of p2 for one p1 row.
@@ -224,13 +239,13 @@ __global__ __launch_bounds__(256) void allpairs_odd_kernel(const float* __restri
         ma[t] = m0 + t * 32 + j; mv[t] = ma[t] < hw; ma[t] = mv[t] ? ma[t] : 0;
         nb[t] = n0 + t * 32 + j; nv[t] = nb[t] < hw; nb[t] = nv[t] ? nb[t] : 0;
     }
-    f32x16 acc[2][2];
+    f32x16 acc[2][2], tot[2][2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[s][t][r] = 0.f;
+            for (int r = 0; r < 16; ++r) { acc[s][t][r] = 0.f; tot[s][t][r] = 0.f; }
 #pragma unroll 4
     for (int k = 0; k < c; k += 2) {
         const int kk = k + h;
@@ -248,7 +263,9 @@ __global__ __launch_bounds__(256) void allpairs_odd_kernel(const float* __restri
 #pragma unroll
             for (int t = 0; t < 2; ++t)
                 acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[t], acc[s][t], 0, 0, 0);
+        if (((k + 2) & (kApRun - 1)) == 0) ap_flush(tot, acc);
     }
+    ap_flush(tot, acc);
     float* o = out + (size_t)b * hw * hw;
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -259,7 +276,7 @@ __global__ __launch_bounds__(256) void allpairs_odd_kernel(const float* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int p1 = m0 + s * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (p1 < hw) o[(size_t)p1 * hw + p2] = acc[s][t][r] * scale;
+                if (p1 < hw) o[(size_t)p1 * hw + p2] = tot[s][t][r] * scale;
             }
         }
 }
@@ -279,13 +296,13 @@ __global__ __launch_bounds__(256) void allpairs_kernel(const float* __restrict__
     const int ma = m0 + 2 * j, nb = n0 + 2 * j;
     const bool mv = ma < hw, nv = nb < hw;
     const int mac = mv ? ma : 0, nbc = nv ? nb : 0;
-    f32x16 acc[2][2];
+    f32x16 acc[2][2], tot[2][2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[s][t][r] = 0.f;
+            for (int r = 0; r < 16; ++r) { acc[s][t][r] = 0.f; tot[s][t][r] = 0.f; }
 #pragma unroll 4
     for (int k = 0; k < c; k += 2) {
         const int kk = k + h;
@@ -300,7 +317,9 @@ __global__ __launch_bounds__(256) void allpairs_kernel(const float* __restrict__
 #pragma unroll
             for (int t = 0; t < 2; ++t)
                 acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[t], acc[s][t], 0, 0, 0);
+        if (((k + 2) & (kApRun - 1)) == 0) ap_flush(tot, acc);
     }
+    ap_flush(tot, acc);
     float* o = out + (size_t)b * hw * hw;
     if (!nv) return;
 #pragma unroll
@@ -308,7 +327,7 @@ __global__ __launch_bounds__(256) void allpairs_kernel(const float* __restrict__
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int p1 = m0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * h) + s;
-            if (p1 < hw) *reinterpret_cast<f32x2*>(o + (size_t)p1 * hw + nb) = f32x2{acc[s][0][r] * scale, acc[s][1][r] * scale};
+            if (p1 < hw) *reinterpret_cast<f32x2*>(o + (size_t)p1 * hw + nb) = f32x2{tot[s][0][r] * scale, tot[s][1][r] * scale};
         }
 }
 
@@ -317,11 +336,11 @@ __global__ __launch_bounds__(256) void allpairs_kernel(const float* __restrict__
 // Here a block's 128 x 128 tile walks the channels in chunks of 16: the chunk's [16][128] slabs of both feature maps (8 KB each, rows of
 // 512 contiguous bytes) arrive by 16-byte LDS-DMA, double-buffered, one barrier per chunk; a wave's two operands of a k-step are one
 // 8-byte LDS read each (same pixel mapping: row j of tile t = pixel 2 j + t), so each staged byte feeds both waves that need it.
-// 32 KB of LDS and 64 accumulator registers per block: four blocks per CU cover each other's waits.  Needs c % 16 == 0, hw % 4 == 0 and
+// 32 KB of LDS and two sets of 64 accumulator registers (a run's and the total's) per wave.  Needs c % 16 == 0, hw % 4 == 0 and
 // 16-byte aligned maps (the launch checks); pixels past hw read a zero page.
 #define AP_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 #define AP_GLB(p) ((const __attribute__((address_space(1))) void*)(p))
-__global__ __launch_bounds__(256, 4) void allpairs_lds_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
+__global__ __launch_bounds__(256, 3) void allpairs_lds_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
                                                               float* __restrict__ out, int c, int hw, float scale,
                                                               const float* __restrict__ zero_page) {
     constexpr int KC = 16, TP = 128;                          // channels per chunk, pixels per block side
@@ -360,13 +379,13 @@ __global__ __launch_bounds__(256, 4) void allpairs_lds_kernel(const float* __res
         }
     };
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;    // this wave's 64 x 64 corner of the block tile
-    f32x16 acc[2][2];
+    f32x16 acc[2][2], tot[2][2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[s][t][r] = 0.f;
+            for (int r = 0; r < 16; ++r) { acc[s][t][r] = 0.f; tot[s][t][r] = 0.f; }
     const int nchunks = c / KC;
     issue(0);
     for (int ch = 0; ch < nchunks; ++ch) {
@@ -386,7 +405,9 @@ __global__ __launch_bounds__(256, 4) void allpairs_lds_kernel(const float* __res
                 for (int t = 0; t < 2; ++t)
                     acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[t], acc[s][t], 0, 0, 0);
         }
+        if ((((ch + 1) * KC) & (kApRun - 1)) == 0) ap_flush(tot, acc);
     }
+    ap_flush(tot, acc);
     float* o = out + (size_t)b * hw * hw;
     const int m0 = mb + wm, nb = nb0 + wn + 2 * j;
     if (nb >= hw) return;
@@ -395,7 +416,7 @@ __global__ __launch_bounds__(256, 4) void allpairs_lds_kernel(const float* __res
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int p1 = m0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * h) + s;
-            if (p1 < hw) *reinterpret_cast<f32x2*>(o + (size_t)p1 * hw + nb) = f32x2{acc[s][0][r] * scale, acc[s][1][r] * scale};
+            if (p1 < hw) *reinterpret_cast<f32x2*>(o + (size_t)p1 * hw + nb) = f32x2{tot[s][0][r] * scale, tot[s][1][r] * scale};
         }
 }
 
@@ -453,13 +474,24 @@ __global__ __launch_bounds__(128) void pool2x3_kernel(const float* __restrict__ 
 // instead of four dependent ones (a load in one arm of a lane-dependent conditional is a branch + s_waitcnt vmcnt(0)); it also loads
 // the corners that fall outside the map, which the coarse levels have many of, so launches that fill the chip (batch 4) keep the
 // conditional form (E-RAFT 640x480: batch 1 149.0 -> 150.8 frames/s with FLAT, batch 4 198 -> 194)
+// The sample position along one axis, as the reference forms it: v -> 2 v / (size - 1) - 1 -> ((. + 1) / 2) (size - 1), its floor and
+// its fractional part, every operation rounded by itself.  Contraction is off in here: fused, t = iv - floor(iv) is formed from the
+// UNROUNDED product - off by up to half an ulp of the coordinate, which beside an integer coordinate (every pixel of the first iteration)
+// is a weight of +-1e-6 on a neighbouring cell instead of 0 (found by tests/test_gpu_eraft_stage_fp64.py in the FLAT instantiations).
+__device__ __forceinline__ void sample_axis(float v, int size, float& fl, float& t) {
+#pragma clang fp contract(off)
+    const float vn = 2.f * v / (float)(size - 1) - 1.f;
+    const float iv = ((vn + 1.f) * 0.5f) * (float)(size - 1);
+    fl = floorf(iv);
+    t = iv - fl;
+}
+
 template <bool FLAT>
 __device__ __forceinline__ float sample_bilinear(const float* __restrict__ img, int h, int w, float x, float y) {
-    const float xn = 2.f * x / (float)(w - 1) - 1.f, yn = 2.f * y / (float)(h - 1) - 1.f;
-    const float ix = ((xn + 1.f) * 0.5f) * (float)(w - 1), iy = ((yn + 1.f) * 0.5f) * (float)(h - 1);
-    const float fx = floorf(ix), fy = floorf(iy);
+    float fx, fy, tx, ty;
+    sample_axis(x, w, fx, tx);
+    sample_axis(y, h, fy, ty);
     const int x0 = (int)fx, y0 = (int)fy;
-    const float tx = ix - fx, ty = iy - fy;
     float v00, v01, v10, v11;
     if (FLAT) {
         const int ya = min(max(y0, 0), h - 1), yb = min(max(y0 + 1, 0), h - 1), xa = min(max(x0, 0), w - 1), xb = min(max(x0 + 1, 0), w - 1);
@@ -541,11 +573,9 @@ __global__ __launch_bounds__(128) void altcorr_kernel(AltCorrArgs a) {
     const int h = a.ph[lvl], w = a.pw[lvl];
     auto tap = [](float c, float scv, int off, int size, int& i0, float& t) {
         const float v = c / scv + (float)(off - 4);
-        const float vn = 2.f * v / (float)(size - 1) - 1.f;
-        const float iv = ((vn + 1.f) * 0.5f) * (float)(size - 1);
-        const float f = floorf(iv);
+        float f;
+        sample_axis(v, size, f, t);
         i0 = (int)fminf(fmaxf(f, -16.f), (float)size + 16.f);    // for the conversion only: a clamped window has no cell in the map
-        t = iv - f;
     };
     int xb, yb; float t0;
     tap(cx, sc, 0, w, xb, t0);
@@ -557,8 +587,16 @@ __global__ __launch_bounds__(128) void altcorr_kernel(AltCorrArgs a) {
         if (Y >= 0 && Y < h && X >= 0 && X < w) {
             const float* q = a.f2[lvl] + (size_t)b * a.c * h * w + (size_t)Y * w + X;
             const size_t plane = (size_t)h * w;
-#pragma unroll 8
-            for (int ch = 0; ch < a.c; ++ch) acc += f1s[ch] * q[ch * plane];
+            // eight partial sums, added pairwise: feature maps share a sign per channel, so the C products mostly do too, and one
+            // chain of C additions rounds every partial sum of a steadily growing total (rms error 2 u of sum |terms| at C = 256)
+            float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            int ch = 0;
+            for (; ch + 8 <= a.c; ch += 8) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) part[e] += f1s[ch + e] * q[(ch + e) * plane];
+            }
+            for (; ch < a.c; ++ch) part[0] += f1s[ch] * q[ch * plane];
+            acc = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
         }
         win[tid] = acc * a.scale;
     }
@@ -675,6 +713,8 @@ inline unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
+thread_local const char* er_last_form = "";
+
 // pad4_kernel's grid: 32 threads along a row of ow4 16-byte pieces, 32 rows per block, the row blocks folded over grid.y and grid.z
 static dim3 pad4_grid(long rows, int ow4) {
     const long rb = (rows + 31) / 32;
@@ -687,6 +727,7 @@ int er_pad2_launch(const float* in0, const float* in1, float* out, int nc, int h
     const int oh = h + top + bottom, ow = w + left + right;
     if ((ow & 3) == 0 && ((uintptr_t)out & 15) == 0) {
         hipLaunchKernelGGL(pad4_kernel, pad4_grid(2L * nc * oh, ow / 4), dim3(256), 0, st, in0, out, nc, h, w, left, top, oh, ow, in1);
+        er_last_form = "pad4_pair";
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }
@@ -696,7 +737,9 @@ int er_pad2_launch(const float* in0, const float* in1, float* out, int nc, int h
 
 int er_pad_launch(const float* in, float* out, int nc, int h, int w, int left, int right, int top, int bottom, hipStream_t st) {
     const int oh = h + top + bottom, ow = w + left + right;
-    if ((ow & 3) == 0 && ((uintptr_t)out & 15) == 0)
+    const bool v4 = (ow & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    er_last_form = v4 ? "pad4" : "pad";
+    if (v4)
         hipLaunchKernelGGL(pad4_kernel, pad4_grid((long)nc * oh, ow / 4), dim3(256), 0, st, in, out, nc, h, w, left, top, oh, ow, (const float*)nullptr);
     else
         hipLaunchKernelGGL(pad_kernel, dim3(blocks((long)nc * oh * ow)), dim3(256), 0, st, in, out, nc, h, w, left, top, oh, ow);
@@ -715,9 +758,11 @@ int er_instnorm_launch(const float* x, float* out, const float* res, int planes,
         const int chunks = ceil_div(hw >> 2, kNormChunk4);
         hipLaunchKernelGGL(instnorm_stats_kernel, dim3(chunks, planes), dim3(1024), 0, st, x, hw, chunks, stats);
         hipLaunchKernelGGL(instnorm_apply_kernel, dim3(chunks, planes), dim3(1024), 0, st, x, out, res, hw, chunks, stats, relu_inner);
+        er_last_form = "instnorm_2pass";
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }
+    er_last_form = al && hw <= 4 * 1024 * 5 ? "instnorm_reg5" : al && hw <= 4 * 1024 * 20 ? "instnorm_reg20" : "instnorm_plain";
     if (al && hw <= 4 * 1024 * 5) hipLaunchKernelGGL(instnorm_reg_kernel<5>, dim3(planes), dim3(1024), 0, st, x, out, res, hw, relu_inner);
     else if (al && hw <= 4 * 1024 * 20) hipLaunchKernelGGL(instnorm_reg_kernel<20>, dim3(planes), dim3(1024), 0, st, x, out, res, hw, relu_inner);
     else hipLaunchKernelGGL(instnorm_kernel, dim3(planes), dim3(256), 0, st, x, out, res, hw, relu_inner);
@@ -737,10 +782,12 @@ int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, 
             EEM_HIP_CHECK(hipMalloc(&zero_pages[dev], 256));
             EEM_HIP_CHECK(hipMemset(zero_pages[dev], 0, 256));
         }
+        er_last_form = "allpairs_lds";
         hipLaunchKernelGGL(allpairs_lds_kernel, grid, dim3(256), 0, st, f1, f2, out, c, hw, 1.0f / sqrtf((float)c), zero_pages[dev]);
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }
+    er_last_form = even ? "allpairs_l2" : "allpairs_odd";
     if (even) hipLaunchKernelGGL(allpairs_kernel, grid, dim3(256), 0, st, f1, f2, out, c, hw, 1.0f / sqrtf((float)c));
     else hipLaunchKernelGGL(allpairs_odd_kernel, grid, dim3(256), 0, st, f1, f2, out, c, hw, 1.0f / sqrtf((float)c));
     EEM_HIP_CHECK(hipGetLastError());
@@ -749,6 +796,7 @@ int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, 
 
 int er_pool2_launch(const float* in, float* out, long planes, int h, int w, hipStream_t st) {
     const long n = planes * (h / 2) * (w / 2);
+    er_last_form = "pool2";
     if (n == 0) return EEM_OK;
     hipLaunchKernelGGL(pool2_kernel, dim3(blocks(n)), dim3(256), 0, st, in, out, planes, h, w);
     EEM_HIP_CHECK(hipGetLastError());
@@ -765,6 +813,7 @@ int er_pool2x3_launch(const float* in, float* o1, float* o2, float* o3, long pla
         if ((rc = er_pool2_launch(in, o1, planes, h, w, st)) != EEM_OK || (rc = er_pool2_launch(o1, o2, planes, h1, w1, st)) != EEM_OK) return rc;
         return er_pool2_launch(o2, o3, planes, h2, w2, st);
     }
+    er_last_form = "pool2x3";
     if (planes == 0) return EEM_OK;
     hipLaunchKernelGGL(pool2x3_kernel, dim3((unsigned)nblk), dim3(128), (4 * w1 + 2 * w2) * sizeof(float), st, in, o1, o2, o3, h, w, ceil_div(h1, 4));
     EEM_HIP_CHECK(hipGetLastError());
@@ -781,6 +830,9 @@ int er_lookup_launch(const LookupArgs& a, hipStream_t st, hipEvent_t done_ev) {
     const char* epx = sw_raw<SW_EEM_LOOKUP_PX>();
     const int px = epx ? atoi(epx) : (blocks64 < kLookupFlatMax ? 16 : 64);
     const dim3 gt(ceil_div(a.h * a.w, px == 16 ? 16 : px == 32 ? 32 : 64), 4, a.batch);
+    const int pxk = px == 16 ? 16 : px == 32 ? 32 : 64;
+    er_last_form = blocks64 < kLookupFlatMax ? (pxk == 16 ? "lookup_flat16" : pxk == 32 ? "lookup_flat32" : "lookup_flat64")
+                                             : (pxk == 16 ? "lookup_cond16" : pxk == 32 ? "lookup_cond32" : "lookup_cond64");
     if (blocks64 < kLookupFlatMax) {
         if (px == 16) hipExtLaunchKernelGGL((lookup_tiled_kernel<true, 16>), gt, dim3(256), 0, st, nullptr, done_ev, 0, a);
         else if (px == 32) hipExtLaunchKernelGGL((lookup_tiled_kernel<true, 32>), gt, dim3(256), 0, st, nullptr, done_ev, 0, a);
@@ -795,30 +847,35 @@ int er_lookup_launch(const LookupArgs& a, hipStream_t st, hipEvent_t done_ev) {
 }
 
 int er_altcorr_launch(const AltCorrArgs& a, hipStream_t st) {
+    er_last_form = "altcorr";
     hipLaunchKernelGGL(altcorr_kernel, dim3(a.h * a.w, 4, a.batch), dim3(128), (a.c + 100) * sizeof(float), st, a);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int er_coords_init_launch(float* c0, float* c1, const float* init, int batch, int h, int w, hipStream_t st) {
+    er_last_form = "coords_init";
     hipLaunchKernelGGL(coords_init_kernel, dim3(blocks((long)batch * 2 * h * w)), dim3(256), 0, st, c0, c1, init, batch, h, w);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int er_flow_launch(const float* c0, const float* c1, float* dst, int dst_ctotal, int dst_coff, int batch, int hw, hipStream_t st) {
+    er_last_form = "flow";
     hipLaunchKernelGGL(flow_kernel, dim3(blocks((long)batch * 2 * hw)), dim3(256), 0, st, c0, c1, dst, dst_ctotal, dst_coff, batch, hw);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int er_axpy_launch(float* y, const float* x, long n, hipStream_t st) {
+    er_last_form = "axpy";
     hipLaunchKernelGGL(axpy_kernel, dim3(blocks(n)), dim3(256), 0, st, y, x, n);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int er_sum_launch(float* out, const float* a, const float* b, long n, hipStream_t st) {
+    er_last_form = "sum";
     hipLaunchKernelGGL(sum_kernel, dim3(blocks(n)), dim3(256), 0, st, out, a, b, n);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -826,6 +883,7 @@ int er_sum_launch(float* out, const float* a, const float* b, long n, hipStream_
 
 int er_mul_channels_launch(float* out, const float* a, int a_ctotal, int a_coff, const float* b, int batch, int c, long hw, hipStream_t st) {
     const long n = (long)batch * c * hw;
+    er_last_form = "mul_channels";
     hipLaunchKernelGGL(mul_channels_kernel, dim3(blocks(n)), dim3(256), 0, st, out, a, a_ctotal, a_coff, b, c, hw, n);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -834,6 +892,7 @@ int er_mul_channels_launch(float* out, const float* a, int a_ctotal, int a_coff,
 int er_convex_up_launch(const float* c0, const float* c1, const float* mask, float* out, int batch, int h, int w, int top,
                         int left, int oh, int ow, hipStream_t st, const float* delta, float* c1n) {
     EEM_REQUIRE((delta == nullptr) == (c1n == nullptr) && (c1n == nullptr || c1n != c1), "er_convex_up_launch: delta and coords1_next come together");
+    er_last_form = c1n ? "convex_up_fused" : "convex_up";
     hipLaunchKernelGGL(convex_up_kernel, dim3(blocks((long)batch * oh * ow + (c1n ? (long)batch * 2 * h * w : 0L))), dim3(256), 0, st, c0, c1,
                        mask, out, batch, h, w, top, left, oh, ow, delta, c1n);
     EEM_HIP_CHECK(hipGetLastError());

@@ -166,6 +166,7 @@ class ERAFT(HipModel, nn.Module):
         self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn='batch', dropout=0, n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.args, hidden_dim=hdim)
         self.keep_stages = False       # True: the first iteration's corr0 / net1 / mask1 / delta1 stay readable through stage()
+        self.record_stages = None      # (prefixes, iterations): eraft_record_stages - every matching launch's output through stage() / stage_names()
         self.final_only = False        # True (inference route): the returned list holds the last prediction only - what test_mvsec.py:1455 reads
         self.alternate_corr = False    # True (inference route): correlation features on the fly, no all-pairs volume (RAFT's alternate_corr)
         self.warm_start = False        # True: forward_stream starts each pair from the previous pair's forward-interpolated flow_low
@@ -194,6 +195,12 @@ class ERAFT(HipModel, nn.Module):
     def _configure(self):
         L = _lib.lib()
         _lib.check(L.eraft_keep_stages(self._ctx, 1 if self.keep_stages else 0))
+        # the stage recorder: a context starts with it off, and the call is made only when the setting changes
+        want = None if self.record_stages is None else (tuple(self.record_stages[0]), int(self.record_stages[1]))
+        last = getattr(self, "_recorder_set", None)                        # (context, setting) of the last call made
+        if want != (last[1] if last is not None and last[0] == self._ctx.value else None):
+            _lib.check(L.eraft_record_stages(self._ctx, None if want is None else ",".join(want[0]).encode(), 0 if want is None else want[1]))
+            self._recorder_set = (self._ctx.value, want)
         _lib.check(L.eraft_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
         _lib.check(L.eraft_set_alternate_corr(self._ctx, 1 if self.alternate_corr else 0))
         _lib.check(L.eraft_set_final_only(self._ctx, 1 if self.final_only else 0))
@@ -227,6 +234,19 @@ class ERAFT(HipModel, nn.Module):
                                                 fi.data_ptr() if fi is not None else None, out.data_ptr(),
                                                 _lib.current_stream_ptr(e1.device)))
         return (events1, events2), [out[i] for i in range(nout)]
+
+    def stage_names(self):
+        """[(name, form, (n, c, h, w))] of everything the stage recorder (`record_stages`) filed in the last forward, in launch order."""
+        L = _lib.lib()
+        need = ctypes.c_size_t()
+        _lib.check(L.eraft_stage_list(self._ctx, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        _lib.check(L.eraft_stage_list(self._ctx, buf, need.value, ctypes.byref(need)))
+        out = []
+        for line in buf.value.decode().splitlines():
+            name, form, *dims = line.split()
+            out.append((name, "" if form == "-" else form, tuple(int(d) for d in dims)))
+        return out
 
     def forward_many(self, frames, iters=12):
         """Several INDEPENDENT samples of the evaluation loop (test_mvsec.py:580-597: one `model(events1, events2)` per sample at batch 1)

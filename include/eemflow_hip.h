@@ -519,6 +519,27 @@ int eraft_forward_many(eraft_ctx* ctx, int n, const float* const* events1, const
  * "delta1" (after the first update). */
 int eraft_keep_stages(eraft_ctx* ctx, int enable);
 
+/* Stage recorder, for tests that hold every launch of eraft_forward / eraft_forward_many to a reference of that one launch (off by
+ * default; eraft_forward_stream records nothing).  prefixes: comma-separated name prefixes ("fnet.,pyr,it0.corr"; "" = everything),
+ * NULL = off.  While on, the forward enqueues - behind every launch whose name starts with one of them, on the stream that launch ran
+ * on - a device copy of that launch's output, filed under the name with the kernel form that wrote it; it launches no kernel
+ * differently, and its predictions are bit for bit those of the forward with the recorder off.  Update iterations 0 .. iterations - 1
+ * are recorded.  The copies live in one arena sized by the forward before: a forward whose records do not fit is run a second time.
+ * Names:  "pad";  "<net>.conv1", "<net>.norm1", "<net>.layer<1..3>.<0|1>.conv1 | norm1 | conv2 | norm2 | down | norm3" for <net> =
+ * "fnet" (convs without activation, every InstanceNorm) and "cnet" (convs with the eval BatchNorm, ReLU and residual folded in; no norm
+ * entries);  "fmap", "net0", "inp", "czr0", "czr1", "cq0", "cq1" (the context features' share of the GRU convs);  "pyr0".."pyr3", or
+ * "f2l1".."f2l3" (pooled fmap2) with eraft_set_alternate_corr;  per iteration K "itK.coords1_in", "itK.corr", "itK.flow", "itK.flo1",
+ * "itK.cor1", "itK.corflo.c" (channels 0..191) and "itK.corflo.f" (192..255), "itK.motion" (channels 0..125), "itK.gru<0|1>.z",
+ * ".r" (only where r itself is stored: EEM_ERAFT_NO_ZR=1), ".rh", ".h", "itK.fhid", "itK.delta", "itK.coords1_out", "itK.mhid",
+ * "itK.mask", "itK.pred".  eraft_corr_lookup records "pyr0".."pyr3" and "corr".  eraft_get_stage serves the recorded names (after its
+ * own); eraft_stage_list writes one line "name form n c h w" per record of the last call ("-": no form), *need = the bytes it takes
+ * (buf NULL: only that). */
+int eraft_record_stages(eraft_ctx* ctx, const char* prefixes, int iterations);
+int eraft_stage_list(eraft_ctx* ctx, char* buf, size_t capacity, size_t* need);
+/* The kernel form of this thread's last E-RAFT helper launch (padding, instance norm, all-pairs, pooling, lookup, convex upsampling,
+ * ...), as eemop_last_conv_form names the convolutions': what the operator-level calls that make one such launch ran. */
+int eraft_last_form(char* buf, int capacity);
+
 /* Correlation features computed on the fly instead of from an all-pairs volume (1: on, 0 = default: the volume stays resident).
  * Replaces the `alt_cuda_corr` pattern of model/flowformer/corr.py:60-91 (RAFT's `alternate_corr`): the 81 taps of a
  * pixel at level l are bilinear samples of <fmap1[:, p], avg_pool2d^l(fmap2)[:, q]> / sqrt(C) over the 10 x 10 cells its window

@@ -458,3 +458,204 @@ def check_form(name, form, got, ref, mag, tile=None, ref32=None):
         rec["form"] = form
         return rec
     return check(name, got, ref, mag, form_family(form), tile=tile, form=form)
+
+
+# --------------------------------------------------------------------------------- E-RAFT inference, launch by launch (eraft_record_stages)
+# tests/test_gpu_eraft_stage_fp64.py and tests/test_fp64_bounds_eraft.py: every launch of eraft_forward the stage recorder files, against
+# an fp64 evaluation of that one launch on the GPU's own recorded input to it.  Three criteria, none fitted to the kernels under test:
+#   1. launches that are plain sums (every convolution whose epilogue is none / ReLU / out_scale / a residual sum, all-pairs, pooling):
+#      `check` under the family of the form that ran (FORM_FAMILY; the Winograd launches "f4" -> wino4, "wnc" -> wino2, "stem7_c<n>" and
+#      the all-pairs forms -> direct, the pooling forms -> pool);
+#   2. launches of a short, fixed number of operations: max|z| against the count of roundings (ER_ROUNDINGS, derived below);
+#   3. launches that end in a nonlinear step (instance norm, sigmoid / tanh epilogues, GEPI_ZR, GEPI_GRU, convex upsampling):
+#      `check_decoder` - rms and max error at most KAPPA_DEC x those of torch's fp32 CPU evaluation (oracle/eraft_oracle.py's functions)
+#      of the same launch on the same input, plus one unit of fp32 rounding at the largest output.
+from . import eraft_oracle as R       # noqa: E402
+
+# (a table of its own: FORM_FAMILY is the operator-level ABI's, and tests/test_gpu_ops_fp64.py wants every name of it produced there)
+ER_FORM_FAMILY = {"f4": "wino4", "wnc": "wino2", "pool2": "pool", "pool2x3": "pool",
+                  "allpairs_lds": "direct", "allpairs_l2": "direct", "allpairs_odd": "direct", "altcorr": "direct"}
+ER_FORM_FAMILY.update({f"stem7_c{_c_}": "direct" for _c_ in range(1, 6)})
+
+
+def er_form_family(name):
+    """Family of a form the E-RAFT stage recorder reports: its own launches' names, else a gconv form's (form_family)."""
+    return ER_FORM_FAMILY[name] if name in ER_FORM_FAMILY else form_family(name)
+
+
+def er_check_form(name, form, got, ref, mag, tile=None):
+    """Criterion 1: `check` under the family of the form that ran."""
+    return check(name, got, ref, mag, er_form_family(form), tile=tile, form=form)
+
+# Criterion 2.  Every fp32 operation returns its exact result times (1 + d), |d| <= u = 2^-24; a result that passes through k roundings is
+# off by at most ((1 + u)^k - 1) <= k u (1 + k u) times the sum of |terms| = k u mag (1 + 1e-6).  The counts:
+#   pool    (a + b + c + d) * 0.25: three sums (the scale by a power of two is exact)                                         -> 3
+#   lookup  v00 (1 - tx)(1 - ty) + v01 tx (1 - ty) + v10 (1 - tx) ty + v11 tx ty with tx, ty given: a term is at most two weight
+#           roundings (1 - tx, 1 - ty) and two products, then three sums (a fused multiply-add only removes roundings)          -> 7
+#   flow = coords1 - coords0, coords1 + delta, r * h: one operation                                                             -> 1
+#   altcorr the lookup's blend (7) of window cells that are themselves C-term dot products: held to criterion 1 instead
+ER_ROUNDINGS = {"pool": 3, "lookup": 7, "flow": 1, "sum": 1, "mul": 1}
+ER_SLACK = 1.0 + 1e-5                  # (1 + k u)'s second-order term and the fp64 reference's own rounding
+
+
+def _f32(t):
+    return torch.as_tensor(t).detach().cpu().float()
+
+
+def check_roundings(name, got, ref, mag, kind, form=None):
+    """Criterion 2: max|z| <= the number of roundings of `kind` (ER_ROUNDINGS)."""
+    k = ER_ROUNDINGS[kind]
+    lim = Limits(k * ER_SLACK, float("inf"), float("inf"), float("inf"))
+    return check(name, got, ref, mag, lim, form=form or kind)
+
+
+def er_bn_fold(sd, prefix):
+    """(scale, shift) of an eval BatchNorm2d `prefix` ("cnet.norm1.") in fp64: y = x * scale + shift."""
+    w, b, rm, rv = (_d(sd[prefix + k]) for k in ("weight", "bias", "running_mean", "running_var"))
+    s = w / torch.sqrt(rv + 1e-5)
+    return s, b - rm * s
+
+
+def er_conv_ref(xs, w, b, stride=1, padding=(1, 1), bn=None, pre=None, res=None, relu=False, out_scale=1.0):
+    """The pre-activation of a conv launch of eraft_forward and its plain-sum epilogues, in fp64: v = conv(cat(xs), w) + b, then the
+    eval BatchNorm `bn` = (scale, shift), then + `pre` (the context features' share of a GRU conv); relu; relu(. + res) (the residual
+    blocks' tail); x out_scale.  mag is the sum of |terms| of everything in front of the (error-contracting) ReLUs."""
+    v, mag = op_conv_ref(xs, w, b, stride=stride, padding=padding)
+    if bn is not None:
+        s, t = (p.view(1, -1, 1, 1) for p in bn)
+        v, mag = v * s + t, mag * s.abs() + t.abs()
+    if pre is not None:
+        v, mag = v + _d(pre), mag + _d(pre).abs()
+    if relu:
+        v = v.clamp_min(0.0)
+    if res is not None:
+        v, mag = (v + _d(res)).clamp_min(0.0), mag + _d(res).abs()
+    s = float(np.float32(out_scale))
+    return v * s, mag * abs(s)
+
+
+def er_conv_f32(xs, w, b, stride=1, padding=(1, 1), bn=None, pre=None):
+    """torch's fp32 CPU evaluation of the same pre-activation (criterion 3's yardstick)."""
+    v = F.conv2d(torch.cat([_f32(x) for x in xs], 1), _f32(w), _f32(b) if b is not None else None, stride=stride, padding=tuple(padding))
+    if bn is not None:
+        v = v * bn[0].float().view(1, -1, 1, 1) + bn[1].float().view(1, -1, 1, 1)
+    return v + _f32(pre) if pre is not None else v
+
+
+def er_instnorm_ref(x, relu_inner, res=None, dtype=torch.float64):
+    """InstanceNorm2d(affine=False, eps=1e-5) per plane with the biased variance; relu_inner: relu(.); res: relu(. + res)
+    (model/extractor.py:43-57).  dtype float32: oracle/eraft_oracle.py's F.instance_norm, the fp32 CPU yardstick."""
+    if dtype == torch.float32:
+        v = F.instance_norm(_f32(x), eps=1e-5)
+    else:
+        x = _d(x)
+        m = x.mean((2, 3), keepdim=True)
+        var = ((x - m) ** 2).mean((2, 3), keepdim=True)
+        v = (x - m) / torch.sqrt(var + 1e-5)
+    if relu_inner:
+        v = torch.relu(v)
+    if res is not None:
+        v = torch.relu(v + torch.as_tensor(res).detach().cpu().to(dtype))
+    return v
+
+
+def er_allpairs_ref(f1, f2):
+    """model/corr.py:53-60: out[b, p1, p2] = sum_c f1[b, c, p1] f2[b, c, p2] / sqrt(C) as [B * hw, 1, h, w]; the factor is inside mag."""
+    f1, f2 = _d(f1), _d(f2)
+    b, c, h, w = f1.shape
+    a, bb = f1.reshape(b, c, h * w), f2.reshape(b, c, h * w)
+    s = 1.0 / float(np.sqrt(np.float32(c)))
+    ref = torch.einsum("bcp,bcq->bpq", a, bb) * s
+    mag = torch.einsum("bcp,bcq->bpq", a.abs(), bb.abs()) * s
+    return ref.reshape(b * h * w, 1, h, w), mag.reshape(b * h * w, 1, h, w)
+
+
+def er_lookup_geometry(coords, level, size):
+    """The sample positions of CorrBlock.__call__ at one pyramid level (model/corr.py:29-50 with model_utils.py:7-21), in fp32 exactly
+    as oracle/eraft_oracle.py's corr_lookup / bilinear_sampler and grid_sample compute them - they are part of the model's definition:
+    coords [B, 2, H, W] -> (x0, y0, tx, ty), each [B * H * W, 9, 9] (window index [i, j] = channel i * 9 + j: x + (i - 4), y + (j - 4))."""
+    h, w = size
+    c = _f32(coords).permute(0, 2, 3, 1)
+    n = c.shape[0] * c.shape[1] * c.shape[2]
+    r = 4
+    d = torch.linspace(-r, r, 2 * r + 1)
+    delta = torch.stack(torch.meshgrid(d, d, indexing="ij"), dim=-1)
+    pos = c.reshape(n, 1, 1, 2) / 2 ** level + delta.view(1, 9, 9, 2)
+    xg, yg = pos[..., 0], pos[..., 1]
+    xg = 2 * xg / (w - 1) - 1                                           # bilinear_sampler's normalisation ...
+    yg = 2 * yg / (h - 1) - 1
+    ix = ((xg + 1) / 2) * (w - 1)                                       # ... and grid_sample's own way back (align_corners=True)
+    iy = ((yg + 1) / 2) * (h - 1)
+    fx, fy = torch.floor(ix), torch.floor(iy)
+    return fx.long(), fy.long(), ix - fx, iy - fy
+
+
+def er_lookup_ref(pyr, coords, levels=(0, 1, 2, 3)):
+    """The correlation lookup against the GPU's own pyramid: positions, floor and the two weights in fp32 (er_lookup_geometry), only
+    the four-term blend in fp64; a corner outside the map is zero.  pyr[l]: [B * H * W, 1, h_l, w_l] -> (ref, mag), [B, 81 * len(levels), H, W]."""
+    b, _, hh, ww = coords.shape
+    refs, mags = [], []
+    for l in levels:
+        img = _d(pyr[l])[:, 0]
+        n, h, w = img.shape
+        x0, y0, tx, ty = er_lookup_geometry(coords, l, (h, w))
+        tx, ty = tx.double(), ty.double()
+        idx = torch.arange(n).view(n, 1, 1)
+        ref = torch.zeros(n, 9, 9, dtype=torch.float64)
+        mag = torch.zeros(n, 9, 9, dtype=torch.float64)
+        for dy, dx, wgt in ((0, 0, (1 - tx) * (1 - ty)), (0, 1, tx * (1 - ty)), (1, 0, (1 - tx) * ty), (1, 1, tx * ty)):
+            yy, xx = y0 + dy, x0 + dx
+            ok = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+            v = torch.where(ok, img[idx, yy.clamp(0, h - 1), xx.clamp(0, w - 1)], torch.zeros((), dtype=torch.float64))
+            ref += v * wgt
+            mag += v.abs() * wgt.abs()
+        refs.append(ref.view(b, hh, ww, 81).permute(0, 3, 1, 2))
+        mags.append(mag.view(b, hh, ww, 81).permute(0, 3, 1, 2))
+    return torch.cat(refs, 1), torch.cat(mags, 1)
+
+
+def er_altcorr_ref(fmap1, f2_levels, coords):
+    """The on-the-fly correlation: the lookup (er_lookup_ref) of the all-pairs volumes of fmap1 against fmap2 and its pooled levels,
+    each volume in fp64 from the GPU's own feature maps.  mag: the blend of the volumes' mag."""
+    b, c, h, w = fmap1.shape
+    s = 1.0 / float(np.sqrt(np.float32(c)))
+    a = _d(fmap1).reshape(b, c, h * w)
+    vol, vmag = [], []
+    for f2 in f2_levels:
+        q = _d(f2)
+        hl, wl = q.shape[-2:]
+        q = q.reshape(b, c, hl * wl)
+        vol.append((torch.einsum("bcp,bcq->bpq", a, q) * s).reshape(b * h * w, 1, hl, wl))
+        vmag.append((torch.einsum("bcp,bcq->bpq", a.abs(), q.abs()) * s).reshape(b * h * w, 1, hl, wl))
+    ref, _ = er_lookup_ref(vol, coords)
+    mag, _ = er_lookup_ref(vmag, coords)
+    return ref, mag
+
+
+def er_gru_blend_ref(z, h, q):
+    """(1 - z) h + z q (model/update.py:58)."""
+    return (1 - z) * h + z * q
+
+
+def er_convex_up_ref(flow, mask, pad, size, dtype=torch.float64):
+    """ERAFT.upsample_flow (model/eraft.py:83-94) of `flow` [B, 2, h, w] with `mask` [B, 576, h, w], cropped by the padder's
+    (left, right, top, bottom) to `size`: oracle/eraft_oracle.py's convex_upsample in `dtype`."""
+    up = R.convex_upsample(torch.as_tensor(flow).detach().cpu().to(dtype), torch.as_tensor(mask).detach().cpu().to(dtype))
+    return up[..., pad[2]:pad[2] + size[0], pad[0]:pad[0] + size[1]]
+
+
+def er_pad_ref(x, pad):
+    """F.pad(mode='replicate') by the padder's (left, right, top, bottom) (utils/image_utils.py:139-140): a copy, compared bitwise."""
+    return F.pad(_f32(x), tuple(pad), mode="replicate")
+
+
+def check_bitwise(name, got, ref):
+    g, r = _f32(got), _f32(ref)
+    if g.shape != r.shape:
+        raise StageError(f"{name}: shape {tuple(g.shape)} against the reference's {tuple(r.shape)}")
+    bad = g.view(torch.int32) != r.view(torch.int32)
+    LOG.append({"name": name, "form": "bitwise", "n": g.numel(), "differ": int(bad.sum())})
+    if bool(bad.any()):
+        w = int(torch.nonzero(bad.reshape(-1))[0])
+        raise StageError(f"{name} [bitwise]: {int(bad.sum())} of {g.numel()} values differ; the first at {where(r.shape, w)}: got "
+                         f"{float(g.reshape(-1)[w]):.9g}, ref {float(r.reshape(-1)[w]):.9g}")
