@@ -66,6 +66,8 @@ _SIGNATURES = {
                                             _c_float_p, ctypes.c_void_p]),
     "eemflow_upsample_bilinear": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "eemflow_upsample_bilinear_bwd": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "eraft_corr_lookup_bwd": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p,
                                              _c_float_p, _c_float_p, _c_float_p, ctypes.c_void_p]),
     "eraft_corr_pyramid_bwd": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int,

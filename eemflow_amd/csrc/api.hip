@@ -775,50 +775,21 @@ extern "C" int eemflow_upsample_bilinear(const float* in, float* out, int nc, in
 // njobs = 1 or 2 voxelizations of one grid shape in one launch sequence (voxel.hip)
 static int voxelize_jobs(int njobs, const double* const* events, const int64_t* n, int bins, int h, int w, int normalize, float* const* grid,
                          int64_t* const* idx_left, int64_t* const* idx_right, void* stream) {
-    // scratch arenas (band counters, moments, 16 B per event of vote records), grown on demand and owned by the LIBRARY, not by the
-    // calling thread (a loader's worker threads come and go; per-thread arenas were never freed): one per (device, stream) for up to
-    // eight streams, so that the voxelizations of frames in flight on different streams do not wait for each other; a ninth stream
-    // takes over the least recently used arena after waiting for the kernels that last used it.  The lock is held over the three
-    // launches and the event record, so a take-over always sees the event of the arena's last user.
-    struct Arena { void* p = nullptr; size_t cap = 0; int dev = -1; hipEvent_t done = nullptr; void* stream = nullptr; unsigned long used = 0; };
-    static Arena arenas[8];
-    static unsigned long tick = 0;
-    static std::mutex arena_lock;
-    std::lock_guard<std::mutex> guard(arena_lock);
-    int dev = 0;
-    EEM_HIP_CHECK(hipGetDevice(&dev));
-    Arena* ar = nullptr;
-    for (Arena& a : arenas)
-        if (a.p && a.dev == dev && a.stream == stream) { ar = &a; break; }
-    if (!ar) {
-        for (Arena& a : arenas)
-            if (!ar || (!a.p && ar->p) || (!!a.p == !!ar->p && a.used < ar->used)) ar = &a;      // an empty slot, else the oldest
-        if (ar->p && ar->dev == dev) EEM_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ar->done, 0));
-        ar->stream = stream;
-    }
-    ar->used = ++tick;
+    // the voxelizer's own pool of scratch arenas (band counters, moments, 16 B per event of vote records; see Arena): the lock is held
+    // over the three launches and the event record
+    static Arena arena;
     EEM_REQUIRE(njobs >= 1 && njobs <= VOX_MAX_JOBS, "voxelize: %d event sets per call (1..%d)", njobs, VOX_MAX_JOBS);
     size_t part[VOX_MAX_JOBS] = {}, need = 0;
     for (int k = 0; k < njobs; ++k) { part[k] = (voxel_scratch_bytes(n[k]) + 255) & ~(size_t)255; need += part[k]; }
-    if (ar->p == nullptr || ar->dev != dev || ar->cap < need) {
-        if (ar->p) {                                                             // synchronises with work using it
-            int cur = dev;
-            if (ar->dev != dev) EEM_HIP_CHECK(hipSetDevice(ar->dev));
-            EEM_HIP_CHECK(hipFree(ar->p));
-            if (ar->dev != cur) { EEM_HIP_CHECK(hipEventDestroy(ar->done)); ar->done = nullptr; EEM_HIP_CHECK(hipSetDevice(cur)); }
-        }
-        ar->p = nullptr;
-        ar->cap = need + need / 4;
-        EEM_HIP_CHECK(hipMalloc(&ar->p, ar->cap));
-        if (!ar->done) EEM_HIP_CHECK(hipEventCreateWithFlags(&ar->done, hipEventDisableTiming));
-        ar->dev = dev;
-    }
+    std::lock_guard<std::mutex> guard(arena.lock);
+    char* base = nullptr;
+    void* token = nullptr;
+    int rc = arena.take(need, stream, &base, &token);
+    if (rc != EEM_OK) return rc;
     void* scratch[VOX_MAX_JOBS];
-    { char* q = (char*)ar->p; for (int k = 0; k < njobs; ++k) { scratch[k] = q; q += part[k]; } }
-    hipEvent_t done = ar->done;
-    const int rc = voxel_launch_jobs(njobs, events, n, bins, h, w, normalize, grid, idx_left, idx_right, scratch, (hipStream_t)stream);
-    if (rc == EEM_OK) EEM_HIP_CHECK(hipEventRecord(done, (hipStream_t)stream));
-    return rc;
+    for (int k = 0; k < njobs; ++k) { scratch[k] = base; base += part[k]; }
+    rc = voxel_launch_jobs(njobs, events, n, bins, h, w, normalize, grid, idx_left, idx_right, scratch, (hipStream_t)stream);
+    return rc == EEM_OK ? arena.done(token, stream) : rc;
 }
 
 extern "C" int eemflow_voxelize(const double* events, int64_t n, int bins, int h, int w, int normalize, float* grid,

@@ -404,3 +404,5 @@ size_t voxel_scratch_bytes(int64_t n);
 #define VOX_MAX_JOBS 32
 int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, int bins, int h, int w, int normalize, float* const* grid,
                       int64_t* const* idx_left, int64_t* const* idx_right, void* const* scratch, hipStream_t stream);
+
+#include "devstate_hip.h"   // per-device launch state, scratch arenas, DevBuf (needs EEM_HIP_CHECK above)

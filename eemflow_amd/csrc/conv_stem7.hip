@@ -163,12 +163,8 @@ static int stem7_launch_t(const GConvArgs& a, hipStream_t stream) {
     const int tiles_x = ceil_div(a.wout, ST_TW), tiles_y = ceil_div(a.hout, ST_TH);
     const int ntiles = tiles_x * tiles_y * a.n;
     const int lds_bytes = (CIN * 14 * 64 * 4 + CIN * ST_PLANE) * 4;
-    static bool raised = false;
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)stem7_kernel<CIN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
-    static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
+    EEM_RAISE_LDS(160 * 1024, stem7_kernel<CIN>);
+    const int cus = eem_cu_count();
     const int grid = ntiles < cus ? ntiles : cus;       // one resident block per CU, each walks tiles blockIdx.x, + grid, ...
     static const char* const names[5] = {"stem7_c1", "stem7_c2", "stem7_c3", "stem7_c4", "stem7_c5"};
     eem_conv_form = names[CIN - 1];

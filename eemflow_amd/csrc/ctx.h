@@ -27,11 +27,6 @@ struct TailW {                         // one packed small-grid conv
     int cin = 0, cout = 0, ksize = 3;
 };
 
-struct DevBuf {
-    float* p = nullptr;
-    size_t cap = 0;                    // floats
-};
-
 struct Shape {
     int batch = 0, in_h = 0, in_w = 0, out_h = 0, out_w = 0;
     int hp = 0, wp = 0;                // padded extent
@@ -312,7 +307,7 @@ struct Hook {
 
 // ------------------------------------------------------------------------------- workspace.hip
 extern thread_local unsigned long g_realloc_events;   // the reallocation counter: bumped whenever ensure() moves a buffer
-int ensure(DevBuf& b, size_t floats);
+int ensure(DevBuf& b, size_t floats);                 // devbuf_ensure for the CONTEXT's buffers: only their moves drop EEMFlow's graphs
 int refresh_wino(eemflow_ctx* c, hipStream_t);
 int ensure_bx3(eemflow_ctx* c, int l, hipStream_t st, const float** w_out);
 int ensure_s2r(eemflow_ctx* c, int l, hipStream_t st, const float** w_out);

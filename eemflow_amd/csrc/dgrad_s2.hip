@@ -210,11 +210,7 @@ int launch(const DgradS2Args& a, hipStream_t st) {
     int gx = 256 * per_cu;
     const int need = ceil_div(T, 8) * 8;
     if (gx > need) gx = need;
-    static bool raised = false;
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)dgrad_s2_kernel<CO, CI, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
+    EEM_RAISE_LDS(160 * 1024, dgrad_s2_kernel<CO, CI, NST>);
     hipLaunchKernelGGL((dgrad_s2_kernel<CO, CI, NST>), dim3(gx), dim3(256), lds_bytes, st, a, tiles_x, tiles_y);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -383,11 +379,7 @@ int launch_wide(const DgradS2Args& a, hipStream_t st) {
     if (gx < 8) gx = 8;
     const int need = ceil_div(T, 8) * 8;
     if (gx > need) gx = need;
-    static bool raised = false;
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)dgrad_s2w_kernel<CO, K1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
+    EEM_RAISE_LDS(160 * 1024, dgrad_s2w_kernel<CO, K1>);
     eem_conv_form = CO == 96 ? (K1 ? "dgrad_s2w_96_1x1" : "dgrad_s2w_96_3x3") : (K1 ? "dgrad_s2w_128_1x1" : "dgrad_s2w_128_3x3");
     hipLaunchKernelGGL((dgrad_s2w_kernel<CO, K1>), dim3(gx, citiles), dim3(256), lds_bytes, st, a, tiles_x, tiles_y);
     EEM_HIP_CHECK(hipGetLastError());

@@ -13,20 +13,6 @@
 
 namespace {
 
-struct Buf {
-    float* p = nullptr;
-    size_t cap = 0;
-};
-
-int ensure(Buf& b, size_t floats) {
-    if (floats <= b.cap) return EEM_OK;
-    if (b.p) EEM_HIP_CHECK(hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    EEM_HIP_CHECK(hipMalloc(&b.p, floats * sizeof(float)));
-    b.cap = floats;
-    return EEM_OK;
-}
-
 struct StageRec {                 // one recorded launch output: [dims] floats at rec_buf + off
     std::string name, form;
     int dims[4];
@@ -71,11 +57,11 @@ struct eraft_ctx {
     // per-pixel addend (gzr_c / gq_c -> czr / cq), and the convs inside the loop run over [h | motion] only (gzr_hm / gq_hm: K = 256
     // instead of 384) with that addend in front of their activation (GConvArgs::pre).  EEM_ERAFT_NO_PRE=1 keeps the full convs.
     Layer gzr_hm[2], gq_hm[2], gzr_c[2], gq_c[2];
-    Buf czr[2], cq[2];
+    DevBuf czr[2], cq[2];
     // workspace
-    Buf padded, s[5], fmap, net[3], inp, pyr[4], c0, c1, c1b, corr, cor1, corflo, flo1, motion, z, rh, fhid, delta, mhid, mask;
-    Buf st_corr0, st_net1, st_mask1, st_delta1, zeros;
-    Buf many_out;                  // eraft_forward_many: the batched predictions before they are copied to the samples' own tensors
+    DevBuf padded, s[5], fmap, net[3], inp, pyr[4], c0, c1, c1b, corr, cor1, corflo, flo1, motion, z, rh, fhid, delta, mhid, mask;
+    DevBuf st_corr0, st_net1, st_mask1, st_delta1, zeros;
+    DevBuf many_out;                  // eraft_forward_many: the batched predictions before they are copied to the samples' own tensors
     int B = 0, h8 = 0, w8 = 0, ph[4] = {0, 0, 0, 0}, pw[4] = {0, 0, 0, 0};
     bool have_last = false;
     bool keep_stages = false;      // copy corr0 / net1 / mask1 / delta1 aside in the first iteration (parity tests)
@@ -89,16 +75,16 @@ struct eraft_ctx {
     // network and the correlation volume, convf1 -> convf2 beside convc1 -> convc2, the flow head's last conv beside the mask head's
     hipStream_t side = nullptr;
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-    Buf s2[5];                     // the context network's own activations (the feature network runs at the same time)
+    DevBuf s2[5];                     // the context network's own activations (the feature network runs at the same time)
     bool alt_corr = false;         // eraft_set_alternate_corr: correlation features on the fly, no all-pairs volume
     bool final_only = false;       // eraft_set_final_only: only the last iteration's prediction leaves the forward
-    Buf f2l[3];                    // avg-pooled fmap2, levels 1..3 (alt_corr)
+    DevBuf f2l[3];                    // avg-pooled fmap2, levels 1..3 (alt_corr)
     bool stages_valid = false;
     int fmap_imgs = 0;             // images in `fmap` after the last forward (2B; nflow + 1 after a stream call)
     unsigned long wver = 0;        // bumped by every eraft_load_weights
     // eraft_forward_stream: the carry - the last window's padded volume and feature map, the last pair's flow_low - in memory of its
     // own (forward / forward_many / the operator-level calls reuse the workspace, never these), and the last call's per-pair flow_low
-    Buf carry_pad, carry_fmap, carry_flow, sflow, finit, fi_ws;
+    DevBuf carry_pad, carry_fmap, carry_flow, sflow, finit, fi_ws;
     bool carry_on = false, carry_has_flow = false;
     int carry_h = 0, carry_w = 0, carry_padv[4] = {0, 0, 0, 0};
     unsigned long carry_wver = 0;
@@ -110,24 +96,13 @@ struct eraft_ctx {
     std::vector<std::string> rec_prefix;
     int rec_iters = 0;             // update iterations 0 .. rec_iters - 1 are recorded
     std::vector<StageRec> rec;
-    Buf rec_buf;
+    DevBuf rec_buf;
     size_t rec_used = 0, rec_need = 0;
 };
 
 namespace {
 
 constexpr int kCorrPad = 336;     // 324 correlation features padded to a multiple of 16 channels
-
-struct Cursor {
-    const float* p;
-    const float* end;
-    const float* take(size_t n) { const float* r = p; p += n; return r; }
-};
-
-struct Packer {
-    std::vector<float> host;
-    size_t push(size_t n) { size_t off = host.size(); host.resize(off + ((n + 3) & ~(size_t)3), 0.f); return off; }
-};
 
 struct BN { const float *w, *b, *rm, *rv; };
 
@@ -360,7 +335,7 @@ bool wnc_upd(const Layer& L, int bit, int n, int h, int w) {
 
 // BasicEncoder forward on `n` images [n][cin0][hp][wp]; result of the residual stack in *feat ([n][128][hp/8][wp/8]).
 // tag ("fnet." / "cnet."; NULL: the recorder is off): every launch's output is recorded as <tag>conv1, <tag>norm1, <tag>layer<l>.<r>.conv1 ...
-int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0, int hp, int wp, float** feat, hipStream_t st, Buf* sc = nullptr,
+int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0, int hp, int wp, float** feat, hipStream_t st, DevBuf* sc = nullptr,
                 const char* tag = nullptr) {
     int rc;
     if (!sc) sc = c->s;
@@ -436,9 +411,9 @@ int build_pyramid(eraft_ctx* c, const float* f1, const float* f2, int batch, int
     for (int l = 1; l < 4; ++l) { c->ph[l] = c->ph[l - 1] / 2; c->pw[l] = c->pw[l - 1] / 2; }
     for (int l = 0; l < 4; ++l) {
         EEM_REQUIRE(c->ph[l] >= 1 && c->pw[l] >= 1, "correlation pyramid level %d is empty for a %dx%d feature map", l, h, w);
-        if ((rc = ensure(c->pyr[l], (size_t)batch * hw * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->pyr[l], (size_t)batch * hw * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
     }
-    if ((rc = er_allpairs_launch(f1, f2, c->pyr[0].p, batch, ch, (int)hw, st)) != EEM_OK) return rc;
+    if ((rc = er_allpairs_launch(f1, f2, c->pyr[0].p, batch, ch, (int)hw, c->arena + c->zero_off, st)) != EEM_OK) return rc;
     if (recd && (rc = rec_stage(c, "pyr0", er_last_form, c->pyr[0].p, (int)(batch * hw), 1, h, w, st)) != EEM_OK) return rc;
     if ((rc = er_pool2x3_launch(c->pyr[0].p, c->pyr[1].p, c->pyr[2].p, c->pyr[3].p, (long)batch * hw, h, w, st)) != EEM_OK) return rc;
     if (recd)
@@ -457,7 +432,7 @@ int build_feature_pyramid(eraft_ctx* c, const float* f2, int batch, int ch, int 
     const float* src = f2;
     for (int l = 1; l < 4; ++l) {
         EEM_REQUIRE(c->ph[l] >= 1 && c->pw[l] >= 1, "correlation pyramid level %d is empty for a %dx%d feature map", l, h, w);
-        if ((rc = ensure(c->f2l[l - 1], (size_t)batch * ch * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->f2l[l - 1], (size_t)batch * ch * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
         if ((rc = er_pool2_launch(src, c->f2l[l - 1].p, (long)batch * ch, c->ph[l - 1], c->pw[l - 1], st)) != EEM_OK) return rc;
         const char nm[5] = {'f', '2', 'l', (char)('0' + l), 0};
         if (recd && (rc = rec_stage(c, nm, er_last_form, c->f2l[l - 1].p, batch, ch, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
@@ -516,13 +491,13 @@ extern "C" int eraft_create(int device, eraft_ctx** out) {
 extern "C" void eraft_destroy(eraft_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    Buf* all[] = {&c->padded, &c->s[0], &c->s[1], &c->s[2], &c->s[3], &c->s[4], &c->fmap, &c->net[0], &c->net[1], &c->net[2], &c->inp,
+    DevBuf* all[] = {&c->padded, &c->s[0], &c->s[1], &c->s[2], &c->s[3], &c->s[4], &c->fmap, &c->net[0], &c->net[1], &c->net[2], &c->inp,
                   &c->pyr[0], &c->pyr[1], &c->pyr[2], &c->pyr[3], &c->c0, &c->c1, &c->c1b, &c->corr, &c->cor1, &c->corflo, &c->flo1,
                   &c->motion, &c->z, &c->rh, &c->fhid, &c->delta, &c->mhid, &c->mask, &c->st_corr0, &c->st_net1, &c->st_mask1,
                   &c->st_delta1, &c->zeros, &c->many_out, &c->f2l[0], &c->f2l[1], &c->f2l[2], &c->czr[0], &c->czr[1], &c->cq[0], &c->cq[1],
                   &c->s2[0], &c->s2[1], &c->s2[2], &c->s2[3], &c->s2[4], &c->carry_pad, &c->carry_fmap, &c->carry_flow, &c->sflow,
                   &c->finit, &c->fi_ws, &c->rec_buf};
-    for (Buf* b : all) if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : all) if (b->p) (void)hipFree(b->p);
     if (c->nstat) (void)hipFree(c->nstat);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
@@ -672,7 +647,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     int rc;
     // ---- workspace
     const size_t big = (size_t)std::max(nfn, 2 * B) * 64 * ((hp + 1) / 2) * ((wp + 1) / 2);
-#define ENS(b, n) if ((rc = ensure(b, n)) != EEM_OK) return rc
+#define ENS(b, n) if ((rc = devbuf_ensure(b, n)) != EEM_OK) return rc
     ENS(c->padded, (size_t)nimg * c->cin0 * hp * wp);
     for (int i = 0; i < 5; ++i) ENS(c->s[i], big);
     {   // scratch of the large-plane instance norm: the first stage has the most (planes x chunks)
@@ -737,7 +712,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             EEM_HIP_CHECK(hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming));
         }
         for (int i = 0; i < 5; ++i)
-            if ((rc = ensure(c->s2[i], big / 2)) != EEM_OK) return rc;
+            if ((rc = devbuf_ensure(c->s2[i], big / 2)) != EEM_OK) return rc;
     }
     // The prediction of an iteration - mask head (3x3 128 -> 256, 1x1 256 -> 576) and convex upsampling - feeds nothing inside the loop
     // (model/eraft.py:141-157: the recurrence is net -> flow head -> coords1 -> lookup): it runs on the side stream beside the NEXT
@@ -771,9 +746,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         guard.forked = false;
         return EEM_OK;
     };
-    // (workspace of the forked region, before the fork: ensure() may free / allocate and synchronise the device)
+    // (workspace of the forked region, before the fork: devbuf_ensure() may free / allocate and synchronise the device)
     for (int pass = 0; pass < 2; ++pass)
-        if ((rc = ensure(c->czr[pass], (size_t)B * 256 * g)) != EEM_OK || (rc = ensure(c->cq[pass], (size_t)B * 128 * g)) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->czr[pass], (size_t)B * 256 * g)) != EEM_OK || (rc = devbuf_ensure(c->cq[pass], (size_t)B * 128 * g)) != EEM_OK) return rc;
     // pad channels of the correlation buffer (never written by the lookup)
     EEM_HIP_CHECK(hipMemset2DAsync(c->corr.p + (size_t)324 * g, (size_t)kCorrPad * g * 4, 0, (size_t)(kCorrPad - 324) * g * 4, B, st));
     // ---- pad both event volumes into one batch (model/eraft.py:106-109)
@@ -1179,7 +1154,7 @@ extern "C" int eraft_forward_many(eraft_ctx* c, int n, const float* const* event
     hipStream_t st = (hipStream_t)stream;
     const int nout = c->final_only ? 1 : iters;
     const size_t per = (size_t)2 * in_h * in_w;                          // floats of one prediction of one sample
-    int rc = ensure(c->many_out, (size_t)nout * n * per);
+    int rc = devbuf_ensure(c->many_out, (size_t)nout * n * per);
     if (rc != EEM_OK) return rc;
     if ((rc = eraft_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, iters, nullptr, c->many_out.p, st)) != EEM_OK) return rc;
     if (c->rec_on && c->rec_used > c->rec_buf.cap &&                      // (the recorder's arena has grown: see eraft_forward)
@@ -1223,14 +1198,14 @@ extern "C" int eraft_forward_stream(eraft_ctx* c, int nvol, const float* const* 
     hipStream_t st = (hipStream_t)stream;
     const size_t g = (size_t)(hp / 8) * (wp / 8), img = (size_t)c->cin0 * hp * wp;
     int rc;
-    if ((rc = ensure(c->carry_pad, img)) != EEM_OK || (rc = ensure(c->carry_fmap, 256 * g)) != EEM_OK ||
-        (rc = ensure(c->carry_flow, 2 * g)) != EEM_OK) return rc;
+    if ((rc = devbuf_ensure(c->carry_pad, img)) != EEM_OK || (rc = devbuf_ensure(c->carry_fmap, 256 * g)) != EEM_OK ||
+        (rc = devbuf_ensure(c->carry_flow, 2 * g)) != EEM_OK) return rc;
     const bool warm = warm_start != 0;
     StreamPlan sp{volumes, nvol, c->carry_on, warm, warm && c->carry_on && c->carry_has_flow ? c->carry_flow.p : nullptr, flow_out};
     c->carry_on = false;                                                 // (a failed call leaves no carry behind)
     const int nout = c->final_only ? 1 : iters;
     const size_t per = (size_t)2 * in_h * in_w;
-    if (P > 0 && !warm && (rc = ensure(c->many_out, (size_t)nout * P * per)) != EEM_OK) return rc;
+    if (P > 0 && !warm && (rc = devbuf_ensure(c->many_out, (size_t)nout * P * per)) != EEM_OK) return rc;
     if ((rc = eraft_forward_impl(c, nullptr, nullptr, nullptr, nullptr, 0, P, in_h, in_w, pad, iters, nullptr, warm ? nullptr : c->many_out.p,
                                  st, &sp)) != EEM_OK) return rc;
     if (P > 0 && !warm)
@@ -1384,7 +1359,7 @@ extern "C" int eraft_corr_lookup(eraft_ctx* c, const float* fmap1, const float* 
     if (c->rec_on) {                                                     // the recorder: "pyr0" .. "pyr3" and "corr", each with the form that ran
         size_t need = (size_t)batch * 324 * h * w + 64 * 5;
         for (int l = 0, ph = h, pw = w; l < 4; ++l, ph /= 2, pw /= 2) need += (size_t)batch * h * w * ph * pw;
-        if ((rc = ensure(c->rec_buf, need)) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->rec_buf, need)) != EEM_OK) return rc;
     }
     rc = build_pyramid(c, fmap1, fmap2, batch, ch, h, w, (hipStream_t)stream, c->rec_on);
     if (rc != EEM_OK) return rc;
@@ -1400,7 +1375,7 @@ extern "C" int eraft_convex_upsample(eraft_ctx* c, const float* flow, const floa
                                      void* stream) {
     EEM_REQUIRE(c && flow && mask && out, "eraft_convex_upsample: NULL argument");
     EEM_HIP_CHECK(hipSetDevice(c->device));
-    int rc = ensure(c->zeros, (size_t)batch * 2 * h * w);
+    int rc = devbuf_ensure(c->zeros, (size_t)batch * 2 * h * w);
     if (rc != EEM_OK) return rc;
     EEM_HIP_CHECK(hipMemsetAsync(c->zeros.p, 0, (size_t)batch * 2 * h * w * 4, (hipStream_t)stream));
     return er_convex_up_launch(c->zeros.p, flow, mask, out, batch, h, w, 0, 0, 8 * h, 8 * w, (hipStream_t)stream);

@@ -22,7 +22,9 @@ int er_instnorm_launch(const float* x, float* out, const float* res, int planes,
                        size_t stats_cap = 0);
 
 // All-pairs correlation (model/corr.py:53-60): out[b][p1][p2] = sum_c f1[b][c][p1] * f2[b][c][p2] / sqrt(C)
-int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, int c, int hw, hipStream_t st);
+// zero_page: 256 bytes of zeros on the launch's device (the LDS-staged form reads the pieces past the last pixel from it), or NULL:
+// the forms that feed the MFMAs from L2
+int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, int c, int hw, const float* zero_page, hipStream_t st);
 
 // avg_pool2d(2, stride 2) over the last two dims of [planes][h][w] -> [planes][h/2][w/2]   (model/corr.py:24-27)
 int er_pool2_launch(const float* in, float* out, long planes, int h, int w, hipStream_t st);

@@ -770,20 +770,13 @@ int er_instnorm_launch(const float* x, float* out, const float* res, int planes,
     return EEM_OK;
 }
 
-int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, int c, int hw, hipStream_t st) {
+int er_allpairs_launch(const float* f1, const float* f2, float* out, int batch, int c, int hw, const float* zero_page, hipStream_t st) {
     const bool even = hw % 2 == 0 && ((uintptr_t)f1 & 7) == 0 && ((uintptr_t)f2 & 7) == 0 && ((uintptr_t)out & 7) == 0;
     dim3 grid(ceil_div(hw, 128), ceil_div(hw, 128), batch);
     // the LDS-staged form where it applies (EEM_ALLPAIRS_L2=1: the form that feeds the MFMAs from L2)
-    static float* zero_pages[16] = {};                       // 256 bytes of zeros per device for the pieces past the last pixel (never freed)
-    int dev = 0;
-    if (even && c % 16 == 0 && hw % 4 == 0 && (((uintptr_t)f1 | (uintptr_t)f2) & 15) == 0 && !sw_on<SW_EEM_ALLPAIRS_L2>() &&
-        hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
-        if (!zero_pages[dev]) {
-            EEM_HIP_CHECK(hipMalloc(&zero_pages[dev], 256));
-            EEM_HIP_CHECK(hipMemset(zero_pages[dev], 0, 256));
-        }
+    if (zero_page && even && c % 16 == 0 && hw % 4 == 0 && (((uintptr_t)f1 | (uintptr_t)f2) & 15) == 0 && !sw_on<SW_EEM_ALLPAIRS_L2>()) {
         er_last_form = "allpairs_lds";
-        hipLaunchKernelGGL(allpairs_lds_kernel, grid, dim3(256), 0, st, f1, f2, out, c, hw, 1.0f / sqrtf((float)c), zero_pages[dev]);
+        hipLaunchKernelGGL(allpairs_lds_kernel, grid, dim3(256), 0, st, f1, f2, out, c, hw, 1.0f / sqrtf((float)c), zero_page);
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }

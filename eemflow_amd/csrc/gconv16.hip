@@ -381,7 +381,7 @@ int launch_wm(const GConvArgs& a, const float* wpk16, const float* zero_page, hi
     const int ng = a.groups > 1 ? a.groups : 1;
     dim3 grid(tiles_x * tiles_y, ceil_div(a.cout, 16 * WM) * ng, a.n);
     // at most one block per CU: two K groups of four waves per tile (see the kernel's KG)
-    static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
+    const int cus = eem_cu_count();
     const int nchunks = cin / 16;
     const long blocks = (long)grid.x * grid.y * grid.z;
     const bool two = nchunks >= 4 && blocks <= cus && a.in_flight < 3;
@@ -431,7 +431,7 @@ int launch(const GConvArgs& a, const float* wpk16, const float* zero_page, hipSt
         // A launch of a few blocks per CU runs as long as the CU with the most blocks: E-RAFT's update block at batch 1 (60 x 80 x 128
         // couts) is 300 blocks of 2-row tiles - 44 CUs take two and the other 212 wait for them; 200 blocks of 3-row tiles are one round
         // of 1.5x the work.  Rows per tile = the one with the least (rounds x rows), the per-block overhead counted as 0.6 rows.
-        static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
+        const int cus = eem_cu_count();
         float best = 1e30f;
         th = 2;
         for (int t = 2; t <= 6; ++t) {

@@ -366,7 +366,7 @@ int gb_launch_t(const GConvArgs& a, hipStream_t stream) {
 // (2 / 4 / 6 / 8 rows everywhere: 208 / 235 / 249 / 243 at batch 4).
 template <int KH, int KW>
 int gb_launch(const GConvArgs& a, hipStream_t stream) {
-    static const int cus = [] { int d = 0, n = 256; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; return n > 0 ? n : 256; }();
+    const int cus = eem_cu_count();
     const auto cost = [&](int th) { return (float)ceil_div(ceil_div(a.wout, 16) * ceil_div(a.hout, th) * ceil_div(a.cout, 128) * a.n, cus) * (float)(th + 2); };
     int th = 8;
     for (int t = 6; t >= 2; t -= 2)

@@ -290,13 +290,7 @@ IweLayout iwe_layout_binned(long n, int ept, const IwePlan& pl) {
 template <int EPT>
 int launch_bin(const IweJobs& jobs, int njobs, long nblk_max, int h, int w, const IwePlan& pl, hipStream_t stream) {
     constexpr int stage_bytes = 2 * VT * EPT * 12;
-    if (stage_bytes > 32 * 1024) {
-        static bool raised = false;
-        if (!raised) {
-            EEM_HIP_CHECK(hipFuncSetAttribute((const void*)iwe_bin_kernel<EPT>, hipFuncAttributeMaxDynamicSharedMemorySize, stage_bytes));
-            raised = true;
-        }
-    }
+    if (stage_bytes > 32 * 1024) EEM_RAISE_LDS(stage_bytes, iwe_bin_kernel<EPT>);
     hipLaunchKernelGGL((iwe_bin_kernel<EPT>), dim3((unsigned)nblk_max, njobs), dim3(VT), stage_bytes, stream, jobs, h, w, pl);
     return EEM_OK;
 }
@@ -382,15 +376,7 @@ int iwe_launch(int k, const double* const* events, const int64_t* n, const float
     if (pl.cells <= 3072) {
         hipLaunchKernelGGL(iwe_band_kernel<256>, dim3(pl.nb, k), dim3(256), lds, stream, jobs, 2 * VT * ept, h, w, pl, sgs);
     } else {
-        if (lds > 32 * 1024) {
-            static int raised = 0;
-            static std::mutex raise_lock;
-            std::lock_guard<std::mutex> guard(raise_lock);
-            if (raised < lds) {
-                EEM_HIP_CHECK(hipFuncSetAttribute((const void*)iwe_band_kernel<VT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                raised = lds;
-            }
-        }
+        if (lds > 32 * 1024) EEM_RAISE_LDS(lds, iwe_band_kernel<VT>);
         hipLaunchKernelGGL(iwe_band_kernel<VT>, dim3(pl.nb, k), dim3(VT), lds, stream, jobs, 2 * VT * ept, h, w, pl, sgs);
     }
     hipLaunchKernelGGL(iwe_moments_kernel, dim3(k), dim3(256), 0, stream, jobs, pl.nb, (double)hw, moments);
@@ -398,51 +384,11 @@ int iwe_launch(int k, const double* const* events, const int64_t* n, const float
     return EEM_OK;
 }
 
-// the arenas that iwe_shared.h describes
-struct Arena { void* p = nullptr; size_t cap = 0; int dev = -1; hipEvent_t done = nullptr; void* stream = nullptr; unsigned long used = 0; };
-Arena g_arenas[8];
-unsigned long g_tick = 0;
-std::mutex g_arena_lock;
+Arena g_iwe_arena;
 
 }  // namespace
 
-std::mutex& iwe_arena_lock() { return g_arena_lock; }
-
-int iwe_arena_take(size_t need, void* stream, char** scratch, void** token) {
-    int dev = 0;
-    EEM_HIP_CHECK(hipGetDevice(&dev));
-    Arena* ar = nullptr;
-    for (Arena& a : g_arenas)
-        if (a.p && a.dev == dev && a.stream == stream) { ar = &a; break; }
-    if (!ar) {
-        for (Arena& a : g_arenas)
-            if (!ar || (!a.p && ar->p) || (!!a.p == !!ar->p && a.used < ar->used)) ar = &a;      // an empty slot, else the oldest
-        if (ar->p && ar->dev == dev) EEM_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ar->done, 0));
-        ar->stream = stream;
-    }
-    ar->used = ++g_tick;
-    if (ar->p == nullptr || ar->dev != dev || ar->cap < need) {
-        if (ar->p) {                                                             // hipFree synchronises with work using it
-            int cur = dev;
-            if (ar->dev != dev) EEM_HIP_CHECK(hipSetDevice(ar->dev));
-            EEM_HIP_CHECK(hipFree(ar->p));
-            if (ar->dev != cur) { EEM_HIP_CHECK(hipEventDestroy(ar->done)); ar->done = nullptr; EEM_HIP_CHECK(hipSetDevice(cur)); }
-        }
-        ar->p = nullptr;
-        ar->cap = need + need / 4;
-        EEM_HIP_CHECK(hipMalloc(&ar->p, ar->cap));
-        if (!ar->done) EEM_HIP_CHECK(hipEventCreateWithFlags(&ar->done, hipEventDisableTiming));
-        ar->dev = dev;
-    }
-    *scratch = (char*)ar->p;
-    *token = ar;
-    return EEM_OK;
-}
-
-int iwe_arena_done(void* token, void* stream) {
-    EEM_HIP_CHECK(hipEventRecord(static_cast<Arena*>(token)->done, (hipStream_t)stream));
-    return EEM_OK;
-}
+Arena& iwe_arena() { return g_iwe_arena; }
 
 extern "C" int eemflow_iwe_map_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
                                     const double* scale, const double (*maps)[4], int h, int w, float* const* iwe, double* moments,
@@ -454,13 +400,13 @@ extern "C" int eemflow_iwe_map_many(int k, const double* const* events, const in
         EEM_REQUIRE(n[i] >= 0 && n[i] < (1LL << 40), "eemflow_iwe_many: job %d has n=%ld events", i, (long)n[i]);
         EEM_REQUIRE((events[i] || n[i] == 0) && iwe[i], "eemflow_iwe_many: job %d has a NULL buffer", i);
     }
-    std::lock_guard<std::mutex> guard(g_arena_lock);
+    std::lock_guard<std::mutex> guard(g_iwe_arena.lock);
     char* scratch = nullptr;
     void* token = nullptr;
-    int rc = iwe_arena_take(iwe_scratch_bytes(k, n, h, w), stream, &scratch, &token);
+    int rc = g_iwe_arena.take(iwe_scratch_bytes(k, n, h, w), stream, &scratch, &token);
     if (rc != EEM_OK) return rc;
     rc = iwe_launch(k, events, n, flows, t0, scale, maps, h, w, iwe, moments, scratch, (hipStream_t)stream);
-    if (rc == EEM_OK) rc = iwe_arena_done(token, stream);
+    if (rc == EEM_OK) rc = g_iwe_arena.done(token, stream);
     return rc;
 }
 

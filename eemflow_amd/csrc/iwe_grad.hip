@@ -250,11 +250,7 @@ template <int EPT>
 int launch_grad_bin(const IweGradJobs& jobs, int njobs, long nblk_max, const double* moments, const double* coef, int h, int w,
                     const IwePlan& pl, hipStream_t stream) {
     constexpr int stage_bytes = GRAD_RPE * VT * EPT * 12;
-    static bool raised = false;                                    // (the caller holds the arena lock)
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)iwe_grad_bin_kernel<EPT>, hipFuncAttributeMaxDynamicSharedMemorySize, stage_bytes));
-        raised = true;
-    }
+    EEM_RAISE_LDS(stage_bytes, iwe_grad_bin_kernel<EPT>);
     hipLaunchKernelGGL((iwe_grad_bin_kernel<EPT>), dim3((unsigned)nblk_max, njobs), dim3(VT), stage_bytes, stream, jobs, moments, coef, h, w, pl);
     return EEM_OK;
 }
@@ -298,10 +294,11 @@ extern "C" int eemflow_iwe_grad_many(int k, const double* const* events, const i
         for (int i = 0; i < m; ++i) need += grad_layout(jobs.j[i].n, ept, pl).total;
     else
         need = up256((size_t)2 * hw * 8);
-    std::lock_guard<std::mutex> guard(iwe_arena_lock());
+    Arena& arena = iwe_arena();
+    std::lock_guard<std::mutex> guard(arena.lock);
     char* scratch = nullptr;
     void* token = nullptr;
-    int rc = iwe_arena_take(need, stream_, &scratch, &token);
+    int rc = arena.take(need, stream_, &scratch, &token);
     if (rc != EEM_OK) return rc;
     if (!binned) {
         // direct form, one job after the other through one fp64 image
@@ -315,7 +312,7 @@ extern "C" int eemflow_iwe_grad_many(int k, const double* const* events, const i
             hipLaunchKernelGGL(iwe_grad_finish_kernel, dim3(fin), dim3(256), 0, stream, acc, J.out, 2 * hw);
             EEM_HIP_CHECK(hipGetLastError());
         }
-        return iwe_arena_done(token, stream_);
+        return arena.done(token, stream_);
     }
     long nblk_max = 0;
     char* q = scratch;
@@ -341,13 +338,9 @@ extern "C" int eemflow_iwe_grad_many(int k, const double* const* events, const i
     if (pl.cells <= 3072) {
         hipLaunchKernelGGL(iwe_grad_band_kernel<256>, dim3(pl.nb, m), dim3(256), lds, stream, jobs, slab, h, w, pl, sgs);
     } else {
-        static int raised = 0;                                     // (under the arena lock)
-        if (lds > 32 * 1024 && raised < lds) {
-            EEM_HIP_CHECK(hipFuncSetAttribute((const void*)iwe_grad_band_kernel<VT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            raised = lds;
-        }
+        if (lds > 32 * 1024) EEM_RAISE_LDS(lds, iwe_grad_band_kernel<VT>);
         hipLaunchKernelGGL(iwe_grad_band_kernel<VT>, dim3(pl.nb, m), dim3(VT), lds, stream, jobs, slab, h, w, pl, sgs);
     }
     EEM_HIP_CHECK(hipGetLastError());
-    return iwe_arena_done(token, stream_);
+    return arena.done(token, stream_);
 }

@@ -182,10 +182,6 @@ inline bool iwe_plan(long nmax, int h, int w, IwePlan* pl, int ept_max = 4) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host: scratch arenas (iwe.hip)
-// Scratch arenas (record slabs, run tables, partials; the direct forms' fp64 image), grown on demand and owned by the library: one per
-// (device, stream) for up to eight streams, so that chunks in flight on different streams do not wait for each other; a ninth stream
-// takes over the least recently used arena after waiting for the kernels that last used it.  A caller holds iwe_arena_lock() from
-// iwe_arena_take over its launches to iwe_arena_done, so a take-over always sees the event of the arena's last user.
-std::mutex& iwe_arena_lock();
-int iwe_arena_take(size_t need, void* stream, char** scratch, void** token);      // EEM_OK and *scratch of at least `need` bytes
-int iwe_arena_done(void* token, void* stream);                                    // records the arena's event behind the launches
+// The pool of scratch arenas (record slabs, run tables, partials; the direct forms' fp64 image) that the image of warped events and its
+// gradient share - apart from the voxelizer's pool, which loader threads use meanwhile.  See Arena for how a caller takes one.
+Arena& iwe_arena();

@@ -928,8 +928,9 @@ extern "C" int eemop_corr_pyramid_fwd(const float* fmap1, const float* fmap2, in
     EEM_REQUIRE((h >> 3) >= 1 && (w >> 3) >= 1, "eemop_corr_pyramid_fwd: a %dx%d map has no fourth pyramid level", h, w);
     hipStream_t st = (hipStream_t)stream;
     const long planes = (long)batch * h * w;
-    int rc = er_allpairs_launch(fmap1, fmap2, pyr0, batch, c, h * w, st);
-    if (rc != EEM_OK) return rc;
+    float* zp = nullptr;
+    int rc = scratch_get(g_scratch[1], 1024, &zp);
+    if (rc != EEM_OK || (rc = er_allpairs_launch(fmap1, fmap2, pyr0, batch, c, h * w, zp, st)) != EEM_OK) return rc;
     return er_pool2x3_launch(pyr0, pyr1, pyr2, pyr3, planes, h, w, st);
 }
 

@@ -16,21 +16,10 @@
 
 namespace {
 
-struct PBuf { float* p = nullptr; size_t cap = 0; };
-
-int pensure(PBuf& b, size_t floats) {
-    if (floats <= b.cap) return EEM_OK;
-    if (b.p) EEM_HIP_CHECK(hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    EEM_HIP_CHECK(hipMalloc(&b.p, floats * sizeof(float)));
-    b.cap = floats;
-    return EEM_OK;
-}
-
 // a buffer whose spare channels are multiplied by zero weights: no NaN bit patterns may lie in it
-int pensure_zeroed(PBuf& b, size_t floats) {
+int pensure_zeroed(DevBuf& b, size_t floats) {
     if (floats <= b.cap) return EEM_OK;
-    int rc = pensure(b, floats);
+    int rc = devbuf_ensure(b, floats);
     if (rc != EEM_OK) return rc;
     EEM_HIP_CHECK(hipMemset(b.p, 0, floats * sizeof(float)));
     return EEM_OK;
@@ -68,11 +57,11 @@ struct eemplus_ctx {
     bool enc_wino[8] = {false};
     int* taps = nullptr;
     PLayer enc[8], rconv[7], dec1[7], decg[7][3][3], dec5[7], dec6[7], dec7[7], de[6], c1x1[6];
-    PBuf padded, f[7], a2, dense, xout, finit[7], tw, fup[7], fw, cat, d[4], t64, t32, flow[7], flow_alt[7];
+    DevBuf padded, f[7], a2, dense, xout, finit[7], tw, fup[7], fw, cat, d[4], t64, t32, flow[7], flow_alt[7];
     // round 6: each level owns its dense-estimator buffer, projection of feature_2 and decoder input (index = level; `dense` above stays the
     // encoder's scratch), so that what a level computes from the feature pyramid alone - the two 1x1 projections and rconv, level_units -
     // CAN run on a side stream beside the coarser levels' chain (EEM_PLUS_SIDE=1; measured slower, see plus_forward_impl)
-    PBuf dense_l[7], a2_l[7], cat_l[7];
+    DevBuf dense_l[7], a2_l[7], cat_l[7];
     size_t cat6_key = 0;                 // (batch, map size) for which cat_l[6]'s two flow channels hold zeros (plus_forward_impl, level 6)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_lvl[7] = {};
@@ -85,7 +74,7 @@ struct eemplus_ctx {
     int f2off = 0;
     // eemplus_forward_stream: levels 2..6 of its windows, one image per window, image 0 the window carried in.  forward / forward_many
     // leave these alone; the carried window sits in image carry_slot until the next stream call moves it to image 0
-    PBuf sf[7];
+    DevBuf sf[7];
     bool carry_on = false;
     int carry_slot = 0, carry_h = 0, carry_w = 0, carry_pad[4] = {0, 0, 0, 0}, carry_cin = 0;
     unsigned long carry_wver = 0;
@@ -93,13 +82,7 @@ struct eemplus_ctx {
 
 namespace {
 
-struct Cur { const float* p; const float* end; const float* take(size_t n) { const float* r = p; p += n; return r; } };
-struct Pk {
-    std::vector<float> host;
-    size_t push(size_t n) { size_t off = host.size(); host.resize(off + ((n + 3) & ~(size_t)3), 0.f); return off; }
-};
-
-void mk(Pk& pk, PLayer& L, const float* w, const float* b, int cin, int cout, int k, int stride) {
+void mk(Packer& pk, PLayer& L, const float* w, const float* b, int cin, int cout, int k, int stride) {
     L.cin = cin; L.cout = cout; L.k = k; L.stride = stride;
     const int cs[1] = {cin};
     L.wpk = pk.push(gconv_packed_floats(cout, cs, 1, k, k));
@@ -237,9 +220,9 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
     int rc;
     const size_t g = (size_t)h * w;
     for (int i = 0; i < 4; ++i)
-        if ((rc = pensure(c->d[i], B * kDW * g)) != EEM_OK) return rc;
-    if ((rc = pensure(c->t64, B * 64 * g)) != EEM_OK || (rc = pensure(c->t32, B * 32 * g)) != EEM_OK ||
-        (rc = pensure(c->flow[l], B * 2 * g)) != EEM_OK)
+        if ((rc = devbuf_ensure(c->d[i], B * kDW * g)) != EEM_OK) return rc;
+    if ((rc = devbuf_ensure(c->t64, B * 64 * g)) != EEM_OK || (rc = devbuf_ensure(c->t32, B * 32 * g)) != EEM_OK ||
+        (rc = devbuf_ensure(c->flow[l], B * 2 * g)) != EEM_OK)
         return rc;
     const int G = c->groups, per = kDW / G;
     // coarse levels: every conv is a handful of 16x16 tiles - the small-grid kernel of EEMFlow's tail (one launch per layer,
@@ -353,9 +336,9 @@ extern "C" int eemplus_create(int device, eemplus_ctx** out) {
 extern "C" void eemplus_destroy(eemplus_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    PBuf* one[] = {&c->padded, &c->a2, &c->dense, &c->xout, &c->tw, &c->fw, &c->cat, &c->t64, &c->t32,
+    DevBuf* one[] = {&c->padded, &c->a2, &c->dense, &c->xout, &c->tw, &c->fw, &c->cat, &c->t64, &c->t32,
                    &c->d[0], &c->d[1], &c->d[2], &c->d[3]};
-    for (PBuf* b : one) if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : one) if (b->p) (void)hipFree(b->p);
     if (c->side) {
         (void)hipStreamSynchronize(c->side);
         (void)hipStreamDestroy(c->side);
@@ -385,8 +368,8 @@ extern "C" int eemplus_load_weights(eemplus_ctx* c, const float* flat, size_t nf
     EEM_REQUIRE(groups == 3 || groups == 1, "eemplus_load_weights: groups must be 3 (reference default) or 1, got %d", groups);
     EEM_HIP_CHECK(hipSetDevice(c->device));
     ++c->wver;                                                     // (a stream's carried window is stale from here on, whatever follows)
-    Cur cur{flat, flat + nfloats};
-    Pk pk;
+    Cursor cur{flat, flat + nfloats};
+    Packer pk;
     c->zero_off = pk.push(4096);
     auto layer = [&](PLayer& L, int cin, int cout, int k, int stride) {
         const float* w = cur.take((size_t)cout * cin * k * k);
@@ -468,7 +451,7 @@ static int level_buffers(eemplus_ctx* c, int l, int B) {
     const size_t g = (size_t)c->hl[l] * c->wl[l];
     int rc;
     if ((rc = pensure_zeroed(c->cat_l[l], B * kCat * g)) != EEM_OK) return rc;
-    if (l <= 5 && ((rc = pensure(c->dense_l[l], B * kDense * g)) != EEM_OK || (rc = pensure(c->a2_l[l], B * 32 * g)) != EEM_OK)) return rc;
+    if (l <= 5 && ((rc = devbuf_ensure(c->dense_l[l], B * kDense * g)) != EEM_OK || (rc = devbuf_ensure(c->a2_l[l], B * 32 * g)) != EEM_OK)) return rc;
     return EEM_OK;
 }
 
@@ -517,9 +500,9 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
     const int h = hl[l], w = wl[l], hc = hl[l + 1], wc = wl[l + 1];
     const size_t g = (size_t)h * w;
     if ((rc = level_buffers(c, l, B)) != EEM_OK ||
-        (rc = pensure(c->xout, B * 3 * g)) != EEM_OK || (rc = pensure(c->finit[l], B * 2 * g)) != EEM_OK ||
-        (rc = pensure(c->tw, B * 2 * g)) != EEM_OK || (rc = pensure(c->fup[l], B * 2 * g)) != EEM_OK ||
-        (rc = pensure(c->fw, B * C[l] * g)) != EEM_OK)
+        (rc = devbuf_ensure(c->xout, B * 3 * g)) != EEM_OK || (rc = devbuf_ensure(c->finit[l], B * 2 * g)) != EEM_OK ||
+        (rc = devbuf_ensure(c->tw, B * 2 * g)) != EEM_OK || (rc = devbuf_ensure(c->fup[l], B * 2 * g)) != EEM_OK ||
+        (rc = devbuf_ensure(c->fw, B * C[l] * g)) != EEM_OK)
         return rc;
     float* const fi = c->finit[l].p;              // cdc_model's upsampled flow_init, kept per level (stage "flow_init<l>")
     float* const dense = c->dense_l[l].p;
@@ -541,7 +524,7 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
     if (!forced_init && (hc != h || wc != w) && fuse3 && (size_t)h * w >= 2 * (size_t)hc * wc) {
         // upsampling, the coarse flow's doubling and the warp by the upsampled flow as ONE launch; the doubled coarse flow lands in a
         // second buffer (the launch's other threads still read the plain one) that takes the coarse flow's place from here on
-        if ((rc = pensure(c->flow_alt[l + 1], B * 2 * (size_t)hc * wc)) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->flow_alt[l + 1], B * 2 * (size_t)hc * wc)) != EEM_OK) return rc;
         if ((rc = pl_upflow_warp_launch(c->flow[l + 1].p, c->flow_alt[l + 1].p, hc, wc, fi, a2, dense, kDense, 152, B, 32, h, w, st)) != EEM_OK) return rc;
         std::swap(c->flow[l + 1], c->flow_alt[l + 1]);
     } else {
@@ -608,11 +591,11 @@ static int stream_pyramid(eemplus_ctx* c, int nimg, bool carried, hipStream_t st
         need[l] = (size_t)nimg * C[l] * c->hl[l] * c->wl[l];
         grow = grow || need[l] > c->sf[l].cap;
     }
-    PBuf old[7];
+    DevBuf old[7];
     if (grow) {
         for (int l = 2; l <= 6; ++l) {
             old[l] = c->sf[l];
-            c->sf[l] = PBuf();
+            c->sf[l] = DevBuf();
             const size_t cap = need[l] > old[l].cap ? need[l] : old[l].cap;
             hipError_t e = hipMalloc(&c->sf[l].p, cap * sizeof(float));
             if (e != hipSuccess) {                               // (levels 2 .. l hold new buffers: back to the old ones)
@@ -649,7 +632,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
     const int B = batch, n2 = sp ? sp->nvol : 2 * batch, hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
     int rc;
     // ---- pad, encoder on both volumes (EEMFlow+.py:162-169); the stream: on its new windows (n2 = nvol images)
-    if ((rc = pensure(c->padded, (size_t)n2 * c->cin0 * hp * wp)) != EEM_OK) return rc;
+    if ((rc = devbuf_ensure(c->padded, (size_t)n2 * c->cin0 * hp * wp)) != EEM_OK) return rc;
     if (sp) {
         const size_t img = (size_t)c->cin0 * hp * wp;
         for (int i = 0; i < sp->nvol; ++i)
@@ -670,7 +653,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
     EEM_REQUIRE(hl[6] >= 1 && wl[6] >= 1, "eemplus_forward: padded input %dx%d is too small for the 6-level pyramid", hp, wp);
     const int C[7] = {0, 16, 32, 64, 64, 64, 64};
     for (int l = 1; l <= (sp ? 1 : 6); ++l)
-        if ((rc = pensure(c->f[l], (size_t)n2 * C[l] * hl[l] * wl[l])) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->f[l], (size_t)n2 * C[l] * hl[l] * wl[l])) != EEM_OK) return rc;
     // where the encoder and the pooling write levels 2..6: the forward's pyramid, or the stream's after the carried window
     float* fo[7] = {nullptr, c->f[1].p};
     if (sp) {
@@ -683,7 +666,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
     {
         const size_t s1 = (size_t)n2 * 16 * hl[1] * wl[1], s2 = (size_t)n2 * 32 * hl[2] * wl[2], s3 = (size_t)n2 * 64 * hl[3] * wl[3];
         size_t big = s1 > s2 ? s1 : s2; big = big > s3 ? big : s3;
-        if ((rc = pensure(c->dense, big)) != EEM_OK || (rc = pensure(c->fw, big)) != EEM_OK) return rc;
+        if ((rc = devbuf_ensure(c->dense, big)) != EEM_OK || (rc = devbuf_ensure(c->fw, big)) != EEM_OK) return rc;
         float* t0 = c->dense.p; float* t1 = c->fw.p;
         struct EStep { const float* in; float* out; int hin, win, hout, wout; };
         const EStep es[8] = {{c->padded.p, t0, hp, wp, hl[1], wl[1]},     {t0, c->f[1].p, hl[1], wl[1], hl[1], wl[1]},

@@ -504,9 +504,11 @@ int tr_loss_launch(const float* flow, const float* gt, const float* valid, float
 int tr_upsample_bwd_launch(const float* d, float* tmp, float* out, int nc, int oh, int ow, int h, int w, hipStream_t st) {
     const bool rows = ow >= 64 && ow <= 8192 && !sw_on<SW_EEM_UPBWD_THREADS>();     // (=1: the thread-per-target form, for the equality test)
     tr_last_form = rows ? "rows" : "threads";
-    if (rows)
-        hipLaunchKernelGGL(upbwd_x_rows_kernel, dim3((unsigned)(((long)nc * oh + 3) / 4)), dim3(256), 4 * ow * sizeof(float), st, d, tmp, (long)nc * oh, ow, w);
-    else
+    if (rows) {
+        const int lds = 4 * ow * (int)sizeof(float);                                // a row per wave: 128 KB at the widest
+        if (lds > 64 * 1024) EEM_RAISE_LDS(lds, upbwd_x_rows_kernel);
+        hipLaunchKernelGGL(upbwd_x_rows_kernel, dim3((unsigned)(((long)nc * oh + 3) / 4)), dim3(256), lds, st, d, tmp, (long)nc * oh, ow, w);
+    } else
         hipLaunchKernelGGL(upbwd_x_kernel, dim3(nblocks((long)nc * oh * w)), dim3(256), 0, st, d, tmp, (long)nc * oh, ow, w);
     hipLaunchKernelGGL(upbwd_y_kernel, dim3(nblocks((long)nc * h * w)), dim3(256), 0, st, tmp, out, nc, oh, h, w);
     EEM_HIP_CHECK(hipGetLastError());
@@ -612,12 +614,8 @@ int tr_wgrad_launch_batch(const WgradArgs* jobs, int njobs, hipStream_t st) {
                 const int tiles = (a0.n + ipt - 1) / ipt;
                 int w = 1024 / (nchunk * njobs);
                 w = w < 1 ? 1 : (w > tiles ? tiles : w);
-                static bool small_attr = false;
-                if (!small_attr) {
-                    EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_small_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_small_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    small_attr = true;
-                }
+                EEM_RAISE_LDS(160 * 1024, wgrad_small_kernel<3>);
+                EEM_RAISE_LDS(160 * 1024, wgrad_small_kernel<1>);
                 tr_last_form = "small";
                 if (a0.k == 3) hipLaunchKernelGGL((wgrad_small_kernel<3>), dim3(w, nchunk, njobs), dim3(256), lb, st, b, ipt);
                 else hipLaunchKernelGGL((wgrad_small_kernel<1>), dim3(w, nchunk, njobs), dim3(256), lb, st, b, ipt);
@@ -632,12 +630,7 @@ int tr_wgrad_launch_batch(const WgradArgs* jobs, int njobs, hipStream_t st) {
     const int kh = a.kh ? a.kh : a.k, kw = a.kh ? a.kw : a.k;
 #define WG_CASE(KH_, KW_, S_)                                                                                                   \
     if (kh == KH_ && kw == KW_ && a.stride == S_) {                                                                             \
-        static bool attr = false;                                                                                               \
-        if (!attr) {                                                                                                            \
-            EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_kernel<KH_, KW_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                              160 * 1024));                                                                     \
-            attr = true;                                                                                                        \
-        }                                                                                                                       \
+        EEM_RAISE_LDS(160 * 1024, wgrad_kernel<KH_, KW_, S_>);                                                                  \
         hipLaunchKernelGGL((wgrad_kernel<KH_, KW_, S_>), grid, dim3(256), lds_bytes, st, b);                                    \
         EEM_HIP_CHECK(hipGetLastError());                                                                                       \
         return EEM_OK;                                                                                                          \

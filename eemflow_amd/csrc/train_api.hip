@@ -498,6 +498,12 @@ extern "C" int eemflow_sequence_loss(const float* flow, const float* flow_gt, co
     return tr_loss_launch(flow, flow_gt, valid, dflow_out, batch, h * w, weight, stats6, (hipStream_t)stream);
 }
 
+// the adjoint of eemflow_upsample_bilinear on caller tensors, as the backward runs it: d [nc][oh][ow] -> out [nc][h][w]; tmp [nc][oh][w]
+extern "C" int eemflow_upsample_bilinear_bwd(const float* d, float* tmp, float* out, int nc, int oh, int ow, int h, int w, void* stream) {
+    EEM_REQUIRE(d && tmp && out && nc >= 1 && h >= 1 && w >= 1 && oh >= 1 && ow >= 1, "eemflow_upsample_bilinear_bwd: bad arguments");
+    return tr_upsample_bwd_launch(d, tmp, out, nc, oh, ow, h, w, (hipStream_t)stream);
+}
+
 // Forward + loss + backward.  grad_out (device, nflat floats, state_dict order) receives d loss / d parameter;
 // stats_out (host, 5 doubles): loss, mean epe, valid count, fraction < 1 px, fraction < 3 px.
 extern "C" int eemflow_forward_backward(eemflow_ctx* c, const float* e1, const float* e2, const float* flow_gt, const float* valid,

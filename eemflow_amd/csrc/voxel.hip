@@ -538,16 +538,11 @@ inline int vox_ept(long n) {
 constexpr long VOX_MAX_BLOCKS = 4096;                              // 33.5 M events at 8 per thread; beyond: direct kernel
 
 template <int EPT>
-void launch_bin(const VoxJobs& jobs, int njobs, long nblk_max, int bins, int h, int w, const VoxPlan& pl, hipStream_t stream) {
+int launch_bin(const VoxJobs& jobs, int njobs, long nblk_max, int bins, int h, int w, const VoxPlan& pl, hipStream_t stream) {
     constexpr int stage_bytes = VT * EPT * 12;
-    if (stage_bytes > 48 * 1024) {
-        static bool raised = false;
-        if (!raised) {
-            (void)hipFuncSetAttribute((const void*)vox_bin_kernel<EPT>, hipFuncAttributeMaxDynamicSharedMemorySize, stage_bytes);
-            raised = true;
-        }
-    }
+    if (stage_bytes > 48 * 1024) EEM_RAISE_LDS(stage_bytes, vox_bin_kernel<EPT>);
     hipLaunchKernelGGL((vox_bin_kernel<EPT>), dim3((unsigned)nblk_max, njobs), dim3(VT), stage_bytes, stream, jobs, bins, h, w, pl);
+    return EEM_OK;
 }
 
 bool make_plan(int64_t n, int bins, int h, int w, const double* events, VoxPlan* pl, int* lds_bytes) {
@@ -631,19 +626,15 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
             EEM_REQUIRE((long)J.nblk * VT * ept <= slots, "voxelize: slab budget (n=%ld, ept=%d)", (long)n[k], ept);
             nblk_max = std::max(nblk_max, (long)J.nblk);
         }
+        int rc;
         switch (ept) {
-            case 1: launch_bin<1>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
-            case 2: launch_bin<2>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
-            case 4: launch_bin<4>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
-            default: launch_bin<8>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
+            case 1: rc = launch_bin<1>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
+            case 2: rc = launch_bin<2>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
+            case 4: rc = launch_bin<4>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
+            default: rc = launch_bin<8>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
         }
-        if (lds > 64 * 1024 - 12 * 1024) {
-            static thread_local int raised = 0;
-            if (raised < lds) {
-                EEM_HIP_CHECK(hipFuncSetAttribute((const void*)vox_band_kernel<VT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                raised = lds;
-            }
-        }
+        if (rc != EEM_OK) return rc;
+        if (lds > 64 * 1024 - 12 * 1024) EEM_RAISE_LDS(lds, vox_band_kernel<VT>);
         bool aligned = true;
         for (int k = 0; k < njobs; ++k) aligned = aligned && ((uintptr_t)grid[k] & 15) == 0;
         const int vec4 = (pl.band_px % 4 == 0 && pl.hw % 4 == 0 && aligned) ? 1 : 0;

@@ -377,12 +377,7 @@ int launch(const WgradArgs& a, hipStream_t st) {
 #ifdef EEM_DIAG
     { static int once = [] { int v = sw_int<SW_EEM_WG_DBG>(); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg_dbg), &v, sizeof v); return v; }(); (void)once; }
 #endif
-    static bool raised = false;
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_enc_kernel<MT, S, TW, CP, KH, KW, BX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024));
-        raised = true;
-    }
+    EEM_RAISE_LDS(160 * 1024, wgrad_enc_kernel<MT, S, TW, CP, KH, KW, BX>);
     // bit 0, the other tile walk, stays clear (measured: no difference, profiles/r06_wgwalk.txt - its operands come out of L2 / MALL either way);
     // bit 1 (EEM_WGRAD_BURST=1): a tile's requests in one block behind the barrier, the form through round 6's first half
     const int flags = sw_on<SW_EEM_WGRAD_BURST>() ? 2 : 0;

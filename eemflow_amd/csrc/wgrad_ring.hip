@@ -457,11 +457,7 @@ int launch_ring(const WgradArgs& a, hipStream_t st) {
 #ifdef EEM_DIAG
     { static int once = [] { int v = sw_int<SW_EEM_WG_DBG>(); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wr_dbg), &v, sizeof v); return v; }(); (void)once; }
 #endif
-    static bool raised = false;
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_ring_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
+    EEM_RAISE_LDS(160 * 1024, wgrad_ring_kernel<C>);
     hipLaunchKernelGGL((wgrad_ring_kernel<C>), dim3(gx), dim3(512), lds_bytes, st, a, q);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

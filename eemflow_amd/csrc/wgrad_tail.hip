@@ -233,11 +233,7 @@ int wgrad_tail_launch(const WgradArgs* jobs, int njobs, int n, int h, int w, hip
     const int PL = (h + 2) * (w + 2);
     const size_t lds_bytes = ((size_t)64 * gp + 16 * ipt * PL + 2 * kmax + PL) * 4;
     EEM_REQUIRE(lds_bytes <= 160 * 1024, "wgrad_tail: %zu bytes of LDS", lds_bytes);
-    static bool raised = false;
-    if (!raised) {
-        EEM_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-    }
+    EEM_RAISE_LDS(160 * 1024, wgrad_tail_kernel);
     const int dbg = sw_int_once<SW_EEM_TW_DBG>();    // measurement: 1 no atomics, 2 no k-loop, 4 no G staging
     tr_last_form = "wgrad_tail";
     hipLaunchKernelGGL(wgrad_tail_kernel, dim3((unsigned)hb.size()), dim3(256), lds_bytes, st, tc->djobs, tc->dblocks, n, h, w, ipt, gp, dbg);

@@ -8,14 +8,8 @@
 thread_local unsigned long g_realloc_events = 0;
 
 int ensure(DevBuf& b, size_t floats) {
-    if (floats <= b.cap) return EEM_OK;
-    ++g_realloc_events;
-    if (b.p) EEM_HIP_CHECK(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    EEM_HIP_CHECK(hipMalloc(&b.p, floats * sizeof(float)));
-    b.cap = floats;
-    return EEM_OK;
+    if (floats > b.cap) ++g_realloc_events;
+    return devbuf_ensure(b, floats);
 }
 
 // The device-resident flat weights changed (load / optimizer step): every Winograd-domain copy is stale; a launch recomputes the one it

@@ -213,6 +213,8 @@ int eemflow_local_corr53(const float* f1, const float* f2, int batch, int c, int
  * Replaces: EEMFlow.upsample_flow = F.interpolate(..., mode='bilinear', align_corners=False)
  * (model/EEMFlow/EEMFlow.py:118-120). */
 int eemflow_upsample_bilinear(const float* in, float* out, int nc, int h, int w, int oh, int ow, void* stream);
+/* Its adjoint, the kernels eemflow_backward runs: d [nc][oh][ow] -> out [nc][h][w]; tmp: [nc][oh][w] floats of scratch. */
+int eemflow_upsample_bilinear_bwd(const float* d, float* tmp, float* out, int nc, int oh, int ow, int h, int w, void* stream);
 
 /* Evaluation statistics of one flow field against its ground truth, on the device.
  * Replaces: Test.flow_error (test_mvsec.py:291-346).  flow_gt, flow_pred: [2][h][w]; event_img: [h][w] event counts for the

@@ -263,6 +263,32 @@ def test_batched_jobs_equal_the_one_job_calls(form, jobs):
             assert abs(a - b) <= 1e-9 * abs(b), k
 
 
+@functools.lru_cache(maxsize=None)
+def stream_sets():
+    h, w = 260, 346
+    flow = smooth_flow(h, w)
+    sets = [make_events(700 + k, 40_000 + 500 * k, h, w) for k in range(4)]
+    return h, w, flow, sets, [iwe_reference(ev, flow, h, w, t_ref="end") for ev in sets]
+
+
+@pytest.mark.parametrize("nstreams", [2, 10])
+def test_alternating_streams_share_the_scratch_safely(form, nstreams):
+    """Calls from one thread on several streams: up to eight streams keep a scratch arena each, further ones take over the least
+    recently used arena behind an event (the ninth and tenth stream here)."""
+    h, w, flow, sets, refs = stream_sets()
+    streams = [torch.cuda.Stream(DEV) for _ in range(nstreams)]
+    outs = []
+    for rep in range(3):
+        for k, ev in enumerate(sets):
+            with torch.cuda.stream(streams[(rep * len(sets) + k) % nstreams]):
+                images, moments = iwe.iwe_many([ev.to(DEV)], [flow.to(DEV)])
+                outs.append((k, images[0], moments[0]))
+    torch.cuda.synchronize(DEV)
+    for k, image, moments in outs:
+        assert close(image, refs[k][0]), k
+        check_moments(image, moments)
+
+
 def test_fwl_many_rides_each_set_twice(form):
     h, w = 64, 61
     flow = smooth_flow(h, w)

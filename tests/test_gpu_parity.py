@@ -554,10 +554,10 @@ def test_voxelizer_more_than_512_blocks(monkeypatch):
     assert float((binned - direct).abs().max()) < 2e-4 and float(direct.abs().max()) > 1.0
 
 
-@pytest.mark.parametrize("nstreams", [2, 6])
+@pytest.mark.parametrize("nstreams", [2, 6, 10])
 def test_voxelizer_alternating_streams_share_the_scratch_safely(nstreams):
-    """Calls from one thread on several streams: up to four streams keep a scratch arena each, further ones take over the least
-    recently used arena behind an event."""
+    """Calls from one thread on several streams: up to eight streams keep a scratch arena each, further ones take over the least
+    recently used arena behind an event (the ninth and tenth of ten streams)."""
     h, w, bins = 260, 346, 5
     seqs = [EventSequence(None, {"height": h, "width": w}, features=_clustered_events(90 + k, 40_000 + 7000 * k, h, w),
                           timestamp_multiplier=1e6, convert_to_relative=True) for k in range(4)]

@@ -348,6 +348,30 @@ def test_backward_stages_against_fp64(monkeypatch, env, b, h, w, kw):
     run_case(monkeypatch, env, b, h, w, seed=40 + b + h % 7, **kw)
 
 
+def test_upsample_backward_rows_of_more_than_64_kb(monkeypatch):
+    """An output width of 4100 is the first whose row form stages more than 64 KB of LDS (4 waves x 4100 floats): the launch has to raise
+    the kernel's limit first.  Both forms against fp64 under the `ups_bwd` limits, as the `upbwd_threads` case compares them, and
+    against each other: they add the same <= 4 products per column in another order and the same two rows, 16 u of the adjoint of |d|
+    covers both sums' rounding (3 u each in x, and the y pass on inputs that differ by that)."""
+    nc, oh, ow, h, w = 1, 2, 4100, 1, 2050
+    d = torch.randn(1, nc, oh, ow, generator=torch.Generator().manual_seed(77))
+    dd = d.to(DEV)
+    got = {}
+    for form, env in (("rows", {}), ("threads", {"EEM_UPBWD_THREADS": "1"})):
+        pin(monkeypatch, env)
+        tmp, out = torch.empty(nc, oh, w, device=DEV), torch.empty(1, nc, h, w, device=DEV)
+        _lib.check(_lib.lib().eemflow_upsample_bilinear_bwd(dd.data_ptr(), tmp.data_ptr(), out.data_ptr(), nc, oh, ow, h, w,
+                                                            _lib.current_stream_ptr(dd.device)))
+        got[form] = out.cpu()
+    ref, mag = B.upsample_bwd_ref(d, (h, w))
+    for form, out in got.items():
+        B.check(f"upsample.bwd {form} {oh}x{ow} -> {h}x{w}", out, ref, mag, "ups_bwd", form=form)
+    diff = (got["rows"].double() - got["threads"].double()).abs()
+    bound = 16 * B.U * mag / (1 + h + w)
+    print("rows against threads: max |d| %.3e, worst d / bound %.3f" % (float(diff.max()), float((diff / bound).max())))
+    assert float(ref.abs().max()) > 1.0 and bool((diff <= bound).all())
+
+
 def test_gradient_buffers_refuse_when_stale(monkeypatch):
     """g_ buffers are readable only after a backward of the CURRENT training forward; the training activations only while the workspace
     holds that forward."""
