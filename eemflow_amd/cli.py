@@ -75,6 +75,19 @@ def build_parser():
             q.add_argument('--smooth_weight_type', default='gauss', choices=('gauss', 'exp'), help='with --smooth_weight: exp(-mean g^2) or exp(-mean |g|)')
             q.add_argument('--smooth_error', default='L1', choices=('L1', 'abs_robust'), help='with --smooth_weight: |d| or (|d| + 0.01)^0.4')
             q.add_argument('--smooth_all', action='store_true', help='with --smooth_weight: all predictions under the sequence loss\'s gamma, not the last alone')
+            q.add_argument('--photo_weight', default=0.0, type=float, metavar='W',
+                           help='add W times the photometric / census loss between the old event volume and the new one warped back by the '
+                                'last prediction to the loss (Loss_tools.photo_loss_multi_type / census_loss_torch of the reference, no '
+                                'ground truth needed; every model then trains through the autograd engine and EEMFlow predicts at the full '
+                                'frame)')
+            q.add_argument('--photo_kind', default='census', choices=('abs_robust', 'charbonnier', 'L1', 'census'), help='with --photo_weight: the loss between the volumes')
+            q.add_argument('--photo_occ', action='store_true',
+                           help='with --photo_weight: a second forward pass with the volumes exchanged (no gradient) and the forward-backward '
+                                'check give the occlusion mask of the loss')
+            q.add_argument('--photo_all', action='store_true', help='with --photo_weight: all predictions under the sequence loss\'s gamma, not the last alone')
+            q.add_argument('--photo_q', default=0.4, type=float, metavar='Q', help='with --photo_kind census: the exponent')
+            q.add_argument('--photo_charbonnier', action='store_true', help='with --photo_kind census: (dist^2 + eps)^q in place of (|dist| + 0.01)^q')
+            q.add_argument('--photo_max_distance', default=3, type=int, choices=(1, 2, 3), metavar='R', help='with --photo_kind census: patches of (2R+1)^2 cells')
         q.add_argument('--device_events', action='store_true',
                        help='prepare the event sets on the GPU from the npz columns (HREM datasets: the columns are uploaded in their file '
                             'dtypes and one launch per sample writes the float64 event tables; the same samples bit for bit, a set whose '
@@ -170,11 +183,20 @@ def smooth_kw(args):
                 smooth_error=getattr(args, "smooth_error", "L1"), smooth_all=bool(getattr(args, "smooth_all", False)))
 
 
+def photo_kw(args):
+    """TrainRaftEvents' photometric arguments of the --photo_* flags."""
+    return dict(photo_weight=float(getattr(args, "photo_weight", 0.0)), photo_kind=getattr(args, "photo_kind", "census"),
+                photo_occ=bool(getattr(args, "photo_occ", False)), photo_all=bool(getattr(args, "photo_all", False)),
+                photo_q=float(getattr(args, "photo_q", 0.4)), photo_charbonnier=bool(getattr(args, "photo_charbonnier", False)),
+                photo_max_distance=int(getattr(args, "photo_max_distance", 3)))
+
+
 def train(args):
     from . import harness, parallel
     from .hrem import HREMEventFlow
-    if getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0:
-        raise SystemExit("--self_supervised needs a --contrast_weight: there is no other loss")
+    photo = float(getattr(args, "photo_weight", 0.0))
+    if getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0 and photo == 0.0:
+        raise SystemExit("--self_supervised needs a --contrast_weight or a --photo_weight: there is no other loss")
     # one process per GPU under torchrun: every rank trains on its shard of the samples, the trainer all-reduces the flat gradient
     # (RCCL), rank 0 writes the logs and checkpoints
     rank, local_rank, world = parallel.init_distributed()
@@ -184,7 +206,7 @@ def train(args):
         parallel.pin_host_threads_to_gpu_numa(parallel.local_device_index(local_rank))
     config = load_config(args.config)
     contrast = float(getattr(args, "contrast_weight", 0.0))
-    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0)
+    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0 and photo == 0.0)    # (both terms need the full frame)
     config["train"]["lr"] = args.lr                                                  # train_EEMFlow_HREM.py:56-59
     config["train"]["wdecay"] = args.wd
     config["train"]["num_steps"] = args.train_iters
@@ -233,11 +255,11 @@ def train(args):
     # EEMFlow: the fused step inside the library; E-RAFT / EEMFlow+: the reference's statement sequence over the operator-level
     # autograd route (their data-parallel exchange is the flat-gradient all-reduce in TrainRaftEvents._train_iters_autograd)
     smooth = float(getattr(args, "smooth_weight", 0.0))
-    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has neither term)
+    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and photo == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has none of the terms)
     tr = harness.TrainRaftEvents(loader, None, lr=tcfg["lr"], wdecay=tcfg["wdecay"], epsilon=tcfg["epsilon"],
                                  num_steps=tcfg["num_steps"], clip=tcfg["clip"], gamma=tcfg["gamma"], logger=logger,
                                  start_iteration=start_iteration, engine=engine, mixed_precision=tcfg.get("mixed_precision", True),
-                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args))
+                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args), **photo_kw(args))
     for epoch in range(start_epoch, max(args.train_iters // args.val_iters, 1)):
         if sampler is not None:
             sampler.set_epoch(epoch)

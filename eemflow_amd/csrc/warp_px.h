@@ -11,6 +11,7 @@ struct WarpTaps {
     float nw, ne, sw, se;        // bilinear weights of the four corners
     int o_nw, o_ne, o_sw, o_se;  // their offsets in a [h][w] plane, -1: outside (zero padding)
     float m;                     // mode 2: the `grid_sample(ones) >= 1` mask, else 1
+    float wx, wy;                // ix - floor(ix), iy - floor(iy): the weights' factors, for the blend's derivative (photo.hip)
 };
 
 // mode 0: align_corners=True (EEMFlow_cdc.warp); 1: align_corners=False (torch_warp);
@@ -33,6 +34,7 @@ __device__ __forceinline__ WarpTaps warp_taps(float fx, float fy, int h, int w, 
     const float wgt_w = ix - xw, wgt_e = 1.f - wgt_w, wgt_n = iy - yn0, wgt_s = 1.f - wgt_n;
     WarpTaps t;
     t.nw = wgt_s * wgt_e; t.ne = wgt_s * wgt_w; t.sw = wgt_n * wgt_e; t.se = wgt_n * wgt_w;
+    t.wx = wgt_w; t.wy = wgt_n;
     // the float -> int conversion must not overflow for wild flows
     const float cx = fminf(fmaxf(xw, -2.f), (float)w + 1.f), cy = fminf(fmaxf(yn0, -2.f), (float)h + 1.f);
     const int x0 = (int)cx, y0 = (int)cy;

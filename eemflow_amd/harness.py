@@ -27,7 +27,7 @@ import torch
 
 from .metrics import flow_error, flow_error_from_sums, flow_error_sums, flow_error_sums_many
 from . import parallel
-from .train import EEMFlowTrainer, contrast_loss, sequence_loss, smoothness_loss
+from .train import EEMFlowTrainer, contrast_loss, photo_loss, sequence_loss, smoothness_loss
 
 
 class Logger:
@@ -477,20 +477,38 @@ class TrainRaftEvents:
     smooth_weight_type ('gauss', 'exp') and smooth_error ('L1', 'abs_robust'); of the last prediction, or with smooth_all=True of all
     predictions under the engine's gamma.  A prediction at mesh size (out_mesh_size=True) has no edge image of its size and is
     regularised unweighted (img=None).  supervised=False still needs a contrast_weight: smoothness alone is minimised by a constant
-    flow.  With smooth_weight == 0 nothing is computed and nothing changes."""
+    flow.  With smooth_weight == 0 nothing is computed and nothing changes.
+
+    photo_weight (the autograd engine only): photo_weight * train.photo_loss(predictions, event_volume_old, event_volume_new as the
+    model received them) is added to the loss - the photometric ('abs_robust', 'charbonnier', 'L1') or 'census' loss between the old
+    volume and the new one warped back by the prediction, photo_q / photo_charbonnier / photo_max_distance being census's settings; of
+    the last prediction, or with photo_all=True of all predictions under the engine's gamma.  The prediction must be at the frame's
+    size.  photo_occ=True runs model(new, old) under torch.no_grad(), takes mask_fw of metrics.fb_check(final forward flow, final
+    backward flow) and hands it to the loss with use_occ=True; a model whose BatchNorm layers are in train mode (E-RAFT before
+    freeze_bn()) is refused, because the second pass would move their running statistics.  supervised=False is satisfied by a
+    contrast_weight or a photo_weight.  With photo_weight == 0 nothing is computed and nothing changes."""
 
     def __init__(self, loader, image_size, lr=1e-4, wdecay=5e-5, epsilon=1e-8, num_steps=1000000, clip=1.0, gamma=0.8,
                  logger=None, print_freq=100, engine="fused", mixed_precision=True, start_iteration=0, contrast_weight=0.0,
                  supervised=True, smooth_weight=0.0, smooth_order=1, smooth_constant=1.0, smooth_weight_type="gauss", smooth_error="L1",
-                 smooth_all=False):
+                 smooth_all=False, photo_weight=0.0, photo_kind="census", photo_occ=False, photo_all=False, photo_q=0.4,
+                 photo_charbonnier=False, photo_max_distance=3):
         if engine not in ("fused", "autograd"):
             raise ValueError("engine must be 'fused' or 'autograd'")
         self.contrast_weight, self.supervised = float(contrast_weight), bool(supervised)
         if engine == "fused" and (self.contrast_weight != 0.0 or not self.supervised):
             raise ValueError("TrainRaftEvents: the contrast term (contrast_weight != 0, supervised=False) is honoured by engine='autograd' "
                              "only - the fused trainer has no contrast term")
-        if not self.supervised and self.contrast_weight == 0.0:
-            raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight")
+        self.photo_weight, self.photo_occ, self.photo_all = float(photo_weight), bool(photo_occ), bool(photo_all)
+        self.photo_kw = dict(kind=photo_kind, q=photo_q, charbonnier=photo_charbonnier, max_distance=photo_max_distance)
+        if self.photo_weight != 0.0:
+            if engine == "fused":
+                raise ValueError("TrainRaftEvents: the photometric term (photo_weight != 0) is honoured by engine='autograd' only - the "
+                                 "fused trainer has no photometric term")
+            from .photo import _settings as photo_settings
+            photo_settings("TrainRaftEvents", photo_kind, photo_occ, photo_q, photo_charbonnier, True, photo_max_distance)
+        if not self.supervised and self.contrast_weight == 0.0 and self.photo_weight == 0.0:
+            raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight or a photo_weight")
         self.smooth_weight, self.smooth_all = float(smooth_weight), bool(smooth_all)
         self.smooth_kw = dict(order=smooth_order, constant=smooth_constant, weight_type=smooth_weight_type, error_type=smooth_error)
         if self.smooth_weight != 0.0:
@@ -536,6 +554,7 @@ class TrainRaftEvents:
                 self._contrast_inputs(batch)                       # (before any GPU work: a loader without events fails at once)
             e1 = batch['event_volume_old'].to(dev).float()
             e2 = batch['event_volume_new'].to(dev).float()
+            back = self._photo_backward_flow(model, e1, e2) if self.photo_weight != 0.0 and self.photo_occ else None
             _, flow_list = model(e1, e2)
             if self.supervised:
                 flow_gt, valid = _target_like(flow_list[-1], batch['flow'].to(dev).float(), batch['valid'].to(dev).float())
@@ -546,6 +565,8 @@ class TrainRaftEvents:
                 loss = loss + self.contrast_weight * self._contrast_term(flow_list[-1], batch, e1)
             if self.smooth_weight != 0.0:
                 loss = loss + self.smooth_weight * self._smooth_term(flow_list, e1)
+            if self.photo_weight != 0.0:
+                loss = loss + self.photo_weight * self._photo_term(flow_list, e1, e2, back)
             self.scaler.scale(loss).backward()
             if parallel.exchange_active():
                 # the still-SCALED gradients are exchanged, then unscaled: an overflow on one rank reaches every rank through the
@@ -597,6 +618,30 @@ class TrainRaftEvents:
         at another size than the volume (the mesh flow) is regularised unweighted."""
         img = volume if tuple(flow_list[-1].shape[-2:]) == tuple(volume.shape[-2:]) else None
         return smoothness_loss(flow_list, img, gamma=self.opt["gamma"] if self.smooth_all else None, **self.smooth_kw).float()
+
+    @staticmethod
+    def _photo_backward_flow(model, e1, e2):
+        """The final flow of a gradient-free pass with the volumes exchanged, for photo_occ's mask.  It runs BEFORE the pass that is
+        differentiated, so whatever the model keeps between its forward and its backward belongs to that one."""
+        if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training for m in model.modules()):
+            raise ValueError("TrainRaftEvents: photo_occ=True runs the model a second time, which would move the running statistics of "
+                             "its train-mode BatchNorm layers - freeze them first (E-RAFT: freeze_bn())")
+        with torch.no_grad():
+            _, back = model(e2, e1)
+        return back[-1].float().contiguous()
+
+    def _photo_term(self, flow_list, e1, e2, back):
+        """train.photo_loss of the predictions between the two event volumes (float32, as the supervised loss is); with photo_occ the
+        mask is mask_fw of the forward-backward check of the final prediction against `back`."""
+        if tuple(flow_list[-1].shape[-2:]) != tuple(e1.shape[-2:]):
+            raise ValueError(f"TrainRaftEvents: the photometric term needs the prediction at the event frame's size {tuple(e1.shape[-2:])}, "
+                             f"got {tuple(flow_list[-1].shape[-2:])} - a model with out_mesh_size=True predicts the mesh flow")
+        mask = None
+        if self.photo_occ:
+            from .metrics import fb_check
+            mask = fb_check(flow_list[-1].detach().float().contiguous(), back)[0]
+        return photo_loss(flow_list, e1, e2, gamma=self.opt["gamma"] if self.photo_all else None, mask=mask, use_occ=self.photo_occ,
+                          **self.photo_kw).float()
 
     def train_iters(self, model, start_epoch=0, val_iters=None):
         if self.image_size is None:                              # padder sized from the data (cli: un-cropped HREM frames)

@@ -341,6 +341,43 @@ int eemflow_smoothness_many(int k, const float* const* pred, const float* const*
  * Replaces: nothing in the reference (torch.mean owns its temporaries). */
 size_t eemflow_smoothness_scratch_doubles(int k, int B, int H, int W);
 
+/* Photometric / census loss between img1 and img2 warped back by a predicted flow, for k (1..16) predictions of one shape, and its
+ * gradient with respect to the flow: the data term of ground-truth-free training.  flow[i] ([B][2][H][W] fp32), img1[i] and img2[i]
+ * ([B][C][H][W] fp32, any C >= 1), mask[i] ([B][1][H][W] fp32; a NULL entry, or mask == NULL, is a mask of ones) and grad[i]
+ * ([B][2][H][W] fp32) are HOST arrays of device pointers, read before the call returns; all contiguous.
+ * Yw = grid_sample(img2, grid + flow) is warp_px.h mode 1 in fp32, bit for bit eemplus_warp(mode 1) and the forward-backward check;
+ * everything after it is unfused fp64 on those fp32 values.  With d = img1 - Yw per element:
+ *   kind 0 'abs_robust' l = (|d| + 0.01)^0.4;   1 'charbonnier' l = (d*d + 1e-6)^0.4;   2 'L1' l = |d + 1e-6|
+ *   use_occ == 0: L = sum(l) / (B*C*H*W);  else L = sum(l * mask) / (sum(mask) + 1e-6), the mask broadcast over C in the numerator
+ *   and summed over its own B*H*W cells in the denominator.
+ *   kind 3 'census', r = max_distance in 1..3: g(I) = sum_c gray[c] * I_c (gray: DEVICE array of C doubles; NULL: 0.2989, 0.5870,
+ *   0.1140 at C == 3, else 1/C each), 0 outside the frame; per centre p and the (2r+1)^2 offsets k: t_k(p) = tau(g(p+k) - g(p)),
+ *   tau(x) = x / sqrt(0.81 + x*x);  e = (t_k(img1) - t_k(Yw))^2;  dist(p) = sum_k e / (0.1 + e);  mask' = mask times the indicator of
+ *   r <= y < H-r, r <= x < W-r;  n = B*H*W;  then the four branches of the reference's photo_loss_function:
+ *     charbonnier, use_occ:  S = sum((dist^2 + 1e-6)^q * mask'), M = sum(mask');  L = (S/n) / ((M/n)*2 + 1e-6) (average) or S / (M*2 + 1e-6)
+ *     charbonnier, no occ:   sum((dist^2 + 1e-8)^q) / n (average) or the sum; no mask, the border included
+ *     abs_robust, use_occ:   sum((|dist| + 0.01)^q * mask') / (2 * sum(mask') + 1e-6), whatever `average` says
+ *     abs_robust, no occ:    sum((|dist| + 0.01)^q) / n (average) or the sum
+ * loss (device, k doubles; may be NULL) receives L per job.  grad (may be NULL) receives coef[i] * dL_i / dflow_i, every cell written:
+ * dL/dflow(p) = sum_c dL/dYw_c(p) * dYw_c/d(u,v)(p), the warp derivative being that of the bilinear blend at the fp32 tap weights
+ * (corners outside the frame are zeros) times (W/2) * (2/max(W-1,1)) (and the same in H), in fp64, rounded to fp32 once; |x| has
+ * derivative 0 at 0 and the denominators do not depend on the flow.  For census dL/dg(Yw)(p) is gathered over p's own taps and the
+ * centres whose patch holds p from a per-centre factor plane in LDS: no atomics anywhere, losses and gradients are bitwise
+ * reproducible.  coef is a DEVICE array of k doubles (the upstream gradient; NULL: 1).  scratch (device,
+ * eemflow_photo_scratch_doubles(k, B, H, W) doubles) is always needed: the denominators and the per-block partial sums, added in a
+ * fixed order.  Consecutive jobs that name one img1 pointer grey-combine it once per tile; a job's results are bitwise those of a
+ * one-job call.  Stream-ordered, no host synchronisation, no allocation.  Errors: k out of range, unknown kind, census with r outside
+ * 1..3 or H <= 2r or W <= 2r, neither loss nor grad.  Non-finite inputs propagate.
+ * Replaces: Loss_tools.photo_loss_multi_type (utils_luo/tools.py:3112-3135; SSIM excepted), Loss_tools.photo_loss_function
+ * (3137-3169) and Loss_tools.census_loss_torch (3171-3212) on tensor_tools.torch_warp (2262-2306), and their autograd. */
+int eemflow_photo_many(int k, const float* const* flow, const float* const* img1, const float* const* img2, const float* const* mask,
+                       int B, int C, int H, int W, int kind, int use_occ, int charbonnier, int average, int max_distance, double q,
+                       const double* gray, const double* coef, double* loss, float* const* grad, double* scratch, void* stream);
+
+/* Doubles of scratch that eemflow_photo_many needs for k jobs of shape [B][2][H][W] (0 for arguments it would refuse).
+ * Replaces: nothing in the reference (torch.sum owns its temporaries). */
+size_t eemflow_photo_scratch_doubles(int k, int B, int H, int W);
+
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
  * receive, per event, the int64 flat index x + y*w + bin*w*h of the left / right temporal vote, or -1
