@@ -27,6 +27,11 @@ void eem_set_error(const char* fmt, ...);
 // name of the kernel instantiation this thread's last convolution launch chose (gconv.hip; eemop_last_conv_form reports it): a test
 // observable - one pointer store on the host per launch
 extern thread_local const char* eem_conv_form;
+// ... and of this thread's last launch through one of the other launch functions EEMFlow+'s forward uses (tail_conv_launch, wnc_launch,
+// enc_conv_launch, corr_launch, the pl_*_launch of plus_kernels.hip): set by the launch function itself, so it names what ran.
+// tail_conv_launch puts its job count beside the name, in eem_launch_jobs; eemplus_record_stages files "<name>_j<jobs>" for it.
+extern thread_local const char* eem_launch_form;
+extern thread_local int eem_launch_jobs;
 
 #define EEM_HIP_CHECK(expr)                                                            \
     do {                                                                               \

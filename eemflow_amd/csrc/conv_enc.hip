@@ -265,23 +265,24 @@ int enc_conv_launch(int cin, int cout, int stride, const EncConvArgs& a, hipStre
         return EEM_ERR_ARG;
     }
     if (a.in_norm) {                                     // raw voxel grids + normalisation records: only conv_enc1.hip reads that form
-        if (cin == 5 && cout == 16 && stride == 2 && enc1_supported(a)) return enc1_launch(a, stream);
+        if (cin == 5 && cout == 16 && stride == 2 && enc1_supported(a)) { eem_launch_form = "enc1"; return enc1_launch(a, stream); }
         eem_set_error("deferred input normalisation needs the 5-bin first layer on 16-byte-aligned volumes whose width is a multiple of 4 "
                       "and that pad on the bottom only (conv_enc1.hip); normalise in the voxelizer instead");
         return EEM_ERR_ARG;
     }
-    if (a.ws2r && s2r_supported(cin, cout, stride, a)) return s2r_launch(cin, a, stream);
-    if (a.wbx3 && bx3_supported(cin, cout, stride, a)) return bx3_launch(cin, stride, a, stream);
-    if (a.wwino && wino_supported(cin, cout, stride, a.win)) return wino_launch(cin, a, stream);
-    if (a.wpk2 && enc2_supported(cin, cout, stride, a.win)) return enc_conv2_launch(cin, cout, stride, a, stream);
+    // (eem_launch_form: the kernel family the launch goes to; the generic launch<> forms carry their shape)
+    if (a.ws2r && s2r_supported(cin, cout, stride, a)) { eem_launch_form = "s2r"; return s2r_launch(cin, a, stream); }
+    if (a.wbx3 && bx3_supported(cin, cout, stride, a)) { eem_launch_form = "bx3"; return bx3_launch(cin, stride, a, stream); }
+    if (a.wwino && wino_supported(cin, cout, stride, a.win)) { eem_launch_form = a.wino_f4 ? "wino4" : "wino"; return wino_launch(cin, a, stream); }
+    if (a.wpk2 && enc2_supported(cin, cout, stride, a.win)) { eem_launch_form = "enc2"; return enc_conv2_launch(cin, cout, stride, a, stream); }
     //                                   CIN COUT S  TH TWT PADIN
-    if (cin == 5 && cout == 16 && stride == 2 && enc1_supported(a) && !sw_present<SW_EEM_NO_ENC1>()) return enc1_launch(a, stream);
-    if (cin == 5 && cout == 16 && stride == 2) return launch<5, 16, 2, 8, 4, true>(a, stream);
-    if (cin == 16 && cout == 16 && stride == 1) return launch<16, 16, 1, 8, 4, false>(a, stream);
-    if (cin == 16 && cout == 32 && stride == 2) return launch<16, 32, 2, 4, 1, false>(a, stream);
-    if (cin == 32 && cout == 32 && stride == 1) return launch<32, 32, 1, 4, 2, false>(a, stream);
-    if (cin == 32 && cout == 64 && stride == 2) return launch<32, 64, 2, 4, 1, false>(a, stream);
-    if (cin == 64 && cout == 64 && stride == 1) return launch<64, 64, 1, 4, 1, false>(a, stream);
+    if (cin == 5 && cout == 16 && stride == 2 && enc1_supported(a) && !sw_present<SW_EEM_NO_ENC1>()) { eem_launch_form = "enc1"; return enc1_launch(a, stream); }
+    if (cin == 5 && cout == 16 && stride == 2) { eem_launch_form = "enc_c5_16_s2"; return launch<5, 16, 2, 8, 4, true>(a, stream); }
+    if (cin == 16 && cout == 16 && stride == 1) { eem_launch_form = "enc_c16_16_s1"; return launch<16, 16, 1, 8, 4, false>(a, stream); }
+    if (cin == 16 && cout == 32 && stride == 2) { eem_launch_form = "enc_c16_32_s2"; return launch<16, 32, 2, 4, 1, false>(a, stream); }
+    if (cin == 32 && cout == 32 && stride == 1) { eem_launch_form = "enc_c32_32_s1"; return launch<32, 32, 1, 4, 2, false>(a, stream); }
+    if (cin == 32 && cout == 64 && stride == 2) { eem_launch_form = "enc_c32_64_s2"; return launch<32, 64, 2, 4, 1, false>(a, stream); }
+    if (cin == 64 && cout == 64 && stride == 1) { eem_launch_form = "enc_c64_64_s1"; return launch<64, 64, 1, 4, 1, false>(a, stream); }
     eem_set_error("enc_conv_launch: unsupported layer cin=%d cout=%d stride=%d", cin, cout, stride);
     return EEM_ERR_ARG;
 }

@@ -495,15 +495,19 @@ __host__ __device__ static inline void wnc_pack_quad(const float* w, int cout, i
     const int ci = (k == nch - 1 && cin % 32 ? cin - 32 : 32 * k) + l;            // (wnc_chunks' offsets)
     if (co >= cout || (k == nch - 1 && l < rep)) { o[0] = o[1] = o[2] = o[3] = 0.f; return; }
     const float* g = w + ((size_t)co * cin + ci) * 9;
-    float m[3];                                              // row xi of G g
+    // G g G^T in double, rounded to fp32 ONCE: the stored weights are a fixed perturbation of the layer's kernel, the same at every
+    // pixel, and in fp32 each of the transform's sums added a rounding of its own (up to four per weight) - a layer of few output
+    // channels whose sums cancel then showed it as a scale error of 0.7 .. 1.7 u (tests/test_gpu_plus_stage_fp64.py).  A one-off cost
+    // of the pack; sums of three floats and halvings are the same numbers on the host and on the device.
+    double m[3];                                             // row xi of G g
     for (int kx = 0; kx < 3; ++kx) {
-        const float g0 = g[kx], g1 = g[3 + kx], g2 = g[6 + kx];
-        m[kx] = xi == 0 ? g0 : (xi == 1 ? 0.5f * (g0 + g1 + g2) : (xi == 2 ? 0.5f * (g0 - g1 + g2) : g2));
+        const double g0 = g[kx], g1 = g[3 + kx], g2 = g[6 + kx];
+        m[kx] = xi == 0 ? g0 : (xi == 1 ? 0.5 * (g0 + g1 + g2) : (xi == 2 ? 0.5 * (g0 - g1 + g2) : g2));
     }
-    o[0] = m[0];
-    o[1] = 0.5f * (m[0] + m[1] + m[2]);
-    o[2] = 0.5f * (m[0] - m[1] + m[2]);
-    o[3] = m[2];
+    o[0] = (float)m[0];
+    o[1] = (float)(0.5 * (m[0] + m[1] + m[2]));
+    o[2] = (float)(0.5 * (m[0] - m[1] + m[2]));
+    o[3] = (float)m[2];
 }
 
 void wnc_pack(const float* w, int cout, int cin, int co0, int m16, float* packed) {
@@ -561,6 +565,7 @@ int wnc_launch(const WncArgs& a, hipStream_t st) {
         if (per_xcd > 64) per_xcd = 64;                      // two resident blocks per CU
         if (a.m16) hipLaunchKernelGGL((wnc_kernel<C, true>), dim3(per_xcd * 8), dim3(C::WAVES * 64), 0, st, a);
         else hipLaunchKernelGGL((wnc_kernel<C, false>), dim3(per_xcd * 8), dim3(C::WAVES * 64), 0, st, a);
+        eem_launch_form = a.m16 ? "wnc32_m16" : "wnc32";             // the block tile's width in pixels
     } else {
         using C = WncCfg<2, 1>;
         const int T = ceil_div(a.w, C::TW) * ceil_div(a.h, C::TH) * a.njobs * a.n;
@@ -568,6 +573,7 @@ int wnc_launch(const WncArgs& a, hipStream_t st) {
         if (per_xcd > 32) per_xcd = 32;                      // one resident block per CU
         if (a.m16) hipLaunchKernelGGL((wnc_kernel<C, true>), dim3(per_xcd * 8), dim3(C::WAVES * 64), 0, st, a);
         else hipLaunchKernelGGL((wnc_kernel<C, false>), dim3(per_xcd * 8), dim3(C::WAVES * 64), 0, st, a);
+        eem_launch_form = a.m16 ? "wnc64_m16" : "wnc64";
     }
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

@@ -256,6 +256,8 @@ __global__ __launch_bounds__(SPLITK ? SPLITK * 64 : 256) void gconv_kernel(GConv
 }  // namespace
 
 thread_local const char* eem_conv_form = "";
+thread_local const char* eem_launch_form = "";
+thread_local int eem_launch_jobs = 0;
 
 size_t gconv_packed_floats(int cout, const int* cs, int nseg, int kh, int kw) {
     int cps = 0;

@@ -40,6 +40,12 @@ constexpr int kDW = 96, kDIn = 87, kDense = 184;
 // whatever a coarser level left there (finite activations; the buffer is zeroed when allocated), times zero.
 constexpr int kCat = 96;
 
+struct PlusStageRec {            // one recorded launch output: [dims] floats at rec_buf + off
+    std::string name, form;
+    int dims[4];
+    size_t off;
+};
+
 }  // namespace
 
 struct eemplus_ctx {
@@ -78,6 +84,15 @@ struct eemplus_ctx {
     bool carry_on = false;
     int carry_slot = 0, carry_h = 0, carry_w = 0, carry_pad[4] = {0, 0, 0, 0}, carry_cin = 0;
     unsigned long carry_wver = 0;
+    // eemplus_record_stages (the fp64 stage tests): a device copy of every launch's output whose name starts with one of `rec_prefix`,
+    // made behind the launch on the launch's own stream and filed with the kernel form that wrote it.  rec_live: this call records
+    // (the recorder is on and the call is not eemplus_forward_stream); every call site tests it first and does nothing else when off.
+    bool rec_on = false, rec_live = false;
+    std::vector<std::string> rec_prefix;
+    std::vector<PlusStageRec> rec;
+    DevBuf rec_buf;
+    size_t rec_used = 0, rec_need = 0;
+    const char* form = "";               // the form of the launch conv() made last (whichever launch function it went to)
 };
 
 namespace {
@@ -176,11 +191,46 @@ bool conv_wnc_args(eemplus_ctx* c, const PLayer& L, const float* in, int in_ctot
     return wnc_supported(a);
 }
 
+// The stage recorder (eemplus_ctx::rec_live): `src` is [n][src_ctotal][h * w], of which the channels [src_coff, src_coff + ch) are copied
+// on `st`, the stream of the launch that has just written them.  It launches no kernel; with the recorder off no call site gets here.
+int rec_stage(eemplus_ctx* c, const char* name, const char* form, const float* src, int n, int ch, int h, int w, hipStream_t st,
+              int src_ctotal = 0, int src_coff = 0) {
+    bool wanted = false;
+    for (const std::string& p : c->rec_prefix) wanted = wanted || strncmp(name, p.c_str(), p.size()) == 0;
+    if (!wanted) return EEM_OK;
+    const size_t hw = (size_t)h * w, cnt = (size_t)n * ch * hw, off = c->rec_used;
+    c->rec_used += (cnt + 63) & ~(size_t)63;
+    if (c->rec_used > c->rec_buf.cap) return EEM_OK;                     // measured only: the forward runs again with the arena grown
+    float* dst = c->rec_buf.p + off;
+    if (src_ctotal == 0 || src_ctotal == ch)
+        EEM_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * 4, hipMemcpyDeviceToDevice, st));
+    else
+        EEM_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)ch * hw * 4, src + (size_t)src_coff * hw, (size_t)src_ctotal * hw * 4, (size_t)ch * hw * 4, n,
+                                       hipMemcpyDeviceToDevice, st));
+    std::string f(form ? form : "");
+    if (f.compare(0, 5, "tail_") == 0) f += "_j" + std::to_string(eem_launch_jobs);      // (the tail launch just made: its job count)
+    c->rec.push_back(PlusStageRec{name, f, {n, ch, h, w}, off});
+    return EEM_OK;
+}
+// a level's stage: "l<level>.<what>"
+int rec_level(eemplus_ctx* c, int l, const char* what, const char* form, const float* src, int n, int ch, int h, int w, hipStream_t st,
+              int src_ctotal = 0, int src_coff = 0) {
+    char name[48];
+    snprintf(name, sizeof(name), "l%d.%s", l, what);
+    return rec_stage(c, name, form, src, n, ch, h, w, st, src_ctotal, src_coff);
+}
+#define PREC(...) do { if (c->rec_live && (rc = rec_stage(c, __VA_ARGS__)) != EEM_OK) return rc; } while (0)
+#define PRECL(...) do { if (c->rec_live && (rc = rec_level(c, __VA_ARGS__)) != EEM_OK) return rc; } while (0)
+
 int conv(eemplus_ctx* c, const PLayer& L, const float* in, int in_ctotal, int in_coff, int n, int hin, int win, float* out,
          int out_ctotal, int out_coff, int out_cmul, int act, const float* add, hipStream_t st, int policy_jobs = 0) {
     if (add == nullptr) {
         WncArgs wa;
-        if (conv_wnc_args(c, L, in, in_ctotal, in_coff, n, hin, win, out, out_ctotal, out_coff, out_cmul, act, wa, policy_jobs)) return wnc_launch(wa, st);
+        if (conv_wnc_args(c, L, in, in_ctotal, in_coff, n, hin, win, out, out_ctotal, out_coff, out_cmul, act, wa, policy_jobs)) {
+            const int rcw = wnc_launch(wa, st);
+            c->form = eem_launch_form;
+            return rcw;
+        }
     }
     // small maps (the coarse pyramid levels): the small-grid kernel of EEMFlow's tail
     const bool add_ok = add == nullptr || (out_ctotal == L.cout && out_coff == 0 && out_cmul <= 1);   // residual indexed like the output
@@ -193,7 +243,9 @@ int conv(eemplus_ctx* c, const PLayer& L, const float* in, int in_ctotal, int in
         j.out_ctotal = out_ctotal; j.out_coff = out_coff; j.out_cmul = out_cmul > 1 ? out_cmul : 1; j.act = act == GACT_LEAKY;
         j.gate = nullptr; j.in_cmul = 1;
         j.add = add;                                               // GEPI_ADD: residual with the output's shape (out_coff 0)
-        return tail_conv_launch(T, st);
+        const int rct = tail_conv_launch(T, st);
+        c->form = eem_launch_form;
+        return rct;
     }
     GConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -211,7 +263,9 @@ int conv(eemplus_ctx* c, const PLayer& L, const float* in, int in_ctotal, int in
     a.act = act; a.out_scale = 1.f;
     a.in_flight = c->frames_in_flight;
     if (add) { a.epi = GEPI_ADD; a.e0 = add; a.e0_ctotal = L.cout; a.e0_coff = 0; }
-    return gconv_launch(a, st);
+    const int rcg = gconv_launch(a, st);
+    c->form = eem_conv_form;
+    return rcg;
 }
 
 // Decoder (EEMFlow+.py:38-71): cat [B][87] -> flow [B][2] (+ residual)
@@ -225,6 +279,7 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
         (rc = devbuf_ensure(c->flow[l], B * 2 * g)) != EEM_OK)
         return rc;
     const int G = c->groups, per = kDW / G;
+    static const char* const kDecg[3] = {"decg0", "decg1", "decg2"};
     // coarse levels: every conv is a handful of 16x16 tiles - the small-grid kernel of EEMFlow's tail (one launch per layer,
     // the groups of a layer as jobs, K split over the waves of a block) instead of one generic-conv launch per group
     const bool small = (long)h * w <= kDecTailMaxCells && c->dec1[l].has_tail && c->decg[l][0][0].has_tail && c->dec5[l].has_tail &&
@@ -242,18 +297,23 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
         L.batch = B; L.h = h; L.w = w; L.ksize = 3;
         L.njobs = 1; L.job[0] = job(c->dec1[l], cat, kCat, 0, c->d[0].p, kDW, 0, 1);
         if ((rc = tail_conv_launch(L, st)) != EEM_OK) return rc;
+        PRECL(l, "dec1", eem_launch_form, c->d[0].p, B, kDW, h, w, st);
         for (int layer = 0; layer < 3; ++layer) {
             L.njobs = 0;
             for (int gi = 0; gi < G; ++gi)
                 L.job[L.njobs++] = job(c->decg[l][layer][gi], c->d[layer].p, kDW, gi * per, c->d[layer + 1].p, kDW, G == 1 ? 0 : gi, G == 1 ? 1 : G);
             if ((rc = tail_conv_launch(L, st)) != EEM_OK) return rc;
+            PRECL(l, kDecg[layer], eem_launch_form, c->d[layer + 1].p, B, kDW, h, w, st);
         }
         L.njobs = 1; L.job[0] = job(c->dec5[l], c->d[3].p, kDW, 0, c->t64.p, 64, 0, 1);
         if ((rc = tail_conv_launch(L, st)) != EEM_OK) return rc;
+        PRECL(l, "dec5", eem_launch_form, c->t64.p, B, 64, h, w, st);
         L.njobs = 1; L.job[0] = job(c->dec6[l], c->t64.p, 64, 0, c->t32.p, 32, 0, 1);
         if ((rc = tail_conv_launch(L, st)) != EEM_OK) return rc;
+        PRECL(l, "dec6", eem_launch_form, c->t32.p, B, 32, h, w, st);
     } else {
         if ((rc = conv(c, c->dec1[l], cat, kCat, 0, B, h, w, c->d[0].p, kDW, 0, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+        PRECL(l, "dec1", c->form, c->d[0].p, B, kDW, h, w, st);
         const bool no_grouped = sw_on<SW_EEM_PLUS_NO_GROUPED>();
         for (int layer = 0; layer < 3; ++layer) {
             // the G groups of a layer as ONE launch of the LDS-tiled kernel when their packings lie at equal distances in the arena
@@ -271,6 +331,7 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
                 }
                 if (per == 32 && wnc_supported(wa)) {
                     if ((rc = wnc_launch(wa, st)) != EEM_OK) return rc;
+                    PRECL(l, kDecg[layer], eem_launch_form, c->d[layer + 1].p, B, kDW, h, w, st);
                     continue;
                 }
             }
@@ -296,6 +357,7 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
                     a.groups = G; a.g_wstride16 = (long)(L1.wpk16 - L0.wpk16); a.g_pstride = (long)(L1.bias - L0.bias); a.g_ocoff = 1;
                     if (gconv16_supported(a)) {
                         if ((rc = gconv_launch(a, st)) != EEM_OK) return rc;
+                        PRECL(l, kDecg[layer], eem_conv_form, c->d[layer + 1].p, B, kDW, h, w, st);
                         continue;
                     }
                 }
@@ -306,11 +368,17 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
                 if ((rc = conv(c, c->decg[l][layer][gi], c->d[layer].p, kDW, gi * per, B, h, w, c->d[layer + 1].p, kDW, oc, om, GACT_LEAKY,
                                nullptr, st, G)) != EEM_OK) return rc;
             }
+            // (one launch per group, every group on the same form: the layer's output is filed once, behind the last of them)
+            PRECL(l, kDecg[layer], c->form, c->d[layer + 1].p, B, kDW, h, w, st);
         }
         if ((rc = conv(c, c->dec5[l], c->d[3].p, kDW, 0, B, h, w, c->t64.p, 64, 0, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+        PRECL(l, "dec5", c->form, c->t64.p, B, 64, h, w, st);
         if ((rc = conv(c, c->dec6[l], c->t64.p, 64, 0, B, h, w, c->t32.p, 32, 0, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+        PRECL(l, "dec6", c->form, c->t32.p, B, 32, h, w, st);
     }
-    return conv(c, c->dec7[l], c->t32.p, 32, 0, B, h, w, c->flow[l].p, 2, 0, 1, GACT_NONE, residual, st);
+    if ((rc = conv(c, c->dec7[l], c->t32.p, 32, 0, B, h, w, c->flow[l].p, 2, 0, 1, GACT_NONE, residual, st)) != EEM_OK) return rc;
+    PRECL(l, "flow", c->form, c->flow[l].p, B, 2, h, w, st);
+    return EEM_OK;
 }
 
 }  // namespace
@@ -356,6 +424,7 @@ extern "C" void eemplus_destroy(eemplus_ctx* c) {
         if (c->flow[l].p) (void)hipFree(c->flow[l].p);
         if (c->flow_alt[l].p) (void)hipFree(c->flow_alt[l].p);
     }
+    if (c->rec_buf.p) (void)hipFree(c->rec_buf.p);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wino) (void)hipFree(c->wino);
     if (c->taps) (void)hipFree(c->taps);
@@ -479,13 +548,19 @@ static int level_units(eemplus_ctx* c, int l, int B, hipStream_t st, bool skip_r
                 j.gate = nullptr; j.in_cmul = 1; j.add = nullptr;
             }
             if ((rc = tail_conv_launch(T, st)) != EEM_OK) return rc;
+            PRECL(l, "a1", eem_launch_form, c->dense_l[l].p, B, 32, h, w, st, kDense, 120);       // (two jobs, two buffers: two stages of one form)
+            PRECL(l, "a2", eem_launch_form, c->a2_l[l].p, B, 32, h, w, st);
         } else {
             if ((rc = conv(c, P, f1, C[l], 0, B, h, w, c->dense_l[l].p, kDense, 120, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+            PRECL(l, "a1", c->form, c->dense_l[l].p, B, 32, h, w, st, kDense, 120);
             if ((rc = conv(c, P, f2, C[l], 0, B, h, w, c->a2_l[l].p, 32, 0, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+            PRECL(l, "a2", c->form, c->a2_l[l].p, B, 32, h, w, st);
         }
     }
     if (skip_rconv) return EEM_OK;                                 // (run_level: rconv rides the mask estimator's first launch)
-    return conv(c, c->rconv[l], f1, C[l], 0, B, h, w, c->cat_l[l].p, kCat, 53, 1, GACT_LEAKY, nullptr, st);
+    if ((rc = conv(c, c->rconv[l], f1, C[l], 0, B, h, w, c->cat_l[l].p, kCat, 53, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+    PRECL(l, "rconv", c->form, c->cat_l[l].p, B, 32, h, w, st, kCat, 53);
+    return EEM_OK;
 }
 
 // One level l = 5..2 of the coarse-to-fine loop (EEMFlow+.py:183-229) on the features of the current forward: cdc_model
@@ -518,6 +593,7 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
     if (forced_init) {
         // teacher-forced level (eemplus_level): cdc_model's upsampled flow_init is supplied by the caller
         EEM_HIP_CHECK(hipMemcpyAsync(fi, forced_init, B * 2 * g * 4, hipMemcpyDeviceToDevice, st));
+        PRECL(l, "flow_init", "", fi, B, 2, h, w, st);
     }
     // warp + blend + the copy of flow_up into the decoder's input as one launch (EEM_PLUS_NO_FUSE=1: the separate launches)
     const bool fuse3 = plus_fuse();
@@ -527,18 +603,26 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
         if ((rc = devbuf_ensure(c->flow_alt[l + 1], B * 2 * (size_t)hc * wc)) != EEM_OK) return rc;
         if ((rc = pl_upflow_warp_launch(c->flow[l + 1].p, c->flow_alt[l + 1].p, hc, wc, fi, a2, dense, kDense, 152, B, 32, h, w, st)) != EEM_OK) return rc;
         std::swap(c->flow[l + 1], c->flow_alt[l + 1]);
+        PRECL(l, "flow_init", eem_launch_form, fi, B, 2, h, w, st);
+        PRECL(l, "coarse_scaled", eem_launch_form, c->flow[l + 1].p, B, 2, hc, wc, st);
+        PRECL(l, "warp_a2", eem_launch_form, dense, B, 32, h, w, st, kDense, 152);
     } else {
         if (forced_init) {
         } else if (hc != h || wc != w) {
             if ((rc = pl_upflow_launch(c->flow[l + 1].p, fi, B, hc, wc, h, w, 1, st)) != EEM_OK) return rc;
+            PRECL(l, "flow_init", eem_launch_form, fi, B, 2, h, w, st);
             // in-place side effect of upsample2d_flow_as(if_rate=True) on the coarser flow (cdc_utils.py:85-86)
             if ((rc = pl_scale_flow_launch(c->flow[l + 1].p, B, hc * wc, (float)w / (float)wc, (float)h / (float)hc, st)) != EEM_OK) return rc;
+            PRECL(l, "coarse_scaled", eem_launch_form, c->flow[l + 1].p, B, 2, hc, wc, st);
         } else {
             EEM_HIP_CHECK(hipMemcpyAsync(fi, c->flow[l + 1].p, B * 2 * g * 4, hipMemcpyDeviceToDevice, st));
+            PRECL(l, "flow_init", "", fi, B, 2, h, w, st);
         }
         if ((rc = pl_warp_launch(a2, fi, 2, dense, kDense, 152, B, 32, h, w, 2, st)) != EEM_OK) return rc;
+        PRECL(l, "warp_a2", eem_launch_form, dense, B, 32, h, w, st, kDense, 152);
     }
     const int din[6] = {64, 96, 128, 160, 176, 184}, dout_off[5] = {88, 56, 24, 8, 0};
+    static const char* const kDe[5] = {"de0", "de1", "de2", "de3", "de4"};
     for (int i = 0; i < 5; ++i) {
         if (i == 0 && rconv_rides) {
             TailConvLaunch T;
@@ -553,23 +637,37 @@ static int run_level(eemplus_ctx* c, int l, int B, const float* forced_init, hip
                 j.gate = nullptr; j.in_cmul = 1; j.add = nullptr;
             }
             if ((rc = tail_conv_launch(T, st)) != EEM_OK) return rc;
+            PRECL(l, "de0", eem_launch_form, dense, B, 32, h, w, st, kDense, dout_off[0]);        // (two jobs, two buffers: two stages of one form)
+            PRECL(l, "rconv", eem_launch_form, cat, B, 32, h, w, st, kCat, 53);
             continue;
         }
         if ((rc = conv(c, c->de[i], dense, kDense, kDense - din[i], B, h, w, dense, kDense, dout_off[i], 1, GACT_LEAKY, nullptr, st)) != EEM_OK) return rc;
+        PRECL(l, kDe[i], c->form, dense, B, c->de[i].cout, h, w, st, kDense, dout_off[i]);
     }
     if ((rc = conv(c, c->de[5], dense, kDense, 0, B, h, w, c->xout.p, 3, 0, 1, GACT_NONE, nullptr, st)) != EEM_OK) return rc;
+    PRECL(l, "xout", c->form, c->xout.p, B, 3, h, w, st);
     if (fuse3) {
         // ... and the warp of feature_2 by that flow_up (:189) in the same launch
         if ((rc = pl_warp_blend_warp_launch(fi, c->xout.p, c->fup[l].p, cat, kCat, 85, f2(l), c->fw.p, C[l], B, h, w, st)) != EEM_OK) return rc;
+        PRECL(l, "flow_up", eem_launch_form, c->fup[l].p, B, 2, h, w, st);
+        PRECL(l, "cat_flow", eem_launch_form, cat, B, 2, h, w, st, kCat, 85);
+        PRECL(l, "fw", eem_launch_form, c->fw.p, B, C[l], h, w, st);
     } else {
         if ((rc = pl_warp_launch(fi, c->xout.p, 3, c->tw.p, 2, 0, B, 2, h, w, 1, st)) != EEM_OK) return rc;
+        PRECL(l, "tw", eem_launch_form, c->tw.p, B, 2, h, w, st);
         if ((rc = pl_blend_launch(c->tw.p, fi, c->xout.p, c->fup[l].p, B, (int)g, st)) != EEM_OK) return rc;
+        PRECL(l, "flow_up", eem_launch_form, c->fup[l].p, B, 2, h, w, st);
         // warp, correlate, decode (:189-193)
         if ((rc = pl_warp_launch(f2(l), c->fup[l].p, 2, c->fw.p, C[l], 0, B, C[l], h, w, 0, st)) != EEM_OK) return rc;
+        PRECL(l, "fw", eem_launch_form, c->fw.p, B, C[l], h, w, st);
     }
     CorrJob cj = {f1(l), c->fw.p, cat, C[l], kCat};
     if ((rc = corr_launch(&cj, 1, B, h, w, c->taps, 53, st)) != EEM_OK) return rc;
-    if (!fuse3 && (rc = pl_copy_channels_launch(c->fup[l].p, 2, 0, cat, kCat, 85, 2, B, (int)g, st)) != EEM_OK) return rc;
+    PRECL(l, "corr", eem_launch_form, cat, B, 53, h, w, st, kCat, 0);
+    if (!fuse3) {
+        if ((rc = pl_copy_channels_launch(c->fup[l].p, 2, 0, cat, kCat, 85, 2, B, (int)g, st)) != EEM_OK) return rc;
+        PRECL(l, "cat_flow", eem_launch_form, cat, B, 2, h, w, st, kCat, 85);
+    }
     if ((rc = run_decoder(c, l, B, h, w, c->fup[l].p, st)) != EEM_OK) return rc;
     return EEM_OK;
 }
@@ -631,6 +729,11 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
                              const PlusStream* sp = nullptr) {
     const int B = batch, n2 = sp ? sp->nvol : 2 * batch, hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
     int rc;
+    // the stage recorder: the arena the forward before measured (a forward whose records do not fit is run again by the caller)
+    c->rec_live = c->rec_on && !sp;
+    c->rec.clear();
+    c->rec_used = 0;
+    if (c->rec_live && (rc = devbuf_ensure(c->rec_buf, c->rec_need)) != EEM_OK) return rc;
     // ---- pad, encoder on both volumes (EEMFlow+.py:162-169); the stream: on its new windows (n2 = nvol images)
     if ((rc = devbuf_ensure(c->padded, (size_t)n2 * c->cin0 * hp * wp)) != EEM_OK) return rc;
     if (sp) {
@@ -646,6 +749,8 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
             if ((rc = er_pad_launch(e2v[i], c->padded.p + (size_t)(B + i) * img, c->cin0, in_h, in_w, pad[0], pad[1], pad[2], pad[3], st)) != EEM_OK) return rc;
         }
     }
+    PREC("pad", er_last_form, c->padded.p, n2, c->cin0, hp, wp, st);
+    static const char* const kPool[3] = {"pool4", "pool5", "pool6"};
     auto half = [](int v) { return (v - 1) / 2 + 1; };
     int* hl = c->hl; int* wl = c->wl;
     hl[1] = half(hp); wl[1] = half(wp); hl[2] = half(hl[1]); wl[2] = half(wl[1]); hl[3] = half(hl[2]); wl[3] = half(wl[2]);
@@ -669,6 +774,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
         if ((rc = devbuf_ensure(c->dense, big)) != EEM_OK || (rc = devbuf_ensure(c->fw, big)) != EEM_OK) return rc;
         float* t0 = c->dense.p; float* t1 = c->fw.p;
         struct EStep { const float* in; float* out; int hin, win, hout, wout; };
+        static const char* const kEnc[8] = {"enc0", "enc1", "enc2", "enc3", "enc4", "enc5", "enc6", "enc7"};
         const EStep es[8] = {{c->padded.p, t0, hp, wp, hl[1], wl[1]},     {t0, c->f[1].p, hl[1], wl[1], hl[1], wl[1]},
                              {c->f[1].p, t0, hl[1], wl[1], hl[2], wl[2]}, {t0, t1, hl[2], wl[2], hl[2], wl[2]},
                              {t1, fo[2], hl[2], wl[2], hl[2], wl[2]},     {fo[2], t0, hl[2], wl[2], hl[3], wl[3]},
@@ -691,13 +797,17 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
                 a.hraw = es[i].hin; a.wraw = es[i].win;
                 a.act = 1;
                 if ((rc = enc_conv_launch(L.cin, L.cout, L.stride, a, st)) != EEM_OK) return rc;
+                c->form = eem_launch_form;
             } else if ((rc = conv(c, L, es[i].in, L.cin, 0, n2, es[i].hin, es[i].win, es[i].out, L.cout, 0, 1, GACT_LEAKY, nullptr, st)) != EEM_OK) {
                 return rc;
             }
+            // (the two scratch buffers are written again two layers on: the copy is what the next layer's reference reads)
+            PREC(kEnc[i], c->form, es[i].out, n2, L.cout, es[i].hout, es[i].wout, st);
         }
     }
     // avg_pool2d(2,2) x3 (:170-175), one launch
     if ((rc = er_pool2x3_launch(fo[3], fo[4], fo[5], fo[6], (long)n2 * 64, hl[3], wl[3], st)) != EEM_OK) return rc;
+    for (int l = 4; l <= 6; ++l) PREC(kPool[l - 4], er_last_form, fo[l], n2, 64, hl[l], wl[l], st);
 
     for (int l = 2; l <= 6; ++l) c->fb[l] = sp ? c->sf[l].p : c->f[l].p;
     c->f2off = sp ? 1 : B;
@@ -734,6 +844,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
         float* const cat = c->cat_l[6].p;
         CorrJob cj = {f1(6), f2(6), cat, 64, kCat};
         if ((rc = corr_launch(&cj, 1, B, h, w, c->taps, 53, st)) != EEM_OK) return rc;
+        PRECL(6, "corr", eem_launch_form, cat, B, 53, h, w, st, kCat, 0);
         // level 6 has no coarser flow: its two flow channels of the decoder input are zeros (:179).  Nothing writes them at this level, so
         // the fill is launched once per (batch, map size) - the buffer's layout - and not per forward (a re-allocated buffer comes zeroed)
         const size_t key = ((size_t)B << 40) | g;
@@ -741,6 +852,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
             if ((rc = pl_copy_channels_launch(nullptr, 0, 0, cat, kCat, 85, 2, B, (int)g, st)) != EEM_OK) return rc;
             c->cat6_key = key;
         }
+        PRECL(6, "cat_flow", "", cat, B, 2, h, w, st, kCat, 85);    // (whatever forward filled them: they must hold zeros in this one)
         if (side) EEM_HIP_CHECK(hipStreamWaitEvent(st, c->ev_lvl[6], 0));
         else if ((rc = level_units(c, 6, B, st)) != EEM_OK) return rc;
         if ((rc = run_decoder(c, 6, B, h, w, nullptr, st)) != EEM_OK) return rc;
@@ -759,7 +871,14 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
             hs[i] = hl[l]; ws[i] = wl[l];
         }
         if ((rc = pl_upflow_multi_launch(ins, outs, hs, ws, 5, frames ? 1 : B, in_h, in_w, 1, st)) != EEM_OK) return rc;
+        if (c->rec_live) {                                       // "pred" [5 * B][2][H][W]; forward_many: "pred<sample>" [5][2][H][W]
+            char name[24];
+            if (frames) snprintf(name, sizeof(name), "pred%d", f);
+            else snprintf(name, sizeof(name), "pred");
+            if ((rc = rec_stage(c, name, eem_launch_form, outs[0], 5 * (frames ? 1 : B), 2, in_h, in_w, st)) != EEM_OK) return rc;
+        }
     }
+    if (c->rec_live) c->rec_need = c->rec_need > c->rec_used ? c->rec_need : c->rec_used;
     c->B = B; c->have_last = true;
     return EEM_OK;
 }
@@ -770,7 +889,11 @@ extern "C" int eemplus_forward(eemplus_ctx* c, const float* e1, const float* e2,
     EEM_REQUIRE(c->loaded, "eemplus_forward: no weights loaded");
     EEM_REQUIRE(batch >= 1 && in_h >= 1 && in_w >= 1, "eemplus_forward: bad sizes");
     EEM_HIP_CHECK(hipSetDevice(c->device));
-    return plus_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, out, nullptr, (hipStream_t)stream);
+    int rc = plus_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, out, nullptr, (hipStream_t)stream);
+    // the stage recorder's arena was too small: that forward measured it; the same forward again, with the arena grown, fills it
+    if (rc == EEM_OK && c->rec_on && c->rec_used > c->rec_buf.cap)
+        rc = plus_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, out, nullptr, (hipStream_t)stream);
+    return rc;
 }
 
 // n independent samples of the evaluation loop (test_mvsec.py:580-597: one model(events1, events2) per sample at batch 1), each in its
@@ -783,7 +906,10 @@ extern "C" int eemplus_forward_many(eemplus_ctx* c, int n, const float* const* e
     EEM_REQUIRE(n >= 1 && n <= 16 && in_h >= 1 && in_w >= 1, "eemplus_forward_many: n = %d (1..16) samples of %dx%d", n, in_h, in_w);
     for (int i = 0; i < n; ++i) EEM_REQUIRE(events1[i] && events2[i] && flow_out[i], "eemplus_forward_many: NULL pointer for sample %d", i);
     EEM_HIP_CHECK(hipSetDevice(c->device));
-    return plus_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream);
+    int rc = plus_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream);
+    if (rc == EEM_OK && c->rec_on && c->rec_used > c->rec_buf.cap)            // (the recorder's arena has grown: see eemplus_forward)
+        rc = plus_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream);
+    return rc;
 }
 
 // Consecutive windows, each through the encoder once (include/eemflow_hip.h): one batch-nflow chain as eemplus_forward_many, the pairs'
@@ -842,6 +968,48 @@ extern "C" int eemplus_set_frames_in_flight(eemplus_ctx* c, int n) {
     return EEM_OK;
 }
 
+// The stage recorder (include/eemflow_hip.h): prefixes = comma-separated name prefixes, NULL = off.
+extern "C" int eemplus_record_stages(eemplus_ctx* c, const char* prefixes) {
+    EEM_REQUIRE(c, "eemplus_record_stages: NULL context");
+    c->rec_prefix.clear();
+    c->rec_on = prefixes != nullptr;
+    if (!c->rec_on) { c->rec_live = false; c->rec.clear(); }
+    if (prefixes) {
+        const std::string all(prefixes);
+        size_t i = 0;
+        while (i <= all.size()) {
+            size_t j = all.find(',', i);
+            if (j == std::string::npos) j = all.size();
+            c->rec_prefix.push_back(all.substr(i, j - i));                   // (an empty prefix matches every name)
+            i = j + 1;
+        }
+    }
+    return EEM_OK;
+}
+
+extern "C" int eemplus_stage_list(eemplus_ctx* c, char* buf, size_t cap, size_t* need) {
+    EEM_REQUIRE(c && need, "eemplus_stage_list: NULL argument");
+    std::string s;
+    for (const PlusStageRec& r : c->rec) {
+        char line[160];
+        snprintf(line, sizeof(line), "%s %s %d %d %d %d\n", r.name.c_str(), r.form.empty() ? "-" : r.form.c_str(), r.dims[0], r.dims[1], r.dims[2], r.dims[3]);
+        s += line;
+    }
+    *need = s.size() + 1;
+    if (buf == nullptr) return EEM_OK;
+    EEM_REQUIRE(cap >= s.size() + 1, "eemplus_stage_list: the list needs %zu bytes, the buffer holds %zu", s.size() + 1, cap);
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return EEM_OK;
+}
+
+// The form of this thread's last launch through the launch functions that report in eem_launch_form (eemplus_warp, eemplus_upsample_flow_as).
+extern "C" int eemplus_last_form(char* buf, int cap) {
+    EEM_REQUIRE(buf && cap > 0, "eemplus_last_form: NULL buffer");
+    if (strncmp(eem_launch_form, "tail_", 5) == 0) snprintf(buf, (size_t)cap, "%s_j%d", eem_launch_form, eem_launch_jobs);
+    else snprintf(buf, (size_t)cap, "%s", eem_launch_form);
+    return EEM_OK;
+}
+
 extern "C" int eemplus_get_stage(eemplus_ctx* c, const char* name, float* dst, size_t cap, int dims[4], void* stream) {
     EEM_REQUIRE(c && name && dims, "eemplus_get_stage: NULL argument");
     EEM_REQUIRE(c->have_last, "eemplus_get_stage: no forward has run");
@@ -857,8 +1025,15 @@ extern "C" int eemplus_get_stage(eemplus_ctx* c, const char* name, float* dst, s
         const int l = nm[9] - '0';
         src = c->finit[l].p; dims[0] = c->B; dims[1] = 2; dims[2] = c->hl[l]; dims[3] = c->wl[l];
     } else {
-        eem_set_error("eemplus_get_stage: unknown stage '%s'", name);
-        return EEM_ERR_ARG;
+        const PlusStageRec* hit = nullptr;                                   // a name of the stage recorder (eemplus_record_stages)
+        for (const PlusStageRec& r : c->rec)
+            if (r.name == nm) { hit = &r; break; }
+        if (!hit) {
+            eem_set_error("eemplus_get_stage: unknown stage '%s'", name);
+            return EEM_ERR_ARG;
+        }
+        src = c->rec_buf.p + hit->off;
+        for (int i = 0; i < 4; ++i) dims[i] = hit->dims[i];
     }
     const size_t n = (size_t)dims[0] * dims[1] * dims[2] * dims[3];
     if (dst == nullptr) return EEM_OK;
@@ -876,8 +1051,13 @@ extern "C" int eemplus_level(eemplus_ctx* c, int level, const float* flow_init, 
     EEM_REQUIRE(level >= 2 && level <= 5, "eemplus_level: level %d (2..5)", level);
     EEM_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    int rc = run_level(c, level, c->B, flow_init, st, false);
-    if (rc != EEM_OK) return rc;
+    int rc;
+    // the stage recorder: this level's launches alone, "l<level>." (a level files fewer than 1024 channels of its map)
+    c->rec_live = c->rec_on;
+    c->rec.clear();
+    c->rec_used = 0;
+    if (c->rec_live && (rc = devbuf_ensure(c->rec_buf, (size_t)c->B * 1024 * c->hl[level] * c->wl[level] + 64 * 64)) != EEM_OK) return rc;
+    if ((rc = run_level(c, level, c->B, flow_init, st, false)) != EEM_OK) return rc;
     const size_t n = (size_t)c->B * 2 * c->hl[level] * c->wl[level] * sizeof(float);
     if (flow_up_out) EEM_HIP_CHECK(hipMemcpyAsync(flow_up_out, c->fup[level].p, n, hipMemcpyDeviceToDevice, st));
     if (flow_out) EEM_HIP_CHECK(hipMemcpyAsync(flow_out, c->flow[level].p, n, hipMemcpyDeviceToDevice, st));

@@ -235,12 +235,14 @@ int pl_warp_launch(const float* x, const float* flow, int flow_ctotal, float* ou
                    int w, int mode, hipStream_t st) {
     hipLaunchKernelGGL(warp_kernel, dim3(nblocks((long)batch * h * w), (c + kWarpCh - 1) / kWarpCh), dim3(256), 0, st, x, flow, flow_ctotal, out, out_ctotal, out_coff,
                        batch, c, h, w, mode);
+    eem_launch_form = "warp";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int pl_upflow_launch(const float* in, float* out, int batch, int h, int w, int oh, int ow, int rate, hipStream_t st) {
     hipLaunchKernelGGL(upflow_kernel, dim3(nblocks((long)batch * 2 * oh * ow)), dim3(256), 0, st, in, out, batch, h, w, oh, ow, rate);
+    eem_launch_form = "upflow";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -259,18 +261,21 @@ int pl_upflow_multi_launch(const float* const* in, float* const* out, const int*
     UpflowJobs J;
     for (int i = 0; i < 5; ++i) { const int k = i < njobs ? i : 0; J.in[i] = in[k]; J.out[i] = out[k]; J.h[i] = h[k]; J.w[i] = w[k]; }
     hipLaunchKernelGGL(upflow_multi_kernel, dim3(nblocks((long)batch * 2 * oh * (ow >> 2)), njobs), dim3(256), 0, st, J, batch, oh, ow, rate);
+    eem_launch_form = "upflow_multi";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int pl_scale_flow_launch(float* f, int batch, int hw, float su, float sv, hipStream_t st) {
     hipLaunchKernelGGL(scale_flow_kernel, dim3(nblocks((long)batch * 2 * hw)), dim3(256), 0, st, f, batch, hw, su, sv);
+    eem_launch_form = "scale_flow";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 int pl_blend_launch(const float* warped, const float* flow_init, const float* xout, float* out, int batch, int hw, hipStream_t st) {
     hipLaunchKernelGGL(blend_kernel, dim3(nblocks((long)batch * 2 * hw)), dim3(256), 0, st, warped, flow_init, xout, out, batch, hw);
+    eem_launch_form = "blend";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -279,6 +284,7 @@ int pl_warp_blend_launch(const float* flow_init, const float* xout, float* out, 
                          hipStream_t st) {
     hipLaunchKernelGGL(warp_blend_kernel, dim3(nblocks((long)batch * h * w)), dim3(256), 0, st, flow_init, xout, out, cat, cat_ctotal, cat_coff,
                        batch, h, w, (const float*)nullptr, (float*)nullptr, 0);
+    eem_launch_form = "warp_blend";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -287,6 +293,7 @@ int pl_warp_blend_warp_launch(const float* flow_init, const float* xout, float* 
                               float* fw, int c2, int batch, int h, int w, hipStream_t st) {
     hipLaunchKernelGGL(warp_blend_kernel, dim3(nblocks((long)batch * h * w), (c2 + kWarpCh - 1) / kWarpCh), dim3(256), 0, st, flow_init, xout, out,
                        cat, cat_ctotal, cat_coff, batch, h, w, f2, fw, c2);
+    eem_launch_form = "warp_blend_warp";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -295,6 +302,7 @@ int pl_upflow_warp_launch(const float* fc, float* fc_scaled, int hc, int wc, flo
                           int batch, int c, int h, int w, hipStream_t st) {
     hipLaunchKernelGGL(upflow_warp_kernel, dim3(nblocks((long)batch * h * w), (c + kWarpCh - 1) / kWarpCh), dim3(256), 0, st, fc, fc_scaled, hc, wc,
                        fi, x, out, out_ctotal, out_coff, batch, c, h, w);
+    eem_launch_form = "upflow_warp";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -303,6 +311,7 @@ int pl_copy_channels_launch(const float* src, int s_ctotal, int s_coff, float* d
                             hipStream_t st) {
     hipLaunchKernelGGL(copy_channels_kernel, dim3(nblocks((long)batch * c * hw)), dim3(256), 0, st, src, s_ctotal, s_coff, dst, d_ctotal,
                        d_coff, c, batch, hw);
+    eem_launch_form = "copy_channels";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }

@@ -151,13 +151,22 @@ __global__ __launch_bounds__(128) void corr_tiled53_kernel(CorrArgs a, int tiles
         if (ci + 1 < nch) fetch((ci + 1) * CK);
         const float* base = &tile[ci & 1][ly * PITCH + lx];
         const float* vb = &f1s[ci & 1][tid];
+        // A chunk's eight products go into a sum of their own, which then joins the running one: feature maps have a per-channel mean, so
+        // a tap's products mostly share a sign, and ONE chain over all 32 / 64 channels rounds a partial sum that grows steadily (rms(z)
+        // 1.50, max|z| 8.9 at 32 channels against the corr family's 1.1 / 7.6; corr_kernel above splits the channels four ways).
+        // Costs 3 % of an EEMFlow+ forward at 1280x720 (53 more registers); summing tap by tap into one register measured 5 %.
+        float q[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) q[t] = 0.f;
         // two channels per trip (fully unrolled, the scheduler hoists all 424 LDS reads of a chunk: 512 VGPRs and scratch)
 #pragma unroll 2
         for (int c = 0; c < CK; ++c) {
             const float v = vb[c * 128];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) s[t] = fmaf(v, base[c * PLANE + (kCorrTaps53[t] / 9) * PITCH + kCorrTaps53[t] % 9], s[t]);   // window origin = (-4, -4)
+            for (int t = 0; t < NT; ++t) q[t] = fmaf(v, base[c * PLANE + (kCorrTaps53[t] / 9) * PITCH + kCorrTaps53[t] % 9], q[t]);   // window origin = (-4, -4)
         }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) s[t] += q[t];
         if (ci + 1 < nch) stage((ci + 1) & 1);
         __syncthreads();
     }
@@ -456,10 +465,12 @@ int corr_launch(const CorrJob* jobs, int njobs, int batch, int h, int w, const i
         // ops.hip - and the tiled kernel has it compiled in)
         const int tiles_x = ceil_div(w, 16);
         hipLaunchKernelGGL(corr_tiled53_kernel, dim3(tiles_x * ceil_div(h, 8), 1, njobs * batch), dim3(128), 0, stream, a, tiles_x);
+        eem_launch_form = "corr_tiled53";
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }
     hipLaunchKernelGGL(corr_kernel, dim3((unsigned)((total * 4 + 255) / 256)), dim3(256), 0, stream, a);   // 4 lanes per output
+    eem_launch_form = "corr_direct";
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -491,6 +502,13 @@ static void tail_launch_t(const TailConvLaunch& l, dim3 grid, hipStream_t stream
     else hipLaunchKernelGGL((tail_conv_kernel<KS, MAXCG, false>), grid, dim3(64 * KS * KS), 0, stream, l);
 }
 
+// eem_launch_form of a tail_conv_launch: the instantiation (filter size, the most 4-channel groups it holds); the launch's job count
+// goes beside it in eem_launch_jobs - two stores per launch
+static inline void tail_form(const char* inst, int njobs) {
+    eem_launch_form = inst;
+    eem_launch_jobs = njobs;
+}
+
 int tail_conv_launch(const TailConvLaunch& l, hipStream_t stream) {
     EEM_REQUIRE(l.njobs >= 1 && l.njobs <= TAIL_MAX_JOBS, "tail_conv_launch: njobs=%d", l.njobs);
     EEM_REQUIRE(l.ksize == 3 || l.ksize == 1, "tail_conv_launch: ksize=%d", l.ksize);
@@ -508,6 +526,7 @@ int tail_conv_launch(const TailConvLaunch& l, hipStream_t stream) {
         dim3 gw(ceil_div(l.h * l.w, 16) * l.batch, ceil_div(max_cout, 16), l.njobs);
         EEM_NOTE_GRID(gw.x * gw.y * gw.z, 576);
         tail_launch_t<3, 46>(l, gw, stream);
+        tail_form("tail_k3_g46", l.njobs);
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }
@@ -525,18 +544,19 @@ int tail_conv_launch(const TailConvLaunch& l, hipStream_t stream) {
     dim3 grid(ceil_div(l.h * l.w, 16) * l.batch, ceil_div(max_cout, 16), l.njobs);
     EEM_NOTE_GRID(grid.x * grid.y * grid.z, 64 * l.ksize * l.ksize);
     if (l.ksize == 1) {
-        if (max_cg <= 2) tail_launch_t<1, 2>(l, grid, stream);
-        else tail_launch_t<1, 25>(l, grid, stream);
+        if (max_cg <= 2) { tail_launch_t<1, 2>(l, grid, stream); tail_form("tail_k1_g2", l.njobs); }
+        else { tail_launch_t<1, 25>(l, grid, stream); tail_form("tail_k1_g25", l.njobs); }
     } else if (multi_ok) {
         constexpr int PT = 5;                                          // pixel tiles per block
         dim3 gm(ceil_div((int)grid.x, PT), grid.y, grid.z);
         EEM_NOTE_GRID(gm.x * gm.y * gm.z, 576);
         hipLaunchKernelGGL((tail_conv_multi_kernel<kMultiMaxCg, PT>), gm, dim3(576), 0, stream, l);
-    } else if (max_cg <= 5) tail_launch_t<3, 5>(l, grid, stream);
-    else if (max_cg <= 8) tail_launch_t<3, 8>(l, grid, stream);
-    else if (max_cg <= 16) tail_launch_t<3, 16>(l, grid, stream);
-    else if (max_cg <= 18) tail_launch_t<3, 18>(l, grid, stream);
-    else tail_launch_t<3, 25>(l, grid, stream);
+        tail_form("tail_multi", l.njobs);
+    } else if (max_cg <= 5) { tail_launch_t<3, 5>(l, grid, stream); tail_form("tail_k3_g5", l.njobs); }
+    else if (max_cg <= 8) { tail_launch_t<3, 8>(l, grid, stream); tail_form("tail_k3_g8", l.njobs); }
+    else if (max_cg <= 16) { tail_launch_t<3, 16>(l, grid, stream); tail_form("tail_k3_g16", l.njobs); }
+    else if (max_cg <= 18) { tail_launch_t<3, 18>(l, grid, stream); tail_form("tail_k3_g18", l.njobs); }
+    else { tail_launch_t<3, 25>(l, grid, stream); tail_form("tail_k3_g25", l.njobs); }
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }

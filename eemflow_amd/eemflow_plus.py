@@ -121,8 +121,30 @@ class EEMFlow_cdc(HipModel, nn.Module):  # noqa: N801
         flat = self._flat_weights().contiguous()
         _lib.check(_lib.lib().eemplus_load_weights(self._ctx, flat.data_ptr(), flat.numel(), self.n_first_channels, self.groups))
 
+    record_stages = None            # name prefixes: eemplus_record_stages - every matching launch's output through stage() / stage_names()
+
     def _configure(self):
-        _lib.check(_lib.lib().eemplus_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
+        L = _lib.lib()
+        # the stage recorder: a context starts with it off, and the call is made only when the setting changes
+        want = None if self.record_stages is None else tuple(self.record_stages)
+        last = getattr(self, "_recorder_set", None)                        # (context, setting) of the last call made
+        if want != (last[1] if last is not None and last[0] == self._ctx.value else None):
+            _lib.check(L.eemplus_record_stages(self._ctx, None if want is None else ",".join(want).encode()))
+            self._recorder_set = (self._ctx.value, want)
+        _lib.check(L.eemplus_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
+
+    def stage_names(self):
+        """[(name, form, (n, c, h, w))] of everything the stage recorder (`record_stages`) filed in the last call, in launch order."""
+        L = _lib.lib()
+        need = ctypes.c_size_t()
+        _lib.check(L.eemplus_stage_list(self._ctx, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        _lib.check(L.eemplus_stage_list(self._ctx, buf, need.value, ctypes.byref(need)))
+        out = []
+        for line in buf.value.decode().splitlines():
+            name, form, *dims = line.split()
+            out.append((name, "" if form == "-" else form, tuple(int(d) for d in dims)))
+        return out
 
     def forward(self, events1, events2):
         self._require_cuda("forward", events1, events2)

@@ -718,9 +718,33 @@ int eemplus_stream_pending(eemplus_ctx* ctx, int* out);
 
 /* Intermediates of the LAST forward: "flow2".."flow6" (low-resolution level flows, incl. the in-place doubling
  * the reference applies to flow3..flow6), "flow_up2".."flow_up5" and "flow_init2".."flow_init5" (cdc_model's upsampled
- * input flow of each level). */
+ * input flow of each level); after them, every name the stage recorder filed in the last call (eemplus_record_stages). */
 int eemplus_get_stage(eemplus_ctx* ctx, const char* name, float* dst, size_t dst_capacity_floats, int dims_out[4],
                       void* stream);
+
+/* Stage recorder, for tests that hold every launch of eemplus_forward / eemplus_forward_many / eemplus_level to a reference of that one
+ * launch (off by default; eemplus_forward_stream records nothing - its flows are bitwise eemplus_forward_many's).  prefixes:
+ * comma-separated name prefixes ("pad,enc,l2."; "" = everything), NULL = off.  While on, the call enqueues - behind every launch whose
+ * name starts with one of them, on the stream that launch ran on (the side stream under EEM_PLUS_SIDE=1 included) - a device copy of that
+ * launch's output, filed under the name with the kernel form that wrote it; it launches no kernel differently, and the predictions are
+ * bit for bit those of the call with the recorder off.  The copies live in one arena sized by the forward before: a forward whose
+ * records do not fit is run a second time.  A copy is taken where a later launch overwrites the buffer (the encoder's two scratch
+ * buffers, the coarse flow that the next level doubles, a level's decoder input), so it is what the consuming launch read.
+ * Names:  "pad";  "enc0".."enc7" (the encoder's layers; enc4 and enc7 are pyramid levels 2 and 3);  "pool4".."pool6" (levels 4..6);
+ * per level K = 6..2 "lK.a1", "lK.a2" (the 1x1 projections of feature_1 / feature_2), "lK.rconv", "lK.flow_init", "lK.coarse_scaled"
+ * (level K + 1's flow after the doubling, [B][2][h_{K+1}][w_{K+1}]), "lK.warp_a2", "lK.de0".."lK.de4", "lK.xout", "lK.tw" (the mode-1
+ * warp of flow_init, EEM_PLUS_NO_FUSE=1 only), "lK.flow_up", "lK.fw", "lK.corr", "lK.cat_flow" (channels 85..86 of the decoder's
+ * input), "lK.dec1", "lK.decg0".."lK.decg2", "lK.dec5", "lK.dec6", "lK.flow" (level 6: corr, cat_flow, rconv and the decoder);
+ * "pred" [5 * B][2][H][W] (eemplus_forward_many: "pred<sample>" [5][2][H][W]).  A launch of two jobs that writes two buffers files two
+ * stages with the same form.  eemplus_level records the one level it runs.  eemplus_stage_list writes one line "name form n c h w" per
+ * record of the last call ("-": no launch wrote it - a device copy), *need = the bytes it takes (buf NULL: only that). */
+int eemplus_record_stages(eemplus_ctx* ctx, const char* prefixes);
+int eemplus_stage_list(eemplus_ctx* ctx, char* buf, size_t capacity, size_t* need);
+/* The kernel form of this thread's last launch by tail_conv_launch ("tail_k<1|3>_g<groups>_j<jobs>", "tail_multi_j<jobs>"), wnc_launch
+ * ("wnc32", "wnc64", "..._m16"), enc_conv_launch ("enc1", "enc_c<cin>_<cout>_s<stride>", "wino", "enc2", ...), corr_launch ("corr_direct",
+ * "corr_tiled53") or a launch of plus_kernels.hip ("warp", "upflow", "upflow_multi", "upflow_warp", "scale_flow", "blend", "warp_blend",
+ * "warp_blend_warp", "copy_channels"): what eemplus_warp / eemplus_upsample_flow_as ran. */
+int eemplus_last_form(char* buf, int capacity);
 
 /* Teacher-forced level: level l (5..2) of the coarse-to-fine loop, re-run on the feature pyramid of the LAST eemplus_forward
  * from a caller-supplied flow_init [batch][2][h_l][w_l] - cdc_model's upsampled input flow, the value the discontinuous

@@ -659,3 +659,353 @@ def check_bitwise(name, got, ref):
         w = int(torch.nonzero(bad.reshape(-1))[0])
         raise StageError(f"{name} [bitwise]: {int(bad.sum())} of {g.numel()} values differ; the first at {where(r.shape, w)}: got "
                          f"{float(g.reshape(-1)[w]):.9g}, ref {float(r.reshape(-1)[w]):.9g}")
+
+
+# --------------------------------------------------------------------------------- EEMFlow+ inference, launch by launch (eemplus_record_stages)
+# tests/test_gpu_plus_stage_fp64.py and tests/test_fp64_bounds_plus.py: every launch of eemplus_forward / eemplus_level the stage recorder
+# files, against an fp64 evaluation of that one launch on the GPU's own recorded input to it.  The three criteria of the E-RAFT section,
+# none fitted to the kernels under test:
+#   1. plain sums (every convolution whose epilogue is none / LeakyReLU / dec7's residual add, the 53-tap correlation, the pooling):
+#      `check` under the family of the form that ran (PL_FORM_FAMILY);
+#   2. the warps' four-term blend, the flow upsampling and the scalings: max|z| against a derived count of roundings (ER_ROUNDINGS);
+#   3. launches that end in the sigmoid blend: `check_decoder` against torch's fp32 CPU evaluation of the same launch.
+from . import eemflow_plus_oracle as P     # noqa: E402
+import re                                  # noqa: E402
+
+# Form -> family, by the form's arithmetic.  tail_conv_kernel / tail_conv_multi_kernel are fp32 16x16x4 MFMA sums with K split over the
+# waves of a block - the direct family's class of arithmetic; conv_wnc.hip is Winograd F(2x2,3x3); the encoder forms as
+# tests/test_gpu_stage_fp64.py holds them (conv_enc1.hip -> enc1, the F(2x2) kernel -> wino2, the direct MFMA kernels -> direct).
+PL_FORM_FAMILY = {"wnc32": "wino2", "wnc64": "wino2", "wnc32_m16": "wino2", "wnc64_m16": "wino2",
+                  "enc1": "enc1", "wino": "wino2", "enc2": "direct",
+                  "corr_direct": "corr", "corr_tiled53": "corr", "pool2x3": "pool"}
+PL_FORM_FAMILY.update({f"enc_c{_a_}_{_b_}_s{_s_}": "direct" for _a_, _b_, _s_ in ((5, 16, 2), (16, 16, 1), (16, 32, 2), (32, 32, 1), (32, 64, 2), (64, 64, 1))})
+PL_FORM_FAMILY.update({f"tail_k1_g{_g_}": "direct" for _g_ in (2, 25)})
+PL_FORM_FAMILY.update({f"tail_k3_g{_g_}": "direct" for _g_ in (5, 8, 16, 18, 25, 46)})
+PL_FORM_FAMILY["tail_multi"] = "direct"
+PL_FORM_FAMILY["enc_c5_16_s2"] = "enc1"      # (pconv1_1 on the generic kernel: the enc1 family holds the first layer on either kernel)
+# the launches held to criteria 2 and 3 (plus_kernels.hip) and the copies: every name the recorder can report is in one of the tables
+PL_OTHER_FORMS = {"warp", "upflow", "upflow_multi", "upflow_warp", "scale_flow", "blend", "warp_blend", "warp_blend_warp", "copy_channels",
+                  "pad", "pad4", "pad4_pair"}
+# the tile a form cuts the output map into (rows, cols), so that a failure names the tile
+PL_TILE = {"wnc32": (4, 32), "wnc64": (4, 64), "wnc32_m16": (4, 32), "wnc64_m16": (4, 64), "corr_tiled53": (8, 16), "wino": (4, 32)}
+
+
+def pl_base_form(name):
+    """A tail form without its job count: "tail_k3_g25_j2" -> ("tail_k3_g25", 2); every other name -> (name, 1)."""
+    m = re.fullmatch(r"(tail_\w+?)_j(\d+)", name)
+    return (m.group(1), int(m.group(2))) if m else (name, 1)
+
+
+def pl_form_family(name):
+    """Family of a form the EEMFlow+ stage recorder reports: its own launches' names, else a gconv form's (form_family)."""
+    base, _ = pl_base_form(name)
+    return PL_FORM_FAMILY[base] if base in PL_FORM_FAMILY else form_family(base)
+
+
+def pl_tile(form):
+    base, _ = pl_base_form(form)
+    if base in PL_TILE:
+        return PL_TILE[base]
+    m = re.fullmatch(r"gconv16_\dx\d_th(\d)_wm\d_kg\d", base)
+    return (int(m.group(1)), 16) if m else None
+
+
+def pl_check_form(name, form, got, ref, mag):
+    """Criterion 1: `check` under the family of the form that ran, the failure naming the form's tile."""
+    return check(name, got, ref, mag, pl_form_family(form), tile=pl_tile(form), form=form)
+
+
+# Criterion 2, counted as ER_ROUNDINGS counts (every fp32 operation one factor (1 + d), |d| <= u; a fused multiply-add only removes one):
+#   warp    ((v0 nw + v1 ne) + v2 sw) + v3 se with the four weights GIVEN (they and the mask are the model's definition, pl_warp_taps):
+#           v0's term passes one product and three sums, the others fewer; the mask's factor 0 / 1 is exact                       -> 4
+#   upflow  (1 - ly) ((1 - lx) s00 + lx s01) + ly ((1 - lx) s10 + lx s11) with lx, ly given: s00's term passes 1 - lx, a product, the
+#           inner sum, 1 - ly (a rounding of its own factor), the outer product and the outer sum                                  -> 6
+#   upflow_rate  the same times the fp32 rate factor ow / w (given: the reference multiplies by that float)                          -> 7
+#   scale   flow * factor (scale_flow, the coarse flow's doubling inside upflow_warp): one product                                  -> 1
+ER_ROUNDINGS.update({"warp": 4, "upflow": 6, "upflow_rate": 7, "scale": 1})
+
+
+def pl_conv_ref(x, w, b, act=True, k=3, groups=1, res=None):
+    """One convolution launch of the path in fp64: leaky(conv(x)) (act) or conv(x) [+ res: dec7's residual epilogue]; zero padding
+    (k - 1) / 2.  groups > 1: the decoder's grouped layer WITH its channel shuffle - output j of group g lands at channel j * G + g
+    (EEMFlow+.py:51-57).  mag: the pre-activation's sum of |terms| (+ |res|), in the output's channel order."""
+    ref, mag = conv_ref(x, w, b, groups=groups, act=act, padding=(k - 1) // 2)
+    if groups > 1:
+        ref, mag = shuffle(ref, groups), shuffle(mag, groups)
+    if res is not None:
+        ref, mag = ref + _d(res), mag + _d(res).abs()
+    return ref, mag
+
+
+def pl_conv_f32(x, w, b, act=True, k=3, groups=1, res=None):
+    """torch's fp32 CPU evaluation of the same launch (what the host tests feed the checks)."""
+    y = F.conv2d(_f32(x), _f32(w), _f32(b), padding=(k - 1) // 2, groups=groups)
+    if act:
+        y = F.leaky_relu(y, 0.1)
+    if groups > 1:
+        y = O.channel_shuffle(y, groups)
+    return y + _f32(res) if res is not None else y
+
+
+PL_DE_OUT = (32, 32, 32, 16, 8)                 # the dense estimator's five convs: output channels ...
+PL_DE_OFF = (88, 56, 24, 8, 0)                  # ... and where each lands in the 184-channel buffer [de4 | de3 | de2 | de1 | de0 | a1 | warp_a2]
+PL_DENSE = 184
+
+
+def pl_dense_input(a1, warp_a2, des):
+    """The input of the dense estimator's conv len(des) (0..5): the buffer's slice [184 - din, 184) = [de_{i-1} .. de_0 | a1 | warp_a2]
+    (cdc_utils.py:109-145: x = cat([conv_i(x), x]))."""
+    return torch.cat([_f32(t) for t in list(des)[::-1] + [a1, warp_a2]], 1)
+
+
+def pl_dense_buffer(a1, warp_a2, des):
+    """The same stages laid out at their offsets in a zeroed 184-channel buffer (the host tests' emulation of the launch's bookkeeping)."""
+    n, _, h, w = a1.shape
+    buf = torch.zeros(n, PL_DENSE, h, w)
+    buf[:, 120:152], buf[:, 152:184] = _f32(a1), _f32(warp_a2)
+    for i, t in enumerate(des):
+        buf[:, PL_DE_OFF[i]:PL_DE_OFF[i] + PL_DE_OUT[i]] = _f32(t)
+    return buf
+
+
+def pl_cat_input(corr, rconv, flow):
+    """The decoder's 87-channel input [53 correlation taps | 32 rconv | 2 flow] (EEMFlow+.py:179,191)."""
+    return torch.cat([_f32(corr), _f32(rconv), _f32(flow)], 1)
+
+
+def _f32c(v):
+    return torch.tensor(float(v), dtype=torch.float32)
+
+
+def pl_warp_taps(flow, mode):
+    """The four taps of a warp, in fp32 operation by operation as csrc/warp_px.h and ATen's CPU grid sampler form them - they and the
+    mode-2 mask are the model's definition.  mode 0: align_corners=True (EEMFlow_cdc.warp); 1: align_corners=False (torch_warp); 2: the
+    same + the `grid_sample(ones) >= 1` mask (WarpingLayer_no_div).  flow [B, 2, h, w] -> {"w": four fp32 weights (nw, ne, sw, se),
+    "y", "x": the four corners' integer positions, "ok": inside the map, "mask": [B, h, w] bool}."""
+    f = _f32(flow)
+    b, _, h, w = f.shape
+    px = torch.arange(w, dtype=torch.float32).view(1, 1, w).expand(b, h, w)
+    py = torch.arange(h, dtype=torch.float32).view(1, h, 1).expand(b, h, w)
+    vx, vy = px + f[:, 0], py + f[:, 1]
+    xn = 2.0 * vx / _f32c(max(w - 1, 1)) - 1.0
+    yn = 2.0 * vy / _f32c(max(h - 1, 1)) - 1.0
+    if mode == 0:
+        ix = (xn + 1.0) * (_f32c(w - 1) / 2.0)
+        iy = (yn + 1.0) * (_f32c(h - 1) / 2.0)
+    else:
+        ix = (xn + 1.0) * (_f32c(w) / 2.0) - 0.5
+        iy = (yn + 1.0) * (_f32c(h) / 2.0) - 0.5
+    xw, yn0 = torch.floor(ix), torch.floor(iy)
+    ww, wn = ix - xw, iy - yn0
+    we, ws = 1.0 - ww, 1.0 - wn
+    wts = (ws * we, ws * ww, wn * we, wn * ww)                          # nw, ne, sw, se
+    x0 = xw.clamp(-2.0, float(w) + 1.0).long()
+    y0 = yn0.clamp(-2.0, float(h) + 1.0).long()
+    xs, ys = (x0, x0 + 1, x0, x0 + 1), (y0, y0, y0 + 1, y0 + 1)
+    ok = tuple((ys[i] >= 0) & (ys[i] < h) & (xs[i] >= 0) & (xs[i] < w) for i in range(4))
+    if mode == 2:
+        o = [ok[i].float() * wts[i] for i in range(4)]
+        mask = (((o[0] + o[1]) + o[2]) + o[3]) >= 1.0
+    else:
+        mask = torch.ones(b, h, w, dtype=torch.bool)
+    assert all(t.dtype == torch.float32 for t in wts)
+    return {"w": wts, "y": ys, "x": xs, "ok": ok, "mask": mask}
+
+
+def pl_warp_ref(x, flow, mode):
+    """A warp launch against fp64: the taps as given (pl_warp_taps), the blend ((v0 nw + v1 ne) + v2 sw) + v3 se in fp64, times the
+    mask -> (ref, mag, mask); mag is the blend's sum of |terms| (NOT masked: a masked pixel must be exactly 0, see pl_check_warp)."""
+    t = pl_warp_taps(flow, mode)
+    xd = _d(x)
+    b, c, h, w = xd.shape
+    bi = torch.arange(b).view(b, 1, 1)
+    ref = torch.zeros(b, c, h, w, dtype=torch.float64)
+    mag = torch.zeros(b, c, h, w, dtype=torch.float64)
+    for i in range(4):
+        v = xd[bi, :, t["y"][i].clamp(0, h - 1), t["x"][i].clamp(0, w - 1)].permute(0, 3, 1, 2)      # [B, C, h, w]
+        v = torch.where(t["ok"][i][:, None], v, torch.zeros((), dtype=torch.float64))
+        wt = t["w"][i].double()[:, None]
+        ref += v * wt
+        mag += v.abs() * wt.abs()
+    m = t["mask"][:, None]
+    return ref * m, mag, t["mask"]
+
+
+def pl_check_warp(name, got, x, flow, mode, form="warp"):
+    """Criterion 2 for a warp launch: where the reference's mask is 0 the output is exactly 0 (so a GPU mask of 1 there shows unless
+    the blend itself is 0); elsewhere max|z| <= 4 roundings of the blend (so a GPU mask of 0 there shows unless the blend is 0)."""
+    ref, mag, mask = pl_warp_ref(x, flow, mode)
+    g = _d(got)
+    if g.shape != ref.shape:
+        raise StageError(f"{name} [{form}]: shape {tuple(g.shape)} against the reference's {tuple(ref.shape)}")
+    out = ~mask[:, None].expand_as(g)
+    bad = out & (g != 0)
+    if bool(bad.any()):
+        wst = int(torch.nonzero(bad.reshape(-1))[0])
+        raise StageError(f"{name} [{form}]: {int(bad.sum())} values are nonzero where the `grid_sample(ones) >= 1` mask is 0; the first at "
+                         f"{where(g.shape, wst)}: {float(g.reshape(-1)[wst]):.9g}")
+    return check_roundings(name, got, ref, mag, "warp", form=form)
+
+
+def pl_mask_of(got):
+    """The mask a mode-2 warp applied, read from its output on an input that is positive everywhere: a pixel is kept iff any channel is
+    nonzero (four inside taps of positive values with weights that sum to 1 cannot give 0)."""
+    return (_f32(got) != 0).any(1)
+
+
+def pl_upflow_geometry(n_in, n_out):
+    """Source index and weight of F.interpolate(bilinear, align_corners=True) along one axis, in fp32 as upflow_px and ATen's CPU
+    kernel compute them: scale = (in - 1) / (out - 1), f = scale * i, i0 = int(f), l = f - i0 -> (i0, i1, l) with l fp32."""
+    s = _f32c(n_in - 1) / _f32c(n_out - 1) if n_out > 1 else _f32c(0.0)
+    f = s * torch.arange(n_out, dtype=torch.float32)
+    i0 = f.long()
+    i1 = i0 + (i0 < n_in - 1).long()
+    return i0, i1, f - i0.float()
+
+
+def pl_rate(out_hw, in_hw):
+    """upsample2d_flow_as(if_rate=True)'s two factors as the fp32 numbers the multiplication uses: (su, sv) = (ow / w, oh / h)."""
+    return float(_f32c(out_hw[1]) / _f32c(in_hw[1])), float(_f32c(out_hw[0]) / _f32c(in_hw[0]))
+
+
+def pl_upflow_ref(coarse, out_hw, rate=True):
+    """upsample2d_flow_as (cdc_utils.py:80-103): the bilinear sum in fp64 with lx, ly given (pl_upflow_geometry), channel 0 times ow / w
+    and channel 1 times oh / h when `rate` -> (ref, mag)."""
+    c = _d(coarse)
+    h, w = c.shape[-2:]
+    oh, ow = out_hw
+    y0, y1, ly = pl_upflow_geometry(h, oh)
+    x0, x1, lx = pl_upflow_geometry(w, ow)
+    ly, lx = ly.double().view(-1, 1), lx.double().view(1, -1)
+
+    def blend(t):
+        r0 = t[..., y0, :]
+        r1 = t[..., y1, :]
+        a = (1 - lx) * r0[..., x0] + lx * r0[..., x1]
+        bb = (1 - lx) * r1[..., x0] + lx * r1[..., x1]
+        return (1 - ly) * a + ly * bb
+    ref, mag = blend(c), blend(c.abs())
+    if rate:
+        su, sv = pl_rate(out_hw, (h, w))
+        s = torch.tensor([su, sv], dtype=torch.float64).view(1, 2, 1, 1)
+        ref, mag = ref * s, mag * s.abs()
+    return ref, mag
+
+
+def pl_scale_ref(flow, out_hw):
+    """The in-place side effect of upsample2d_flow_as(if_rate=True) on its input (cdc_utils.py:85-86): channel 0 * ow / w, 1 * oh / h."""
+    f = _d(flow)
+    su, sv = pl_rate(out_hw, f.shape[-2:])
+    s = torch.tensor([su, sv], dtype=torch.float64).view(1, 2, 1, 1)
+    return f * s, (f * s).abs()
+
+
+def pl_blend_ref(warped, flow_init, xout, dtype=torch.float64):
+    """flow_up = warped (1 - sigmoid(m)) + flow_init sigmoid(m), m = xout[:, 2:3] (cdc_utils.py:163-173)."""
+    t = lambda a: torch.as_tensor(a).detach().cpu().to(dtype)       # noqa: E731
+    m = torch.sigmoid(t(xout)[:, 2:3])
+    return t(warped) * (1 - m) + t(flow_init) * m
+
+
+def pl_warp_blend_refs(flow_init, xout):
+    """The fused launch's flow_up -> (fp64 reference: the mode-1 warp's taps as given, its blend and the sigmoid blend in fp64;
+    torch's fp32 CPU evaluation: the oracle's torch_warp and the same expression)."""
+    w64, _, _ = pl_warp_ref(flow_init, _f32(xout)[:, :2], 1)
+    ref64 = pl_blend_ref(w64, flow_init, xout)
+    fi, xo = _f32(flow_init), _f32(xout)
+    ref32 = pl_blend_ref(P.torch_warp(fi, xo[:, :2]), fi, xo, torch.float32)
+    return ref64, ref32
+
+
+def pl_check_leaky(name, got, form=None):
+    """Bitwise: every negative output of a LeakyReLU launch is fl(q * LEAKY) for some fp32 q - the activation of an fp32 pre-activation
+    by the fp32 slope.  y = fl(q s) puts q within one ulp of fl(y / s) (s ~ 0.1: an ulp of y is at most 1 / 8 of q's), so seven
+    candidates are tried.  Multiplying by s thins a binade to ~62 % of its values, so a slope that is not the float nearest 0.1 (0.1 in
+    double is a relative 0.25 u off - beneath every family's limits) leaves values outside the image."""
+    y = _f32(got).reshape(-1)
+    y = y[(y < 0) & (y.abs() > 1e-30)]
+    s = torch.tensor(LEAKY, dtype=torch.float32)
+    q0 = y / s
+    lo, hi = q0.clone(), q0.clone()
+    hit = (q0 * s) == y
+    ninf, pinf = torch.tensor(float("-inf")), torch.tensor(float("inf"))
+    for _ in range(3):
+        lo, hi = torch.nextafter(lo, ninf), torch.nextafter(hi, pinf)
+        hit |= ((lo * s) == y) | ((hi * s) == y)
+    LOG.append({"name": name, "form": "leaky", "n": int(y.numel()), "differ": int((~hit).sum())})
+    if not bool(hit.all()):
+        w = int(torch.nonzero(~hit)[0])
+        raise StageError(f"{name} [{form or 'leaky'}]: {int((~hit).sum())} of {y.numel()} negative outputs are no fp32 value times the fp32 "
+                         f"slope {LEAKY!r}; the first: {float(y[w]):.9g}")
+
+
+# (map height, width, seed) of the direct warp checks of tests/test_gpu_plus_stage_fp64.py; tests/test_fp64_bounds_plus.py holds the tap
+# reference to F.grid_sample on exactly these
+PL_WARP_CASES = [(25, 37, 11), (6, 9, 12)]
+
+
+def pl_position_is_plain(flow):
+    """Where the sample position of modes 1 and 2, ix = (xn + 1) (w / 2) - 0.5, is the same fp32 number whether the product is rounded
+    before the subtraction (csrc/warp_px.h, built without contraction) or not (a fused multiply-add: what torch's vectorised CPU grid
+    sampler and its CUDA one compile to): [B, h, w] bool, both axes.  Mode 0's position has no such pair of operations."""
+    f = _f32(flow)
+    b, _, h, w = f.shape
+    ok = torch.ones(b, h, w, dtype=torch.bool)
+    for ch, n in ((0, w), (1, h)):
+        p = torch.arange(n, dtype=torch.float32).view((1, 1, n) if ch == 0 else (1, n, 1)).expand(b, h, w)
+        c1 = (2.0 * (p + f[:, ch]) / _f32c(max(n - 1, 1)) - 1.0) + 1.0
+        plain = c1 * (_f32c(n) / 2.0) - 0.5
+        fused = (c1.double() * (n / 2.0) - 0.5).float()
+        ok &= plain == fused
+    return ok
+
+
+def pl_hostile_flows(h, w, seed, plain_only=True):
+    """Flows [6, 2, h, w] for the direct warp checks (the flows a seeded network produces are small): image 0 exact integer
+    displacements; 1 displacements of x.5; 2 every pixel sent just inside / outside a border of the map by 1e-3 - in the coordinates
+    of mode 0 (x = px + fx against 0 and w - 1); 3 the same in the coordinates of modes 1 and 2 (ix = (px + fx) w / (w - 1) - 0.5
+    against -1, 0, w - 1 and w); 4 far outside (1e4 and 1e9: the float -> int conversion) between small smooth flows; 5 random
+    sub-pixel flows.  A pixel whose position depends on whether torch's build contracts the unnormalisation (pl_position_is_plain) is
+    drawn again from its image's rule, so that the reference, warp_px.h and every build of F.grid_sample agree on all of them.  Both
+    test modules build their warp inputs here: the host module's conditions hold for exactly what the GPU runs.  plain_only=False:
+    the first draw as it is - on it a kernel that contracts the position's multiply-add differs from pl_warp_taps (and pl_warp_taps
+    from a contracting torch build), so it is compared with pl_warp_taps alone."""
+    g = torch.Generator().manual_seed(seed)
+    px = torch.arange(w, dtype=torch.float32).view(1, w).expand(h, w)
+    py = torch.arange(h, dtype=torch.float32).view(h, 1).expand(h, w)
+
+    def pick(vals):
+        return torch.tensor(vals, dtype=torch.float32)[torch.randint(0, len(vals), (h, w), generator=g)]
+
+    def eps():
+        return torch.where(torch.rand(h, w, generator=g) < 0.5, -1e-3, 1e-3)
+
+    def ints():
+        return torch.randint(-3, 4, (2, h, w), generator=g).float()
+
+    def border0():
+        return torch.stack([pick([0.0, w - 1.0]) + eps() - px, pick([0.0, h - 1.0]) + eps() - py])
+
+    def border1():
+        tx, ty = pick([-1.0, 0.0, w - 1.0, float(w)]) + eps(), pick([-1.0, 0.0, h - 1.0, float(h)]) + eps()
+        return torch.stack([(tx + 0.5) * ((w - 1) / w) - px, (ty + 0.5) * ((h - 1) / h) - py])
+
+    def far():
+        f = torch.randn(2, h, w, generator=g) * 0.3
+        sel = torch.rand(h, w, generator=g)
+        f[:, sel < 0.15] = 1e4
+        f[:, (sel >= 0.15) & (sel < 0.3)] = -1e4
+        f[0, (sel >= 0.3) & (sel < 0.4)] = 1e9
+        f[1, (sel >= 0.4) & (sel < 0.5)] = -1e9
+        return f
+    rules = (ints, lambda: ints() + 0.5, border0, border1, far, lambda: torch.randn(2, h, w, generator=g) * 1.5)
+    out = torch.stack([r() for r in rules]).float()
+    if not plain_only:
+        return out
+    for _ in range(64):
+        bad = ~pl_position_is_plain(out)
+        if not bool(bad.any()):
+            return out
+        new = torch.stack([r() for r in rules]).float()
+        out = torch.where(bad[:, None], new, out)
+    raise AssertionError("pl_hostile_flows: no build-independent draw found")
