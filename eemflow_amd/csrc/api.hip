@@ -12,7 +12,7 @@
 
 // ------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
-thread_local int eem_last_grid_blocks = 0, eem_last_grid_threads = 0, eem_last_pipe = 0;
+thread_local int eem_last_grid_blocks = 0, eem_last_grid_threads = 0, eem_last_pipe = 0, eem_last_variant = 0;
 
 void eem_set_error(const char* fmt, ...) {
     va_list ap;

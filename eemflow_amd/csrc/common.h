@@ -55,12 +55,15 @@ __host__ __device__ static inline int ceil_div(int a, int b) { return (a + b - 1
 
 // grid of the encoder launch this thread made last (blocks x threads per block): eemflow_time_kernels reports it beside the
 // duration - a kernel that runs on a quarter of the chip by design is not a slow kernel (api.hip defines it)
-extern thread_local int eem_last_grid_blocks, eem_last_grid_threads, eem_last_pipe;
+extern thread_local int eem_last_grid_blocks, eem_last_grid_threads, eem_last_pipe, eem_last_variant;
 #define EEM_NOTE_GRID(blocks, threads) do { eem_last_grid_blocks = (int)(blocks); eem_last_grid_threads = (int)(threads); } while (0)
 // which matrix pipe the launch's contraction runs on: 0 fp32 MFMA (157 TFLOP/s), 1 fp32 products as six bf16-piece MFMAs (2.5 PFLOP/s / 6),
 // 2 Winograd F(4x4,3x3) on the fp32 MFMA (36 products per 16 outputs where the direct form has 144: its roof in direct-convolution FLOPs
 // is 4 x 157), 3 F(2x2,3x3) (16 per 4 outputs against 36: 2.25 x)
 #define EEM_NOTE_PIPE(p) do { eem_last_pipe = (int)(p); } while (0)
+// a launcher's own tag for the instantiation it chose, 0 unless it says otherwise (conv_wino4.hip: 1 = the shared-V form);
+// eemflow_time_kernels reports it in eemflow_kernel_stat::reserved, so a test of a form switch can see that the switch switched
+#define EEM_NOTE_VARIANT(v) do { eem_last_variant = (int)(v); } while (0)
 
 // compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, N) - the index is usable as a template /
 // inline-asm immediate inside f
@@ -214,6 +217,9 @@ struct EncConvArgs {
     // a layer whose output is only read through its fused pooling partial sums (pconv3_3 in inference: f13, EEMFlow.py:152-154) may skip
     // the feature-map stores: a hint - kernels built with a store-free form honour it (the two Winograd forms at C = 64), the others store
     int no_store = 0;
+    // conv_wino4.hip at C = 64, plain and store-free epilogues: the form whose tile groups compute V = B^T d B once (two duty waves, half the
+    // Winograd rows each, through LDS) instead of once per cout group; bitwise the other form's result.  Set by the EEMFlow forward (schedule.hip, EEM_W4_VSHARE)
+    int vshare = 0;
 };
 // Every launch argument a block uses, wanted in scalar registers at its first instruction: one batch of scalar loads instead of the three or
 // four dependent ones the compiler otherwise spreads over the prologue (see tail_conv_kernel in tail.hip for what a memory round trip costs

@@ -61,17 +61,33 @@ struct W4Cfg {
 #ifdef EEM_STAMPS
 // diagnostic build only (-DEEM_STAMPS=<C>: the layers with that channel count): s_memtime stamps of every wave (slot 0: start,
 // 1: prologue done, 2 + 2L: k-step L has passed its barrier, 3 + 2L: its MFMAs are issued, 60: after the last output phase,
-// 61: s_memrealtime ticks of the whole kernel), written as they are taken
-__device__ unsigned long long g_stamps4[1024 * 8 * 64];
-#define STAMP4(i) do { if (C == EEM_STAMPS && lane == 0 && blockIdx.x < 1024 && (i) < 64) g_stamps4[(blockIdx.x * 8 + wave) * 64 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+// 61: s_memrealtime ticks of the whole kernel, 62: the first tile's output phase is done, 64 + 2L: k-step L's DMA is issued,
+// 65 + 2L: its patch reads and column pass are done - in the shared-V form: its duty pass, after the MFMAs), written as they are
+// taken; a stamp pins the schedule around it
+__device__ unsigned long long g_stamps4[1024 * 8 * 128];
+#define STAMP4(i) do { if (C == EEM_STAMPS && blockIdx.x < 1024 && (i) < 128) { __builtin_amdgcn_sched_barrier(0); if (lane == 0) g_stamps4[(blockIdx.x * 8 + wave) * 128 + (i)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#define STAMP4K(base, L) do { if ((L) < 29) STAMP4((base) + 2 * (L)); } while (0)
 #else
 #define STAMP4(i)
+#define STAMP4K(base, L)
 #endif
 
 // EPI: 0 plain, 1 the result is multiplied by LeakyReLU'(gate) (data gradients), 2 relu(residual + result) (E-RAFT's residual blocks),
 // 3 pooling partial sums only, no feature-map stores (pconv3_3 in inference: f13 is read through its pooled map alone) -
 // separate instantiations, so the forward kernels' register allocation (252 of 256 VGPRs, no scratch) does not carry them
-template <int C, int NGX, int NGY, int POOLK, int EPI>
+//
+// VS (V shared; C = 64, EPI 0 / 3 only): the four waves of a tile group (one per cout group) need the same V = B^T d B, and f32 VALU
+// and MFMA share one issue port - so it is computed ONCE per group (two duty waves, half the Winograd rows each), a k-step ahead and
+// behind their own MFMAs, into LDS in the fragment order of U; every wave then reads both MFMA operands as ds_read_b128.  LDS (148 KB):
+//   raw input slices  3 x 12 KB   (as the input part of a ring slot; read by the duty waves only)
+//   U slices          2 x 36 KB   (all of U is L2-resident and re-streamed by every tile: one k-step of lead is enough)
+//   V slices          2 x 18 KB   ([group][q = p / 4][lane] float4)
+//   pooling scratch   2 x RED1
+// After barrier s: U[s], raw s + 1 and V[s] (written during k-step s - 1) are complete.  K-step s requests U[s + 1] (into the slot of
+// U[s - 1]), then raw s + 3 (into the slot of raw s, transformed during k-step s - 1), issues its 36 MFMAs, and the duty waves turn
+// raw s + 1 into V[s + 1].  One barrier per k-step; the duty branch is wave-uniform.  Same expressions per V value, same MFMA
+// sequence per accumulator: bitwise the VS = false result.
+template <int C, int NGX, int NGY, int POOLK, int EPI, bool VS = false>
 __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
     ENC_ARGS_NOW(a);
     using K = W4Cfg<C, NGX, NGY>;
@@ -81,11 +97,17 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
     constexpr int NSTORE = EPI == 3 ? 0 : 16;                            // feature-map stores per wave and tile
     static_assert(EPI != 3 || POOLK > 0, "a store-free launch needs the pooling output");
     constexpr int NPOOL = POOLK > 0 ? 1 : 0;
-    static_assert((R * K::STAGE + 2 * RED1) * 4 <= 160 * 1024, "LDS budget");
+    // VS: floats of a raw slice, a U slice, a V slice; where the U and V slots start
+    constexpr int RAWF = K::INP * 4, UF = K::UP * 4, VF = K::NG * 9 * 64 * 4;
+    constexpr int UBASE = 3 * RAWF, VBASE = UBASE + 2 * UF;
+    constexpr int RING = VS ? VBASE + 2 * VF : R * K::STAGE;
+    static_assert(!VS || (K::COG == 4 && (EPI == 0 || EPI == 3) && K::INP + K::UP == NI * 512 && K::UP % 64 == 0 && KS >= 3),
+                  "shared V: four waves per tile group, a piece plan without padding whose wave-instructions are all weights or all input");
+    static_assert((RING + 2 * RED1) * 4 <= 160 * 1024, "LDS budget");
     static_assert(POOLK == 0 || (POOLK % 8 == 0 && K::TW % POOLK == 0 && C * NWX * NGY <= 512 && POOLK <= 32), "pool windows");
     static_assert(NI + NSTORE + NPOOL <= 63, "vmcnt immediate");
-    __shared__ __attribute__((aligned(256))) float lds[R * K::STAGE + 2 * RED1];
-    float* red0 = lds + R * K::STAGE;
+    __shared__ __attribute__((aligned(256))) float lds[RING + 2 * RED1];
+    float* red0 = lds + RING;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -144,8 +166,13 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
     int pryq[NI];                                                        // input: ry | q << 8 (| 1 << 16 padding); weights: 1 << 17
 #pragma unroll
     for (int k = 0; k < NI; ++k) {
-        const int p = (k * 8 + wave) * 64 + lane;
-        if (p < K::INP) {
+        // VS: the weight pieces are numbered first (a k-step's requests are then U before input: in-order retirement lets the
+        // input pieces, which have two more k-steps to land, stay outstanding behind a counted wait)
+        const int p = VS ? (k * 8 + wave) * 64 + lane - K::UP : (k * 8 + wave) * 64 + lane;
+        if (VS && p < 0) {
+            poff[k] = (unsigned)(p + K::UP) * 16u;
+            pryq[k] = 1 << 17;
+        } else if (p < K::INP) {
             const int c = p / K::PLANE_P;
             int rem = p - c * K::PLANE_P;
             const bool pad = rem >= K::PC;
@@ -204,6 +231,30 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
         if (++dma_s == KS) { dma_s = 0; step_tile(nxt); dma_tile(); }
         if (++dma_slot == R) dma_slot = 0;
     };
+    // VS: the weight pieces of k-step `ws` into U slot `uslot` (do_w), then the next input slice into raw slot dma_slot (do_raw)
+    const bool raw_hi = (4 * 8 + wave) * 64 >= K::UP;                    // (VS, C = 64) this wave's fifth instruction is input: 2 input instructions, else 1
+    auto dma_issue_vs = [&](bool do_w, bool do_raw, int ws, int uslot) {
+        float* ub = lds + UBASE + uslot * UF;
+        float* rb = lds + dma_slot * RAWF;
+        const char* usrc = wbase + (size_t)ws * (K::UP * 16);
+#pragma unroll
+        for (int k = 0; k < NI; ++k) {
+            const bool all_u = (k + 1) * 512 <= K::UP, all_in = k * 512 >= K::UP;            // compile-time per k
+            const int pb = (k * 8 + wave) * 64;                                              // wave-uniform
+            if (all_u || (!all_in && pb < K::UP)) {
+                if (do_w) __builtin_amdgcn_global_load_lds(GLB_PTR(usrc + poff[k]), LDS_PTR(ub + pb * 4), 16, 0, 0);
+            } else if (do_raw) {
+                const char* gp = dsrc + poff[k];
+                if (!dma_interior) gp = (okm >> k) & 1 ? gp : zero_page;
+                __builtin_amdgcn_global_load_lds(GLB_PTR(gp), LDS_PTR(rb + (pb - K::UP) * 4), 16, 0, 0);
+            }
+        }
+        if (do_raw) {
+            dsrc += (size_t)plane_in * 16;                               // the next four channels
+            if (++dma_s == KS) { dma_s = 0; step_tile(nxt); dma_tile(); }
+            if (++dma_slot == R) dma_slot = 0;
+        }
+    };
 
     f32x4 biasq;
 #pragma unroll
@@ -234,7 +285,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (S0 && POOLK > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the output phase's pooling sums are in LDS
         __builtin_amdgcn_s_barrier();
-        STAMP4(2 + 2 * L);
+        STAMP4K(2, L);
         if constexpr (S0 && POOLK > 0) {
             // (b) finish the previous tile's pooling partial sums (written before this barrier); every lane stores (idle ones into
             // the scratch page) so that the wave's store count is fixed
@@ -248,6 +299,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
         }
         // (c) request k-step L+R-1 into the slot k-step L-1 has left
         if (L + R - 1 < total) dma_issue();
+        STAMP4K(64, L);
 
         // (d) the patch, then its column transform (rows -> xi) on the column pairs (-1,4) (0,1) (2,3) the reads deliver
         const float* sl = lds + slot * K::STAGE;
@@ -272,6 +324,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
             for (int r = 0; r < 6; ++r) x[r] = f32x2{pmid[r][2], pmid[r][3]};
             bt6(x, t34);
         }
+        STAMP4K(65, L);
         // (e) row transform (columns -> nu), then the 36 MFMAs back to back, A operands from LDS four positions at a time:
         // rows in blocks of RB - their transforms (independent chains: instruction-level parallelism for the lone issue slot), then
         // their MFMAs back to back with the A operands read two quads ahead
@@ -300,9 +353,122 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        STAMP4(3 + 2 * L);
+        STAMP4K(3, L);
         ++L;
         slot = slot + 1 == R ? 0 : slot + 1;
+    };
+
+    // ---- VS: the duty pass, in halves - the lane's patch of the raw slice in slot `rslot` -> the V values of Winograd rows
+    // xi = 3 H .. 3 H + 2 (positions 18 H .. 18 H + 17: four quads and half of quad 4; the expressions of (d) and (e) above, the column
+    // pass reduced to the three outputs of bt6 these rows need) -> V slot `vslot`, in the order the MFMAs read them
+    auto duty_half = [&](auto h_tag, int rslot, int vslot) {
+        constexpr int H = decltype(h_tag)::value;
+        const float* p = lds + rslot * RAWF + lbase;
+        f32x2 t05[6], t12[6], t34[6];
+        {
+            f32x2 pout[6];
+            f32x4 pmid[6];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                pout[r] = f32x2{p[r * K::ROWP + 1], p[r * K::ROWP + 6]};
+                pmid[r] = *reinterpret_cast<const f32x4*>(p + r * K::ROWP + 2);
+            }
+            f32x2 x[6];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) x[r] = pout[r];
+            bt6(x, t05);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) x[r] = f32x2{pmid[r][0], pmid[r][1]};
+            bt6(x, t12);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) x[r] = f32x2{pmid[r][2], pmid[r][3]};
+            bt6(x, t34);
+        }
+        float v[18];
+#pragma unroll
+        for (int xi = 0; xi < 3; ++xi) bt6_row(t05[3 * H + xi], t12[3 * H + xi], t34[3 * H + xi], v + 6 * xi);
+        float* vb = lds + VBASE + vslot * VF + (grp * 9 * 64 + lane) * 4;
+        if constexpr (H == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(vb + q * 256) = f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+            *reinterpret_cast<f32x2*>(vb + 4 * 256) = f32x2{v[16], v[17]};
+        } else {
+            *reinterpret_cast<f32x2*>(vb + 4 * 256 + 2) = f32x2{v[0], v[1]};
+#pragma unroll
+            for (int q = 5; q < 9; ++q) *reinterpret_cast<f32x4*>(vb + q * 256) = f32x4{v[4 * q - 18], v[4 * q - 17], v[4 * q - 16], v[4 * q - 15]};
+        }
+    };
+    // Who makes a V slice: a SIMD holds wave cog of BOTH groups and every k-step ends at a barrier, so the duty has to be even over
+    // the SIMDs of EACH k-step.  One rotating duty wave per group (cog == k % 4, the whole pass) puts both groups' passes on one SIMD:
+    // the k-step is then as long as when every wave transforms for itself (measured: 116.3 -> 115.4 us per ten-frame launch; group 1
+    // two SIMDs on: 112.1).  Halves - group 0's on waves cog 0 / 1, group 1's on cog 2 / 3 - give every SIMD half a pass per k-step: 109.8
+    auto make_v = [&](int rslot, int vslot) {
+        if ((cog >> 1) == grp) {                                         // wave-uniform
+            if (cog & 1) duty_half(std::integral_constant<int, 1>{}, rslot, vslot);
+            else duty_half(std::integral_constant<int, 0>{}, rslot, vslot);
+        }
+    };
+    int uslot = 0;                                                       // VS: U / V slot of k-step L (L & 1)
+    int wnext = 1;                                                       // VS: (L + 1) % KS, the k-step whose weights k-step L requests
+    // VS: one k-step.  XTRA: the feature-map stores issued behind the previous k-step's requests (first k-step of a later tile).
+    auto step_vs = [&](auto s0_tag, auto xtra_tag) {
+        constexpr bool S0 = decltype(s0_tag)::value;
+        constexpr int XTRA = decltype(xtra_tag)::value;
+        constexpr int NR_LO = (NI * 512 - K::UP) / 512, NR_HI = (NI * 512 - K::UP + 511) / 512;     // input instructions per wave
+        // (a) everything but the input pieces k-step L-1 requested has landed (U[L], raw L+1; see the table below the kernel); the
+        // duty waves' V[L] and the output phase's pooling sums are in LDS
+        if (L + 2 < total) {
+            if (raw_hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NR_HI + XTRA) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NR_LO + XTRA) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        STAMP4K(2, L);
+        if constexpr (S0 && POOLK > 0) {
+            // (b) finish the previous tile's pooling partial sums, as in the other form
+            if (L > 0) {
+                const float* redp = red0 + (((L / KS) - 1) & 1) * RED1;
+                const float s = redp[(pf_gy * C + pf_co) * NWX + pf_wx];
+                float* pb = a.pool_partial + ((size_t)prv.n * C * prow + prv.by * NGY) * (a.tiles_x * NWX) + prv.bx * NWX;
+                float* p = pf_act && prv.by * NGY + pf_gy < prow ? pb + ((size_t)pf_co * prow + pf_gy) * (a.tiles_x * NWX) + pf_wx : a.trash + lane * 4;
+                *p = s;
+            }
+        }
+        // (c) U[L+1] into the slot U[L-1] has left, raw L+3 into the slot of raw L (transformed during k-step L-1)
+        if (L + 1 < total) dma_issue_vs(true, L + 3 < total, wnext, uslot ^ 1);
+        STAMP4K(64, L);
+
+        // (d) both operands from LDS, a quad of positions at a time and one quad ahead of the MFMAs that take them
+        const f32x4* wl = reinterpret_cast<const f32x4*>(lds + UBASE + uslot * UF + (cog * 9 * 64 + lane) * 4);
+        const f32x4* vl = reinterpret_cast<const f32x4*>(lds + VBASE + uslot * VF + (grp * 9 * 64 + lane) * 4);
+        f32x4 wq0 = wl[0], vq0 = vl[0], wq1 = wl[64], vq1 = vl[64];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int p = 0; p < 36; ++p) {
+            if (p > 0 && (p & 3) == 0) {
+                wq0 = wq1; vq0 = vq1;
+                if ((p >> 2) + 1 < 9) { wq1 = wl[((p >> 2) + 1) * 64]; vq1 = vl[((p >> 2) + 1) * 64]; }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (S0) {
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq0[p & 3], vq0[p & 3], p == 7 ? biasq : z, 0, 0, 0);
+            } else {
+                acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq0[p & 3], vq0[p & 3], acc[p], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        STAMP4K(3, L);
+        // (e) the duty wave of k-step L+1, behind its own MFMAs
+        const int rnext = slot + 1 == R ? 0 : slot + 1;
+        if (L + 1 < total) make_v(rnext, uslot ^ 1);
+        STAMP4K(65, L);
+        ++L;
+        slot = rnext;
+        uslot ^= 1;
+        wnext = wnext + 1 == KS ? 0 : wnext + 1;
     };
 
     // ---- output phase of the tile in `cur`: A^T M A on pairs of cout registers, LeakyReLU, [gate], stores, pooling partial sums
@@ -414,6 +580,39 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
         }
     };
 
+    using T = std::true_type;
+    using F = std::false_type;
+    if constexpr (VS) {
+        // ---- prologue: raw 0, U[0], raw 1, raw 2 requested (total >= KS >= 3); raw 0 landed -> the duty waves make V[0]
+        (void)wlbase;
+        dma_tile();
+        dma_issue_vs(false, true, 0, 0);
+        dma_issue_vs(true, false, 0, 0);
+        dma_issue_vs(false, true, 0, 0);
+        dma_issue_vs(false, true, 0, 0);
+        if (raw_hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI + 2) : "memory");          // everything but this wave's raw-0 pieces may be in flight
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI + 1) : "memory");
+        __builtin_amdgcn_s_barrier();
+        make_v(0, 0);
+        STAMP4(1);
+        // vmcnt table (VS; per wave: nr = 1 (waves 0-3) or 2 (waves 4-7) input instructions, NI - nr weight instructions, weights first).
+        // When k-step L starts it needs U[L] (requested in k-step L-1) and raw L+1 (k-step L-2 or the prologue); the only operations
+        // that may stay in flight are those behind the weight pieces of k-step L-1:
+        //   k-step L-1 requested raw L+2 (L + 2 < total), nothing between it and here (the pooling store of an s = 0 step goes out
+        //   BEFORE that step's requests; the prologue ends with raw 2):                                        -> nr
+        //   ... and the output phase of the previous tile lies between (s = 0 of later tiles): + its stores      -> nr + NSTORE
+        //   k-step L-1 requested weights only, or nothing (the last three k-steps of a block):                  -> 0
+        for (int it = 0; it < ntile; ++it) {
+            if (it == 0) step_vs(T{}, std::integral_constant<int, 0>{});
+            else step_vs(T{}, std::integral_constant<int, NSTORE>{});
+#pragma unroll 1
+            for (int s = 1; s < KS; ++s) step_vs(F{}, std::integral_constant<int, 0>{});
+            output(it);
+            if (it == 0) STAMP4(62);
+            prv = cur;
+            step_tile(cur);
+        }
+    } else {
     // ---- prologue: R-1 slices in flight
     dma_tile();
 #pragma unroll
@@ -427,8 +626,6 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
     //   later tiles, s = 0: + the NSTORE stores of the output phase before it                                -> NI + NSTORE
     //   later tiles, s = 1: + those stores + the pooling store of k-step (s = 0)                             -> NI + NSTORE + NPOOL
     // (the last k-step of a block, behind which nothing was requested, waits for everything)
-    using T = std::true_type;
-    using F = std::false_type;
     for (int it = 0; it < ntile; ++it) {
         if (it == 0) {
             step(T{}, std::integral_constant<int, NI>{});
@@ -440,12 +637,14 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
 #pragma unroll 1
         for (int s = 2; s < KS; ++s) step(F{}, std::integral_constant<int, NI>{});
         output(it);
+        if (it == 0) STAMP4(62);
         prv = cur;
         step_tile(cur);
     }
+    }
     STAMP4(60);
 #ifdef EEM_STAMPS
-    if (C == EEM_STAMPS && lane == 0 && blockIdx.x < 1024) g_stamps4[(blockIdx.x * 8 + wave) * 64 + 61] = __builtin_amdgcn_s_memrealtime() - rt0;
+    if (C == EEM_STAMPS && lane == 0 && blockIdx.x < 1024) g_stamps4[(blockIdx.x * 8 + wave) * 128 + 61] = __builtin_amdgcn_s_memrealtime() - rt0;
 #endif
     if constexpr (POOLK > 0) {                       // last tile's pooling partial sums
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -527,6 +726,20 @@ int launch4_c(const EncConvArgs& a0, hipStream_t stream) {
         eem_set_error("wino4: gate / residual epilogues come without pooling and one at a time");
         return EEM_ERR_ARG;
     }
+    // the shared-V form (EncConvArgs::vshare: the EEMFlow forward's launches under EEM_W4_VSHARE): C = 64, plain and store-free epilogues
+    if constexpr (C == 64) {
+        if (a.vshare && a.gate == nullptr && a.res == nullptr) {
+            if (a.pool_partial != nullptr && a.no_store)
+                hipLaunchKernelGGL((wino4_kernel<C, W::NGX, W::NGY, W::POOLK, 3, true>), dim3(per_xcd * 8), dim3(512), 0, stream, a);
+            else if (a.pool_partial != nullptr)
+                hipLaunchKernelGGL((wino4_kernel<C, W::NGX, W::NGY, W::POOLK, 0, true>), dim3(per_xcd * 8), dim3(512), 0, stream, a);
+            else
+                hipLaunchKernelGGL((wino4_kernel<C, W::NGX, W::NGY, 0, 0, true>), dim3(per_xcd * 8), dim3(512), 0, stream, a);
+            EEM_HIP_CHECK(hipGetLastError());
+            EEM_NOTE_VARIANT(1);
+            return EEM_OK;
+        }
+    }
     if (a.pool_partial != nullptr && a.no_store && C == 64)
         hipLaunchKernelGGL((wino4_kernel<C, W::NGX, W::NGY, W::POOLK, (C == 64 ? 3 : 0)>), dim3(per_xcd * 8), dim3(512), 0, stream, a);
     else if (a.pool_partial != nullptr)
@@ -548,7 +761,7 @@ extern "C" __attribute__((visibility("default"))) int eemflow_debug_read_stamps4
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps4), n * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
 }
 extern "C" __attribute__((visibility("default"))) int eemflow_debug_clear_stamps4() {
-    static unsigned long long zero[1024 * 8 * 64];
+    static unsigned long long zero[1024 * 8 * 128];
     return hipMemcpyToSymbol(HIP_SYMBOL(g_stamps4), zero, sizeof zero) == hipSuccess ? 0 : 2;
 }
 #endif

@@ -259,7 +259,7 @@ struct Hook {
             // instead - its inputs then come from whatever cache the repetition before left them in, which at one frame per launch is
             // where the launch before it in the chain leaves them too)
             if (evs.size() < 2) { evs.resize(2, nullptr); EEM_HIP_CHECK(hipEventCreate(&evs[0])); EEM_HIP_CHECK(hipEventCreate(&evs[1])); }
-            eem_last_grid_blocks = eem_last_grid_threads = eem_last_pipe = 0;
+            eem_last_grid_blocks = eem_last_grid_threads = eem_last_pipe = eem_last_variant = 0;
             int rc = launch(st);
             if (rc != EEM_OK) return rc;
             EEM_HIP_CHECK(hipEventRecord(evs[0], st));
@@ -274,7 +274,7 @@ struct Hook {
             strncpy(ks.name, name, sizeof(ks.name) - 1);
             ks.flops = flops; ks.bytes = bytes; ks.ms = ms;      // (divided by reps by the caller, like the chain form's sums)
             ks.blocks = eem_last_grid_blocks;
-            ks.pipe = eem_last_pipe;
+            ks.pipe = eem_last_pipe; ks.reserved = eem_last_variant;
             stats.push_back(ks);
             return EEM_OK;
         }
@@ -283,7 +283,7 @@ struct Hook {
             EEM_HIP_CHECK(hipEventCreate(&evs[2 * slot]));
             EEM_HIP_CHECK(hipEventCreate(&evs[2 * slot + 1]));
         }
-        eem_last_grid_blocks = eem_last_grid_threads = eem_last_pipe = 0;
+        eem_last_grid_blocks = eem_last_grid_threads = eem_last_pipe = eem_last_variant = 0;
         EEM_HIP_CHECK(hipEventRecord(evs[2 * slot], st));
         const int rc = launch(st);
         if (rc != EEM_OK) return rc;
@@ -294,7 +294,7 @@ struct Hook {
             strncpy(ks.name, name, sizeof(ks.name) - 1);
             ks.flops = flops; ks.bytes = bytes; ks.ms = 0.f;
             ks.blocks = eem_last_grid_blocks;                     // 0: a launcher that does not report its grid
-            ks.pipe = eem_last_pipe;
+            ks.pipe = eem_last_pipe; ks.reserved = eem_last_variant;
             stats.push_back(ks);
         }
         ++slot;

@@ -28,6 +28,14 @@ bool dec_wnc_wanted(const eemflow_ctx* c, int gw, int batch) {
     if (c->dec_wnc == nullptr || gw % 4 != 0 || (e && e[0] == '0')) return false;
     return (e && e[0] == '1') || batch >= 4;
 }
+// The F(4x4) kernel's shared-V form (conv_wino4.hip: a tile group's input transform computed once instead of by each of its four
+// waves; bitwise the other form) for the 64-channel stride-1 layers of this forward - the only channel count whose LDS holds it.
+// EEM_W4_VSHARE: 0 never, 1 wherever the form is built, unset: the default - on (the two launches are 6 - 9 % shorter, +1.8 % on the
+// frame rate over six alternating pairs, docs/NOTEBOOK.md section 14).  Read per launch.
+static bool w4_vshare_wanted(int cin) {
+    const char* e = sw_raw<SW_EEM_W4_VSHARE>();
+    return cin == 64 && !(e && e[0] == '0');
+}
 // The tail head's LDS form (tail_fused.hip: every pooled value formed once per block, correlation and rconv operands from LDS) for
 // batched launches that are no stream call, where the launch supports the shapes (tail_head_lds_supported: the three stages' fused
 // partial sums, kTaps53 - the only list this schedule passes -, at most 240 cells), from four frames per launch on - the decoders' rule:
@@ -333,6 +341,7 @@ int run_enc_layer(eemflow_ctx* c, const Shape& s, int li, const float* e1, const
         a.io_frames = (sp.layer == ENC_1_1 && io != nullptr) ? c->cur_io_frames : 0;
         a.in_norm = (sp.layer == ENC_1_1 && c->deferred_norm && prepadded == nullptr) ? 1 : 0;
         a.no_store = 0;
+        a.vshare = w4_vshare_wanted(d.cin) ? 1 : 0;
         enc_walk(c, s, sp.layer, a);
         for (int k = 0; k < 3; ++k)
             if (s.fuse[k] && sp.layer == (k == 0 ? ENC_1_2 : k == 1 ? ENC_2_3 : ENC_3_3)) {

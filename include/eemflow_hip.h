@@ -171,7 +171,8 @@ typedef struct eemflow_kernel_stat {
                         so blocks < 256 means the launch occupies that many of the 256 CUs */
     int pipe;        /* matrix pipe of the launch's contraction: 0 = fp32 MFMA, 1 = fp32 products as six bf16-piece MFMAs (conv_bx3.hip),
                         2 = Winograd F(4x4,3x3) on the fp32 MFMA (a quarter of the direct form's multiplies), 3 = F(2x2,3x3) (1 / 2.25) */
-    int reserved;
+    int reserved;    /* the launcher's tag for the instantiation it chose, 0 where it has none (the 64-channel F(4x4) layers: 1 = the
+                        shared-V form of conv_wino4.hip) */
 } eemflow_kernel_stat;
 int eemflow_time_kernels(eemflow_ctx* ctx, const float* events1, const float* events2, int batch, int in_h,
                          int in_w, float* flow_out, int out_h, int out_w, int reps, eemflow_kernel_stat* stats,
