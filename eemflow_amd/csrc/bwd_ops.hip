@@ -58,15 +58,19 @@ __global__ __launch_bounds__(256) void lookup_bwd_kernel(LookupBwdArgs a) {
 // <= 4 taps whose bilinear corners fall on the cell - plain read-modify-writes (no two threads share a cell), 10 consecutive floats
 // per thread, and dout read as full-width runs over p (the scatter form issues 4 atomics per (tap, pixel), each on another map:
 // 25 M atomics on distinct lines per call at batch 4, 0.95 ms).  A tap's corner and weight are evaluated with lookup_tiled_kernel's own
-// arithmetic; only a corner that rounding moved by one cell beside an (almost) integer coordinate is not found - its weight is ~1e-7.
+// arithmetic.  Beside an (almost) integer coordinate the round trip through the normalised position moves a tap's floor by one cell
+// relative to the first tap's (E-RAFT's first iteration samples at exactly integer coordinates), so a window row looks for its cell
+// among the corners of FOUR taps, jj in [r - 2, r + 1] (and a cell among four columns' taps), and the window has an eleventh row and
+// column for the last tap's second corner when its floor moved up: ten rows serving only the taps {r - 1, r} lost the moved
+// corners - up to 7e-7 |dout| in a cell, 23 times its rounding bound (tests/test_fp64_bounds_opsbwd.py).
 __global__ __launch_bounds__(256) void lookup_bwd_rows_kernel(LookupBwdArgs a) {
     const int hw = a.h * a.w;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)a.batch * 40 * hw) return;
+    if (idx >= (long)a.batch * 44 * hw) return;
     const int p = idx % hw;
-    const int r = (idx / hw) % 10;
-    const int lvl = (idx / ((long)hw * 10)) % 4;
-    const int b = idx / ((long)hw * 40);
+    const int r = (idx / hw) % 11;
+    const int lvl = (idx / ((long)hw * 11)) % 4;
+    const int b = idx / ((long)hw * 44);
     const float cx = a.coords[((size_t)b * 2 + 0) * hw + p], cy = a.coords[((size_t)b * 2 + 1) * hw + p];
     const float sc = (float)(1 << lvl);
     const int h = a.ph[lvl], w = a.pw[lvl];
@@ -86,10 +90,10 @@ __global__ __launch_bounds__(256) void lookup_bwd_rows_kernel(LookupBwdArgs a) {
     tap(cy, sc, 0, h, yb, tyb);
     const int Y = yb + r;
     if (Y < 0 || Y >= h) return;
-    float wy[2]; int jy[2];
+    float wy[4]; int jy[4];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int jj = r - 1 + q;
+    for (int q = 0; q < 4; ++q) {
+        const int jj = r - 2 + q;
         jy[q] = jj;
         wy[q] = 0.f;
         if (jj >= 0 && jj <= 8) {
@@ -103,33 +107,35 @@ __global__ __launch_bounds__(256) void lookup_bwd_rows_kernel(LookupBwdArgs a) {
     for (int i = 0; i < 9; ++i) tap(cx, sc, i, w, x0[i], tx[i]);
     const float* dch = a.dout + ((size_t)b * 324 + lvl * 81) * hw + p;
     float* row = a.dpyr[lvl] + ((size_t)b * hw + p) * h * w + (size_t)Y * w;
-    // dout of the two candidate rows for every x tap: d[q][i]
+    // dout of the four candidate rows for every x tap, weighted and summed: ds[i]
     // (every load unconditional, from a clamped index: a load inside a lane-dependent branch is followed by the compiler's
     // s_waitcnt vmcnt(0) - eighteen dout reads and ten read-modify-writes were 28 dependent round trips per thread)
-    float d[2][9];
+    float ds[9];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int i = 0; i < 9; ++i) ds[i] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
         const int jc = min(max(jy[q], 0), 8);
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             const float v = dch[(size_t)(i * 9 + jc) * hw];
-            d[q][i] = (wy[q] != 0.f) ? v * wy[q] : 0.f;
+            ds[i] += (wy[q] != 0.f) ? v * wy[q] : 0.f;
         }
     }
     const int xb = x0[0];
-    float old[10];
+    float old[11];
 #pragma unroll
-    for (int c = 0; c < 10; ++c) old[c] = row[min(max(xb + c, 0), w - 1)];
+    for (int c = 0; c < 11; ++c) old[c] = row[min(max(xb + c, 0), w - 1)];
 #pragma unroll
-    for (int c = 0; c < 10; ++c) {
+    for (int c = 0; c < 11; ++c) {
         const int X = xb + c;
         float sum = 0.f;
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = c - 1 + q;
+        for (int q = 0; q < 4; ++q) {
+            const int i = c - 2 + q;
             if (i < 0 || i > 8) continue;
             const float wx = x0[i] == X ? 1.f - tx[i] : (x0[i] + 1 == X ? tx[i] : 0.f);
-            sum += wx * (d[0][i] + d[1][i]);
+            sum += wx * ds[i];
         }
         if (X >= 0 && X < w) row[X] = old[c] + sum;
     }
@@ -349,8 +355,9 @@ extern "C" int eraft_corr_lookup_bwd(const float* coords, const float* dout, int
         ph /= 2; pw /= 2;
     }
     a.coords = coords; a.dout = dout; a.batch = batch; a.h = h; a.w = w;
+    eem_op_form = sw_on<SW_EEM_LOOKUP_BWD_SCATTER>() ? "lookup_bwd_scatter" : "lookup_bwd_rows";
     if (sw_on<SW_EEM_LOOKUP_BWD_SCATTER>()) hipLaunchKernelGGL(lookup_bwd_kernel, dim3(nblocks((long)batch * 324 * h * w)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(lookup_bwd_rows_kernel, dim3(nblocks((long)batch * 40 * h * w)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(lookup_bwd_rows_kernel, dim3(nblocks((long)batch * 44 * h * w)), dim3(256), 0, st, a);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -361,6 +368,8 @@ extern "C" int eraft_corr_pyramid_bwd(const float* fmap1, const float* fmap2, fl
     EEM_REQUIRE(fmap1 && fmap2 && dpyr0 && dpyr1 && dpyr2 && dpyr3 && dfmap1 && dfmap2, "eraft_corr_pyramid_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const int hw = h * w;
+    // refused before anything is launched: the pooling chain below folds dpyr3..1 into dpyr2..0 in place
+    EEM_REQUIRE((hw & 3) == 0, "eraft_corr_pyramid_bwd: h*w must be a multiple of 4 (16-byte rows)");
     const long planes = (long)batch * hw;
     // avg_pool2d chain (model/corr.py:24-27): level 3 -> 2 -> 1 -> 0, accumulated in place
     const int hs[4] = {h, h / 2, h / 4, h / 8}, ws[4] = {w, w / 2, w / 4, w / 8};
@@ -375,13 +384,9 @@ extern "C" int eraft_corr_pyramid_bwd(const float* fmap1, const float* fmap2, fl
     const float scale = 1.0f / sqrtf((float)c);
     dim3 grid(ceil_div(hw, 128), ceil_div(c, 64), batch);
     // d fmap1[c][p1] = scale * sum_p2 dcorr[p1][p2] fmap2[c][p2];   d fmap2[c][p2] = scale * sum_p1 dcorr[p1][p2] fmap1[c][p1]
-    if ((hw & 3) == 0) {
-        hipLaunchKernelGGL((allpairs_bwd_kernel<true>), grid, dim3(256), 0, st, fmap2, dpyr0, dfmap1, c, hw, scale);
-        hipLaunchKernelGGL((allpairs_bwd_kernel<false>), grid, dim3(256), 0, st, fmap1, dpyr0, dfmap2, c, hw, scale);
-    } else {
-        eem_set_error("eraft_corr_pyramid_bwd: h*w must be a multiple of 4 (16-byte rows)");
-        return EEM_ERR_ARG;
-    }
+    eem_op_form = "allpairs_bwd";
+    hipLaunchKernelGGL((allpairs_bwd_kernel<true>), grid, dim3(256), 0, st, fmap2, dpyr0, dfmap1, c, hw, scale);
+    hipLaunchKernelGGL((allpairs_bwd_kernel<false>), grid, dim3(256), 0, st, fmap1, dpyr0, dfmap2, c, hw, scale);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
@@ -391,6 +396,7 @@ extern "C" int eraft_convex_upsample_bwd(const float* flow, const float* mask, c
     EEM_REQUIRE(flow && mask && dout && dflow && dmask && batch >= 1 && h >= 1 && w >= 1, "eraft_convex_upsample_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     EEM_HIP_CHECK(hipMemsetAsync(dflow, 0, (size_t)batch * 2 * h * w * sizeof(float), st));
+    eem_op_form = "convex_up_bwd";
     hipLaunchKernelGGL(convex_up_bwd_kernel, dim3(nblocks((long)batch * 8 * h * w)), dim3(256), 0, st, flow, mask, dout, dflow, dmask,
                        batch, h, w);
     EEM_HIP_CHECK(hipGetLastError());
@@ -403,6 +409,8 @@ extern "C" int eemplus_warp_bwd(const float* x, const float* flow, const float* 
                 "eemplus_warp_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     EEM_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)batch * c * h * w * sizeof(float), st));
+    static const char* const names[3] = {"warp_bwd_m0", "warp_bwd_m1", "warp_bwd_m2"};
+    eem_op_form = names[mode];
     hipLaunchKernelGGL(warp_bwd_kernel, dim3(nblocks((long)batch * h * w)), dim3(256), 0, st, x, flow, dout, dx, dflow, batch, c, h, w, mode);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

@@ -32,6 +32,9 @@ extern thread_local const char* eem_conv_form;
 // tail_conv_launch puts its job count beside the name, in eem_launch_jobs; eemplus_record_stages files "<name>_j<jobs>" for it.
 extern thread_local const char* eem_launch_form;
 extern thread_local int eem_launch_jobs;
+// ... and of this thread's last non-convolution operator launch (the eemop_* entry points of ops.hip that launch a kernel of their own
+// and the four backward entry points of bwd_ops.hip; eemop_last_op_form reports it)
+extern thread_local const char* eem_op_form;
 
 #define EEM_HIP_CHECK(expr)                                                            \
     do {                                                                               \

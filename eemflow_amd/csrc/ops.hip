@@ -143,7 +143,11 @@ __global__ __launch_bounds__(256) void pool2_bwd_kernel(const float* __restrict_
 }
 
 // F.interpolate(bilinear, align_corners=True) of [nc][h][w] -> [nc][oh][ow] and its adjoint (dx zeroed by the caller, atomics)
+// Contraction is off in here: fused, ly = fy - y0 is formed from the UNROUNDED product sy * Y - off by up to half an ulp of the source
+// coordinate from the fraction F.interpolate (and upflow_px of the forward path) blends with, 48 roundings of the blend's own sum on a
+// 6x8 -> 48x64 upsampling (tests/test_gpu_opsbwd_fp64.py).
 __device__ __forceinline__ void ac_taps(int Y, int X, int h, int w, int oh, int ow, int& y0, int& y1, int& x0, int& x1, float& ly, float& lx) {
+#pragma clang fp contract(off)
     const float sy = oh > 1 ? (float)(h - 1) / (float)(oh - 1) : 0.f, sx = ow > 1 ? (float)(w - 1) / (float)(ow - 1) : 0.f;
     const float fy = sy * (float)Y, fx = sx * (float)X;
     y0 = (int)fy; x0 = (int)fx;
@@ -629,6 +633,14 @@ extern "C" int eemop_pack_forget(long long token) {
 }
 
 // ================================================================================================ convolution
+thread_local const char* eem_op_form = "";
+
+extern "C" int eemop_last_op_form(char* buf, int cap) {
+    EEM_REQUIRE(buf && cap >= 1, "eemop_last_op_form: bad arguments");
+    snprintf(buf, (size_t)cap, "%s", eem_op_form);
+    return EEM_OK;
+}
+
 extern "C" int eemop_last_conv_form(char* buf, int cap) {
     EEM_REQUIRE(buf && cap >= 1, "eemop_last_conv_form: bad arguments");
     snprintf(buf, (size_t)cap, "%s", eem_conv_form);
@@ -802,6 +814,7 @@ extern "C" int eemop_conv2d_bwd_weight_cat(const float* x0, int c0, const float*
 extern "C" int eemop_act_bwd(const float* dy, const float* y, long long n, int kind, float scale, float* out, void* stream) {
     EEM_REQUIRE(dy && y && out && n >= 0, "eemop_act_bwd: bad arguments");
     if (n == 0) return EEM_OK;
+    eem_op_form = "act_bwd";
     hipLaunchKernelGGL(act_bwd_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dy, y, out, (long)n, kind, scale);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -810,6 +823,7 @@ extern "C" int eemop_act_bwd(const float* dy, const float* y, long long n, int k
 extern "C" int eemop_binary(int kind, const float* a, const float* b, float alpha, long long n, float* out, void* stream) {
     EEM_REQUIRE(a && out && (b || kind == 4) && kind >= 0 && kind <= 4, "eemop_binary: bad arguments");
     if (n == 0) return EEM_OK;
+    eem_op_form = "binary";
     hipLaunchKernelGGL(binary_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long)n, kind, alpha);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -827,13 +841,16 @@ extern "C" int eemop_sum_n(const float* const* in, int count, long long n, float
     }
     a.n = count;
     const long n4 = aligned ? (long)(n / 4) : 0;
+    eem_op_form = aligned ? "sum_n_v4" : "sum_n_scalar";
     hipLaunchKernelGGL(sum_n_kernel, dim3(nblk(n4 + 1)), dim3(256), 0, (hipStream_t)stream, a, out, n4, (long)n);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 extern "C" int eemop_gru_blend(const float* z, const float* h, const float* q, long long n, float* out, void* stream) {
-    EEM_REQUIRE(z && h && q && out, "eemop_gru_blend: NULL argument");
+    EEM_REQUIRE(z && h && q && out && n >= 0, "eemop_gru_blend: bad arguments");
+    if (n == 0) return EEM_OK;
+    eem_op_form = "gru_blend";
     hipLaunchKernelGGL(gru_blend_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, z, h, q, out, (long)n);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -841,7 +858,9 @@ extern "C" int eemop_gru_blend(const float* z, const float* h, const float* q, l
 
 extern "C" int eemop_gru_blend_bwd(const float* dout, const float* z, const float* h, const float* q, long long n, float* dz, float* dh,
                                    float* dq, void* stream) {
-    EEM_REQUIRE(dout && z && h && q && dz && dh && dq, "eemop_gru_blend_bwd: NULL argument");
+    EEM_REQUIRE(dout && z && h && q && dz && dh && dq && n >= 0, "eemop_gru_blend_bwd: bad arguments");
+    if (n == 0) return EEM_OK;
+    eem_op_form = "gru_blend_bwd";
     hipLaunchKernelGGL(gru_blend_bwd_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dout, z, h, q, dz, dh, dq, (long)n);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -851,6 +870,7 @@ extern "C" int eemop_copy_channels(const float* src, int src_ctotal, int src_cof
                                    int hw, void* stream) {
     EEM_REQUIRE(src && dst && cc >= 1 && n >= 1 && hw >= 1, "eemop_copy_channels: bad arguments");
     const long total = (long)n * cc * hw;
+    eem_op_form = "copy_channels";
     hipLaunchKernelGGL(copy_channels_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, src, src_ctotal, src_coff, dst,
                        dst_ctotal, dst_coff, cc, hw, total);
     EEM_HIP_CHECK(hipGetLastError());
@@ -875,6 +895,8 @@ extern "C" int eemop_instnorm_fwd(const float* x, const float* res, int planes, 
 
 extern "C" int eemop_instnorm_bwd(const float* x, const float* y, const float* dy, int planes, int hw, int relu, float* dx, void* stream) {
     EEM_REQUIRE(x && y && dy && dx, "eemop_instnorm_bwd: NULL argument");
+    if (planes == 0 || hw == 0) return EEM_OK;
+    eem_op_form = hw >= 16384 ? "instnorm_bwd_t1024" : "instnorm_bwd_t256";
     hipLaunchKernelGGL(instnorm_bwd_kernel, dim3(planes), dim3(hw >= 16384 ? 1024 : 256), 0, (hipStream_t)stream, x, y, dy, dx, hw, relu, 1e-5f);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -884,6 +906,7 @@ extern "C" int eemop_batchnorm_train_fwd(const float* x, const float* weight, co
                                          int n, int c, int hw, float momentum, float eps, int relu, float* y, float* save_mean,
                                          float* save_rstd, void* stream) {
     EEM_REQUIRE(x && weight && bias && running_mean && running_var && y && save_mean && save_rstd, "eemop_batchnorm_train_fwd: NULL argument");
+    eem_op_form = (long)n * hw >= 16384 ? "bn_train_fwd_t1024" : "bn_train_fwd_t256";
     hipLaunchKernelGGL(bn_train_fwd_kernel, dim3(c), dim3((long)n * hw >= 16384 ? 1024 : 256), 0, (hipStream_t)stream, x, weight, bias, running_mean, running_var, y,
                        save_mean, save_rstd, n, c, hw, momentum, eps, relu);
     EEM_HIP_CHECK(hipGetLastError());
@@ -894,6 +917,7 @@ extern "C" int eemop_batchnorm_train_bwd(const float* x, const float* y, const f
                                          const float* save_rstd, int n, int c, int hw, int relu, float* dx, float* dweight, float* dbias,
                                          void* stream) {
     EEM_REQUIRE(x && y && dy && weight && save_mean && save_rstd && dx && dweight && dbias, "eemop_batchnorm_train_bwd: NULL argument");
+    eem_op_form = (long)n * hw >= 16384 ? "bn_train_bwd_t1024" : "bn_train_bwd_t256";
     hipLaunchKernelGGL(bn_train_bwd_kernel, dim3(c), dim3((long)n * hw >= 16384 ? 1024 : 256), 0, (hipStream_t)stream, x, y, dy, weight, save_mean, save_rstd, dx, dweight,
                        dbias, n, c, hw, relu);
     EEM_HIP_CHECK(hipGetLastError());
@@ -904,6 +928,7 @@ extern "C" int eemop_batchnorm_eval_fwd(const float* x, const float* weight, con
                                         const float* running_var, int n, int c, int hw, float eps, int relu, float* y, void* stream) {
     EEM_REQUIRE(x && weight && bias && running_mean && running_var && y, "eemop_batchnorm_eval_fwd: NULL argument");
     EEM_REQUIRE(n >= 1 && c >= 1 && hw >= 1, "eemop_batchnorm_eval_fwd: bad sizes");
+    eem_op_form = (long)n * hw >= 16384 ? "bn_eval_fwd_t1024" : "bn_eval_fwd_t256";
     hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(c), dim3((long)n * hw >= 16384 ? 1024 : 256), 0, (hipStream_t)stream, x, weight, bias, running_mean,
                        running_var, y, n, c, hw, eps, relu);
     EEM_HIP_CHECK(hipGetLastError());
@@ -914,6 +939,7 @@ extern "C" int eemop_batchnorm_eval_bwd(const float* x, const float* y, const fl
                                         const float* running_var, int n, int c, int hw, float eps, int relu, float* dx, float* dweight,
                                         float* dbias, void* stream) {
     EEM_REQUIRE(x && y && dy && weight && running_mean && running_var && dx && dweight && dbias, "eemop_batchnorm_eval_bwd: NULL argument");
+    eem_op_form = (long)n * hw >= 16384 ? "bn_eval_bwd_t1024" : "bn_eval_bwd_t256";
     hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(c), dim3((long)n * hw >= 16384 ? 1024 : 256), 0, (hipStream_t)stream, x, y, dy, weight, running_mean,
                        running_var, dx, dweight, dbias, n, c, hw, eps, relu);
     EEM_HIP_CHECK(hipGetLastError());
@@ -957,22 +983,27 @@ extern "C" int eemop_convex_upsample_fwd(const float* zeros, const float* flow, 
 extern "C" int eemop_act_fwd(const float* x, long long n, int kind, float* out, void* stream) {
     EEM_REQUIRE(x && out && n >= 0, "eemop_act_fwd: bad arguments");
     if (n == 0) return EEM_OK;
+    eem_op_form = "act_fwd";
     hipLaunchKernelGGL(act_fwd_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, out, (long)n, kind);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 extern "C" int eemop_shuffle_channels(const float* src, float* dst, int n, int c, int groups, int hw, int inverse, void* stream) {
-    EEM_REQUIRE(src && dst && groups >= 1 && c % groups == 0, "eemop_shuffle_channels: bad arguments");
+    EEM_REQUIRE(src && dst && groups >= 1 && c % groups == 0 && n >= 0 && c >= 0 && hw >= 0, "eemop_shuffle_channels: bad arguments");
     const long total = (long)n * c * hw;
+    if (total == 0) return EEM_OK;
+    eem_op_form = "shuffle";
     hipLaunchKernelGGL(shuffle_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, src, dst, c, groups, hw, total, inverse);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 extern "C" int eemop_scale_flow(const float* x, int n, int hw, float su, float sv, float* out, void* stream) {
-    EEM_REQUIRE(x && out, "eemop_scale_flow: NULL argument");
+    EEM_REQUIRE(x && out && n >= 0 && hw >= 0, "eemop_scale_flow: bad arguments");
     const long total = (long)n * 2 * hw;
+    if (total == 0) return EEM_OK;
+    eem_op_form = "scale_flow";
     hipLaunchKernelGGL(scale_flow2_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, out, hw, total, su, sv);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
@@ -984,32 +1015,43 @@ extern "C" int eemop_pool2_fwd(const float* x, float* out, long long planes, int
 }
 
 extern "C" int eemop_pool2_bwd(const float* dy, float* dx, long long planes, int h, int w, void* stream) {
-    EEM_REQUIRE(dy && dx, "eemop_pool2_bwd: NULL argument");
+    EEM_REQUIRE(dy && dx && planes >= 0 && h >= 0 && w >= 0, "eemop_pool2_bwd: bad arguments");
     const long total = (long)planes * h * w;
+    if (total == 0) return EEM_OK;
+    eem_op_form = "pool2_bwd";
     hipLaunchKernelGGL(pool2_bwd_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, h, w, total);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 extern "C" int eemop_resize_ac_fwd(const float* in, float* out, int nc, int h, int w, int oh, int ow, void* stream) {
-    EEM_REQUIRE(in && out && nc >= 1, "eemop_resize_ac_fwd: bad arguments");
+    EEM_REQUIRE(in && out && nc >= 0 && h >= 1 && w >= 1 && oh >= 0 && ow >= 0, "eemop_resize_ac_fwd: bad arguments");
     const long total = (long)nc * oh * ow;
+    if (total == 0) return EEM_OK;
+    eem_op_form = "resize_ac";
     hipLaunchKernelGGL(resize_ac_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, in, out, h, w, oh, ow, total);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;
 }
 
 extern "C" int eemop_resize_ac_bwd(const float* dout, float* dx, int nc, int h, int w, int oh, int ow, void* stream) {
-    EEM_REQUIRE(dout && dx && nc >= 1, "eemop_resize_ac_bwd: bad arguments");
+    EEM_REQUIRE(dout && dx && nc >= 0 && h >= 1 && w >= 1 && oh >= 0 && ow >= 0, "eemop_resize_ac_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
+    if (nc == 0) return EEM_OK;
+    if ((long)oh * ow == 0) {                                  // no output pixel: the adjoint of nothing is zero
+        EEM_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)nc * h * w * sizeof(float), st));
+        return EEM_OK;
+    }
     if (!sw_on<SW_EEM_RESIZE_BWD_SCATTER>()) {
         const long npix = (long)nc * h * w;
+        eem_op_form = "resize_ac_bwd_gather";
         hipLaunchKernelGGL(resize_ac_bwd_gather_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, st, dout, dx, h, w, oh, ow, npix);
         EEM_HIP_CHECK(hipGetLastError());
         return EEM_OK;
     }
     EEM_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)nc * h * w * sizeof(float), st));
     const long total = (long)nc * oh * ow;
+    eem_op_form = "resize_ac_bwd_scatter";
     hipLaunchKernelGGL(resize_ac_bwd_kernel, dim3(nblk(total)), dim3(256), 0, st, dout, dx, h, w, oh, ow, total);
     EEM_HIP_CHECK(hipGetLastError());
     return EEM_OK;

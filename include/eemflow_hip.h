@@ -821,6 +821,13 @@ int eemop_conv2d_bwd_weight_cat(const float* x0, int c0, const float* x1, int c1
  * "fewout_k8_c4", "stem7_c5", "dgrad_s2w_128_3x3", "wgrad_enc_bx3_tw16_c32_s2", "wgrad_generic_7x7_s2_bias"; a weight gradient served by
  * one launch per input segment reports the segments' names joined with '+'.  A host-side pointer store per launch; "" before any. */
 int eemop_last_conv_form(char* buf, int cap);
+/* TEST OBSERVABLE: the same for the non-convolution operators - the kernel (and launch form) that the calling thread's most recent
+ * eemop_* call of that kind, or eraft_corr_lookup_bwd / eraft_corr_pyramid_bwd / eraft_convex_upsample_bwd / eemplus_warp_bwd, launched:
+ * "instnorm_bwd_t256" / "_t1024", "bn_train_fwd_t256", ..., "lookup_bwd_rows" / "lookup_bwd_scatter", "allpairs_bwd", "convex_up_bwd",
+ * "warp_bwd_m0..2", "resize_ac", "resize_ac_bwd_gather" / "_scatter", "pool2_bwd", "act_fwd", "act_bwd", "binary", "sum_n_v4" /
+ * "sum_n_scalar", "gru_blend", "gru_blend_bwd", "copy_channels", "shuffle", "scale_flow".  A call that launches nothing (zero elements,
+ * refused arguments) leaves it as it was; the entry points that forward to an er_* launcher report through eraft_last_form. */
+int eemop_last_op_form(char* buf, int cap);
 /* out = scale * dy * act'(y) for y = act(pre): kind 1 ReLU, 2 sigmoid, 3 tanh, 0 identity.  Replaces: autograd of F.relu /
  * torch.sigmoid / torch.tanh (model/update.py:14,45-47,54-56,74-79,95; model/eraft.py:130-131) and of the 0.25 mask scale (:105). */
 int eemop_act_bwd(const float* dy, const float* y, long long n, int kind, float scale, float* out, void* stream);

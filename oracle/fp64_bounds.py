@@ -809,7 +809,7 @@ def pl_warp_taps(flow, mode):
     else:
         mask = torch.ones(b, h, w, dtype=torch.bool)
     assert all(t.dtype == torch.float32 for t in wts)
-    return {"w": wts, "y": ys, "x": xs, "ok": ok, "mask": mask}
+    return {"w": wts, "y": ys, "x": xs, "ok": ok, "mask": mask, "frac": (ww, wn)}
 
 
 def pl_warp_ref(x, flow, mode):
@@ -1009,3 +1009,635 @@ def pl_hostile_flows(h, w, seed, plain_only=True):
         new = torch.stack([r() for r in rules]).float()
         out = torch.where(bad[:, None], new, out)
     raise AssertionError("pl_hostile_flows: no build-independent draw found")
+
+
+# ------------------------------------------------------------- the non-convolution autograd kernels (ops.hip, bwd_ops.hip), call by call
+# tests/test_gpu_opsbwd_fp64.py and tests/test_fp64_bounds_opsbwd.py: every case makes ONE ABI call on the test's own inputs (ReLU gates from
+# the y passed in, the mode-2 warp mask from the GPU forward), asserts the form by eemop_last_op_form and holds each output to one of the
+# three criteria above; no limit is fitted to these kernels.  Geometry (floor, the bilinear fractions, ac_taps' sy * Y) is the operators'
+# definition and is taken in fp32 (er_lookup_geometry, pl_warp_taps, pl_upflow_geometry = ac_taps along one axis); all after it is fp64.
+OB_FORMS = {"instnorm_bwd_t256", "instnorm_bwd_t1024", "lookup_bwd_rows", "lookup_bwd_scatter", "allpairs_bwd", "convex_up_bwd",
+            "warp_bwd_m0", "warp_bwd_m1", "warp_bwd_m2", "resize_ac", "resize_ac_bwd_gather", "resize_ac_bwd_scatter", "pool2_bwd", "act_fwd",
+            "act_bwd", "binary", "sum_n_v4", "sum_n_scalar", "gru_blend", "gru_blend_bwd", "copy_channels", "shuffle", "scale_flow"}
+OB_FORMS |= {f"bn_{_k_}_{_t_}" for _k_ in ("train_fwd", "train_bwd", "eval_fwd", "eval_bwd") for _t_ in ("t256", "t1024")}
+
+F64 = 2.0 ** -29        # one fp64 rounding in units of u: a statistic accumulated in double over n values adds n * F64 to a count
+GACT_NONE, GACT_RELU, GACT_SIGMOID, GACT_TANH, GACT_LEAKY = 0, 1, 2, 3, 4
+
+# Criterion 2's counts for these kernels, as ER_ROUNDINGS counts (every fp32 operation one factor (1 + d), |d| <= u, relative to the sum
+# of |terms| = mag; a fused multiply-add only removes one; a product by 0, 1 or a power of two is exact):
+#   gru_blend      (1 - z) h + z q: 1 - z, its product, the sum                                                                    -> 3
+#   gru_dz         g (q - h): the difference, the product (mag |g| (|q| + |h|))                                                    -> 2
+#   gru_dh         g (1 - z): the difference, the product                                                                          -> 2
+#   gru_dq         g z                                                                                                             -> 1
+#   act_bwd_gate   dy d scale with d in {0, 1} (ReLU, identity): the product by d is exact, the one by scale rounds                 -> 1
+#   act_bwd_leaky  d in {1, 0.1f}: two products                                                                                    -> 2
+#   act_bwd_sigmoid  d = v (1 - v): 1 - v, v (1 - v), dy d, scale (mag |dy| |v| (1 + |v|) |scale|)                                  -> 4
+#   act_bwd_tanh   d = 1 - v v: v v, the difference, dy d, scale (mag |dy| (1 + v v) |scale|: the difference cancels near |v| = 1)    -> 4
+#   resize_ac      the four-term blend with lx, ly given: "upflow"'s count                                                         -> 6
+#   binary         a + b, a - b, a b, relu(a + b), alpha a: one operation                                                           -> 1
+#   sum_n          count - 1 sums (passed by the caller)
+#   bn_mean        (float) of the fp64 mean                                                              -> 1 + n F64
+#   bn_running     (1 - m) r + m s: 1 - m, its product, the sum | (float) s, its product, the sum       -> 3 + n F64
+#   bn_dbias       (float) of the fp64 sum of g                                                          -> 1 + n F64
+#   bn_dweight     (float) of the fp64 sum of g xhat, xhat = (x - mean) rstd in fp32 with mean, rstd given: two per term + the conversion -> 3 + n F64
+#   bn_eval_y      (x - mean) k + b with k = w / sqrtf(var + eps): sum, root, quotient, product, the difference, product, sum          -> 7
+#   bn_eval_dweight  the same with rstd = 1 / sqrtf(var + eps) formed in fp32 (sum, root, quotient)       -> 6 + n F64
+#   save_rstd is held to one conversion plus the fp64 statistic's own error carried through 1 / sqrt (ob_bn_train_fwd_ref's `extra`).
+# Scatter / gather adjoints: an element that receives N contributions of k roundings each is held to k + N - 1 (N counted per element by
+# the reference; the N - 1 sums in any order, atomics included).  k per contribution:
+#   lookup_bwd_scatter  g ((1 - tx)(1 - ty)): two differences, two products                                                        -> 4
+#   lookup_bwd_rows     wx (sum of v wy over the four candidate taps): 1 - ty, its product, three inner sums, 1 - tx, the outer product -> 7
+#   warp_dx        (dout m) w with the four weights and the mask given: one product                                                 -> 1
+#   resize_bwd_scatter  ((g (1 - ly)) (1 - lx)): two differences, two products                                                     -> 4
+#   resize_bwd_gather   (g wy) wx with wy = (1 - ly) + ly on the last row (two roundings), wx alike                                  -> 6
+#   pyr_pool       fine += 0.25 coarse: one sum per level, the coarser level's own error carried along: level 2 -> 1, 1 -> 2, 0 -> 3
+#   convex_dflow   a term 8 w_k dout with w_k the kernel's own softmax: exponent difference (|l_k - max| roundings of the exponent = that
+#                  many relative ones of exp), expf (2), the denominator (8 sums + its terms' 2 + sum w |l - max| <= 2 + 9 / e), the
+#                  quotient, the product: 18 + |l_k - max| per term, weighted term by term by the reference (ob_convex_up_bwd_ref)
+ER_ROUNDINGS.update({"gru_blend": 3, "gru_dz": 2, "gru_dh": 2, "gru_dq": 1, "act_bwd_gate": 1, "act_bwd_leaky": 2, "act_bwd_sigmoid": 4,
+                     "act_bwd_tanh": 4, "resize_ac": 6, "binary": 1, "bn_mean": 1, "bn_running": 3, "bn_dbias": 1, "bn_dweight": 3,
+                     "bn_eval_dweight": 6, "bn_eval_y": 7, "lookup_bwd_scatter": 4, "lookup_bwd_rows": 7, "warp_dx": 1, "resize_ac_bwd_scatter": 4,
+                     "resize_ac_bwd_gather": 6, "pool2_fwd": 3, "warp_fwd": 4, "lookup_fwd": 7})
+CONVEX_K = 18.0
+TINY = 1e-37            # results beneath fp32's normal range are not rounded relatively
+
+
+def bound_counted(mag, k, extra=None):
+    """The absolute bound of criterion 2 per element: k u mag (k a number or a tensor) + extra."""
+    b = torch.as_tensor(k, dtype=torch.float64) * U * mag * ER_SLACK + TINY
+    return b + extra if extra is not None else b
+
+
+def check_counted(name, got, ref, mag, k, form, extra=None):
+    """Criterion 2 with a count per element: |got - ref| <= k u mag (+ extra, an absolute allowance per element) everywhere."""
+    g = _d(got)
+    if g.shape != ref.shape:
+        raise StageError(f"{name} [{form}]: shape {tuple(g.shape)} against the reference's {tuple(ref.shape)}")
+    d = (g - ref).abs()
+    bound = bound_counted(mag, k, extra).expand_as(ref)
+    bad = ~(d <= bound)
+    pos = mag > 0
+    z = torch.where(pos, d / (U * mag.clamp_min(1e-300)), torch.zeros_like(d))
+    ratio = d / bound
+    rec = {"name": name, "form": form, "max_z": float(z.max()) if z.numel() else 0.0, "rms_z": float(z.pow(2).mean().sqrt()) if z.numel() else 0.0,
+           "mean_z": 0.0, "slope_u": 0.0, "n": d.numel(), "of_bound": float(ratio.max()) if ratio.numel() else 0.0,
+           "k_max": float(torch.as_tensor(k, dtype=torch.float64).max())}
+    LOG.append(rec)
+    if bool(bad.any()):
+        w = int(torch.nonzero(bad.reshape(-1))[0]) if bool(torch.isnan(d).any()) else int((ratio.reshape(-1)).argmax())
+        raise StageError(f"{name} [{form}]: {int(bad.sum())} of {d.numel()} values are outside their counted bound; the worst at "
+                         f"{where(ref.shape, w)}: got {float(g.reshape(-1)[w]):.9g}, ref {float(ref.reshape(-1)[w]):.9g}, |diff| "
+                         f"{float(d.reshape(-1)[w]):.4g} against {float(bound.reshape(-1)[w]):.4g} (mag {float(mag.expand_as(ref).reshape(-1)[w]):.4g})")
+    return rec
+
+
+def check_adjoint(name, x, fx, g, ftg, bound_f, bound_ft, form):
+    """|<F x, g> - <x, F^T g>| for the GPU's own F x and F^T g, accumulated in fp64, within the summed rounding bounds of both sides."""
+    x, fx, g, ftg = _d(x), _d(fx), _d(g), _d(ftg)
+    lhs, rhs = float((fx * g).sum()), float((x * ftg).sum())
+    tol = float((g.abs() * bound_f).sum() + (x.abs() * bound_ft).sum())
+    LOG.append({"name": name, "form": form + ":adjoint", "of_bound": abs(lhs - rhs) / max(tol, 1e-300), "n": x.numel()})
+    if not abs(lhs - rhs) <= tol:
+        raise StageError(f"{name} [{form}]: <F x, g> = {lhs!r} against <x, F^T g> = {rhs!r}: |difference| {abs(lhs - rhs):.4g} > {tol:.4g}")
+
+
+def ulp32(v):
+    """Spacing of fp32 at |v| (towards larger magnitudes), as fp64."""
+    a = _f32(v).abs()
+    return (torch.nextafter(a, torch.tensor(float("inf"))) - a).double()
+
+
+# ---- elementwise
+def ob_gru_blend_ref(z, h, q):
+    z, h, q = _d(z), _d(h), _d(q)
+    return (1 - z) * h + z * q, (1 - z).abs() * h.abs() + z.abs() * q.abs()
+
+
+def ob_gru_blend_bwd_ref(g, z, h, q):
+    """{dz, dh, dq: (ref, mag, kind)}."""
+    g, z, h, q = _d(g), _d(z), _d(h), _d(q)
+    return {"dz": (g * (q - h), g.abs() * (q.abs() + h.abs()), "gru_dz"), "dh": (g * (1 - z), g.abs() * (1 - z).abs(), "gru_dh"),
+            "dq": (g * z, (g * z).abs(), "gru_dq")}
+
+
+def ob_act_bwd_ref(dy, y, kind, scale):
+    """scale * dy * act'(y) from the y passed in (ReLU / LeakyReLU: y > 0, so 0.0 and -0.0 are both closed) -> (ref, mag, kind of count)."""
+    dy, v = _d(dy), _d(y)
+    s = float(np.float32(scale))
+    one = torch.ones_like(v)
+    if kind == GACT_RELU:
+        d, m, kk = (v > 0).double(), (v > 0).double(), "act_bwd_gate"
+    elif kind == GACT_LEAKY:
+        d = torch.where(v > 0, one, LEAKY * one)
+        m, kk = d, "act_bwd_leaky"
+    elif kind == GACT_SIGMOID:
+        d, m, kk = v * (1 - v), v.abs() * (1 + v.abs()), "act_bwd_sigmoid"
+    elif kind == GACT_TANH:
+        d, m, kk = 1 - v * v, 1 + v * v, "act_bwd_tanh"
+    else:
+        d, m, kk = one, one, "act_bwd_gate"
+    return dy * d * s, dy.abs() * m * abs(s), kk
+
+
+def ob_binary_ref(kind, a, b, alpha):
+    a = _d(a)
+    if kind == 4:
+        s = float(np.float32(alpha))
+        return a * s, (a * s).abs()
+    b = _d(b)
+    ref = {0: a + b, 1: a - b, 2: a * b, 3: (a + b).clamp_min(0.0)}[kind]
+    return ref, (a * b).abs() if kind == 2 else a.abs() + b.abs()
+
+
+def ob_sum_ref(ts):
+    """(ref, mag, count - 1 sums)."""
+    ts = [_d(t) for t in ts]
+    return sum(ts), sum(t.abs() for t in ts), len(ts) - 1
+
+
+def ob_scale_flow_ref(x, su, sv):
+    x = _d(x)
+    s = torch.tensor([float(np.float32(su)), float(np.float32(sv))], dtype=torch.float64).view(1, 2, *([1] * (x.dim() - 2)))
+    return x * s, (x * s).abs()
+
+
+def ob_shuffle_ref(x, groups, inverse):
+    """channel_shuffle (EEMFlow+.py:52-58) by the oracle's own reshape; its inverse is the shuffle by c / groups."""
+    x = _f32(x)
+    y = O.channel_shuffle(x.reshape(*x.shape[:2], -1, 1), x.shape[1] // groups if inverse else groups)
+    return y.reshape(x.shape)
+
+
+# ---- F.interpolate(bilinear, align_corners=True) and its adjoint
+def ob_ac_taps(h, w, oh, ow):
+    """ac_taps of ops.hip for every output row and column, in fp32: (y0, y1, ly), (x0, x1, lx)."""
+    return pl_upflow_geometry(h, oh), pl_upflow_geometry(w, ow)
+
+
+def ob_resize_ref(x, out_hw):
+    return pl_upflow_ref(x, out_hw, rate=False)
+
+
+def _ac_matrix(n_in, n_out):
+    """[n_out, n_in] fp64 weights of one axis (l given in fp32) and the number of nonzero tap entries per cell."""
+    i0, i1, l = pl_upflow_geometry(n_in, n_out)
+    l = l.double()
+    wm = torch.zeros(n_out, n_in, dtype=torch.float64)
+    cm = torch.zeros(n_out, n_in, dtype=torch.float64)
+    r = torch.arange(n_out)
+    wm.index_put_((r, i0), 1 - l, accumulate=True)
+    wm.index_put_((r, i1), l, accumulate=True)
+    cm.index_put_((r, i0), (1 - l != 0).double(), accumulate=True)
+    cm.index_put_((r, i1), (l != 0).double(), accumulate=True)
+    return wm, cm
+
+
+def ob_resize_bwd_ref(dout, in_hw):
+    """Adjoint of the resize: (ref, mag, N) with N the number of (output, corner) contributions of nonzero weight per source pixel."""
+    d = _d(dout)
+    oh, ow = d.shape[-2:]
+    wy, cy = _ac_matrix(in_hw[0], oh)
+    wx, cx = _ac_matrix(in_hw[1], ow)
+    ref = torch.einsum("Yy,...YX,Xx->...yx", wy, d, wx)
+    mag = torch.einsum("Yy,...YX,Xx->...yx", wy, d.abs(), wx)
+    n = cy.sum(0).view(-1, 1) * cx.sum(0).view(1, -1)
+    return ref, mag, n.expand_as(ref)
+
+
+# ---- norms
+def _gate(dy, y, relu):
+    return dy * (y > 0).to(dy.dtype) if relu else dy
+
+
+def ob_instnorm_bwd_ref(x, y, dy, relu, dtype=torch.float64):
+    """InstanceNorm2d(affine=False, eps=1e-5) [+ ReLU] backward on [planes, hw]: dx = rstd (g - mean g - xhat mean(g xhat)), g = dy [y > 0],
+    the statistics (biased variance) recomputed from x.  dtype float32: the same expression evaluated by torch in fp32 on the CPU."""
+    x, y, dy = (torch.as_tensor(t).detach().cpu().to(dtype) for t in (x, y, dy))
+    m = x.mean(1, keepdim=True)
+    var = ((x - m) ** 2).mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + 1e-5)
+    g = _gate(dy, y, relu)
+    xh = (x - m) * rstd
+    return rstd * (g - g.mean(1, keepdim=True) - xh * (g * xh).mean(1, keepdim=True))
+
+
+def _bn_view(p, dtype):
+    return torch.as_tensor(p).detach().cpu().to(dtype).view(1, -1, 1)
+
+
+def ob_bn_train_fwd_ref(x, w, b, rm, rv, momentum, eps, relu):
+    """BatchNorm2d in training mode on x [n, c, hw]: {"y": fp64, "y32": torch's fp32 CPU evaluation of the same expression, and the
+    counted outputs save_mean / save_rstd / running_mean / running_var: (ref, mag, k, extra)}.  One value per channel (n * hw = 1) keeps
+    the biased variance for the running one, as the kernel documents."""
+    xd = _d(x)
+    n, c, hw = xd.shape
+    cnt = n * hw
+    mom, eps = float(np.float32(momentum)), float(np.float32(eps))
+    mean = xd.mean((0, 2))
+    var = ((xd - mean.view(1, -1, 1)) ** 2).mean((0, 2))
+    rstd = 1.0 / torch.sqrt(var + eps)
+    mabs = xd.abs().mean((0, 2))
+    mvar = (xd * xd).mean((0, 2)) + mabs * mabs                       # the terms of E x^2 - (E x)^2
+    ub = cnt / (cnt - 1.0) if cnt > 1 else 1.0
+    y = (xd - mean.view(1, -1, 1)) * rstd.view(1, -1, 1) * _bn_view(w, torch.float64) + _bn_view(b, torch.float64)
+    x32 = _f32(x)
+    m32 = x32.mean((0, 2), keepdim=True)
+    v32 = ((x32 - m32) ** 2).mean((0, 2), keepdim=True)
+    y32 = (x32 - m32) * (1.0 / torch.sqrt(v32 + eps)) * _bn_view(w, torch.float32) + _bn_view(b, torch.float32)
+    if relu:
+        y, y32 = y.clamp_min(0.0), y32.clamp_min(0.0)
+    nf = (cnt + 4) * F64
+    rstd_extra = 0.5 * rstd * ((cnt + 4) * 2.0 ** -53 * mvar) / (var + eps)
+    return {"y": y, "y32": y32,
+            "save_mean": (mean, mabs, ER_ROUNDINGS["bn_mean"] + nf, None),
+            "save_rstd": (rstd, rstd, 1.0, rstd_extra),
+            "running_mean": ((1 - mom) * _d(rm) + mom * mean, abs(1 - mom) * _d(rm).abs() + mom * mabs, ER_ROUNDINGS["bn_running"] + nf, None),
+            "running_var": ((1 - mom) * _d(rv) + mom * var * ub, abs(1 - mom) * _d(rv).abs() + mom * mvar * ub, ER_ROUNDINGS["bn_running"] + nf, None)}
+
+
+def _bn_bwd(x, y, dy, w, mean, rstd, relu, dtype, train):
+    x, y, dy = (torch.as_tensor(t).detach().cpu().to(dtype) for t in (x, y, dy))
+    w, mean, rstd = _bn_view(w, dtype), _bn_view(mean, dtype), _bn_view(rstd, dtype)
+    g = _gate(dy, y, relu)
+    xh = (x - mean) * rstd
+    sg, sgx = g.sum((0, 2)), (g * xh).sum((0, 2))
+    cnt = x.shape[0] * x.shape[2]
+    dx = w * rstd * (g - sg.view(1, -1, 1) / cnt - xh * sgx.view(1, -1, 1) / cnt) if train else g * (w * rstd)
+    return dx, sgx, sg, (g.abs() * xh.abs()).sum((0, 2)), g.abs().sum((0, 2))
+
+
+def ob_bn_train_bwd_ref(x, y, dy, w, save_mean, save_rstd, relu):
+    """{"dx", "dx32", "dweight": (ref, mag, k), "dbias": (ref, mag, k)} with the saved statistics as given."""
+    dx, dw, db, mw, mb = _bn_bwd(x, y, dy, w, save_mean, save_rstd, relu, torch.float64, True)
+    dx32 = _bn_bwd(x, y, dy, w, save_mean, save_rstd, relu, torch.float32, True)[0]
+    nf = (x.shape[0] * x.shape[2] + 4) * F64
+    return {"dx": dx, "dx32": dx32, "dweight": (dw, mw, ER_ROUNDINGS["bn_dweight"] + nf), "dbias": (db, mb, ER_ROUNDINGS["bn_dbias"] + nf)}
+
+
+def ob_bn_eval_fwd_ref(x, w, b, rm, rv, eps, relu, dtype=torch.float64):
+    x = torch.as_tensor(x).detach().cpu().to(dtype)
+    k = _bn_view(w, dtype) * (1.0 / torch.sqrt(_bn_view(rv, dtype) + float(np.float32(eps))))
+    y = (x - _bn_view(rm, dtype)) * k + _bn_view(b, dtype)
+    return y.clamp_min(0.0) if relu else y
+
+
+def ob_bn_eval_fwd_mag(x, w, b, rm, rv, eps):
+    """The sum of |terms| of the eval BatchNorm's output (ReLU never enlarges an error of its argument)."""
+    k = _bn_view(w, torch.float64) / torch.sqrt(_bn_view(rv, torch.float64) + float(np.float32(eps)))
+    return (_d(x) - _bn_view(rm, torch.float64)).abs() * k.abs() + _bn_view(b, torch.float64).abs()
+
+
+def ob_bn_eval_bwd_ref(x, y, dy, w, rm, rv, eps, relu):
+    e = float(np.float32(eps))
+    out = {}
+    for key, dt in (("", torch.float64), ("32", torch.float32)):
+        rstd = 1.0 / torch.sqrt(torch.as_tensor(rv).detach().cpu().to(dt) + e)
+        r = _bn_bwd(x, y, dy, w, rm, rstd, relu, dt, False)
+        out["dx" + key] = r[0]
+        if dt == torch.float64:
+            nf = (x.shape[0] * x.shape[2] + 4) * F64
+            out["dweight"] = (r[1], r[3], ER_ROUNDINGS["bn_eval_dweight"] + nf)
+            out["dbias"] = (r[2], r[4], ER_ROUNDINGS["bn_dbias"] + nf)
+    return out
+
+
+# ---- correlation lookup / pyramid
+def ob_lookup_bwd_ref(coords, dout, rows):
+    """Adjoint of the correlation lookup for dout [B, 324, H, W]: per level (ref, mag, N, allowance, cells) on [B * H * W, h_l, w_l].
+    N: the taps' corners of nonzero weight that land in the cell.  rows: the allowance of lookup_bwd_rows_kernel - a row / column of
+    its 11 x 11 window serves the taps jj in [r - 2, r + 1] of its offset r from the FIRST tap's corner, so a corner that rounding moved by
+    more than one cell relative to the first tap's would not be found: such a corner may lose |dout| ulp32(|ix|) (|iy|) in its cell.
+    `cells`: how many cells use it (none, on every input set of the tests: the round trip through the normalised position moves a floor
+    by at most one cell); `lost_over_ulp`: the largest lost weight in units of that ulp."""
+    b, _, hh, ww = coords.shape
+    n = b * hh * ww
+    d = _d(dout)
+    out = []
+    ph, pw = hh, ww
+    for l in range(4):
+        h, w = ph, pw
+        x0, y0, tx, ty = er_lookup_geometry(coords, l, (h, w))
+        ix, iy = x0.float() + tx, y0.float() + ty
+        txd, tyd = tx.double(), ty.double()
+        g = d[:, l * 81:(l + 1) * 81].permute(0, 2, 3, 1).reshape(n, 9, 9)
+        ref, mag, cnt, allow = (torch.zeros(n * h * w, dtype=torch.float64) for _ in range(4))
+        base = (torch.arange(n) * (h * w)).view(n, 1, 1)
+        ii = torch.arange(9).view(1, 9, 1)
+        jj = torch.arange(9).view(1, 1, 9)
+        yb = y0[:, :1, :1].clamp(-16, h + 16)
+        xb = x0[:, :1, :1].clamp(-16, w + 16)
+        worst = 0.0
+        for dy, dx, wy, wx in ((0, 0, 1 - tyd, 1 - txd), (0, 1, 1 - tyd, txd), (1, 0, tyd, 1 - txd), (1, 1, tyd, txd)):
+            yy, xx = y0 + dy, x0 + dx
+            ok = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+            at = (base + yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1))[ok]
+            wgt = wy * wx
+            ref.index_put_((at,), (g * wgt)[ok], accumulate=True)
+            mag.index_put_((at,), (g.abs() * wgt)[ok], accumulate=True)
+            cnt.index_put_((at,), (wgt != 0).double()[ok], accumulate=True)
+            if rows:
+                ry, rx = yy - yb - jj, xx - xb - ii
+                off_y, off_x = yy - yb, xx - xb
+                lost_y = ok & ~((ry >= -1) & (ry <= 2) & (off_y >= 0) & (off_y <= 10))
+                lost_x = ok & ~((rx >= -1) & (rx <= 2) & (off_x >= 0) & (off_x <= 10))
+                uy, ux = ulp32(iy), ulp32(ix)
+                a = g.abs() * (lost_y.double() * uy + lost_x.double() * ux)
+                allow.index_put_((at,), a[ok], accumulate=True)
+                for lost, wl, u in ((lost_y, wy, uy), (lost_x, wx, ux)):
+                    if bool(lost.any()):
+                        worst = max(worst, float((wl / u)[lost].max()))
+        out.append({"ref": ref.view(n, h, w), "mag": mag.view(n, h, w), "n": cnt.view(n, h, w), "allow": allow.view(n, h, w),
+                    "cells": int((allow > 0).sum()), "lost_over_ulp": worst})
+        ph, pw = ph // 2, pw // 2
+    return out
+
+
+def ob_lookup_bound(lv, form):
+    """The absolute bound of a level's cells under `form`: (k + N - 1) u mag + the rows form's allowance."""
+    k = ER_ROUNDINGS[form] + (lv["n"] - 1).clamp_min(0)
+    return k, (lv["allow"] if form == "lookup_bwd_rows" else None)
+
+
+def ob_allpairs_scale(c):
+    """1 / sqrt(C) as the fp32 number the launch multiplies by."""
+    return float(np.float32(1.0) / np.sqrt(np.float32(c)))
+
+
+def ob_pyramid_fold_ref(dpyr):
+    """The avg_pool2d chain's adjoint folded in place (model/corr.py:24-27): level l += 0.25 * repeat(level l + 1), from level 3 down:
+    [(ref, mag, k)] for levels 0, 1, 2 (dpyr[l]: [planes, h_l, w_l])."""
+    lv = [_d(p) for p in dpyr]
+    ref, mag = lv[3], lv[3].abs()
+    out = {}
+    for l in (2, 1, 0):
+        up, _ = pool_bwd_ref(ref[:, None], lv[l].shape[-2:], 2)
+        um, _ = pool_bwd_ref(mag[:, None], lv[l].shape[-2:], 2)
+        ref, mag = lv[l] + up[:, 0], lv[l].abs() + um[:, 0]
+        out[l] = (ref, mag, 3 - l)
+    return [out[0], out[1], out[2]]
+
+
+def ob_allpairs_bwd_ref(fmap1, fmap2, dcorr, scale=None):
+    """d fmap1[c, p1] = s sum_p2 dcorr[p1, p2] fmap2[c, p2], d fmap2[c, p2] = s sum_p1 dcorr[p1, p2] fmap1[c, p1] for dcorr [B * hw, h, w]
+    (the folded level 0 the call left): ((ref, mag), (ref, mag)) as [B, C, h, w]."""
+    f1, f2 = _d(fmap1), _d(fmap2)
+    b, c, h, w = f1.shape
+    hw = h * w
+    s = ob_allpairs_scale(c) if scale is None else scale
+    dc = _d(dcorr).reshape(b, hw, hw)
+    a1, a2 = f1.reshape(b, c, hw), f2.reshape(b, c, hw)
+    r1, m1 = torch.einsum("bpq,bcq->bcp", dc, a2) * s, torch.einsum("bpq,bcq->bcp", dc.abs(), a2.abs()) * s
+    r2, m2 = torch.einsum("bpq,bcp->bcq", dc, a1) * s, torch.einsum("bpq,bcp->bcq", dc.abs(), a1.abs()) * s
+    return (r1.reshape(b, c, h, w), m1.reshape(b, c, h, w)), (r2.reshape(b, c, h, w), m2.reshape(b, c, h, w))
+
+
+# ---- convex upsampling
+def _convex_fold(t, h, w):
+    """Adjoint of the 3 x 3 unfold: t [B, C, 9, h, w] (neighbour k of centre (y, x)) summed onto the neighbour's own position."""
+    out = torch.zeros(t.shape[0], t.shape[1], h, w, dtype=t.dtype)
+    for k in range(9):
+        dy, dx = k // 3 - 1, k % 3 - 1
+        ys, ye, xs, xe = max(0, -dy), min(h, h - dy), max(0, -dx), min(w, w - dx)
+        if ys < ye and xs < xe:
+            out[:, :, ys + dy:ye + dy, xs + dx:xe + dx] += t[:, :, k, ys:ye, xs:xe]
+    return out
+
+
+def ob_convex_weights(mask):
+    """softmax over the nine neighbours in fp64 and each weight's count of roundings: w, kt [B, 9, 8, 8, h, w]."""
+    m = _d(mask)
+    b, _, h, w = m.shape
+    lg = m.view(b, 9, 8, 8, h, w)
+    mx = lg.max(1, keepdim=True).values
+    return torch.softmax(lg, 1), CONVEX_K + (lg - mx).abs()
+
+
+def ob_convex_up_bwd_ref(flow, mask, dout):
+    """ERAFT.upsample_flow's backward: {"dflow": (ref, bound), "dmask", "dmask32"}.  dflow's bound: every term 8 w_k dout at its own count
+    (CONVEX_K + |l_k - max|) plus N - 1 sums, N = 64 per neighbour inside the map; dmask and dmask32 by autograd of the oracle's
+    convex_upsample in fp64 and in fp32."""
+    out = {}
+    for key, dt in (("", torch.float64), ("32", torch.float32)):
+        f = torch.as_tensor(flow).detach().cpu().to(dt).requires_grad_(True)
+        m = torch.as_tensor(mask).detach().cpu().to(dt).requires_grad_(True)
+        df, dm = torch.autograd.grad(R.convex_upsample(f, m), (f, m), torch.as_tensor(dout).detach().cpu().to(dt))
+        out["dflow" + key], out["dmask" + key] = df, dm
+    b, _, h, w = flow.shape
+    wk, kt = ob_convex_weights(mask)
+    d = _d(dout).view(b, 2, h, 8, w, 8).permute(0, 1, 3, 5, 2, 4)                     # [B, 2, sy, sx, h, w]
+    term = 8.0 * wk[:, None] * d[:, :, None].abs()                                      # [B, 2, 9, sy, sx, h, w]
+    mag = _convex_fold(term.sum((3, 4)), h, w)
+    kw = _convex_fold((term * kt[:, None]).sum((3, 4)), h, w)
+    n = _convex_fold(torch.full((b, 2, 9, h, w), 64.0, dtype=torch.float64), h, w)
+    out["dflow"] = (out["dflow"], U * ER_SLACK * (kw + (n - 1) * mag) + TINY)
+    return out
+
+
+def ob_convex_up_fwd_bound(flow, mask):
+    """The forward's own bound for the adjoint identity: a term 8 w_k flow_k at its count, the product and 8 sums."""
+    b, _, h, w = flow.shape
+    wk, kt = ob_convex_weights(mask)
+    f = F.unfold(8.0 * _d(flow).abs(), (3, 3), padding=1).view(b, 2, 9, 1, 1, h, w)
+    bd = (wk[:, None] * f * (kt[:, None] + 9.0)).sum(2)                                 # [B, 2, sy, sx, h, w]
+    return U * ER_SLACK * bd.permute(0, 1, 4, 2, 5, 3).reshape(b, 2, 8 * h, 8 * w)
+
+
+# ---- warp
+def ob_warp_bwd_ref(x, flow, dout, mode, mask=None):
+    """Adjoint of the warp with the taps (and, mode 2, the mask: pass the GPU forward's) given: {"dx": (ref, mag, N), "dflow": fp64 with
+    the weights' fractions and d ix / d vx in fp32 as the kernel forms them}."""
+    t = pl_warp_taps(flow, mode)
+    xd, dd = _d(x), _d(dout)
+    b, c, h, w = xd.shape
+    m = (t["mask"] if mask is None else torch.as_tensor(mask).cpu().bool()).double()[:, None]
+    g = dd * m
+    bi = torch.arange(b).view(b, 1, 1)
+    ref, mag, cnt = (torch.zeros(b, c, h * w, dtype=torch.float64) for _ in range(3))
+    v = []
+    for i in range(4):
+        ok = t["ok"][i]
+        at = (t["y"][i].clamp(0, h - 1) * w + t["x"][i].clamp(0, w - 1)).view(b, 1, h * w).expand(b, c, h * w)
+        wt = (t["w"][i].double() * ok.double())[:, None]
+        ref.scatter_add_(2, at, (g * wt).reshape(b, c, h * w))
+        mag.scatter_add_(2, at, (g.abs() * wt).reshape(b, c, h * w))
+        cnt.scatter_add_(2, at, (wt != 0).double().expand(b, c, h, w).reshape(b, c, h * w))
+        vi = xd[bi, :, t["y"][i].clamp(0, h - 1), t["x"][i].clamp(0, w - 1)].permute(0, 3, 1, 2)
+        v.append(torch.where(ok[:, None], vi, torch.zeros((), dtype=torch.float64)))
+    ww, wn = (f.double()[:, None] for f in t["frac"])
+    gix = (g * ((v[1] - v[0]) * (1 - wn) + (v[3] - v[2]) * wn)).sum(1)
+    giy = (g * ((v[2] - v[0]) * (1 - ww) + (v[3] - v[1]) * ww)).sum(1)
+    one = _f32c(1.0)
+    if mode == 0:
+        mx, my = (2.0 * one / _f32c(max(w - 1, 1))) * (_f32c(w - 1) / 2.0), (2.0 * one / _f32c(max(h - 1, 1))) * (_f32c(h - 1) / 2.0)
+    else:
+        mx, my = (2.0 * one / _f32c(max(w - 1, 1))) * (_f32c(w) / 2.0), (2.0 * one / _f32c(max(h - 1, 1))) * (_f32c(h) / 2.0)
+    dflow = torch.stack([gix * float(mx), giy * float(my)], 1)
+    return {"dx": (ref.view(b, c, h, w), mag.view(b, c, h, w), cnt.view(b, c, h, w)), "dflow": dflow}
+
+
+# ---- the inputs of tests/test_gpu_opsbwd_fp64.py; tests/test_fp64_bounds_opsbwd.py holds its conditions on exactly these
+OB_LOOKUP_SHAPES = [(16, 20), (17, 19)]
+OB_PYRAMID_CASES = [(256, 16, 20), (40, 18, 18), (96, 10, 10), (16, 8, 8)]          # (c, h, w)
+OB_CONVEX_SHAPES = [(5, 7), (1, 1), (1, 9)]
+OB_CONVEX_KINDS = ("normal", "extreme", "equal")
+OB_WARP_SHAPES = [(5, 17, 23), (1, 1, 9), (3, 9, 1)]                                # (c, h, w)
+OB_RESIZE_CASES = [((3, 4), (37, 50)), ((6, 8), (48, 64)), ((5, 7), (5, 7)), ((9, 11), (4, 5)), ((1, 5), (8, 5)), ((4, 4), (1, 9)), ((2, 2), (3, 3))]
+OB_INSTNORM_HW = [1, 63, 437, 16383, 16384, 16385]
+OB_BN_CASES = [(3, 3, 357), (2, 3, 8192), (1, 2, 16384), (1, 2, 1)]                 # (n, c, hw)
+OB_ELEMENTWISE_N = [1, 255, 256, 257, 1027]
+# The rows form's allowance (ob_lookup_bwd_ref) may serve fewer than this fraction of a case's cells, and none of a case without near-integer
+# coordinates.  Cells that use it: 16x20 hostile 0 of 271 360, 16x20 smooth 0, 17x19 hostile 0 of 268 090, 17x19 smooth 0 (the window of ten
+# rows serving two taps each, which the kernel had, would have used it in 5204 and 3038 cells of the two hostile cases).
+LOOKUP_ALLOWANCE_CAP = 0.01
+
+
+def ob_seed(*key):
+    import zlib
+    return zlib.crc32(repr(key).encode())
+
+
+def ob_lookup_coords(h, w, kind, seed):
+    """coords [2, 2, h, w] for the lookup adjoint.  "smooth": the pixel grid plus a smooth sub-pixel field (no coordinate near an integer
+    at any level).  "hostile": per pixel and axis one of - an exact integer, an integer +- 1 ulp, +- 2^-12, a half-integer, -0.5 or
+    size - 0.5, a position whose 9 x 9 window straddles a border of the map, +-1e4, +-1e9 (the kernels' clamps)."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == "smooth":
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+        f = [torch.stack([2.3 * torch.sin(0.31 * yy + 0.17 * xx + 0.4 + i) + 0.3137, 1.9 * torch.cos(0.23 * xx - 0.29 * yy + i) - 0.2871]) for i in range(2)]
+        return (R.coords_grid(2, h, w) + torch.stack(f)).float()
+    out = torch.empty(2, 2, h, w)
+    inf = torch.tensor(float("inf"))
+    for ax, size in ((0, w), (1, h)):
+        n = torch.randint(-3, size + 4, (2, h, w), generator=g).float()
+        sgn = torch.where(torch.rand(2, h, w, generator=g) < 0.5, -1.0, 1.0)
+        lo = torch.rand(2, h, w, generator=g) < 0.5
+        cand = [n, torch.nextafter(n, sgn * inf), n + sgn * 2.0 ** -12, n + 0.5, torch.where(lo, -0.5, size - 0.5),
+                torch.where(lo, -5.0, size - 6.0) + 10.0 * torch.rand(2, h, w, generator=g), sgn * 1e4, sgn * 1e9]
+        pick = torch.multinomial(torch.tensor([4.0, 4, 3, 3, 2, 3, 0.5, 0.5]), 2 * h * w, replacement=True, generator=g).view(2, h, w)
+        out[:, ax] = torch.stack(cand).gather(0, pick[None])[0]
+    return out
+
+
+def ob_convex_inputs(h, w, kind, seed):
+    """(flow [2, 2, h, w], mask logits [2, 576, h, w], dout [2, 2, 8h, 8w] zero outside a crop, as ConvexUpsample.backward produces)."""
+    g = torch.Generator().manual_seed(seed)
+    flow = torch.randn(2, 2, h, w, generator=g) * 3.0
+    mask = torch.randn(2, 576, h, w, generator=g)
+    if kind == "extreme":
+        mask[:, 2 * 64:3 * 64] += 40.0
+        mask[:, 6 * 64:7 * 64] -= 40.0
+    elif kind == "equal":
+        mask = torch.full_like(mask, 0.7)
+    dout = torch.zeros(2, 2, 8 * h, 8 * w)
+    dout[:, :, 3:8 * h - 2, 5:8 * w - 1] = torch.randn(2, 2, 8 * h - 5, 8 * w - 6, generator=g)
+    return flow, mask, dout
+
+
+def ob_warp_flows(h, w, seed):
+    """pl_hostile_flows (integers, half-integers, landing on -1 / 0 / size - 1 / size in both conventions, far outside, random) with the
+    far displacements at +-1e6 and +-1e9."""
+    f = pl_hostile_flows(h, w, seed)
+    return torch.where(f.abs() == 1e4, torch.sign(f) * 1e6, f)
+
+
+def ob_norm_input(n, c, hw, seed, constant=True):
+    """x [n, c, hw]: channel 0 ordinary, channel 1 constant (var = 0; `constant`), the last channel (when c > 2) with mean / std = 100.
+    The BatchNorm cases take no constant channel: criterion 3 compares error norms over a channel, and a channel that holds one distinct
+    value has one error sample on either side - the ratio of two single roundings (the instance-norm gradient of a constant plane is
+    rstd (g - mean g), as many samples as pixels)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, c, hw, generator=g) * 2.0 + 0.5
+    if constant:
+        x[:, 1] = 1.25
+    if c > 2:
+        x[:, c - 1] = 100.0 + torch.randn(n, hw, generator=g)
+    return x
+
+
+def ob_gated_output(y, seed):
+    """A stored layer output for the gates: relu(y) with exact 0.0 and -0.0 planted."""
+    g = torch.Generator().manual_seed(seed)
+    y = torch.relu(_f32(y)).clone()
+    r = torch.rand(y.shape, generator=g)
+    y[r < 0.05] = 0.0
+    y[(r >= 0.05) & (r < 0.1)] = -0.0
+    return y
+
+
+# ---- the composite checks: what the GPU module asserts of a call's outputs, and the host module of torch's fp32 restatements
+def ob_check_lookup(name, got_levels, coords, dout, form):
+    """The four levels of a lookup adjoint; returns the reference's levels (bounds included) for the adjoint identity."""
+    refs = ob_lookup_bwd_ref(coords, dout, rows=form == "lookup_bwd_rows")
+    for l, lv in enumerate(refs):
+        k, extra = ob_lookup_bound(lv, form)
+        check_counted(f"{name}.l{l}", got_levels[l], lv["ref"], lv["mag"], k, form, extra)
+        lv["bound"] = bound_counted(lv["mag"], k, extra)
+    return refs
+
+
+def ob_check_pyramid(name, got, fmap1, fmap2, dpyr):
+    """eraft_corr_pyramid_bwd: got = {"dpyr": the three folded levels, "dfmap1", "dfmap2"}; the GEMMs against the folded level 0 the
+    call itself left (its own check is the fold's)."""
+    for l, (ref, mag, k) in enumerate(ob_pyramid_fold_ref(dpyr)):
+        check_counted(f"{name}.fold{l}", got["dpyr"][l], ref, mag, k, "allpairs_bwd")
+    (r1, m1), (r2, m2) = ob_allpairs_bwd_ref(fmap1, fmap2, got["dpyr"][0])
+    check(f"{name}.dfmap1", got["dfmap1"], r1, m1, "direct", form="allpairs_bwd")
+    check(f"{name}.dfmap2", got["dfmap2"], r2, m2, "direct", form="allpairs_bwd")
+
+
+def ob_check_convex(name, dflow, dmask, flow, mask, dout):
+    r = ob_convex_up_bwd_ref(flow, mask, dout)
+    ref, bound = r["dflow"]
+    check_counted(f"{name}.dflow", dflow, ref, bound / (U * ER_SLACK), 1.0, "convex_up_bwd")
+    if dmask is not None:
+        rec = check_decoder(f"{name}.dmask", dmask, r["dmask"], r["dmask32"])
+        rec["form"] = "convex_up_bwd:kappa"
+    return r
+
+
+def ob_check_warp_bwd(name, dx, dflow, x, flow, dout, mode, mask):
+    form = f"warp_bwd_m{mode}"
+    r = ob_warp_bwd_ref(x, flow, dout, mode, mask)
+    ref, mag, n = r["dx"]
+    k = ER_ROUNDINGS["warp_dx"] + (n - 1).clamp_min(0)
+    check_counted(f"{name}.dx", dx, ref, mag, k, form)
+    if dflow is not None:
+        rec = check_decoder(f"{name}.dflow", dflow, r["dflow"], ob_warp_dflow_f32(x, flow, dout, mode, mask))
+        rec["form"] = form + ":kappa"
+    r["dx_bound"] = bound_counted(mag, k)
+    return r
+
+
+def ob_check_resize_bwd(name, dx, dout, in_hw, form):
+    ref, mag, n = ob_resize_bwd_ref(dout, in_hw)
+    k = ER_ROUNDINGS[form] + (n - 1).clamp_min(0)
+    check_counted(name, dx, ref, mag, k, form)
+    return bound_counted(mag, k)
+
+
+def ob_check_planes(name, got, ref64, ref32, form, dim):
+    """check_decoder plane by plane (channel by channel) along `dim`: an ill-conditioned plane does not cover for the others."""
+    for i in range(ref64.shape[dim]):
+        rec = check_decoder(f"{name}[{i}]", _d(got).select(dim, i), ref64.select(dim, i), ref32.select(dim, i))
+        rec["form"] = form + ":kappa"
+
+
+def ob_check_counted_map(name, got, refs, form, keys):
+    """The counted outputs of a norm reference: refs[key] = (ref, mag, k[, extra])."""
+    for key in keys:
+        ref, mag, k, *extra = refs[key]
+        check_counted(f"{name}.{key}", got[key], ref, mag, k, form, extra[0] if extra else None)
+
+
+def ob_warp_dflow_f32(x, flow, dout, mode, mask=None):
+    """torch's fp32 CPU autograd of the oracle's warp w.r.t. the flow (mode 2: torch_warp times the given mask, which has no gradient)."""
+    xf, do = _f32(x), _f32(dout)
+    fl = _f32(flow).clone().requires_grad_(True)
+    if mode == 0:
+        out = P.warp_align_true(xf, fl)
+    else:
+        out = P.torch_warp(xf, fl)
+        if mode == 2:
+            out = out * torch.as_tensor(mask).cpu().float()[:, None]
+    return torch.autograd.grad(out, fl, do)[0]
