@@ -17,5 +17,6 @@ from .metrics import fb_check          # noqa: F401
 from .padder import InputPadder         # noqa: F401
 from .smooth import smoothness_loss, smoothness_many   # noqa: F401
 from .photo import photo_loss, photo_many   # noqa: F401
+from .ssim import ssim_loss, ssim_many   # noqa: F401
 from .viz import ImageWriter, event_image, event_image_many, flow_to_image, flow_to_image_many   # noqa: F401
 from .voxelizer import EventSequence, EventSequenceToVoxelGrid_Pytorch   # noqa: F401

@@ -111,6 +111,9 @@ _SIGNATURES = {
                            + [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
                               ctypes.c_void_p, ctypes.c_void_p]),
     "eemflow_photo_scratch_doubles": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "eemflow_ssim_many": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.c_int] * 5 + [ctypes.c_double] * 3
+                          + [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]),
+    "eemflow_ssim_scratch_doubles": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "eemflow_voxelize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, _c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "eemflow_voxelize_pair": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,

@@ -88,6 +88,16 @@ def build_parser():
             q.add_argument('--photo_q', default=0.4, type=float, metavar='Q', help='with --photo_kind census: the exponent')
             q.add_argument('--photo_charbonnier', action='store_true', help='with --photo_kind census: (dist^2 + eps)^q in place of (|dist| + 0.01)^q')
             q.add_argument('--photo_max_distance', default=3, type=int, choices=(1, 2, 3), metavar='R', help='with --photo_kind census: patches of (2R+1)^2 cells')
+            q.add_argument('--ssim_weight', default=0.0, type=float, metavar='W',
+                           help='add W times the weighted SSIM loss between the old event volume and the new one warped back by the last '
+                                'prediction to the loss (Loss_tools.weighted_ssim under photo_loss_multi_type of the reference, no ground '
+                                'truth needed; every model then trains through the autograd engine and EEMFlow predicts at the full frame)')
+            q.add_argument('--ssim_occ', action='store_true',
+                           help='with --ssim_weight: the forward-backward occlusion mask of --photo_occ weights the loss (one exchanged pass '
+                                'per step serves both)')
+            q.add_argument('--ssim_all', action='store_true', help='with --ssim_weight: all predictions under the sequence loss\'s gamma, not the last alone')
+            q.add_argument('--ssim_c1', default=float('inf'), type=float, metavar='C1', help='with --ssim_weight: regularises the luminance term (inf: off, the reference\'s default)')
+            q.add_argument('--ssim_c2', default=9e-6, type=float, metavar='C2', help='with --ssim_weight: regularises the structure term (inf: off)')
         q.add_argument('--device_events', action='store_true',
                        help='prepare the event sets on the GPU from the npz columns (HREM datasets: the columns are uploaded in their file '
                             'dtypes and one launch per sample writes the float64 event tables; the same samples bit for bit, a set whose '
@@ -191,12 +201,20 @@ def photo_kw(args):
                 photo_max_distance=int(getattr(args, "photo_max_distance", 3)))
 
 
+def ssim_kw(args):
+    """TrainRaftEvents' SSIM arguments of the --ssim_* flags."""
+    return dict(ssim_weight=float(getattr(args, "ssim_weight", 0.0)), ssim_occ=bool(getattr(args, "ssim_occ", False)),
+                ssim_all=bool(getattr(args, "ssim_all", False)), ssim_c1=float(getattr(args, "ssim_c1", float("inf"))),
+                ssim_c2=float(getattr(args, "ssim_c2", 9e-6)))
+
+
 def train(args):
     from . import harness, parallel
     from .hrem import HREMEventFlow
     photo = float(getattr(args, "photo_weight", 0.0))
-    if getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0 and photo == 0.0:
-        raise SystemExit("--self_supervised needs a --contrast_weight or a --photo_weight: there is no other loss")
+    ssim = float(getattr(args, "ssim_weight", 0.0))
+    if getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0 and photo == 0.0 and ssim == 0.0:
+        raise SystemExit("--self_supervised needs a --contrast_weight, a --photo_weight or an --ssim_weight: there is no other loss")
     # one process per GPU under torchrun: every rank trains on its shard of the samples, the trainer all-reduces the flat gradient
     # (RCCL), rank 0 writes the logs and checkpoints
     rank, local_rank, world = parallel.init_distributed()
@@ -206,7 +224,7 @@ def train(args):
         parallel.pin_host_threads_to_gpu_numa(parallel.local_device_index(local_rank))
     config = load_config(args.config)
     contrast = float(getattr(args, "contrast_weight", 0.0))
-    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0 and photo == 0.0)    # (both terms need the full frame)
+    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0 and photo == 0.0 and ssim == 0.0)    # (these terms need the full frame)
     config["train"]["lr"] = args.lr                                                  # train_EEMFlow_HREM.py:56-59
     config["train"]["wdecay"] = args.wd
     config["train"]["num_steps"] = args.train_iters
@@ -255,11 +273,11 @@ def train(args):
     # EEMFlow: the fused step inside the library; E-RAFT / EEMFlow+: the reference's statement sequence over the operator-level
     # autograd route (their data-parallel exchange is the flat-gradient all-reduce in TrainRaftEvents._train_iters_autograd)
     smooth = float(getattr(args, "smooth_weight", 0.0))
-    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and photo == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has none of the terms)
+    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and photo == 0.0 and ssim == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has none of the terms)
     tr = harness.TrainRaftEvents(loader, None, lr=tcfg["lr"], wdecay=tcfg["wdecay"], epsilon=tcfg["epsilon"],
                                  num_steps=tcfg["num_steps"], clip=tcfg["clip"], gamma=tcfg["gamma"], logger=logger,
                                  start_iteration=start_iteration, engine=engine, mixed_precision=tcfg.get("mixed_precision", True),
-                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args), **photo_kw(args))
+                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args), **photo_kw(args), **ssim_kw(args))
     for epoch in range(start_epoch, max(args.train_iters // args.val_iters, 1)):
         if sampler is not None:
             sampler.set_epoch(epoch)

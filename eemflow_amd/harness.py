@@ -27,7 +27,7 @@ import torch
 
 from .metrics import flow_error, flow_error_from_sums, flow_error_sums, flow_error_sums_many
 from . import parallel
-from .train import EEMFlowTrainer, contrast_loss, photo_loss, sequence_loss, smoothness_loss
+from .train import EEMFlowTrainer, contrast_loss, photo_loss, sequence_loss, smoothness_loss, ssim_loss
 
 
 class Logger:
@@ -486,13 +486,22 @@ class TrainRaftEvents:
     size.  photo_occ=True runs model(new, old) under torch.no_grad(), takes mask_fw of metrics.fb_check(final forward flow, final
     backward flow) and hands it to the loss with use_occ=True; a model whose BatchNorm layers are in train mode (E-RAFT before
     freeze_bn()) is refused, because the second pass would move their running statistics.  supervised=False is satisfied by a
-    contrast_weight or a photo_weight.  With photo_weight == 0 nothing is computed and nothing changes."""
+    contrast_weight or a photo_weight.  With photo_weight == 0 nothing is computed and nothing changes.
+
+    ssim_weight (the autograd engine only): ssim_weight * train.ssim_loss(predictions, event_volume_old, event_volume_new as the model
+    received them) is added to the loss - the weighted SSIM between the old volume and the new one warped back by the prediction, with
+    ssim_c1 / ssim_c2 regularising its luminance / structure term (inf switches one off; the reference's default is the structure
+    term alone); of the last prediction, or with ssim_all=True of all predictions under the engine's gamma.  The prediction must be at
+    the frame's size.  ssim_occ=True weights the moments and the mean by mask_fw of the same gradient-free exchanged pass as
+    photo_occ - it runs once per step when both are on.  supervised=False is satisfied by an ssim_weight too.  With ssim_weight == 0
+    nothing is computed and nothing changes."""
 
     def __init__(self, loader, image_size, lr=1e-4, wdecay=5e-5, epsilon=1e-8, num_steps=1000000, clip=1.0, gamma=0.8,
                  logger=None, print_freq=100, engine="fused", mixed_precision=True, start_iteration=0, contrast_weight=0.0,
                  supervised=True, smooth_weight=0.0, smooth_order=1, smooth_constant=1.0, smooth_weight_type="gauss", smooth_error="L1",
                  smooth_all=False, photo_weight=0.0, photo_kind="census", photo_occ=False, photo_all=False, photo_q=0.4,
-                 photo_charbonnier=False, photo_max_distance=3):
+                 photo_charbonnier=False, photo_max_distance=3, ssim_weight=0.0, ssim_occ=False, ssim_all=False, ssim_c1=float("inf"),
+                 ssim_c2=9e-6):
         if engine not in ("fused", "autograd"):
             raise ValueError("engine must be 'fused' or 'autograd'")
         self.contrast_weight, self.supervised = float(contrast_weight), bool(supervised)
@@ -507,8 +516,17 @@ class TrainRaftEvents:
                                  "fused trainer has no photometric term")
             from .photo import _settings as photo_settings
             photo_settings("TrainRaftEvents", photo_kind, photo_occ, photo_q, photo_charbonnier, True, photo_max_distance)
-        if not self.supervised and self.contrast_weight == 0.0 and self.photo_weight == 0.0:
-            raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight or a photo_weight")
+        self.ssim_weight, self.ssim_occ, self.ssim_all = float(ssim_weight), bool(ssim_occ), bool(ssim_all)
+        self.ssim_kw = dict(c1=float(ssim_c1), c2=float(ssim_c2))
+        if self.ssim_weight != 0.0:
+            if engine == "fused":
+                raise ValueError("TrainRaftEvents: the SSIM term (ssim_weight != 0) is honoured by engine='autograd' only - the fused "
+                                 "trainer has no SSIM term")
+            from .ssim import _settings as ssim_settings
+            ssim_settings("TrainRaftEvents", ssim_occ, ssim_c1, ssim_c2, 0.01)
+        if not self.supervised and self.contrast_weight == 0.0 and self.photo_weight == 0.0 and self.ssim_weight == 0.0:
+            raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight or a photo_weight (or an "
+                             "ssim_weight)")
         self.smooth_weight, self.smooth_all = float(smooth_weight), bool(smooth_all)
         self.smooth_kw = dict(order=smooth_order, constant=smooth_constant, weight_type=smooth_weight_type, error_type=smooth_error)
         if self.smooth_weight != 0.0:
@@ -554,7 +572,8 @@ class TrainRaftEvents:
                 self._contrast_inputs(batch)                       # (before any GPU work: a loader without events fails at once)
             e1 = batch['event_volume_old'].to(dev).float()
             e2 = batch['event_volume_new'].to(dev).float()
-            back = self._photo_backward_flow(model, e1, e2) if self.photo_weight != 0.0 and self.photo_occ else None
+            need_back = (self.photo_weight != 0.0 and self.photo_occ) or (self.ssim_weight != 0.0 and self.ssim_occ)
+            back = self._photo_backward_flow(model, e1, e2) if need_back else None     # (one exchanged pass serves both terms)
             _, flow_list = model(e1, e2)
             if self.supervised:
                 flow_gt, valid = _target_like(flow_list[-1], batch['flow'].to(dev).float(), batch['valid'].to(dev).float())
@@ -567,6 +586,8 @@ class TrainRaftEvents:
                 loss = loss + self.smooth_weight * self._smooth_term(flow_list, e1)
             if self.photo_weight != 0.0:
                 loss = loss + self.photo_weight * self._photo_term(flow_list, e1, e2, back)
+            if self.ssim_weight != 0.0:
+                loss = loss + self.ssim_weight * self._ssim_term(flow_list, e1, e2, back)
             self.scaler.scale(loss).backward()
             if parallel.exchange_active():
                 # the still-SCALED gradients are exchanged, then unscaled: an overflow on one rank reaches every rank through the
@@ -642,6 +663,19 @@ class TrainRaftEvents:
             mask = fb_check(flow_list[-1].detach().float().contiguous(), back)[0]
         return photo_loss(flow_list, e1, e2, gamma=self.opt["gamma"] if self.photo_all else None, mask=mask, use_occ=self.photo_occ,
                           **self.photo_kw).float()
+
+    def _ssim_term(self, flow_list, e1, e2, back):
+        """train.ssim_loss of the predictions between the two event volumes (float32, as the supervised loss is); with ssim_occ the
+        mask is mask_fw of the forward-backward check of the final prediction against `back`."""
+        if tuple(flow_list[-1].shape[-2:]) != tuple(e1.shape[-2:]):
+            raise ValueError(f"TrainRaftEvents: the SSIM term needs the prediction at the event frame's size {tuple(e1.shape[-2:])}, "
+                             f"got {tuple(flow_list[-1].shape[-2:])} - a model with out_mesh_size=True predicts the mesh flow")
+        mask = None
+        if self.ssim_occ:
+            from .metrics import fb_check
+            mask = fb_check(flow_list[-1].detach().float().contiguous(), back)[0]
+        return ssim_loss(flow_list, e1, e2, gamma=self.opt["gamma"] if self.ssim_all else None, mask=mask, use_occ=self.ssim_occ,
+                         **self.ssim_kw).float()
 
     def train_iters(self, model, start_epoch=0, val_iters=None):
         if self.image_size is None:                              # padder sized from the data (cli: un-cropped HREM frames)

@@ -41,7 +41,7 @@ def default_gray(channels):
 
 def _settings(name, kind, use_occ, q, charbonnier, average, max_distance):
     if kind not in KINDS:
-        raise ValueError(f"{name}: kind is one of {sorted(KINDS)} (the reference's SSIM is not provided), got {kind!r}")
+        raise ValueError(f"{name}: kind is one of {sorted(KINDS)} (the reference's SSIM is a term of its own: eemflow_amd.ssim_loss), got {kind!r}")
     if kind == "census" and max_distance not in MAX_DISTANCES:
         raise ValueError(f"{name}: max_distance is 1, 2 or 3, got {max_distance!r}")
     return KINDS[kind], bool(use_occ), float(q), bool(charbonnier), bool(average), int(max_distance) if kind == "census" else 0

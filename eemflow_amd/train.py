@@ -136,6 +136,24 @@ def photo_loss(flow_preds, img1, img2, gamma=None, mask=None, **kw):
     return (losses * weights).sum()
 
 
+def ssim_loss(flow_preds, img1, img2, gamma=None, mask=None, **kw):
+    """The weighted SSIM data term of a model's predictions (a list of (B,2,H,W) tensors, the last one final): the loss between `img1`
+    and `img2` warped back by the flow (both (B,C,H,W), in training the old and the new event volume), ssim.ssim_loss of the last
+    prediction with gamma=None, else sum_i gamma^(n-1-i) * L_i over all n predictions - one library call forward and one backward per
+    16 predictions.  mask: a (B,1,H,W) weight, with use_occ=True the occlusion mask.  A differentiable 0-dim float64 CUDA tensor;
+    **kw: use_occ, c1, c2, weight_epsilon of ssim.ssim_many."""
+    from .ssim import ssim_many
+    flow_preds = list(flow_preds)
+    if len(flow_preds) < 1:
+        raise ValueError("ssim_loss: at least one prediction")
+    if gamma is None:
+        return ssim_many([flow_preds[-1].float()], img1, img2, mask, **kw)[0]
+    n = len(flow_preds)
+    losses = ssim_many([f.float() for f in flow_preds], img1, img2, mask, **kw)
+    weights = torch.tensor([float(gamma) ** (n - 1 - i) for i in range(n)], dtype=torch.float64).to(losses.device, non_blocking=True)
+    return (losses * weights).sum()
+
+
 class EEMFlowTrainer:
     """One optimisation step per `step()` call; owns the flat gradient buffer and the schedule."""
 

@@ -369,7 +369,7 @@ size_t eemflow_smoothness_scratch_doubles(int k, int B, int H, int W);
  * fixed order.  Consecutive jobs that name one img1 pointer grey-combine it once per tile; a job's results are bitwise those of a
  * one-job call.  Stream-ordered, no host synchronisation, no allocation.  Errors: k out of range, unknown kind, census with r outside
  * 1..3 or H <= 2r or W <= 2r, neither loss nor grad.  Non-finite inputs propagate.
- * Replaces: Loss_tools.photo_loss_multi_type (utils_luo/tools.py:3112-3135; SSIM excepted), Loss_tools.photo_loss_function
+ * Replaces: Loss_tools.photo_loss_multi_type (utils_luo/tools.py:3112-3135; its 'SSIM' kind is eemflow_ssim_many), Loss_tools.photo_loss_function
  * (3137-3169) and Loss_tools.census_loss_torch (3171-3212) on tensor_tools.torch_warp (2262-2306), and their autograd. */
 int eemflow_photo_many(int k, const float* const* flow, const float* const* img1, const float* const* img2, const float* const* mask,
                        int B, int C, int H, int W, int kind, int use_occ, int charbonnier, int average, int max_distance, double q,
@@ -378,6 +378,41 @@ int eemflow_photo_many(int k, const float* const* flow, const float* const* img1
 /* Doubles of scratch that eemflow_photo_many needs for k jobs of shape [B][2][H][W] (0 for arguments it would refuse).
  * Replaces: nothing in the reference (torch.sum owns its temporaries). */
 size_t eemflow_photo_scratch_doubles(int k, int B, int H, int W);
+
+/* Weighted SSIM loss between img1 and img2 warped back by a predicted flow, for k (1..16) predictions of one shape, and its gradient
+ * with respect to the flow: the structural data term of ground-truth-free training, beside eemflow_photo_many.  flow, img1, img2, mask
+ * and grad are as there: HOST arrays of device pointers to contiguous fp32 [B][2|C|C|1|2][H][W]; a NULL mask entry, or mask == NULL, is
+ * a weight of ones.  Yw = grid_sample(img2, grid + flow) is warp_px.h mode 1 in fp32, bit for bit eemplus_warp(mode 1); everything
+ * after it is unfused fp64 on those fp32 values.  With x = img1, y = Yw, w = mask, per channel and per centre m of [1,H-2] x [1,W-2],
+ * avg3x3(z)(m) = (the nine values of z around m, added in row-major order - rows top to bottom, each left to right) / 9:
+ *   aw = avg3x3(w);  wpe = w + weight_epsilon;  inv = 1 / (aw + weight_epsilon);  P[z] = avg3x3(z * wpe) * inv
+ *   mu_x = P[x], mu_y = P[y], s_x = P[x*x] - mu_x*mu_x, s_y = P[y*y] - mu_y*mu_y, s_xy = P[x*y] - mu_x*mu_y
+ *   c1 == inf:  n = 2 s_xy + c2,  d = s_x + s_y + c2            (the structure term; the default with c2 = 9e-6)
+ *   c2 == inf:  n = 2 mu_x mu_y + c1,  d = mu_x*mu_x + mu_y*mu_y + c1                     (the luminance term)
+ *   both finite:  n and d are the products of the two
+ *   l = clamp((1 - n / d) / 2, 0, 1)
+ *   use_occ == 0: L = sum(l) / (B*C*(H-2)*(W-2));  else L = sum(l * aw) / (sum(aw) + 1e-6), aw broadcast over C in the numerator and
+ *   summed over its own B*(H-2)*(W-2) cells in the denominator (photo_loss_multi_type's form).
+ * loss (device, k doubles; may be NULL) receives L per job.  grad (may be NULL) receives coef[i] * dL_i / dflow_i, every cell written:
+ * per centre the three factors dl/dmu_y, dl/dP[y*y] and dl/dP[x*y] (the clamp passes the gradient on 0 <= v <= 1, both ends included),
+ * each times inv/9, aw with use_occ, and coef / (n1 D), go into LDS planes; every cell p gathers their sums SA, SB, SC over the up to
+ * nine centres whose window holds it, dL/dYw_c(p) = wpe(p) * (SA + 2 y(p) SB + x(p) SC), then the derivative of the bilinear blend at
+ * the fp32 tap weights times (W/2) * (2/max(W-1,1)) (and the same in H) as in eemflow_photo_many, summed over the channels in fp64 and
+ * rounded to fp32 once.  The images and the mask receive no gradient and the denominators do not depend on the flow.  No atomics:
+ * losses and gradients are bitwise reproducible, and a job's results are bitwise those of a one-job call.  coef is a DEVICE array of k
+ * doubles (the upstream gradient; NULL: 1).  scratch (device, eemflow_ssim_scratch_doubles(k, B, H, W) doubles) is always needed: the
+ * denominators and the per-block partial sums, added in a fixed order.  Stream-ordered, no host synchronisation, no allocation.
+ * Errors: k out of range, H < 3 or W < 3, C < 1, c1 or c2 not positive or both infinite, weight_epsilon not positive, neither loss nor
+ * grad, a NULL pointer.  Non-finite inputs propagate.
+ * Replaces: Loss_tools.weighted_ssim (utils_luo/tools.py:2951-3006) under Loss_tools.photo_loss_multi_type's 'SSIM' kind (3126-3135) on
+ * tensor_tools.torch_warp (2262-2306), and their autograd. */
+int eemflow_ssim_many(int k, const float* const* flow, const float* const* img1, const float* const* img2, const float* const* mask,
+                      int B, int C, int H, int W, int use_occ, double c1, double c2, double weight_epsilon, const double* coef,
+                      double* loss, float* const* grad, double* scratch, void* stream);
+
+/* Doubles of scratch that eemflow_ssim_many needs for k jobs of shape [B][2][H][W] (0 for arguments it would refuse).
+ * Replaces: nothing in the reference (torch.sum owns its temporaries). */
+size_t eemflow_ssim_scratch_doubles(int k, int B, int H, int W);
 
 /* Event voxelization: events [n][4] f64 (t, x, y, p) on the device, time-sorted, as held by the
  * reference's EventSequence -> grid [bins][h][w] fp32.  idx_left / idx_right (optional, may be NULL)
