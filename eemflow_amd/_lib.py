@@ -120,6 +120,7 @@ _SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_void_p]),
     "eemflow_voxelize_many": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
+    "eemflow_voxelize_last_form": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "eemflow_pack_events_many": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.POINTER(ctypes.c_int),
                                                 ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),

@@ -42,6 +42,7 @@
 // reference's fp32 index_add_, whose order is not defined either; the integer indices are bit-exact.
 // Grids too large for the LDS band layout (band_px * bins > 19 200 cells, bins > 64) and more than 33.5 M events
 // take the direct atomic kernel (one job at a time).
+// Which of these a call ran is reported by eemflow_voxelize_last_form (a test observable: integers stored on the host, no launch).
 #include <string.h>
 
 #include "common.h"
@@ -566,7 +567,36 @@ bool make_plan(int64_t n, int bins, int h, int w, const double* events, VoxPlan*
     return true;
 }
 
+// what this thread's last launch sequence ran (eemflow_voxelize_last_form): small integers stored on the host beside the launches
+struct VoxForm {
+    int njobs;               // 0: no sequence yet
+    int ept;                 // binning kernel's events per thread; 0: the direct kernel
+    int bt, vec4, sgs;       // band kernel: threads per block, 16-byte read-out, log2 of the lanes per run
+    int moments;             // the raw band launch left its moments / vox_moments_kernel followed the direct kernel
+    int after;               // 0 nothing, 1 vox_norm_kernel, 2 vox_stats_kernel, 3 the two band passes
+};
+thread_local VoxForm t_vox_form = {0, 0, 0, 0, 0, 0, 0};
+
 }  // namespace
+
+extern "C" int eemflow_voxelize_last_form(char* buf, int cap) {
+    EEM_REQUIRE(buf && cap >= 1, "eemflow_voxelize_last_form: bad arguments");
+    const VoxForm& f = t_vox_form;
+    static const char* const kAfter[4] = {"", "+norm", "+stats", ""};
+    if (f.njobs == 0) {
+        buf[0] = 0;
+    } else if (f.ept == 0) {
+        snprintf(buf, (size_t)cap, "j%d:direct%s%s", f.njobs, f.moments ? "+moments" : "", kAfter[f.after]);
+    } else {
+        char band[48];
+        snprintf(band, sizeof(band), "band%d_%s_s%d", f.bt, f.vec4 ? "v4" : "v1", f.sgs);
+        if (f.after == 3)
+            snprintf(buf, (size_t)cap, "j%d:bin_e%d+%s_moments+%s_normalised", f.njobs, f.ept, band, band);
+        else
+            snprintf(buf, (size_t)cap, "j%d:bin_e%d+%s_%s%s", f.njobs, f.ept, band, f.moments ? "raw_sums" : "raw", kAfter[f.after]);
+    }
+    return EEM_OK;
+}
 
 #ifdef EEM_VOX_STAMPS
 extern "C" __attribute__((visibility("default"))) int eemflow_debug_read_vox_stamps(unsigned long long* dst, size_t n) {
@@ -609,6 +639,7 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
     }
     VoxJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
+    VoxForm vf = {njobs, 0, 0, 0, 0, normalize ? 1 : 0, normalize};   // (host only: what eemflow_voxelize_last_form reports)
     if (planned) {
         const int ept = vox_ept((long)nmax);                           // the run table is sized for these block counts
         // one EPT for both jobs (the longer set's): the shorter one's slabs are the same size, it just fills fewer of them
@@ -649,18 +680,25 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
         const long lanes_x10 = (long)VT * ept < 4L * pl.nb ? 40L : 17L;
         int sgs = 2;
         while (sgs < 6 && (1 << sgs) * 10L * pl.nb < lanes_x10 * VT * ept) ++sgs;
+        vf.ept = ept; vf.vec4 = vec4; vf.sgs = sgs;
         auto band = [&](int with_moments, int mode) {
-            if (lds <= 24 * 1024)
+            if (lds <= 24 * 1024) {
+                vf.bt = 256;
                 hipLaunchKernelGGL(vox_band_kernel<256>, dim3(pl.nb, njobs), dim3(256), lds, stream, jobs, VT * ept, bins, pl, vec4, with_moments, mode, sgs);
-            else if (lds <= 40 * 1024)
+            } else if (lds <= 40 * 1024) {
+                vf.bt = 512;
                 hipLaunchKernelGGL(vox_band_kernel<512>, dim3(pl.nb, njobs), dim3(512), lds, stream, jobs, VT * ept, bins, pl, vec4, with_moments, mode, sgs);
-            else
+            } else {
+                vf.bt = VT;
                 hipLaunchKernelGGL(vox_band_kernel<VT>, dim3(pl.nb, njobs), dim3(VT), lds, stream, jobs, VT * ept, bins, pl, vec4, with_moments, mode, sgs);
+            }
         };
         if (normalize == 1 && two_pass_ratio > 0 && (long)nmax * two_pass_ratio <= total) {
             band(1, (int)VOX_BAND_MOMENTS);
             band(1, (int)VOX_BAND_NORMALISED);
             EEM_HIP_CHECK(hipGetLastError());
+            vf.after = 3;
+            t_vox_form = vf;
             return EEM_OK;
         }
         band(normalize ? 1 : 0, (int)VOX_BAND_RAW);
@@ -680,6 +718,7 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
     if (normalize == 2) {                                              // deferred: the record behind each grid, no pass over the grids
         hipLaunchKernelGGL(vox_stats_kernel, dim3(njobs), dim3(VT), 0, stream, jobs, total, nsums);
         EEM_HIP_CHECK(hipGetLastError());
+        t_vox_form = vf;
         return EEM_OK;
     }
     if (normalize) {
@@ -689,6 +728,7 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
         hipLaunchKernelGGL(vox_norm_kernel, dim3((unsigned)blocks, njobs), dim3(VT), 0, stream, jobs, total, nsums);
         EEM_HIP_CHECK(hipGetLastError());
     }
+    t_vox_form = vf;
     return EEM_OK;
 }
 

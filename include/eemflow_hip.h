@@ -439,6 +439,15 @@ int eemflow_voxelize_pair(const double* events1, int64_t n1, const double* event
 int eemflow_voxelize_many(int nsets, const double* const* events, const int64_t* n_events, int bins, int h, int w, int normalize,
                           float* const* grids, void* stream);
 
+/* TEST OBSERVABLE: what the calling thread's most recent eemflow_voxelize / _pair / _many call launched, as "j<sets>:" and the launches
+ * joined with '+': "bin_e<1|2|4|8>" (the binning kernel's events per thread), "band<256|512|1024>_<v4|v1>_s<2..6>_<mode>" (the band
+ * kernel's threads per block, its 16-byte or scalar read-out, log2 of the lanes per run; mode "raw", "raw_sums" - raw grid, moments left
+ * for the pass that follows -, "moments", "normalised"), then "norm" (vox_norm_kernel) or "stats" (the deferred record); the direct atomic
+ * kernel reports "direct", "direct+moments+norm" or "direct+moments+stats".  E.g. "j1:bin_e1+band1024_v4_s2_raw_sums+norm",
+ * "j2:bin_e2+band256_v1_s4_moments+band256_v1_s4_normalised".  Several sets that fall to the direct kernel run one after the other and
+ * report the last ("j1:direct...").  A few integers stored on the host per call; "" before any call, unchanged by a refused one. */
+int eemflow_voxelize_last_form(char* buf, int cap);
+
 /* Event preparation: nsets (1..EEMFLOW_PACK_MAX) event sets, each given as its four COLUMNS on the device - t[k], x[k], y[k], p[k], n_events[k]
  * elements each, of the dtype codes[4*k + 0..3] (EEMFLOW_PACK_*; a bool column is uploaded as u8) - packed by ONE launch into
  * out[k] [n_events[k]][4] f64 (t, x, y, p): the table eemflow_voxelize, the IWE entry points and a loader's `events` take.  Every value

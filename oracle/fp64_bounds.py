@@ -1641,3 +1641,414 @@ def ob_warp_dflow_f32(x, flow, dout, mode, mask=None):
         if mode == 2:
             out = out * torch.as_tensor(mask).cpu().float()[:, None]
     return torch.autograd.grad(out, fl, do)[0]
+
+
+# ------------------------------------------------------------------------- the voxelizer (voxel.hip), launch form by launch form
+# tests/test_gpu_vox_fp64.py and tests/test_fp64_bounds_vox.py: every case is ONE call of eemflow_voxelize / _many, asserts the sequence
+# that ran by eemflow_voxelize_last_form and holds every output to a criterion that follows from the arithmetic, none fitted:
+#   indices    vox_votes restates vox_vote (the reference's order of the f64 time scaling, truncating casts, polarity 0 -> -1, dts rounded
+#              to fp32): the int64 index outputs are equal, -1 where the reference masks the vote.
+#   raw grid, banded path   the band kernel adds a cell's votes in fp64 and rounds once.  vox_exact gives the fp64 sum of every occupied
+#              cell and its error-free residual; residual 0: the cell equals the sum rounded to fp32, bit for bit; otherwise either fp32
+#              neighbour of the sum, on at most VOX_RESIDUAL_SHARE of a case's occupied cells.  Unoccupied cells are +0.0.
+#   raw grid, dyadic inputs  integer timestamps in [0, 2^20] with t0 = 0, t_last = 2^20: every vote is a multiple of 2^-20, every fp64 partial
+#              sum is exact, every fp32 partial sum of fewer than VOX_DYADIC_DIRECT_CAP votes too (|sum| < 8 keeps 2^-20 within 24 bits):
+#              banded AND direct path bitwise the exact sum, no exception.
+#   raw grid, direct path    fp32 atomics in any order: check_counted with k = votes - 1 against sum |votes|.
+#   record / moments         against fp64 moments of the GPU's OWN raw grid (vox_moment_bounds).  A band thread folds K cells into fp32
+#              partial sums (sum and fma'd sum of squares) that are widened once and added in fp64; K = vox_plan's "K", 1 for the direct
+#              path's fp64 vox_moments_kernel.  With u = 2^-24, c non-zero voxels, m the mean:
+#                 dS = K u sum|v|            dQ = (K + 1) u sum v^2
+#                 |mean err| <= dS / c + u |m|                      (the record's own rounding)
+#                 |m2 err|   <= dQ + 2 |m| dS + dS^2 / c            (m2 = Q - S^2 / c)
+#                 |sd err|   <= m2 err / (2 sd (c - 1)) + u sd
+#              `any` and `scale` are exact: flags 1 / 0, sd = 1 where scale is 0 (c = 1: sd NaN; equal voxels: sd 0).
+#   normalised grid          out = fl(fl(v - m') / sd') with m' = m + em, sd' = sd (1 + es), |em| <= dmean, |es| <= dsd / sd:
+#                 out - (v - m) / sd = ref (d1 + d2 - es) - em / sd + second order, |d1|, |d2| <= u, so
+#                 |err| <= |ref| (2 u + dsd / sd) + dmean / sd      (scale 0: u |v - m| + dmean), times ER_SLACK; zero voxels stay 0.
+#              The norm pass, the two band passes and the fp32 expression applied on the host to the deferred record take the same
+#              moments and the same expression (the file is built without contraction): bitwise equal (vox_normalise_f32).
+VOX_RESIDUAL_SHARE = 1e-3
+VOX_DYADIC_DIRECT_CAP = 8
+VOX_T_DYADIC = 2 ** 20
+
+
+def vox_plan(ns, bins, h, w, aligned=True, direct=False):
+    """make_plan and the launch code of voxel.hip restated: None where the direct kernel runs, else band_px, nb, BT, vec4, sgs, EPT and
+    K = the cells one band thread folds in fp32 in the read-out loop (bins x its share of band_px pixels, four at a time with vec4)."""
+    ns = [int(ns)] if np.isscalar(ns) else [int(n) for n in ns]
+    hw = h * w
+    blocks = lambda n, e: (n + 1024 * e - 1) // (1024 * e)        # noqa: E731
+    if direct or bins > 64 or hw >= 2 ** 31 or any(blocks(n, 8) > 4096 for n in ns):
+        return None
+    band_px = max((9216 // bins) & ~3, 64)
+    spread = ((hw + 511) // 512 + 3) & ~3
+    if band_px > spread:
+        band_px = max(spread, 64)
+    if (hw + band_px - 1) // band_px > 1023:
+        band_px = ((hw + 1022) // 1023 + 3) & ~3
+    if band_px * bins > 19200 or band_px > 65535:
+        return None
+    nb = (hw + band_px - 1) // band_px
+    lds = band_px * bins * 8
+    bt = 256 if lds <= 24 * 1024 else 512 if lds <= 40 * 1024 else 1024
+    ept = 1
+    while ept < 8 and blocks(max(ns), ept) > 512:
+        ept *= 2
+    vec4 = band_px % 4 == 0 and hw % 4 == 0 and aligned
+    lanes_x10 = 40 if 1024 * ept < 4 * nb else 17
+    sgs = 2
+    while sgs < 6 and (1 << sgs) * 10 * nb < lanes_x10 * 1024 * ept:
+        sgs += 1
+    per = 4 * -(-band_px // (4 * bt)) if vec4 else -(-band_px // bt)
+    return {"band_px": band_px, "nb": nb, "bt": bt, "vec4": vec4, "sgs": sgs, "ept": ept, "K": bins * per, "last_px": hw - (nb - 1) * band_px}
+
+
+def vox_form(plan, njobs, normalize, twopass=False):
+    """The string eemflow_voxelize_last_form gives for vox_plan's plan."""
+    if plan is None:
+        return "j1:direct" + ("", "+moments+norm", "+moments+stats")[normalize]
+    band = f"band{plan['bt']}_{'v4' if plan['vec4'] else 'v1'}_s{plan['sgs']}"
+    head = f"j{njobs}:bin_e{plan['ept']}+{band}"
+    if normalize == 1 and twopass:
+        return f"{head}_moments+{band}_normalised"
+    return head + ("_raw", "_raw_sums+norm", "_raw_sums+stats")[normalize]
+
+
+# sgs, log2 of the lanes that share a run, is the smallest s in 2..6 with 2^s 10 nb >= L 1024 EPT, L = 40 where 1024 EPT < 4 nb, else 17.
+# s = 2 needs nb >= 1024 EPT (L = 40; nb <= 1023) or nb >= 436 EPT together with nb <= 256 EPT (L = 17): unreachable.  3 .. 6 are reached.
+VOX_SGS_REACHABLE = (3, 4, 5, 6)
+
+
+def vox_events(kind, seed, n, h, w, bins=5):
+    """Time-sorted (n, 4) f64 events [t, x, y, p].
+    clustered  70 % of the events in one 40 x 40 patch (one hot band, many votes per cell), as tests/test_gpu_parity.py's;
+    hostile    clustered, with 12 % strays: x in [w, w + 4), y in [h, 3 h) and y in [-2 h, 0) (flat-index semantics: votes move by whole
+               planes, the t2 == -1 branch, votes that leave the grid), the image's last pixel, and eight events at t_last;
+    dyadic     integer timestamps in [0, 2^20], t0 = 0, t_last = 2^20, uniform pixels, and a tenth of the events doubled by an event of
+               the opposite polarity (cells that cancel to exactly 0); with strays as `hostile` when h * w > 4096;
+    equal, one_voxel, same_t   the degenerate sets below (dT = 0)."""
+    rng = np.random.default_rng(seed)
+    if kind in ("equal", "one_voxel", "same_t"):
+        # dT = 0: every event in bin 0 with a left vote of +-1.  equal: distinct pixels, polarity +1 (an all-equal grid: sd 0);
+        # one_voxel: one pixel (c = 1: sd NaN); same_t: repeated pixels, both polarities (integer voxels, some cancel to 0)
+        pix = {"equal": lambda: rng.choice(h * w, n, replace=False), "one_voxel": lambda: np.full(n, (h // 2) * w + w // 3),
+               "same_t": lambda: rng.integers(0, h * w, n)}[kind]()
+        p = rng.integers(0, 2, n) * 2.0 - 1.0 if kind == "same_t" else np.ones(n)
+        return np.ascontiguousarray(np.stack([np.full(n, 7.5), (pix % w).astype(np.float64), (pix // w).astype(np.float64), p], 1))
+    if kind == "dyadic":
+        m = max(1, n - n // 10)
+        t = rng.integers(0, VOX_T_DYADIC + 1, m).astype(np.float64)
+        x = rng.integers(0, w, m).astype(np.float64)
+        y = rng.integers(0, h, m).astype(np.float64)
+        p = rng.integers(0, 2, m) * 2.0 - 1.0
+        if h * w > 4096:
+            k = rng.random(m) < 0.05
+            y = np.where(k, np.where(rng.random(m) < 0.5, h + rng.integers(0, 2 * h, m), -1.0 - rng.integers(0, 2 * h, m)), y)
+        twin = rng.choice(m, n - m, replace=False) if n > m else np.zeros(0, dtype=np.int64)
+        ev = np.stack([np.concatenate([t, t[twin]]), np.concatenate([x, x[twin]]), np.concatenate([y, y[twin]]),
+                       np.concatenate([p, -p[twin]])], 1)
+        ev = ev[np.argsort(ev[:, 0], kind="stable")]
+        ev[0, 0], ev[-1, 0] = 0.0, float(VOX_T_DYADIC)
+        return np.ascontiguousarray(ev)
+    hot = rng.random(n) < 0.7
+    ph, pw = min(40, h), min(40, w)
+    x = np.where(hot, rng.integers(0, pw, n) + (w - pw) // 2, rng.integers(0, w, n)).astype(np.float64)
+    y = np.where(hot, rng.integers(0, ph, n) + (h - ph) // 2, rng.integers(0, h, n)).astype(np.float64)
+    t = np.sort(rng.uniform(100.0, 50100.0, n))
+    p = rng.integers(0, 2, n) * 2.0 - 1.0
+    if kind == "hostile":
+        r = rng.random(n)
+        x = np.where(r < 0.04, w + rng.integers(0, 4, n), x)
+        y = np.where((r >= 0.04) & (r < 0.08), h + rng.integers(0, 2 * h, n), y)
+        y = np.where((r >= 0.08) & (r < 0.12), -1.0 - rng.integers(0, 2 * h, n), y)
+        p = np.where(rng.random(n) < 0.1, 0.0, p)                  # polarity 0 counts as -1
+        x[n // 2], y[n // 2] = w - 1.0, h - 1.0                    # the last pixel of the last band
+        t[-min(8, n):] = t[-1]
+    else:
+        assert kind == "clustered", kind
+    return np.ascontiguousarray(np.stack([t, x, y, p], 1))
+
+
+def vox_votes(events, bins, h, w):
+    """vox_vote of voxel.hip (loader_utils.py:476-523) restated: per event the int64 index outputs il / ir (-1 where the reference masks the
+    vote), the fp32 votes vl / vr, the unmasked flat indices and `inl` / `inr`: the vote is not masked AND its own flat index lies in
+    [0, bins h w) - the flat-index semantics of index_add_ on the flattened grid, under which both kernels drop the rest."""
+    ev = np.asarray(events, dtype=np.float64)
+    t0 = ev[0, 0]
+    dT = ev[-1, 0] - t0
+    if dT == 0:
+        dT = 1.0
+    ts = (float(bins - 1) * (ev[:, 0] - t0)) / dT
+    xs, ys = ev[:, 1].astype(np.int64), ev[:, 2].astype(np.int64)              # truncation
+    pol = ev[:, 3].astype(np.float32)
+    pol[pol == 0] = -1
+    tis = np.floor(ts)
+    tl = tis.astype(np.int64)
+    dts = (ts - tis).astype(np.float32)
+    vl, vr = pol * (np.float32(1.0) - dts), pol * dts
+    okl = (tis < bins) & (tis >= 0)
+    okr = ((tis + 1) < bins) & (tis >= 0)
+    plane = h * w
+    total = bins * plane
+    fl = xs + ys * w + tl * plane
+    fr = fl + plane
+    return {"il": np.where(okl, fl, -1), "ir": np.where(okr, fr, -1), "vl": vl, "vr": vr, "okl": okl, "okr": okr, "flat_l": fl, "flat_r": fr,
+            "inl": okl & (fl >= 0) & (fl < total), "inr": okr & (fr >= 0) & (fr < total), "tl": tl, "pix": xs + ys * w, "total": total}
+
+
+def vox_exact(events, bins, h, w, votes=None):
+    """Per occupied cell (flat index in `cells`, ascending): `sum`, the fp64 sum of its votes in event order (left votes first); `res`,
+    the error-free residual exact sum - `sum` (TwoSum along the way flags the cells where an addition rounded; math.fsum of the votes and
+    -sum gives those cells' residual, correctly rounded); `abs`, the sum of |votes|; `count`, the votes."""
+    import math
+    V = votes if votes is not None else vox_votes(events, bins, h, w)
+    cells = np.concatenate([V["flat_l"][V["inl"]], V["flat_r"][V["inr"]]])
+    vals = np.concatenate([V["vl"][V["inl"]], V["vr"][V["inr"]]]).astype(np.float64)
+    order = np.argsort(cells, kind="stable")
+    c, v = cells[order], vals[order]
+    uniq, start, count = np.unique(c, return_index=True, return_counts=True)
+    cid = np.repeat(np.arange(len(uniq)), count)
+    rank = np.arange(len(c)) - np.repeat(start, count)
+    by_rank = np.argsort(rank, kind="stable")
+    maxc = int(count.max()) if len(count) else 0
+    edge = np.searchsorted(rank[by_rank], np.arange(maxc + 1))
+    s = np.zeros(len(uniq))
+    rounded = np.zeros(len(uniq), dtype=bool)
+    for r in range(maxc):
+        sel = by_rank[edge[r]:edge[r + 1]]
+        k, x = cid[sel], v[sel]
+        a = s[k]
+        t = a + x
+        bb = t - a
+        e = (a - (t - bb)) + (x - bb)                               # TwoSum: a + x = t + e exactly
+        s[k] = t
+        rounded[k] |= e != 0
+    res = np.zeros(len(uniq))
+    for k in np.nonzero(rounded)[0]:
+        res[k] = math.fsum(list(v[start[k]:start[k] + count[k]]) + [-s[k]])
+    return {"cells": uniq, "sum": s, "res": res, "abs": np.bincount(cid, weights=np.abs(v), minlength=len(uniq)), "count": count,
+            "total": V["total"]}
+
+
+def vox_dense(E, key="sum", dtype=np.float64):
+    out = np.zeros(E["total"], dtype=dtype)
+    out[E["cells"]] = E[key]
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _vox_empty_cells_zero(name, form, got, g):
+    """Everything outside the occupied cells is +0.0 (no stray vote, no -0.0, no sentinel left behind)."""
+    stray = int(np.count_nonzero(_bits(got))) - int(np.count_nonzero(_bits(g)))
+    if stray:
+        raise StageError(f"{name} [{form}]: {stray} cells that received no vote are not +0.0")
+
+
+def vox_check_raw_exact(name, got, E, form, allow_residual=True):
+    """The banded path's contract (and, on dyadic inputs, the direct path's): a cell is the exact sum of its votes rounded once."""
+    got = np.ascontiguousarray(got, dtype=np.float32).reshape(-1)
+    g, s = got[E["cells"]], E["sum"]
+    r32 = s.astype(np.float32)
+    inexact = E["res"] != 0
+    differ = _bits(g) != _bits(r32)
+    bad = differ & ~inexact
+    n_in = int(inexact.sum())
+    if n_in:
+        up, dn = np.nextafter(r32, np.float32(np.inf)), np.nextafter(r32, np.float32(-np.inf))
+        below = r32.astype(np.float64) <= s
+        lo, hi = np.where(below, r32, dn), np.where(below, up, r32)
+        bad |= inexact & (g != lo) & (g != hi)
+    LOG.append({"name": name, "form": form + ":exact", "n": len(s), "differ": int(differ.sum()), "inexact": n_in,
+                "of_bound": n_in / max(1, len(s)) / VOX_RESIDUAL_SHARE})
+    if n_in and not allow_residual:
+        raise StageError(f"{name} [{form}]: {n_in} cells of an input that must sum exactly have a residual")
+    if n_in > VOX_RESIDUAL_SHARE * len(s):
+        raise StageError(f"{name} [{form}]: {n_in} of {len(s)} occupied cells have a residual: more than {VOX_RESIDUAL_SHARE:g} of them")
+    if bool(bad.any()):
+        i = int(np.nonzero(bad)[0][0])
+        raise StageError(f"{name} [{form}]: {int(bad.sum())} of {len(s)} occupied cells are not their exact sum rounded once; the first at flat "
+                         f"index {int(E['cells'][i])} ({int(E['count'][i])} votes): got {float(g[i])!r}, exact {float(s[i])!r} -> {float(r32[i])!r}")
+    _vox_empty_cells_zero(name, form, got, g)
+
+
+def vox_check_raw_counted(name, got, E, form):
+    """The direct path on generic inputs: fp32 atomics in any order, k = votes - 1 roundings against sum |votes|."""
+    got = np.ascontiguousarray(got, dtype=np.float32).reshape(-1)
+    g = got[E["cells"]]
+    k = torch.from_numpy(np.maximum(E["count"] - 1, 0).astype(np.float64))
+    check_counted(name, torch.from_numpy(g), torch.from_numpy(E["sum"]), torch.from_numpy(E["abs"]), k, form + ":counted")
+    _vox_empty_cells_zero(name, form, got, g)
+
+
+def vox_moment_bounds(raw, K):
+    """fp64 moments of the non-zero voxels of a raw grid and the bounds above for a path that folds K cells per thread in fp32."""
+    v = np.asarray(raw, dtype=np.float64).reshape(-1)
+    v = v[v != 0]
+    c = v.size
+    if c == 0:
+        return {"c": 0, "mean": 0.0, "sd": float("nan"), "any": False, "scale": False, "dmean": 0.0, "dsd": 0.0}
+    m = float(v.sum() / c)
+    m2 = float(((v - m) ** 2).sum())
+    sd = float(np.sqrt(m2 / (c - 1))) if c > 1 else float("nan")
+    dS = K * U * float(np.abs(v).sum())
+    dQ = (K + 1) * U * float((v * v).sum())
+    dm2 = dQ + 2 * abs(m) * dS + dS * dS / c
+    dsd = dm2 / (2 * sd * (c - 1)) + U * sd if sd > 0 else 0.0
+    return {"c": c, "mean": m, "sd": sd, "any": True, "scale": bool(sd > 0), "dmean": dS / c + U * abs(m), "dsd": dsd, "dm2": dm2, "m2": m2}
+
+
+def vox_check_record(name, rec, raw, K, form):
+    """The deferred record {mean, sd, scale, any} against the fp64 moments of the raw grid in front of it."""
+    rec = np.asarray(rec, dtype=np.float32).astype(np.float64)
+    M = vox_moment_bounds(raw, K)
+    if M["scale"] and not M["sd"] > 4 * M["dsd"]:
+        raise StageError(f"{name} [{form}]: the case does not decide `scale`: sd {M['sd']:.3g} against its bound {M['dsd']:.3g}")
+    want_any, want_scale = (1.0 if M["any"] else 0.0), (1.0 if M["scale"] else 0.0)
+    if rec[3] != want_any or rec[2] != want_scale:
+        raise StageError(f"{name} [{form}]: record flags scale {rec[2]}, any {rec[3]}; {M['c']} non-zero voxels, sd {M['sd']!r}")
+    em, es = abs(rec[0] - M["mean"]), (abs(rec[1] - M["sd"]) if M["scale"] else 0.0)
+    LOG.append({"name": name, "form": form + ":record", "n": M["c"], "of_bound": max(em / max(M["dmean"], 1e-300), es / max(M["dsd"], 1e-300)) if M["any"] else 0.0,
+                "mean_share": em / max(M["dmean"], 1e-300), "sd_share": es / max(M["dsd"], 1e-300)})
+    if not M["scale"] and rec[1] != 1.0:
+        raise StageError(f"{name} [{form}]: scale is 0, yet the record's sd is {rec[1]!r}, not 1")
+    if not em <= M["dmean"]:
+        raise StageError(f"{name} [{form}]: mean {rec[0]!r} against {M['mean']!r}: |diff| {em:.4g} > {M['dmean']:.4g} (K = {K})")
+    if M["scale"] and not es <= M["dsd"]:
+        raise StageError(f"{name} [{form}]: sd {rec[1]!r} against {M['sd']!r}: |diff| {es:.4g} > {M['dsd']:.4g} (K = {K})")
+    return M
+
+
+def vox_normalise_f32(raw, rec):
+    """(v - mean) / sd on the non-zero voxels in fp32, operation by operation as vox_norm_kernel, the band kernel's normalised mode and
+    conv_enc1.hip's consumer of the record evaluate it."""
+    raw = np.ascontiguousarray(raw, dtype=np.float32)
+    mean, sd, scale, anyv = (np.float32(r) for r in rec)
+    if anyv == 0:
+        return raw.copy()
+    out = raw - mean
+    if scale != 0:
+        out = out / sd
+    return np.where(raw != 0, out, raw).astype(np.float32)
+
+
+def vox_check_normalised(name, got, raw, K, form):
+    """A normalised grid against fp64 (v - m) / sd of the raw grid, by the bound derived above."""
+    got = np.asarray(got, dtype=np.float32).astype(np.float64).reshape(-1)
+    v = np.asarray(raw, dtype=np.float64).reshape(-1)
+    M = vox_moment_bounds(raw, K)
+    nz = v != 0
+    if bool((got[~nz] != 0).any()):
+        raise StageError(f"{name} [{form}]: {int((got[~nz] != 0).sum())} zero voxels were changed by the normalisation")
+    if not M["any"]:
+        return M
+    d = v[nz] - M["mean"]
+    if M["scale"]:
+        ref = d / M["sd"]
+        bound = (np.abs(ref) * (2 * U + M["dsd"] / M["sd"]) + M["dmean"] / M["sd"]) * ER_SLACK + TINY
+    else:
+        ref = d
+        bound = (np.abs(d) * U + M["dmean"]) * ER_SLACK + TINY
+    err = np.abs(got[nz] - ref)
+    LOG.append({"name": name, "form": form + ":normalised", "n": int(nz.sum()), "of_bound": float((err / bound).max())})
+    bad = ~(err <= bound)
+    if bool(bad.any()):
+        i = int(np.argmax(np.where(bad, err / bound, 0)))
+        raise StageError(f"{name} [{form}]: {int(bad.sum())} of {int(nz.sum())} normalised voxels are outside their bound; the worst: got "
+                         f"{got[nz][i]!r}, ref {ref[i]!r}, |diff| {err[i]:.4g} against {bound[i]:.4g}")
+    return M
+
+
+def vox_check_indices(name, il, ir, V, form):
+    for key, got in (("il", il), ("ir", ir)):
+        got = np.asarray(got)
+        if got.dtype != np.int64 or not np.array_equal(got, V[key]):
+            bad = np.nonzero(got != V[key])[0]
+            raise StageError(f"{name} [{form}]: {len(bad)} of {len(got)} {key} indices differ; the first at event {int(bad[0])}: "
+                             f"got {int(got[bad[0]])}, reference {int(V[key][bad[0]])}")
+
+
+# The cases of tests/test_gpu_vox_fp64.py: name -> (kind, n (a list: the sets of one eemflow_voxelize_many call), h, w, bins, modes, options).
+# Modes: raw (normalize 0, with the index outputs), deferred (2), norm (1), twopass (1 under EEM_VOX_TWOPASS=1).  Options: direct
+# (EEM_VOX_DIRECT=1), misalign (the grid starts 4 bytes past a 16-byte boundary).  Shapes are the smallest that reach the form, worked out
+# from vox_plan: band_px is 64 below 64 x 512 pixels, (h w / 512 rounded up to 4) above, at most 9216 / bins.
+_ALL = ("raw", "deferred", "norm", "twopass")
+VOX_MANY_32 = [1 + (k * 577) % 2900 for k in range(32)]          # ragged: set 0 is a single event, twelve sets fill three binning blocks, eight one
+VOX_CASES = {
+    # BT 256 (bands of up to 24 KiB): vec4 off by h w % 4 (37 x 53), on (260 x 346); both end in a short band (41 of 64, 24 of 176 pixels)
+    "bt256_v1_s6": ("hostile", 5_000, 37, 53, 3, _ALL, {}),
+    "bt256_v4_s3": ("hostile", 50_000, 260, 346, 5, _ALL, {}),
+    "bt256_misaligned": ("hostile", 50_000, 260, 346, 5, ("deferred", "norm", "twopass"), {"misalign": True}),
+    # BT 512 (24 .. 40 KiB): 64 bins of 64 pixels = 32 KiB; 5 bins of 752 pixels, last band 480
+    "bt512_s5": ("clustered", 20_000, 64, 64, 64, _ALL, {}),
+    "bt512_s4": ("hostile", 50_000, 480, 800, 5, _ALL, {}),
+    # BT 1024 (above 40 KiB): 64 bins of 144 pixels and 5 bins of 1800 pixels, 72 KiB each
+    "bt1024_bins64": ("clustered", 20_000, 192, 384, 64, ("deferred", "norm"), {}),
+    "bt1024_720p": ("clustered", 50_000, 720, 1280, 5, _ALL, {}),
+    # the binning kernel's 1, 2, 4, 8 events per thread at the smallest counts that select them, on 33 bands of 64 pixels (the last 32):
+    # runs of 31 .. 250 records for 64 lanes, the clean-up loop from EPT 4 on.  Dyadic: exact whatever the count
+    "ept1": ("dyadic", 524_288, 40, 52, 3, ("deferred",), {}),
+    "ept2": ("dyadic", 524_289, 40, 52, 3, ("deferred",), {}),
+    "ept4": ("dyadic", 1_048_577, 40, 52, 3, ("deferred",), {}),
+    "ept8": ("dyadic", 2_097_153, 40, 52, 3, ("raw", "norm"), {}),
+    # dyadic inputs with fewer than 8 votes per cell: banded and direct path bitwise the exact sum
+    "dyadic_banded": ("dyadic", 6_000, 60, 80, 5, _ALL, {}),
+    "dyadic_direct": ("dyadic", 6_000, 60, 80, 5, ("raw", "deferred", "norm"), {"direct": True}),
+    # the direct kernel on generic inputs (four runs of each mode) and by size: band_px 304 x 64 bins = 19 456 cells; 65 bins
+    "generic_direct": ("hostile", 20_000, 60, 80, 5, ("raw", "deferred"), {"direct": True}),
+    "direct_by_cells": ("dyadic", 20_000, 480, 644, 64, ("deferred",), {}),
+    "direct_by_bins": ("dyadic", 3_000, 20, 24, 65, ("raw", "norm"), {}),
+    # degenerate sets
+    "one_event": ("clustered", 1, 37, 53, 3, _ALL, {}),
+    "one_event_direct": ("clustered", 1, 37, 53, 3, ("deferred", "norm"), {"direct": True}),
+    "one_voxel": ("one_voxel", 5, 37, 53, 3, ("deferred", "norm", "twopass"), {}),
+    "one_voxel_direct": ("one_voxel", 5, 37, 53, 3, ("deferred", "norm"), {"direct": True}),
+    "equal_voxels": ("equal", 300, 37, 53, 3, ("deferred", "norm", "twopass"), {}),
+    "same_t": ("same_t", 900, 37, 53, 3, _ALL, {}),
+    "bins1": ("hostile", 1_500, 37, 53, 1, _ALL, {}),
+    # eemflow_voxelize_many: 1, 2 and 32 ragged sets; a set with fewer binning blocks than the longest, a set of one event
+    "many1": ("hostile", [2_500], 40, 52, 3, ("deferred",), {}),
+    "many2": ("hostile", [1, 2_500], 40, 52, 3, ("deferred", "twopass"), {}),
+    "many32": ("hostile", VOX_MANY_32, 40, 52, 3, ("raw", "deferred", "norm"), {}),
+    "many2_direct": ("hostile", [700, 1], 20, 24, 65, ("deferred",), {}),
+}
+VOX_MODE_NORMALIZE = {"raw": 0, "deferred": 2, "norm": 1, "twopass": 1}
+
+
+def vox_case_form(name, mode):
+    kind, n, h, w, bins, modes, opt = VOX_CASES[name]
+    ns = n if isinstance(n, list) else [n]
+    plan = vox_plan(ns, bins, h, w, aligned=not opt.get("misalign", False), direct=opt.get("direct", False))
+    # (EEM_VOX_TWOPASS=<r> takes the two band passes while the longest set has at most one event per r voxels)
+    return plan, vox_form(plan, len(ns), VOX_MODE_NORMALIZE[mode], mode == "twopass" and max(ns) <= bins * h * w)
+
+
+def vox_case_events(name):
+    kind, n, h, w, bins, modes, opt = VOX_CASES[name]
+    ns = n if isinstance(n, list) else [n]
+    return [vox_events(kind, ob_seed("vox", name, k), m, h, w, bins) for k, m in enumerate(ns)]
+
+
+# Every launch sequence the cases reach, as eemflow_voxelize_last_form names it (tests/test_fp64_bounds_vox.py: vox_plan gives exactly these;
+# the GPU module: every one was reported).  BT 256 / 512 / 1024, vec4 on and off (by h w % 4 and by the pointer), sgs 3 .. 6, EPT 1 .. 8, the
+# three modes and what follows them, 1 / 2 / 32 jobs, the direct kernel with and without moments.
+VOX_FORMS = {
+    "j1:bin_e1+band1024_v4_s3_moments+band1024_v4_s3_normalised", "j1:bin_e1+band1024_v4_s3_raw", "j1:bin_e1+band1024_v4_s3_raw_sums+norm",
+    "j1:bin_e1+band1024_v4_s3_raw_sums+stats", "j1:bin_e1+band256_v1_s3_moments+band256_v1_s3_normalised",
+    "j1:bin_e1+band256_v1_s3_raw_sums+norm", "j1:bin_e1+band256_v1_s3_raw_sums+stats",
+    "j1:bin_e1+band256_v1_s6_moments+band256_v1_s6_normalised", "j1:bin_e1+band256_v1_s6_raw", "j1:bin_e1+band256_v1_s6_raw_sums+norm",
+    "j1:bin_e1+band256_v1_s6_raw_sums+stats", "j1:bin_e1+band256_v4_s3_moments+band256_v4_s3_normalised", "j1:bin_e1+band256_v4_s3_raw",
+    "j1:bin_e1+band256_v4_s3_raw_sums+norm", "j1:bin_e1+band256_v4_s3_raw_sums+stats",
+    "j1:bin_e1+band256_v4_s5_moments+band256_v4_s5_normalised", "j1:bin_e1+band256_v4_s5_raw", "j1:bin_e1+band256_v4_s5_raw_sums+norm",
+    "j1:bin_e1+band256_v4_s5_raw_sums+stats", "j1:bin_e1+band256_v4_s6_raw_sums+stats",
+    "j1:bin_e1+band512_v4_s4_moments+band512_v4_s4_normalised", "j1:bin_e1+band512_v4_s4_raw", "j1:bin_e1+band512_v4_s4_raw_sums+norm",
+    "j1:bin_e1+band512_v4_s4_raw_sums+stats", "j1:bin_e1+band512_v4_s5_moments+band512_v4_s5_normalised", "j1:bin_e1+band512_v4_s5_raw",
+    "j1:bin_e1+band512_v4_s5_raw_sums+norm", "j1:bin_e1+band512_v4_s5_raw_sums+stats", "j1:bin_e2+band256_v4_s6_raw_sums+stats",
+    "j1:bin_e4+band256_v4_s6_raw_sums+stats", "j1:bin_e8+band256_v4_s6_raw", "j1:bin_e8+band256_v4_s6_raw_sums+norm", "j1:direct",
+    "j1:direct+moments+norm", "j1:direct+moments+stats", "j2:bin_e1+band256_v4_s6_moments+band256_v4_s6_normalised",
+    "j2:bin_e1+band256_v4_s6_raw_sums+stats", "j32:bin_e1+band256_v4_s6_raw", "j32:bin_e1+band256_v4_s6_raw_sums+norm",
+    "j32:bin_e1+band256_v4_s6_raw_sums+stats",
+}

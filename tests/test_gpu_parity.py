@@ -473,7 +473,8 @@ def _clustered_events(seed, n, h, w, wrap=False):
 def test_voxelizer_binned_path_equals_direct_path_and_oracle(monkeypatch, h, w, bins, n, wrap):
     """The LDS-band voxelizer (count / bin / band kernels) against the direct atomic kernel of the same library
     (EEM_VOX_DIRECT=1) and the oracle, on clustered events: identical int64 indices, same support, values to fp32
-    summation-order round-off, raw and normalised.  The last two cases: bands of 112 KiB of LDS; a grid too large for bands (both runs take the direct kernel)."""
+    summation-order round-off, raw and normalised.  The last two cases: grids too large for bands (more than 19 200 cells per band at 1023 bands:
+    both take the direct kernel in every mode, as eemflow_voxelize_last_form reports)."""
     ev = _clustered_events(h * 7 + bins, n, h, w, wrap)
     seq = EventSequence(None, {"height": h, "width": w}, features=ev.copy(), timestamp_multiplier=1e6,
                         convert_to_relative=True)
