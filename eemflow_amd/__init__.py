@@ -13,6 +13,7 @@ from .augmentor import AugPlan, apply_host, augment_many   # noqa: F401
 from .eemflow import EEMFlow            # noqa: F401
 from .events import pack_events_many, read_event_columns   # noqa: F401
 from .iwe import contrast_many, fwl, fwl_loss, fwl_many, iwe, iwe_many, warp_events   # noqa: F401
+from .tsimg import avg_timestamps, avg_timestamps_many, rsat, rsat_many, timestamp_loss, timestamp_loss_many   # noqa: F401
 from .metrics import fb_check          # noqa: F401
 from .padder import InputPadder         # noqa: F401
 from .smooth import smoothness_loss, smoothness_many   # noqa: F401

@@ -64,8 +64,15 @@ def build_parser():
                                 'ground truth needed - to the loss (not in the reference; the samples then carry their events, every model '
                                 'trains through the autograd engine and EEMFlow predicts at the full frame; needs --device_batches or an '
                                 'un-augmented dataset)')
+            q.add_argument('--timestamp_weight', default=0.0, type=float, metavar='W',
+                           help='add W times the average-timestamp term - the sum of squares of the image of average timestamps of the '
+                                'batch\'s events warped by the last prediction, forward plus backward, no ground truth needed - to the '
+                                'loss (not in the reference; under every rule of --contrast_weight: the samples carry their events, every '
+                                'model trains through the autograd engine and EEMFlow predicts at the full frame; needs --device_batches '
+                                'or an un-augmented dataset)')
             q.add_argument('--self_supervised', action='store_true',
-                           help='with --contrast_weight: train on the contrast term alone, the ground-truth flow is not read')
+                           help='with --contrast_weight (or --timestamp_weight, --photo_weight, --ssim_weight): train on that term alone, '
+                                'the ground-truth flow is not read')
             q.add_argument('--smooth_weight', default=0.0, type=float, metavar='W',
                            help='add W times the edge-aware smoothness of the last prediction, weighted by the edges of the old event '
                                 'volume, to the loss (Loss_tools.edge_aware_smoothness_order1/2 of the reference; every model then '
@@ -131,6 +138,10 @@ def build_parser():
             q.add_argument('--fwl', action='store_true',
                            help='evaluation: add the flow warp loss of every sample - the variance of the image of its events warped by the '
                                 'estimated flow over the variance of the event-count image, no ground truth needed - to every line')
+            q.add_argument('--rsat', action='store_true',
+                           help='evaluation: add RSAT of every sample - the average-timestamp loss of its events warped by the estimated '
+                                'flow over that loss under zero flow, below 1 where the flow sharpens the events, no ground truth needed - '
+                                'to every line')
             q.add_argument('--vis_events', action='store_true', help='with -v: also the red / blue images of both event volumes, their density in the file name')
             q.add_argument('--print_epe', action='store_true', help="with -v: the sample's AEE in the name of the estimated flow's file")
             q.add_argument('--visualize_every', default=1, type=int, metavar='N', help='with -v: every N-th sample only (the reference: every sample)')
@@ -213,8 +224,11 @@ def train(args):
     from .hrem import HREMEventFlow
     photo = float(getattr(args, "photo_weight", 0.0))
     ssim = float(getattr(args, "ssim_weight", 0.0))
-    if getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0 and photo == 0.0 and ssim == 0.0:
-        raise SystemExit("--self_supervised needs a --contrast_weight, a --photo_weight or an --ssim_weight: there is no other loss")
+    tsw = float(getattr(args, "timestamp_weight", 0.0))
+    if (getattr(args, "self_supervised", False) and float(getattr(args, "contrast_weight", 0.0)) == 0.0 and photo == 0.0 and ssim == 0.0
+            and tsw == 0.0):
+        raise SystemExit("--self_supervised needs a --contrast_weight, a --photo_weight or an --ssim_weight (or a --timestamp_weight): "
+                         "there is no other loss")
     # one process per GPU under torchrun: every rank trains on its shard of the samples, the trainer all-reduces the flat gradient
     # (RCCL), rank 0 writes the logs and checkpoints
     rank, local_rank, world = parallel.init_distributed()
@@ -224,7 +238,8 @@ def train(args):
         parallel.pin_host_threads_to_gpu_numa(parallel.local_device_index(local_rank))
     config = load_config(args.config)
     contrast = float(getattr(args, "contrast_weight", 0.0))
-    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0 and photo == 0.0 and ssim == 0.0)    # (these terms need the full frame)
+    on_events = contrast != 0.0 or tsw != 0.0                                        # a term that reads the samples' events
+    model = build_model(args.model_name, config, training=True, mesh=contrast == 0.0 and photo == 0.0 and ssim == 0.0 and tsw == 0.0)    # (these terms need the full frame)
     config["train"]["lr"] = args.lr                                                  # train_EEMFlow_HREM.py:56-59
     config["train"]["wdecay"] = args.wd
     config["train"]["num_steps"] = args.train_iters
@@ -243,13 +258,13 @@ def train(args):
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
     train_set = HREMEventFlow(args=config["data_loader"]["train"]["args"], train=True, root=args.data_root, device=dev,
-                              with_events=contrast != 0.0, **device_events_kw(args, HREMEventFlow))
-    if contrast != 0.0 and train_set.augmentor is not None and not args.device_batches:
+                              with_events=on_events, **device_events_kw(args, HREMEventFlow))
+    if on_events and train_set.augmentor is not None and not args.device_batches:
         # the host route flips the volumes without telling where the events went; get_batch hands out batch['events_map']
-        raise SystemExit("--contrast_weight with an augmented dataset needs --device_batches: only batches assembled on the device carry "
+        raise SystemExit(("--contrast_weight" if contrast != 0.0 else "--timestamp_weight") + " with an augmented dataset needs --device_batches: only batches assembled on the device carry "
                          "the event map of their augmentation")
     sampler = torch.utils.data.distributed.DistributedSampler(train_set, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
-    if contrast != 0.0:
+    if on_events:
         args.device_batches = True                                   # (un-augmented: get_batch all the same - it stacks nothing ragged)
     if args.num_workers > 0 or args.device_batches:   # the reference's worker count: here host threads that read / inflate / voxelize samples ahead
         from .loader import ThreadedBatchLoader
@@ -273,11 +288,11 @@ def train(args):
     # EEMFlow: the fused step inside the library; E-RAFT / EEMFlow+: the reference's statement sequence over the operator-level
     # autograd route (their data-parallel exchange is the flat-gradient all-reduce in TrainRaftEvents._train_iters_autograd)
     smooth = float(getattr(args, "smooth_weight", 0.0))
-    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and photo == 0.0 and ssim == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has none of the terms)
+    engine = "fused" if args.model_name == "EEMFlow" and contrast == 0.0 and tsw == 0.0 and photo == 0.0 and ssim == 0.0 and smooth == 0.0 else "autograd"     # (the fused trainer has none of the terms)
     tr = harness.TrainRaftEvents(loader, None, lr=tcfg["lr"], wdecay=tcfg["wdecay"], epsilon=tcfg["epsilon"],
                                  num_steps=tcfg["num_steps"], clip=tcfg["clip"], gamma=tcfg["gamma"], logger=logger,
                                  start_iteration=start_iteration, engine=engine, mixed_precision=tcfg.get("mixed_precision", True),
-                                 contrast_weight=contrast, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args), **photo_kw(args), **ssim_kw(args))
+                                 contrast_weight=contrast, timestamp_weight=tsw, supervised=not getattr(args, "self_supervised", False), **smooth_kw(args), **photo_kw(args), **ssim_kw(args))
     for epoch in range(start_epoch, max(args.train_iters // args.val_iters, 1)):
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -312,7 +327,7 @@ def test(args):
     dev = torch.device(args.device)
     coalesce = args.coalesce if args.model_name == 'EEMFlow' else 1      # (forward_many is EEMFlow's)
     test_set = HREMEventFlow(args=config["data_loader"]["test"]["args"], train=False, root=args.data_root, device=dev,
-                             deferred_norm=coalesce > 1, with_events=args.fwl, **device_events_kw(args, HREMEventFlow))
+                             deferred_norm=coalesce > 1, with_events=args.fwl or args.rsat, **device_events_kw(args, HREMEventFlow))
     model = model.to(dev)
     sequences = [args.test_sequence] if args.test_sequence else list(test_set.nori_list.keys())
     ev = harness.TestRaftEvents(test_set, tuple(config["val_img_size"]), logger=logger)
@@ -323,6 +338,8 @@ def test(args):
         extra["fb_check"] = tuple(args.fb_check)
     if args.fwl:
         extra["fwl"] = True
+    if args.rsat:
+        extra["rsat"] = True
     if args.visualize:
         extra.update(visualize_map=True, vis_events=args.vis_events, print_epe=args.print_epe, visualize_every=args.visualize_every,
                      save_path=save_path)

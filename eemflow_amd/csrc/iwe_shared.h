@@ -152,7 +152,7 @@ __device__ __forceinline__ unsigned block_exscan(unsigned v, unsigned* sh) {
 struct IwePlan {
     int rows;                // image rows per band
     int nb;                  // bands
-    int cells;               // fp64 cells of a band: 2 * rows * w
+    int cells;               // fp64 cells of a band: cpp * rows * w
 };
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -161,13 +161,14 @@ constexpr long IWE_MAX_BLOCKS = 4096;                              // 16.7 M eve
 
 inline bool iwe_direct_forced() { return sw_on<SW_EEM_IWE_DIRECT>(); }
 
-// the band layout of an h x w frame for binning blocks of up to `ept_max` events per thread, or false: the direct form serves it
-inline bool iwe_plan(long nmax, int h, int w, IwePlan* pl, int ept_max = 4) {
+// the band layout of an h x w frame for binning blocks of up to `ept_max` events per thread, or false: the direct form serves it.
+// cpp: fp64 LDS cells per pixel of a band - 2 for the image and the gradient (both channels), 4 for tsimg.hip's D and N planes
+inline bool iwe_plan(long nmax, int h, int w, IwePlan* pl, int ept_max = 4, int cpp = 2) {
     if (iwe_direct_forced() || iwe_blocks(nmax, ept_max) > IWE_MAX_BLOCKS) return false;
     // 9216 fp64 cells (72 KB) per band: two blocks per CU; a frame wider than that still gets one-row bands up to 150 KB of LDS
-    long rows = 9216 / (2L * w);
+    long rows = 9216 / ((long)cpp * w);
     if (rows < 1) {
-        if (2L * w > 19200) return false;                      // 150 KB of fp64 cells beside the static tables
+        if ((long)cpp * w > 19200) return false;                      // 150 KB of fp64 cells beside the static tables
         rows = 1;
     }
     const long spread = std::max(1L, (h + 239L) / 240);            // small frames: still up to a few hundred bands
@@ -175,7 +176,7 @@ inline bool iwe_plan(long nmax, int h, int w, IwePlan* pl, int ept_max = 4) {
     if ((h + rows - 1) / rows > VT - 1) return false;              // thread nb of a binning block holds the slab's fill
     pl->rows = (int)rows;
     pl->nb = (int)((h + rows - 1) / rows);
-    pl->cells = (int)(2 * rows * w);
+    pl->cells = (int)(cpp * rows * w);
     return true;
 }
 

@@ -27,7 +27,7 @@ import torch
 
 from .metrics import flow_error, flow_error_from_sums, flow_error_sums, flow_error_sums_many
 from . import parallel
-from .train import EEMFlowTrainer, contrast_loss, photo_loss, sequence_loss, smoothness_loss, ssim_loss
+from .train import EEMFlowTrainer, contrast_loss, photo_loss, sequence_loss, smoothness_loss, ssim_loss, timestamp_loss
 
 
 class Logger:
@@ -144,7 +144,8 @@ class TestRaftEvents:
         return preds[-1]
 
     def test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
-                            fb_check=None, visualize_map=False, vis_events=False, print_epe=False, visualize_every=1, save_path=None, fwl=False):
+                            fb_check=None, visualize_map=False, vis_events=False, print_epe=False, visualize_every=1, save_path=None, fwl=False,
+                            rsat=False):
         """The evaluation loop of test_mvsec.py:580-597.  It reads the LAST prediction of every sample only (run_network, :1455): a
         model that can skip forming the earlier ones (ERAFT.final_only) does so for the duration of the call.
         stream = n > 0 (stride 1, a model with forward_stream - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset of consecutive windows with
@@ -170,7 +171,15 @@ class TestRaftEvents:
         (eemflow_amd.iwe.fwl_many, t_ref="end"; the measure of Test.inference_img_warp_loss, test_mvsec.py:753-852, which needs no
         ground truth) - by ONE fwl_many call per chunk on the chunk's stream.  Every per-sample line gains
         '  FWL: {:2.6f}  meanFWL:{:2.6f}' (NaN samples - a constant count image - are left out of the mean) and every sequence one
-        summary line "Mean FWL: {:.6f}".  Off (the default): lines, numbers and launches are unchanged."""
+        summary line "Mean FWL: {:.6f}".  Off (the default): lines, numbers and launches are unchanged.
+        rsat (all four loops; a dataset built with with_events=True): RSAT of every sample's last prediction - the average-timestamp
+        loss of the old window's events warped by the flow over that loss under zero flow (eemflow_amd.tsimg.rsat_many, t_ref="end";
+        below 1 where the flow sharpens the events, no ground truth needed) - by ONE rsat_many call per chunk on the chunk's stream.
+        Every per-sample line gains '  RSAT: {:2.6f}  meanRSAT:{:2.6f}' (after FWL's fields; NaN samples are left out of the mean) and
+        every sequence one summary line "Mean RSAT: {:.6f}".  Off (the default): lines, numbers and launches are unchanged."""
+        if rsat and not getattr(self.dataset, "with_events", False):
+            raise ValueError(f"rsat= needs a dataset whose samples carry their events (with_events=True: MvsecEventFlow, MvsecEventFlow_dt4, "
+                             f"HREMEventFlow); {type(self.dataset).__name__} was built without")
         if fwl and not getattr(self.dataset, "with_events", False):
             raise ValueError(f"fwl= needs a dataset whose samples carry their events (with_events=True: MvsecEventFlow, MvsecEventFlow_dt4, "
                              f"HREMEventFlow); {type(self.dataset).__name__} was built without")
@@ -203,6 +212,8 @@ class TestRaftEvents:
             extra = {"fb_check": fb_check} if fb_check is not None else {}
             if fwl:
                 extra["fwl"] = True
+            if rsat:
+                extra["rsat"] = True
             if visualize_map:
                 extra["visualize"] = dict(vis_events=bool(vis_events), print_epe=bool(print_epe), every=int(visualize_every), save_path=save_path)
             return self._test_multi_sequence(model, epoch, sequence_list, stride, frames_in_flight, loader_threads, coalesce, stream, **extra)
@@ -214,7 +225,7 @@ class TestRaftEvents:
                 writer.close(reraise=False)
 
     def _test_multi_sequence(self, model, epoch=0, sequence_list=(), stride=10, frames_in_flight=1, loader_threads=0, coalesce=1, stream=0,
-                             fb_check=None, visualize=None, fwl=False):
+                             fb_check=None, visualize=None, fwl=False, rsat=False):
         """coalesce > 1 (a model with forward_many - EEMFlow, EEMFlow_cdc, ERAFT - and a dataset with get_samples): that many samples are read, voxelized by
         ONE voxelizer launch sequence and handed to ONE model.forward_many call - n independent batch-1 samples riding a batch-n chain of
         launches, every sample in its own tensors; raw volumes with a normalisation record (HREMEventFlow(deferred_norm=True)) are
@@ -263,15 +274,23 @@ class TestRaftEvents:
                 viz_images = {}                                  # visualize: sample -> its images, converted on the chunk's stream
                 fwl_extra = {}                                   # fwl: sample -> its flow warp loss (a 0-dim device tensor)
                 fwl_count = 0
+                rsat_extra = {}                                  # rsat: sample -> its RSAT (a 0-dim device tensor)
+                rsat_count = 0
 
                 def warp_loss(chunk, carriers, f_ests):
-                    """The chunk's flow warp losses by ONE fwl_many call on the current stream; carriers: the samples (or stream
-                    targets), each with its 'events' and 'events_offset'."""
-                    from .iwe import fwl_many     # (the package's attribute `iwe` is the one-job function, not the module)
-                    vals = fwl_many([c_['events'] for c_ in carriers], [f_[0].contiguous().float() for f_ in f_ests],
-                                        offset=carriers[0]['events_offset'])
-                    for i_, idx in enumerate(chunk):
-                        fwl_extra[idx] = vals[i_]
+                    """The chunk's flow warp losses by ONE fwl_many call on the current stream (and its RSATs by ONE rsat_many
+                    call); carriers: the samples (or stream targets), each with its 'events' and 'events_offset'."""
+                    flows_ = [f_[0].contiguous().float() for f_ in f_ests]
+                    if fwl:
+                        from .iwe import fwl_many     # (the package's attribute `iwe` is the one-job function, not the module)
+                        vals = fwl_many([c_['events'] for c_ in carriers], flows_, offset=carriers[0]['events_offset'])
+                        for i_, idx in enumerate(chunk):
+                            fwl_extra[idx] = vals[i_]
+                    if rsat:
+                        from .tsimg import rsat_many
+                        vals = rsat_many([c_['events'] for c_ in carriers], flows_, offset=carriers[0]['events_offset'])
+                        for i_, idx in enumerate(chunk):
+                            rsat_extra[idx] = vals[i_]
                 writer = None
                 if visualize is not None:
                     from . import viz
@@ -304,11 +323,12 @@ class TestRaftEvents:
                         writer.submit('{:d}_events2_{:.3f}.jpg'.format(idx + 1, d2), events[1])
 
                 def retire():
-                    nonlocal iters, n_points, fwl_count
+                    nonlocal iters, n_points, fwl_count, rsat_count
                     idx, k, sums, keep = pending.popleft()
                     with torch.cuda.stream(streams[k]):
                         aee, p1, p3, n_points, s_ee, aee_gt, s_gt = flow_error_from_sums(sums)
                         fwl_val = float(fwl_extra.pop(idx)) if idx in fwl_extra else None
+                        rsat_val = float(rsat_extra.pop(idx)) if idx in rsat_extra else None
                         if idx in viz_images:
                             submit(idx, aee)
                     for name, v in (("aee", aee), ("sum", s_ee), ("aee_gt", aee_gt), ("sum_gt", s_gt), ("p1", p1), ("p3", p3)):
@@ -324,6 +344,11 @@ class TestRaftEvents:
                             acc["fwl"] += fwl_val
                             fwl_count += 1
                         line += '  FWL: {:2.6f}  meanFWL:{:2.6f}'.format(fwl_val, acc["fwl"] / fwl_count if fwl_count else float("nan"))
+                    if rsat_val is not None:
+                        if rsat_val == rsat_val:                 # NaN (no loss under zero flow) stays out of the mean
+                            acc["rsat"] += rsat_val
+                            rsat_count += 1
+                        line += '  RSAT: {:2.6f}  meanRSAT:{:2.6f}'.format(rsat_val, acc["rsat"] / rsat_count if rsat_count else float("nan"))
                     print(line)
 
                 indices = [idx for idx in range(len(self.dataset)) if idx % stride == 0]
@@ -352,7 +377,7 @@ class TestRaftEvents:
                         sums_fb = flow_error_sums_many(f_gts, f_ests, cons, is_car=self.is_car, evaluation_type="sparse")
                         for i_, idx in enumerate(chunk):
                             fb_extra[idx] = (fb_masks[0][i_].mean(), sums_fb[i_])
-                    if fwl:
+                    if fwl or rsat:
                         warp_loss(chunk, targets, f_ests)
                     if visualize is not None:
                         convert(chunk, f_ests, f_gts, vol_pairs)
@@ -377,7 +402,7 @@ class TestRaftEvents:
                         evs_ = [s_['event_valid'].to(dev).sum(0) for s_ in samples] if (sparse and all('event_valid' in s_ for s_ in samples)) else None
                         all_sums = flow_error_sums_many(f_gts, f_ests, evs_, is_car=self.is_car,        # the chunk's statistics by one launch
                                                         evaluation_type="sparse" if evs_ is not None else "dense")
-                        if fwl:
+                        if fwl or rsat:
                             warp_loss(chunk, samples, f_ests)
                         if visualize is not None:
                             norms = None
@@ -404,7 +429,7 @@ class TestRaftEvents:
                         f_gt = sample['flow'].to(dev)[None].float()
                         ev = sample['event_valid'].to(dev).sum(0) if ('event_valid' in sample and sparse) else None
                         sums = flow_error_sums(f_gt, f_est, ev, is_car=self.is_car, evaluation_type="sparse" if ev is not None else "dense")
-                        if fwl:
+                        if fwl or rsat:
                             warp_loss([idx], [sample], [f_est])
                         if visualize is not None and idx % visualize["every"] == 0:
                             vols_ = [(sample['event_volume_old'].to(dev)[None], sample['event_volume_new'].to(dev)[None])] if visualize["vis_events"] else None
@@ -426,6 +451,8 @@ class TestRaftEvents:
                                                                   1. - acc["p3"] / iters, n_points), True)
                 if fwl:
                     self.logger.write_line("Mean FWL: {:.6f}".format(acc["fwl"] / fwl_count if fwl_count else float("nan")), True)
+                if rsat:
+                    self.logger.write_line("Mean RSAT: {:.6f}".format(acc["rsat"] / rsat_count if rsat_count else float("nan")), True)
                 mean_aee += acc["aee"] / iters
                 mean_out += 1. - acc["p3"] / iters
                 aee_list.append(acc["aee"] / iters)
@@ -472,6 +499,11 @@ class TrainRaftEvents:
     carry their events (a dataset built with with_events=True; get_batch adds 'events_map', batches without it use 'events_offset'),
     and the prediction must be at the event frame's size (not out_mesh_size).
 
+    timestamp_weight (the autograd engine only): timestamp_weight * train.timestamp_loss(last prediction, batch['events'],
+    batch['events_map']) is added to the loss - the average-timestamp term (tsimg.py), beside the contrast term and under its rules:
+    the batches carry their events, the prediction is at the event frame's size.  supervised=False is satisfied by a timestamp_weight
+    alone.  With timestamp_weight == 0 nothing is computed and nothing changes.
+
     smooth_weight (the autograd engine only): smooth_weight * train.smoothness_loss(predictions, batch['event_volume_old'] as the
     model received it) is added to the loss - the edge-aware smoothness regulariser of order smooth_order with smooth_constant,
     smooth_weight_type ('gauss', 'exp') and smooth_error ('L1', 'abs_robust'); of the last prediction, or with smooth_all=True of all
@@ -501,10 +533,14 @@ class TrainRaftEvents:
                  supervised=True, smooth_weight=0.0, smooth_order=1, smooth_constant=1.0, smooth_weight_type="gauss", smooth_error="L1",
                  smooth_all=False, photo_weight=0.0, photo_kind="census", photo_occ=False, photo_all=False, photo_q=0.4,
                  photo_charbonnier=False, photo_max_distance=3, ssim_weight=0.0, ssim_occ=False, ssim_all=False, ssim_c1=float("inf"),
-                 ssim_c2=9e-6):
+                 ssim_c2=9e-6, timestamp_weight=0.0):
         if engine not in ("fused", "autograd"):
             raise ValueError("engine must be 'fused' or 'autograd'")
         self.contrast_weight, self.supervised = float(contrast_weight), bool(supervised)
+        self.timestamp_weight = float(timestamp_weight)
+        if engine == "fused" and self.timestamp_weight != 0.0:
+            raise ValueError("TrainRaftEvents: the average-timestamp term (timestamp_weight != 0) is honoured by engine='autograd' only - "
+                             "the fused trainer has no average-timestamp term")
         if engine == "fused" and (self.contrast_weight != 0.0 or not self.supervised):
             raise ValueError("TrainRaftEvents: the contrast term (contrast_weight != 0, supervised=False) is honoured by engine='autograd' "
                              "only - the fused trainer has no contrast term")
@@ -524,9 +560,10 @@ class TrainRaftEvents:
                                  "trainer has no SSIM term")
             from .ssim import _settings as ssim_settings
             ssim_settings("TrainRaftEvents", ssim_occ, ssim_c1, ssim_c2, 0.01)
-        if not self.supervised and self.contrast_weight == 0.0 and self.photo_weight == 0.0 and self.ssim_weight == 0.0:
+        if (not self.supervised and self.contrast_weight == 0.0 and self.photo_weight == 0.0 and self.ssim_weight == 0.0
+                and self.timestamp_weight == 0.0):
             raise ValueError("TrainRaftEvents: supervised=False leaves no loss without a contrast_weight or a photo_weight (or an "
-                             "ssim_weight)")
+                             "ssim_weight or a timestamp_weight)")
         self.smooth_weight, self.smooth_all = float(smooth_weight), bool(smooth_all)
         self.smooth_kw = dict(order=smooth_order, constant=smooth_constant, weight_type=smooth_weight_type, error_type=smooth_error)
         if self.smooth_weight != 0.0:
@@ -570,6 +607,8 @@ class TrainRaftEvents:
             self.optimizer.zero_grad()
             if self.contrast_weight != 0.0:
                 self._contrast_inputs(batch)                       # (before any GPU work: a loader without events fails at once)
+            if self.timestamp_weight != 0.0:
+                self._contrast_inputs(batch, "timestamp_weight")
             e1 = batch['event_volume_old'].to(dev).float()
             e2 = batch['event_volume_new'].to(dev).float()
             need_back = (self.photo_weight != 0.0 and self.photo_occ) or (self.ssim_weight != 0.0 and self.ssim_occ)
@@ -582,6 +621,8 @@ class TrainRaftEvents:
                 loss, metrics = 0.0, {"epe": float("nan")}
             if self.contrast_weight != 0.0:
                 loss = loss + self.contrast_weight * self._contrast_term(flow_list[-1], batch, e1)
+            if self.timestamp_weight != 0.0:
+                loss = loss + self.timestamp_weight * self._timestamp_term(flow_list[-1], batch, e1)
             if self.smooth_weight != 0.0:
                 loss = loss + self.smooth_weight * self._smooth_term(flow_list, e1)
             if self.photo_weight != 0.0:
@@ -615,10 +656,11 @@ class TrainRaftEvents:
         return model
 
     @staticmethod
-    def _contrast_inputs(batch):
-        """(event sets, maps) of a batch for the contrast term: 'events_map' where get_batch made one, else the pure offset maps."""
+    def _contrast_inputs(batch, what="contrast_weight"):
+        """(event sets, maps) of a batch for the contrast term (and the average-timestamp term): 'events_map' where get_batch made one,
+        else the pure offset maps."""
         if 'events' not in batch:
-            raise ValueError("TrainRaftEvents: contrast_weight needs batches that carry their events - build the dataset with "
+            raise ValueError(f"TrainRaftEvents: {what} needs batches that carry their events - build the dataset with "
                              "with_events=True (its get_batch / samples then have 'events')")
         maps = batch.get('events_map')
         if maps is None:
@@ -633,6 +675,16 @@ class TrainRaftEvents:
             raise ValueError(f"TrainRaftEvents: the contrast term needs the prediction at the event frame's size {tuple(volume.shape[-2:])}, "
                              f"got {tuple(flow_pred.shape[-2:])} - a model with out_mesh_size=True predicts the mesh flow")
         return contrast_loss(flow_pred, events, maps).float()
+
+    @classmethod
+    def _timestamp_term(cls, flow_pred, batch, volume):
+        """train.timestamp_loss of the last prediction on the batch's events (float32, as the supervised loss is)."""
+        events, maps = cls._contrast_inputs(batch, "timestamp_weight")
+        if tuple(flow_pred.shape[-2:]) != tuple(volume.shape[-2:]):
+            raise ValueError(f"TrainRaftEvents: the average-timestamp term needs the prediction at the event frame's size "
+                             f"{tuple(volume.shape[-2:])}, got {tuple(flow_pred.shape[-2:])} - a model with out_mesh_size=True predicts "
+                             "the mesh flow")
+        return timestamp_loss(flow_pred, events, maps).float()
 
     def _smooth_term(self, flow_list, volume):
         """train.smoothness_loss of the predictions against the old event volume (float32, as the supervised loss is); a prediction

@@ -32,6 +32,9 @@ in y) times w_k * tau to each in-frame sample neighbour k of (xe, ye).  `iwe`, `
 EVENT MAPS.  `maps=` gives one affine map (ax, bx, ay, by) per event set in place of `offset`: xe = ax * x + bx, ye = ay * y + by - where
 the events of an augmented (resized, flipped, cropped) sample lie in its frame (AugPlan.event_map; the datasets' get_batch hands them
 out as batch['events_map']).  offset = (ox, oy) is the map (1, -ox, 1, -oy), bit for bit.
+
+The image of average timestamps, the objective that divides every pixel by its own vote count, and RSAT are in tsimg.py: the same
+warp, the same votes (its D image is this module's image, bit for bit) and the same gradient kernels under another per-target factor.
 """
 import ctypes
 

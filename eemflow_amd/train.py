@@ -100,6 +100,24 @@ def contrast_loss(flow_pred, events, maps=None):
     return fwl_loss(events, [pred[i] for i in range(pred.shape[0])], maps=maps)
 
 
+def timestamp_loss(flow_pred, events, maps=None):
+    """The average-timestamp term of a (B,2,H,W) prediction: tsimg.timestamp_loss of the B samples' event sets (a list of (N,4) float64
+    device tensors) under flow_pred[i] - the mean over the samples of L(end) + L(start), L the sum of squares of the image of average
+    timestamps over its active pixels; a differentiable 0-dim float64 CUDA tensor whose backward is the library's
+    eemflow_tsimg_grad_many (csrc/tsimg.hip) and lands in flow_pred.  maps: one (ax, bx, ay, by) per sample, where its events lie in
+    the prediction's frame (batch['events_map']); None: the identity."""
+    from .tsimg import timestamp_loss as term
+    if not torch.is_tensor(flow_pred) or flow_pred.dim() != 4 or flow_pred.shape[1] != 2:
+        raise ValueError("timestamp_loss: the prediction is a (B,2,H,W) tensor")
+    if not flow_pred.is_cuda:
+        raise _lib.EEMFlowHipError("timestamp_loss: CUDA (ROCm) tensors required - there is no CPU path")
+    events = list(events)
+    if len(events) != flow_pred.shape[0]:
+        raise ValueError(f"timestamp_loss: one event set per sample; got {len(events)} sets for a batch of {flow_pred.shape[0]}")
+    pred = flow_pred.float().contiguous()
+    return term(events, [pred[i] for i in range(pred.shape[0])], maps=maps)
+
+
 def smoothness_loss(flow_preds, img, gamma=None, **kw):
     """The edge-aware smoothness term of a model's predictions (a list of (B,2,H,W) tensors, the last one final) against the shared
     edge image `img` ((B,C,H,W), in training the old event volume; None: unweighted): smooth.smoothness_loss of the last prediction

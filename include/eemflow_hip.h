@@ -315,6 +315,44 @@ int eemflow_iwe_grad_many(int k, const double* const* events, const int64_t* n, 
                           const double* scale, const double (*maps)[4], int h, int w, const float* const* iwe, const double* moments,
                           const double* coef, float* const* grads, void* stream);
 
+/* Images of average timestamps of k (1..32) jobs of one frame size by ONE launch sequence.  A job is an eemflow_iwe_map_many job (the
+ * same HOST arrays, the same warp, votes and drops) plus the scalar eps > 0.  An event's timestamp value is a = max(1 - |tau|, 0),
+ * tau = (t - t0) * scale, rounded to fp32 once (ah).  Per channel and cell, in unfused fp64: D = sum of the votes' weights and
+ * N = sum of weight * ah, both with the fixed-point weights q / 2^31, q = round(w * 2^31), so iwe_out[i] ([2][h][w] fp32) is bitwise
+ * the image eemflow_iwe_map_many's binned form writes for the job; ts_out[i] ([2][h][w] fp32) is T = N / (D + eps) rounded to fp32
+ * once.  Every cell of both is written.  moments (device, k x 4 doubles): {h*w, sum T^2 over both channels of the stored T, active =
+ * pixels with stored D[0] + D[1] > 0, dropped}, summed in a fixed order; the loss of a job is sum T^2 / (active + 1e-9) (or sum T^2).
+ * EEM_IWE_DIRECT=1 (read per call), a frame wider than 4800 or taller than 1023 one-row bands, or more than 16.7 M events take the
+ * direct atomic form (the same quantised weights, the same D).  Stream-ordered, no host synchronisation; scratch is owned by the
+ * library.
+ * Replaces: warp_events_flow_torch (utils_luo/event_utils.py:9-51) is the warp being composed; the loss itself (the image of average
+ * timestamps of Zhu et al. 2019 / Hagenaars et al. 2021) has no counterpart in the reference. */
+int eemflow_tsimg_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                       const double* scale, const double (*maps)[4], int h, int w, double eps, float* const* iwe_out,
+                       float* const* ts_out, double* moments, void* stream);
+
+/* Gradient of sum T^2 of eemflow_tsimg_many's images with respect to the flows, times a scalar per job: grads[i] ([2][h][w] fp32, HOST
+ * array of device pointers) = coef[i] * d (sum T^2)_i / d flows[i].  events .. eps are the forward's; a NULL flows[i] (zero flow) skips
+ * job i, whose grads[i] is not touched.  iwe and ts (HOST arrays of device pointers) are the D and T images the forward stored; coef is
+ * a DEVICE array of k doubles (the upstream gradient times 1 / (active + 1e-9) for the normalised loss), so nothing synchronises.
+ * Teacher-forced, fp32 roundings straight-through: for an event of channel c at an in-frame target cell
+ * G = ((2.0 * T) * (ah - T)) / (D + eps) in fp64 in this order from the stored T and D of channel c (= dL/dN * ah + dL/dD); from G on
+ * it is eemflow_iwe_grad_many's arithmetic and kernels: dX = sum of G * wy * (+1 or -1), dY likewise, coef * w_k * tau * dX and
+ * coef * w_k * tau * dY to every in-frame sample neighbour, the same conventions at integer positions, the same binned (each
+ * contribution rounded to fp32 first) and direct forms.  Every cell of a gradient is written, an fp64 sum rounded to fp32 once.
+ * Replaces: warp_events_flow_torch (utils_luo/event_utils.py:9-51) is the warp being differentiated; the loss itself has no counterpart
+ * in the reference. */
+int eemflow_tsimg_grad_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
+                            const double* scale, const double (*maps)[4], int h, int w, double eps, const float* const* iwe,
+                            const float* const* ts, const double* coef, float* const* grads, void* stream);
+
+/* Test observable: the launch sequence this thread's last eemflow_tsimg_many / eemflow_tsimg_grad_many call ran, e.g.
+ * "bin_e2+band1024_s3+moments", "direct", "grad_bin_e1+grad_band", "grad_direct"; "" before any call.  A refused call, and a gradient
+ * call without any flow, leave it unchanged.  A string stored on the host beside the launches: no launch, no synchronisation.
+ * Replaces: nothing in the reference - warp_events_flow_torch (utils_luo/event_utils.py:9-51) has one form, and the loss itself has no
+ * counterpart in the reference. */
+int eemflow_tsimg_last_form(char* buf, int cap);
+
 /* Edge-aware smoothness loss of k (1..16) predictions of one shape, and its gradient, by one launch: pred[i] ([B][2][H][W] fp32,
  * contiguous), img[i] ([B][C][H][W] fp32, any C >= 1; a NULL entry, or img == NULL, means every weight is 1) and grad[i] ([B][2][H][W]
  * fp32) are HOST arrays of device pointers, read before the call returns.  For s = order in {1, 2} and both axes (axis 2 = rows, the
