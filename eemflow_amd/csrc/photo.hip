@@ -17,50 +17,21 @@
 // - one stencil pass over m's own taps that GATHERS the neighbours' factors from an LDS plane: no atomics anywhere.  F needs dist on
 // the tile plus r of halo, hence g on 2r of halo.  dL/dYw_c = gray[c] * dL/dg2, so the warp derivative is grey-combined with g2 in the
 // staging pass and kept in registers (a thread owns the same four cells in every phase).
-// A block walks tiles of 16 x 64 cells (grid = tiles, capped at 2048 blocks that stride over them; it depends on the shape alone) and,
-// inside a tile, the jobs: consecutive jobs that name one img1 pointer grey-combine it once.  Per-thread fp64 sums are reduced per wave by
-// shuffles and per block in LDS; the blocks' partial sums go to scratch and are added in a fixed order by a one-wave-per-job launch, so
-// a job's loss and gradient are bitwise the same from run to run and bitwise those of a one-job call.
+// The tile walk, the jobs inside a tile, the partial sums and their fixed-order finish are dense_loss.h's, with its bitwise contract;
+// consecutive jobs that name one img1 pointer grey-combine it once.
 // LDS (census): two g planes of 28 x 76 doubles and the factor plane of 22 x 70: 46.9 KB, static.
 // What bounds it: census is bound by the fp64 sqrt and divides of its taps (two sqrt and three divides per tap in the distance pass, one
 // more sqrt and two more divides in the gradient's pass); abs_robust and charbonnier by one fp64 pow per element; L1 by the four
 // gathers per channel of the warp.
-#include "common.h"
+#include "dense_loss.h"
 #include "warp_px.h"
-
-#include <algorithm>
 
 namespace {
 
-constexpr int PH_TH = 16, PH_TW = 64;
-constexpr int PH_NT = 256;
-constexpr int PH_CELLS = PH_TH * PH_TW / PH_NT;  // cells of the tile per thread: cell n of thread t is row (t + 256 n) / 64, column t % 64
-constexpr int PH_MAX_JOBS = 16;
-constexpr int PH_MAX_BLOCKS = 2048;
 constexpr int PH_RMAX = 3;
-constexpr int PH_GO = 2 * PH_RMAX, PH_GH = PH_TH + 2 * PH_GO, PH_GW = PH_TW + 2 * PH_GO;      // g planes: origin (r0 - 6, c0 - 6)
-constexpr int PH_FO = PH_RMAX, PH_FH = PH_TH + 2 * PH_FO, PH_FW = PH_TW + 2 * PH_FO;          // factor plane: origin (r0 - 3, c0 - 3)
+constexpr int PH_GO = 2 * PH_RMAX, PH_GH = DL_TH + 2 * PH_GO, PH_GW = DL_TW + 2 * PH_GO;      // g planes: origin (r0 - 6, c0 - 6)
+constexpr int PH_FO = PH_RMAX, PH_FH = DL_TH + 2 * PH_FO, PH_FW = DL_TW + 2 * PH_FO;          // factor plane: origin (r0 - 3, c0 - 3)
 enum { PH_ABS_ROBUST = 0, PH_CHARBONNIER = 1, PH_L1 = 2, PH_CENSUS = 3 };
-
-struct PhotoJobs {
-    const float* flow[PH_MAX_JOBS];
-    const float* img1[PH_MAX_JOBS];
-    const float* img2[PH_MAX_JOBS];
-    const float* mask[PH_MAX_JOBS];
-    float* grad[PH_MAX_JOBS];
-};
-
-struct PhotoShape {
-    int B, C, H, W, tiles_x, tiles_y;
-    double sx, sy;               // d ix / du, d iy / dv
-    double n1;                   // the numerator's divisor
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ double gray_of(const double* __restrict__ gray, int c, int C) {
     if (gray) return gray[c];
@@ -68,45 +39,30 @@ __device__ __forceinline__ double gray_of(const double* __restrict__ gray, int c
     return 1.0 / (double)C;
 }
 
-// the derivative of the blend of the corner values v with respect to ix and iy
-__device__ __forceinline__ void blend_grad(const float v[4], const WarpTaps& t, double& dx, double& dy) {
-    const double ww = (double)t.wx, we = (double)(1.f - t.wx), wn = (double)t.wy, ws = (double)(1.f - t.wy);
-    dx = ws * ((double)v[1] - (double)v[0]) + wn * ((double)v[3] - (double)v[2]);
-    dy = we * ((double)v[2] - (double)v[0]) + ww * ((double)v[3] - (double)v[1]);
-}
-
 // ---- sums of the masks (use_occ): block partial sums of mask * [rin <= y < H - rin, rin <= x < W - rin] per job
-__global__ __launch_bounds__(PH_NT) void photo_mask_kernel(PhotoJobs jobs, int k, PhotoShape s, int rin, double* __restrict__ part) {
-    __shared__ double lp[PH_MAX_JOBS][PH_NT / 64];
+__global__ __launch_bounds__(DL_NT) void photo_mask_kernel(DenseJobs jobs, int k, DenseShape s, int rin, double* __restrict__ part) {
+    __shared__ alignas(16) DenseSlots<1> lp;
     const int tid = threadIdx.x;
     const size_t hw = (size_t)s.H * s.W;
-    if (tid < PH_MAX_JOBS * (PH_NT / 64)) (&lp[0][0])[tid] = 0.0;
+    dense_slots_zero(lp, tid);
     __syncthreads();
-    const long tiles = (long)s.B * s.tiles_y * s.tiles_x;
+    const long tiles = dense_tiles(s.B, s.tiles_x, s.tiles_y);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b = (int)(tile / ((long)s.tiles_y * s.tiles_x));
-        const int rem = (int)(tile % ((long)s.tiles_y * s.tiles_x));
-        const int r0 = (rem / s.tiles_x) * PH_TH, c0 = (rem % s.tiles_x) * PH_TW;
+        const auto [b, r0, c0] = dense_tile(tile, s.tiles_x, s.tiles_y);
         for (int job = 0; job < k; ++job) {
             const float* mask = jobs.mask[job];
             double acc = 0.0;
 #pragma unroll
-            for (int n = 0; n < PH_CELLS; ++n) {
-                const int y = r0 + (tid + n * PH_NT) / PH_TW, x = c0 + tid % PH_TW;
+            for (int n = 0; n < DL_CELLS; ++n) {
+                const int y = r0 + dense_cell_row(tid, n), x = c0 + dense_cell_col(tid);
                 if (y < s.H && x < s.W && y >= rin && y < s.H - rin && x >= rin && x < s.W - rin)
                     acc += mask ? (double)mask[(size_t)b * hw + (size_t)y * s.W + x] : 1.0;
             }
-            acc = wave_sum(acc);
-            if ((tid & 63) == 0) lp[job][tid >> 6] += acc;     // a wave owns its slot; tiles arrive in the block's fixed order
+            dense_slots_add(lp, tid, job, acc);
         }
     }
     __syncthreads();
-    if (tid < k) {
-        double v = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < PH_NT / 64; ++wv) v += lp[tid][wv];
-        part[(size_t)tid * gridDim.x + blockIdx.x] = v;
-    }
+    dense_slots_write(lp, tid, k, part);
 }
 
 // one wave per job: den[job] = D.  mode 0: 1;  1: M + 1e-6;  2: M * 2 + 1e-6;  3: (M / n) * 2 + 1e-6
@@ -120,30 +76,18 @@ __global__ __launch_bounds__(64) void photo_den_kernel(const double* __restrict_
     if (lane == 0) den[job] = mode == 0 ? 1.0 : mode == 1 ? m + 1e-6 : mode == 2 ? m * 2.0 + 1e-6 : (m / n) * 2.0 + 1e-6;
 }
 
-// one wave per job: the blocks' partial sums in a fixed order, then L = (S / n1) / D
-__global__ __launch_bounds__(64) void photo_finish_kernel(const double* __restrict__ part, int nblk, double n1, const double* __restrict__ den,
-                                                          double* __restrict__ loss) {
-    const int job = blockIdx.x, lane = threadIdx.x;
-    double v = 0.0;
-    for (int i = lane; i < nblk; i += 64) v += part[(size_t)job * nblk + i];
-    v = wave_sum(v);
-    if (lane == 0) loss[job] = (v / n1) / den[job];
-}
-
 // ---- the pointwise kinds: no neighbours, no LDS but the loss sums
 template <int KIND>
-__global__ __launch_bounds__(PH_NT) void photo_point_kernel(PhotoJobs jobs, int k, PhotoShape s, int use_occ, const double* __restrict__ coef,
+__global__ __launch_bounds__(DL_NT) void photo_point_kernel(DenseJobs jobs, int k, DenseShape s, int use_occ, const double* __restrict__ coef,
                                                             const double* __restrict__ den, double* __restrict__ part, int want_loss) {
-    __shared__ double lp[PH_MAX_JOBS][PH_NT / 64];
+    __shared__ alignas(16) DenseSlots<1> lp;
     const int tid = threadIdx.x;
     const size_t hw = (size_t)s.H * s.W;
-    if (tid < PH_MAX_JOBS * (PH_NT / 64)) (&lp[0][0])[tid] = 0.0;
+    dense_slots_zero(lp, tid);
     __syncthreads();
-    const long tiles = (long)s.B * s.tiles_y * s.tiles_x;
+    const long tiles = dense_tiles(s.B, s.tiles_x, s.tiles_y);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b = (int)(tile / ((long)s.tiles_y * s.tiles_x));
-        const int rem = (int)(tile % ((long)s.tiles_y * s.tiles_x));
-        const int r0 = (rem / s.tiles_x) * PH_TH, c0 = (rem % s.tiles_x) * PH_TW;
+        const auto [b, r0, c0] = dense_tile(tile, s.tiles_x, s.tiles_y);
         for (int job = 0; job < k; ++job) {
             const float* flow = jobs.flow[job] + (size_t)b * 2 * hw;
             const float* img1 = jobs.img1[job] + (size_t)b * s.C * hw;
@@ -153,8 +97,8 @@ __global__ __launch_bounds__(PH_NT) void photo_point_kernel(PhotoJobs jobs, int 
             const double sc = grad ? ((coef ? coef[job] : 1.0) / s.n1) / den[job] : 0.0;
             double acc = 0.0;
 #pragma unroll
-            for (int n = 0; n < PH_CELLS; ++n) {
-                const int y = r0 + (tid + n * PH_NT) / PH_TW, x = c0 + tid % PH_TW;
+            for (int n = 0; n < DL_CELLS; ++n) {
+                const int y = r0 + dense_cell_row(tid, n), x = c0 + dense_cell_col(tid);
                 if (y >= s.H || x >= s.W) continue;
                 const int p = y * s.W + x;
                 const WarpTaps t = warp_taps(flow[p], flow[hw + p], s.H, s.W, p, 1);
@@ -192,20 +136,12 @@ __global__ __launch_bounds__(PH_NT) void photo_point_kernel(PhotoJobs jobs, int 
                     grad[(size_t)b * 2 * hw + hw + p] = (float)(gv * s.sy);
                 }
             }
-            if (want_loss) {
-                acc = wave_sum(acc);
-                if ((tid & 63) == 0) lp[job][tid >> 6] += acc;
-            }
+            if (want_loss) dense_slots_add(lp, tid, job, acc);
         }
     }
     if (!want_loss) return;
     __syncthreads();
-    if (tid < k) {
-        double v = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < PH_NT / 64; ++wv) v += lp[tid][wv];
-        part[(size_t)tid * gridDim.x + blockIdx.x] = v;
-    }
+    dense_slots_write(lp, tid, k, part);
 }
 
 // ---- census
@@ -213,7 +149,7 @@ struct CensusLds {
     double g1[PH_GH * PH_GW];
     double g2[PH_GH * PH_GW];
     double f[PH_FH * PH_FW];
-    double part[PH_MAX_JOBS][PH_NT / 64];
+    DenseSlots<1> part;
 };
 
 struct CensusTap {
@@ -231,19 +167,18 @@ __device__ __forceinline__ CensusTap census_tap(double x1, double x2) {
 }
 
 template <int CHARB>
-__global__ __launch_bounds__(PH_NT) void photo_census_kernel(PhotoJobs jobs, int k, PhotoShape s, int r, int use_occ, double q, double eps,
+__global__ __launch_bounds__(DL_NT) void photo_census_kernel(DenseJobs jobs, int k, DenseShape s, int r, int use_occ, double q, double eps,
                                                              const double* __restrict__ gray, const double* __restrict__ coef,
                                                              const double* __restrict__ den, double* __restrict__ part, int want_loss) {
     __shared__ CensusLds L;
     const int tid = threadIdx.x;
     const int H = s.H, W = s.W, C = s.C;
     const size_t hw = (size_t)H * W;
-    if (tid < PH_MAX_JOBS * (PH_NT / 64)) (&L.part[0][0])[tid] = 0.0;
-    const long tiles = (long)s.B * s.tiles_y * s.tiles_x;
+    dense_slots_zero(L.part, tid);                             // (the job loop's first barrier stands before the first add)
+    const long tiles = dense_tiles(s.B, s.tiles_x, s.tiles_y);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b = (int)(tile / ((long)s.tiles_y * s.tiles_x));
-        const int rem = (int)(tile % ((long)s.tiles_y * s.tiles_x));
-        const int r0 = (rem / s.tiles_x) * PH_TH, c0 = (rem % s.tiles_x) * PH_TW;
+        const DenseTile at = dense_tile(tile, s.tiles_x, s.tiles_y);
+        const int b = at.b, r0 = at.r0, c0 = at.c0;            // (named: the lambdas below capture them)
         const float* cur1 = nullptr;
         for (int job = 0; job < k; ++job) {
             const float* flow = jobs.flow[job] + (size_t)b * 2 * hw;
@@ -256,7 +191,7 @@ __global__ __launch_bounds__(PH_NT) void photo_census_kernel(PhotoJobs jobs, int
             cur1 = jobs.img1[job];
             const double sc = want_grad ? ((coef ? coef[job] : 1.0) / s.n1) / den[job] : 0.0;
             const int hg = want_grad ? 2 * r : r;              // halo of the g planes
-            double gx[PH_CELLS], gy[PH_CELLS];                 // sum_c gray[c] * dYw_c/d(ix, iy) of this thread's cells
+            double gx[DL_CELLS], gy[DL_CELLS];                 // sum_c gray[c] * dYw_c/d(ix, iy) of this thread's cells
             __syncthreads();                                   // the job (or tile) before has read the planes
             // ---- stage g1 and g2: the tile's cells by their owners, then the halo
             auto stage = [&](int y, int x, double& dxs, double& dys) {
@@ -284,12 +219,12 @@ __global__ __launch_bounds__(PH_NT) void photo_census_kernel(PhotoJobs jobs, int
                 if (new1) L.g1[li] = a1;
             };
 #pragma unroll
-            for (int n = 0; n < PH_CELLS; ++n) stage(r0 + (tid + n * PH_NT) / PH_TW, c0 + tid % PH_TW, gx[n], gy[n]);
+            for (int n = 0; n < DL_CELLS; ++n) stage(r0 + dense_cell_row(tid, n), c0 + dense_cell_col(tid), gx[n], gy[n]);
             {
-                const int rw = PH_TW + 2 * hg, cells = (PH_TH + 2 * hg) * rw;
-                for (int idx = tid; idx < cells; idx += PH_NT) {
+                const int rw = DL_TW + 2 * hg, cells = (DL_TH + 2 * hg) * rw;
+                for (int idx = tid; idx < cells; idx += DL_NT) {
                     const int ly = idx / rw - hg, lx = idx % rw - hg;
-                    if (ly >= 0 && ly < PH_TH && lx >= 0 && lx < PH_TW) continue;
+                    if (ly >= 0 && ly < DL_TH && lx >= 0 && lx < DL_TW) continue;
                     double u0, u1;
                     stage(r0 + ly, c0 + lx, u0, u1);
                 }
@@ -332,22 +267,18 @@ __global__ __launch_bounds__(PH_NT) void photo_census_kernel(PhotoJobs jobs, int
             };
             double acc = 0.0;
 #pragma unroll
-            for (int n = 0; n < PH_CELLS; ++n) {
+            for (int n = 0; n < DL_CELLS; ++n) {
                 double term;
-                centre(r0 + (tid + n * PH_NT) / PH_TW, c0 + tid % PH_TW, term);
+                centre(r0 + dense_cell_row(tid, n), c0 + dense_cell_col(tid), term);
                 acc += term;
             }
-            if (want_loss) {
-                // wave-uniform: every lane of the wave arrives here.  A wave owns its slot, tiles arrive in the block's fixed order.
-                acc = wave_sum(acc);
-                if ((tid & 63) == 0) L.part[job][tid >> 6] += acc;
-            }
+            if (want_loss) dense_slots_add(L.part, tid, job, acc);
             if (!want_grad) continue;                          // block-uniform
             {
-                const int rw = PH_TW + 2 * r, cells = (PH_TH + 2 * r) * rw;
-                for (int idx = tid; idx < cells; idx += PH_NT) {
+                const int rw = DL_TW + 2 * r, cells = (DL_TH + 2 * r) * rw;
+                for (int idx = tid; idx < cells; idx += DL_NT) {
                     const int ly = idx / rw - r, lx = idx % rw - r;
-                    if (ly >= 0 && ly < PH_TH && lx >= 0 && lx < PH_TW) continue;
+                    if (ly >= 0 && ly < DL_TH && lx >= 0 && lx < DL_TW) continue;
                     double term;
                     centre(r0 + ly, c0 + lx, term);
                 }
@@ -355,8 +286,8 @@ __global__ __launch_bounds__(PH_NT) void photo_census_kernel(PhotoJobs jobs, int
             __syncthreads();
             // ---- gather: dL/dg2(m) = -sum_k s(m,k) * (F(m) + F(m+k)), then the warp derivative
 #pragma unroll
-            for (int n = 0; n < PH_CELLS; ++n) {
-                const int ly = (tid + n * PH_NT) / PH_TW, lx = tid % PH_TW;
+            for (int n = 0; n < DL_CELLS; ++n) {
+                const int ly = dense_cell_row(tid, n), lx = dense_cell_col(tid);
                 const int y = r0 + ly, x = c0 + lx;
                 if (y >= H || x >= W) continue;
                 const int li = (ly + PH_GO) * PH_GW + (lx + PH_GO), fi = (ly + PH_FO) * PH_FW + (lx + PH_FO);
@@ -380,39 +311,21 @@ __global__ __launch_bounds__(PH_NT) void photo_census_kernel(PhotoJobs jobs, int
     }
     if (!want_loss) return;
     __syncthreads();
-    if (tid < k) {
-        double v = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < PH_NT / 64; ++wv) v += L.part[tid][wv];
-        part[(size_t)tid * gridDim.x + blockIdx.x] = v;
-    }
+    dense_slots_write(L.part, tid, k, part);
 }
-
-inline int photo_blocks(int B, int H, int W, int* tx, int* ty) {
-    *tx = ceil_div(W, PH_TW);
-    *ty = ceil_div(H, PH_TH);
-    const long tiles = (long)B * *tx * *ty;
-    return (int)std::min<long>(tiles, PH_MAX_BLOCKS);
-}
-
-inline bool photo_shape_ok(int B, int H, int W) { return B >= 1 && H >= 1 && W >= 1 && (long)B * H * W <= (1L << 30); }
 
 }  // namespace
 
-extern "C" size_t eemflow_photo_scratch_doubles(int k, int B, int H, int W) {
-    if (k < 1 || k > PH_MAX_JOBS || !photo_shape_ok(B, H, W)) return 0;
-    int tx, ty;
-    return PH_MAX_JOBS + (size_t)k * photo_blocks(B, H, W, &tx, &ty);
-}
+extern "C" size_t eemflow_photo_scratch_doubles(int k, int B, int H, int W) { return dense_scratch_doubles(k, B, H, W, DL_MAX_JOBS, 1); }
 
 extern "C" int eemflow_photo_many(int k, const float* const* flow, const float* const* img1, const float* const* img2,
                                   const float* const* mask, int B, int C, int H, int W, int kind, int use_occ, int charbonnier, int average,
                                   int max_distance, double q, const double* gray, const double* coef, double* loss, float* const* grad,
                                   double* scratch, void* stream_) {
-    EEM_REQUIRE(k >= 1 && k <= PH_MAX_JOBS, "eemflow_photo_many: 1..%d jobs per call; got %d", PH_MAX_JOBS, k);
+    EEM_REQUIRE(k >= 1 && k <= DL_MAX_JOBS, "eemflow_photo_many: 1..%d jobs per call; got %d", DL_MAX_JOBS, k);
     EEM_REQUIRE(kind >= PH_ABS_ROBUST && kind <= PH_CENSUS,
                 "eemflow_photo_many: kind is 0 (abs_robust), 1 (charbonnier), 2 (L1) or 3 (census); got %d", kind);
-    EEM_REQUIRE(photo_shape_ok(B, H, W), "eemflow_photo_many: bad shape B=%d H=%d W=%d", B, H, W);
+    EEM_REQUIRE(dense_shape_ok(B, H, W), "eemflow_photo_many: bad shape B=%d H=%d W=%d", B, H, W);
     EEM_REQUIRE(C >= 1 && (long)B * C * H * W <= (1L << 34), "eemflow_photo_many: bad channel count C=%d", C);
     const int r = max_distance;
     if (kind == PH_CENSUS) {
@@ -420,26 +333,13 @@ extern "C" int eemflow_photo_many(int k, const float* const* flow, const float* 
         EEM_REQUIRE(H > 2 * r && W > 2 * r, "eemflow_photo_many: census with max_distance %d needs H > %d and W > %d; got %dx%d", r, 2 * r,
                     2 * r, H, W);
     }
-    EEM_REQUIRE(flow && img1 && img2, "eemflow_photo_many: flow, img1 or img2 is NULL");
     EEM_REQUIRE(loss || grad, "eemflow_photo_many: neither loss nor grad is asked for");
     EEM_REQUIRE(scratch, "eemflow_photo_many: scratch is NULL (eemflow_photo_scratch_doubles)");
-    PhotoJobs jobs;
-    for (int i = 0; i < PH_MAX_JOBS; ++i) jobs.flow[i] = jobs.img1[i] = jobs.img2[i] = jobs.mask[i] = nullptr, jobs.grad[i] = nullptr;
-    for (int i = 0; i < k; ++i) {
-        EEM_REQUIRE(flow[i] && img1[i] && img2[i], "eemflow_photo_many: job %d lacks its flow, img1 or img2", i);
-        EEM_REQUIRE(!grad || grad[i], "eemflow_photo_many: job %d has no gradient buffer", i);
-        jobs.flow[i] = flow[i];
-        jobs.img1[i] = img1[i];
-        jobs.img2[i] = img2[i];
-        jobs.mask[i] = mask ? mask[i] : nullptr;
-        jobs.grad[i] = grad ? grad[i] : nullptr;
-    }
+    DenseJobs jobs;
+    if (const int rc = dense_fill_jobs(jobs, "eemflow_photo_many", k, flow, img1, img2, mask, grad)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    PhotoShape s;
-    s.B = B, s.C = C, s.H = H, s.W = W;
-    const int nblk = photo_blocks(B, H, W, &s.tiles_x, &s.tiles_y);
-    s.sx = ((double)W / 2.0) * (2.0 / (double)std::max(W - 1, 1));
-    s.sy = ((double)H / 2.0) * (2.0 / (double)std::max(H - 1, 1));
+    DenseShape s;
+    const int nblk = dense_shape(s, B, C, H, W);
     const double n = (double)B * (double)H * (double)W;
     int den_mode;
     if (kind != PH_CENSUS) {
@@ -453,28 +353,28 @@ extern "C" int eemflow_photo_many(int k, const float* const* flow, const float* 
         s.n1 = average ? n : 1.0;
     }
     double* den = scratch;
-    double* part = scratch + PH_MAX_JOBS;
+    double* part = scratch + DL_MAX_JOBS;
     if (den_mode != 0) {
-        hipLaunchKernelGGL(photo_mask_kernel, dim3(nblk), dim3(PH_NT), 0, stream, jobs, k, s, kind == PH_CENSUS ? r : 0, part);
+        hipLaunchKernelGGL(photo_mask_kernel, dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, kind == PH_CENSUS ? r : 0, part);
         EEM_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(photo_den_kernel, dim3(k), dim3(64), 0, stream, part, nblk, den_mode, n, den);
     EEM_HIP_CHECK(hipGetLastError());
     const int wl = loss ? 1 : 0, uo = use_occ ? 1 : 0;
     if (kind == PH_ABS_ROBUST)
-        hipLaunchKernelGGL((photo_point_kernel<PH_ABS_ROBUST>), dim3(nblk), dim3(PH_NT), 0, stream, jobs, k, s, uo, coef, den, part, wl);
+        hipLaunchKernelGGL((photo_point_kernel<PH_ABS_ROBUST>), dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, uo, coef, den, part, wl);
     else if (kind == PH_CHARBONNIER)
-        hipLaunchKernelGGL((photo_point_kernel<PH_CHARBONNIER>), dim3(nblk), dim3(PH_NT), 0, stream, jobs, k, s, uo, coef, den, part, wl);
+        hipLaunchKernelGGL((photo_point_kernel<PH_CHARBONNIER>), dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, uo, coef, den, part, wl);
     else if (kind == PH_L1)
-        hipLaunchKernelGGL((photo_point_kernel<PH_L1>), dim3(nblk), dim3(PH_NT), 0, stream, jobs, k, s, uo, coef, den, part, wl);
+        hipLaunchKernelGGL((photo_point_kernel<PH_L1>), dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, uo, coef, den, part, wl);
     else if (charbonnier)
-        hipLaunchKernelGGL((photo_census_kernel<1>), dim3(nblk), dim3(PH_NT), 0, stream, jobs, k, s, r, uo, q, use_occ ? 1e-6 : 1e-8, gray, coef,
+        hipLaunchKernelGGL((photo_census_kernel<1>), dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, r, uo, q, use_occ ? 1e-6 : 1e-8, gray, coef,
                            den, part, wl);
     else
-        hipLaunchKernelGGL((photo_census_kernel<0>), dim3(nblk), dim3(PH_NT), 0, stream, jobs, k, s, r, uo, q, 0.0, gray, coef, den, part, wl);
+        hipLaunchKernelGGL((photo_census_kernel<0>), dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, r, uo, q, 0.0, gray, coef, den, part, wl);
     EEM_HIP_CHECK(hipGetLastError());
     if (loss) {
-        hipLaunchKernelGGL(photo_finish_kernel, dim3(k), dim3(64), 0, stream, part, nblk, s.n1, den, loss);
+        hipLaunchKernelGGL(dense_finish_kernel, dim3(k), dim3(64), 0, stream, part, nblk, s.n1, den, loss);
         EEM_HIP_CHECK(hipGetLastError());
     }
     return EEM_OK;

@@ -13,54 +13,39 @@
 // The gradient is a GATHER: a tile of 16 x 64 cells computes the q of every term that touches it (a halo of s term rows above and s
 // term columns to the left) into LDS once, then every cell reads its 2 (s + 1) terms - no atomics, so a gradient is bitwise
 // reproducible; a cell is an fp64 sum, times coef, rounded to fp32 once.  The loss counts a term in the tile that holds its first
-// cell; per-thread fp64 sums are reduced per wave by shuffles, per block in LDS, and the blocks' partial sums go to `scratch` and
-// are added in a fixed order by a second small launch: a loss is bitwise the same from run to run.
+// cell, with one accumulator per axis.
 //
-// Up to 16 jobs of one shape ride one launch and are walked INSIDE the tile loop: consecutive jobs that name the same img pointer
-// (E-RAFT's twelve predictions, EEMFlow+'s five, all against one event volume) read img and take the exps once per tile.  The grid
-// depends on the shape alone (tiles, capped at 2048 blocks that stride over them), and a job's arithmetic and summation order do not
-// depend on its neighbours, so a job's results are bitwise those of a one-job call.
+// The tile walk, the jobs inside a tile, the partial sums and their fixed-order finish are dense_loss.h's, with its bitwise contract.
+// Consecutive jobs that name the same img pointer (E-RAFT's twelve predictions, EEMFlow+'s five, all against one event volume) read
+// img and take the exps once per tile.
 // Planes are staged through LDS one at a time (img channel by channel, then each flow channel) with 16-byte row reads where W % 4 == 0
 // and the base is 16-byte aligned; the halo columns and the ragged edge are scalar.  LDS: 40.9 KB at order 2 - three blocks per CU.
-#include "common.h"
-
-#include <algorithm>
+#include "dense_loss.h"
 
 namespace {
 
-constexpr int SM_TH = 16, SM_TW = 64;            // cells per tile: 16 rows x 16 float4
-constexpr int SM_NT = 256;
-constexpr int SM_MAX_JOBS = 16;
-constexpr int SM_MAX_BLOCKS = 2048;
-
 struct SmoothJobs {
-    const float* pred[SM_MAX_JOBS];
-    const float* img[SM_MAX_JOBS];
-    float* grad[SM_MAX_JOBS];
+    const float* pred[DL_MAX_JOBS];
+    const float* img[DL_MAX_JOBS];
+    float* grad[DL_MAX_JOBS];
 };
 
 template <int S>
 struct SmoothLds {
-    float p[SM_TH + 2 * S][SM_TW + 2 * S];       // one plane: rows r0-S .. r0+TH+S-1, columns c0-S .. c0+TW+S-1, zero outside the frame
-    double w2[(SM_TH + S) * SM_TW];              // axis-2 terms: rows r0-S .. r0+TH-1
-    double w3[SM_TH * (SM_TW + S)];              // axis-3 terms: columns c0-S .. c0+TW-1
-    double q2[(SM_TH + S) * SM_TW];
-    double q3[SM_TH * (SM_TW + S)];
-    double part[SM_MAX_JOBS][SM_NT / 64][2];     // loss sums per job and wave: {axis 2, axis 3}
+    float p[DL_TH + 2 * S][DL_TW + 2 * S];       // one plane: rows r0-S .. r0+TH+S-1, columns c0-S .. c0+TW+S-1, zero outside the frame
+    double w2[(DL_TH + S) * DL_TW];              // axis-2 terms: rows r0-S .. r0+TH-1
+    double w3[DL_TH * (DL_TW + S)];              // axis-3 terms: columns c0-S .. c0+TW-1
+    double q2[(DL_TH + S) * DL_TW];
+    double q3[DL_TH * (DL_TW + S)];
+    DenseSlots<2> part;                          // loss sums per job and wave: {axis 2, axis 3}
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 template <int S>
-__device__ __forceinline__ void load_plane(float (*sp)[SM_TW + 2 * S], const float* __restrict__ plane, int r0, int c0, int H, int W,
+__device__ __forceinline__ void load_plane(float (*sp)[DL_TW + 2 * S], const float* __restrict__ plane, int r0, int c0, int H, int W,
                                            bool vec, int tid) {
-    constexpr int R = SM_TH + 2 * S;
-    for (int idx = tid; idx < R * (SM_TW / 4); idx += SM_NT) {
-        const int lr = idx / (SM_TW / 4), v = idx % (SM_TW / 4);
+    constexpr int R = DL_TH + 2 * S;
+    for (int idx = tid; idx < R * (DL_TW / 4); idx += DL_NT) {
+        const int lr = idx / (DL_TW / 4), v = idx % (DL_TW / 4);
         const int r = r0 - S + lr, c = c0 + 4 * v;
         float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f;
         if (r >= 0 && r < H && c < W) {
@@ -78,9 +63,9 @@ __device__ __forceinline__ void load_plane(float (*sp)[SM_TW + 2 * S], const flo
         float* d = &sp[lr][S + 4 * v];
         d[0] = x0, d[1] = x1, d[2] = x2, d[3] = x3;
     }
-    for (int idx = tid; idx < R * 2 * S; idx += SM_NT) {
+    for (int idx = tid; idx < R * 2 * S; idx += DL_NT) {
         const int lr = idx / (2 * S), hc = idx % (2 * S);
-        const int lc = hc < S ? hc : SM_TW + hc;
+        const int lc = hc < S ? hc : DL_TW + hc;
         const int r = r0 - S + lr, c = c0 - S + lc;
         sp[lr][lc] = (r >= 0 && r < H && c >= 0 && c < W) ? plane[(size_t)r * W + c] : 0.0f;
     }
@@ -109,22 +94,20 @@ __device__ __forceinline__ void error_term(double d, bool grad, double& e, doubl
 }
 
 template <int S, int ERR>
-__global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, int B, int C, int H, int W, int weight_type, double constant,
+__global__ __launch_bounds__(DL_NT) void smooth_kernel(SmoothJobs jobs, int k, int B, int C, int H, int W, int weight_type, double constant,
                                                        const double* __restrict__ coef, double* __restrict__ scratch, int want_loss,
                                                        int tiles_x, int tiles_y) {
     __shared__ SmoothLds<S> L;
     const int tid = threadIdx.x;
-    constexpr int N2S = (SM_TH + S) * SM_TW, N3S = SM_TH * (SM_TW + S);
-    constexpr int W3 = SM_TW + S;
+    constexpr int N2S = (DL_TH + S) * DL_TW, N3S = DL_TH * (DL_TW + S);
+    constexpr int W3 = DL_TW + S;
     const double N2 = (double)B * 2.0 * (double)(H - S) * (double)W, N3 = (double)B * 2.0 * (double)H * (double)(W - S);
     const size_t hw = (size_t)H * W;
     const bool w4 = (W & 3) == 0;
-    for (int i = tid; i < SM_MAX_JOBS * (SM_NT / 64) * 2; i += SM_NT) (&L.part[0][0][0])[i] = 0.0;
-    const long tiles = (long)B * tiles_y * tiles_x;
+    dense_slots_zero(L.part, tid);                             // (every job's first barrier stands before the first add)
+    const long tiles = dense_tiles(B, tiles_x, tiles_y);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b = (int)(tile / ((long)tiles_y * tiles_x));
-        const int rem = (int)(tile % ((long)tiles_y * tiles_x));
-        const int r0 = (rem / tiles_x) * SM_TH, c0 = (rem % tiles_x) * SM_TW;
+        const auto [b, r0, c0] = dense_tile(tile, tiles_x, tiles_y);
         const float* cur = nullptr;
         bool have = false;
         for (int job = 0; job < k; ++job) {
@@ -135,8 +118,8 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
                 cur = img;
                 if (!img) {
                     __syncthreads();
-                    for (int idx = tid; idx < N2S; idx += SM_NT) L.w2[idx] = 1.0;
-                    for (int idx = tid; idx < N3S; idx += SM_NT) L.w3[idx] = 1.0;
+                    for (int idx = tid; idx < N2S; idx += DL_NT) L.w2[idx] = 1.0;
+                    for (int idx = tid; idx < N3S; idx += DL_NT) L.w3[idx] = 1.0;
                 } else {
                     const bool vec = w4 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
                     for (int c = 0; c < C; ++c) {
@@ -144,21 +127,21 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
                         load_plane<S>(L.p, img + ((size_t)b * C + c) * hw, r0, c0, H, W, vec, tid);
                         __syncthreads();
                         // every slot belongs to one thread for the whole phase (idx = tid + n * 256)
-                        for (int idx = tid; idx < N2S; idx += SM_NT) {
-                            const int lt = idx / SM_TW, lj = idx % SM_TW;
+                        for (int idx = tid; idx < N2S; idx += DL_NT) {
+                            const int lt = idx / DL_TW, lj = idx % DL_TW;
                             const double g = constant * ((double)L.p[lt][lj + S] - (double)L.p[lt + S][lj + S]);
                             const double f = weight_type == 0 ? g * g : fabs(g);
                             L.w2[idx] = c == 0 ? f : L.w2[idx] + f;
                         }
-                        for (int idx = tid; idx < N3S; idx += SM_NT) {
+                        for (int idx = tid; idx < N3S; idx += DL_NT) {
                             const int li = idx / W3, lu = idx % W3;
                             const double g = constant * ((double)L.p[li + S][lu] - (double)L.p[li + S][lu + S]);
                             const double f = weight_type == 0 ? g * g : fabs(g);
                             L.w3[idx] = c == 0 ? f : L.w3[idx] + f;
                         }
                     }
-                    for (int idx = tid; idx < N2S; idx += SM_NT) L.w2[idx] = exp(-(L.w2[idx] / (double)C));
-                    for (int idx = tid; idx < N3S; idx += SM_NT) L.w3[idx] = exp(-(L.w3[idx] / (double)C));
+                    for (int idx = tid; idx < N2S; idx += DL_NT) L.w2[idx] = exp(-(L.w2[idx] / (double)C));
+                    for (int idx = tid; idx < N3S; idx += DL_NT) L.w3[idx] = exp(-(L.w3[idx] / (double)C));
                 }
             }
             const float* pred = jobs.pred[job];
@@ -173,8 +156,8 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
                 __syncthreads();
                 load_plane<S>(L.p, pred + plane, r0, c0, H, W, vec_p, tid);
                 __syncthreads();
-                for (int idx = tid; idx < N2S; idx += SM_NT) {
-                    const int lt = idx / SM_TW, lj = idx % SM_TW;
+                for (int idx = tid; idx < N2S; idx += DL_NT) {
+                    const int lt = idx / DL_TW, lj = idx % DL_TW;
                     const int t = r0 - S + lt, j = c0 + lj;
                     double q = 0.0;
                     if (t >= 0 && t < H - S && j < W) {
@@ -187,7 +170,7 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
                     }
                     if (want_grad) L.q2[idx] = q;
                 }
-                for (int idx = tid; idx < N3S; idx += SM_NT) {
+                for (int idx = tid; idx < N3S; idx += DL_NT) {
                     const int li = idx / W3, lu = idx % W3;
                     const int i = r0 + li, u = c0 - S + lu;
                     double q = 0.0;
@@ -204,7 +187,7 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
                 if (!want_grad) continue;
                 __syncthreads();
                 // ---- gather: the 2 (S + 1) terms of every cell, axis 2 then axis 3, nearest term first
-                const int li = tid / (SM_TW / 4), v = tid % (SM_TW / 4);
+                const int li = tid / (DL_TW / 4), v = tid % (DL_TW / 4);
                 const int i = r0 + li, j = c0 + 4 * v;
                 if (i >= H || j >= W) continue;
                 float out[4];
@@ -215,7 +198,7 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
 #pragma unroll
                     for (int kk = 0; kk <= S; ++kk) {
                         const double ck = (S == 2 && kk == 1) ? -2.0 : (kk == 0 || kk == 2) ? 1.0 : -1.0;
-                        g += ck * L.q2[(li + S - kk) * SM_TW + lj];
+                        g += ck * L.q2[(li + S - kk) * DL_TW + lj];
                     }
 #pragma unroll
                     for (int kk = 0; kk <= S; ++kk) {
@@ -236,25 +219,12 @@ __global__ __launch_bounds__(SM_NT) void smooth_kernel(SmoothJobs jobs, int k, i
                     if (j + 3 < W) dst[3] = out[3];
                 }
             }
-            if (want_loss) {
-                // wave-uniform: every lane of the wave arrives here.  A wave owns its slot, tiles arrive in the block's fixed order.
-                const double s2 = wave_sum(acc2), s3 = wave_sum(acc3);
-                if ((tid & 63) == 0) {
-                    L.part[job][tid >> 6][0] += s2;
-                    L.part[job][tid >> 6][1] += s3;
-                }
-            }
+            if (want_loss) dense_slots_add(L.part, tid, job, acc2, acc3);
         }
     }
     if (!want_loss) return;
     __syncthreads();
-    if (tid < 2 * k) {
-        const int job = tid >> 1, ax = tid & 1;
-        double s = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < SM_NT / 64; ++wv) s += L.part[job][wv][ax];
-        scratch[((size_t)job * gridDim.x + blockIdx.x) * 2 + ax] = s;
-    }
+    dense_slots_write(L.part, tid, k, scratch);
 }
 
 // one wave per job: the blocks' partial sums in a fixed order, then L = sum2 / N2 + sum3 / N3
@@ -272,31 +242,18 @@ __global__ __launch_bounds__(64) void smooth_finish_kernel(const double* __restr
     if (lane == 0) loss[job] = s2 / N2 + s3 / N3;
 }
 
-inline int smooth_blocks(int B, int H, int W, int* tx, int* ty) {
-    *tx = ceil_div(W, SM_TW);
-    *ty = ceil_div(H, SM_TH);
-    const long tiles = (long)B * *tx * *ty;
-    return (int)std::min<long>(tiles, SM_MAX_BLOCKS);
-}
-
-inline bool smooth_shape_ok(int B, int H, int W) { return B >= 1 && H >= 1 && W >= 1 && (long)B * H * W <= (1L << 30); }
-
 }  // namespace
 
-extern "C" size_t eemflow_smoothness_scratch_doubles(int k, int B, int H, int W) {
-    if (k < 1 || k > SM_MAX_JOBS || !smooth_shape_ok(B, H, W)) return 0;
-    int tx, ty;
-    return (size_t)k * smooth_blocks(B, H, W, &tx, &ty) * 2;
-}
+extern "C" size_t eemflow_smoothness_scratch_doubles(int k, int B, int H, int W) { return dense_scratch_doubles(k, B, H, W, 0, 2); }
 
 extern "C" int eemflow_smoothness_many(int k, const float* const* pred, const float* const* img, int B, int C, int H, int W, int order,
                                        int weight_type, int error_type, double constant, const double* coef, double* loss,
                                        float* const* grad, double* scratch, void* stream_) {
-    EEM_REQUIRE(k >= 1 && k <= SM_MAX_JOBS, "eemflow_smoothness_many: 1..%d jobs per call; got %d", SM_MAX_JOBS, k);
+    EEM_REQUIRE(k >= 1 && k <= DL_MAX_JOBS, "eemflow_smoothness_many: 1..%d jobs per call; got %d", DL_MAX_JOBS, k);
     EEM_REQUIRE(order == 1 || order == 2, "eemflow_smoothness_many: order is 1 or 2; got %d", order);
     EEM_REQUIRE(weight_type == 0 || weight_type == 1, "eemflow_smoothness_many: weight_type is 0 (gauss) or 1 (exp); got %d", weight_type);
     EEM_REQUIRE(error_type == 0 || error_type == 1, "eemflow_smoothness_many: error_type is 0 (L1) or 1 (abs_robust); got %d", error_type);
-    EEM_REQUIRE(smooth_shape_ok(B, H, W), "eemflow_smoothness_many: bad shape B=%d H=%d W=%d", B, H, W);
+    EEM_REQUIRE(dense_shape_ok(B, H, W), "eemflow_smoothness_many: bad shape B=%d H=%d W=%d", B, H, W);
     EEM_REQUIRE(H > order && W > order, "eemflow_smoothness_many: order %d needs H > %d and W > %d (the mean of no terms); got %dx%d", order,
                 order, order, H, W);
     EEM_REQUIRE(pred, "eemflow_smoothness_many: pred is NULL");
@@ -304,7 +261,7 @@ extern "C" int eemflow_smoothness_many(int k, const float* const* pred, const fl
     EEM_REQUIRE(!loss || scratch, "eemflow_smoothness_many: the loss needs scratch (eemflow_smoothness_scratch_doubles)");
     SmoothJobs jobs;
     bool any_img = false;
-    for (int i = 0; i < SM_MAX_JOBS; ++i) jobs.pred[i] = jobs.img[i] = nullptr, jobs.grad[i] = nullptr;
+    for (int i = 0; i < DL_MAX_JOBS; ++i) jobs.pred[i] = jobs.img[i] = nullptr, jobs.grad[i] = nullptr;
     for (int i = 0; i < k; ++i) {
         EEM_REQUIRE(pred[i], "eemflow_smoothness_many: job %d has no prediction", i);
         EEM_REQUIRE(!grad || grad[i], "eemflow_smoothness_many: job %d has no gradient buffer", i);
@@ -316,10 +273,10 @@ extern "C" int eemflow_smoothness_many(int k, const float* const* pred, const fl
     EEM_REQUIRE(!any_img || (C >= 1 && (long)B * C * H * W <= (1L << 34)), "eemflow_smoothness_many: bad channel count C=%d", C);
     hipStream_t stream = (hipStream_t)stream_;
     int tx, ty;
-    const int nblk = smooth_blocks(B, H, W, &tx, &ty);
+    const int nblk = dense_blocks(B, H, W, &tx, &ty);
     const int wl = loss ? 1 : 0;
 #define EEM_SMOOTH_LAUNCH(S, E)                                                                                                       \
-    hipLaunchKernelGGL((smooth_kernel<S, E>), dim3(nblk), dim3(SM_NT), 0, stream, jobs, k, B, C, H, W, weight_type, constant, coef, scratch, \
+    hipLaunchKernelGGL((smooth_kernel<S, E>), dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, B, C, H, W, weight_type, constant, coef, scratch, \
                        wl, tx, ty)
     if (order == 1) {
         if (error_type == 0) EEM_SMOOTH_LAUNCH(1, 0); else EEM_SMOOTH_LAUNCH(1, 1);

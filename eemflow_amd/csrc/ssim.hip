@@ -19,13 +19,10 @@
 //             SA, SB, SC over the up to nine centres whose window holds it (row-major order, zeros where there is no centre):
 //             dL/dYw_c(p) = wpe(p) * (SA + 2 y(p) SB + x(p) SC).  Then, as in photo.hip, the derivative of the bilinear blend at the fp32
 //             tap weights, d ix/du = (W/2) * (2/max(W-1,1)), the sum over the channels in fp64 and one rounding to fp32.  No atomics.
-// A block walks tiles of 16 x 64 cells (grid = tiles, capped at 2048 blocks that stride over them; it depends on the shape alone) and,
-// inside a tile, the jobs, inside a job the channels.  A thread owns the same four cells of the tile in every phase, plus up to two
-// cells of the two-cell ring around it for staging and one centre of the one-cell ring for the factors; aw, inv and fs of its centres
-// live in registers for all channels, the fp32 tap weights are taken again per channel (keeping them costs 44 VGPRs and spills).
-// Per-thread fp64 sums are reduced per wave by shuffles and per block in LDS; the blocks' partial sums go to scratch and are added in
-// a fixed order by a one-wave-per-job launch, so a job's loss and gradient are bitwise the same from run to run and bitwise those of
-// a one-job call.
+// The tile walk, the jobs inside a tile, the partial sums and their fixed-order finish are dense_loss.h's, with its bitwise contract;
+// inside a job the block walks the channels.  Beside its four cells of the tile a thread owns up to two cells of the two-cell ring
+// around it for staging and one centre of the one-cell ring for the factors; aw, inv and fs of its centres live in registers for all
+// channels, the fp32 tap weights are taken again per channel (keeping them costs 44 VGPRs and spills).
 // LDS, static: x, y and w as the fp32 values they are on two cells of halo, 3 planes of 20 x 68 floats (15.9 KB); the three factor planes
 // on one cell of halo, 18 x 66 doubles each (27.8 KB); the loss slots (0.5 KB): 44.3 KB - three blocks per CU by LDS, two by registers
 // (253 VGPRs).  Without a gradient asked for, the outer ring of the staged planes and the factor planes are left alone.
@@ -35,37 +32,20 @@
 // sums, then six fp64 divisions (five by 9, one n / d), in the forward and again in the backward; the four gathers per cell and channel
 // of the warp come second.  1.7 - 1.8 ms per prediction forward + backward at 1280x720, batch 8, C = 5 (profiles/r21_ssim_bench.txt):
 // about twice the arithmetic's count of issue slots, so latency that two waves per SIMD do not hide takes a share (not read from counters).
-#include "common.h"
+#include "dense_loss.h"
 #include "warp_px.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int SS_TH = 16, SS_TW = 64;
-constexpr int SS_NT = 256;
-constexpr int SS_CELLS = SS_TH * SS_TW / SS_NT;    // cells of the tile per thread: cell n of thread t is row (t + 256 n) / 64, column t % 64
-constexpr int SS_MAX_JOBS = 16;
-constexpr int SS_MAX_BLOCKS = 2048;
-constexpr int SS_XH = SS_TH + 4, SS_XW = SS_TW + 4;              // x, y, w planes: origin (r0 - 2, c0 - 2)
-constexpr int SS_FH = SS_TH + 2, SS_FW = SS_TW + 2;              // factor planes: origin (r0 - 1, c0 - 1)
-constexpr int SS_RING2 = SS_XH * SS_XW - SS_TH * SS_TW;          // 336 cells around the tile, two deep
-constexpr int SS_RING1 = SS_FH * SS_FW - SS_TH * SS_TW;          // 164 cells around the tile, one deep
-static_assert(SS_RING1 <= SS_NT, "one ring centre per thread");
+constexpr int SS_XH = DL_TH + 4, SS_XW = DL_TW + 4;              // x, y, w planes: origin (r0 - 2, c0 - 2)
+constexpr int SS_FH = DL_TH + 2, SS_FW = DL_TW + 2;              // factor planes: origin (r0 - 1, c0 - 1)
+constexpr int SS_RING2 = SS_XH * SS_XW - DL_TH * DL_TW;          // 336 cells around the tile, two deep
+constexpr int SS_RING1 = SS_FH * SS_FW - DL_TH * DL_TW;          // 164 cells around the tile, one deep
+static_assert(SS_RING1 <= DL_NT, "one ring centre per thread");
 
-struct SsimJobs {
-    const float* flow[SS_MAX_JOBS];
-    const float* img1[SS_MAX_JOBS];
-    const float* img2[SS_MAX_JOBS];
-    const float* mask[SS_MAX_JOBS];
-    float* grad[SS_MAX_JOBS];
-};
-
-struct SsimShape {
-    int B, C, H, W, tiles_x, tiles_y;
-    double sx, sy;               // d ix / du, d iy / dv
-    double n1;                   // the numerator's divisor
+struct SsimShape : DenseShape {
     double c1, c2, eps;
     int lum, str;                // c1 finite: the luminance term takes part;  c2 finite: the structure term
 };
@@ -77,44 +57,31 @@ struct SsimLds {
     double fa[SS_FH * SS_FW];
     double fb[SS_FH * SS_FW];
     double fc[SS_FH * SS_FW];
-    double part[SS_MAX_JOBS][SS_NT / 64];
+    DenseSlots<1> part;
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// the derivative of the blend of the corner values v with respect to ix and iy (photo.hip's)
-__device__ __forceinline__ void blend_grad(const float v[4], const WarpTaps& t, double& dx, double& dy) {
-    const double ww = (double)t.wx, we = (double)(1.f - t.wx), wn = (double)t.wy, ws = (double)(1.f - t.wy);
-    dx = ws * ((double)v[1] - (double)v[0]) + wn * ((double)v[3] - (double)v[2]);
-    dy = we * ((double)v[2] - (double)v[0]) + ww * ((double)v[3] - (double)v[1]);
-}
 
 // cell r of the two-deep ring, relative to the tile's origin: the rows -2, -1, 16, 17 in full, then the four side columns of rows 0..15
 __device__ __forceinline__ void ring2_pos(int r, int& ly, int& lx) {
     if (r < 4 * SS_XW) {
         const int row = r / SS_XW;
-        ly = row < 2 ? row - 2 : SS_TH + row - 2;
+        ly = row < 2 ? row - 2 : DL_TH + row - 2;
         lx = r % SS_XW - 2;
     } else {
         const int q = r - 4 * SS_XW, j = q & 3;
         ly = q >> 2;
-        lx = j < 2 ? j - 2 : SS_TW + j - 2;
+        lx = j < 2 ? j - 2 : DL_TW + j - 2;
     }
 }
 
 // cell r of the one-deep ring: the rows -1 and 16 in full, then the two side columns of rows 0..15
 __device__ __forceinline__ void ring1_pos(int r, int& ly, int& lx) {
     if (r < 2 * SS_FW) {
-        ly = r < SS_FW ? -1 : SS_TH;
+        ly = r < SS_FW ? -1 : DL_TH;
         lx = r % SS_FW - 1;
     } else {
         const int q = r - 2 * SS_FW;
         ly = q >> 1;
-        lx = (q & 1) ? SS_TW : -1;
+        lx = (q & 1) ? DL_TW : -1;
     }
 }
 
@@ -130,36 +97,28 @@ __device__ __forceinline__ double aw_global(const float* __restrict__ mask, size
 }
 
 // ---- sums of aw (use_occ): block partial sums over the centres per job
-__global__ __launch_bounds__(SS_NT) void ssim_aw_kernel(SsimJobs jobs, int k, SsimShape s, double* __restrict__ part) {
-    __shared__ double lp[SS_MAX_JOBS][SS_NT / 64];
+__global__ __launch_bounds__(DL_NT) void ssim_aw_kernel(DenseJobs jobs, int k, SsimShape s, double* __restrict__ part) {
+    __shared__ alignas(16) DenseSlots<1> lp;
     const int tid = threadIdx.x;
     const size_t hw = (size_t)s.H * s.W;
-    if (tid < SS_MAX_JOBS * (SS_NT / 64)) (&lp[0][0])[tid] = 0.0;
+    dense_slots_zero(lp, tid);
     __syncthreads();
-    const long tiles = (long)s.B * s.tiles_y * s.tiles_x;
+    const long tiles = dense_tiles(s.B, s.tiles_x, s.tiles_y);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b = (int)(tile / ((long)s.tiles_y * s.tiles_x));
-        const int rem = (int)(tile % ((long)s.tiles_y * s.tiles_x));
-        const int r0 = (rem / s.tiles_x) * SS_TH, c0 = (rem % s.tiles_x) * SS_TW;
+        const auto [b, r0, c0] = dense_tile(tile, s.tiles_x, s.tiles_y);
         for (int job = 0; job < k; ++job) {
             const float* mask = jobs.mask[job];
             double acc = 0.0;
 #pragma unroll
-            for (int n = 0; n < SS_CELLS; ++n) {
-                const int y = r0 + (tid + n * SS_NT) / SS_TW, x = c0 + tid % SS_TW;
+            for (int n = 0; n < DL_CELLS; ++n) {
+                const int y = r0 + dense_cell_row(tid, n), x = c0 + dense_cell_col(tid);
                 if (y >= 1 && y <= s.H - 2 && x >= 1 && x <= s.W - 2) acc += aw_global(mask, (size_t)b * hw, y, x, s.W);
             }
-            acc = wave_sum(acc);
-            if ((tid & 63) == 0) lp[job][tid >> 6] += acc;     // a wave owns its slot; tiles arrive in the block's fixed order
+            dense_slots_add(lp, tid, job, acc);
         }
     }
     __syncthreads();
-    if (tid < k) {
-        double v = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < SS_NT / 64; ++wv) v += lp[tid][wv];
-        part[(size_t)tid * gridDim.x + blockIdx.x] = v;
-    }
+    dense_slots_write(lp, tid, k, part);
 }
 
 // one wave per job: den[job] = D = 1, or with use_occ sum(aw) + 1e-6
@@ -171,16 +130,6 @@ __global__ __launch_bounds__(64) void ssim_den_kernel(const double* __restrict__
         m = wave_sum(m);
     }
     if (lane == 0) den[job] = use_occ ? m + 1e-6 : 1.0;
-}
-
-// one wave per job: the blocks' partial sums in a fixed order, then L = (S / n1) / D
-__global__ __launch_bounds__(64) void ssim_finish_kernel(const double* __restrict__ part, int nblk, double n1, const double* __restrict__ den,
-                                                         double* __restrict__ loss) {
-    const int job = blockIdx.x, lane = threadIdx.x;
-    double v = 0.0;
-    for (int i = lane; i < nblk; i += 64) v += part[(size_t)job * nblk + i];
-    v = wave_sum(v);
-    if (lane == 0) loss[job] = (v / n1) / den[job];
 }
 
 // what a centre leaves: l, and the three factors before their scale fs
@@ -243,23 +192,21 @@ __device__ __forceinline__ double aw_staged(const float* __restrict__ pw, int li
 }
 
 // (two waves per SIMD: the allocator then keeps within 256 VGPRs and nothing spills; three would need 168 and spills)
-__global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, SsimShape s, int use_occ, const double* __restrict__ coef,
+__global__ __launch_bounds__(DL_NT, 2) void ssim_kernel(DenseJobs jobs, int k, SsimShape s, int use_occ, const double* __restrict__ coef,
                                                      const double* __restrict__ den, double* __restrict__ part, int want_loss) {
     __shared__ SsimLds L;
     const int tid = threadIdx.x;
     const int H = s.H, W = s.W, C = s.C;
     const size_t hw = (size_t)H * W;
-    if (tid < SS_MAX_JOBS * (SS_NT / 64)) (&L.part[0][0])[tid] = 0.0;
-    const int oly = tid / SS_TW, olx = tid % SS_TW;              // this thread's cell n of the tile: row oly + 4 n, column olx
+    dense_slots_zero(L.part, tid);                               // (the job loop's first barrier stands before the first add)
+    const int oly = tid / DL_TW, olx = tid % DL_TW;              // this thread's cell n of the tile: row oly + 4 n, column olx
     int rly, rlx;                                                // the ring centre of this thread
     const bool ract = tid < SS_RING1;
     ring1_pos(ract ? tid : 0, rly, rlx);
     const int rli = (rly + 2) * SS_XW + (rlx + 2), rfi = (rly + 1) * SS_FW + (rlx + 1);
-    const long tiles = (long)s.B * s.tiles_y * s.tiles_x;
+    const long tiles = dense_tiles(s.B, s.tiles_x, s.tiles_y);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b = (int)(tile / ((long)s.tiles_y * s.tiles_x));
-        const int rem = (int)(tile % ((long)s.tiles_y * s.tiles_x));
-        const int r0 = (rem / s.tiles_x) * SS_TH, c0 = (rem % s.tiles_x) * SS_TW;
+        const auto [b, r0, c0] = dense_tile(tile, s.tiles_x, s.tiles_y);
         for (int job = 0; job < k; ++job) {
             const float* flow = jobs.flow[job] + (size_t)b * 2 * hw;
             const float* img1 = jobs.img1[job] + (size_t)b * C * hw;
@@ -271,30 +218,30 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
             const int ring = want_grad ? 2 : 1;                  // halo of the staged planes: the tile's own centres alone without a gradient
             __syncthreads();                                     // the job (or tile) before has read the planes
             // ---- the mask: it serves all channels
-            bool in[SS_CELLS];                                   // the cell lies in the frame
-            int op[SS_CELLS];
+            bool in[DL_CELLS];                                   // the cell lies in the frame
+            int op[DL_CELLS];
 #pragma unroll
-            for (int n = 0; n < SS_CELLS; ++n) {
-                const int ly = oly + n * (SS_NT / SS_TW), y = r0 + ly, x = c0 + olx;
+            for (int n = 0; n < DL_CELLS; ++n) {
+                const int ly = oly + n * (DL_NT / DL_TW), y = r0 + ly, x = c0 + olx;
                 in[n] = y < H && x < W;
                 op[n] = in[n] ? y * W + x : 0;
                 L.w[(ly + 2) * SS_XW + (olx + 2)] = in[n] ? (mask ? mask[op[n]] : 1.f) : 0.f;
             }
-            for (int r = tid; r < SS_RING2; r += SS_NT) {
+            for (int r = tid; r < SS_RING2; r += DL_NT) {
                 int ly, lx;
                 ring2_pos(r, ly, lx);
-                if (ring == 1 && (ly < -1 || ly > SS_TH || lx < -1 || lx > SS_TW)) continue;
+                if (ring == 1 && (ly < -1 || ly > DL_TH || lx < -1 || lx > DL_TW)) continue;
                 const int y = r0 + ly, x = c0 + lx;
                 const bool inside = y >= 0 && y < H && x >= 0 && x < W;
                 L.w[(ly + 2) * SS_XW + (lx + 2)] = inside ? (mask ? mask[y * W + x] : 1.f) : 0.f;
             }
             __syncthreads();
             // ---- aw, inv and the factors' scale fs of this thread's centres
-            double aw[SS_CELLS], inv[SS_CELLS], fs[SS_CELLS], inv_r = 0.0, fs_r = 0.0;
-            bool cv[SS_CELLS];                                   // the cell is a centre
+            double aw[DL_CELLS], inv[DL_CELLS], fs[DL_CELLS], inv_r = 0.0, fs_r = 0.0;
+            bool cv[DL_CELLS];                                   // the cell is a centre
 #pragma unroll
-            for (int n = 0; n < SS_CELLS; ++n) {
-                const int ly = oly + n * (SS_NT / SS_TW), y = r0 + ly, x = c0 + olx;
+            for (int n = 0; n < DL_CELLS; ++n) {
+                const int ly = oly + n * (DL_NT / DL_TW), y = r0 + ly, x = c0 + olx;
                 cv[n] = y >= 1 && y <= H - 2 && x >= 1 && x <= W - 2;
                 aw[n] = 0.0, inv[n] = 0.0, fs[n] = 0.0;
                 if (cv[n]) {
@@ -309,19 +256,19 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
                 inv_r = 1.0 / (a + s.eps);
                 fs_r = (use_occ ? (inv_r / 9.0) * a : inv_r / 9.0) * sc;
             }
-            double gu[SS_CELLS], gv[SS_CELLS];
+            double gu[DL_CELLS], gv[DL_CELLS];
 #pragma unroll
-            for (int n = 0; n < SS_CELLS; ++n) gu[n] = 0.0, gv[n] = 0.0;
+            for (int n = 0; n < DL_CELLS; ++n) gu[n] = 0.0, gv[n] = 0.0;
             double acc = 0.0;
             for (int c = 0; c < C; ++c) {
                 const float* i1 = img1 + (size_t)c * hw;
                 const float* i2 = img2 + (size_t)c * hw;
                 if (c > 0) __syncthreads();                      // the channel before has read x, y and the factor planes
                 // ---- stage x and y of this channel; the blend's derivative of the tile's own cells stays in registers
-                double dxs[SS_CELLS], dys[SS_CELLS];
+                double dxs[DL_CELLS], dys[DL_CELLS];
 #pragma unroll
-                for (int n = 0; n < SS_CELLS; ++n) {
-                    const int li = (oly + n * (SS_NT / SS_TW) + 2) * SS_XW + (olx + 2);
+                for (int n = 0; n < DL_CELLS; ++n) {
+                    const int li = (oly + n * (DL_NT / DL_TW) + 2) * SS_XW + (olx + 2);
                     float v[4];
                     const WarpTaps t = warp_taps(flow[op[n]], flow[hw + op[n]], H, W, op[n], 1);
                     warp_gather(i2, t, v);
@@ -329,10 +276,10 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
                     L.y[li] = in[n] ? warp_sum(v, t) : 0.f;
                     blend_grad(v, t, dxs[n], dys[n]);
                 }
-                for (int r = tid; r < SS_RING2; r += SS_NT) {
+                for (int r = tid; r < SS_RING2; r += DL_NT) {
                     int ly, lx;
                     ring2_pos(r, ly, lx);
-                    if (ring == 1 && (ly < -1 || ly > SS_TH || lx < -1 || lx > SS_TW)) continue;
+                    if (ring == 1 && (ly < -1 || ly > DL_TH || lx < -1 || lx > DL_TW)) continue;
                     const int y = r0 + ly, x = c0 + lx, li = (ly + 2) * SS_XW + (lx + 2);
                     if (y >= 0 && y < H && x >= 0 && x < W) {    // (no centre's window reaches a cell outside the frame)
                         const int p = y * W + x;
@@ -346,8 +293,8 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
                 __syncthreads();
                 // ---- the centres: l of the tile's own, and the three factors of all
 #pragma unroll
-                for (int n = 0; n < SS_CELLS; ++n) {
-                    const int ly = oly + n * (SS_NT / SS_TW);
+                for (int n = 0; n < DL_CELLS; ++n) {
+                    const int ly = oly + n * (DL_NT / DL_TW);
                     SsimCentre o = {0.0, 0.0, 0.0, 0.0};
                     if (cv[n]) o = ssim_centre(L.x, L.y, L.w, (ly + 2) * SS_XW + (olx + 2), inv[n], s);
                     acc += use_occ ? o.l * aw[n] : o.l;
@@ -369,8 +316,8 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
                 __syncthreads();
                 // ---- gather the factors of the centres around every cell, then the warp derivative
 #pragma unroll
-                for (int n = 0; n < SS_CELLS; ++n) {
-                    const int ly = oly + n * (SS_NT / SS_TW);
+                for (int n = 0; n < DL_CELLS; ++n) {
+                    const int ly = oly + n * (DL_NT / DL_TW);
                     const int fi = (ly + 1) * SS_FW + (olx + 1), li = (ly + 2) * SS_XW + (olx + 2);
                     double sa = 0.0, sb = 0.0, sg = 0.0;
 #pragma unroll
@@ -388,14 +335,10 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
                     gv[n] += gy * dys[n];
                 }
             }
-            if (want_loss) {
-                // wave-uniform: every lane of the wave arrives here.  A wave owns its slot, tiles arrive in the block's fixed order.
-                acc = wave_sum(acc);
-                if ((tid & 63) == 0) L.part[job][tid >> 6] += acc;
-            }
+            if (want_loss) dense_slots_add(L.part, tid, job, acc);
             if (want_grad) {
 #pragma unroll
-                for (int n = 0; n < SS_CELLS; ++n) {
+                for (int n = 0; n < DL_CELLS; ++n) {
                     if (!in[n]) continue;
                     grad[(size_t)b * 2 * hw + op[n]] = (float)(gu[n] * s.sx);
                     grad[(size_t)b * 2 * hw + hw + op[n]] = (float)(gv[n] * s.sy);
@@ -405,78 +348,49 @@ __global__ __launch_bounds__(SS_NT, 2) void ssim_kernel(SsimJobs jobs, int k, Ss
     }
     if (!want_loss) return;
     __syncthreads();
-    if (tid < k) {
-        double v = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < SS_NT / 64; ++wv) v += L.part[tid][wv];
-        part[(size_t)tid * gridDim.x + blockIdx.x] = v;
-    }
+    dense_slots_write(L.part, tid, k, part);
 }
-
-inline int ssim_blocks(int B, int H, int W, int* tx, int* ty) {
-    *tx = ceil_div(W, SS_TW);
-    *ty = ceil_div(H, SS_TH);
-    const long tiles = (long)B * *tx * *ty;
-    return (int)std::min<long>(tiles, SS_MAX_BLOCKS);
-}
-
-inline bool ssim_shape_ok(int B, int H, int W) { return B >= 1 && H >= 3 && W >= 3 && (long)B * H * W <= (1L << 30); }
 
 }  // namespace
 
 extern "C" size_t eemflow_ssim_scratch_doubles(int k, int B, int H, int W) {
-    if (k < 1 || k > SS_MAX_JOBS || !ssim_shape_ok(B, H, W)) return 0;
-    int tx, ty;
-    return SS_MAX_JOBS + (size_t)k * ssim_blocks(B, H, W, &tx, &ty);
+    return H >= 3 && W >= 3 ? dense_scratch_doubles(k, B, H, W, DL_MAX_JOBS, 1) : 0;
 }
 
 extern "C" int eemflow_ssim_many(int k, const float* const* flow, const float* const* img1, const float* const* img2,
                                  const float* const* mask, int B, int C, int H, int W, int use_occ, double c1, double c2,
                                  double weight_epsilon, const double* coef, double* loss, float* const* grad, double* scratch, void* stream_) {
-    EEM_REQUIRE(k >= 1 && k <= SS_MAX_JOBS, "eemflow_ssim_many: 1..%d jobs per call; got %d", SS_MAX_JOBS, k);
-    EEM_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (long)B * H * W <= (1L << 30), "eemflow_ssim_many: bad shape B=%d H=%d W=%d", B, H, W);
+    EEM_REQUIRE(k >= 1 && k <= DL_MAX_JOBS, "eemflow_ssim_many: 1..%d jobs per call; got %d", DL_MAX_JOBS, k);
+    EEM_REQUIRE(dense_shape_ok(B, H, W), "eemflow_ssim_many: bad shape B=%d H=%d W=%d", B, H, W);
     EEM_REQUIRE(H >= 3 && W >= 3, "eemflow_ssim_many: the 3 x 3 windows need H >= 3 and W >= 3; got %dx%d", H, W);
     EEM_REQUIRE(C >= 1 && (long)B * C * H * W <= (1L << 34), "eemflow_ssim_many: bad channel count C=%d", C);
     EEM_REQUIRE(c1 > 0.0 && c2 > 0.0, "eemflow_ssim_many: c1 and c2 are positive (inf switches a term off); got c1=%g c2=%g", c1, c2);
     EEM_REQUIRE(!(std::isinf(c1) && std::isinf(c2)), "eemflow_ssim_many: c1 and c2 are both infinite: the loss would be zero");
     EEM_REQUIRE(weight_epsilon > 0.0 && std::isfinite(weight_epsilon), "eemflow_ssim_many: weight_epsilon is positive and finite; got %g",
                 weight_epsilon);
-    EEM_REQUIRE(flow && img1 && img2, "eemflow_ssim_many: flow, img1 or img2 is NULL");
     EEM_REQUIRE(loss || grad, "eemflow_ssim_many: neither loss nor grad is asked for");
     EEM_REQUIRE(scratch, "eemflow_ssim_many: scratch is NULL (eemflow_ssim_scratch_doubles)");
-    SsimJobs jobs;
-    for (int i = 0; i < SS_MAX_JOBS; ++i) jobs.flow[i] = jobs.img1[i] = jobs.img2[i] = jobs.mask[i] = nullptr, jobs.grad[i] = nullptr;
-    for (int i = 0; i < k; ++i) {
-        EEM_REQUIRE(flow[i] && img1[i] && img2[i], "eemflow_ssim_many: job %d lacks its flow, img1 or img2 (NULL)", i);
-        EEM_REQUIRE(!grad || grad[i], "eemflow_ssim_many: job %d has no gradient buffer (NULL)", i);
-        jobs.flow[i] = flow[i];
-        jobs.img1[i] = img1[i];
-        jobs.img2[i] = img2[i];
-        jobs.mask[i] = mask ? mask[i] : nullptr;
-        jobs.grad[i] = grad ? grad[i] : nullptr;
-    }
+    DenseJobs jobs;
+    if (const int rc = dense_fill_jobs(jobs, "eemflow_ssim_many", k, flow, img1, img2, mask, grad)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     SsimShape s;
-    s.B = B, s.C = C, s.H = H, s.W = W;
-    const int nblk = ssim_blocks(B, H, W, &s.tiles_x, &s.tiles_y);
-    s.sx = ((double)W / 2.0) * (2.0 / (double)std::max(W - 1, 1));
-    s.sy = ((double)H / 2.0) * (2.0 / (double)std::max(H - 1, 1));
+    const int nblk = dense_shape(s, B, C, H, W);
     s.n1 = use_occ ? 1.0 : (double)B * (double)C * (double)(H - 2) * (double)(W - 2);
     s.c1 = c1, s.c2 = c2, s.eps = weight_epsilon;
     s.lum = std::isinf(c1) ? 0 : 1, s.str = std::isinf(c2) ? 0 : 1;
     double* den = scratch;
-    double* part = scratch + SS_MAX_JOBS;
+    double* part = scratch + DL_MAX_JOBS;
     const int uo = use_occ ? 1 : 0;
     if (uo) {
-        hipLaunchKernelGGL(ssim_aw_kernel, dim3(nblk), dim3(SS_NT), 0, stream, jobs, k, s, part);
+        hipLaunchKernelGGL(ssim_aw_kernel, dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, part);
         EEM_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(ssim_den_kernel, dim3(k), dim3(64), 0, stream, part, nblk, uo, den);
     EEM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(ssim_kernel, dim3(nblk), dim3(SS_NT), 0, stream, jobs, k, s, uo, coef, den, part, loss ? 1 : 0);
+    hipLaunchKernelGGL(ssim_kernel, dim3(nblk), dim3(DL_NT), 0, stream, jobs, k, s, uo, coef, den, part, loss ? 1 : 0);
     EEM_HIP_CHECK(hipGetLastError());
     if (loss) {
-        hipLaunchKernelGGL(ssim_finish_kernel, dim3(k), dim3(64), 0, stream, part, nblk, s.n1, den, loss);
+        hipLaunchKernelGGL(dense_finish_kernel, dim3(k), dim3(64), 0, stream, part, nblk, s.n1, den, loss);
         EEM_HIP_CHECK(hipGetLastError());
     }
     return EEM_OK;

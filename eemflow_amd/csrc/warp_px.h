@@ -11,7 +11,7 @@ struct WarpTaps {
     float nw, ne, sw, se;        // bilinear weights of the four corners
     int o_nw, o_ne, o_sw, o_se;  // their offsets in a [h][w] plane, -1: outside (zero padding)
     float m;                     // mode 2: the `grid_sample(ones) >= 1` mask, else 1
-    float wx, wy;                // ix - floor(ix), iy - floor(iy): the weights' factors, for the blend's derivative (photo.hip)
+    float wx, wy;                // ix - floor(ix), iy - floor(iy): the weights' factors, for the blend's derivative (blend_grad)
 };
 
 // mode 0: align_corners=True (EEMFlow_cdc.warp); 1: align_corners=False (torch_warp);
@@ -65,4 +65,11 @@ __device__ __forceinline__ void warp_gather(const float* __restrict__ s, const W
 // the warped value before the mode-2 mask
 __device__ __forceinline__ float warp_sum(const float v[4], const WarpTaps& t) {
     return ((v[0] * t.nw + v[1] * t.ne) + v[2] * t.sw) + v[3] * t.se;
+}
+
+// the derivative of the blend of the corner values v with respect to ix and iy, in fp64 at the fp32 tap weights (photo.hip, ssim.hip)
+__device__ __forceinline__ void blend_grad(const float v[4], const WarpTaps& t, double& dx, double& dy) {
+    const double ww = (double)t.wx, we = (double)(1.f - t.wx), wn = (double)t.wy, ws = (double)(1.f - t.wy);
+    dx = ws * ((double)v[1] - (double)v[0]) + wn * ((double)v[3] - (double)v[2]);
+    dy = we * ((double)v[2] - (double)v[0]) + ww * ((double)v[3] - (double)v[1]);
 }

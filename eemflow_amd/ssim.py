@@ -22,15 +22,10 @@ torch.clamp does); the backward is the same entry point asked for the gradient, 
 nothing is saved between the passes but the inputs, and nothing synchronises with the host.  No atomics: losses and gradients are
 bitwise reproducible.  CUDA tensors only: there is no CPU path.
 """
-import ctypes
 import math
 
-import torch
-
-from . import _lib
-from .photo import _check
-
-MAX_JOBS_PER_CALL = 16
+from . import _dense, _lib
+from ._dense import MAX_JOBS_PER_CALL  # noqa: F401
 
 
 def _settings(name, use_occ, c1, c2, weight_epsilon):
@@ -44,48 +39,6 @@ def _settings(name, use_occ, c1, c2, weight_epsilon):
     return bool(use_occ), c1, c2, weight_epsilon
 
 
-def _launch(flows, job, want_loss, coef):
-    """One eemflow_ssim_many call per 16 jobs on the current stream: ((N,) float64 losses or None, list of gradients or None).
-    flows and the job's tensors are contiguous and detached; coef: None (the loss alone) or a (N,) float64 device tensor."""
-    img1, img2, masks, settings = job
-    use_occ, c1, c2, eps = settings
-    n = len(flows)
-    b, _, h, w = flows[0].shape
-    c = int(img1[0].shape[1])
-    dev = flows[0].device
-    lib = _lib.lib()
-    loss = torch.empty(n, device=dev, dtype=torch.float64) if want_loss else None
-    grads = [torch.empty_like(f) for f in flows] if coef is not None else None
-    scratch = torch.empty(max(1, int(lib.eemflow_ssim_scratch_doubles(min(n, MAX_JOBS_PER_CALL), b, h, w))), device=dev, dtype=torch.float64)
-
-    def ptrs(ts, i0, k):
-        return (ctypes.c_void_p * k)(*[t.data_ptr() if t is not None else None for t in ts[i0:i0 + k]])
-    with torch.cuda.device(dev):
-        for i0 in range(0, n, MAX_JOBS_PER_CALL):
-            k = min(MAX_JOBS_PER_CALL, n - i0)
-            _lib.check(lib.eemflow_ssim_many(
-                k, ptrs(flows, i0, k), ptrs(img1, i0, k), ptrs(img2, i0, k), ptrs(masks, i0, k), b, c, h, w, int(use_occ), c1, c2, eps,
-                coef[i0:].data_ptr() if coef is not None else None, loss[i0:].data_ptr() if want_loss else None,
-                ptrs(grads, i0, k) if grads is not None else None, scratch.data_ptr(), _lib.current_stream_ptr(dev)))
-    return loss, grads
-
-
-class _Ssim(torch.autograd.Function):
-    """(N,) losses of N flows; backward: the same entry point asked for coef * dL/dflow (nothing saved but the inputs)."""
-
-    @staticmethod
-    def forward(ctx, job, *flows):
-        flows = [f.detach() for f in flows]
-        ctx.job, ctx.flows = job, flows
-        return _launch(flows, job, True, None)[0]
-
-    @staticmethod
-    def backward(ctx, gloss):
-        coef = gloss.detach().to(torch.float64).contiguous()
-        grads = _launch(ctx.flows, ctx.job, False, coef)[1]
-        return (None,) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:]))
-
-
 def ssim_many(flows, img1, img2, mask=None, use_occ=False, c1=float("inf"), c2=9e-6, weight_epsilon=0.01):
     """Weighted SSIM losses between img1 and img2 warped back by each of `flows` (a list of (B,2,H,W) float32 CUDA tensors of one
     shape): a (N,) float64 device tensor, differentiable with respect to every flow.  img1, img2 and mask are one tensor shared by all
@@ -94,51 +47,16 @@ def ssim_many(flows, img1, img2, mask=None, use_occ=False, c1=float("inf"), c2=9
     backward, on the current stream; non-contiguous inputs are made contiguous."""
     name = "ssim_many"
     settings = _settings(name, use_occ, c1, c2, weight_epsilon)
-    flows = list(flows)
-    if len(flows) < 1:
-        raise ValueError(f"{name}: at least one flow")
-    for f in flows:
-        _check(name, "a flow", f, 2)
-    shape, dev = tuple(flows[0].shape), flows[0].device
-    if any(tuple(f.shape) != shape for f in flows):
-        raise ValueError(f"{name}: all flows share one (B,2,H,W) shape, got {[tuple(f.shape) for f in flows]}")
+    flows, img1, img2, masks, channels = _dense.warp_inputs(name, flows, img1, img2, mask)
+    h, w = flows[0].shape[2:]
+    if h < 3 or w < 3:
+        raise ValueError(f"{name}: the 3 x 3 windows need H >= 3 and W >= 3, got {h}x{w}")
+    lib = _lib.lib()
 
-    def per_flow(what, x, optional=False):
-        xs = [x] * len(flows) if x is None or torch.is_tensor(x) else list(x)
-        if len(xs) != len(flows):
-            raise ValueError(f"{name}: one {what} per flow; got {len(xs)} for {len(flows)} flows")
-        if not optional and any(t is None for t in xs):
-            raise ValueError(f"{name}: {what} is required")
-        return xs
-    img1, img2, masks = per_flow("img1", img1), per_flow("img2", img2), per_flow("mask", mask, optional=True)
-    channels = int(img1[0].shape[1]) if torch.is_tensor(img1[0]) and img1[0].dim() == 4 else None
-    for what, ts in (("img1", img1), ("img2", img2)):
-        for t in ts:
-            _check(name, what, t)
-            if (t.shape[0],) + tuple(t.shape[2:]) != (shape[0],) + shape[2:]:
-                raise ValueError(f"{name}: {what} {tuple(t.shape)} beside a flow {shape}: B, H and W must agree")
-            if t.shape[1] < 1 or t.shape[1] != channels:
-                raise ValueError(f"{name}: img1 and img2 share one channel count C >= 1")
-    for t in masks:
-        if t is None:
-            continue
-        _check(name, "mask", t, 1)
-        if (t.shape[0],) + tuple(t.shape[2:]) != (shape[0],) + shape[2:]:
-            raise ValueError(f"{name}: mask {tuple(t.shape)} beside a flow {shape}: B, H and W must agree")
-    if any(t.device != dev for t in flows + img1 + img2 + [m for m in masks if m is not None]):
-        raise ValueError(f"{name}: flows, images and masks live on one device")
-    if shape[2] < 3 or shape[3] < 3:
-        raise ValueError(f"{name}: the 3 x 3 windows need H >= 3 and W >= 3, got {shape[2]}x{shape[3]}")
-    made = {}                                                      # one contiguous tensor per distinct input: shared stays shared
-
-    def cont(t):
-        if t is None:
-            return None
-        if id(t) not in made:
-            made[id(t)] = t.detach().contiguous()
-        return made[id(t)]
-    job = ([cont(t) for t in img1], [cont(t) for t in img2], [cont(t) for t in masks], settings)
-    return _Ssim.apply(job, *[f.contiguous() for f in flows])
+    def call(k, f, i1, i2, m, b, h, w, *tail):
+        use_occ, c1, c2, eps = settings
+        return lib.eemflow_ssim_many(k, f, i1, i2, m, b, channels, h, w, int(use_occ), c1, c2, eps, *tail)
+    return _dense.losses((call, lib.eemflow_ssim_scratch_doubles, _dense.contiguous(img1, img2, masks), True), flows)
 
 
 def ssim_loss(flow, img1, img2, mask=None, **kw):

@@ -118,6 +118,20 @@ def timestamp_loss(flow_pred, events, maps=None):
     return term(events, [pred[i] for i in range(pred.shape[0])], maps=maps)
 
 
+def _dense_term(name, many, flow_preds, gamma, *inputs, **kw):
+    """A dense term of a model's predictions through its `many` (smoothness_many, photo_many, ssim_many): the loss of the last
+    prediction with gamma=None, else sum_i gamma^(n-1-i) * L_i over all n predictions."""
+    flow_preds = list(flow_preds)
+    if len(flow_preds) < 1:
+        raise ValueError(f"{name}: at least one prediction")
+    if gamma is None:
+        return many([flow_preds[-1].float()], *inputs, **kw)[0]
+    n = len(flow_preds)
+    losses = many([f.float() for f in flow_preds], *inputs, **kw)
+    weights = torch.tensor([float(gamma) ** (n - 1 - i) for i in range(n)], dtype=torch.float64).to(losses.device, non_blocking=True)
+    return (losses * weights).sum()
+
+
 def smoothness_loss(flow_preds, img, gamma=None, **kw):
     """The edge-aware smoothness term of a model's predictions (a list of (B,2,H,W) tensors, the last one final) against the shared
     edge image `img` ((B,C,H,W), in training the old event volume; None: unweighted): smooth.smoothness_loss of the last prediction
@@ -125,15 +139,7 @@ def smoothness_loss(flow_preds, img, gamma=None, **kw):
     predictions, img read and its weights taken once per tile for all of them.  A differentiable 0-dim float64 CUDA tensor;
     **kw: order, constant, weight_type, error_type of smooth.smoothness_many."""
     from .smooth import smoothness_many
-    flow_preds = list(flow_preds)
-    if len(flow_preds) < 1:
-        raise ValueError("smoothness_loss: at least one prediction")
-    if gamma is None:
-        return smoothness_many([flow_preds[-1].float()], img, **kw)[0]
-    n = len(flow_preds)
-    losses = smoothness_many([f.float() for f in flow_preds], img, **kw)
-    weights = torch.tensor([float(gamma) ** (n - 1 - i) for i in range(n)], dtype=torch.float64).to(losses.device, non_blocking=True)
-    return (losses * weights).sum()
+    return _dense_term("smoothness_loss", smoothness_many, flow_preds, gamma, img, **kw)
 
 
 def photo_loss(flow_preds, img1, img2, gamma=None, mask=None, **kw):
@@ -143,15 +149,7 @@ def photo_loss(flow_preds, img1, img2, gamma=None, mask=None, **kw):
     per 16 predictions.  mask: a (B,1,H,W) occlusion mask for use_occ=True.  A differentiable 0-dim float64 CUDA tensor;
     **kw: kind, use_occ, q, charbonnier, average, max_distance, gray of photo.photo_many."""
     from .photo import photo_many
-    flow_preds = list(flow_preds)
-    if len(flow_preds) < 1:
-        raise ValueError("photo_loss: at least one prediction")
-    if gamma is None:
-        return photo_many([flow_preds[-1].float()], img1, img2, mask, **kw)[0]
-    n = len(flow_preds)
-    losses = photo_many([f.float() for f in flow_preds], img1, img2, mask, **kw)
-    weights = torch.tensor([float(gamma) ** (n - 1 - i) for i in range(n)], dtype=torch.float64).to(losses.device, non_blocking=True)
-    return (losses * weights).sum()
+    return _dense_term("photo_loss", photo_many, flow_preds, gamma, img1, img2, mask, **kw)
 
 
 def ssim_loss(flow_preds, img1, img2, gamma=None, mask=None, **kw):
@@ -161,15 +159,7 @@ def ssim_loss(flow_preds, img1, img2, gamma=None, mask=None, **kw):
     16 predictions.  mask: a (B,1,H,W) weight, with use_occ=True the occlusion mask.  A differentiable 0-dim float64 CUDA tensor;
     **kw: use_occ, c1, c2, weight_epsilon of ssim.ssim_many."""
     from .ssim import ssim_many
-    flow_preds = list(flow_preds)
-    if len(flow_preds) < 1:
-        raise ValueError("ssim_loss: at least one prediction")
-    if gamma is None:
-        return ssim_many([flow_preds[-1].float()], img1, img2, mask, **kw)[0]
-    n = len(flow_preds)
-    losses = ssim_many([f.float() for f in flow_preds], img1, img2, mask, **kw)
-    weights = torch.tensor([float(gamma) ** (n - 1 - i) for i in range(n)], dtype=torch.float64).to(losses.device, non_blocking=True)
-    return (losses * weights).sum()
+    return _dense_term("ssim_loss", ssim_many, flow_preds, gamma, img1, img2, mask, **kw)
 
 
 class EEMFlowTrainer:

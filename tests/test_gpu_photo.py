@@ -111,6 +111,17 @@ def test_loss_and_gradient_match_the_fp64_restatement(inputs, case):
             check(name + ("" if m is not None else " no mask"), flow, img1, img2, m, losses[0], grads[0], **kw)
 
 
+@pytest.mark.parametrize("kw", [dict(kind="census", use_occ=True, q=R.Q, charbonnier=True, average=True, max_distance=3),
+                                dict(kind="abs_robust", use_occ=False)], ids=["census", "abs_robust"])
+def test_more_tiles_than_blocks(kw):
+    """520 samples of 2 x 2 tiles: 2080 tiles on the grid's cap of 2048 blocks, so 32 blocks walk a second tile and add it to their
+    loss slots; census with its mask, abs_robust without one.  The same bounds as everywhere."""
+    flow, img1, img2, mask = (torch.from_numpy(a) for a in R.inputs(23, (520, 3, TILE_H + 1, TILE_W + 1)))
+    m = mask if kw["use_occ"] else None
+    losses, grads = run_gpu([flow], img1, img2, m, **kw)
+    check("520 x 17x65", flow, img1, img2, m, losses[0], grads[0], **kw)
+
+
 def test_losses_match_the_reference_own_values(golden):
     g = golden("photo.npz")
     gap = float(g["ref_gap"])

@@ -98,6 +98,15 @@ def test_loss_and_gradient_match_the_fp64_restatement(inputs, case):
     assert float(run_gpu([flow], img1, img2, None, **kw)[1][0].abs().max()) > 0.0      # the one centre has a gradient
 
 
+def test_more_tiles_than_blocks():
+    """520 samples of 2 x 2 tiles: 2080 tiles on the grid's cap of 2048 blocks, so 32 blocks walk a second tile and add it to their
+    loss slots; the structure branch with its mask.  The same bounds as everywhere."""
+    flow, img1, img2, mask = (torch.from_numpy(a) for a in R.inputs(23, (520, 2, TILE_H + 1, TILE_W + 1)))
+    kw = dict(use_occ=True, c1=INF, c2=9e-6)
+    losses, grads = run_gpu([flow], img1, img2, mask, **kw)
+    check("520 x 17x65", flow, img1, img2, mask, losses[0], grads[0], **kw)
+
+
 def test_losses_match_the_reference_own_values(golden):
     g = golden("ssim.npz")
     gap = float(g["ref_gap"])
