@@ -53,9 +53,8 @@ struct VarFactor {
 extern "C" int eemflow_iwe_grad_many(int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
                                      const double* scale, const double (*maps)[4], int h, int w, const float* const* iwe,
                                      const double* moments, const double* coef, float* const* grads, void* stream_) {
-    EEM_REQUIRE(k >= 1 && k <= IWE_MAX_JOBS, "eemflow_iwe_grad_many: 1..%d jobs per call; got %d", IWE_MAX_JOBS, k);
-    EEM_REQUIRE(events && n && flows && t0 && scale && maps && iwe && moments && coef && grads, "eemflow_iwe_grad_many: NULL argument");
-    EEM_REQUIRE(h >= 1 && w >= 1 && (long)h * w <= (1L << 30), "eemflow_iwe_grad_many: bad size %dx%d", h, w);
+    const int rc = iwe_check_many("eemflow_iwe_grad_many", k, events && n && flows && t0 && scale && maps && iwe && moments && coef && grads, h, w, n);
+    if (rc != EEM_OK) return rc;
     int form = 0;
     return iwe_grad_run<VarFactor>("eemflow_iwe_grad_many", k, events, n, flows, t0, scale, maps, h, w, iwe, nullptr, moments, 0.0, coef, grads,
                                    stream_, &form);

@@ -240,7 +240,7 @@ int launch_grad_bin(const IweGradJobs& jobs, int njobs, long nblk_max, const dou
     return EEM_OK;
 }
 
-// The body of a gradient entry point: `img` (and `img2`, or NULL) are the forward's stored images of the k jobs, `aux` and `eps` what
+// The body of a gradient entry point, after iwe_check_many: `img` (and `img2`, or NULL) are the forward's stored images of the k jobs, `aux` and `eps` what
 // the Factor loads from.  *form: 0 when no job had a flow (nothing ran), -1 for the direct form, else the binning kernel's EPT.
 template <class Factor>
 int iwe_grad_run(const char* name, int k, const double* const* events, const int64_t* n, const float* const* flows, const double* t0,
@@ -252,7 +252,6 @@ int iwe_grad_run(const char* name, int k, const double* const* events, const int
     int m = 0;                                                     // jobs with a flow: the others have no gradient
     long nmax = 0;
     for (int i = 0; i < k; ++i) {
-        EEM_REQUIRE(n[i] >= 0 && n[i] < (1LL << 40), "%s: job %d has n=%ld events", name, i, (long)n[i]);
         if (!flows[i]) continue;
         EEM_REQUIRE((events[i] || n[i] == 0) && img[i] && (!img2 || img2[i]) && grads[i], "%s: job %d has a NULL buffer", name, i);
         IweGradJob& J = jobs.j[m++];
@@ -317,17 +316,10 @@ int iwe_grad_run(const char* name, int k, const double* const* events, const int
                       : launch_grad_bin<2, Factor>(jobs, m, nblk_max, aux, eps, coef, h, w, pl, stream);
         if (rc != EEM_OK) return rc;
     }
-    const int lds = pl.cells * 8;
     const int slab = GRAD_RPE * VT * ept;
-    // lanes per run: the smallest power of two >= 1.7 x the mean run length (a slab's records / bands), 4 .. 64
-    int sgs = 2;
-    while (sgs < 6 && (1 << sgs) * 10L * pl.nb < 17L * slab) ++sgs;
-    if (pl.cells <= 3072) {
-        hipLaunchKernelGGL(iwe_grad_band_kernel<256>, dim3(pl.nb, m), dim3(256), lds, stream, jobs, slab, h, w, pl, sgs);
-    } else {
-        if (lds > 32 * 1024) EEM_RAISE_LDS(lds, iwe_grad_band_kernel<VT>);
-        hipLaunchKernelGGL(iwe_grad_band_kernel<VT>, dim3(pl.nb, m), dim3(VT), lds, stream, jobs, slab, h, w, pl, sgs);
-    }
+    int bt = 0;
+    rc = iwe_launch_bands<iwe_grad_band_kernel<256>, iwe_grad_band_kernel<VT>>(pl, m, stream, &bt, jobs, slab, h, w, pl, iwe_run_lanes(pl, slab));
+    if (rc != EEM_OK) return rc;
     EEM_HIP_CHECK(hipGetLastError());
     *form = ept;
     return arena.done(token, stream_);

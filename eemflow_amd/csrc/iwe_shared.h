@@ -1,6 +1,7 @@
-// What iwe.hip (the image of warped events) and iwe_grad.hip (its gradient) share: the per-event arithmetic, the block helpers of the
-// binning kernels, the band plan and the scratch arenas.  Both files are built with -ffp-contract=off: the gradient recomputes the
-// forward's warp with the same expressions in the same order, so it finds the same cells bit for bit.
+// What the forward (iwe_fwd_shared.h: iwe.hip, tsimg.hip) and the gradient (iwe_grad_shared.h: iwe_grad.hip, tsimg.hip) of the event
+// losses share: the per-event arithmetic, the block helpers of the binning kernels, the band plan with its lanes-per-run rule and band
+// launch, the entry points' argument check and the scratch arenas.  All three files are built with -ffp-contract=off: the gradient
+// recomputes the forward's warp with the same expressions in the same order, so it finds the same cells bit for bit.
 #pragma once
 
 #include "common.h"
@@ -178,6 +179,37 @@ inline bool iwe_plan(long nmax, int h, int w, IwePlan* pl, int ept_max = 4, int 
     pl->nb = (int)((h + rows - 1) / rows);
     pl->cells = (int)(cpp * rows * w);
     return true;
+}
+
+// lanes per run of a band kernel, as log2: the smallest power of two >= 1.7 x the mean run length (a slab's records / bands), 4 .. 64
+inline int iwe_run_lanes(const IwePlan& pl, int slab) {
+    int sgs = 2;
+    while (sgs < 6 && (1 << sgs) * 10L * pl.nb < 17L * slab) ++sgs;
+    return sgs;
+}
+
+// the launch of a band kernel, one block per band and job: 256 threads for a small band, else VT with the band's LDS allowed; *bt: which
+template <auto K256, auto KVT, class... Args>
+int iwe_launch_bands(const IwePlan& pl, int njobs, hipStream_t stream, int* bt, Args... args) {
+    const int lds = pl.cells * 8;
+    if (pl.cells <= 3072) {
+        *bt = 256;
+        hipLaunchKernelGGL(K256, dim3(pl.nb, njobs), dim3(256), lds, stream, args...);
+    } else {
+        *bt = VT;
+        if (lds > 32 * 1024) EEM_RAISE_LDS(lds, KVT);
+        hipLaunchKernelGGL(KVT, dim3(pl.nb, njobs), dim3(VT), lds, stream, args...);
+    }
+    return EEM_OK;
+}
+
+// what every *_many entry point checks first (nonnull: its own pointer arguments, n among them), under the entry's name
+inline int iwe_check_many(const char* name, int k, bool nonnull, int h, int w, const int64_t* n) {
+    EEM_REQUIRE(k >= 1 && k <= IWE_MAX_JOBS, "%s: 1..%d jobs per call; got %d", name, IWE_MAX_JOBS, k);
+    EEM_REQUIRE(nonnull, "%s: NULL argument", name);
+    EEM_REQUIRE(h >= 1 && w >= 1 && (long)h * w <= (1L << 30), "%s: bad size %dx%d", name, h, w);
+    for (int i = 0; i < k; ++i) EEM_REQUIRE(n[i] >= 0 && n[i] < (1LL << 40), "%s: job %d has n=%ld events", name, i, (long)n[i]);
+    return EEM_OK;
 }
 
 }  // namespace

@@ -36,13 +36,10 @@ out as batch['events_map']).  offset = (ox, oy) is the map (1, -ox, 1, -oy), bit
 The image of average timestamps, the objective that divides every pixel by its own vote count, and RSAT are in tsimg.py: the same
 warp, the same votes (its D image is this module's image, bit for bit) and the same gradient kernels under another per-target factor.
 """
-import ctypes
-
 import torch
 
-from . import _lib
-
-MAX_JOBS_PER_CALL = 32
+from . import _events, _lib
+from ._events import MAX_JOBS_PER_CALL, map_table as _map_table  # noqa: F401
 
 
 def _check_events(name, ev):
@@ -124,39 +121,34 @@ def _time_refs(name, event_sets, t_ref, dev):
     """(t0, scale) per set of the metric convention: one device-to-host copy for all sets."""
     if t_ref not in ("end", "start"):
         raise ValueError(f"{name}: t_ref is 'end' or 'start', got {t_ref!r}")
-    live = [ev for ev in event_sets if ev.shape[0] > 0]
-    ends = torch.stack([ev[0, 0] for ev in live] + [ev[-1, 0] for ev in live]).tolist() if live else []
-    t0s, scales, q = [], [], 0
-    for ev in event_sets:
-        if ev.shape[0] == 0:
-            t0s.append(0.0)
-            scales.append(-1.0)
-            continue
-        first, last = ends[q], ends[len(live) + q]
-        q += 1
-        span = last - first
-        if span == 0:
-            span = 1.0
-        t0s.append(last if t_ref == "end" else first)
-        scales.append(-1.0 / span)
-    return t0s, scales
+    firsts, lasts, scales = _events.window_ends(event_sets)
+    return (lasts if t_ref == "end" else firsts), scales
 
 
-def _launch(event_sets, flows, t0s, scales, ox, oy, h, w, dev):
+def _maps(name, maps, offset, k):
+    if maps is None:
+        ox, oy = _offset(name, offset)
+        return [(1.0, -ox, 1.0, -oy)] * k
+    maps = list(maps)
+    if len(maps) != k:
+        raise ValueError(f"{name}: one map (ax, bx, ay, by) per event set; got {len(maps)} maps for {k} sets")
+    out = []
+    for m in maps:
+        try:
+            ax, bx, ay, by = m
+            out.append((float(ax), float(bx), float(ay), float(by)))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: a map is (ax, bx, ay, by)") from None
+    return out
+
+
+def _launch_maps(event_sets, flows, t0s, scales, maps, h, w, dev):
+    """(images, (k,4) moments) of k jobs: one eemflow_iwe_map_many call per 32 jobs on the current stream."""
     k = len(event_sets)
     images = [torch.empty(2, h, w, device=dev, dtype=torch.float32) for _ in range(k)]
     moments = torch.empty(k, 4, device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        for i0 in range(0, k, MAX_JOBS_PER_CALL):
-            c = min(MAX_JOBS_PER_CALL, k - i0)
-            ptr = ctypes.c_void_p * c
-            dbl = ctypes.c_double * c
-            _lib.check(_lib.lib().eemflow_iwe_many(
-                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
-                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
-                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
-                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), ox, oy, h, w, ptr(*[t.data_ptr() for t in images[i0:i0 + c]]),
-                moments[i0:].data_ptr(), _lib.current_stream_ptr(dev)))
+    _events.call_many("eemflow_iwe_map_many", event_sets, flows, t0s, scales, maps, h, w, dev,
+                      lambda sl, i0: (_events.pointers(images[sl]), moments[i0:].data_ptr()))
     return images, moments
 
 
@@ -165,11 +157,11 @@ def iwe_many(event_sets, flows, t_ref="end", offset=(0, 0), size=None):
     `(list of (2,H,W) float32, (k,4) float64 moments)`, both on the device.  One library call per 32 jobs, on the current stream; one
     device-to-host copy of the sets' first and last timestamps.  size=(H, W) names the frame when every flow is None."""
     event_sets, flows, dev, h, w = _check_sets("iwe_many", event_sets, flows, size)
-    ox, oy = _offset("iwe_many", offset)
+    maps = _maps("iwe_many", None, offset, len(event_sets))
     event_sets = [e.detach() for e in event_sets]
     flows = [f.detach() if f is not None else None for f in flows]
     t0s, scales = _time_refs("iwe_many", event_sets, t_ref, dev)
-    return _launch(event_sets, flows, t0s, scales, ox, oy, h, w, dev)
+    return _launch_maps(event_sets, flows, t0s, scales, maps, h, w, dev)
 
 
 def iwe(events, flow, t_ref="end", offset=(0, 0), size=None):
@@ -193,18 +185,14 @@ def fwl_many(event_sets, flows, t_ref="end", offset=(0, 0)):
     if any(f is None for f in flows):
         raise ValueError("fwl_many: every event set needs its flow (zero flow is the denominator)")
     event_sets, flows, dev, h, w = _check_sets("fwl_many", event_sets, flows, None)
-    ox, oy = _offset("fwl_many", offset)
+    maps = _maps("fwl_many", None, offset, len(event_sets))
     event_sets = [e.detach() for e in event_sets]
     flows = [f.detach() for f in flows]
     t0s, scales = _time_refs("fwl_many", event_sets, t_ref, dev)
     out = []
-    half = MAX_JOBS_PER_CALL // 2
-    for i0 in range(0, len(event_sets), half):
-        evs, fls = event_sets[i0:i0 + half], flows[i0:i0 + half]
-        _, m = _launch(evs + evs, fls + [None] * len(evs), t0s[i0:i0 + half] * 2, scales[i0:i0 + half] * 2, ox, oy, h, w, dev)
-        var = variance(m)
-        num, den = var[:len(evs)], var[len(evs):]
-        out.append(torch.where(den == 0, torch.full_like(den, float("nan")), num / den))
+    for c, jobs in _events.riding_twice((event_sets, event_sets), (flows, [None] * len(flows)), (t0s, t0s), (scales, scales), (maps, maps)):
+        var = variance(_launch_maps(*jobs, h, w, dev)[1])
+        out.append(_events.ratio_or_nan(var[:c], var[c:]))
     return torch.cat(out)
 
 
@@ -214,97 +202,26 @@ def fwl(events, flow, t_ref="end", offset=(0, 0)):
 
 
 # ------------------------------------------------------------------------------------------------ gradient: contrast maximisation
-def _maps(name, maps, offset, k):
-    if maps is None:
-        ox, oy = _offset(name, offset)
-        return [(1.0, -ox, 1.0, -oy)] * k
-    maps = list(maps)
-    if len(maps) != k:
-        raise ValueError(f"{name}: one map (ax, bx, ay, by) per event set; got {len(maps)} maps for {k} sets")
-    out = []
-    for m in maps:
-        try:
-            ax, bx, ay, by = m
-            out.append((float(ax), float(bx), float(ay), float(by)))
-        except (TypeError, ValueError):
-            raise ValueError(f"{name}: a map is (ax, bx, ay, by)") from None
-    return out
-
-
-def _map_table(maps):
-    return (ctypes.c_double * (4 * len(maps)))(*[v for m in maps for v in m])
-
-
-def _launch_maps(event_sets, flows, t0s, scales, maps, h, w, dev):
-    """_launch with one event map per job (eemflow_iwe_map_many)."""
-    k = len(event_sets)
-    images = [torch.empty(2, h, w, device=dev, dtype=torch.float32) for _ in range(k)]
-    moments = torch.empty(k, 4, device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        for i0 in range(0, k, MAX_JOBS_PER_CALL):
-            c = min(MAX_JOBS_PER_CALL, k - i0)
-            ptr = ctypes.c_void_p * c
-            dbl = ctypes.c_double * c
-            _lib.check(_lib.lib().eemflow_iwe_map_many(
-                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
-                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
-                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
-                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), _map_table(maps[i0:i0 + c]), h, w,
-                ptr(*[t.data_ptr() for t in images[i0:i0 + c]]), moments[i0:].data_ptr(), _lib.current_stream_ptr(dev)))
-    return images, moments
-
-
 def iwe_grad_many(event_sets, flows, t0s, scales, maps, images, moments, coef):
     """coef[i] * d var_i / d flows[i] for the jobs of a forward (`_launch_maps`' arguments, its images and moments): a list with one
     (2,H,W) float32 tensor per job, None where the flow is None.  coef is a (k,) float64 device tensor; one eemflow_iwe_grad_many call
     per 32 jobs on the current stream, no host synchronisation."""
-    k = len(event_sets)
     dev = moments.device
     h, w = images[0].shape[1], images[0].shape[2]
     coef = coef.detach().to(torch.float64).contiguous()
     moments = moments.contiguous()
     grads = [torch.empty(2, h, w, device=dev, dtype=torch.float32) if f is not None else None for f in flows]
-    with torch.cuda.device(dev):
-        for i0 in range(0, k, MAX_JOBS_PER_CALL):
-            c = min(MAX_JOBS_PER_CALL, k - i0)
-            if all(f is None for f in flows[i0:i0 + c]):
-                continue
-            ptr = ctypes.c_void_p * c
-            dbl = ctypes.c_double * c
-            _lib.check(_lib.lib().eemflow_iwe_grad_many(
-                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
-                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
-                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
-                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), _map_table(maps[i0:i0 + c]), h, w,
-                ptr(*[t.data_ptr() for t in images[i0:i0 + c]]), moments[i0:].data_ptr(), coef[i0:].data_ptr(),
-                ptr(*[g.data_ptr() if g is not None else None for g in grads[i0:i0 + c]]), _lib.current_stream_ptr(dev)))
+    _events.call_many("eemflow_iwe_grad_many", event_sets, flows, t0s, scales, maps, h, w, dev,
+                      lambda sl, i0: (_events.pointers(images[sl]), moments[i0:].data_ptr(), coef[i0:].data_ptr(), _events.pointers(grads[sl])),
+                      needs_flow=True)
     return grads
 
 
-class _Contrast(torch.autograd.Function):
-    """(k,) variances of the images of warped events of k jobs; backward: one eemflow_iwe_grad_many call per 32 jobs."""
-
-    @staticmethod
-    def forward(ctx, job, *flows):
-        event_sets, slots, t0s, scales, maps, h, w, dev = job
-        full = [None] * len(event_sets)                            # the flow (or None: zero flow) of every job
-        for i, f in zip(slots, flows):
-            full[i] = f.detach()
-        images, moments = _launch_maps(event_sets, full, t0s, scales, maps, h, w, dev)
-        ctx.job, ctx.full, ctx.images, ctx.moments = job, full, images, moments
-        var = variance(moments)
-        ctx.mark_non_differentiable(moments)
-        return var, moments
-
-    @staticmethod
-    def backward(ctx, gvar, _gmoments):
-        event_sets, slots, t0s, scales, maps, h, w, dev = ctx.job
-        wanted = [None] * len(event_sets)                          # a flow that needs no gradient is skipped like a zero flow
-        for q, i in enumerate(slots):
-            if ctx.needs_input_grad[1 + q]:
-                wanted[i] = ctx.full[i]
-        grads = iwe_grad_many(event_sets, wanted, t0s, scales, maps, ctx.images, ctx.moments, gvar)
-        return (None,) + tuple(grads[i] if wanted[i] is not None else None for i in slots)
+# (k,) variances of the images of warped events of k jobs; backward: one eemflow_iwe_grad_many call per 32 jobs
+_CONTRAST = _events.Term(forward=_launch_maps,
+                         backward=lambda ev, flows, t0s, scales, maps, images, moments, coef:
+                             iwe_grad_many(ev, flows, t0s, scales, maps, images[0], moments, coef),
+                         loss=variance, coef=lambda gvar, moments: gvar)
 
 
 def _contrast(name, event_sets, flows, t_ref, offset, maps):
@@ -316,9 +233,7 @@ def _contrast(name, event_sets, flows, t_ref, offset, maps):
 
 
 def _variances(event_sets, flows, t0s, scales, maps, h, w, dev):
-    slots = [i for i, f in enumerate(flows) if f is not None]
-    var, moments = _Contrast.apply((event_sets, slots, t0s, scales, maps, h, w, dev), *[flows[i] for i in slots])
-    return var, moments
+    return _events.losses(_CONTRAST, event_sets, flows, t0s, scales, maps, h, w, dev)
 
 
 def contrast_many(event_sets, flows, t_ref="end", offset=(0, 0), maps=None):
@@ -339,13 +254,10 @@ def fwl_loss(event_sets, flows, t_ref="end", offset=(0, 0), maps=None):
     if any(f is None for f in flows):
         raise ValueError("fwl_loss: every event set needs its flow (zero flow is the denominator)")
     event_sets, flows, t0s, scales, maps, h, w, dev = _contrast("fwl_loss", event_sets, flows, t_ref, offset, maps)
-    half = MAX_JOBS_PER_CALL // 2
     total = torch.zeros((), device=dev, dtype=torch.float64)
     count = torch.zeros((), device=dev, dtype=torch.float64)
-    for i0 in range(0, len(event_sets), half):
-        sl = slice(i0, i0 + half)
-        c = len(event_sets[sl])
-        var, _ = _variances(event_sets[sl] * 2, flows[sl] + [None] * c, t0s[sl] * 2, scales[sl] * 2, maps[sl] * 2, h, w, dev)
+    for c, jobs in _events.riding_twice((event_sets, event_sets), (flows, [None] * len(flows)), (t0s, t0s), (scales, scales), (maps, maps)):
+        var, _ = _variances(*jobs, h, w, dev)
         num, den = var[:c], var[c:]
         ok = torch.isfinite(den) & (den != 0)
         ratio = torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(num))

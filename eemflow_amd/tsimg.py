@@ -23,8 +23,8 @@ import ctypes
 
 import torch
 
-from . import _lib
-from .iwe import MAX_JOBS_PER_CALL, _check_sets, _map_table, _maps, _time_refs
+from . import _events, _lib
+from .iwe import _check_sets, _maps, _time_refs
 
 ACTIVE_EPS = 1e-9
 
@@ -45,46 +45,14 @@ def _normalize(name, normalize):
     return normalize
 
 
-def _both_refs(name, event_sets):
-    """(t0 of 'end', t0 of 'start', scale) per set: one device-to-host copy for all sets (iwe._time_refs makes one per reference)."""
-    live = [ev for ev in event_sets if ev.shape[0] > 0]
-    ends = torch.stack([ev[0, 0] for ev in live] + [ev[-1, 0] for ev in live]).tolist() if live else []
-    t_end, t_start, scales, q = [], [], [], 0
-    for ev in event_sets:
-        if ev.shape[0] == 0:
-            t_end.append(0.0)
-            t_start.append(0.0)
-            scales.append(-1.0)
-            continue
-        first, last = ends[q], ends[len(live) + q]
-        q += 1
-        span = last - first
-        if span == 0:
-            span = 1.0
-        t_end.append(last)
-        t_start.append(first)
-        scales.append(-1.0 / span)
-    return t_end, t_start, scales
-
-
 def _launch(event_sets, flows, t0s, scales, maps, h, w, eps, dev):
     """(T images, D images, (k,4) moments) of k jobs: one eemflow_tsimg_many call per 32 jobs on the current stream."""
     k = len(event_sets)
     timgs = [torch.empty(2, h, w, device=dev, dtype=torch.float32) for _ in range(k)]
     dimgs = [torch.empty(2, h, w, device=dev, dtype=torch.float32) for _ in range(k)]
     moments = torch.empty(k, 4, device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        for i0 in range(0, k, MAX_JOBS_PER_CALL):
-            c = min(MAX_JOBS_PER_CALL, k - i0)
-            ptr = ctypes.c_void_p * c
-            dbl = ctypes.c_double * c
-            _lib.check(_lib.lib().eemflow_tsimg_many(
-                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
-                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
-                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
-                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), _map_table(maps[i0:i0 + c]), h, w, eps,
-                ptr(*[t.data_ptr() for t in dimgs[i0:i0 + c]]), ptr(*[t.data_ptr() for t in timgs[i0:i0 + c]]),
-                moments[i0:].data_ptr(), _lib.current_stream_ptr(dev)))
+    _events.call_many("eemflow_tsimg_many", event_sets, flows, t0s, scales, maps, h, w, dev,
+                      lambda sl, i0: (eps, _events.pointers(dimgs[sl]), _events.pointers(timgs[sl]), moments[i0:].data_ptr()))
     return timgs, dimgs, moments
 
 
@@ -92,25 +60,13 @@ def tsimg_grad_many(event_sets, flows, t0s, scales, maps, timgs, dimgs, coef, ep
     """coef[i] * d (sum T^2)_i / d flows[i] for the jobs of a forward (`_launch`'s arguments and images): a list with one (2,H,W) float32
     tensor per job, None where the flow is None.  coef is a (k,) float64 device tensor; one eemflow_tsimg_grad_many call per 32 jobs
     on the current stream, no host synchronisation."""
-    k = len(event_sets)
     dev = coef.device
     h, w = timgs[0].shape[1], timgs[0].shape[2]
     coef = coef.detach().to(torch.float64).contiguous()
     grads = [torch.empty(2, h, w, device=dev, dtype=torch.float32) if f is not None else None for f in flows]
-    with torch.cuda.device(dev):
-        for i0 in range(0, k, MAX_JOBS_PER_CALL):
-            c = min(MAX_JOBS_PER_CALL, k - i0)
-            if all(f is None for f in flows[i0:i0 + c]):
-                continue
-            ptr = ctypes.c_void_p * c
-            dbl = ctypes.c_double * c
-            _lib.check(_lib.lib().eemflow_tsimg_grad_many(
-                c, ptr(*[e.data_ptr() if e.shape[0] else None for e in event_sets[i0:i0 + c]]),
-                (ctypes.c_int64 * c)(*[e.shape[0] for e in event_sets[i0:i0 + c]]),
-                ptr(*[f.data_ptr() if f is not None else None for f in flows[i0:i0 + c]]),
-                dbl(*t0s[i0:i0 + c]), dbl(*scales[i0:i0 + c]), _map_table(maps[i0:i0 + c]), h, w, eps,
-                ptr(*[t.data_ptr() for t in dimgs[i0:i0 + c]]), ptr(*[t.data_ptr() for t in timgs[i0:i0 + c]]), coef[i0:].data_ptr(),
-                ptr(*[g.data_ptr() if g is not None else None for g in grads[i0:i0 + c]]), _lib.current_stream_ptr(dev)))
+    _events.call_many("eemflow_tsimg_grad_many", event_sets, flows, t0s, scales, maps, h, w, dev,
+                      lambda sl, i0: (eps, _events.pointers(dimgs[sl]), _events.pointers(timgs[sl]), coef[i0:].data_ptr(),
+                                      _events.pointers(grads[sl])), needs_flow=True)
     return grads
 
 
@@ -146,35 +102,13 @@ def loss_of(moments, normalize="active"):
     return moments[..., 1] / (moments[..., 2] + ACTIVE_EPS) if normalize == "active" else moments[..., 1]
 
 
-class _Timestamp(torch.autograd.Function):
-    """(k,) timestamp losses of k jobs; backward: one eemflow_tsimg_grad_many call per 32 jobs, coef computed on the device."""
-
-    @staticmethod
-    def forward(ctx, job, *flows):
-        event_sets, slots, t0s, scales, maps, h, w, dev, eps, normalize = job
-        full = [None] * len(event_sets)                            # the flow (or None: zero flow) of every job
-        for i, f in zip(slots, flows):
-            full[i] = f.detach()
-        timgs, dimgs, moments = _launch(event_sets, full, t0s, scales, maps, h, w, eps, dev)
-        ctx.job, ctx.full, ctx.timgs, ctx.dimgs, ctx.moments = job, full, timgs, dimgs, moments
-        ctx.mark_non_differentiable(moments)
-        return loss_of(moments, normalize), moments
-
-    @staticmethod
-    def backward(ctx, gloss, _gmoments):
-        event_sets, slots, t0s, scales, maps, h, w, dev, eps, normalize = ctx.job
-        wanted = [None] * len(event_sets)                          # a flow that needs no gradient is skipped like a zero flow
-        for q, i in enumerate(slots):
-            if ctx.needs_input_grad[1 + q]:
-                wanted[i] = ctx.full[i]
-        coef = gloss / (ctx.moments[:, 2] + ACTIVE_EPS) if normalize == "active" else gloss
-        grads = tsimg_grad_many(event_sets, wanted, t0s, scales, maps, ctx.timgs, ctx.dimgs, coef, eps)
-        return (None,) + tuple(grads[i] if wanted[i] is not None else None for i in slots)
-
-
 def _losses(event_sets, flows, t0s, scales, maps, h, w, dev, eps, normalize):
-    slots = [i for i, f in enumerate(flows) if f is not None]
-    return _Timestamp.apply((event_sets, slots, t0s, scales, maps, h, w, dev, eps, normalize), *[flows[i] for i in slots])
+    """((k,) timestamp losses, moments) of k jobs; backward: one eemflow_tsimg_grad_many call per 32 jobs, coef computed on the device."""
+    term = _events.Term(forward=lambda *job: _launch(*job[:-1], eps, job[-1]),
+                        backward=lambda ev, fls, t0, sc, mp, images, moments, coef: tsimg_grad_many(ev, fls, t0, sc, mp, *images, coef, eps),
+                        loss=lambda moments: loss_of(moments, normalize),
+                        coef=lambda gloss, moments: gloss / (moments[:, 2] + ACTIVE_EPS) if normalize == "active" else gloss)
+    return _events.losses(term, event_sets, flows, t0s, scales, maps, h, w, dev)
 
 
 def timestamp_loss_many(event_sets, flows, t_ref="end", offset=(0, 0), maps=None, eps=1e-9, normalize="active"):
@@ -203,15 +137,11 @@ def timestamp_loss(event_sets, flows, offset=(0, 0), maps=None, eps=1e-9, normal
     maps = _maps(name, maps, offset, len(event_sets))
     eps, normalize = _eps(name, eps), _normalize(name, normalize)
     event_sets = [e.detach() for e in event_sets]
-    t_end, t_start, scales = _both_refs(name, event_sets)
-    half = MAX_JOBS_PER_CALL // 2
+    t_start, t_end, scales = _events.window_ends(event_sets)
     total = torch.zeros((), device=dev, dtype=torch.float64)
     count = torch.zeros((), device=dev, dtype=torch.float64)
-    for i0 in range(0, len(event_sets), half):
-        sl = slice(i0, i0 + half)
-        c = len(event_sets[sl])
-        loss, moments = _losses(event_sets[sl] * 2, flows[sl] * 2, t_end[sl] + t_start[sl], scales[sl] * 2, maps[sl] * 2, h, w, dev, eps,
-                                normalize)
+    for c, jobs in _events.riding_twice((event_sets, event_sets), (flows, flows), (t_end, t_start), (scales, scales), (maps, maps)):
+        loss, moments = _losses(*jobs, h, w, dev, eps, normalize)
         active = moments[:, 2]
         ok = (active[:c] > 0) & (active[c:] > 0)
         total = total + torch.where(ok, loss[:c] + loss[c:], torch.zeros_like(loss[:c])).sum()
@@ -234,14 +164,9 @@ def rsat_many(event_sets, flows, t_ref="end", offset=(0, 0), eps=1e-9):
     flows = [f.detach() for f in flows]
     t0s, scales = _time_refs(name, event_sets, t_ref, dev)
     out = []
-    half = MAX_JOBS_PER_CALL // 2
-    for i0 in range(0, len(event_sets), half):
-        sl = slice(i0, i0 + half)
-        c = len(event_sets[sl])
-        _, _, m = _launch(event_sets[sl] * 2, flows[sl] + [None] * c, t0s[sl] * 2, scales[sl] * 2, maps[sl] * 2, h, w, eps, dev)
-        loss = loss_of(m)
-        num, den = loss[:c], loss[c:]
-        out.append(torch.where(den == 0, torch.full_like(den, float("nan")), num / den))
+    for c, jobs in _events.riding_twice((event_sets, event_sets), (flows, [None] * len(flows)), (t0s, t0s), (scales, scales), (maps, maps)):
+        loss = loss_of(_launch(*jobs, h, w, eps, dev)[2])
+        out.append(_events.ratio_or_nan(loss[:c], loss[c:]))
     return torch.cat(out)
 
 

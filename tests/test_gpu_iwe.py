@@ -29,7 +29,8 @@ DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "iwe.npz")
 # name -> (H, W, N, fractional coordinates)
 SHAPES = {"37x50": (37, 50, 5000, False), "64x61": (64, 61, 5000, True), "260x346": (260, 346, 50000, False),
-          "8x1280": (8, 1280, 3000, False), "720x1280": (720, 1280, 200000, False)}
+          "8x1280": (8, 1280, 3000, False), "720x1280": (720, 1280, 200000, False),
+          "241x40": (241, 40, 5000, True)}               # rows = 2 per band, 121 bands, the last of them one row: the short last band
 
 
 @pytest.fixture(params=["binned", "direct"])

@@ -39,7 +39,8 @@ DEV = "cuda:0"
 BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "iwe_forward_bits.json")
 # name -> (H, W, N, fractional coordinates)
 SHAPES = {"37x50": (37, 50, 5000, False), "64x61": (64, 61, 5000, True), "8x1280": (8, 1280, 3000, False),
-          "260x346": (260, 346, 50000, False), "720x1280": (720, 1280, 200000, False)}
+          "260x346": (260, 346, 50000, False), "720x1280": (720, 1280, 200000, False),
+          "241x40": (241, 40, 5000, True)}               # rows = 2 per band, 121 bands, the last of them one row: the short last band
 C_A = {"binned": 2.0 ** -23, "direct": 2.0 ** -40}
 IDENTITY = (1.0, 0.0, 1.0, 0.0)
 
@@ -468,7 +469,8 @@ def test_contrast_loss_through_eraft():
 # ------------------------------------------------------------------------------------------------ the forward's bits
 def forward_digests():
     """sha256 of the forward's image and moments bytes, per case, time reference and form: tests/golden/iwe_forward_bits.json holds
-    them as the library gave them BEFORE the per-event device functions moved into iwe_shared.h and the offset became an event map.
+    them as the library gave them BEFORE the per-event device functions moved into iwe_shared.h and the offset became an event map
+    (241x40: before the forward's kernels moved into iwe_fwd_shared.h, recorded with the library of the commit before that one).
     The binned image does not depend on the order of its adds (fixed-point weights, exact fp64 sums); the direct form's fp64 atomics
     could round a cell apart once in ~1e7 cells, so it is pinned on the three small frames only."""
     out = {}
@@ -498,5 +500,5 @@ def test_forward_bits_are_the_parent_commits(monkeypatch):
     monkeypatch.delenv("EEM_IWE_DIRECT", raising=False)            # (forward_digests sets and clears it itself; restored afterwards)
     want = json.load(open(BITS))
     got = forward_digests()
-    assert sorted(got) == sorted(want) and len(want) == 32
+    assert sorted(got) == sorted(want) and len(want) == 40
     assert [k for k in want if got[k] != want[k]] == []

@@ -44,7 +44,8 @@ EPS = 1e-9
 # name -> (H, W, N, fractional coordinates, time references)
 SHAPES = {"37x50": (37, 50, 5000, False, ("end", "start")), "64x61": (64, 61, 5000, True, ("end", "start")),
           "8x1280": (8, 1280, 3000, False, ("end", "start")), "720x1280": (720, 1280, 20000, False, ("end",)),
-          "3x4804": (3, 4804, 2000, False, ("end", "start"))}      # 4 planes of 4804 cells pass 150 KB of LDS: the plan refuses the frame
+          "3x4804": (3, 4804, 2000, False, ("end", "start")),      # 4 planes of 4804 cells pass 150 KB of LDS: the plan refuses the frame
+          "241x40": (241, 40, 5000, True, ("end", "start"))}       # rows = 2 per band of 4 planes, 121 bands, the last of them one row
 CASES = [(name, t_ref) for name, s in SHAPES.items() for t_ref in s[4]]
 C_A = {"binned": 2.0 ** -23, "direct": 2.0 ** -40}
 IDENTITY = (1.0, 0.0, 1.0, 0.0)

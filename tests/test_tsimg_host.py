@@ -110,6 +110,10 @@ def test_abi_is_declared_with_its_replaces_lines():
     assert '#include "iwe_grad_shared.h"' in text and "void iwe_sample(" not in text and "iwe_grad_event(" not in text.split("namespace {", 1)[1]
     assert '#include "iwe_grad_shared.h"' in open(os.path.join(csrc, "iwe_grad.hip")).read()
     assert '#include "iwe_shared.h"' in open(os.path.join(csrc, "iwe_grad_shared.h")).read()
+    # one forward: both objectives instantiate iwe_fwd_shared.h's kernels and define none of their own (iwe.hip: the warp alone)
+    iwe_text = open(os.path.join(csrc, "iwe.hip")).read()
+    assert '#include "iwe_fwd_shared.h"' in text and '#include "iwe_fwd_shared.h"' in iwe_text
+    assert text.count("__global__") == 0 and iwe_text.count("__global__") == 1 and "iwe_warp_kernel" in iwe_text
     switches = open(os.path.join(csrc, "switches.def.h")).read()
     assert "TSIMG" not in switches.upper() and "TIMESTAMP" not in switches.upper()      # no new switch: the IWE's two apply
     for name in ("avg_timestamps", "avg_timestamps_many", "timestamp_loss", "timestamp_loss_many", "rsat", "rsat_many"):
