@@ -10,6 +10,7 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 from .augmentor import AugPlan, apply_host, augment_many   # noqa: F401
+from .dsec import VoxelGrid, flow_16bit_to_float, flow_float_to_16bit, voxel_grid_many, voxelize_windows   # noqa: F401
 from .eemflow import EEMFlow            # noqa: F401
 from .events import pack_events_many, read_event_columns   # noqa: F401
 from .iwe import contrast_many, fwl, fwl_loss, fwl_many, iwe, iwe_many, warp_events   # noqa: F401

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "eemflow_voxelize_many": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "eemflow_voxelize_last_form": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
+    "eemflow_voxelize_trilinear_many": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "eemflow_pack_events_many": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.POINTER(ctypes.c_int),
                                                 ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),

@@ -810,6 +810,43 @@ extern "C" int eemflow_voxelize_many(int nsets, const double* const* events, con
     return voxelize_jobs(nsets, events, n_events, bins, h, w, normalize, grids, none, none, stream);
 }
 
+// The DSEC trilinear grid (voxel_tri.hip): the sets arrive as columns; its own pool of scratch arenas (four records per event)
+extern "C" int eemflow_voxelize_trilinear_many(int nsets, const void* const* x, const void* const* y, const float* const* t, const float* const* p,
+                                               const int64_t* n_events, int xy_type, const float* const* rectify_maps, int map_h, int map_w,
+                                               int bins, int h, int w, int normalize, float* const* grids, void* stream) {
+    static Arena arena;
+    EEM_REQUIRE(x && y && t && p && n_events && grids, "eemflow_voxelize_trilinear_many: NULL argument");
+    EEM_REQUIRE(nsets >= 1 && nsets <= VOX_MAX_JOBS, "eemflow_voxelize_trilinear_many: 1..%d event sets per call; got %d", VOX_MAX_JOBS, nsets);
+    EEM_REQUIRE(bins > 0 && h > 0 && w > 0, "eemflow_voxelize_trilinear_many: bad shape bins=%d h=%d w=%d", bins, h, w);
+    EEM_REQUIRE(normalize == 0 || normalize == 1, "eemflow_voxelize_trilinear_many: normalize is 0 (raw) or 1 (normalised grid); got %d", normalize);
+    EEM_REQUIRE(xy_type >= EEMFLOW_XY_F32 && xy_type <= EEMFLOW_XY_I32, "eemflow_voxelize_trilinear_many: unknown coordinate type %d", xy_type);
+    EEM_REQUIRE((xy_type == EEMFLOW_XY_F32) == (rectify_maps == nullptr),
+                "eemflow_voxelize_trilinear_many: raw integer coordinates come with rectification maps, fp32 coordinates without");
+    EEM_REQUIRE(!rectify_maps || (map_h >= 1 && map_w >= 1), "eemflow_voxelize_trilinear_many: bad map shape %d x %d", map_h, map_w);
+    const size_t elem = xy_type == EEMFLOW_XY_I16 ? 2 : 4;
+    for (int k = 0; k < nsets; ++k) {
+        EEM_REQUIRE(x[k] && y[k] && t[k] && p[k] && grids[k], "eemflow_voxelize_trilinear_many: set %d has a NULL buffer", k);
+        EEM_REQUIRE(n_events[k] >= 1, "eemflow_voxelize_trilinear_many: set %d is empty (the reference indexes t[-1], dsec_utils.py:33)", k);
+        EEM_REQUIRE(((uintptr_t)x[k] % elem) == 0 && ((uintptr_t)y[k] % elem) == 0 && ((uintptr_t)t[k] & 3) == 0 && ((uintptr_t)p[k] & 3) == 0 &&
+                    ((uintptr_t)grids[k] & 3) == 0, "eemflow_voxelize_trilinear_many: set %d has a buffer that is not aligned to its elements", k);
+        if (rectify_maps) EEM_REQUIRE(rectify_maps[k] && ((uintptr_t)rectify_maps[k] & 3) == 0, "eemflow_voxelize_trilinear_many: set %d has no rectification map", k);
+    }
+    size_t part[VOX_MAX_JOBS] = {}, need = 0;
+    int64_t nmax = 0;
+    for (int k = 0; k < nsets; ++k) nmax = std::max(nmax, n_events[k]);
+    for (int k = 0; k < nsets; ++k) { part[k] = (voxel_tri_scratch_bytes(n_events[k], nmax, bins, h, w) + 255) & ~(size_t)255; need += part[k]; }
+    std::lock_guard<std::mutex> guard(arena.lock);
+    char* base = nullptr;
+    void* token = nullptr;
+    int rc = arena.take(need, stream, &base, &token);
+    if (rc != EEM_OK) return rc;
+    void* scratch[VOX_MAX_JOBS];
+    for (int k = 0; k < nsets; ++k) { scratch[k] = base; base += part[k]; }
+    rc = voxel_tri_launch_jobs(nsets, x, y, t, p, n_events, xy_type, rectify_maps, map_h, map_w, bins, h, w, normalize, grids, scratch,
+                               (hipStream_t)stream);
+    return rc == EEM_OK ? arena.done(token, stream) : rc;
+}
+
 // Both event sets of a sample (loader/HREM.py:226-232: event_volume_old, event_volume_new) in ONE three-launch sequence instead of
 // two: the kernels are latency chains at these sizes (36 us for 2 x 10^5 events), two of them side by side cost little more than one
 extern "C" int eemflow_voxelize_pair(const double* events1, int64_t n1, const double* events2, int64_t n2, int bins, int h, int w,

@@ -418,5 +418,11 @@ size_t voxel_scratch_bytes(int64_t n);
 #define VOX_MAX_JOBS 32
 int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, int bins, int h, int w, int normalize, float* const* grid,
                       int64_t* const* idx_left, int64_t* const* idx_right, void* const* scratch, hipStream_t stream);
+// the DSEC trilinear voxelizer (voxel_tri.hip): columns x, y (EEMFLOW_XY_F32, or raw _I16 / _I32 with a rectification map), t, p (fp32)
+size_t voxel_tri_scratch_bytes(int64_t n, int64_t nmax, int bins, int h, int w);
+int voxel_tri_launch_jobs(int njobs, const void* const* x, const void* const* y, const float* const* t, const float* const* p, const int64_t* n,
+                          int xy_type, const float* const* maps, int map_h, int map_w, int bins, int h, int w, int normalize,
+                          float* const* grid, void* const* scratch, hipStream_t stream);
+void voxel_note_form(const char* text);          // what eemflow_voxelize_last_form reports for such a sequence
 
 #include "devstate_hip.h"   // per-device launch state, scratch arenas, DevBuf (needs EEM_HIP_CHECK above)

@@ -486,6 +486,30 @@ int eemflow_voxelize_many(int nsets, const double* const* events, const int64_t*
  * report the last ("j1:direct...").  A few integers stored on the host per call; "" before any call, unchanged by a refused one. */
 int eemflow_voxelize_last_form(char* buf, int cap);
 
+/* The DSEC voxel grid E-RAFT was trained on: nsets (1..32) event sets of ONE grid shape by one launch sequence, each given as its four
+ * COLUMNS on the device, n_events[k] >= 1 elements each.  t[k], p[k] are fp32; x[k], y[k] are fp32 sub-pixel coordinates (xy_type
+ * EEMFLOW_XY_F32, rectify_maps NULL), or RAW sensor coordinates (EEMFLOW_XY_I16 / _I32) that rectify_maps[k] - [map_h][map_w][2] fp32 on the
+ * device, one per set - turns into (x, y) = map[y_raw][x_raw]; an event whose raw coordinate lies outside the map is dropped.
+ * Every operation is unfused fp32:  dT = t[n-1] - t[0];  tn = ((float)(bins-1) * (t_i - t[0])) / dT;  x0 = (int)x, y0 = (int)y,
+ * b0 = (int)tn (truncation toward zero, so a coordinate in (-1, 0) votes with one negative weight);  val = 2 p - 1;  each of the eight
+ * corners (xl, yl, bl) in {x0, x0+1} x {y0, y0+1} x {b0, b0+1} that lies inside the grid receives
+ * ((val * (1 - |xl - x|)) * (1 - |yl - y|)) * (1 - |bl - tn|); corners at xl == w, yl == h, bl == bins are masked (nothing wraps).
+ * An event whose x, y or tn is not finite or not below 2^31 in magnitude is dropped whole - dT == 0 (one event included) drops every
+ * event and leaves a grid of +0.0.  Only t[0] and t[n-1] set the scale: the sets need not be sorted.  grids[k] [bins][h][w] fp32: every
+ * cell is the fp64 sum of its votes rounded to fp32 once, every untouched cell +0.0, all cells stored (no memset needed; any 4-byte
+ * alignment).  normalize: 0 raw, 1 mean / unbiased sd over the non-zero voxels (std > 0, else the mean alone).  Each grid is bitwise what
+ * a call with that set alone gives.  x, y, t, p, n_events, rectify_maps and grids are HOST arrays, read before the call returns.
+ * Stream-ordered, no host synchronisation.  eemflow_voxelize_last_form reports the sequence as "tri:j<sets>:" + "bin_e<1|2>[_i16|_i32]" +
+ * the band kernel's form as above (+ "+norm"), or "tri:j1:direct64[...]+finish[+norm]" for the fp64-atomic form that grids beyond the
+ * LDS layout (and EEM_VOX_DIRECT=1) take.
+ * Replaces: VoxelGrid.convert (utils/dsec_utils.py:19-64) and, with a map, the rectification lookup in front of it. */
+#define EEMFLOW_XY_F32 0
+#define EEMFLOW_XY_I16 1
+#define EEMFLOW_XY_I32 2
+int eemflow_voxelize_trilinear_many(int nsets, const void* const* x, const void* const* y, const float* const* t, const float* const* p,
+                                    const int64_t* n_events, int xy_type, const float* const* rectify_maps, int map_h, int map_w,
+                                    int bins, int h, int w, int normalize, float* const* grids, void* stream);
+
 /* Event preparation: nsets (1..EEMFLOW_PACK_MAX) event sets, each given as its four COLUMNS on the device - t[k], x[k], y[k], p[k], n_events[k]
  * elements each, of the dtype codes[4*k + 0..3] (EEMFLOW_PACK_*; a bool column is uploaded as u8) - packed by ONE launch into
  * out[k] [n_events[k]][4] f64 (t, x, y, p): the table eemflow_voxelize, the IWE entry points and a loader's `events` take.  Every value
