@@ -2,6 +2,7 @@
 
     python -m eemflow_amd.cli train [flags]      # train_EEMFlow_HREM.py: HREM meshflow training, checkpoint per epoch
     python -m eemflow_amd.cli test  [flags]      # test_EEMFlow_HREM.py: evaluation over every sequence of the HREM test split
+    python -m eemflow_amd.cli run   [flags]      # not in the reference: the flows along ONE recording (an events npz cut into windows)
 
 Same flags and defaults as the reference scripts (`--lr --wd --train_iters --val_iters --batch_size --input_type --model_name
 --start-epoch --num_workers --test_only --test_sequence ...`), the `lr{lr}_we{wd}` run folder, `config.json` / `train.log` /
@@ -153,6 +154,26 @@ def build_parser():
                                 'share and the AEE over the consistent pixels to every line (threshold A1 * (|fw| + |bw|) + A2)')
     common(sub.add_parser('train', help='train_EEMFlow_HREM.py'), True)
     common(sub.add_parser('test', help='test_EEMFlow_HREM.py'), False)
+    r = sub.add_parser('run', help='flows along one recording (not in the reference): the events npz is uploaded once, cut into consecutive '
+                                   'windows and voxelized on the GPU straight from its columns, window pairs go through forward_stream')
+    r.add_argument('--events', required=True, help='the recording: an HREM-style npz with the arrays t, x, y, p')
+    r.add_argument('--height', required=True, type=int, help='sensor rows')
+    r.add_argument('--width', required=True, type=int, help='sensor columns')
+    r.add_argument('--model_name', '-model', default='EEMFlow', type=str)
+    r.add_argument('--checkpoint', required=True, help='checkpoint file of the model')
+    r.add_argument('--config', default=None, help='JSON with the layout of config/a_meshflow.json (default: built-in copy of its used fields)')
+    r.add_argument('--device', default='cuda:0')
+    r.add_argument('--window_ms', default=None, type=float, metavar='MS', help='cut by duration: windows of MS milliseconds from the first event')
+    r.add_argument('--window_events', default=None, type=int, metavar='N', help='cut by count: windows of N events')
+    r.add_argument('--t_unit', default='ns', choices=('ns', 'us', 's'), help='unit of the t array (HREM: ns)')
+    r.add_argument('--stream', default=0, type=int, metavar='N', help='windows per forward_stream call (default: as many as the model takes)')
+    r.add_argument('--out', default=None, metavar='DIR', help='write the flow of pair k (window k -> window k + 1) as DIR/%%06d.flo')
+    r.add_argument('-v', '--visualize', action='store_true', help='with --out: also the colour-wheel image of every flow, DIR/%%06d_flow.jpg')
+    r.add_argument('--fwl', action='store_true', help='the flow warp loss of every pair (the events of its first window under its flow) on its line, the mean in the summary')
+    r.add_argument('--rsat', action='store_true', help='RSAT of every pair on its line, the mean in the summary')
+    r.add_argument('--fb_check', nargs=2, type=float, default=None, metavar=('A1', 'A2'),
+                   help='EEMFlow: run the stream bidirectionally and add the forward-backward consistent share of every pair to its line '
+                        '(threshold A1 * (|fw| + |bw|) + A2); with --out the backward flows go to DIR/%%06d_bw.flo')
     return p
 
 
@@ -347,9 +368,100 @@ def test(args):
                                   loader_threads=args.loader_threads, coalesce=coalesce, **extra)
 
 
+T_UNITS = {'ns': (1e-9, 1_000_000), 'us': (1e-6, 1_000), 's': (1.0, 1e-3)}     # unit -> (scale_a to seconds, t units per millisecond)
+
+
+def run(args):
+    """`cli run`: returns {'windows', 'events', 'pairs', 'frames_per_s', 'meanFWL', 'meanRSAT'} (the means None where not asked)."""
+    import time
+    if (args.window_ms is None) == (args.window_events is None):
+        raise SystemExit("run: give exactly one of --window_ms MS and --window_events N")
+    if args.window_ms is not None and not args.window_ms > 0:
+        raise SystemExit("--window_ms MS: MS > 0")
+    if args.window_events is not None and args.window_events < 1:
+        raise SystemExit("--window_events N: N >= 1")
+    if args.height < 1 or args.width < 1:
+        raise SystemExit("--height H --width W: the sensor size, both >= 1")
+    if args.visualize and not args.out:
+        raise SystemExit("-v (--visualize) writes its images beside the flows: it needs --out DIR")
+    if args.fb_check is not None and args.model_name != 'EEMFlow':
+        raise SystemExit(f"--fb_check needs a model whose forward_stream is bidirectional (EEMFlow); {args.model_name} has none")
+    if args.stream < 0 or args.stream == 1:
+        raise SystemExit("--stream N: N >= 2 windows per forward_stream call (0: as many as the model takes)")
+    if not os.path.isfile(args.events):
+        raise SystemExit(f"--events {args.events}: no such file")
+    from . import harness
+    from .hrem import write_flo
+    from .recording import EventRecording
+    config = load_config(args.config)
+    model = build_model(args.model_name, config, training=False)
+    harness.load_checkpoint(args.checkpoint, model)
+    dev = torch.device(args.device)
+    torch.cuda.set_device(dev)
+    model = model.to(dev).eval()
+    scale_a, per_ms = T_UNITS[args.t_unit]
+    rec = EventRecording.from_npz(args.events, args.height, args.width, device=dev, scale_a=scale_a)
+    if args.window_ms is not None:
+        span = args.window_ms * per_ms
+        offsets = rec.window_offsets(window=int(span) if float(span).is_integer() else span)
+    else:
+        offsets = rec.window_offsets(count=args.window_events)
+    nwin = len(offsets) - 1
+    if nwin < 2:
+        raise SystemExit(f"run: the recording's {rec.n} events give {nwin} full windows; a flow needs two")
+    limit = model.MAX_STREAM_BIDIR if args.fb_check is not None else model.MAX_STREAM
+    if args.stream > limit:
+        raise SystemExit(f"--stream {args.stream}: {args.model_name} takes at most {limit} windows per call" + (" with --fb_check" if args.fb_check is not None else ""))
+    writer = None
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        if args.visualize:
+            from .viz import ImageWriter, flow_to_image_many
+            writer = ImageWriter(args.out)
+    sums = {'FWL': [0.0, 0], 'RSAT': [0.0, 0]}
+    pairs = 0
+    torch.cuda.synchronize(dev)
+    start = time.perf_counter()
+    try:
+        for item in harness.run_recording(model, rec, offsets, chunk=args.stream or None, fwl=args.fwl, rsat=args.rsat, fb_check=args.fb_check):
+            k = item['k']
+            line = 'pair {:6d}  events {:9d}'.format(k, int(offsets[k + 1] - offsets[k]))
+            for key in ('FWL', 'RSAT'):
+                if key in item:
+                    val = float(item[key])
+                    if val == val:                                   # NaN (nothing to compare with) stays out of the mean
+                        sums[key][0] += val
+                        sums[key][1] += 1
+                    line += '  {}: {:2.6f}'.format(key, val)
+            if 'mask_fw' in item:
+                line += '  consistent: {:.4f}'.format(float(item['mask_fw'].mean()))
+            if args.out:
+                write_flo(os.path.join(args.out, '%06d.flo' % k), item['flow'][0].permute(1, 2, 0).cpu().numpy())
+                if 'flow_bw' in item:
+                    write_flo(os.path.join(args.out, '%06d_bw.flo' % k), item['flow_bw'][0].permute(1, 2, 0).cpu().numpy())
+                if writer is not None:
+                    writer.submit('%06d_flow.jpg' % k, flow_to_image_many([item['flow']], bgr=True)[0])
+            print(line)
+            pairs += 1
+        torch.cuda.synchronize(dev)
+    finally:
+        if writer is not None:
+            writer.close()
+    wall = time.perf_counter() - start
+    mean = {key: (v[0] / v[1] if v[1] else float('nan')) for key, v in sums.items()}
+    line = 'windows {}  events {}  pairs {}  {:.1f} frames/s'.format(nwin, int(offsets[-1] - offsets[0]), pairs, pairs / wall if wall > 0 else float('nan'))
+    if args.fwl:
+        line += '  meanFWL: {:2.6f}'.format(mean['FWL'])
+    if args.rsat:
+        line += '  meanRSAT: {:2.6f}'.format(mean['RSAT'])
+    print(line)
+    return {'windows': nwin, 'events': int(offsets[-1] - offsets[0]), 'pairs': pairs, 'frames_per_s': pairs / wall if wall > 0 else float('nan'),
+            'meanFWL': mean['FWL'] if args.fwl else None, 'meanRSAT': mean['RSAT'] if args.rsat else None}
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    return train(args) if args.command == 'train' else test(args)
+    return {'train': train, 'test': test, 'run': run}[args.command](args)
 
 
 if __name__ == '__main__':

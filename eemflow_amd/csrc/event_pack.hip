@@ -23,6 +23,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "event_cols.h"   // pk_load, pk_elem_bytes
+
 namespace {
 
 constexpr int PK_THREADS = 256;
@@ -36,20 +38,6 @@ struct PackJob {
     int code[4];
 };
 struct PackJobs { PackJob j[EEMFLOW_PACK_MAX]; };        // 64 bytes each: 2 KB of kernel arguments at 32 jobs
-
-// element i of a column as astype(float64) gives it (the code is the same in every lane: a scalar branch)
-__device__ __forceinline__ double pk_load(const void* __restrict__ p, int code, long i) {
-    switch (code) {
-        case EEMFLOW_PACK_U8: return (double)static_cast<const uint8_t*>(p)[i];
-        case EEMFLOW_PACK_I8: return (double)static_cast<const int8_t*>(p)[i];
-        case EEMFLOW_PACK_U16: return (double)static_cast<const uint16_t*>(p)[i];
-        case EEMFLOW_PACK_I16: return (double)static_cast<const int16_t*>(p)[i];
-        case EEMFLOW_PACK_I32: return (double)static_cast<const int32_t*>(p)[i];
-        case EEMFLOW_PACK_I64: return (double)static_cast<const long long*>(p)[i];       // round to nearest even
-        case EEMFLOW_PACK_F32: return (double)static_cast<const float*>(p)[i];
-        default: return static_cast<const double*>(p)[i];
-    }
-}
 
 __global__ __launch_bounds__(PK_THREADS) void event_pack_kernel(PackJobs jobs, double scale_a, double scale_b, int relative) {
     const PackJob& J = jobs.j[blockIdx.y];
@@ -85,16 +73,6 @@ __global__ __launch_bounds__(PK_THREADS) void event_pack_kernel(PackJobs jobs, d
                 out[i * 2 + 1] = f64x2{y[k], p[k]};
             }
         }
-    }
-}
-
-inline int pk_elem_bytes(int code) {
-    switch (code) {
-        case EEMFLOW_PACK_U8: case EEMFLOW_PACK_I8: return 1;
-        case EEMFLOW_PACK_U16: case EEMFLOW_PACK_I16: return 2;
-        case EEMFLOW_PACK_I32: case EEMFLOW_PACK_F32: return 4;
-        case EEMFLOW_PACK_I64: case EEMFLOW_PACK_F64: return 8;
-        default: return 0;
     }
 }
 

@@ -3,7 +3,9 @@
 // {pixel-in-band | bin << 16, left vote, right vote} sorted by band, beside a run table; from there on the work is the same and lives
 // here once: the band kernel that adds the records in fp64 LDS cells and rounds every cell to fp32 once, the moments, the
 // normalisation / statistics kernels, the plan that sizes the bands and the host helpers that launch them.  The algorithm is
-// described in voxel.hip's header comment.  Both files are built with -ffp-contract=off.
+// described in voxel.hip's header comment.  A third binning kernel, voxel_cols.hip's, makes voxel.hip's two votes from the raw columns
+// of a recording: the per-event arithmetic of those votes (vox_vote, vox_record) and the second half of every binning block
+// (vox_slab_out) live here too, once.  All three files are built with -ffp-contract=off.
 #pragma once
 
 #include <string.h>
@@ -65,6 +67,70 @@ struct VoxPlan {
     int nb;                  // bands
     unsigned hw;             // H * W
 };
+// ------------------------------------------------------------------------------------------------ per-event arithmetic (two temporal votes)
+// What voxel.hip's binning kernel (events from the float64 table) and voxel_cols.hip's (events from a recording's raw columns) do with one
+// event [t, x, y, p] once it is four doubles: the same text, so the same votes bit for bit.
+struct VoxVote {
+    long long il, ir;        // flat int64 indices of the two votes (valid where okl / okr)
+    long long pix;           // x + y*W
+    int tl;                  // left bin
+    float vl, vr;
+    bool okl, okr;
+};
+
+struct VoxTime {
+    double t0, dT;
+};
+
+__device__ __forceinline__ VoxVote vox_vote(double t, double x, double y, double p, const VoxTime& tm, int bins, int h,
+                                            int w) {
+    VoxVote v;
+    const double ts = ((double)(bins - 1) * (t - tm.t0)) / tm.dT;  // :488
+    const long long xs = (long long)x;                             // .long() truncates, :490-491
+    const long long ys = (long long)y;
+    float pol = (float)p;
+    if (pol == 0.f) pol = -1.f;                                    // :493
+    const double tis = floor(ts);
+    const long long tl = (long long)tis;
+    const float dts = (float)(ts - tis);
+    v.vl = pol * (1.0f - dts);
+    v.vr = pol * dts;
+    const long long plane = (long long)w * h;
+    v.okl = (tis < (double)bins) && (tis >= 0.0);                  // :502-503
+    v.okr = ((tis + 1.0) < (double)bins) && (tis >= 0.0);          // :517-518
+    v.pix = xs + ys * w;
+    v.il = v.pix + tl * plane;
+    v.ir = v.pix + (tl + 1) * plane;
+    v.tl = (int)tl;
+    return v;
+}
+
+// The 12-byte record of an event's pair of votes: false where nothing of it lands inside the grid; else *band = its band and
+// {*key, *vl, *vr} = {pixel-in-band | bin << 16, left vote, right vote}
+__device__ __forceinline__ bool vox_record(const VoxVote& v, int bins, const VoxPlan& pl, unsigned* band, unsigned* key, float* vl,
+                                           float* vr) {
+    long long pix = v.pix;
+    int tl = v.tl;
+    float wl = v.vl, wr_ = v.okr ? v.vr : 0.f;                     // a masked right vote stays masked wherever the pair lands
+    if (v.okl && (unsigned long long)pix >= (unsigned long long)pl.hw) {
+        // flat-index semantics of the reference (see voxel_scatter_kernel): a pixel index outside the plane moves the
+        // pair of votes by whole planes; each vote survives while ITS flat index stays inside the grid
+        long long q = pix / (long long)pl.hw;
+        if (pix - q * (long long)pl.hw < 0) --q;                   // floor division
+        pix -= q * (long long)pl.hw;
+        const long long t2 = (long long)tl + q;
+        if (t2 == -1) { tl = 0; wl = wr_; wr_ = 0.f; }             // left vote in front of the grid, right vote in plane 0
+        else tl = (t2 >= 0 && t2 < bins) ? (int)t2 : -1;
+    }
+    if (!(v.okl && tl >= 0)) return false;
+    const unsigned bd = (unsigned)pix / (unsigned)pl.band_px;
+    *band = bd;
+    *key = ((unsigned)pix - bd * (unsigned)pl.band_px) | ((unsigned)tl << 16);
+    *vl = wl;
+    *vr = wr_;
+    return true;
+}
+
 // One voxelization of a launch: blockIdx.y picks the job, so the two event sets of a sample (loader/HREM.py:226-232) share each of
 // the three launches (same grid shape and plan, their own events, slabs, run tables, moments and grid)
 struct VoxJob {
@@ -79,6 +145,36 @@ struct VoxJob {
     int nblk;                // binning blocks (slabs) of this job
 };
 struct VoxJobs { VoxJob j[VOX_MAX_JOBS]; };      // (72 bytes each: 2.3 KB of kernel arguments at 32 jobs)
+
+// The second half of a binning block (all VT threads call it, after the last rank was taken from hist[]): scans the band counts, writes
+// row blockIdx.x of the run table, sorts the thread's up to R records {key, vl, vr} (band == 0xffffffff: none) by band into the LDS slab
+// `stage` and stores the slab - R * VT record slots from recs on - as whole 16-byte pieces of consecutive threads (scattered 12-byte
+// stores ran at half the rate).  hist, lpos: VT words of LDS; sh: VT / 64.
+template <int R>
+__device__ __forceinline__ void vox_slab_out(const unsigned (&key)[R], const unsigned (&band)[R], const unsigned (&rank)[R], const float (&vl)[R],
+                                             const float (&vr)[R], unsigned* hist, unsigned* lpos, unsigned* sh, unsigned* stage,
+                                             unsigned* __restrict__ run_start, unsigned* __restrict__ recs, const VoxPlan& pl) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    const unsigned start = block_exscan(hist[tid], sh);            // bands >= nb hold 0: thread nb gets the slab's fill
+    lpos[tid] = start;
+    if (tid <= pl.nb) run_start[(size_t)blockIdx.x * (pl.nb + 1) + tid] = start;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        if (band[k] != 0xffffffffu) {
+            unsigned* r = stage + 3u * (lpos[band[k]] + rank[k]);
+            r[0] = key[k];
+            r[1] = __float_as_uint(vl[k]);
+            r[2] = __float_as_uint(vr[k]);
+        }
+    }
+    __syncthreads();
+    const unsigned words = 3u * lpos[pl.nb];
+    u32x4* slab = reinterpret_cast<u32x4*>(recs + (size_t)blockIdx.x * (VT * R) * 3);
+    const u32x4* st4 = reinterpret_cast<const u32x4*>(stage);
+    for (unsigned i = tid; i * 4 < words; i += VT) slab[i] = st4[i];   // (the last piece may carry up to three stale words: nobody reads them)
+}
 
 // ------------------------------------------------------------------------------------------------ moments
 // Every block stores the f64 (count, sum, sum of squares) of its non-zero voxels in its own slot; the normalisation
@@ -426,6 +522,64 @@ inline int vox_launch_norm(const VoxJobs& jobs, int njobs, long total, int nsums
     if (njobs >= 2 && blocks > 256 / njobs) blocks = std::max(16L, 256L / njobs);     // the jobs share the chip
     hipLaunchKernelGGL(vox_norm_kernel, dim3((unsigned)blocks, njobs), dim3(VT), 0, stream, jobs, total, nsums);
     EEM_HIP_CHECK(hipGetLastError());
+    return EEM_OK;
+}
+
+// what a launch sequence ran (eemflow_voxelize_last_form): small integers stored on the host beside the launches
+struct VoxForm {
+    int njobs;               // 0: no sequence yet
+    int ept;                 // binning kernel's events per thread; 0: the direct kernel
+    int bt, vec4, sgs;       // band kernel: threads per block, 16-byte read-out, log2 of the lanes per run
+    int moments;             // the raw band launch left its moments / vox_moments_kernel followed the direct kernel
+    int after;               // 0 nothing, 1 vox_norm_kernel, 2 vox_stats_kernel, 3 the two band passes
+};
+
+// the report of a form; bin: the binning kernel's name in it ("bin": vox_bin_kernel, "colbin": vox_bin_cols_kernel)
+inline void vox_form_text(const VoxForm& f, const char* bin, char* buf, size_t cap) {
+    static const char* const kAfter[4] = {"", "+norm", "+stats", ""};
+    if (f.njobs == 0) {
+        buf[0] = 0;
+    } else if (f.ept == 0) {
+        snprintf(buf, cap, "j%d:direct%s%s", f.njobs, f.moments ? "+moments" : "", kAfter[f.after]);
+    } else {
+        char band[48];
+        snprintf(band, sizeof(band), "band%d_%s_s%d", f.bt, f.vec4 ? "v4" : "v1", f.sgs);
+        if (f.after == 3)
+            snprintf(buf, cap, "j%d:%s_e%d+%s_moments+%s_normalised", f.njobs, bin, f.ept, band, band);
+        else
+            snprintf(buf, cap, "j%d:%s_e%d+%s_%s%s", f.njobs, bin, f.ept, band, f.moments ? "raw_sums" : "raw", kAfter[f.after]);
+    }
+}
+
+// The launches behind a binning kernel that has left the slabs and run tables of `jobs` (ept events per thread, the longest set nmax
+// events): the band kernel and, by `normalize`, vox_norm_kernel or vox_stats_kernel - or the two band passes of EEM_VOX_TWOPASS.  Fills
+// in what *vf reports of them.
+inline int vox_launch_after_bin(const VoxJobs& jobs, int njobs, int ept, long nmax, int bins, long total, int normalize, const VoxPlan& pl,
+                                int lds, float* const* grid, VoxForm* vf, hipStream_t stream) {
+    int rc;
+    const int vec4 = vox_vec4(pl, njobs, grid);
+    // Few events per voxel: accumulating the bands twice (16 B per vote from L2 / HBM each time) is cheaper than the normalisation's
+    // read + write of the whole grid - a moments-only launch, then a launch that stores the bands already normalised
+    const long two_pass_ratio = sw_long<SW_EEM_VOX_TWOPASS>();   // (the tests run both forms in one process)
+    const int sgs = vox_sgs((long)VT * ept, pl.nb);
+    vf->ept = ept; vf->vec4 = vec4; vf->sgs = sgs;
+    auto band = [&](int with_moments, int mode) {
+        return vox_launch_band(jobs, njobs, VT * ept, bins, pl, lds, vec4, with_moments, mode, sgs, &vf->bt, stream);
+    };
+    if (normalize == 1 && two_pass_ratio > 0 && nmax * two_pass_ratio <= total) {
+        if ((rc = band(1, (int)VOX_BAND_MOMENTS)) != EEM_OK || (rc = band(1, (int)VOX_BAND_NORMALISED)) != EEM_OK) return rc;
+        EEM_HIP_CHECK(hipGetLastError());
+        vf->after = 3;
+        return EEM_OK;
+    }
+    if ((rc = band(normalize ? 1 : 0, (int)VOX_BAND_RAW)) != EEM_OK) return rc;
+    EEM_HIP_CHECK(hipGetLastError());
+    if (normalize == 2) {                                              // deferred: the record behind each grid, no pass over the grids
+        hipLaunchKernelGGL(vox_stats_kernel, dim3(njobs), dim3(VT), 0, stream, jobs, total, pl.nb);
+        EEM_HIP_CHECK(hipGetLastError());
+    } else if (normalize) {
+        if ((rc = vox_launch_norm(jobs, njobs, total, pl.nb, stream)) != EEM_OK) return rc;
+    }
     return EEM_OK;
 }
 

@@ -44,7 +44,8 @@
 // take the direct atomic kernel (one job at a time).
 // Which of these a call ran is reported by eemflow_voxelize_last_form (a test observable: integers stored on the host, no launch).
 // Everything behind the binning kernel - the record format, the band kernel, the moments, the normalisation / statistics kernels, the
-// plan - lives in vox_shared.h, which the DSEC trilinear voxelizer (voxel_tri.hip: four records per event) includes too.
+// plan - lives in vox_shared.h, which the DSEC trilinear voxelizer (voxel_tri.hip: four records per event) includes too; so does the per-event
+// arithmetic of this file's votes, which voxel_cols.hip applies to the raw columns of a recording (no float64 table in between).
 #include <string.h>
 
 #include "common.h"
@@ -56,19 +57,7 @@
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------ per-event arithmetic
-struct VoxVote {
-    long long il, ir;        // flat int64 indices of the two votes (valid where okl / okr)
-    long long pix;           // x + y*W
-    int tl;                  // left bin
-    float vl, vr;
-    bool okl, okr;
-};
-
-struct VoxTime {
-    double t0, dT;
-};
-
+// ------------------------------------------------------------------------------------------------ per-event arithmetic (vox_shared.h: VoxVote, VoxTime, vox_vote, vox_record)
 __device__ __forceinline__ VoxTime vox_time(const double* __restrict__ ev, long n) {
     VoxTime tm;
     tm.t0 = ev[0];
@@ -76,30 +65,6 @@ __device__ __forceinline__ VoxTime vox_time(const double* __restrict__ ev, long 
     if (tm.dT == 0.0) tm.dT = 1.0;                                 // loader_utils.py:485-486
     return tm;
 }
-
-__device__ __forceinline__ VoxVote vox_vote(double t, double x, double y, double p, const VoxTime& tm, int bins, int h,
-                                            int w) {
-    VoxVote v;
-    const double ts = ((double)(bins - 1) * (t - tm.t0)) / tm.dT;  // :488
-    const long long xs = (long long)x;                             // .long() truncates, :490-491
-    const long long ys = (long long)y;
-    float pol = (float)p;
-    if (pol == 0.f) pol = -1.f;                                    // :493
-    const double tis = floor(ts);
-    const long long tl = (long long)tis;
-    const float dts = (float)(ts - tis);
-    v.vl = pol * (1.0f - dts);
-    v.vr = pol * dts;
-    const long long plane = (long long)w * h;
-    v.okl = (tis < (double)bins) && (tis >= 0.0);                  // :502-503
-    v.okr = ((tis + 1.0) < (double)bins) && (tis >= 0.0);          // :517-518
-    v.pix = xs + ys * w;
-    v.il = v.pix + tl * plane;
-    v.ir = v.pix + (tl + 1) * plane;
-    v.tl = (int)tl;
-    return v;
-}
-
 
 // ------------------------------------------------------------------------------------------------ direct atomic path
 __global__ __launch_bounds__(256) void voxel_scatter_kernel(const double* __restrict__ ev, long n, int bins, int h,
@@ -129,7 +94,6 @@ __global__ __launch_bounds__(VT) void vox_bin_kernel(VoxJobs jobs, int bins, int
     if ((int)blockIdx.x >= J.nblk) return;                         // the shorter event set of a pair
     const double* __restrict__ ev = J.ev;
     const long n = J.n;
-    unsigned* __restrict__ run_start = J.run_start;
     long long* __restrict__ idx_left = J.idx_left;
     long long* __restrict__ idx_right = J.idx_right;
     __shared__ unsigned hist[VT];
@@ -152,49 +116,14 @@ __global__ __launch_bounds__(VT) void vox_bin_kernel(VoxJobs jobs, int bins, int
             const VoxVote v = vox_vote(a[0], a[1], b[0], b[1], tm, bins, h, w);
             if (idx_left) idx_left[i] = v.okl ? v.il : -1;
             if (idx_right) idx_right[i] = v.okr ? v.ir : -1;
-            long long pix = v.pix;
-            int tl = v.tl;
-            float wl = v.vl, wr_ = v.okr ? v.vr : 0.f;             // a masked right vote stays masked wherever the pair lands
-            if (v.okl && (unsigned long long)pix >= (unsigned long long)pl.hw) {
-                // flat-index semantics of the reference (see voxel_scatter_kernel): a pixel index outside the plane moves the
-                // pair of votes by whole planes; each vote survives while ITS flat index stays inside the grid
-                long long q = pix / (long long)pl.hw;
-                if (pix - q * (long long)pl.hw < 0) --q;           // floor division
-                pix -= q * (long long)pl.hw;
-                const long long t2 = (long long)tl + q;
-                if (t2 == -1) { tl = 0; wl = wr_; wr_ = 0.f; }     // left vote in front of the grid, right vote in plane 0
-                else tl = (t2 >= 0 && t2 < bins) ? (int)t2 : -1;
-            }
-            if (v.okl && tl >= 0) {
-                const unsigned bd = (unsigned)pix / (unsigned)pl.band_px;
+            unsigned bd;
+            if (vox_record(v, bins, pl, &bd, &key[k], &vl[k], &vr[k])) {
                 band[k] = bd;
-                key[k] = ((unsigned)pix - bd * (unsigned)pl.band_px) | ((unsigned)tl << 16);
-                vl[k] = wl;
-                vr[k] = wr_;
                 rank[k] = atomicAdd(&hist[bd], 1u);                // LDS: the returned count is the rank inside the run
             }
         }
     }
-    __syncthreads();
-    const unsigned start = block_exscan(hist[tid], sh);            // bands >= nb hold 0: thread nb gets the slab's fill
-    lpos[tid] = start;
-    if (tid <= pl.nb) run_start[(size_t)blockIdx.x * (pl.nb + 1) + tid] = start;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        if (band[k] != 0xffffffffu) {
-            unsigned* r = stage + 3u * (lpos[band[k]] + rank[k]);
-            r[0] = key[k];
-            r[1] = __float_as_uint(vl[k]);
-            r[2] = __float_as_uint(vr[k]);
-        }
-    }
-    __syncthreads();
-    // the sorted slab leaves as whole 16-byte pieces of consecutive threads (scattered 12-byte stores ran at half the rate)
-    const unsigned words = 3u * lpos[pl.nb];
-    u32x4* slab = reinterpret_cast<u32x4*>(J.recs + (size_t)blockIdx.x * (VT * EPT) * 3);
-    const u32x4* st4 = reinterpret_cast<const u32x4*>(stage);
-    for (unsigned i = tid; i * 4 < words; i += VT) slab[i] = st4[i];   // (the last piece may carry up to three stale words: nobody reads them)
+    vox_slab_out<EPT>(key, band, rank, vl, vr, hist, lpos, sh, stage, J.run_start, J.recs, pl);
 }
 
 template <int EPT>
@@ -205,37 +134,16 @@ int launch_bin(const VoxJobs& jobs, int njobs, long nblk_max, int bins, int h, i
     return EEM_OK;
 }
 
-// what this thread's last launch sequence ran (eemflow_voxelize_last_form): small integers stored on the host beside the launches
-struct VoxForm {
-    int njobs;               // 0: no sequence yet
-    int ept;                 // binning kernel's events per thread; 0: the direct kernel
-    int bt, vec4, sgs;       // band kernel: threads per block, 16-byte read-out, log2 of the lanes per run
-    int moments;             // the raw band launch left its moments / vox_moments_kernel followed the direct kernel
-    int after;               // 0 nothing, 1 vox_norm_kernel, 2 vox_stats_kernel, 3 the two band passes
-};
+// what this thread's last launch sequence ran (eemflow_voxelize_last_form)
 thread_local VoxForm t_vox_form = {0, 0, 0, 0, 0, 0, 0};
-thread_local char t_vox_text[128] = "";   // not empty: the last sequence was voxel_tri.hip's and this is its report
+thread_local char t_vox_text[128] = "";   // not empty: the last sequence was voxel_tri.hip's or voxel_cols.hip's and this is its report
 
 }  // namespace
 
 extern "C" int eemflow_voxelize_last_form(char* buf, int cap) {
     EEM_REQUIRE(buf && cap >= 1, "eemflow_voxelize_last_form: bad arguments");
-    const VoxForm& f = t_vox_form;
-    static const char* const kAfter[4] = {"", "+norm", "+stats", ""};
-    if (t_vox_text[0]) {
-        snprintf(buf, (size_t)cap, "%s", t_vox_text);
-    } else if (f.njobs == 0) {
-        buf[0] = 0;
-    } else if (f.ept == 0) {
-        snprintf(buf, (size_t)cap, "j%d:direct%s%s", f.njobs, f.moments ? "+moments" : "", kAfter[f.after]);
-    } else {
-        char band[48];
-        snprintf(band, sizeof(band), "band%d_%s_s%d", f.bt, f.vec4 ? "v4" : "v1", f.sgs);
-        if (f.after == 3)
-            snprintf(buf, (size_t)cap, "j%d:bin_e%d+%s_moments+%s_normalised", f.njobs, f.ept, band, band);
-        else
-            snprintf(buf, (size_t)cap, "j%d:bin_e%d+%s_%s%s", f.njobs, f.ept, band, f.moments ? "raw_sums" : "raw", kAfter[f.after]);
-    }
+    if (t_vox_text[0]) snprintf(buf, (size_t)cap, "%s", t_vox_text);
+    else vox_form_text(t_vox_form, "bin", buf, (size_t)cap);
     return EEM_OK;
 }
 
@@ -306,35 +214,19 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
             default: rc = launch_bin<8>(jobs, njobs, nblk_max, bins, h, w, pl, stream); break;
         }
         if (rc != EEM_OK) return rc;
-        const int vec4 = vox_vec4(pl, njobs, grid);
-        // Few events per voxel: accumulating the bands twice (16 B per vote from L2 / HBM each time) is cheaper than the normalisation's
-        // read + write of the whole grid - a moments-only launch, then a launch that stores the bands already normalised
-        const long two_pass_ratio = sw_long<SW_EEM_VOX_TWOPASS>();   // (the tests run both forms in one process)
-        const int sgs = vox_sgs((long)VT * ept, pl.nb);
-        vf.ept = ept; vf.vec4 = vec4; vf.sgs = sgs;
-        auto band = [&](int with_moments, int mode) {
-            return vox_launch_band(jobs, njobs, VT * ept, bins, pl, lds, vec4, with_moments, mode, sgs, &vf.bt, stream);
-        };
-        if (normalize == 1 && two_pass_ratio > 0 && (long)nmax * two_pass_ratio <= total) {
-            if ((rc = band(1, (int)VOX_BAND_MOMENTS)) != EEM_OK || (rc = band(1, (int)VOX_BAND_NORMALISED)) != EEM_OK) return rc;
-            EEM_HIP_CHECK(hipGetLastError());
-            vf.after = 3;
-            t_vox_form = vf;
-            t_vox_text[0] = 0;
-            return EEM_OK;
-        }
-        if ((rc = band(normalize ? 1 : 0, (int)VOX_BAND_RAW)) != EEM_OK) return rc;
-        nsums = pl.nb;
-    } else {
-        VoxScratch* sc = (VoxScratch*)scratch[0];
-        jobs.j[0].grid = grid[0]; jobs.j[0].acc = sc->acc;
-        EEM_HIP_CHECK(hipMemsetAsync(grid[0], 0, total * sizeof(float), stream));
-        hipLaunchKernelGGL(voxel_scatter_kernel, dim3((unsigned)((n[0] + 255) / 256)), dim3(256), 0, stream, events[0],
-                           (long)n[0], bins, h, w, grid[0], (long long*)idx_left[0], (long long*)idx_right[0]);
-        if (normalize) {
-            nsums = (int)((total + 4095) / 4096 < 512 ? (total + 4095) / 4096 : 512);
-            hipLaunchKernelGGL(vox_moments_kernel, dim3(nsums), dim3(VT), 0, stream, grid[0], total, sc->acc);
-        }
+        if ((rc = vox_launch_after_bin(jobs, njobs, ept, (long)nmax, bins, total, normalize, pl, lds, grid, &vf, stream)) != EEM_OK) return rc;
+        t_vox_form = vf;
+        t_vox_text[0] = 0;
+        return EEM_OK;
+    }
+    VoxScratch* sc = (VoxScratch*)scratch[0];
+    jobs.j[0].grid = grid[0]; jobs.j[0].acc = sc->acc;
+    EEM_HIP_CHECK(hipMemsetAsync(grid[0], 0, total * sizeof(float), stream));
+    hipLaunchKernelGGL(voxel_scatter_kernel, dim3((unsigned)((n[0] + 255) / 256)), dim3(256), 0, stream, events[0],
+                       (long)n[0], bins, h, w, grid[0], (long long*)idx_left[0], (long long*)idx_right[0]);
+    if (normalize) {
+        nsums = (int)((total + 4095) / 4096 < 512 ? (total + 4095) / 4096 : 512);
+        hipLaunchKernelGGL(vox_moments_kernel, dim3(nsums), dim3(VT), 0, stream, grid[0], total, sc->acc);
     }
     EEM_HIP_CHECK(hipGetLastError());
     if (normalize == 2) {                                              // deferred: the record behind each grid, no pass over the grids
@@ -353,7 +245,7 @@ int voxel_launch_jobs(int njobs, const double* const* events, const int64_t* n, 
     return EEM_OK;
 }
 
-// voxel_tri.hip's launch sequences report through the same observable, in their own words
+// voxel_tri.hip's and voxel_cols.hip's launch sequences report through the same observable, in their own words
 void voxel_note_form(const char* text) {
     snprintf(t_vox_text, sizeof(t_vox_text), "%s", text);
 }

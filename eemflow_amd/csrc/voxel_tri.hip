@@ -106,7 +106,6 @@ __global__ __launch_bounds__(VT) void voxtri_bin_kernel(TriJobs jobs, int bins, 
     const TriJob& J = jobs.j[blockIdx.y];
     if ((int)blockIdx.x >= J.nblk) return;                         // a shorter event set
     const long n = J.n;
-    unsigned* __restrict__ run_start = J.run_start;
     __shared__ unsigned hist[VT];
     __shared__ unsigned lpos[VT];
     __shared__ unsigned sh[VT / 64];
@@ -145,26 +144,7 @@ __global__ __launch_bounds__(VT) void voxtri_bin_kernel(TriJobs jobs, int bins, 
             }
         }
     }
-    __syncthreads();
-    const unsigned start = block_exscan(hist[tid], sh);            // bands >= nb hold 0: thread nb gets the slab's fill
-    lpos[tid] = start;
-    if (tid <= pl.nb) run_start[(size_t)blockIdx.x * (pl.nb + 1) + tid] = start;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        if (band[k] != 0xffffffffu) {
-            unsigned* r = stage + 3u * (lpos[band[k]] + rank[k]);
-            r[0] = key[k];
-            r[1] = __float_as_uint(vl[k]);
-            r[2] = __float_as_uint(vr[k]);
-        }
-    }
-    __syncthreads();
-    // the sorted slab leaves as whole 16-byte pieces of consecutive threads
-    const unsigned words = 3u * lpos[pl.nb];
-    u32x4* slab = reinterpret_cast<u32x4*>(J.recs + (size_t)blockIdx.x * (VT * R) * 3);
-    const u32x4* st4 = reinterpret_cast<const u32x4*>(stage);
-    for (unsigned i = tid; i * 4 < words; i += VT) slab[i] = st4[i];   // (the last piece may carry up to three stale words: nobody reads them)
+    vox_slab_out<R>(key, band, rank, vl, vr, hist, lpos, sh, stage, J.run_start, J.recs, pl);
 }
 
 // ------------------------------------------------------------------------------------------------ direct form

@@ -126,6 +126,74 @@ def stream_chunks(dataset, model, n, dev, fb_check=None, with_volumes=False):
             yield (list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]) + tail
 
 
+def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, bidirectional=False, fb_check=None, iters=None):
+    """Flow along the consecutive windows [offsets[k], offsets[k+1]) of a resident recording (eemflow_amd.recording.EventRecording): a
+    generator of one dict per pair of neighbouring windows, in time order -
+        'k'         the pair's first window (the flow runs from window k to window k + 1)
+        'flow'      [1, 2, H, W], the last prediction of model.forward_stream
+        'flow_bw', 'mask_fw', 'mask_bw'   with bidirectional / fb_check (models whose forward_stream takes them: EEMFlow)
+        'FWL', 'RSAT'                     with fwl / rsat: 0-dim float64 device tensors, the flow warp loss / RSAT of window k's events
+                                          under the flow (iwe.fwl_many, tsimg.rsat_many on recording.tables, t_ref="end")
+    Per step `chunk` windows (default: the model's MAX_STREAM, or MAX_STREAM_BIDIR when bidirectional) are voxelized straight from the
+    recording's columns by one launch sequence (recording.voxelize_windows, num_bins = model.n_first_channels) and go through ONE
+    forward_stream call; the window the model carries joins the chunks, so every window is voxelized and encoded once.  The stream
+    is reset at the start and the model sized to the recording's sensor.  fb_check = (alpha1, alpha2[, 'all' | 'obj' | 'out']) implies
+    bidirectional; iters: E-RAFT's refinement steps per pair (forward_stream's own default when None).  The loop itself reads nothing back from the device (fwl_many / rsat_many read their windows' end times, one small
+    copy per chunk)."""
+    from .recording import _check_offsets, voxelize_windows
+    if fb_check is not None:
+        bidirectional = True
+    if bidirectional and not hasattr(model, "MAX_STREAM_BIDIR"):
+        raise ValueError(f"fb_check= needs a model whose forward_stream takes bidirectional=True (EEMFlow); {type(model).__name__} has none")
+    if not hasattr(model, "forward_stream"):
+        raise ValueError(f"run_recording needs a model with forward_stream (EEMFlow, EEMFlow_cdc, ERAFT); {type(model).__name__} has none")
+    offs = _check_offsets("run_recording", offsets, recording.n)
+    limit = model.MAX_STREAM_BIDIR if bidirectional else model.MAX_STREAM
+    chunk = limit if chunk is None else int(chunk)
+    if not 1 <= chunk <= limit:
+        raise ValueError(f"run_recording: chunk is 1..{limit} windows per forward_stream call" + (" with bidirectional=True" if bidirectional else "")
+                         + f", got {chunk}")
+    size = (recording.height, recording.width)
+    if tuple(int(v) for v in getattr(model, "image_size", None) or ()) != size:
+        model.change_imagesize(size)
+    model.reset_stream()
+    extra = dict(bidirectional=True, **({"fb_check": tuple(fb_check)} if fb_check is not None else {})) if bidirectional else {}
+    if iters is not None:
+        import inspect
+        if "iters" not in inspect.signature(model.forward_stream).parameters:
+            raise ValueError(f"iters= needs a model whose forward_stream takes the refinement steps per pair (ERAFT); {type(model).__name__} has none")
+        if int(iters) < 1:
+            raise ValueError(f"run_recording: iters is a positive number of refinement steps, got {iters}")
+        extra["iters"] = int(iters)
+    nwin = len(offs) - 1
+    k = 0                                                            # the next pair's first window
+    for w0 in range(0, nwin, chunk):
+        part = offs[w0:w0 + chunk + 1]
+        vols = voxelize_windows(recording, part, model.n_first_channels)
+        outs = model.forward_stream(vols, **extra)
+        if not outs:
+            continue                                                 # the first chunk held one window: it is carried
+        items = [{'k': k + i, 'flow': o[1][-1]} for i, o in enumerate(outs)]
+        if bidirectional:
+            for it, o in zip(items, outs):
+                it['flow_bw'] = o[2][-1]
+                if fb_check is not None:
+                    it['mask_fw'], it['mask_bw'] = o[3]
+        if fwl or rsat:
+            tables = recording.tables(offs[k:k + len(outs) + 1])     # the pairs' first windows
+            flows = [it['flow'][0] for it in items]
+            if fwl:
+                from .iwe import fwl_many                            # (the package's attribute `iwe` is the one-job function, not the module)
+                for it, v in zip(items, fwl_many(tables, flows)):
+                    it['FWL'] = v
+            if rsat:
+                from .tsimg import rsat_many
+                for it, v in zip(items, rsat_many(tables, flows)):
+                    it['RSAT'] = v
+        k += len(outs)
+        yield from items
+
+
 class TestRaftEvents:
     """Evaluation loop of test_mvsec.py:538-671 on a dataset object (HREMEventFlow-like: change_test_sequence, __len__,
     __getitem__ -> sample dict)."""

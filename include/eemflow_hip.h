@@ -535,6 +535,34 @@ int eemflow_pack_events_many(int nsets, const void* const* t, const void* const*
                              const int* codes, const int64_t* n_events, double scale_a, double scale_b, int relative,
                              double* const* out, void* stream);
 
+/* The consecutive windows of ONE device-resident recording, voxelized straight from its columns: t, x, y, p are the recording's four
+ * base columns on the device in the dtypes codes[0..3] (EEMFLOW_PACK_*, p already 2*p - 1, the recording in time order), window k
+ * is the elements [offsets[k], offsets[k+1]) of each (offsets: nwin + 1 HOST integers, ascending, offsets[0] >= 0, the columns at
+ * least offsets[nwin] elements long), nwin = 1..32.  Per event of window k, in registers:
+ *     tt = ((double)t * scale_a) * scale_b                 two separately rounded products, then - tt[offsets[k]] with `relative`:
+ *                                                          eemflow_pack_events_many's row of that slice, bit for bit
+ *     the two temporal votes of eemflow_voxelize with t0 = tt[first], dT = tt[last] - tt[first] (0 -> 1) of the WINDOW
+ * so grids[k] ((bins,H,W) fp32 on the device, any 4-byte alignment; + four floats with normalize = 2) is bitwise what
+ * eemflow_voxelize_many gives for the table that eemflow_pack_events_many makes of the window's slice: the same votes, the same fp64
+ * cell sums rounded once, the same moments.  No float64 table is written or read: 13 B of HBM traffic per HREM event in front of
+ * the records instead of 13 + 32 + 32.  A window may start at any element (an odd index of a 2-byte column too): the columns are
+ * read element by element, and only each column's BASE must be aligned to its element size.
+ * Empty windows (offsets[k] == offsets[k+1]) are allowed - the reference cannot be asked about one (it indexes events[-1]); here
+ * an empty window's grid is all +0.0 and, with normalize = 2, its record is {0, 1, 0, 0}.
+ * normalize: 0 raw, 1 normalised, 2 raw grid + record behind it (as eemflow_voxelize).  Grids beyond the LDS band layout (bins > 64,
+ * band_px * bins > 19 200 cells, more than 33.5 M events in a window) and EEM_VOX_DIRECT=1 run, inside this call, as
+ * eemflow_pack_events_many into a scratch table and the direct kernel, window by window (fp32 atomics: the values agree with the
+ * banded form within 2e-5, not bitwise).  eemflow_voxelize_last_form reports "j<nwin>:colbin_e<1|2|4|8>+band..." (the rest as for
+ * eemflow_voxelize) or "j<nwin>:pack+direct[+bin(<m>)][+moments+norm|+moments+stats]"
+ * (+bin(<m>): only the longest window was beyond the bands, and m shorter ones took them behind their tables).  codes, offsets and
+ * grids are HOST arrays, read before the call returns.  Stream-ordered, no host synchronisation; scratch from the library's arenas as for eemflow_voxelize_many; a bad
+ * argument is an error return before any launch.
+ * Replaces, for a recording cut into windows: per window a host slice, get_compressed_events and EventSequence.__init__
+ * (loader/loader_utils.py:26-37, :352-397) and EventSequenceToVoxelGrid_Pytorch.__call__ (:447-537). */
+int eemflow_voxelize_windows(int nwin, const void* t, const void* x, const void* y, const void* p, const int codes[4],
+                             const int64_t* offsets, double scale_a, double scale_b, int relative, int bins, int h, int w,
+                             int normalize, float* const* grids, void* stream);
+
 /* Augmentation of n (1..EEMFLOW_AUGMENT_MAX) training samples of one source size and one output size by ONE launch, written into the
  * batch tensors: vol_old[i], vol_new[i] ([C][H][W] fp32), flow[i] ([2][H][W]; fp64 with flow_f64 != 0, else fp32; a NULL entry, or
  * flow == NULL, is a sample without flow: HREM's mesh flow is returned un-augmented by the reference) and plans[i] are HOST arrays, read
