@@ -23,6 +23,8 @@
 // Inputs with an infinity give NaN here where the fp32 kernels give an infinity (inf - inf in the split): the output is non-finite at
 // exactly the positions where the fp32 kernel's is and unchanged elsewhere (contract, tests/test_gpu_parity.py::
 // test_bf16_piece_kernel_and_an_infinity_in_the_input); a guard would add two VALU per value to a split that runs once per USE here.
+// The contract for every kernel, and what it allows this one, is stated once in DESIGN 3 ("The non-finite contract");
+// tests/test_gpu_nonfinite_models.py holds these layers to it stage by stage.
 #include "common.h"
 
 namespace {

@@ -24,7 +24,7 @@ constexpr int ST_QPR = ST_COLS / 4;                      // 16-byte pieces per p
 
 __device__ __forceinline__ float st_act(float v, int act) {
     switch (act) {
-        case GACT_RELU: return v > 0.f ? v : 0.f;
+        case GACT_RELU: return !(v <= 0.f) ? v : 0.f;          // (not v > 0: a NaN stays a NaN, as torch.relu keeps it - DESIGN 3)
         case GACT_LEAKY: return v > 0.f ? v : 0.1f * v;
         case GACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case GACT_TANH: return tanhf(v);
@@ -108,8 +108,10 @@ __global__ __launch_bounds__(256) void stem7_kernel(GConvArgs a, const f32x4* __
                     const f32x4 av = wl[ks * 64 + lane];
                     const float* pb = patch + c * ST_PLANE + ky * ST_COLS + 4 * half + bbase;
                     float bv[4];
+                    // (the eighth tap's weight is zero, and so must its input be: 0 * NaN would reach one output column more than the
+                    // filter does - DESIGN 3.  half is a compile-time constant and the test a lane's own: four selects per 16 MFMAs)
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) bv[p] = pb[(p >> 1) * 2 * ST_COLS + (p & 1) * 32];
+                    for (int p = 0; p < 4; ++p) bv[p] = (half == 1 && kg == 3) ? 0.f : pb[(p >> 1) * 2 * ST_COLS + (p & 1) * 32];
 #pragma unroll
                     for (int p = 0; p < 4; ++p)
 #pragma unroll

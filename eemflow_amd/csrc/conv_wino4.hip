@@ -547,7 +547,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(EncConvArgs a) {
 #pragma unroll
                     for (int yy = 0; yy < 4; ++yy)
 #pragma unroll
-                        for (int x = 0; x < 4; ++x) o[yy][x] = fmaxf(o[yy][x] + rv[yy][x], 0.f);
+                        for (int x = 0; x < 4; ++x) { const float t = o[yy][x] + rv[yy][x]; o[yy][x] = !(t <= 0.f) ? t : 0.f; }
                 }
                 float ps = 0.f;
 #pragma unroll

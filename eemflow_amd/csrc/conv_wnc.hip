@@ -429,8 +429,8 @@ __global__ __launch_bounds__(C::WAVES * 64, C::TEAMS == 1 ? 2 : 1) void wnc_kern
                 if (tcur.res) {                              // (wave-uniform) residual block: relu(res + .); outside lanes read the zero page
                     const f32x2 r0 = *reinterpret_cast<const f32x2*>(in0 && okc ? tcur.res + po : a.zero_page);
                     const f32x2 r1 = *reinterpret_cast<const f32x2*>(in1 && okc ? tcur.res + po + a.w : a.zero_page);
-                    y00 = fmaxf(y00 + r0[0], 0.f); y01 = fmaxf(y01 + r0[1], 0.f);
-                    y10 = fmaxf(y10 + r1[0], 0.f); y11 = fmaxf(y11 + r1[1], 0.f);
+                    y00 += r0[0]; y01 += r0[1]; y10 += r1[0]; y11 += r1[1];         // (not fmaxf: a NaN stays a NaN - DESIGN 3)
+                    y00 = !(y00 <= 0.f) ? y00 : 0.f; y01 = !(y01 <= 0.f) ? y01 : 0.f; y10 = !(y10 <= 0.f) ? y10 : 0.f; y11 = !(y11 <= 0.f) ? y11 : 0.f;
                 }
                 // every lane stores (lanes outside the image or beyond cout into a scratch page): exactly NST stores per wave and tile
                 *reinterpret_cast<f32x2*>(in0 && okc ? p : sink) = f32x2{y00, y01};

@@ -76,8 +76,8 @@ __global__ __launch_bounds__(256) void instnorm_kernel(const float* __restrict__
     const float* r = res ? res + (size_t)blockIdx.x * hw : nullptr;
     for (int i = threadIdx.x; i < hw; i += 256) {
         float v = (p[i] - mean) * rstd;
-        if (relu_inner) v = v > 0.f ? v : 0.f;
-        if (r) { v += r[i]; v = v > 0.f ? v : 0.f; }
+        if (relu_inner) v = !(v <= 0.f) ? v : 0.f;
+        if (r) { v += r[i]; v = !(v <= 0.f) ? v : 0.f; }
         o[i] = v;
     }
 }
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(1024) void instnorm_reg_kernel(const float* __restr
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float t = (v[k][e] - mean) * rstd;
-            if (relu_inner) t = t > 0.f ? t : 0.f;
-            if (r) { t += rv[e]; t = t > 0.f ? t : 0.f; }
+            if (relu_inner) t = !(t <= 0.f) ? t : 0.f;
+            if (r) { t += rv[e]; t = !(t <= 0.f) ? t : 0.f; }
             w[e] = t;
         }
         o[i] = w;
@@ -195,8 +195,8 @@ __global__ __launch_bounds__(1024) void instnorm_apply_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float t = (v[e] - mean) * rstd;
-            if (relu_inner) t = t > 0.f ? t : 0.f;
-            if (r) { t += rv[e]; t = t > 0.f ? t : 0.f; }
+            if (relu_inner) t = !(t <= 0.f) ? t : 0.f;
+            if (r) { t += rv[e]; t = !(t <= 0.f) ? t : 0.f; }
             w[e] = t;
         }
         o[i] = w;

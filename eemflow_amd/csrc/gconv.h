@@ -38,7 +38,10 @@ struct GConvArgs {
     int n, hin, win, hout, wout, cout;
     int kh, kw, stride, pad_h, pad_w;
     int tstride;           // 0/1: ordinary conv.  2: transposed conv (data gradient of a stride-2 conv): the
-                           // source position (o - pad + tap) must be a multiple of tstride and is divided by it
+                           // source position (o - pad + tap) must be a multiple of tstride and is divided by it.
+                           // A tap that is not read - the padding, the other parity classes of a transposed conv, a surplus k slot -
+                           // enters the MFMA as B = 0: a non-finite WEIGHT is a NaN at every pixel of its output channel, also where
+                           // torch skips the tap (deliberate; DESIGN 3: more NaN, never less).  Non-finite inputs spread as in torch.
     int act, epi;
     const float* e0; int e0_ctotal, e0_coff;
     const float* e1; int e1_ctotal, e1_coff;

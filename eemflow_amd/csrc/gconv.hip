@@ -14,7 +14,7 @@ namespace {
 
 __device__ __forceinline__ float g_act(float v, int act) {
     switch (act) {
-        case GACT_RELU: return v > 0.f ? v : 0.f;
+        case GACT_RELU: return !(v <= 0.f) ? v : 0.f;          // (not v > 0: a NaN stays a NaN, as torch.relu keeps it - DESIGN 3)
         case GACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case GACT_TANH: return tanhf(v);
         case GACT_LEAKY: return v > 0.f ? v : 0.1f * v;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(SPLITK ? SPLITK * 64 : 256) void gconv_kernel(GConv
             v = (1.f - z) * hh + z * v;
         } else if (a.epi == GEPI_ADD_RELU) {
             v += a.e0[((size_t)n * a.e0_ctotal + a.e0_coff + co) * hwo + p];
-            v = v > 0.f ? v : 0.f;
+            v = !(v <= 0.f) ? v : 0.f;
         } else if (a.epi == GEPI_ADD) {
             v += a.e0[((size_t)n * a.e0_ctotal + a.e0_coff + co) * hwo + p];
         }
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(FEW_WAVES * 64, (FEW_WAVES == 8 ? 8 : 4)) void fewo
     for (int k = 0; k < FEW_WAVES; ++k) r += part[k][co][lane];
     if (a.scale) r *= a.scale[co];
     if (a.shift) r += a.shift[co];
-    if (a.act == GACT_RELU) r = r > 0.f ? r : 0.f;
+    if (a.act == GACT_RELU) r = !(r <= 0.f) ? r : 0.f;
     else if (a.act == GACT_LEAKY) r = r > 0.f ? r : 0.1f * r;
     else if (a.act == GACT_SIGMOID) r = 1.f / (1.f + expf(-r));
     else if (a.act == GACT_TANH) r = tanhf(r);
@@ -495,7 +495,9 @@ __global__ __launch_bounds__(1024) void fewout_wide_kernel(GConvArgs a, int cpl)
     float v[CPL][9];
 #pragma unroll
     for (int q = 0; q < CPL; ++q) {
-        const float* plane = in + (size_t)min(c0 + q, sg.c - 1) * hw;     // (requests past the layer's last channel meet zero weights)
+        // (requests past the layer's last channel repeat it and meet zero weights; their values are dropped below, or an infinity
+        // of the last channel would come back as 0 * inf = NaN - DESIGN 3)
+        const float* plane = in + (size_t)min(c0 + q, sg.c - 1) * hw;
 #pragma unroll
         for (int t = 0; t < 9; ++t) v[q][t] = plane[off[t]];
     }
@@ -510,9 +512,10 @@ __global__ __launch_bounds__(1024) void fewout_wide_kernel(GConvArgs a, int cpl)
 #pragma unroll
     for (int q = 0; q < CPL; ++q) {
         if (q >= cpl) break;                                       // (uniform: channels c0 + cpl .. are the next group's)
+        const bool real = c0 + q < sg.c;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const float vv = keep[t] ? v[q][t] : 0.f;
+            const float vv = keep[t] && real ? v[q][t] : 0.f;
 #pragma unroll
             for (int k = 0; k < NP; ++k) acc[k] = __builtin_elementwise_fma(f32x2{vv, vv}, wc[(q * 9 + t) * (WS / 2) + k], acc[k]);
         }
@@ -529,7 +532,7 @@ __global__ __launch_bounds__(1024) void fewout_wide_kernel(GConvArgs a, int cpl)
     for (int k = 0; k < 32; ++k) r += part[k][co][tid & 31];
     if (a.scale) r *= a.scale[co];
     if (a.shift) r += a.shift[co];
-    if (a.act == GACT_RELU) r = r > 0.f ? r : 0.f;
+    if (a.act == GACT_RELU) r = !(r <= 0.f) ? r : 0.f;
     else if (a.act == GACT_LEAKY) r = r > 0.f ? r : 0.1f * r;
     else if (a.act == GACT_SIGMOID) r = 1.f / (1.f + expf(-r));
     else if (a.act == GACT_TANH) r = tanhf(r);

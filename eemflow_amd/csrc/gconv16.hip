@@ -28,7 +28,7 @@ __device__ unsigned long long g_g16_stamps[1024 * 4 * 8];
 
 __device__ __forceinline__ float g16_act(float v, int act) {
     switch (act) {
-        case GACT_RELU: return v > 0.f ? v : 0.f;
+        case GACT_RELU: return !(v <= 0.f) ? v : 0.f;          // (not v > 0: a NaN stays a NaN, as torch.relu keeps it - DESIGN 3)
         case GACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case GACT_TANH: return tanhf(v);
         case GACT_LEAKY: return v > 0.f ? v : 0.1f * v;
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(256 * KG, (KG > 1 || S > 1 || (THT != 2 && THT != 4
                     v = (1.f - e1v[t][r]) * e0v[t][r] + e1v[t][r] * v;
                 } else if (a.epi == GEPI_ADD_RELU) {
                     v += e0v[t][r];
-                    v = v > 0.f ? v : 0.f;
+                    v = !(v <= 0.f) ? v : 0.f;
                 } else if (a.epi == GEPI_ADD) {
                     v += e0v[t][r];
                 }

@@ -8,6 +8,8 @@
 // an infinity is inf - inf = NaN, so an infinite input leaves this kernel as NaN where gconv16.hip leaves an infinity - the output is
 // non-finite at exactly the positions where the fp32 kernel's is, every other value agrees, nothing non-finite ever becomes a number
 // (the training step's inf / NaN test sees it either way).  A guard would cost two VALU per value of the split for no caller of the path.
+// Under a ReLU epilogue an infinite operand is therefore a NaN also where fp32 arithmetic gives relu(-inf) = 0.  The contract for every
+// kernel is stated once in DESIGN 3 ("The non-finite contract"); tests/test_gpu_nonfinite_ops.py holds every form of this file to it.
 //
 // Why here: these are direct convolutions with K = 256 .. 3 456 and no cheaper algorithm (1x5, 5x1, 1x1; the 3x3 ones sit beside them in
 // the same loops); gconv16.hip runs them at 0.4-0.55 of the fp32 MFMA's 155 TFLOP/s.  tools/micro/mfma_clock.hip: six
@@ -50,7 +52,7 @@ struct GBCfg {
 
 __device__ __forceinline__ float gb_act(float v, int act) {
     switch (act) {
-        case GACT_RELU: return v > 0.f ? v : 0.f;
+        case GACT_RELU: return !(v <= 0.f) ? v : 0.f;          // (not v > 0: a NaN stays a NaN, as torch.relu keeps it - DESIGN 3)
         case GACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case GACT_TANH: return tanhf(v);
         case GACT_LEAKY: return v > 0.f ? v : 0.1f * v;
@@ -327,7 +329,7 @@ __global__ __launch_bounds__(768, 3) void gconvb_kernel(GConvArgs ka, const u32x
                 t = gb_act(t, (dbg & 16) ? GACT_NONE : a_act);
                 if (a_epi == GEPI_MUL) t *= e0v[p][q][j];
                 else if (a_epi == GEPI_GRU) t = (1.f - e1v[p][q][j]) * e0v[p][q][j] + e1v[p][q][j] * t;
-                else if (a_epi == GEPI_ADD_RELU) { t += e0v[p][q][j]; t = t > 0.f ? t : 0.f; }
+                else if (a_epi == GEPI_ADD_RELU) { t += e0v[p][q][j]; t = !(t <= 0.f) ? t : 0.f; }
                 else if (a_epi == GEPI_ADD) t += e0v[p][q][j];
                 else if (a_epi == GEPI_ZR && co[q] >= a_split) t *= e0v[p][q][j];
                 v[j] = t * a_out_scale;

@@ -31,7 +31,9 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
     if (i >= n) return;
     const float v = y[i];
     float d;
-    if (kind == GACT_RELU) d = v > 0.f ? 1.f : 0.f;
+    // (ReLU: the gate is a factor, not a select - a NaN or an infinity in dy under a closed gate leaves as 0 * NaN = NaN where torch's
+    // threshold_backward writes 0.  Deliberate: more NaN, never less - DESIGN 3)
+    if (kind == GACT_RELU) d = !(v <= 0.f) ? 1.f : 0.f;               // (a NaN output keeps its gate open, as torch.relu's backward does)
     else if (kind == GACT_SIGMOID) d = v * (1.f - v);
     else if (kind == GACT_TANH) d = 1.f - v * v;
     else if (kind == GACT_LEAKY) d = v > 0.f ? 1.f : 0.1f;
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void binary_kernel(const float* __restrict__ a
     if (kind == 4) r = alpha * x;
     else {
         const float y = b[i];
-        r = kind == 0 ? x + y : kind == 1 ? x - y : kind == 2 ? x * y : fmaxf(x + y, 0.f);
+        r = kind == 0 ? x + y : kind == 1 ? x - y : kind == 2 ? x * y : (!(x + y <= 0.f) ? x + y : 0.f);     // (not fmaxf: a NaN sum stays a NaN - DESIGN 3)
     }
     out[i] = r;
 }
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const float* __restrict__ 
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float v = x[i];
-    out[i] = kind == GACT_RELU ? fmaxf(v, 0.f) : kind == GACT_SIGMOID ? 1.f / (1.f + expf(-v)) : kind == GACT_TANH ? tanhf(v)
+    out[i] = kind == GACT_RELU ? (!(v <= 0.f) ? v : 0.f) : kind == GACT_SIGMOID ? 1.f / (1.f + expf(-v)) : kind == GACT_TANH ? tanhf(v)
            : kind == GACT_LEAKY ? (v > 0.f ? v : 0.1f * v) : v;
 }
 
@@ -207,7 +209,9 @@ __global__ __launch_bounds__(256) void resize_ac_bwd_gather_kernel(const float* 
         ac_taps(Y, X, h, w, oh, ow, y0, y1, x0, x1, ly, lx);
         const float wy = (y0 == y ? 1.f - ly : 0.f) + (y1 == y ? ly : 0.f);     // y0 == y1 == y on the last row: (1 - ly) + ly
         const float wx = (x0 == x ? 1.f - lx : 0.f) + (x1 == x ? lx : 0.f);
-        if (wy != 0.f && wx != 0.f) acc += g[(long)Y * ow + X] * wy * wx;
+        // every output whose taps touch this pixel adds its term, a weight of exactly 0 included: 0 * NaN is a NaN in the scatter form
+        // and in torch's adjoint, and must be one here; for finite gradients the term is a zero
+        if ((y0 == y || y1 == y) && (x0 == x || x1 == x)) acc += g[(long)Y * ow + X] * wy * wx;
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
@@ -228,6 +232,8 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* sh) {
 
 // InstanceNorm2d(affine=False, eps) [+ ReLU] backward, one block per (n, c) plane; x is the layer input (the statistics are
 // recomputed), y the layer output (ReLU gate):  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * [y > 0]
+// (the gates of this file close on y <= 0, not on !(y > 0): a NaN output passes its dy on, as torch's threshold_backward does - with
+// the other test a batch norm's bias gradient stayed finite over a channel of NaN outputs)
 __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            const float* __restrict__ dy, float* __restrict__ dx, int hw, int relu, float eps) {
     __shared__ double sh[32];
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float* __restr
     double sg = 0.0, sgx = 0.0;
     for (int i = threadIdx.x; i < hw; i += blockDim.x) {
         float g = dy[base + i];
-        if (relu && !(y[base + i] > 0.f)) g = 0.f;
+        if (relu && y[base + i] <= 0.f) g = 0.f;
         const float xh = (x[base + i] - meanf) * rstd;
         sg += g; sgx += (double)g * xh;
     }
@@ -250,7 +256,7 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float* __restr
     const float mg = (float)(sg / hw), mgx = (float)(sgx / hw);
     for (int i = threadIdx.x; i < hw; i += blockDim.x) {
         float g = dy[base + i];
-        if (relu && !(y[base + i] > 0.f)) g = 0.f;
+        if (relu && y[base + i] <= 0.f) g = 0.f;
         const float xh = (x[base + i] - meanf) * rstd;
         dx[base + i] = rstd * (g - mg - xh * mgx);
     }
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(1024) void bn_train_fwd_kernel(const float* __restr
         const size_t o = ((size_t)img * c + ch) * hw;
         for (int i = threadIdx.x; i < hw; i += blockDim.x) {
             float v = (x[o + i] - meanf) * rstd * ww + bb;
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = !(v <= 0.f) ? v : 0.f;
             y[o + i] = v;
         }
     }
@@ -309,7 +315,7 @@ __global__ __launch_bounds__(1024) void bn_train_bwd_kernel(const float* __restr
         const size_t o = ((size_t)img * c + ch) * hw;
         for (int i = threadIdx.x; i < hw; i += blockDim.x) {
             float g = dy[o + i];
-            if (relu && !(y[o + i] > 0.f)) g = 0.f;
+            if (relu && y[o + i] <= 0.f) g = 0.f;
             sg += g; sgx += (double)g * ((x[o + i] - meanf) * rstd);
         }
     }
@@ -320,7 +326,7 @@ __global__ __launch_bounds__(1024) void bn_train_bwd_kernel(const float* __restr
         const size_t o = ((size_t)img * c + ch) * hw;
         for (int i = threadIdx.x; i < hw; i += blockDim.x) {
             float g = dy[o + i];
-            if (relu && !(y[o + i] > 0.f)) g = 0.f;
+            if (relu && y[o + i] <= 0.f) g = 0.f;
             dx[o + i] = k * (g - mg - (x[o + i] - meanf) * rstd * mgx);
         }
     }
@@ -338,7 +344,7 @@ __global__ __launch_bounds__(1024) void bn_eval_fwd_kernel(const float* __restri
         const size_t o = ((size_t)img * c + ch) * hw;
         for (int i = threadIdx.x; i < hw; i += blockDim.x) {
             const float v = (x[o + i] - mean) * k + bias;
-            y[o + i] = relu ? fmaxf(v, 0.f) : v;
+            y[o + i] = relu && (v <= 0.f) ? 0.f : v;
         }
     }
 }
@@ -355,7 +361,7 @@ __global__ __launch_bounds__(1024) void bn_eval_bwd_kernel(const float* __restri
         const size_t o = ((size_t)img * c + ch) * hw;
         for (int i = threadIdx.x; i < hw; i += blockDim.x) {
             float g = dy[o + i];
-            if (relu && !(y[o + i] > 0.f)) g = 0.f;
+            if (relu && y[o + i] <= 0.f) g = 0.f;
             sg += g; sgx += (double)g * ((x[o + i] - mean) * rstd);
             dx[o + i] = g * k;
         }

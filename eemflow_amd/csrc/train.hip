@@ -25,6 +25,11 @@ __global__ __launch_bounds__(256) void repack_kernel(const float* __restrict__ f
 
 // ---- sequence_loss for one prediction (train_mvsec.py:201-227): loss = mean(valid * |flow - gt|) over B*2*H*W,
 // valid = (valid >= 0.5) & (|gt| < 400); dflow = sign(flow - gt) * valid / (B*2*H*W); epe statistics of :218-226.
+// Non-finite values: an invalid pixel is SELECTED out, not multiplied by 0 - deliberately unlike the reference's
+// valid * |flow - gt|, whose 0 * inf is a NaN: MVSEC's ground truth holds an infinity at every pixel without a measurement
+// (valid = ~isinf(u) & ~isinf(v) & ...), the loaders hand it on as it is, and |gt| < 400 fails for an infinity and for a NaN, so a
+// non-finite ground truth makes its pixel invalid and never reaches the loss.  A non-finite FLOW at a valid pixel does: the loss is
+// then non-finite; its gradient there is 0 as in torch (sign(NaN) = 0), and the NaN that made the flow is in the weight gradients.
 __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ flow, const float* __restrict__ gt,
                                                    const float* __restrict__ valid, float* __restrict__ dflow, int batch, int hw,
                                                    float weight, double* __restrict__ stats) {

@@ -206,7 +206,11 @@ def test_mask_head_beside_the_next_iteration_equals_the_serial_order(monkeypatch
     (EEM_ERAFT_NO_LAG=1, read per forward): every prediction, the low-resolution flow and the kept stages of the first iteration are
     the same (the hidden state is read by the lagging launches while the next iteration reads it, and overwritten only after they have
     finished); with final_only; on a map of less than 256 cells (the generic kernel and a separate sum); twice in a row on one
-    context (the events are reused)."""
+    context (the events are reused).
+    A map of less than 16 cells a side (64x96: 8 x 12) has a coarsest pyramid level one cell wide, where the reference's bilinear_sampler
+    divides by W - 1 = 0 (see maxerr): the lookup's channels of that level are NaN, and since every ReLU keeps a NaN as torch.relu does
+    (DESIGN 3), so are the predictions - the reference's own result at that size.  The two orders must then be non-finite at the same
+    places, and equal wherever they are finite."""
     net, _ = make_net(91)
     net.final_only = final
     net.change_imagesize((h, w))
@@ -217,9 +221,16 @@ def test_mask_head_beside_the_next_iteration_equals_the_serial_order(monkeypatch
         with torch.no_grad():
             preds = torch.stack(net(e1, e2, iters=iters)[1]).clone()
             outs[lag] = (preds, net.stage("flow_low").clone(), net.stage("mask1").clone(), net.stage("delta1").clone(), net.stage("net1").clone())
+    degenerate = h // 8 < 16 or w // 8 < 16
     for x, y in zip(outs["0"], outs["1"]):
-        assert maxerr(x, y) < 1e-5 * max(1.0, float(y.abs().max()))
-    assert float(outs["1"][0].abs().max()) > 1e-3
+        assert torch.equal(torch.isfinite(x), torch.isfinite(y))
+        assert degenerate or bool(torch.isfinite(y).all())
+        if bool(torch.isfinite(y).any()):
+            assert maxerr(x, y) < 1e-5 * max(1.0, float(y[torch.isfinite(y)].abs().max()))
+    if degenerate:
+        assert not bool(torch.isfinite(outs["1"][0]).any())          # (the NaN of the one-cell level reaches every prediction)
+    else:
+        assert float(outs["1"][0].abs().max()) > 1e-3
 
 
 @pytest.mark.parametrize("b,h,w,iters", [(1, 480, 640, 2), (4, 480, 640, 1), (3, 136, 200, 2), (1, 128, 160, 2)])

@@ -699,14 +699,17 @@ def test_trainer_self_supervised_on_the_timestamp_term_alone():
 
 def eraft_step(h, w, term):
     """One forward and backward of E-RAFT (two iterations, batch 2) under `term(prediction, batch)`: (loss, dL/d prediction, the
-    names of the parameters whose gradient is not finite, the largest finite gradient entry)."""
+    names of the parameters whose gradient is not finite, the largest finite gradient entry).  term=None: the predictions alone."""
     from eemflow_amd.eraft import ERAFT
     torch.manual_seed(5)
     net = ERAFT("", n_first_channels=5).to(DEV).train()
     net.change_imagesize((h, w))
     b = synthetic_batch(120, 2, h, w, with_flow=False)
     preds = net(b["event_volume_old"], b["event_volume_new"], iters=2)[1]
-    assert tuple(preds[-1].shape) == (2, 2, h, w) and preds[-1].requires_grad and bool(torch.isfinite(preds[-1]).all())
+    assert tuple(preds[-1].shape) == (2, 2, h, w) and preds[-1].requires_grad
+    if term is None:
+        return preds
+    assert bool(torch.isfinite(preds[-1]).all())
     loss = term(preds[-1], b)
     (g,) = torch.autograd.grad(loss, preds[-1], retain_graph=True)
     loss.backward()
@@ -718,19 +721,18 @@ def eraft_step(h, w, term):
 
 
 def test_timestamp_loss_through_eraft():
-    """One step through E-RAFT with two iterations, batch 2, at 64 x 64 and at the size E-RAFT's training tests use (128 x 160).
+    """One step through E-RAFT with two iterations, batch 2, at the size E-RAFT's training tests use (128 x 160): a finite loss, a finite
+    non-zero gradient into the prediction, finite gradients in every parameter.
     At 64 x 64 the coarsest level of the correlation pyramid is 1 x 1, where the reference's lookup divides by W - 1 = 0
-    (bilinear_sampler, as this library restates it): its 81 features are not finite under ANY loss, the ReLU behind convc1 hides them
-    in the forward, and convc1.weight's gradient carries them.  So at that size the term is held to what a plain loss reaches - a
-    finite loss, a finite non-zero gradient into the prediction, finite gradients everywhere the control has them - and at 128 x 160
-    to finite gradients in every parameter."""
+    (bilinear_sampler, as this library restates it): its 81 features are not finite under ANY input, and since every ReLU keeps a NaN
+    as torch.relu does (no kernel turns a NaN into a number) neither is any prediction - the reference's own result at that
+    size.  (The ReLU behind convc1 used to map NaN to 0, which hid them in the forward and switched the correlation branch off; this
+    test then held the term to what a plain loss reached there.)  So 64 x 64 is held to that: both predictions are NaN throughout."""
     def term(pred, b):
         return hip_train.timestamp_loss(pred, b["events"], b["events_map"]).float()
-    loss, g, bad, big = eraft_step(64, 64, term)
-    _, _, control_bad, _ = eraft_step(64, 64, lambda pred, b: pred.abs().mean())
-    print("E-RAFT 64x64: loss", loss, "max|dL/dpred|", float(g.abs().max()), "non-finite", bad, "under a plain loss", control_bad)
-    assert math.isfinite(loss) and loss > 0 and bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0 and big > 0
-    assert bad == control_bad and set(bad) <= {"update_block.encoder.convc1.weight"}
+    preds = eraft_step(64, 64, None)
+    print("E-RAFT 64x64: finite values per prediction", [int(torch.isfinite(p).sum()) for p in preds])
+    assert len(preds) == 2 and not any(bool(torch.isfinite(p).any()) for p in preds)
     loss, g, bad, big = eraft_step(128, 160, term)
     print("E-RAFT 128x160: loss", loss, "max|dL/dpred|", float(g.abs().max()), "non-finite", bad)
     assert math.isfinite(loss) and loss > 0 and bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0 and big > 0
