@@ -14,6 +14,7 @@ from .dsec import VoxelGrid, flow_16bit_to_float, flow_float_to_16bit, voxel_gri
 from .eemflow import EEMFlow            # noqa: F401
 from .events import pack_events_many, read_event_columns   # noqa: F401
 from .recording import EventRecording, voxelize_windows as voxelize_recording_windows   # noqa: F401
+from .mvsec_raw import MvsecGroundTruth, MvsecRaw   # noqa: F401
 from .iwe import contrast_many, fwl, fwl_loss, fwl_many, iwe, iwe_many, warp_events   # noqa: F401
 from .tsimg import avg_timestamps, avg_timestamps_many, rsat, rsat_many, timestamp_loss, timestamp_loss_many   # noqa: F401
 from .metrics import fb_check          # noqa: F401

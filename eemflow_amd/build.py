@@ -15,12 +15,13 @@ CSRC = os.path.join(PKG, "csrc")
 # libeemflow_hip_<tag>.so - which tools load through EEM_LIB_PATH
 TAG = os.environ.get("EEM_BUILD_TAG", "")
 LIB = os.path.join(PKG, f"libeemflow_hip_{TAG}.so" if TAG else "libeemflow_hip.so")
-SOURCES = ["api.hip", "conv_enc.hip", "conv_enc1.hip", "conv_enc2.hip", "conv_s2.hip", "conv_s2r.hip", "conv_bx3.hip", "conv_wino.hip", "conv_wino32.hip", "conv_wino4.hip", "conv_enc12.hip", "conv_wnc.hip", "tail.hip", "tail_fused.hip", "voxel.hip", "voxel_tri.hip", "voxel_cols.hip", "event_pack.hip", "metrics.hip", "fb_check.hip", "viz.hip", "iwe.hip", "iwe_grad.hip", "tsimg.hip", "smooth.hip", "photo.hip", "ssim.hip", "augment.hip", "gconv.hip", "gconv16.hip", "gconvb.hip", "conv_stem7.hip", "eraft_kernels.hip",
+SOURCES = ["api.hip", "conv_enc.hip", "conv_enc1.hip", "conv_enc2.hip", "conv_s2.hip", "conv_s2r.hip", "conv_bx3.hip", "conv_wino.hip", "conv_wino32.hip", "conv_wino4.hip", "conv_enc12.hip", "conv_wnc.hip", "tail.hip", "tail_fused.hip", "voxel.hip", "voxel_tri.hip", "voxel_cols.hip", "gt_prop.hip", "event_pack.hip", "metrics.hip", "fb_check.hip", "viz.hip", "iwe.hip", "iwe_grad.hip", "tsimg.hip", "smooth.hip", "photo.hip", "ssim.hip", "augment.hip", "gconv.hip", "gconv16.hip", "gconvb.hip", "conv_stem7.hip", "eraft_kernels.hip",
            "eraft_warm.hip", "eraft_api.hip", "train.hip", "wgrad_enc.hip", "wgrad_ring.hip", "wgrad_tail.hip", "dgrad_s2.hip", "train_api.hip", "workspace.hip", "schedule.hip", "plus_kernels.hip", "plus_api.hip", "bwd_ops.hip", "ops.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]   # hidden: only include/eemflow_hip.h's entry points are dynamic symbols
 EXTRA = {"voxel.hip": ["-ffp-contract=off"],
          "voxel_tri.hip": ["-ffp-contract=off"],       # the vote weights are unfused fp32 products, as tests/dsec_reference.py restates them
          "voxel_cols.hip": ["-ffp-contract=off"],      # voxel.hip's votes on event_pack.hip's timestamps, both bit for bit
+         "gt_prop.hip": ["-ffp-contract=off"],         # x + fu * scale is NumPy's separately rounded float64 product and sum, bit for bit
          "conv_wino.hip": ["-fno-slp-vectorize"], "conv_wino32.hip": ["-fno-slp-vectorize"], "conv_wino4.hip": ["-fno-slp-vectorize"], "conv_enc12.hip": ["-fno-slp-vectorize"], "conv_wnc.hip": ["-fno-slp-vectorize"],     # packed f32 VALU beside MFMAs is slower than scalar (guide: anti-lever)      # bit-exact f64 time scaling
          "iwe.hip": ["-ffp-contract=off"],             # the warp and the vote weights are unfused fp64, as the tests restate them
          "iwe_grad.hip": ["-ffp-contract=off"],        # recomputes iwe.hip's warp (iwe_shared.h) and must find the same cells

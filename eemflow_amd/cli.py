@@ -3,6 +3,7 @@
     python -m eemflow_amd.cli train [flags]      # train_EEMFlow_HREM.py: HREM meshflow training, checkpoint per epoch
     python -m eemflow_amd.cli test  [flags]      # test_EEMFlow_HREM.py: evaluation over every sequence of the HREM test split
     python -m eemflow_amd.cli run   [flags]      # not in the reference: the flows along ONE recording (an events npz cut into windows)
+    python -m eemflow_amd.cli mvsec [flags]      # not in the reference: one raw MVSEC sequence scored against ground truth propagated on the GPU
 
 Same flags and defaults as the reference scripts (`--lr --wd --train_iters --val_iters --batch_size --input_type --model_name
 --start-epoch --num_workers --test_only --test_sequence ...`), the `lr{lr}_we{wd}` run folder, `config.json` / `train.log` /
@@ -174,6 +175,25 @@ def build_parser():
     r.add_argument('--fb_check', nargs=2, type=float, default=None, metavar=('A1', 'A2'),
                    help='EEMFlow: run the stream bidirectionally and add the forward-backward consistent share of every pair to its line '
                         '(threshold A1 * (|fw| + |bw|) + A2); with --out the backward flows go to DIR/%%06d_bw.flo')
+    m = sub.add_parser('mvsec', help='score one raw MVSEC sequence (not in the reference, which needs the files of loader/MVSEC_encoder.py): events, '
+                                     'grey-frame timestamps and the ground-truth stack go to the GPU once; windows of --dt grey frames are voxelized, '
+                                     'run through forward_stream and scored against ground truth propagated on the GPU')
+    m.add_argument('--data', required=True, help='npz with the arrays events (N,4: x, y, t seconds, p), image_raw_ts, image_raw_event_inds')
+    m.add_argument('--gt', required=True, help='npz with the arrays flow_dist (T,2,H,W) and flow_dist_ts (T,)')
+    m.add_argument('--checkpoint', required=True, help='checkpoint file of the model')
+    m.add_argument('--model_name', '-model', default='EEMFlow', type=str)
+    m.add_argument('--config', default=None, help='JSON with the layout of config/a_meshflow.json (default: built-in copy of its used fields)')
+    m.add_argument('--device', default='cuda:0')
+    m.add_argument('--first', default=None, type=int, metavar='I', help='first pair: grey frame I (default: the first frame the ground truth covers)')
+    m.add_argument('--last', default=None, type=int, metavar='J', help='last pair starts at grey frame <= J (default: the last one the ground truth and the frames cover)')
+    m.add_argument('--dt', default=1, type=int, metavar='N', help='grey frames per window (consecutive windows; 1 = MvsecEventFlow\'s samples)')
+    m.add_argument('--eval_type', default='dense', choices=('dense', 'sparse'), help='sparse: only pixels of the first window that hold an event')
+    m.add_argument('--is_car', action='store_true', help='outdoor sequences: rows from 190 on are not scored')
+    m.add_argument('--crop', nargs=2, type=int, default=None, metavar=('H', 'W'), help='centre crop of volumes, ground truth and mask (the dataset\'s validation branch: 256 256)')
+    m.add_argument('--height', default=260, type=int, help='sensor rows')
+    m.add_argument('--width', default=346, type=int, help='sensor columns')
+    m.add_argument('--stream', default=0, type=int, metavar='N', help='windows per forward_stream call (default: as many as the model takes)')
+    m.add_argument('--out', default=None, metavar='DIR', help='write the flow of pair k as DIR/%%06d.flo and its ground truth as DIR/%%06d_gt.flo')
     return p
 
 
@@ -459,9 +479,100 @@ def run(args):
             'meanFWL': mean['FWL'] if args.fwl else None, 'meanRSAT': mean['RSAT'] if args.rsat else None}
 
 
+def mvsec_pair_range(image_raw_ts, n_frames, gt_ts, first, last, dt):
+    """The pairs --first / --last select, defaults filled in: a pair starting at grey frame i needs the frames i .. i + 2*dt (two windows)
+    and ground truth over [ts[i], ts[i + dt]].  Host only."""
+    import numpy as np
+    from .mvsec_raw import plan_window
+
+    def covered(i):
+        try:
+            plan_window(gt_ts, image_raw_ts[i], image_raw_ts[i + dt])
+            return True
+        except ValueError:
+            return False
+    top = n_frames - 1 - 2 * dt                                      # the last frame a pair can start at
+    if top < 0:
+        raise SystemExit(f"mvsec: {n_frames} grey frames give no pair of windows at --dt {dt}")
+    if first is None:
+        first = int(np.searchsorted(image_raw_ts, gt_ts[0], side='left'))
+    if last is None:
+        last = top
+        while last >= first and not covered(last):
+            last -= 1
+    if first < 0 or last < first or last > top:
+        raise SystemExit(f"--first {first} --last {last}: pairs start at grey frames 0..{top} at --dt {dt}, first <= last")
+    for i in (first, first + (last - first) // dt * dt):
+        if not covered(i):
+            raise SystemExit(f"mvsec: the ground truth ({gt_ts[0]:.6f} .. {gt_ts[-1]:.6f} s) does not cover the pair at grey frame {i} "
+                             f"({image_raw_ts[i]:.6f} .. {image_raw_ts[i + dt]:.6f} s)")
+    return first, last
+
+
+def mvsec(args):
+    """`cli mvsec`: returns {'pairs', 'events', 'meanAEE', 'mean1px', 'mean3px', 'frames_per_s'}."""
+    import time
+    if args.dt < 1:
+        raise SystemExit("--dt N: N >= 1 grey frames per window")
+    if args.height < 1 or args.width < 1:
+        raise SystemExit("--height H --width W: the sensor size, both >= 1")
+    if args.crop is not None and not (1 <= args.crop[0] <= args.height and 1 <= args.crop[1] <= args.width):
+        raise SystemExit(f"--crop {args.crop[0]} {args.crop[1]}: the crop must fit the {args.height} x {args.width} sensor")
+    if args.stream < 0 or args.stream == 1:
+        raise SystemExit("--stream N: N >= 2 windows per forward_stream call (0: as many as the model takes)")
+    if (args.first is not None and args.first < 0) or (args.first is not None and args.last is not None and args.last < args.first):
+        raise SystemExit("--first I --last J: 0 <= I <= J")
+    for flag, path in (('--data', args.data), ('--gt', args.gt)):
+        if not os.path.isfile(path):
+            raise SystemExit(f"{flag} {path}: no such file")
+    from . import harness
+    from .hrem import write_flo
+    from .metrics import flow_error_from_sums
+    from .mvsec_raw import MvsecRaw
+    config = load_config(args.config)
+    model = build_model(args.model_name, config, training=False)
+    harness.load_checkpoint(args.checkpoint, model)
+    dev = torch.device(args.device)
+    torch.cuda.set_device(dev)
+    model = model.to(dev).eval()
+    if args.stream > model.MAX_STREAM:
+        raise SystemExit(f"--stream {args.stream}: {args.model_name} takes at most {model.MAX_STREAM} windows per call")
+    raw = MvsecRaw.from_npz(args.data, args.gt, height=args.height, width=args.width, device=dev)
+    first, last = mvsec_pair_range(raw.image_raw_ts, raw.image_raw_ts.shape[0], raw.gt.ts, args.first, args.last, args.dt)
+    offsets, t_edges = raw.frame_windows(first, last, args.dt)
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+    acc = {'aee': 0.0, 'p1': 0.0, 'p3': 0.0}
+    pairs = 0
+    torch.cuda.synchronize(dev)
+    start = time.perf_counter()
+    with torch.no_grad():
+        for item in harness.run_recording(model, raw.recording, offsets, chunk=args.stream or None, gt=raw.gt, t_edges=t_edges, crop=args.crop,
+                                          eval_type=args.eval_type, is_car=args.is_car):
+            k = item['k']
+            aee, p1, p3 = flow_error_from_sums(item['err_sums'])[:3]
+            p1, p3 = 1.0 - p1, 1.0 - p3                              # the outlier shares, as the evaluation loop's "1 - mean %AEE" / "3 - mean %AEE"
+            acc['aee'] += aee
+            acc['p1'] += p1
+            acc['p3'] += p3
+            pairs += 1
+            print('pair {:6d}  frame {:6d}  events {:9d}  AEE: {:2.6f}  %1px: {:.6f}  %3px: {:.6f}'.format(
+                k, first + k * args.dt, int(offsets[k + 1] - offsets[k]), aee, p1, p3))
+            if args.out:
+                write_flo(os.path.join(args.out, '%06d.flo' % k), item['flow'][0].permute(1, 2, 0).cpu().numpy())
+                write_flo(os.path.join(args.out, '%06d_gt.flo' % k), item['flow_gt'][0].permute(1, 2, 0).cpu().numpy())
+    torch.cuda.synchronize(dev)
+    wall = time.perf_counter() - start
+    n = max(pairs, 1)
+    print('pairs {}  events {}  Mean AEE: {:.6f}  mean %1px: {:.6f}  mean %3px: {:.6f}  {:.1f} frames/s'.format(
+        pairs, int(offsets[-1] - offsets[0]), acc['aee'] / n, acc['p1'] / n, acc['p3'] / n, pairs / wall if wall > 0 else float('nan')))
+    return {'pairs': pairs, 'events': int(offsets[-1] - offsets[0]), 'meanAEE': acc['aee'] / n, 'mean1px': acc['p1'] / n, 'mean3px': acc['p3'] / n,
+            'frames_per_s': pairs / wall if wall > 0 else float('nan')}
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    return {'train': train, 'test': test, 'run': run}[args.command](args)
+    return {'train': train, 'test': test, 'run': run, 'mvsec': mvsec}[args.command](args)
 
 
 if __name__ == '__main__':

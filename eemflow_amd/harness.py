@@ -126,7 +126,8 @@ def stream_chunks(dataset, model, n, dev, fb_check=None, with_volumes=False):
             yield (list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]) + tail
 
 
-def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, bidirectional=False, fb_check=None, iters=None):
+def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, bidirectional=False, fb_check=None, iters=None, gt=None,
+                  t_edges=None, crop=None, eval_type='dense', is_car=False):
     """Flow along the consecutive windows [offsets[k], offsets[k+1]) of a resident recording (eemflow_amd.recording.EventRecording): a
     generator of one dict per pair of neighbouring windows, in time order -
         'k'         the pair's first window (the flow runs from window k to window k + 1)
@@ -139,10 +140,30 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
     forward_stream call; the window the model carries joins the chunks, so every window is voxelized and encoded once.  The stream
     is reset at the start and the model sized to the recording's sensor.  fb_check = (alpha1, alpha2[, 'all' | 'obj' | 'out']) implies
     bidirectional; iters: E-RAFT's refinement steps per pair (forward_stream's own default when None).  The loop itself reads nothing back from the device (fwl_many / rsat_many read their windows' end times, one small
-    copy per chunk)."""
+    copy per chunk).
+    gt = a mvsec_raw.MvsecGroundTruth, with t_edges = the K + 1 timestamps of the window edges (offsets[k] is the first event of the
+    window that starts at t_edges[k]: MvsecRaw.frame_windows gives both): every item gains
+        'flow_gt'   [1, 2, h, w], the ground-truth displacement over [t_edges[k], t_edges[k+1]] (MvsecGroundTruth.flow_many)
+        'err_sums'  the five doubles of metrics.flow_error_sums_many for the pair (metrics.flow_error_from_sums turns them into
+                    the reference's AEE / outlier tuple); is_car drops the rows from 190 on, as Test.flow_error does
+    by ONE ground-truth launch and ONE metrics launch per chunk, no synchronisation.  eval_type='sparse' scores the pixels of window k
+    that hold an event (mvsec_raw.event_mask_windows on the chunk's first windows; the item gains 'event_valid', [h, w] fp32 0 / 1).
+    crop = (th, tw): the voxel grids are centre-cropped (mvsec.center_crop) before forward_stream, the model is sized to the crop,
+    ground truth and mask are cropped the same way - the dataset's validation branch (MVSEC.py:193-197).  crop with fwl or rsat is
+    refused: the events would need the crop's offset.  Without these keywords items, launches and lines are exactly as before."""
     from .recording import _check_offsets, voxelize_windows
     if fb_check is not None:
         bidirectional = True
+    if eval_type not in ('dense', 'sparse'):
+        raise ValueError(f"run_recording: eval_type is 'dense' or 'sparse', got {eval_type!r}")
+    if gt is None and (t_edges is not None or eval_type != 'dense' or is_car):
+        raise ValueError("run_recording: t_edges=, eval_type='sparse' and is_car= qualify gt= (the ground truth they score against)")
+    if crop is not None:
+        if fwl or rsat:
+            raise ValueError("run_recording: crop= with fwl= or rsat= is refused: the events are not moved into the crop's frame")
+        crop = (int(crop[0]), int(crop[1]))
+        if not (1 <= crop[0] <= recording.height and 1 <= crop[1] <= recording.width):
+            raise ValueError(f"run_recording: crop {crop} does not fit the recording's {recording.height} x {recording.width} sensor")
     if bidirectional and not hasattr(model, "MAX_STREAM_BIDIR"):
         raise ValueError(f"fb_check= needs a model whose forward_stream takes bidirectional=True (EEMFlow); {type(model).__name__} has none")
     if not hasattr(model, "forward_stream"):
@@ -153,7 +174,15 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
     if not 1 <= chunk <= limit:
         raise ValueError(f"run_recording: chunk is 1..{limit} windows per forward_stream call" + (" with bidirectional=True" if bidirectional else "")
                          + f", got {chunk}")
-    size = (recording.height, recording.width)
+    if gt is not None:
+        if t_edges is None or len(t_edges) != len(offs):
+            raise ValueError(f"run_recording: gt= needs t_edges=, one timestamp per window edge ({len(offs)} for these offsets)")
+        t_edges = [float(t) for t in t_edges]
+        if (gt.height, gt.width) != (recording.height, recording.width) or gt.device != recording.device:
+            raise ValueError("run_recording: the ground truth and the recording differ in size or device")
+        for t0, t1 in zip(t_edges, t_edges[1:-1]):
+            gt.plan(t0, t1)                                          # a window the stack cannot serve is refused before any launch
+    size = crop if crop is not None else (recording.height, recording.width)
     if tuple(int(v) for v in getattr(model, "image_size", None) or ()) != size:
         model.change_imagesize(size)
     model.reset_stream()
@@ -170,6 +199,9 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
     for w0 in range(0, nwin, chunk):
         part = offs[w0:w0 + chunk + 1]
         vols = voxelize_windows(recording, part, model.n_first_channels)
+        if crop is not None:
+            from .mvsec import center_crop
+            vols = [center_crop(v, crop) for v in vols]
         outs = model.forward_stream(vols, **extra)
         if not outs:
             continue                                                 # the first chunk held one window: it is carried
@@ -190,6 +222,23 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
                 from .tsimg import rsat_many
                 for it, v in zip(items, rsat_many(tables, flows)):
                     it['RSAT'] = v
+        if gt is not None:
+            n = len(outs)
+            gts = gt.flow_many(t_edges[k:k + n], t_edges[k + 1:k + n + 1])
+            masks = None
+            if eval_type == 'sparse':
+                from .mvsec_raw import event_mask_windows
+                masks = event_mask_windows(recording, offs[k:k + n + 1])
+            if crop is not None:
+                from .mvsec import center_crop
+                gts = center_crop(gts, crop).contiguous()            # (one copy for the chunk; its slices are contiguous)
+                masks = center_crop(masks, crop).contiguous() if masks is not None else None
+            sums = flow_error_sums_many([gts[i:i + 1] for i in range(n)], [it['flow'] for it in items],
+                                        [masks[i] for i in range(n)] if masks is not None else None, is_car=is_car, evaluation_type=eval_type)
+            for i, it in enumerate(items):
+                it['flow_gt'], it['err_sums'] = gts[i:i + 1], sums[i]
+                if masks is not None:
+                    it['event_valid'] = masks[i]
         k += len(outs)
         yield from items
 

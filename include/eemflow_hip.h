@@ -563,6 +563,41 @@ int eemflow_voxelize_windows(int nwin, const void* t, const void* x, const void*
                              const int64_t* offsets, double scale_a, double scale_b, int relative, int bins, int h, int w,
                              int normalize, float* const* grids, void* stream);
 
+/* MVSEC ground-truth flow of njobs (1..32) windows by ONE launch, from the device-resident ground-truth stack gt ([nframes][2][h][w]
+ * fp32: MVSEC's flow_dist, 20 Hz displacement maps; frame f is the displacement between timestamps f and f + 1).  The host plans each
+ * window [start, end] (eemflow_amd.mvsec_raw.MvsecGroundTruth.plan, NumPy float64, the reference's searchsorted and scale factors):
+ * frame0[k], nsteps[k], a[k], b[k]; out[k] is (2,h,w) fp32 on the device.  frame0, nsteps, a, b and out are HOST arrays, read
+ * before the call returns.  One thread walks one pixel of one job through all its steps, the position in registers:
+ *   nsteps == 0   the window is shorter than the ground-truth interval (the reference's early return), a = dt, b = gt_dt:
+ *                     out = (float)(((double)gt[frame0] * a) / b)          the reference returns this float64; rounded to fp32 ONCE here
+ *   nsteps >= 2   x, y start at the pixel's integer coordinates as fp32; step s = 0 .. nsteps-1 reads frame frame0 + s with the
+ *                 scale a for the first step, b for the last and 1.0 between:
+ *                     ix = rint(x), iy = rint(y)                           round half to even: cv2.remap(INTER_NEAREST) on float maps (cvRound)
+ *                     (fu, fv) = gt[frame0 + s][:, iy, ix], or 0 outside [0,w) x [0,h)      BORDER_CONSTANT
+ *                     fu == 0 clears the x mask, fv == 0 the y mask        independent and sticky; also on a last step of scale 0
+ *                     x = (float)((double)x + (double)fu * scale), y likewise               product and sum unfused, rounded to fp32 once
+ *                 out = x - x0, y - y0 in fp32, 0 where the component's mask is cleared.
+ *   nsteps == 1 does not occur (the long branch has a first and a last step) and is refused.
+ * A NaN flow value is not == 0: it keeps its mask and its component is NaN.  A non-finite position finds no cell and reads 0; that
+ * read clears the mask of a component whose own coordinate is finite and leaves a non-finite component as it is, so no NaN or infinity
+ * becomes a number (cv2's integer conversion of a non-finite coordinate is undefined).  A job whose frames leave the stack, njobs
+ * outside 1..32 or a NULL / misaligned pointer is an error return before any launch.  Stream-ordered, no host synchronisation, no
+ * allocation: the plans travel as kernel arguments.
+ * Replaces: estimate_corresponding_gt_flow and prop_flow (loader/loader_utils.py:70-161, duplicated in utils/mvsec_utils.py) as
+ * loader/MVSEC_encoder.py:130-158 calls them per frame on the CPU - one cv2.remap of each component plus one add per step. */
+int eemflow_gt_flow_many(int njobs, const float* gt, int nframes, int h, int w, const int* frame0, const int* nsteps, const double* a,
+                         const double* b, float* const* out, void* stream);
+
+/* The event masks of nwin (1..32) consecutive windows of ONE device-resident recording: x, y are the recording's base columns in the
+ * dtypes code_x, code_y (EEMFLOW_PACK_*), window k the elements [offsets[k], offsets[k+1]) (offsets: nwin + 1 HOST integers, ascending;
+ * empty windows allowed), masks[k] an [h][w] fp32 image on the device (masks: a HOST array).  Every mask is zero-filled, then pixel
+ * (min(floor(y), h-1), min(floor(x), w-1)) of every event with 0 <= x <= w and 0 <= y <= h is set to 1.0f by plain stores:
+ * np.histogram2d(x, y, bins=(w,h), range=[[0,w],[0,h]]).T > 0, whose last bin is closed.  Two launches, stream-ordered, no host
+ * synchronisation.  A mask is a valid `event_img` of the 'sparse' eemflow_flow_error.
+ * Replaces: the event_valid image of loader/MVSEC.py:132-142 (eemflow_amd.mvsec.event_mask), built on the host per sample. */
+int eemflow_event_mask_windows(int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* offsets, int h, int w,
+                               float* const* masks, void* stream);
+
 /* Augmentation of n (1..EEMFLOW_AUGMENT_MAX) training samples of one source size and one output size by ONE launch, written into the
  * batch tensors: vol_old[i], vol_new[i] ([C][H][W] fp32), flow[i] ([2][H][W]; fp64 with flow_f64 != 0, else fp32; a NULL entry, or
  * flow == NULL, is a sample without flow: HREM's mesh flow is returned un-augmented by the reference) and plans[i] are HOST arrays, read
