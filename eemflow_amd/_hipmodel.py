@@ -160,6 +160,20 @@ class HipModel:
                                  _lib.current_stream_ptr(self._ctx_device)))
         return out
 
+    def stage_names(self):
+        """[(name, form, (n, c, h, w))] of everything the stage recorder (`record_stages`; EEMFlow+ and E-RAFT) filed in the last call,
+        in launch order."""
+        stage_list = self._abi("stage_list")
+        need = ctypes.c_size_t()
+        _lib.check(stage_list(self._ctx, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        _lib.check(stage_list(self._ctx, buf, need.value, ctypes.byref(need)))
+        out = []
+        for line in buf.value.decode().splitlines():
+            name, form, *dims = line.split()
+            out.append((name, "" if form == "-" else form, tuple(int(d) for d in dims)))
+        return out
+
     def _release(self):
         if self._ctx is not None:
             self._abi("destroy")(self._ctx)

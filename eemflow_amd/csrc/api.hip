@@ -27,14 +27,8 @@ extern "C" int eemflow_abi_version(void) { return 1; }
 // ------------------------------------------------------------------------------- C ABI
 extern "C" int eemflow_create(int device, eemflow_ctx** out) {
     EEM_REQUIRE(out != nullptr, "eemflow_create: out is NULL");
-    int ndev = 0;
-    EEM_HIP_CHECK(hipGetDeviceCount(&ndev));
-    EEM_REQUIRE(device >= 0 && device < ndev, "eemflow_create: device %d of %d", device, ndev);
-    EEM_HIP_CHECK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    EEM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
-    EEM_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0,
-                "this library is built for gfx950 (MI355X) only; device %d is %s", device, prop.gcnArchName);
+    const int rc = ctx_open_device("eemflow_create", device);
+    if (rc != EEM_OK) return rc;
     eemflow_ctx* c = new eemflow_ctx();
     c->device = device;
     hipError_t e = hipMalloc(&c->taps, sizeof(kTaps53));
@@ -56,16 +50,6 @@ extern "C" void eemflow_destroy(eemflow_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     drop_graph(c);
-    DevBuf* bufs[] = {&c->a1, &c->f11, &c->a2, &c->b2, &c->f12, &c->a3, &c->b3, &c->f13, &c->flowcat, &c->coarse, &c->carry,
-                      &c->padded, &c->fuse_scratch, &c->g_a1, &c->g_f11, &c->g_a2, &c->g_b2, &c->g_f12, &c->g_a3, &c->g_b3, &c->g_f13,
-                      &c->g_flowcat, &c->g_coarse, &c->g_flow, &c->ups_tmp, &c->grad_flat, &c->adam_m, &c->adam_v, &c->scalars};
-    for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
-    for (int k = 0; k < 3; ++k) {
-        if (c->ppart[k].p) (void)hipFree(c->ppart[k].p);
-        DevBuf* kb[] = {&c->pool[k], &c->cat[k], &c->ta[k], &c->tb[k], &c->tc[k], &c->td[k], &c->t64[k], &c->t32[k],
-                        &c->g_pool[k], &c->g_cat[k], &c->g_ta[k], &c->g_tb[k], &c->g_tc[k], &c->g_td[k], &c->g_t64[k], &c->g_t32[k]};
-        for (DevBuf* b : kb) if (b->p) (void)hipFree(b->p);
-    }
     if (c->cstream) { (void)hipStreamSynchronize(c->cstream); (void)hipStreamDestroy(c->cstream); }
     if (c->loss_ev) (void)hipEventDestroy(c->loss_ev);
     if (c->stats_ev) (void)hipEventDestroy(c->stats_ev);
@@ -498,16 +482,11 @@ static int forward_stream_impl(eemflow_ctx* c, int nvol, const float* const* vol
     EEM_REQUIRE(c->have_pad, "%s: call eemflow_set_image_size first", fn);
     EEM_REQUIRE(in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, "%s: bad sizes", fn);
     EEM_REQUIRE(!c->enc0_generic, "%s: built for the 5-bin first layer (n_first_channels == 5)", fn);
-    if (c->stream_pending) {
-        EEM_REQUIRE(c->stream_wver == c->weights_version, "%s: the weights changed since the carried window was encoded; "
-                    "call eemflow_stream_reset to start a new stream", fn);
-        EEM_REQUIRE(c->stream_h == in_h && c->stream_w == in_w && memcmp(c->stream_pad, c->pad, sizeof(c->pad)) == 0,
-                    "%s: the carried window is %dx%d, this call's volumes are %dx%d (or the padding changed); "
-                    "call eemflow_stream_reset to start a new stream", fn, c->stream_h, c->stream_w, in_h, in_w);
-    }
-    const int want = c->stream_pending ? nvol : nvol - 1;
+    int rc = stream_carry_check(c->stream, fn, "eemflow", in_h, in_w, c->pad, 0, (unsigned long)c->weights_version);
+    if (rc != EEM_OK) return rc;
+    const int want = c->stream.pairs(nvol);
     EEM_REQUIRE(nflow == want, "%s: %d volumes %s give %d flows; nflow = %d", fn, nvol,
-                c->stream_pending ? "after the carried window" : "with no carried window", want, nflow);
+                c->stream.on ? "after the carried window" : "with no carried window", want, nflow);
     EEM_REQUIRE(nflow == 0 || flow_out, "%s: %s is NULL", fn, bidir ? "flow_fw_out" : "flow_out");
     EEM_REQUIRE(nflow == 0 || !bidir || flow_bw, "%s: flow_bw_out is NULL", fn);
     for (int i = 0; i < nvol; ++i) {
@@ -531,18 +510,15 @@ static int forward_stream_impl(eemflow_ctx* c, int nvol, const float* const* vol
     }
     StreamCall sc;
     sc.bidir = bidir;
-    sc.carry_in = c->stream_pending ? 1 : 0;
+    sc.carry_in = c->stream.on ? 1 : 0;
     sc.slot_in = c->stream_slot;
-    sc.slot_out = c->stream_pending ? 1 - c->stream_slot : 0;
-    c->stream_pending = false;                                   // (a failed call leaves no carry behind)
-    const int rc = forward_common(c, nvol, vols, none, outs, nout, in_h, in_w, out_h, out_w, stream, &sc);
+    sc.slot_out = c->stream.on ? 1 - c->stream_slot : 0;
+    c->stream.clear();                                           // (a failed call leaves no carry behind)
+    rc = forward_common(c, nvol, vols, none, outs, nout, in_h, in_w, out_h, out_w, stream, &sc);
     c->have_last = false;                                        // the workspace holds windows, not a forward's pairs (eemflow_get_stage)
     if (rc != EEM_OK) return rc;
-    c->stream_pending = true;
     c->stream_slot = sc.slot_out;
-    c->stream_wver = c->weights_version;
-    c->stream_h = in_h; c->stream_w = in_w;
-    memcpy(c->stream_pad, c->pad, sizeof(c->pad));
+    c->stream.take(in_h, in_w, c->pad, 0, (unsigned long)c->weights_version);
     return EEM_OK;
 }
 
@@ -560,13 +536,13 @@ extern "C" int eemflow_forward_stream_bidir(eemflow_ctx* c, int nvol, const floa
 
 extern "C" int eemflow_stream_reset(eemflow_ctx* c) {
     EEM_REQUIRE(c, "eemflow_stream_reset: NULL context");
-    c->stream_pending = false;
+    c->stream.clear();
     return EEM_OK;
 }
 
 extern "C" int eemflow_stream_pending(eemflow_ctx* c, int* out) {
     EEM_REQUIRE(c && out, "eemflow_stream_pending: NULL argument");
-    *out = c->stream_pending ? 1 : 0;
+    *out = c->stream.on ? 1 : 0;
     return EEM_OK;
 }
 

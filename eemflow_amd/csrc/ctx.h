@@ -15,10 +15,7 @@
 #include "wnc.h"
 
 // ------------------------------------------------------------------------------- context
-inline constexpr int kTaps53[53] = {0,  2,  4,  6,  8,  10, 12, 14, 16, 18, 20, 21, 22, 23, 24, 26, 28, 29,
-                                    30, 31, 32, 33, 34, 36, 38, 39, 40, 41, 42, 44, 46, 47, 48, 49, 50, 51,
-                                    52, 54, 56, 57, 58, 59, 60, 62, 64, 66, 68, 70, 72, 74, 76, 78, 80};
-constexpr int kNTaps = 53;
+constexpr int kNTaps = 53;            // (kTaps53: devstate.h)
 constexpr int kDecIn = kNTaps + 16;   // 69
 constexpr int kDecW = 100;
 
@@ -180,10 +177,8 @@ struct eemflow_ctx {
     // (a call reads one and writes the other).  Owned by the context, apart from the shared workspace: forward / forward_many /
     // forward_train between two stream calls leave it alone
     DevBuf carry;
-    bool stream_pending = false;
+    StreamCarry stream;                                  // (its wver: weights_version the window was encoded with)
     int stream_slot = 0;                                 // the slot holding the carried window
-    long stream_wver = 0;                                // weights_version it was encoded with
-    int stream_h = 0, stream_w = 0, stream_pad[4] = {0, 0, 0, 0};
     int frames_in_flight = 1;                            // eemflow_set_frames_in_flight: >= 3 shrinks the persistent encoder grids
     // eemflow_set_deferred_input_norm: the event volumes handed to forward / forward_many are RAW voxel grids with their normalisation
     // record behind them (eemflow_voxelize*, normalize = 2); pconv1_1 normalises as it reads

@@ -13,12 +13,6 @@
 
 namespace {
 
-struct StageRec {                 // one recorded launch output: [dims] floats at rec_buf + off
-    std::string name, form;
-    int dims[4];
-    size_t off;
-};
-
 struct Layer {                    // one convolution, weights packed for gconv
     size_t wpk = 0, wpk16 = 0, wpkb = 0, wfew = 0, wstem = 0, scale = 0, shift = 0;
     bool hasb = false, has_stem = false;
@@ -85,19 +79,14 @@ struct eraft_ctx {
     // eraft_forward_stream: the carry - the last window's padded volume and feature map, the last pair's flow_low - in memory of its
     // own (forward / forward_many / the operator-level calls reuse the workspace, never these), and the last call's per-pair flow_low
     DevBuf carry_pad, carry_fmap, carry_flow, sflow, finit, fi_ws;
-    bool carry_on = false, carry_has_flow = false;
-    int carry_h = 0, carry_w = 0, carry_padv[4] = {0, 0, 0, 0};
-    unsigned long carry_wver = 0;
+    StreamCarry stream;
+    bool carry_has_flow = false;
     int stream_pairs = 0;          // > 0: the last forward was a stream call of that many pairs ("flow_low" reads sflow)
-    // eraft_record_stages (the fp64 stage tests): a device copy of every launch's output whose name starts with one of `rec_prefix`,
-    // filed with the kernel form that wrote it.  The copies live in one arena sized by the forward before: a forward whose records do
-    // not fit only measures them and is run again (eraft_forward / eraft_forward_many) with the arena grown before its first fork
-    bool rec_on = false;
-    std::vector<std::string> rec_prefix;
+    // eraft_record_stages (the fp64 stage tests): a device copy of every launch's output whose name starts with one of the prefixes,
+    // filed with the kernel form that wrote it.  A forward whose records do not fit only measures them and is run again
+    // (eraft_forward / eraft_forward_many) with the arena grown before its first fork
+    DevStageRecorder rec;
     int rec_iters = 0;             // update iterations 0 .. rec_iters - 1 are recorded
-    std::vector<StageRec> rec;
-    DevBuf rec_buf;
-    size_t rec_used = 0, rec_need = 0;
 };
 
 namespace {
@@ -259,26 +248,6 @@ void set_seg(GConvArgs& a, int i, const float* ptr, int cch, int ctotal, int cof
     a.seg[i].ptr = ptr; a.seg[i].c = cch; a.seg[i].ctotal = ctotal; a.seg[i].coff = coff;
 }
 
-// The stage recorder (eraft_ctx::rec_on): `src` is [n][src_ctotal][h * w], of which the channels [src_coff, src_coff + ch) are copied on
-// `st`, the stream of the launch that has just written them.  It launches no kernel; with the recorder off no call site gets here.
-int rec_stage(eraft_ctx* c, const char* name, const char* form, const float* src, int n, int ch, int h, int w, hipStream_t st,
-              int src_ctotal = 0, int src_coff = 0) {
-    bool wanted = false;
-    for (const std::string& p : c->rec_prefix) wanted = wanted || strncmp(name, p.c_str(), p.size()) == 0;
-    if (!wanted) return EEM_OK;
-    const size_t hw = (size_t)h * w, cnt = (size_t)n * ch * hw, off = c->rec_used;
-    c->rec_used += (cnt + 63) & ~(size_t)63;
-    if (c->rec_used > c->rec_buf.cap) return EEM_OK;                     // measured only: the forward runs again with the arena grown
-    float* dst = c->rec_buf.p + off;
-    if (src_ctotal == 0 || src_ctotal == ch)
-        EEM_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * 4, hipMemcpyDeviceToDevice, st));
-    else
-        EEM_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)ch * hw * 4, src + (size_t)src_coff * hw, (size_t)src_ctotal * hw * 4, (size_t)ch * hw * 4, n,
-                                       hipMemcpyDeviceToDevice, st));
-    c->rec.push_back(StageRec{name, form ? form : "", {n, ch, h, w}, off});
-    return EEM_OK;
-}
-
 // A 64 -> 64 3x3 conv of the encoder on the Winograd F(4x4,3x3) kernel: out = act(conv(x) + shift) [then relu(res + .)];
 // act: 0 none (an InstanceNorm follows), 2 ReLU (eval BatchNorm folded into weights and shift).  From 128 tiles of 32x16 pixels on
 // (fewer leave most CUs without a block and the LDS-tiled kernel wins); EEM_ERAFT_NO_F4=1 keeps every conv on gconv.
@@ -344,7 +313,7 @@ int run_encoder(eraft_ctx* c, const Encoder& E, const float* x, int n, int cin0,
     auto recl = [&](int l, int r, const char* what, const char* form, const float* p, int ch, int hh, int ww) -> int {
         if (l < 0) snprintf(rname, sizeof(rname), "%s%s", tag, what);
         else snprintf(rname, sizeof(rname), "%slayer%d.%d.%s", tag, l + 1, r, what);
-        return rec_stage(c, rname, form, p, n, ch, hh, ww, st);
+        return c->rec.stage(rname, form, p, n, ch, hh, ww, st);
     };
     float* X = sc[0].p; float* R = sc[1].p; float* Y = sc[2].p; float* D = sc[3].p; float* O = sc[4].p;
     int h = hp, w = wp;
@@ -414,12 +383,12 @@ int build_pyramid(eraft_ctx* c, const float* f1, const float* f2, int batch, int
         if ((rc = devbuf_ensure(c->pyr[l], (size_t)batch * hw * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
     }
     if ((rc = er_allpairs_launch(f1, f2, c->pyr[0].p, batch, ch, (int)hw, c->arena + c->zero_off, st)) != EEM_OK) return rc;
-    if (recd && (rc = rec_stage(c, "pyr0", er_last_form, c->pyr[0].p, (int)(batch * hw), 1, h, w, st)) != EEM_OK) return rc;
+    if (recd && (rc = c->rec.stage("pyr0", er_last_form, c->pyr[0].p, (int)(batch * hw), 1, h, w, st)) != EEM_OK) return rc;
     if ((rc = er_pool2x3_launch(c->pyr[0].p, c->pyr[1].p, c->pyr[2].p, c->pyr[3].p, (long)batch * hw, h, w, st)) != EEM_OK) return rc;
     if (recd)
         for (int l = 1; l < 4; ++l) {
             const char nm[5] = {'p', 'y', 'r', (char)('0' + l), 0};
-            if ((rc = rec_stage(c, nm, er_last_form, c->pyr[l].p, (int)(batch * hw), 1, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
+            if ((rc = c->rec.stage(nm, er_last_form, c->pyr[l].p, (int)(batch * hw), 1, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
         }
     return EEM_OK;
 }
@@ -435,7 +404,7 @@ int build_feature_pyramid(eraft_ctx* c, const float* f2, int batch, int ch, int 
         if ((rc = devbuf_ensure(c->f2l[l - 1], (size_t)batch * ch * c->ph[l] * c->pw[l])) != EEM_OK) return rc;
         if ((rc = er_pool2_launch(src, c->f2l[l - 1].p, (long)batch * ch, c->ph[l - 1], c->pw[l - 1], st)) != EEM_OK) return rc;
         const char nm[5] = {'f', '2', 'l', (char)('0' + l), 0};
-        if (recd && (rc = rec_stage(c, nm, er_last_form, c->f2l[l - 1].p, batch, ch, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
+        if (recd && (rc = c->rec.stage(nm, er_last_form, c->f2l[l - 1].p, batch, ch, c->ph[l], c->pw[l], st)) != EEM_OK) return rc;
         src = c->f2l[l - 1].p;
     }
     return EEM_OK;
@@ -474,14 +443,8 @@ int run_lookup(eraft_ctx* c, const float* coords, float* out, int out_ctotal, in
 
 extern "C" int eraft_create(int device, eraft_ctx** out) {
     EEM_REQUIRE(out != nullptr, "eraft_create: out is NULL");
-    int ndev = 0;
-    EEM_HIP_CHECK(hipGetDeviceCount(&ndev));
-    EEM_REQUIRE(device >= 0 && device < ndev, "eraft_create: device %d of %d", device, ndev);
-    EEM_HIP_CHECK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    EEM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
-    EEM_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0, "built for gfx950 (MI355X) only; device %d is %s", device,
-                prop.gcnArchName);
+    const int rc = ctx_open_device("eraft_create", device);
+    if (rc != EEM_OK) return rc;
     eraft_ctx* c = new eraft_ctx();
     c->device = device;
     *out = c;
@@ -491,17 +454,10 @@ extern "C" int eraft_create(int device, eraft_ctx** out) {
 extern "C" void eraft_destroy(eraft_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    DevBuf* all[] = {&c->padded, &c->s[0], &c->s[1], &c->s[2], &c->s[3], &c->s[4], &c->fmap, &c->net[0], &c->net[1], &c->net[2], &c->inp,
-                  &c->pyr[0], &c->pyr[1], &c->pyr[2], &c->pyr[3], &c->c0, &c->c1, &c->c1b, &c->corr, &c->cor1, &c->corflo, &c->flo1,
-                  &c->motion, &c->z, &c->rh, &c->fhid, &c->delta, &c->mhid, &c->mask, &c->st_corr0, &c->st_net1, &c->st_mask1,
-                  &c->st_delta1, &c->zeros, &c->many_out, &c->f2l[0], &c->f2l[1], &c->f2l[2], &c->czr[0], &c->czr[1], &c->cq[0], &c->cq[1],
-                  &c->s2[0], &c->s2[1], &c->s2[2], &c->s2[3], &c->s2[4], &c->carry_pad, &c->carry_fmap, &c->carry_flow, &c->sflow,
-                  &c->finit, &c->fi_ws, &c->rec_buf};
-    for (DevBuf* b : all) if (b->p) (void)hipFree(b->p);
-    if (c->nstat) (void)hipFree(c->nstat);
-    if (c->side) (void)hipStreamDestroy(c->side);
+    if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->join_ev) (void)hipEventDestroy(c->join_ev);
+    if (c->nstat) (void)hipFree(c->nstat);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wino) (void)hipFree(c->wino);
     if (c->trash) (void)hipFree(c->trash);
@@ -670,11 +626,9 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     ENS(c->mask, B * 576 * g);
     const bool keep = c->keep_stages && !sp;
     if (keep) { ENS(c->st_corr0, B * 324 * g); ENS(c->st_net1, B * 128 * g); ENS(c->st_mask1, B * 576 * g); ENS(c->st_delta1, B * 2 * g); }
-    // the stage recorder (a stream call records nothing): its arena, sized by the forward before (see eraft_ctx)
-    const bool recd = c->rec_on && !sp;
-    c->rec.clear();
-    c->rec_used = 0;
-    if (recd) ENS(c->rec_buf, c->rec_need);
+    // the stage recorder (a stream call records nothing): its arena, sized by the forward before (stagerec.h)
+    const bool recd = c->rec.on && !sp;
+    if ((rc = c->rec.begin_call(recd, c->rec.need)) != EEM_OK) return rc;
     if (sp) {
         ENS(c->sflow, (size_t)std::max(B, 1) * 2 * g); ENS(c->finit, 2 * g);
         ENS(c->fi_ws, eraft_forward_interpolate_scratch(1, h8, w8));    // (ints)
@@ -683,12 +637,12 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     const int cin0 = c->cin0;
     const size_t img = (size_t)cin0 * hp * wp;
     char rname[48];
-#define REC(...) if (recd && (rc = rec_stage(c, __VA_ARGS__)) != EEM_OK) return rc
+#define REC(...) if (recd && (rc = c->rec.stage(__VA_ARGS__)) != EEM_OK) return rc
     // (inside the update loop: iteration `it`'s stage `what`, a [B][ch][h8][w8] slice, on stream `strm`)
 #define RECIT(what, form, src, ch, strm, ctotal, coff)                                                              \
     if (recd && it < c->rec_iters) {                                                                                \
         snprintf(rname, sizeof(rname), "it%d.%s", it, what);                                                        \
-        if ((rc = rec_stage(c, rname, form, src, B, ch, h8, w8, strm, ctotal, coff)) != EEM_OK) return rc;          \
+        if ((rc = c->rec.stage(rname, form, src, B, ch, h8, w8, strm, ctotal, coff)) != EEM_OK) return rc;          \
     }
     if (sp) {                                                            // the windows into slots s0.., the carried one into slot 0
         if (sp->carried) EEM_HIP_CHECK(hipMemcpyAsync(c->padded.p, c->carry_pad.p, img * 4, hipMemcpyDeviceToDevice, st));
@@ -851,7 +805,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
         char pname[48];
         auto recs = [&](const char* what, const char* form, const float* src, int ch, int hh, int ww) -> int {
             snprintf(pname, sizeof(pname), "it%d.%s", pend.it, what);
-            return rec_stage(c, pname, form, src, LB, ch, hh, ww, sd);
+            return c->rec.stage(pname, form, src, LB, ch, hh, ww, sd);
         };
         if (recp && (r2 = recs("mhid", eem_conv_form, c->mhid.p, 256, h8, w8)) != EEM_OK) return r2;
         m = conv_args(c, c->mk2, LB, h8, w8, c->mask.p, 576, 0, GACT_NONE);
@@ -1100,7 +1054,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
             }
             if (recd && it < c->rec_iters) {
                 snprintf(rname, sizeof(rname), "it%d.pred", it);
-                if ((rc = rec_stage(c, rname, er_last_form, lout + (size_t)oi * B * 2 * in_h * in_w, B, 2, in_h, in_w, st)) != EEM_OK) return rc;
+                if ((rc = c->rec.stage(rname, er_last_form, lout + (size_t)oi * B * 2 * in_h * in_w, B, 2, in_h, in_w, st)) != EEM_OK) return rc;
             }
         }
         if (it == 0 && keep) {
@@ -1120,7 +1074,7 @@ static int eraft_forward_impl(eraft_ctx* c, const float* e1, const float* e2, co
     c->stages_valid = keep;
     c->fmap_imgs = nimg;
     c->stream_pairs = sp ? B : 0;
-    if (recd) c->rec_need = std::max(c->rec_need, c->rec_used);
+    if (recd) c->rec.end();
 #undef REC
 #undef RECIT
     return EEM_OK;
@@ -1134,7 +1088,7 @@ extern "C" int eraft_forward(eraft_ctx* c, const float* e1, const float* e2, int
     EEM_HIP_CHECK(hipSetDevice(c->device));
     int rc = eraft_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, iters, flow_init, out, (hipStream_t)stream);
     // the stage recorder's arena was too small: that forward measured it; the same forward again, with the arena grown, fills it
-    if (rc == EEM_OK && c->rec_on && c->rec_used > c->rec_buf.cap)
+    if (rc == EEM_OK && c->rec.rerun())
         rc = eraft_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, iters, flow_init, out, (hipStream_t)stream);
     return rc;
 }
@@ -1157,7 +1111,7 @@ extern "C" int eraft_forward_many(eraft_ctx* c, int n, const float* const* event
     int rc = devbuf_ensure(c->many_out, (size_t)nout * n * per);
     if (rc != EEM_OK) return rc;
     if ((rc = eraft_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, iters, nullptr, c->many_out.p, st)) != EEM_OK) return rc;
-    if (c->rec_on && c->rec_used > c->rec_buf.cap &&                      // (the recorder's arena has grown: see eraft_forward)
+    if (c->rec.rerun() &&                                                 // (the recorder's arena has grown: see eraft_forward)
         (rc = eraft_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, iters, nullptr, c->many_out.p, st)) != EEM_OK) return rc;
     for (int i = 0; i < n; ++i)                                          // [nout][n][2][H][W] -> sample i's [nout][1][2][H][W]
         EEM_HIP_CHECK(hipMemcpy2DAsync(flow_out[i], per * 4, c->many_out.p + (size_t)i * per, (size_t)n * per * 4, per * 4, nout,
@@ -1179,17 +1133,12 @@ extern "C" int eraft_forward_stream(eraft_ctx* c, int nvol, const float* const* 
     for (int j = 0; j < nvol; ++j) EEM_REQUIRE(volumes[j], "eraft_forward_stream: NULL pointer for window %d", j);
     const int hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
     EEM_REQUIRE(hp % 8 == 0 && wp % 8 == 0, "eraft_forward_stream: padded size %dx%d must be a multiple of 8", hp, wp);
-    if (c->carry_on) {
-        EEM_REQUIRE(c->carry_wver == c->wver, "eraft_forward_stream: the weights changed since the carried window was encoded; "
-                    "call eraft_stream_reset to start a new stream");
-        EEM_REQUIRE(c->carry_h == in_h && c->carry_w == in_w && memcmp(c->carry_padv, pad, sizeof(c->carry_padv)) == 0,
-                    "eraft_forward_stream: the carried window is %dx%d (pad %d %d %d %d), this call's %dx%d (pad %d %d %d %d); call "
-                    "eraft_stream_reset to start a new stream", c->carry_h, c->carry_w, c->carry_padv[0], c->carry_padv[1], c->carry_padv[2],
-                    c->carry_padv[3], in_h, in_w, pad[0], pad[1], pad[2], pad[3]);
-    }
-    const int P = c->carry_on ? nvol : nvol - 1;
+    int rc = stream_carry_check(c->stream, "eraft_forward_stream", "eraft", in_h, in_w, pad, 0, c->wver);
+    if (rc != EEM_OK) return rc;
+    const bool carried = c->stream.on;
+    const int P = c->stream.pairs(nvol);
     EEM_REQUIRE(nflow == P, "eraft_forward_stream: %d windows %s make %d pairs, nflow = %d", nvol,
-                c->carry_on ? "after the carried window" : "with no carried window", P, nflow);
+                carried ? "after the carried window" : "with no carried window", P, nflow);
     if (P > 0) {
         EEM_REQUIRE(flow_out, "eraft_forward_stream: flow_out is NULL");
         for (int p = 0; p < P; ++p) EEM_REQUIRE(flow_out[p], "eraft_forward_stream: NULL output for pair %d", p);
@@ -1197,12 +1146,11 @@ extern "C" int eraft_forward_stream(eraft_ctx* c, int nvol, const float* const* 
     EEM_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t g = (size_t)(hp / 8) * (wp / 8), img = (size_t)c->cin0 * hp * wp;
-    int rc;
     if ((rc = devbuf_ensure(c->carry_pad, img)) != EEM_OK || (rc = devbuf_ensure(c->carry_fmap, 256 * g)) != EEM_OK ||
         (rc = devbuf_ensure(c->carry_flow, 2 * g)) != EEM_OK) return rc;
     const bool warm = warm_start != 0;
-    StreamPlan sp{volumes, nvol, c->carry_on, warm, warm && c->carry_on && c->carry_has_flow ? c->carry_flow.p : nullptr, flow_out};
-    c->carry_on = false;                                                 // (a failed call leaves no carry behind)
+    StreamPlan sp{volumes, nvol, carried, warm, warm && carried && c->carry_has_flow ? c->carry_flow.p : nullptr, flow_out};
+    c->stream.clear();                                                   // (a failed call leaves no carry behind)
     const int nout = c->final_only ? 1 : iters;
     const size_t per = (size_t)2 * in_h * in_w;
     if (P > 0 && !warm && (rc = devbuf_ensure(c->many_out, (size_t)nout * P * per)) != EEM_OK) return rc;
@@ -1217,23 +1165,20 @@ extern "C" int eraft_forward_stream(eraft_ctx* c, int nvol, const float* const* 
     EEM_HIP_CHECK(hipMemcpyAsync(c->carry_fmap.p, c->fmap.p + (size_t)P * 256 * g, 256 * g * 4, hipMemcpyDeviceToDevice, st));
     if (P > 0) EEM_HIP_CHECK(hipMemcpyAsync(c->carry_flow.p, c->sflow.p + (size_t)(P - 1) * 2 * g, 2 * g * 4, hipMemcpyDeviceToDevice, st));
     c->carry_has_flow = P > 0;
-    c->carry_on = true;
-    c->carry_h = in_h; c->carry_w = in_w;
-    memcpy(c->carry_padv, pad, sizeof(c->carry_padv));
-    c->carry_wver = c->wver;
+    c->stream.take(in_h, in_w, pad, 0, c->wver);
     return EEM_OK;
 }
 
 extern "C" int eraft_stream_reset(eraft_ctx* c) {
     EEM_REQUIRE(c, "eraft_stream_reset: NULL context");
-    c->carry_on = false;
+    c->stream.clear();
     c->carry_has_flow = false;
     return EEM_OK;
 }
 
 extern "C" int eraft_stream_pending(eraft_ctx* c, int* out) {
     EEM_REQUIRE(c && out, "eraft_stream_pending: NULL argument");
-    *out = c->carry_on ? 1 : 0;
+    *out = c->stream.on ? 1 : 0;
     return EEM_OK;
 }
 
@@ -1248,19 +1193,8 @@ extern "C" int eraft_keep_stages(eraft_ctx* c, int enable) {
 extern "C" int eraft_record_stages(eraft_ctx* c, const char* prefixes, int iterations) {
     EEM_REQUIRE(c, "eraft_record_stages: NULL context");
     EEM_REQUIRE(prefixes == nullptr || iterations >= 0, "eraft_record_stages: iterations = %d", iterations);
-    c->rec_prefix.clear();
-    c->rec_on = prefixes != nullptr;
+    c->rec.set_prefixes(prefixes);                                       // (the last forward's records stay until the next call)
     c->rec_iters = prefixes ? iterations : 0;
-    if (prefixes) {
-        const std::string all(prefixes);
-        size_t i = 0;
-        while (i <= all.size()) {
-            size_t j = all.find(',', i);
-            if (j == std::string::npos) j = all.size();
-            c->rec_prefix.push_back(all.substr(i, j - i));                   // (an empty prefix matches every name)
-            i = j + 1;
-        }
-    }
     return EEM_OK;
 }
 
@@ -1273,17 +1207,7 @@ extern "C" int eraft_last_form(char* buf, int cap) {
 
 extern "C" int eraft_stage_list(eraft_ctx* c, char* buf, size_t cap, size_t* need) {
     EEM_REQUIRE(c && need, "eraft_stage_list: NULL argument");
-    std::string s;
-    for (const StageRec& r : c->rec) {
-        char line[160];
-        snprintf(line, sizeof(line), "%s %s %d %d %d %d\n", r.name.c_str(), r.form.empty() ? "-" : r.form.c_str(), r.dims[0], r.dims[1], r.dims[2], r.dims[3]);
-        s += line;
-    }
-    *need = s.size() + 1;
-    if (buf == nullptr) return EEM_OK;
-    EEM_REQUIRE(cap >= s.size() + 1, "eraft_stage_list: the list needs %zu bytes, the buffer holds %zu", s.size() + 1, cap);
-    memcpy(buf, s.c_str(), s.size() + 1);
-    return EEM_OK;
+    return c->rec.list_into("eraft_stage_list", buf, cap, need);
 }
 
 // The evaluation loop reads flow_list[-1] only (test_mvsec.py:1455): with this switch the forward writes that one prediction.
@@ -1327,15 +1251,8 @@ extern "C" int eraft_get_stage(eraft_ctx* c, const char* name, float* dst, size_
         EEM_REQUIRE(!c->alt_corr && c->pyr[l].p, "eraft_get_stage: '%s' does not exist - the last forward computed the correlation on the fly", name);
         src = c->pyr[l].p; dims[0] = c->B * c->h8 * c->w8; dims[1] = 1; dims[2] = c->ph[l]; dims[3] = c->pw[l];
     } else {
-        const StageRec* hit = nullptr;                                       // a name of the stage recorder (eraft_record_stages)
-        for (const StageRec& r : c->rec)
-            if (r.name == nm) { hit = &r; break; }
-        if (!hit) {
-            eem_set_error("eraft_get_stage: unknown stage '%s'", name);
-            return EEM_ERR_ARG;
-        }
-        src = c->rec_buf.p + hit->off;
-        for (int i = 0; i < 4; ++i) dims[i] = hit->dims[i];
+        src = c->rec.lookup(name, dims);                                     // a name of the stage recorder (eraft_record_stages)
+        EEM_REQUIRE(src, "eraft_get_stage: unknown stage '%s'", name);
     }
     const size_t n = (size_t)dims[0] * dims[1] * dims[2] * dims[3];
     if (dst == nullptr) return EEM_OK;
@@ -1354,19 +1271,15 @@ extern "C" int eraft_corr_lookup(eraft_ctx* c, const float* fmap1, const float* 
     EEM_REQUIRE(c && fmap1 && fmap2 && coords && out, "eraft_corr_lookup: NULL argument");
     EEM_HIP_CHECK(hipSetDevice(c->device));
     int rc;
-    c->rec.clear();
-    c->rec_used = 0;
-    if (c->rec_on) {                                                     // the recorder: "pyr0" .. "pyr3" and "corr", each with the form that ran
-        size_t need = (size_t)batch * 324 * h * w + 64 * 5;
-        for (int l = 0, ph = h, pw = w; l < 4; ++l, ph /= 2, pw /= 2) need += (size_t)batch * h * w * ph * pw;
-        if ((rc = devbuf_ensure(c->rec_buf, need)) != EEM_OK) return rc;
-    }
-    rc = build_pyramid(c, fmap1, fmap2, batch, ch, h, w, (hipStream_t)stream, c->rec_on);
+    size_t need = (size_t)batch * 324 * h * w + 64 * 5;                  // the recorder: "pyr0" .. "pyr3" and "corr", each with the form that ran
+    for (int l = 0, ph = h, pw = w; l < 4; ++l, ph /= 2, pw /= 2) need += (size_t)batch * h * w * ph * pw;
+    if ((rc = c->rec.begin_call(c->rec.on, need)) != EEM_OK) return rc;
+    rc = build_pyramid(c, fmap1, fmap2, batch, ch, h, w, (hipStream_t)stream, c->rec.on);
     if (rc != EEM_OK) return rc;
     c->B = batch; c->h8 = h; c->w8 = w; c->have_last = true;
     c->stream_pairs = 0; c->fmap_imgs = 2 * batch;
     if ((rc = run_lookup(c, coords, out, 324, batch, h, w, (hipStream_t)stream)) != EEM_OK) return rc;
-    if (c->rec_on) rc = rec_stage(c, "corr", er_last_form, out, batch, 324, h, w, (hipStream_t)stream);
+    if (c->rec.on) rc = c->rec.stage("corr", er_last_form, out, batch, 324, h, w, (hipStream_t)stream);
     return rc;
 }
 

@@ -32,19 +32,11 @@ struct PLayer {
     int cin = 0, cout = 0, k = 3, stride = 1;
 };
 
-const int kTaps[53] = {0,  2,  4,  6,  8,  10, 12, 14, 16, 18, 20, 21, 22, 23, 24, 26, 28, 29, 30, 31, 32, 33, 34, 36, 38, 39, 40,
-                       41, 42, 44, 46, 47, 48, 49, 50, 51, 52, 54, 56, 57, 58, 59, 60, 62, 64, 66, 68, 70, 72, 74, 76, 78, 80};
 constexpr int kDW = 96, kDIn = 87, kDense = 184;
 // The decoder input [53 correlation taps | 32 rconv | 2 flow] lives in a 96-channel buffer and dec1 is packed as 96 -> 96 with zero
 // weights for the nine spare channels: 16-aligned, it runs on the LDS-tiled kernel (180 x 320: 170 -> 118 us).  The spare channels hold
 // whatever a coarser level left there (finite activations; the buffer is zeroed when allocated), times zero.
 constexpr int kCat = 96;
-
-struct PlusStageRec {            // one recorded launch output: [dims] floats at rec_buf + off
-    std::string name, form;
-    int dims[4];
-    size_t off;
-};
 
 }  // namespace
 
@@ -81,17 +73,13 @@ struct eemplus_ctx {
     // eemplus_forward_stream: levels 2..6 of its windows, one image per window, image 0 the window carried in.  forward / forward_many
     // leave these alone; the carried window sits in image carry_slot until the next stream call moves it to image 0
     DevBuf sf[7];
-    bool carry_on = false;
-    int carry_slot = 0, carry_h = 0, carry_w = 0, carry_pad[4] = {0, 0, 0, 0}, carry_cin = 0;
-    unsigned long carry_wver = 0;
-    // eemplus_record_stages (the fp64 stage tests): a device copy of every launch's output whose name starts with one of `rec_prefix`,
+    StreamCarry stream;
+    int carry_slot = 0;
+    // eemplus_record_stages (the fp64 stage tests): a device copy of every launch's output whose name starts with one of the prefixes,
     // made behind the launch on the launch's own stream and filed with the kernel form that wrote it.  rec_live: this call records
     // (the recorder is on and the call is not eemplus_forward_stream); every call site tests it first and does nothing else when off.
-    bool rec_on = false, rec_live = false;
-    std::vector<std::string> rec_prefix;
-    std::vector<PlusStageRec> rec;
-    DevBuf rec_buf;
-    size_t rec_used = 0, rec_need = 0;
+    DevStageRecorder rec;
+    bool rec_live = false;
     const char* form = "";               // the form of the launch conv() made last (whichever launch function it went to)
 };
 
@@ -191,26 +179,16 @@ bool conv_wnc_args(eemplus_ctx* c, const PLayer& L, const float* in, int in_ctot
     return wnc_supported(a);
 }
 
-// The stage recorder (eemplus_ctx::rec_live): `src` is [n][src_ctotal][h * w], of which the channels [src_coff, src_coff + ch) are copied
-// on `st`, the stream of the launch that has just written them.  It launches no kernel; with the recorder off no call site gets here.
+// a launch form as it is reported: the tail launch just made with its job count, "tail_..._j<jobs>"
+std::string reported_form(const char* form) {
+    std::string f(form ? form : "");
+    if (f.compare(0, 5, "tail_") == 0) f += "_j" + std::to_string(eem_launch_jobs);
+    return f;
+}
+// The stage recorder (eemplus_ctx::rec_live; with the recorder off no call site gets here): the launch just made, see DevStageRecorder::stage
 int rec_stage(eemplus_ctx* c, const char* name, const char* form, const float* src, int n, int ch, int h, int w, hipStream_t st,
               int src_ctotal = 0, int src_coff = 0) {
-    bool wanted = false;
-    for (const std::string& p : c->rec_prefix) wanted = wanted || strncmp(name, p.c_str(), p.size()) == 0;
-    if (!wanted) return EEM_OK;
-    const size_t hw = (size_t)h * w, cnt = (size_t)n * ch * hw, off = c->rec_used;
-    c->rec_used += (cnt + 63) & ~(size_t)63;
-    if (c->rec_used > c->rec_buf.cap) return EEM_OK;                     // measured only: the forward runs again with the arena grown
-    float* dst = c->rec_buf.p + off;
-    if (src_ctotal == 0 || src_ctotal == ch)
-        EEM_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * 4, hipMemcpyDeviceToDevice, st));
-    else
-        EEM_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)ch * hw * 4, src + (size_t)src_coff * hw, (size_t)src_ctotal * hw * 4, (size_t)ch * hw * 4, n,
-                                       hipMemcpyDeviceToDevice, st));
-    std::string f(form ? form : "");
-    if (f.compare(0, 5, "tail_") == 0) f += "_j" + std::to_string(eem_launch_jobs);      // (the tail launch just made: its job count)
-    c->rec.push_back(PlusStageRec{name, f, {n, ch, h, w}, off});
-    return EEM_OK;
+    return c->rec.stage(name, reported_form(form).c_str(), src, n, ch, h, w, st, src_ctotal, src_coff);
 }
 // a level's stage: "l<level>.<what>"
 int rec_level(eemplus_ctx* c, int l, const char* what, const char* form, const float* src, int n, int ch, int h, int w, hipStream_t st,
@@ -385,17 +363,12 @@ int run_decoder(eemplus_ctx* c, int l, int B, int h, int w, const float* residua
 
 extern "C" int eemplus_create(int device, eemplus_ctx** out) {
     EEM_REQUIRE(out != nullptr, "eemplus_create: out is NULL");
-    int ndev = 0;
-    EEM_HIP_CHECK(hipGetDeviceCount(&ndev));
-    EEM_REQUIRE(device >= 0 && device < ndev, "eemplus_create: device %d of %d", device, ndev);
-    EEM_HIP_CHECK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    EEM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
-    EEM_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0, "built for gfx950 (MI355X) only; device %d is %s", device, prop.gcnArchName);
+    const int rc = ctx_open_device("eemplus_create", device);
+    if (rc != EEM_OK) return rc;
     eemplus_ctx* c = new eemplus_ctx();
     c->device = device;
-    hipError_t e = hipMalloc(&c->taps, sizeof(kTaps));
-    if (e == hipSuccess) e = hipMemcpy(c->taps, kTaps, sizeof(kTaps), hipMemcpyHostToDevice);
+    hipError_t e = hipMalloc(&c->taps, sizeof(kTaps53));
+    if (e == hipSuccess) e = hipMemcpy(c->taps, kTaps53, sizeof(kTaps53), hipMemcpyHostToDevice);
     if (e != hipSuccess) { eem_set_error("eemplus_create: %s", hipGetErrorString(e)); delete c; return EEM_ERR_HIP; }
     *out = c;
     return EEM_OK;
@@ -404,27 +377,12 @@ extern "C" int eemplus_create(int device, eemplus_ctx** out) {
 extern "C" void eemplus_destroy(eemplus_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    DevBuf* one[] = {&c->padded, &c->a2, &c->dense, &c->xout, &c->tw, &c->fw, &c->cat, &c->t64, &c->t32,
-                   &c->d[0], &c->d[1], &c->d[2], &c->d[3]};
-    for (DevBuf* b : one) if (b->p) (void)hipFree(b->p);
     if (c->side) {
         (void)hipStreamSynchronize(c->side);
         (void)hipStreamDestroy(c->side);
         (void)hipEventDestroy(c->ev_fork);
         for (hipEvent_t e : c->ev_lvl) if (e) (void)hipEventDestroy(e);
     }
-    for (int l = 0; l < 7; ++l) {
-        if (c->dense_l[l].p) (void)hipFree(c->dense_l[l].p);
-        if (c->a2_l[l].p) (void)hipFree(c->a2_l[l].p);
-        if (c->cat_l[l].p) (void)hipFree(c->cat_l[l].p);
-        if (c->f[l].p) (void)hipFree(c->f[l].p);
-        if (c->sf[l].p) (void)hipFree(c->sf[l].p);
-        if (c->fup[l].p) (void)hipFree(c->fup[l].p);
-        if (c->finit[l].p) (void)hipFree(c->finit[l].p);
-        if (c->flow[l].p) (void)hipFree(c->flow[l].p);
-        if (c->flow_alt[l].p) (void)hipFree(c->flow_alt[l].p);
-    }
-    if (c->rec_buf.p) (void)hipFree(c->rec_buf.p);
     if (c->arena) (void)hipFree(c->arena);
     if (c->wino) (void)hipFree(c->wino);
     if (c->taps) (void)hipFree(c->taps);
@@ -689,15 +647,14 @@ static int stream_pyramid(eemplus_ctx* c, int nimg, bool carried, hipStream_t st
         need[l] = (size_t)nimg * C[l] * c->hl[l] * c->wl[l];
         grow = grow || need[l] > c->sf[l].cap;
     }
-    DevBuf old[7];
+    DevBuf old[7];                                               // (what is still in here on the way out is freed)
     if (grow) {
         for (int l = 2; l <= 6; ++l) {
-            old[l] = c->sf[l];
-            c->sf[l] = DevBuf();
+            old[l] = std::move(c->sf[l]);
             const size_t cap = need[l] > old[l].cap ? need[l] : old[l].cap;
             hipError_t e = hipMalloc(&c->sf[l].p, cap * sizeof(float));
             if (e != hipSuccess) {                               // (levels 2 .. l hold new buffers: back to the old ones)
-                for (int k = 2; k <= l; ++k) { if (c->sf[k].p) (void)hipFree(c->sf[k].p); c->sf[k] = old[k]; }
+                for (int k = 2; k <= l; ++k) c->sf[k] = std::move(old[k]);
                 eem_set_error("eemplus_forward_stream: %s", hipGetErrorString(e));
                 return EEM_ERR_HIP;
             }
@@ -716,10 +673,7 @@ static int stream_pyramid(eemplus_ctx* c, int nimg, bool carried, hipStream_t st
         const int rc = pl_carry_launch(J, st);
         if (rc != EEM_OK) return rc;
     }
-    if (grow) {
-        EEM_HIP_CHECK(hipStreamSynchronize(st));
-        for (int l = 2; l <= 6; ++l) if (old[l].p) EEM_HIP_CHECK(hipFree(old[l].p));
-    }
+    if (grow) EEM_HIP_CHECK(hipStreamSynchronize(st));          // (the move is through: the old buffers go with `old`)
     c->carry_slot = 0;
     return EEM_OK;
 }
@@ -730,10 +684,8 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
     const int B = batch, n2 = sp ? sp->nvol : 2 * batch, hp = in_h + pad[2] + pad[3], wp = in_w + pad[0] + pad[1];
     int rc;
     // the stage recorder: the arena the forward before measured (a forward whose records do not fit is run again by the caller)
-    c->rec_live = c->rec_on && !sp;
-    c->rec.clear();
-    c->rec_used = 0;
-    if (c->rec_live && (rc = devbuf_ensure(c->rec_buf, c->rec_need)) != EEM_OK) return rc;
+    c->rec_live = c->rec.on && !sp;
+    if ((rc = c->rec.begin_call(c->rec_live, c->rec.need)) != EEM_OK) return rc;
     // ---- pad, encoder on both volumes (EEMFlow+.py:162-169); the stream: on its new windows (n2 = nvol images)
     if ((rc = devbuf_ensure(c->padded, (size_t)n2 * c->cin0 * hp * wp)) != EEM_OK) return rc;
     if (sp) {
@@ -878,7 +830,7 @@ static int plus_forward_impl(eemplus_ctx* c, const float* e1, const float* e2, c
             if ((rc = rec_stage(c, name, eem_launch_form, outs[0], 5 * (frames ? 1 : B), 2, in_h, in_w, st)) != EEM_OK) return rc;
         }
     }
-    if (c->rec_live) c->rec_need = c->rec_need > c->rec_used ? c->rec_need : c->rec_used;
+    if (c->rec_live) c->rec.end();
     c->B = B; c->have_last = true;
     return EEM_OK;
 }
@@ -891,7 +843,7 @@ extern "C" int eemplus_forward(eemplus_ctx* c, const float* e1, const float* e2,
     EEM_HIP_CHECK(hipSetDevice(c->device));
     int rc = plus_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, out, nullptr, (hipStream_t)stream);
     // the stage recorder's arena was too small: that forward measured it; the same forward again, with the arena grown, fills it
-    if (rc == EEM_OK && c->rec_on && c->rec_used > c->rec_buf.cap)
+    if (rc == EEM_OK && c->rec.rerun())
         rc = plus_forward_impl(c, e1, e2, nullptr, nullptr, 0, batch, in_h, in_w, pad, out, nullptr, (hipStream_t)stream);
     return rc;
 }
@@ -907,7 +859,7 @@ extern "C" int eemplus_forward_many(eemplus_ctx* c, int n, const float* const* e
     for (int i = 0; i < n; ++i) EEM_REQUIRE(events1[i] && events2[i] && flow_out[i], "eemplus_forward_many: NULL pointer for sample %d", i);
     EEM_HIP_CHECK(hipSetDevice(c->device));
     int rc = plus_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream);
-    if (rc == EEM_OK && c->rec_on && c->rec_used > c->rec_buf.cap)            // (the recorder's arena has grown: see eemplus_forward)
+    if (rc == EEM_OK && c->rec.rerun())                                       // (the recorder's arena has grown: see eemplus_forward)
         rc = plus_forward_impl(c, nullptr, nullptr, events1, events2, n, n, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream);
     return rc;
 }
@@ -921,44 +873,34 @@ extern "C" int eemplus_forward_stream(eemplus_ctx* c, int n, const float* const*
     EEM_REQUIRE(n >= 1 && n <= EEM_STREAM_MAX_VOLUMES && in_h >= 1 && in_w >= 1, "eemplus_forward_stream: n = %d (1..%d) windows of %dx%d", n,
                 EEM_STREAM_MAX_VOLUMES, in_h, in_w);
     for (int j = 0; j < n; ++j) EEM_REQUIRE(volumes[j], "eemplus_forward_stream: NULL pointer for window %d", j);
-    if (c->carry_on) {
-        EEM_REQUIRE(c->carry_wver == c->wver && c->carry_cin == c->cin0, "eemplus_forward_stream: the weights changed since the carried window "
-                    "was encoded; call eemplus_stream_reset to start a new stream");
-        EEM_REQUIRE(c->carry_h == in_h && c->carry_w == in_w && memcmp(c->carry_pad, pad, sizeof(c->carry_pad)) == 0,
-                    "eemplus_forward_stream: the carried window is %dx%d (pad %d %d %d %d), this call's %dx%d (pad %d %d %d %d); call "
-                    "eemplus_stream_reset to start a new stream", c->carry_h, c->carry_w, c->carry_pad[0], c->carry_pad[1], c->carry_pad[2],
-                    c->carry_pad[3], in_h, in_w, pad[0], pad[1], pad[2], pad[3]);
-    }
-    const int P = c->carry_on ? n : n - 1;
+    int rc = stream_carry_check(c->stream, "eemplus_forward_stream", "eemplus", in_h, in_w, pad, c->cin0, c->wver);
+    if (rc != EEM_OK) return rc;
+    const int P = c->stream.pairs(n);
     EEM_REQUIRE(nflow == P, "eemplus_forward_stream: %d windows %s make %d pairs, nflow = %d", n,
-                c->carry_on ? "after the carried window" : "with no carried window", P, nflow);
+                c->stream.on ? "after the carried window" : "with no carried window", P, nflow);
     if (P > 0) {
         EEM_REQUIRE(flow_out, "eemplus_forward_stream: flow_out is NULL");
         for (int p = 0; p < P; ++p) EEM_REQUIRE(flow_out[p], "eemplus_forward_stream: NULL output for pair %d", p);
     }
     EEM_HIP_CHECK(hipSetDevice(c->device));
-    const PlusStream sp{volumes, n, c->carry_on};
-    c->carry_on = false;                                                 // (a call that fails from here on leaves no carry behind)
-    const int rc = plus_forward_impl(c, nullptr, nullptr, nullptr, nullptr, P, P, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream, &sp);
+    const PlusStream sp{volumes, n, c->stream.on};
+    c->stream.clear();                                                   // (a call that fails from here on leaves no carry behind)
+    rc = plus_forward_impl(c, nullptr, nullptr, nullptr, nullptr, P, P, in_h, in_w, pad, nullptr, flow_out, (hipStream_t)stream, &sp);
     if (rc != EEM_OK) return rc;
-    c->carry_on = true;
     c->carry_slot = P;                                                   // the last window: image P of the stream's pyramid
-    c->carry_h = in_h; c->carry_w = in_w;
-    memcpy(c->carry_pad, pad, sizeof(c->carry_pad));
-    c->carry_cin = c->cin0;
-    c->carry_wver = c->wver;
+    c->stream.take(in_h, in_w, pad, c->cin0, c->wver);
     return EEM_OK;
 }
 
 extern "C" int eemplus_stream_reset(eemplus_ctx* c) {
     EEM_REQUIRE(c, "eemplus_stream_reset: NULL context");
-    c->carry_on = false;
+    c->stream.clear();
     return EEM_OK;
 }
 
 extern "C" int eemplus_stream_pending(eemplus_ctx* c, int* out) {
     EEM_REQUIRE(c && out, "eemplus_stream_pending: NULL argument");
-    *out = c->carry_on ? 1 : 0;
+    *out = c->stream.on ? 1 : 0;
     return EEM_OK;
 }
 
@@ -971,42 +913,20 @@ extern "C" int eemplus_set_frames_in_flight(eemplus_ctx* c, int n) {
 // The stage recorder (include/eemflow_hip.h): prefixes = comma-separated name prefixes, NULL = off.
 extern "C" int eemplus_record_stages(eemplus_ctx* c, const char* prefixes) {
     EEM_REQUIRE(c, "eemplus_record_stages: NULL context");
-    c->rec_prefix.clear();
-    c->rec_on = prefixes != nullptr;
-    if (!c->rec_on) { c->rec_live = false; c->rec.clear(); }
-    if (prefixes) {
-        const std::string all(prefixes);
-        size_t i = 0;
-        while (i <= all.size()) {
-            size_t j = all.find(',', i);
-            if (j == std::string::npos) j = all.size();
-            c->rec_prefix.push_back(all.substr(i, j - i));                   // (an empty prefix matches every name)
-            i = j + 1;
-        }
-    }
+    c->rec.set_prefixes(prefixes);
+    if (!c->rec.on) { c->rec_live = false; c->rec.rec.clear(); }         // (switched off: the last call's records go at once)
     return EEM_OK;
 }
 
 extern "C" int eemplus_stage_list(eemplus_ctx* c, char* buf, size_t cap, size_t* need) {
     EEM_REQUIRE(c && need, "eemplus_stage_list: NULL argument");
-    std::string s;
-    for (const PlusStageRec& r : c->rec) {
-        char line[160];
-        snprintf(line, sizeof(line), "%s %s %d %d %d %d\n", r.name.c_str(), r.form.empty() ? "-" : r.form.c_str(), r.dims[0], r.dims[1], r.dims[2], r.dims[3]);
-        s += line;
-    }
-    *need = s.size() + 1;
-    if (buf == nullptr) return EEM_OK;
-    EEM_REQUIRE(cap >= s.size() + 1, "eemplus_stage_list: the list needs %zu bytes, the buffer holds %zu", s.size() + 1, cap);
-    memcpy(buf, s.c_str(), s.size() + 1);
-    return EEM_OK;
+    return c->rec.list_into("eemplus_stage_list", buf, cap, need);
 }
 
 // The form of this thread's last launch through the launch functions that report in eem_launch_form (eemplus_warp, eemplus_upsample_flow_as).
 extern "C" int eemplus_last_form(char* buf, int cap) {
     EEM_REQUIRE(buf && cap > 0, "eemplus_last_form: NULL buffer");
-    if (strncmp(eem_launch_form, "tail_", 5) == 0) snprintf(buf, (size_t)cap, "%s_j%d", eem_launch_form, eem_launch_jobs);
-    else snprintf(buf, (size_t)cap, "%s", eem_launch_form);
+    snprintf(buf, (size_t)cap, "%s", reported_form(eem_launch_form).c_str());
     return EEM_OK;
 }
 
@@ -1025,15 +945,8 @@ extern "C" int eemplus_get_stage(eemplus_ctx* c, const char* name, float* dst, s
         const int l = nm[9] - '0';
         src = c->finit[l].p; dims[0] = c->B; dims[1] = 2; dims[2] = c->hl[l]; dims[3] = c->wl[l];
     } else {
-        const PlusStageRec* hit = nullptr;                                   // a name of the stage recorder (eemplus_record_stages)
-        for (const PlusStageRec& r : c->rec)
-            if (r.name == nm) { hit = &r; break; }
-        if (!hit) {
-            eem_set_error("eemplus_get_stage: unknown stage '%s'", name);
-            return EEM_ERR_ARG;
-        }
-        src = c->rec_buf.p + hit->off;
-        for (int i = 0; i < 4; ++i) dims[i] = hit->dims[i];
+        src = c->rec.lookup(name, dims);                                     // a name of the stage recorder (eemplus_record_stages)
+        EEM_REQUIRE(src, "eemplus_get_stage: unknown stage '%s'", name);
     }
     const size_t n = (size_t)dims[0] * dims[1] * dims[2] * dims[3];
     if (dst == nullptr) return EEM_OK;
@@ -1053,10 +966,8 @@ extern "C" int eemplus_level(eemplus_ctx* c, int level, const float* flow_init, 
     hipStream_t st = (hipStream_t)stream;
     int rc;
     // the stage recorder: this level's launches alone, "l<level>." (a level files fewer than 1024 channels of its map)
-    c->rec_live = c->rec_on;
-    c->rec.clear();
-    c->rec_used = 0;
-    if (c->rec_live && (rc = devbuf_ensure(c->rec_buf, (size_t)c->B * 1024 * c->hl[level] * c->wl[level] + 64 * 64)) != EEM_OK) return rc;
+    c->rec_live = c->rec.on;
+    if ((rc = c->rec.begin_call(c->rec_live, (size_t)c->B * 1024 * c->hl[level] * c->wl[level] + 64 * 64)) != EEM_OK) return rc;
     if ((rc = run_level(c, level, c->B, flow_init, st, false)) != EEM_OK) return rc;
     const size_t n = (size_t)c->B * 2 * c->hl[level] * c->wl[level] * sizeof(float);
     if (flow_up_out) EEM_HIP_CHECK(hipMemcpyAsync(flow_up_out, c->fup[level].p, n, hipMemcpyDeviceToDevice, st));

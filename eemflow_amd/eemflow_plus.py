@@ -133,19 +133,6 @@ class EEMFlow_cdc(HipModel, nn.Module):  # noqa: N801
             self._recorder_set = (self._ctx.value, want)
         _lib.check(L.eemplus_set_frames_in_flight(self._ctx, max(1, int(self.frames_in_flight))))
 
-    def stage_names(self):
-        """[(name, form, (n, c, h, w))] of everything the stage recorder (`record_stages`) filed in the last call, in launch order."""
-        L = _lib.lib()
-        need = ctypes.c_size_t()
-        _lib.check(L.eemplus_stage_list(self._ctx, None, 0, ctypes.byref(need)))
-        buf = ctypes.create_string_buffer(need.value)
-        _lib.check(L.eemplus_stage_list(self._ctx, buf, need.value, ctypes.byref(need)))
-        out = []
-        for line in buf.value.decode().splitlines():
-            name, form, *dims = line.split()
-            out.append((name, "" if form == "-" else form, tuple(int(d) for d in dims)))
-        return out
-
     def forward(self, events1, events2):
         self._require_cuda("forward", events1, events2)
         if not hasattr(self, "image_padder"):

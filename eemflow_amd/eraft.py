@@ -235,19 +235,6 @@ class ERAFT(HipModel, nn.Module):
                                                 _lib.current_stream_ptr(e1.device)))
         return (events1, events2), [out[i] for i in range(nout)]
 
-    def stage_names(self):
-        """[(name, form, (n, c, h, w))] of everything the stage recorder (`record_stages`) filed in the last forward, in launch order."""
-        L = _lib.lib()
-        need = ctypes.c_size_t()
-        _lib.check(L.eraft_stage_list(self._ctx, None, 0, ctypes.byref(need)))
-        buf = ctypes.create_string_buffer(need.value)
-        _lib.check(L.eraft_stage_list(self._ctx, buf, need.value, ctypes.byref(need)))
-        out = []
-        for line in buf.value.decode().splitlines():
-            name, form, *dims = line.split()
-            out.append((name, "" if form == "-" else form, tuple(int(d) for d in dims)))
-        return out
-
     def forward_many(self, frames, iters=12):
         """Several INDEPENDENT samples of the evaluation loop (test_mvsec.py:580-597: one `model(events1, events2)` per sample at batch 1)
         as one batch-n forward, each sample staying in its own tensors: `frames` is a sequence of (events1, events2) pairs of [1, C, H, W]

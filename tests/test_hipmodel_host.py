@@ -4,6 +4,7 @@ window of forward_stream, replicate and change_imagesize, through a stand-in for
 Only public methods and the fields other modules rely on (_ctx, _ctx_device, _weights_version, _stream_prev, _context, _release) are
 used, so the file describes the wrappers' behaviour independently of how they are written."""
 import contextlib
+import ctypes
 import gc
 import os
 import re
@@ -243,6 +244,33 @@ def test_what_only_eemflow_can_do():
     for name in ("MAX_STREAM_BIDIR", "invalidate_weights"):
         assert hasattr(EEMFlow, name)
         assert not hasattr(EEMFlow_cdc, name) and not hasattr(ERAFT, name)
+
+
+def test_stage_names_is_shared():
+    """The recorder's list is read in one place, through the model's own <prefix>_stage_list."""
+    from eemflow_amd._hipmodel import HipModel
+    assert "stage_names" in vars(HipModel)
+    assert "stage_names" not in vars(ERAFT) and "stage_names" not in vars(EEMFlow_cdc)
+    pkg = os.path.dirname(_lib.__file__)
+    for name in ("eraft.py", "eemflow_plus.py"):
+        assert "stage_list" not in open(os.path.join(pkg, name), encoding="utf-8").read(), name
+
+
+@pytest.mark.parametrize("kind", ["eemplus", "eraft"])
+def test_stage_names_parses_the_list(rig, kind, monkeypatch):
+    lib, make = rig
+    net = make(kind)
+    net._context(CPU)
+    text = b"pad pad 2 5 64 64\nl6.cat_flow - 1 2 1 1\n\x00"
+
+    def stage_list(ctx, buf, cap, need):
+        need._obj.value = len(text)
+        if buf is not None:
+            assert cap == len(text)
+            ctypes.memmove(buf, text, len(text))
+        return 0
+    monkeypatch.setattr(lib, f"{kind}_stage_list", stage_list, raising=False)
+    assert net.stage_names() == [("pad", "pad", (2, 5, 64, 64)), ("l6.cat_flow", "", (1, 2, 1, 1))]
 
 
 def test_stream_limits_match_the_header():
