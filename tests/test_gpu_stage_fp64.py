@@ -14,12 +14,14 @@ Sizes (input -> padded -> 1/2, 1/4, 1/8): 260x346 -> 320x384 -> 160x192 / 80x96 
 2.5 tile rows at 1/8, replicate padding 19 px left and right); 480x640 -> 512x640 (2.5 tiles wide at 1/2); 130x70 -> 192x128 (24x16
 at 1/8); 64x64 (8x8 at 1/8: smaller than any tile); 720x1280 (headline, a few cases).
 
-Left out, and why: the stride-2 and fused / deferred first-layer forms at batch > 1 (their tile walk does not depend on the batch:
-the walk and in-flight grids are those of the stride-1 kernels, checked at batch 3, 4, 10 and 16); F(2x2) and the direct forms at
-720x1280 (the same tiles as at 480x640, whose width is not a tile multiple); every image of the 720x1280 batches (the fp64 references
-cost ~1 s per image there: the first and the last frame are checked); `forward_stream`'s own stages (after a stream call the
-workspace holds windows, not pairs, and eemflow_get_stage refuses - its flows are compared bitwise with a forward_many whose stages are
-all checked here).
+Left out, and why: the stride-2 and fused / deferred first-layer forms at batch > 1 (the stride-2 kernels take one tile per block at
+any batch; pconv1_1's contiguous ranges and the stride-1 kernels' interleaved walk DO depend on the batch and on the in-flight grids -
+tests/test_tile_walk_host.py proves the dealing on the host, tests/test_gpu_walk_batched.py runs the batches and settings at which
+blocks take two, three and four tiles; this module's batches 3, 4, 10 and 16 give the interleaved walk one tile per block except at
+720x1280); F(2x2) and the direct forms at 720x1280 (the same tiles as at 480x640, whose width is not a tile multiple); every image of
+the 720x1280 batches (the fp64 references cost ~1 s per image there: the first and the last frame are checked); `forward_stream`'s
+own stages (after a stream call the workspace holds windows, not pairs, and eemflow_get_stage refuses - its flows are compared
+bitwise with a forward_many whose stages are all checked here).
 
 Measured on an MI355X (seeds as committed, bitwise repeatable; the worst value over all cases of the family -> the limit in
 oracle/fp64_bounds.py):
@@ -96,8 +98,9 @@ def pin(monkeypatch, env):
         monkeypatch.setenv(k, v)
 
 
-def launches(net, e1, e2):
-    """(name, pipe) of every launch of a forward of this batch in the module's configuration (eemflow_time_kernels, one pass)."""
+def launches(net, e1, e2, blocks=False):
+    """(name, pipe) of every launch of a forward of this batch in the module's configuration (eemflow_time_kernels, one pass);
+    blocks=True: (name, pipe, blocks of the launch's grid)."""
     b, _, h, w = e1.shape
     out = torch.empty(b, 2, h, w, device=DEV)
     st = (_lib.KernelStat * 128)()
@@ -106,7 +109,7 @@ def launches(net, e1, e2):
     _lib.check(_lib.lib().eemflow_time_kernels(ctx, e1.data_ptr(), e2.data_ptr(), b, h, w, out.data_ptr(), h, w, 1, st, 128,
                                                ctypes.byref(n), _lib.current_stream_ptr(e1.device)))
     torch.cuda.synchronize()
-    return [(st[i].name.decode(), st[i].pipe) for i in range(n.value)]
+    return [(st[i].name.decode(), st[i].pipe) + ((st[i].blocks,) if blocks else ()) for i in range(n.value)]
 
 
 def assert_forms(ks, forms, env, gw, batch):
