@@ -139,12 +139,18 @@ _SIGNATURES = {
     "eemflow_voxelize_windows": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
                                                 ctypes.c_double, ctypes.c_double] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_void_p),
                                                 ctypes.c_void_p]),
+    "eemflow_voxelize_spans": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_int64), ctypes.c_double, ctypes.c_double] + [ctypes.c_int] * 5 +
+                               [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "eemflow_gt_flow_many": (ctypes.c_int, [ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "eemflow_event_mask_windows": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                   ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                                   ctypes.c_void_p]),
+    "eemflow_event_mask_spans": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "eemflow_augment_many": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(AugPlanC), ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p, _c_float_p, _c_float_p,

@@ -166,9 +166,12 @@ def build_parser():
     r.add_argument('--device', default='cuda:0')
     r.add_argument('--window_ms', default=None, type=float, metavar='MS', help='cut by duration: windows of MS milliseconds from the first event')
     r.add_argument('--window_events', default=None, type=int, metavar='N', help='cut by count: windows of N events')
+    r.add_argument('--stride_ms', default=None, type=float, metavar='MS', help='with --window_ms: a window starts every MS milliseconds (MS divides the window); '
+                                                                               'pair m runs from window m to window m + window/stride, the one that starts where it ends')
+    r.add_argument('--stride_events', default=None, type=int, metavar='N', help='with --window_events: a window starts every N events (N divides the window)')
     r.add_argument('--t_unit', default='ns', choices=('ns', 'us', 's'), help='unit of the t array (HREM: ns)')
     r.add_argument('--stream', default=0, type=int, metavar='N', help='windows per forward_stream call (default: as many as the model takes)')
-    r.add_argument('--out', default=None, metavar='DIR', help='write the flow of pair k (window k -> window k + 1) as DIR/%%06d.flo')
+    r.add_argument('--out', default=None, metavar='DIR', help='write the flow of pair k (window k -> window k + 1; with a stride, window k -> window k + window/stride) as DIR/%%06d.flo')
     r.add_argument('-v', '--visualize', action='store_true', help='with --out: also the colour-wheel image of every flow, DIR/%%06d_flow.jpg')
     r.add_argument('--fwl', action='store_true', help='the flow warp loss of every pair (the events of its first window under its flow) on its line, the mean in the summary')
     r.add_argument('--rsat', action='store_true', help='RSAT of every pair on its line, the mean in the summary')
@@ -186,7 +189,11 @@ def build_parser():
     m.add_argument('--device', default='cuda:0')
     m.add_argument('--first', default=None, type=int, metavar='I', help='first pair: grey frame I (default: the first frame the ground truth covers)')
     m.add_argument('--last', default=None, type=int, metavar='J', help='last pair starts at grey frame <= J (default: the last one the ground truth and the frames cover)')
-    m.add_argument('--dt', default=1, type=int, metavar='N', help='grey frames per window (consecutive windows; 1 = MvsecEventFlow\'s samples)')
+    m.add_argument('--dt', default=1, type=int, metavar='N', help='grey frames per window (consecutive windows unless --stride / --reference_pairs say otherwise; 1 = MvsecEventFlow\'s samples)')
+    m.add_argument('--stride', default=None, type=int, metavar='S', help='a window starts every S grey frames (S divides --dt; default --dt: consecutive windows); '
+                                                                         'pair m runs from window m to the window that starts where it ends')
+    m.add_argument('--reference_pairs', action='store_true', help='the samples of MvsecEventFlow_dt4 (--dt 4) / MvsecEventFlow (--dt 1): windows one grey frame '
+                                                                  'apart, ground truth over --dt frames')
     m.add_argument('--eval_type', default='dense', choices=('dense', 'sparse'), help='sparse: only pixels of the first window that hold an event')
     m.add_argument('--is_car', action='store_true', help='outdoor sequences: rows from 190 on are not scored')
     m.add_argument('--crop', nargs=2, type=int, default=None, metavar=('H', 'W'), help='centre crop of volumes, ground truth and mask (the dataset\'s validation branch: 256 256)')
@@ -400,6 +407,17 @@ def run(args):
         raise SystemExit("--window_ms MS: MS > 0")
     if args.window_events is not None and args.window_events < 1:
         raise SystemExit("--window_events N: N >= 1")
+    if (args.stride_ms is not None and args.window_ms is None) or (args.stride_events is not None and args.window_events is None):
+        raise SystemExit("run: --stride_ms MS goes with --window_ms, --stride_events N with --window_events")
+    lag = 1
+    if args.stride_ms is not None:
+        lag = int(round(args.window_ms / args.stride_ms)) if args.stride_ms > 0 else 0
+        if lag < 1 or abs(lag * args.stride_ms - args.window_ms) > 1e-9 * args.window_ms:
+            raise SystemExit(f"--stride_ms {args.stride_ms}: the stride is > 0 and divides --window_ms {args.window_ms}")
+    if args.stride_events is not None:
+        if args.stride_events < 1 or args.window_events % args.stride_events != 0:
+            raise SystemExit(f"--stride_events {args.stride_events}: the stride is >= 1 and divides --window_events {args.window_events}")
+        lag = args.window_events // args.stride_events
     if args.height < 1 or args.width < 1:
         raise SystemExit("--height H --width W: the sensor size, both >= 1")
     if args.visualize and not args.out:
@@ -421,14 +439,33 @@ def run(args):
     model = model.to(dev).eval()
     scale_a, per_ms = T_UNITS[args.t_unit]
     rec = EventRecording.from_npz(args.events, args.height, args.width, device=dev, scale_a=scale_a)
-    if args.window_ms is not None:
-        span = args.window_ms * per_ms
-        offsets = rec.window_offsets(window=int(span) if float(span).is_integer() else span)
+    def units(ms):                                                   # a duration in the units of the raw t column, an integer where it is one
+        span = ms * per_ms
+        return int(span) if float(span).is_integer() else span
+
+    sliding = args.stride_ms is not None or args.stride_events is not None
+    if sliding:                                                      # windows by span, pairs (m, m + lag)
+        if args.stride_ms is not None:
+            stride = units(args.stride_ms)
+            spans = rec.sliding_spans(window=stride * lag, stride=stride)
+        else:
+            spans = rec.sliding_spans(count=args.window_events, stride_count=args.stride_events)
+        offsets = None
+        nwin = len(spans)
+        counts = [int(b - a) for a, b in spans]
+        total = int(spans[-1][1] - spans[0][0]) if nwin else 0
+        windows_kw = dict(spans=spans, lag=lag)
     else:
-        offsets = rec.window_offsets(count=args.window_events)
-    nwin = len(offsets) - 1
-    if nwin < 2:
-        raise SystemExit(f"run: the recording's {rec.n} events give {nwin} full windows; a flow needs two")
+        if args.window_ms is not None:
+            offsets = rec.window_offsets(window=units(args.window_ms))
+        else:
+            offsets = rec.window_offsets(count=args.window_events)
+        nwin = len(offsets) - 1
+        counts = [int(offsets[k + 1] - offsets[k]) for k in range(nwin)]
+        total = int(offsets[-1] - offsets[0])
+        windows_kw = dict(offsets=offsets)
+    if nwin < lag + 1:
+        raise SystemExit(f"run: the recording's {rec.n} events give {nwin} full windows; a flow needs " + ("two" if lag == 1 else f"{lag + 1} at this stride"))
     limit = model.MAX_STREAM_BIDIR if args.fb_check is not None else model.MAX_STREAM
     if args.stream > limit:
         raise SystemExit(f"--stream {args.stream}: {args.model_name} takes at most {limit} windows per call" + (" with --fb_check" if args.fb_check is not None else ""))
@@ -443,9 +480,9 @@ def run(args):
     torch.cuda.synchronize(dev)
     start = time.perf_counter()
     try:
-        for item in harness.run_recording(model, rec, offsets, chunk=args.stream or None, fwl=args.fwl, rsat=args.rsat, fb_check=args.fb_check):
+        for item in harness.run_recording(model, rec, chunk=args.stream or None, fwl=args.fwl, rsat=args.rsat, fb_check=args.fb_check, **windows_kw):
             k = item['k']
-            line = 'pair {:6d}  events {:9d}'.format(k, int(offsets[k + 1] - offsets[k]))
+            line = 'pair {:6d}  events {:9d}'.format(k, counts[k])
             for key in ('FWL', 'RSAT'):
                 if key in item:
                     val = float(item[key])
@@ -469,19 +506,21 @@ def run(args):
             writer.close()
     wall = time.perf_counter() - start
     mean = {key: (v[0] / v[1] if v[1] else float('nan')) for key, v in sums.items()}
-    line = 'windows {}  events {}  pairs {}  {:.1f} frames/s'.format(nwin, int(offsets[-1] - offsets[0]), pairs, pairs / wall if wall > 0 else float('nan'))
+    line = 'windows {}  events {}  pairs {}  {:.1f} frames/s'.format(nwin, total, pairs, pairs / wall if wall > 0 else float('nan'))
     if args.fwl:
         line += '  meanFWL: {:2.6f}'.format(mean['FWL'])
     if args.rsat:
         line += '  meanRSAT: {:2.6f}'.format(mean['RSAT'])
     print(line)
-    return {'windows': nwin, 'events': int(offsets[-1] - offsets[0]), 'pairs': pairs, 'frames_per_s': pairs / wall if wall > 0 else float('nan'),
+    return {'windows': nwin, 'events': total, 'pairs': pairs, 'frames_per_s': pairs / wall if wall > 0 else float('nan'),
             'meanFWL': mean['FWL'] if args.fwl else None, 'meanRSAT': mean['RSAT'] if args.rsat else None}
 
 
-def mvsec_pair_range(image_raw_ts, n_frames, gt_ts, first, last, dt):
+def mvsec_pair_range(image_raw_ts, n_frames, gt_ts, first, last, dt, frames_needed=None, step=None):
     """The pairs --first / --last select, defaults filled in: a pair starting at grey frame i needs the frames i .. i + 2*dt (two windows)
-    and ground truth over [ts[i], ts[i + dt]].  Host only."""
+    and ground truth over [ts[i], ts[i + dt]].  frames_needed: the pair needs the frames i .. i + frames_needed instead (dt + 1 for
+    --reference_pairs, whose second window starts one frame after the first); step: pairs start every `step` frames from `first`
+    (default dt).  Host only."""
     import numpy as np
     from .mvsec_raw import plan_window
 
@@ -491,7 +530,8 @@ def mvsec_pair_range(image_raw_ts, n_frames, gt_ts, first, last, dt):
             return True
         except ValueError:
             return False
-    top = n_frames - 1 - 2 * dt                                      # the last frame a pair can start at
+    step = dt if step is None else int(step)
+    top = n_frames - 1 - (2 * dt if frames_needed is None else int(frames_needed))     # the last frame a pair can start at
     if top < 0:
         raise SystemExit(f"mvsec: {n_frames} grey frames give no pair of windows at --dt {dt}")
     if first is None:
@@ -502,7 +542,7 @@ def mvsec_pair_range(image_raw_ts, n_frames, gt_ts, first, last, dt):
             last -= 1
     if first < 0 or last < first or last > top:
         raise SystemExit(f"--first {first} --last {last}: pairs start at grey frames 0..{top} at --dt {dt}, first <= last")
-    for i in (first, first + (last - first) // dt * dt):
+    for i in (first, first + (last - first) // step * step):
         if not covered(i):
             raise SystemExit(f"mvsec: the ground truth ({gt_ts[0]:.6f} .. {gt_ts[-1]:.6f} s) does not cover the pair at grey frame {i} "
                              f"({image_raw_ts[i]:.6f} .. {image_raw_ts[i + dt]:.6f} s)")
@@ -514,6 +554,10 @@ def mvsec(args):
     import time
     if args.dt < 1:
         raise SystemExit("--dt N: N >= 1 grey frames per window")
+    if args.reference_pairs and args.stride not in (None, 1):
+        raise SystemExit("--reference_pairs: the windows are one grey frame apart; --stride does not apply")
+    if args.stride is not None and (args.stride < 1 or args.dt % args.stride != 0):
+        raise SystemExit(f"--stride {args.stride}: S >= 1 and S divides --dt {args.dt}")
     if args.height < 1 or args.width < 1:
         raise SystemExit("--height H --width W: the sensor size, both >= 1")
     if args.crop is not None and not (1 <= args.crop[0] <= args.height and 1 <= args.crop[1] <= args.width):
@@ -538,8 +582,21 @@ def mvsec(args):
     if args.stream > model.MAX_STREAM:
         raise SystemExit(f"--stream {args.stream}: {args.model_name} takes at most {model.MAX_STREAM} windows per call")
     raw = MvsecRaw.from_npz(args.data, args.gt, height=args.height, width=args.width, device=dev)
-    first, last = mvsec_pair_range(raw.image_raw_ts, raw.image_raw_ts.shape[0], raw.gt.ts, args.first, args.last, args.dt)
-    offsets, t_edges = raw.frame_windows(first, last, args.dt)
+    if args.reference_pairs or args.stride not in (None, args.dt):   # windows by span: overlapping, pairs at a lag
+        step = 1 if args.reference_pairs else args.stride
+        first, last = mvsec_pair_range(raw.image_raw_ts, raw.image_raw_ts.shape[0], raw.gt.ts, args.first, args.last, args.dt,
+                                       frames_needed=args.dt + 1 if args.reference_pairs else None, step=step)
+        spans, t_spans, lag = raw.frame_spans(first, last, args.dt, stride=step, reference_pairs=args.reference_pairs)
+        counts = [int(b - a) for a, b in spans]
+        total = int(spans[-1][1] - spans[0][0])
+        windows_kw = dict(spans=spans, lag=lag, t_spans=t_spans)
+    else:
+        step = args.dt
+        first, last = mvsec_pair_range(raw.image_raw_ts, raw.image_raw_ts.shape[0], raw.gt.ts, args.first, args.last, args.dt)
+        offsets, t_edges = raw.frame_windows(first, last, args.dt)
+        counts = [int(offsets[k + 1] - offsets[k]) for k in range(len(offsets) - 1)]
+        total = int(offsets[-1] - offsets[0])
+        windows_kw = dict(offsets=offsets, t_edges=t_edges)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     acc = {'aee': 0.0, 'p1': 0.0, 'p3': 0.0}
@@ -547,8 +604,8 @@ def mvsec(args):
     torch.cuda.synchronize(dev)
     start = time.perf_counter()
     with torch.no_grad():
-        for item in harness.run_recording(model, raw.recording, offsets, chunk=args.stream or None, gt=raw.gt, t_edges=t_edges, crop=args.crop,
-                                          eval_type=args.eval_type, is_car=args.is_car):
+        for item in harness.run_recording(model, raw.recording, chunk=args.stream or None, gt=raw.gt, crop=args.crop, eval_type=args.eval_type,
+                                          is_car=args.is_car, **windows_kw):
             k = item['k']
             aee, p1, p3 = flow_error_from_sums(item['err_sums'])[:3]
             p1, p3 = 1.0 - p1, 1.0 - p3                              # the outlier shares, as the evaluation loop's "1 - mean %AEE" / "3 - mean %AEE"
@@ -557,7 +614,7 @@ def mvsec(args):
             acc['p3'] += p3
             pairs += 1
             print('pair {:6d}  frame {:6d}  events {:9d}  AEE: {:2.6f}  %1px: {:.6f}  %3px: {:.6f}'.format(
-                k, first + k * args.dt, int(offsets[k + 1] - offsets[k]), aee, p1, p3))
+                k, first + k * step, counts[k], aee, p1, p3))
             if args.out:
                 write_flo(os.path.join(args.out, '%06d.flo' % k), item['flow'][0].permute(1, 2, 0).cpu().numpy())
                 write_flo(os.path.join(args.out, '%06d_gt.flo' % k), item['flow_gt'][0].permute(1, 2, 0).cpu().numpy())
@@ -565,8 +622,8 @@ def mvsec(args):
     wall = time.perf_counter() - start
     n = max(pairs, 1)
     print('pairs {}  events {}  Mean AEE: {:.6f}  mean %1px: {:.6f}  mean %3px: {:.6f}  {:.1f} frames/s'.format(
-        pairs, int(offsets[-1] - offsets[0]), acc['aee'] / n, acc['p1'] / n, acc['p3'] / n, pairs / wall if wall > 0 else float('nan')))
-    return {'pairs': pairs, 'events': int(offsets[-1] - offsets[0]), 'meanAEE': acc['aee'] / n, 'mean1px': acc['p1'] / n, 'mean3px': acc['p3'] / n,
+        pairs, total, acc['aee'] / n, acc['p1'] / n, acc['p3'] / n, pairs / wall if wall > 0 else float('nan')))
+    return {'pairs': pairs, 'events': total, 'meanAEE': acc['aee'] / n, 'mean1px': acc['p1'] / n, 'mean3px': acc['p3'] / n,
             'frames_per_s': pairs / wall if wall > 0 else float('nan')}
 
 

@@ -18,7 +18,7 @@
 // finite (the reference's border read), and leaves the mask of the non-finite one: the NaN (or infinity) stays in the output, where
 // cv2's conversion of a NaN coordinate to an integer is undefined.  More NaN than the reference, never less.
 //
-// eemflow_event_mask_windows: the event masks of the windows of a resident recording (mvsec.event_mask on each slice), read through
+// eemflow_event_mask_windows / eemflow_event_mask_spans: the event masks of the windows of a resident recording (mvsec.event_mask on each slice), read through
 // event_cols.h in the columns' own dtypes: a zero-fill launch, then plain stores of 1.0f (every racing store writes the same value).
 #include "event_cols.h"
 
@@ -124,28 +124,36 @@ extern "C" int eemflow_gt_flow_many(int njobs, const float* gt, int nframes, int
     return EEM_OK;
 }
 
-extern "C" int eemflow_event_mask_windows(int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* offsets, int h, int w,
-                                          float* const* masks, void* stream) {
-    EEM_REQUIRE(nwin >= 1 && nwin <= GT_MAX_JOBS, "eemflow_event_mask_windows: 1..%d windows per call; got %d", GT_MAX_JOBS, nwin);
-    EEM_REQUIRE(offsets && masks, "eemflow_event_mask_windows: NULL argument");
-    EEM_REQUIRE(h >= 1 && w >= 1, "eemflow_event_mask_windows: bad shape h=%d w=%d", h, w);
-    EEM_REQUIRE(offsets[0] >= 0, "eemflow_event_mask_windows: offsets[0] = %ld", (long)offsets[0]);
+namespace {
+
+// the body of eemflow_event_mask_windows (starts = offsets, ends = offsets + 1) and eemflow_event_mask_spans
+int mask_windows(const char* who, bool offsets, int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* starts,
+                 const int64_t* ends, int h, int w, float* const* masks, void* stream) {
+    EEM_REQUIRE(nwin >= 1 && nwin <= GT_MAX_JOBS, "%s: 1..%d windows per call; got %d", who, GT_MAX_JOBS, nwin);
+    EEM_REQUIRE(starts && ends && masks, "%s: NULL argument", who);
+    EEM_REQUIRE(h >= 1 && w >= 1, "%s: bad shape h=%d w=%d", who, h, w);
+    if (offsets) EEM_REQUIRE(starts[0] >= 0, "%s: offsets[0] = %ld", who, (long)starts[0]);
     const int ebx = pk_elem_bytes(code_x), eby = pk_elem_bytes(code_y);
-    EEM_REQUIRE(ebx != 0 && eby != 0, "eemflow_event_mask_windows: unknown dtype code %d / %d", code_x, code_y);
-    const bool any_event = offsets[nwin] > offsets[0];
-    EEM_REQUIRE((x && y) || !any_event, "eemflow_event_mask_windows: a column is NULL");
-    EEM_REQUIRE(((uintptr_t)x & (uintptr_t)(ebx - 1)) == 0 && ((uintptr_t)y & (uintptr_t)(eby - 1)) == 0,
-                "eemflow_event_mask_windows: a column is not aligned to its elements");
+    EEM_REQUIRE(ebx != 0 && eby != 0, "%s: unknown dtype code %d / %d", who, code_x, code_y);
+    // the columns are asked about before the windows, as they always were: offsets[nwin] > offsets[0] for the consecutive form
+    bool any_event = offsets && ends[nwin - 1] > starts[0];
+    for (int k = 0; k < nwin && !offsets; ++k) any_event = any_event || ends[k] > starts[k];
+    EEM_REQUIRE((x && y) || !any_event, "%s: a column is NULL", who);
+    EEM_REQUIRE(((uintptr_t)x & (uintptr_t)(ebx - 1)) == 0 && ((uintptr_t)y & (uintptr_t)(eby - 1)) == 0, "%s: a column is not aligned to its elements",
+                who);
     MaskJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     long nmax = 0;
     for (int k = 0; k < nwin; ++k) {
-        EEM_REQUIRE(offsets[k + 1] >= offsets[k], "eemflow_event_mask_windows: the offsets must ascend (window %d: %ld .. %ld)", k, (long)offsets[k],
-                    (long)offsets[k + 1]);
-        EEM_REQUIRE(masks[k] != nullptr && ((uintptr_t)masks[k] & 3) == 0, "eemflow_event_mask_windows: window %d has no 4-byte aligned mask", k);
+        if (offsets) {
+            EEM_REQUIRE(ends[k] >= starts[k], "%s: the offsets must ascend (window %d: %ld .. %ld)", who, k, (long)starts[k], (long)ends[k]);
+        } else {
+            EEM_REQUIRE(starts[k] >= 0 && ends[k] >= starts[k], "%s: span %d is [%ld, %ld): 0 <= start <= end", who, k, (long)starts[k], (long)ends[k]);
+        }
+        EEM_REQUIRE(masks[k] != nullptr && ((uintptr_t)masks[k] & 3) == 0, "%s: window %d has no 4-byte aligned mask", who, k);
         jobs.out[k] = masks[k];
-        jobs.first[k] = offsets[k];
-        jobs.n[k] = offsets[k + 1] - offsets[k];
+        jobs.first[k] = starts[k];
+        jobs.n[k] = ends[k] - starts[k];
         nmax = std::max(nmax, (long)jobs.n[k]);
     }
     const long hw = (long)h * w;
@@ -158,4 +166,16 @@ extern "C" int eemflow_event_mask_windows(int nwin, const void* x, const void* y
         EEM_HIP_CHECK(hipGetLastError());
     }
     return EEM_OK;
+}
+
+}  // namespace
+
+extern "C" int eemflow_event_mask_windows(int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* offsets, int h, int w,
+                                          float* const* masks, void* stream) {
+    return mask_windows("eemflow_event_mask_windows", true, nwin, x, y, code_x, code_y, offsets, offsets ? offsets + 1 : nullptr, h, w, masks, stream);
+}
+
+extern "C" int eemflow_event_mask_spans(int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* starts, const int64_t* ends, int h,
+                                        int w, float* const* masks, void* stream) {
+    return mask_windows("eemflow_event_mask_spans", false, nwin, x, y, code_x, code_y, starts, ends, h, w, masks, stream);
 }

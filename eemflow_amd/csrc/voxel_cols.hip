@@ -1,4 +1,5 @@
-// The windows of one device-resident recording, voxelized straight from its raw columns (eemflow_voxelize_windows): voxel.hip's two
+// The windows of one device-resident recording, voxelized straight from its raw columns (eemflow_voxelize_windows, and by span
+// - overlapping, nested, repeated windows in any order - eemflow_voxelize_spans; one body, cols_voxelize): voxel.hip's two
 // temporal votes per event, without the float64 table in between.  Cutting a recording into windows through the table costs, per
 // event, 13 B read + 32 B written by event_pack_kernel and 32 B read again by vox_bin_kernel; here the binning kernel reads the 13 B
 // (t int64, x and y uint16, p one byte in an HREM-style npz) and does event_pack_kernel's arithmetic in registers:
@@ -137,18 +138,18 @@ int launch_bin_cols(const VoxJobs& jobs, const ColsFirst& firsts, const ColsReco
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the banded form: the launch sequence of voxel.hip's planned path with the other first kernel
-int cols_launch_banded(int nwin, const ColsRecording& rec, const int64_t* offsets, int bins, int h, int w, int normalize, float* const* grid,
+int cols_launch_banded(const char* who, int nwin, const ColsRecording& rec, const int64_t* starts, const int64_t* ends, int bins, int h, int w, int normalize, float* const* grid,
                        void* const* scratch, const VoxPlan& pl, int lds, hipStream_t stream) {
     VoxJobs jobs;
     ColsFirst firsts;
     memset(&jobs, 0, sizeof(jobs));
     memset(&firsts, 0, sizeof(firsts));
     int64_t nmax = 0;
-    for (int k = 0; k < nwin; ++k) nmax = std::max(nmax, offsets[k + 1] - offsets[k]);
+    for (int k = 0; k < nwin; ++k) nmax = std::max(nmax, ends[k] - starts[k]);
     const int ept = vox_ept((long)nmax);                               // one EPT for all windows (the longest one's)
     long nblk_max = 0;
     for (int k = 0; k < nwin; ++k) {
-        const long n = (long)(offsets[k + 1] - offsets[k]);
+        const long n = (long)(ends[k] - starts[k]);
         VoxScratch* sc = (VoxScratch*)scratch[k];
         const long slots = (n + 8191) / 8192 * 8192 + 8192;            // (voxel_scratch_bytes)
         VoxJob& J = jobs.j[k];
@@ -157,8 +158,8 @@ int cols_launch_banded(int nwin, const ColsRecording& rec, const int64_t* offset
         J.run_start = J.recs + slots * 3;
         J.grid = grid[k]; J.acc = sc->acc;
         J.nblk = (int)std::max(1L, vox_blocks(n, ept));                // an empty window: one block, a run table row of zeros
-        EEM_REQUIRE((long)J.nblk * VT * ept <= slots, "eemflow_voxelize_windows: slab budget (n=%ld, ept=%d)", n, ept);
-        firsts.first[k] = (long long)offsets[k];
+        EEM_REQUIRE((long)J.nblk * VT * ept <= slots, "%s: slab budget (n=%ld, ept=%d)", who, n, ept);
+        firsts.first[k] = (long long)starts[k];
         nblk_max = std::max(nblk_max, (long)J.nblk);
     }
     int rc;
@@ -178,7 +179,7 @@ int cols_launch_banded(int nwin, const ColsRecording& rec, const int64_t* offset
 }
 
 // the other grids: the windows' tables into scratch (behind each window's voxelizer scratch), then voxel.hip's direct kernel window by window
-int cols_launch_direct(int nwin, const ColsRecording& rec, const int64_t* offsets, int bins, int h, int w, int normalize, float* const* grid,
+int cols_launch_direct(int nwin, const ColsRecording& rec, const int64_t* starts, const int64_t* ends, int bins, int h, int w, int normalize, float* const* grid,
                        void* const* scratch, hipStream_t stream) {
     const long total = (long)bins * h * w;
     const void* col[4][VOX_MAX_JOBS];
@@ -186,10 +187,10 @@ int cols_launch_direct(int nwin, const ColsRecording& rec, const int64_t* offset
     int64_t n[VOX_MAX_JOBS];
     double* table[VOX_MAX_JOBS];
     for (int k = 0; k < nwin; ++k) {
-        n[k] = offsets[k + 1] - offsets[k];
+        n[k] = ends[k] - starts[k];
         table[k] = reinterpret_cast<double*>((char*)scratch[k] + up256(voxel_scratch_bytes(n[k])));
         for (int c = 0; c < 4; ++c) {
-            col[c][k] = (const char*)rec.col[c] + (size_t)offsets[k] * pk_elem_bytes(rec.code[c]);
+            col[c][k] = (const char*)rec.col[c] + (size_t)starts[k] * pk_elem_bytes(rec.code[c]);
             codes[4 * k + c] = rec.code[c];
         }
     }
@@ -224,45 +225,48 @@ int cols_launch_direct(int nwin, const ColsRecording& rec, const int64_t* offset
     return EEM_OK;
 }
 
-}  // namespace
-
-extern "C" int eemflow_voxelize_windows(int nwin, const void* t, const void* x, const void* y, const void* p, const int codes[4],
-                                        const int64_t* offsets, double scale_a, double scale_b, int relative, int bins, int h, int w,
-                                        int normalize, float* const* grids, void* stream) {
+// the body of both entry points: job k is the elements [starts[k], ends[k]) of the recording.  `who` names the entry point in the error
+// messages; `offsets` (the consecutive form: starts = offsets, ends = offsets + 1) only words two of them
+int cols_voxelize(const char* who, bool offsets, int nwin, const void* t, const void* x, const void* y, const void* p, const int codes[4],
+                  const int64_t* starts, const int64_t* ends, double scale_a, double scale_b, int relative, int bins, int h, int w, int normalize,
+                  float* const* grids, void* stream) {
     static Arena arena;                                                // its own pool of scratch arenas, handled as eemflow_voxelize_many's
-    EEM_REQUIRE(nwin >= 1 && nwin <= VOX_MAX_JOBS, "eemflow_voxelize_windows: 1..%d windows per call; got %d", VOX_MAX_JOBS, nwin);
-    EEM_REQUIRE(codes && offsets && grids, "eemflow_voxelize_windows: NULL argument");
-    EEM_REQUIRE(bins > 0 && h > 0 && w > 0, "eemflow_voxelize_windows: bad shape bins=%d h=%d w=%d", bins, h, w);
-    EEM_REQUIRE(normalize >= 0 && normalize <= 2, "eemflow_voxelize_windows: normalize is 0 (raw), 1 (normalised grid) or 2 (raw grid + record); got %d",
-                normalize);
-    EEM_REQUIRE(offsets[0] >= 0, "eemflow_voxelize_windows: offsets[0] = %ld", (long)offsets[0]);
+    EEM_REQUIRE(nwin >= 1 && nwin <= VOX_MAX_JOBS, "%s: 1..%d windows per call; got %d", who, VOX_MAX_JOBS, nwin);
+    EEM_REQUIRE(codes && starts && ends && grids, "%s: NULL argument", who);
+    EEM_REQUIRE(bins > 0 && h > 0 && w > 0, "%s: bad shape bins=%d h=%d w=%d", who, bins, h, w);
+    EEM_REQUIRE(normalize >= 0 && normalize <= 2, "%s: normalize is 0 (raw), 1 (normalised grid) or 2 (raw grid + record); got %d", who, normalize);
+    if (offsets) EEM_REQUIRE(starts[0] >= 0, "%s: offsets[0] = %ld", who, (long)starts[0]);
+    bool any_event = false;
     for (int k = 0; k < nwin; ++k) {
-        EEM_REQUIRE(offsets[k + 1] >= offsets[k], "eemflow_voxelize_windows: the offsets must ascend (window %d: %ld .. %ld)", k, (long)offsets[k],
-                    (long)offsets[k + 1]);
-        EEM_REQUIRE(grids[k] != nullptr && ((uintptr_t)grids[k] & 3) == 0, "eemflow_voxelize_windows: window %d has no 4-byte aligned grid", k);
+        if (offsets) {
+            EEM_REQUIRE(ends[k] >= starts[k], "%s: the offsets must ascend (window %d: %ld .. %ld)", who, k, (long)starts[k], (long)ends[k]);
+        } else {
+            EEM_REQUIRE(starts[k] >= 0 && ends[k] >= starts[k], "%s: span %d is [%ld, %ld): 0 <= start <= end", who, k, (long)starts[k], (long)ends[k]);
+        }
+        EEM_REQUIRE(grids[k] != nullptr && ((uintptr_t)grids[k] & 3) == 0, "%s: window %d has no 4-byte aligned grid", who, k);
+        any_event = any_event || ends[k] > starts[k];
     }
     ColsRecording rec;
     memset(&rec, 0, sizeof(rec));
     const void* col[4] = {t, x, y, p};
-    const bool any_event = offsets[nwin] > offsets[0];
     for (int c = 0; c < 4; ++c) {
         const int eb = pk_elem_bytes(codes[c]);
-        EEM_REQUIRE(eb != 0, "eemflow_voxelize_windows: column %d: unknown dtype code %d", c, codes[c]);
-        EEM_REQUIRE(col[c] != nullptr || !any_event, "eemflow_voxelize_windows: column %d is NULL", c);
-        EEM_REQUIRE((reinterpret_cast<uintptr_t>(col[c]) & (uintptr_t)(eb - 1)) == 0,
-                    "eemflow_voxelize_windows: column %d is not aligned to its %d-byte elements", c, eb);
+        EEM_REQUIRE(eb != 0, "%s: column %d: unknown dtype code %d", who, c, codes[c]);
+        EEM_REQUIRE(col[c] != nullptr || !any_event, "%s: column %d is NULL", who, c);
+        EEM_REQUIRE((reinterpret_cast<uintptr_t>(col[c]) & (uintptr_t)(eb - 1)) == 0, "%s: column %d is not aligned to its %d-byte elements", who, c,
+                    eb);
         rec.col[c] = col[c];
         rec.code[c] = codes[c];
     }
     rec.scale_a = scale_a; rec.scale_b = scale_b; rec.relative = relative ? 1 : 0;
     int64_t nmax = 0;
-    for (int k = 0; k < nwin; ++k) nmax = std::max(nmax, offsets[k + 1] - offsets[k]);
+    for (int k = 0; k < nwin; ++k) nmax = std::max(nmax, ends[k] - starts[k]);
     VoxPlan pl;
     int lds = 0;
     const bool banded = make_plan(nmax, bins, h, w, nullptr, &pl, &lds);
     size_t part[VOX_MAX_JOBS] = {}, need = 0;
     for (int k = 0; k < nwin; ++k) {
-        const int64_t n = offsets[k + 1] - offsets[k];
+        const int64_t n = ends[k] - starts[k];
         part[k] = up256(voxel_scratch_bytes(n)) + (banded ? 0 : up256((size_t)n * 32));
         need += part[k];
     }
@@ -273,7 +277,24 @@ extern "C" int eemflow_voxelize_windows(int nwin, const void* t, const void* x, 
     if (rc != EEM_OK) return rc;
     void* scratch[VOX_MAX_JOBS];
     for (int k = 0; k < nwin; ++k) { scratch[k] = base; base += part[k]; }
-    rc = banded ? cols_launch_banded(nwin, rec, offsets, bins, h, w, normalize, grids, scratch, pl, lds, (hipStream_t)stream)
-                : cols_launch_direct(nwin, rec, offsets, bins, h, w, normalize, grids, scratch, (hipStream_t)stream);
+    rc = banded ? cols_launch_banded(who, nwin, rec, starts, ends, bins, h, w, normalize, grids, scratch, pl, lds, (hipStream_t)stream)
+                : cols_launch_direct(nwin, rec, starts, ends, bins, h, w, normalize, grids, scratch, (hipStream_t)stream);
     return rc == EEM_OK ? arena.done(token, stream) : rc;
+}
+
+}  // namespace
+
+extern "C" int eemflow_voxelize_windows(int nwin, const void* t, const void* x, const void* y, const void* p, const int codes[4],
+                                        const int64_t* offsets, double scale_a, double scale_b, int relative, int bins, int h, int w,
+                                        int normalize, float* const* grids, void* stream) {
+    // (the body refuses nwin outside 1..32 before it reads an element; offsets + 1 of a NULL offsets must stay NULL)
+    return cols_voxelize("eemflow_voxelize_windows", true, nwin, t, x, y, p, codes, offsets, offsets ? offsets + 1 : nullptr, scale_a, scale_b,
+                         relative, bins, h, w, normalize, grids, stream);
+}
+
+extern "C" int eemflow_voxelize_spans(int nwin, const void* t, const void* x, const void* y, const void* p, const int codes[4], const int64_t* starts,
+                                      const int64_t* ends, double scale_a, double scale_b, int relative, int bins, int h, int w, int normalize,
+                                      float* const* grids, void* stream) {
+    return cols_voxelize("eemflow_voxelize_spans", false, nwin, t, x, y, p, codes, starts, ends, scale_a, scale_b, relative, bins, h, w, normalize,
+                         grids, stream);
 }

@@ -126,8 +126,27 @@ def stream_chunks(dataset, model, n, dev, fb_check=None, with_volumes=False):
             yield (list(range(s0, s0 + nflow)), pair_targets, [preds[-1] for _, preds in outs]) + tail
 
 
-def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, bidirectional=False, fb_check=None, iters=None, gt=None,
-                  t_edges=None, crop=None, eval_type='dense', is_car=False):
+def lag_plan(nwin, lag, chunk):
+    """The forward_stream calls of run_recording over nwin windows whose pairs are (a, a + lag), at most `chunk` windows per call:
+    [(reset, windows, pairs)].  The windows fall into `lag` classes r = 0 .. lag-1 - r, r + lag, r + 2*lag, ... - and each class is an
+    ordinary stream of neighbouring windows: its first call follows a reset_stream (reset True) and gives one flow fewer than it has
+    windows, every later call starts at the window the call before carried and gives as many flows as windows.  windows: the indices that
+    go into the call, in order; pairs: the (a, a + lag) that come out, in order.  Every window is in exactly one call, every pair comes
+    out once, class by class.  lag = 1 is the walk over consecutive windows (stream_plan's calls)."""
+    nwin, lag, chunk = int(nwin), int(lag), int(chunk)
+    if lag < 1 or chunk < 1:
+        raise ValueError(f"lag_plan: lag and chunk are positive, got {lag} and {chunk}")
+    plan = []
+    for r in range(min(lag, nwin)):
+        members = list(range(r, nwin, lag))
+        for i0 in range(0, len(members), chunk):
+            part = members[i0:i0 + chunk]
+            plan.append((i0 == 0, part, [(a - lag, a) for a in part if a - lag >= 0]))
+    return plan
+
+
+def run_recording(model, recording, offsets=None, chunk=None, fwl=False, rsat=False, bidirectional=False, fb_check=None, iters=None, gt=None,
+                  t_edges=None, crop=None, eval_type='dense', is_car=False, spans=None, lag=1, t_spans=None):
     """Flow along the consecutive windows [offsets[k], offsets[k+1]) of a resident recording (eemflow_amd.recording.EventRecording): a
     generator of one dict per pair of neighbouring windows, in time order -
         'k'         the pair's first window (the flow runs from window k to window k + 1)
@@ -150,14 +169,22 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
     that hold an event (mvsec_raw.event_mask_windows on the chunk's first windows; the item gains 'event_valid', [h, w] fp32 0 / 1).
     crop = (th, tw): the voxel grids are centre-cropped (mvsec.center_crop) before forward_stream, the model is sized to the crop,
     ground truth and mask are cropped the same way - the dataset's validation branch (MVSEC.py:193-197).  crop with fwl or rsat is
-    refused: the events would need the crop's offset.  Without these keywords items, launches and lines are exactly as before."""
-    from .recording import _check_offsets, voxelize_windows
+    refused: the events would need the crop's offset.  Without these keywords items, launches and lines are exactly as before.
+    Windows BY SPAN and pairs at a LAG: instead of offsets, spans = a (K, 2) array of [start, end) event indices whose starts and
+    whose ends are each non-decreasing (windows that overlap: EventRecording.sliding_spans, MvsecRaw.frame_spans), and lag >= 1: the
+    pairs are (a, a + lag), K - lag of them.  No model knows about the lag: the windows are walked class by class (lag_plan) - class r
+    is the windows r, r + lag, r + 2*lag, ..., an ordinary stream of neighbouring pairs after a reset_stream - so every window is
+    still voxelized once and encoded once, and E-RAFT's warm start runs along each class.  The items come out class-major, not in time
+    order; with spans each also carries 'k2', the pair's second window.  FWL / RSAT / the sparse mask use window k's events.  With
+    spans, gt= takes t_spans = (K - lag, 2) timestamps: pair p = (p, p + lag) is scored over [t_spans[p, 0], t_spans[p, 1]]; with
+    offsets and a lag, pair k is scored over [t_edges[k], t_edges[k + lag]].  Give exactly one of offsets and spans."""
+    from .recording import _windows_of, voxelize_windows
     if fb_check is not None:
         bidirectional = True
     if eval_type not in ('dense', 'sparse'):
         raise ValueError(f"run_recording: eval_type is 'dense' or 'sparse', got {eval_type!r}")
-    if gt is None and (t_edges is not None or eval_type != 'dense' or is_car):
-        raise ValueError("run_recording: t_edges=, eval_type='sparse' and is_car= qualify gt= (the ground truth they score against)")
+    if gt is None and (t_edges is not None or t_spans is not None or eval_type != 'dense' or is_car):
+        raise ValueError("run_recording: t_edges=, t_spans=, eval_type='sparse' and is_car= qualify gt= (the ground truth they score against)")
     if crop is not None:
         if fwl or rsat:
             raise ValueError("run_recording: crop= with fwl= or rsat= is refused: the events are not moved into the crop's frame")
@@ -168,19 +195,38 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
         raise ValueError(f"fb_check= needs a model whose forward_stream takes bidirectional=True (EEMFlow); {type(model).__name__} has none")
     if not hasattr(model, "forward_stream"):
         raise ValueError(f"run_recording needs a model with forward_stream (EEMFlow, EEMFlow_cdc, ERAFT); {type(model).__name__} has none")
-    offs = _check_offsets("run_recording", offsets, recording.n)
+    offs, span_list = _windows_of("run_recording", offsets, spans, recording.n)
+    if int(lag) != lag or int(lag) < 1:
+        raise ValueError(f"run_recording: lag is a positive number of windows (the pairs are (a, a + lag)), got {lag!r}")
+    lag = int(lag)
+    if offs is None and any(b[0] < a[0] or b[1] < a[1] for a, b in zip(span_list, span_list[1:])):
+        raise ValueError("run_recording: the spans' starts and ends must each be non-decreasing (windows in time order)")
+    nwin = len(span_list)
+    npairs = max(nwin - lag, 0)
     limit = model.MAX_STREAM_BIDIR if bidirectional else model.MAX_STREAM
     chunk = limit if chunk is None else int(chunk)
     if not 1 <= chunk <= limit:
         raise ValueError(f"run_recording: chunk is 1..{limit} windows per forward_stream call" + (" with bidirectional=True" if bidirectional else "")
                          + f", got {chunk}")
+    pair_times = None                                                # per pair (a, a + lag), by a: the [start, end] its ground truth covers
     if gt is not None:
-        if t_edges is None or len(t_edges) != len(offs):
-            raise ValueError(f"run_recording: gt= needs t_edges=, one timestamp per window edge ({len(offs)} for these offsets)")
-        t_edges = [float(t) for t in t_edges]
+        if offs is not None:
+            if t_spans is not None:
+                raise ValueError("run_recording: t_spans= goes with spans=; with offsets give t_edges=")
+            if t_edges is None or len(t_edges) != len(offs):
+                raise ValueError(f"run_recording: gt= needs t_edges=, one timestamp per window edge ({len(offs)} for these offsets)")
+            t_edges = [float(t) for t in t_edges]
+            pair_times = [(t_edges[a], t_edges[a + lag]) for a in range(npairs)]
+        else:
+            if t_edges is not None:
+                raise ValueError("run_recording: t_edges= goes with offsets; with spans= give t_spans=")
+            rows = [] if t_spans is None else [tuple(float(v) for v in row) for row in t_spans]
+            if t_spans is None or len(rows) != npairs or any(len(row) != 2 for row in rows):
+                raise ValueError(f"run_recording: gt= needs t_spans=, one (start, end) per pair ({npairs} for {nwin} spans at lag {lag})")
+            pair_times = rows
         if (gt.height, gt.width) != (recording.height, recording.width) or gt.device != recording.device:
             raise ValueError("run_recording: the ground truth and the recording differ in size or device")
-        for t0, t1 in zip(t_edges, t_edges[1:-1]):
+        for t0, t1 in pair_times:
             gt.plan(t0, t1)                                          # a window the stack cannot serve is refused before any launch
     size = crop if crop is not None else (recording.height, recording.width)
     if tuple(int(v) for v in getattr(model, "image_size", None) or ()) != size:
@@ -194,25 +240,38 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
         if int(iters) < 1:
             raise ValueError(f"run_recording: iters is a positive number of refinement steps, got {iters}")
         extra["iters"] = int(iters)
-    nwin = len(offs) - 1
-    k = 0                                                            # the next pair's first window
-    for w0 in range(0, nwin, chunk):
-        part = offs[w0:w0 + chunk + 1]
-        vols = voxelize_windows(recording, part, model.n_first_channels)
+    consecutive = offs is not None and lag == 1                      # today's walk: every call's windows are neighbours in offs
+
+    def windows_of(idx):                                             # how recording.* is told about the windows idx
+        if consecutive:
+            return dict(offsets=offs[idx[0]:idx[-1] + 2])
+        return dict(spans=[span_list[i] for i in idx])
+
+    for call, (reset, wins, pairs) in enumerate(lag_plan(nwin, lag, chunk)):
+        if reset and call > 0:
+            model.reset_stream()                                     # the next class is a stream of its own
+        vols = voxelize_windows(recording, num_bins=model.n_first_channels, **windows_of(wins))
         if crop is not None:
             from .mvsec import center_crop
             vols = [center_crop(v, crop) for v in vols]
         outs = model.forward_stream(vols, **extra)
+        if len(outs) != len(pairs):
+            raise RuntimeError(f"run_recording: windows {wins} gave {len(outs)} flows for the pairs {pairs}")
         if not outs:
-            continue                                                 # the first chunk held one window: it is carried
-        items = [{'k': k + i, 'flow': o[1][-1]} for i, o in enumerate(outs)]
+            continue                                                 # the call held one window: it is carried
+        firsts = [a for a, _ in pairs]                               # the pairs' first windows
+        n = len(outs)
+        items = [{'k': a, 'flow': o[1][-1]} for (a, _), o in zip(pairs, outs)]
+        if offs is None:
+            for it, (_, b) in zip(items, pairs):
+                it['k2'] = b
         if bidirectional:
             for it, o in zip(items, outs):
                 it['flow_bw'] = o[2][-1]
                 if fb_check is not None:
                     it['mask_fw'], it['mask_bw'] = o[3]
         if fwl or rsat:
-            tables = recording.tables(offs[k:k + len(outs) + 1])     # the pairs' first windows
+            tables = recording.tables(**windows_of(firsts))
             flows = [it['flow'][0] for it in items]
             if fwl:
                 from .iwe import fwl_many                            # (the package's attribute `iwe` is the one-job function, not the module)
@@ -223,12 +282,11 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
                 for it, v in zip(items, rsat_many(tables, flows)):
                     it['RSAT'] = v
         if gt is not None:
-            n = len(outs)
-            gts = gt.flow_many(t_edges[k:k + n], t_edges[k + 1:k + n + 1])
+            gts = gt.flow_many([pair_times[a][0] for a in firsts], [pair_times[a][1] for a in firsts])
             masks = None
             if eval_type == 'sparse':
                 from .mvsec_raw import event_mask_windows
-                masks = event_mask_windows(recording, offs[k:k + n + 1])
+                masks = event_mask_windows(recording, **windows_of(firsts))
             if crop is not None:
                 from .mvsec import center_crop
                 gts = center_crop(gts, crop).contiguous()            # (one copy for the chunk; its slices are contiguous)
@@ -239,7 +297,6 @@ def run_recording(model, recording, offsets, chunk=None, fwl=False, rsat=False, 
                 it['flow_gt'], it['err_sums'] = gts[i:i + 1], sums[i]
                 if masks is not None:
                     it['event_valid'] = masks[i]
-        k += len(outs)
         yield from items
 
 

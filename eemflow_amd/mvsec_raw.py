@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, events
-from .recording import EventRecording, _check_offsets
+from .recording import EventRecording, _check_offsets, _check_spans, _windows_of
 
 MAX_JOBS_PER_CALL = 32                                             # GT_MAX_JOBS
 UPLOAD_CHUNK_BYTES = 64 << 20
@@ -180,27 +180,34 @@ def estimate_corresponding_gt_flow(x_flow_in, y_flow_in, gt_timestamps, start_ti
     return out[0], out[1]
 
 
-def event_mask_windows(recording, offsets, out=None):
+def event_mask_windows(recording, offsets=None, out=None, spans=None):
     """The event masks of the windows [offsets[k], offsets[k+1]) of a resident recording: a (K,H,W) fp32 tensor of 0 / 1, mask k
-    `mvsec.event_mask` of window k's events (eemflow_event_mask_windows).  32 windows per call, no synchronisation."""
+    `mvsec.event_mask` of window k's events (eemflow_event_mask_windows).  32 windows per call, no synchronisation.  Instead of
+    offsets, spans=: a (K, 2) array of [start, end) event indices in any order (eemflow_event_mask_spans).  Exactly one of the two."""
     if not isinstance(recording, EventRecording):
         raise TypeError("event_mask_windows: recording is an EventRecording")
-    offs = _check_offsets("event_mask_windows", offsets, recording.n)
-    k_all, h, w, dev = len(offs) - 1, recording.height, recording.width, recording.device
+    offs, span_list = _windows_of("event_mask_windows", offsets, spans, recording.n)
+    k_all, h, w, dev = len(span_list), recording.height, recording.width, recording.device
     if k_all < 1:
-        raise ValueError("event_mask_windows: offsets are K + 1 >= 2 event indices")
+        raise ValueError("event_mask_windows: offsets are K + 1 >= 2 event indices" if offs is not None else
+                         "event_mask_windows: spans are K >= 1 windows")
     if out is None:
         out = torch.empty(k_all, h, w, dtype=torch.float32, device=dev)
     elif tuple(out.shape) != (k_all, h, w) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
         raise ValueError(f"event_mask_windows: out is a contiguous ({k_all},{h},{w}) float32 tensor on {dev}")
     with torch.no_grad(), torch.cuda.device(dev):
+        xy = (ctypes.c_void_p(recording.column_ptr(1)), ctypes.c_void_p(recording.column_ptr(2)), recording.codes[1], recording.codes[2])
         for i0 in range(0, k_all, MAX_JOBS_PER_CALL):
-            part = offs[i0:i0 + MAX_JOBS_PER_CALL + 1]
-            k = len(part) - 1
-            _lib.check(_lib.lib().eemflow_event_mask_windows(
-                k, ctypes.c_void_p(recording.column_ptr(1)), ctypes.c_void_p(recording.column_ptr(2)), recording.codes[1], recording.codes[2],
-                (ctypes.c_int64 * (k + 1))(*part), h, w, (ctypes.c_void_p * k)(*[out[i0 + i].data_ptr() for i in range(k)]),
-                _lib.current_stream_ptr(dev)))
+            part = span_list[i0:i0 + MAX_JOBS_PER_CALL]
+            k = len(part)
+            ptrs = (ctypes.c_void_p * k)(*[out[i0 + i].data_ptr() for i in range(k)])
+            if offs is None:
+                _lib.check(_lib.lib().eemflow_event_mask_spans(k, *xy, (ctypes.c_int64 * k)(*[a for a, _ in part]),
+                                                               (ctypes.c_int64 * k)(*[b for _, b in part]), h, w, ptrs,
+                                                               _lib.current_stream_ptr(dev)))
+            else:
+                _lib.check(_lib.lib().eemflow_event_mask_windows(k, *xy, (ctypes.c_int64 * (k + 1))(*offs[i0:i0 + k + 1]), h, w, ptrs,
+                                                                 _lib.current_stream_ptr(dev)))
     return out
 
 
@@ -243,6 +250,54 @@ class MvsecRaw:
         _check_offsets("MvsecRaw.frame_windows", offsets, self.recording.n)
         return offsets, t_edges
 
+    def frame_spans(self, first, last, dt=1, stride=None, reference_pairs=False):
+        """frame_spans(image_raw_ts, image_raw_event_inds, first, last, dt, stride, reference_pairs) checked against this sequence's
+        events."""
+        spans, t_spans, lag = frame_spans(self.image_raw_ts, self.image_raw_event_inds, first, last, dt, stride=stride,
+                                          reference_pairs=reference_pairs)
+        _check_spans("MvsecRaw.frame_spans", spans, self.recording.n)
+        return spans, t_spans, lag
+
+
+def frame_spans(image_raw_ts, image_raw_event_inds, first, last, dt=1, stride=None, reference_pairs=False):
+    """Windows of dt grey frames that start every `stride` frames, and the pairs to run on them: (spans, t_spans, lag).  Window m starts
+    at grey frame f_m = first + m*stride and is the events [inds[f_m], inds[f_m + dt]) (an index < 0 counts as 0): spans is (K, 2) int64.
+    Pair m is windows (m, m + lag), its ground truth covers [t_spans[m, 0], t_spans[m, 1]] (t_spans: (P, 2) float64), K = P + lag:
+      stride = None or dt    lag 1, P = (last - first) // dt + 1: the windows and edges of frame_windows - consecutive windows;
+      stride dividing dt     lag = dt // stride, P = (last - first) // stride + 1: pair m compares window m with the window that starts
+                             where it ends, t_spans[m] = (ts[f_m], ts[f_m + dt]) - a flow over dt frames every `stride` frames;
+      reference_pairs        stride is 1, lag 1, P = last - first + 1: pair m compares window m with the window ONE frame later and its
+                             ground truth covers (ts[first + m], ts[first + m + dt]).  For dt = 4 these are exactly the samples
+                             first..last of MvsecEventFlow_dt4 (loader/MVSEC.py:201-283: files i+1..i+4 against i+2..i+5, flowgt_dt4/i.npy),
+                             for dt = 1 those of MvsecEventFlow.
+    Refused: a stride that does not divide dt, frames beyond the sequence, descending indices.  Host only."""
+    ts = np.asarray(image_raw_ts, dtype=np.float64)
+    inds = np.asarray(image_raw_event_inds).astype(np.int64)
+    first, last, dt = int(first), int(last), int(dt)
+    if dt < 1:
+        raise ValueError(f"frame_spans: dt is a positive number of frames, got {dt}")
+    if first < 0 or last < first:
+        raise ValueError(f"frame_spans: 0 <= first <= last, got {first}, {last}")
+    if reference_pairs:
+        if stride is not None and int(stride) != 1:
+            raise ValueError(f"frame_spans: reference_pairs slide by one frame; got stride={stride}")
+        stride, lag = 1, 1
+    else:
+        stride = dt if stride is None else int(stride)
+        if stride < 1 or dt % stride != 0:
+            raise ValueError(f"frame_spans: the stride must divide dt={dt}, got {stride}")
+        lag = dt // stride
+    pairs = (last - first) // stride + 1
+    f = first + stride * np.arange(pairs + lag)
+    if f[-1] + dt >= inds.shape[0]:
+        raise ValueError(f"frame_spans: pairs {first}..{last} at dt={dt}, stride={stride} need grey frame {int(f[-1] + dt)}; the sequence "
+                         f"has {inds.shape[0]}")
+    spans = np.stack([np.maximum(inds[f], 0), np.maximum(inds[f + dt], 0)], axis=1).astype(np.int64)
+    if np.any(spans[:, 1] < spans[:, 0]) or np.any(spans[1:] < spans[:-1]):
+        raise ValueError("frame_spans: image_raw_event_inds does not ascend over these frames")
+    t_spans = np.ascontiguousarray(np.stack([ts[f[:pairs]], ts[f[:pairs] + dt]], axis=1))
+    return spans, t_spans, lag
+
 
 def frame_windows(image_raw_ts, image_raw_event_inds, first, last, dt=1):
     """The windows of the pairs first, first + dt, ..., <= last, cut on the grey frames: (offsets, t_edges), K + 1 event indices and K + 1
@@ -253,8 +308,8 @@ def frame_windows(image_raw_ts, image_raw_event_inds, first, last, dt=1):
     MvsecEventFlow (sample i: event files i + 1 and i + 2, flowgt_dt1/i.npy over [ts[i], ts[i+1]]).
     With dt > 1 the windows are CONSECUTIVE: pair m compares frames [first + m*dt, first + (m+1)*dt) with the dt frames after them.
     MvsecEventFlow_dt4 pairs windows that OVERLAP by three frames (sample i: files i+1..i+4 against i+2..i+5, flowgt_dt4/i.npy over
-    [ts[i], ts[i+4]]); its samples are reproduced here only at a stride of dt, old window and ground truth alike, and its new window is
-    not the one used here.  Host only."""
+    [ts[i], ts[i+4]]): that is another protocol, and these windows do not reproduce it.  `frame_spans(..., dt=4, reference_pairs=True)`
+    does, sample for sample; frame_spans also gives windows that slide by less than dt.  Host only."""
     ts = np.asarray(image_raw_ts, dtype=np.float64)
     inds = np.asarray(image_raw_event_inds).astype(np.int64)
     first, last, dt = int(first), int(last), int(dt)

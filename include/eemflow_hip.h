@@ -563,6 +563,20 @@ int eemflow_voxelize_windows(int nwin, const void* t, const void* x, const void*
                              const int64_t* offsets, double scale_a, double scale_b, int relative, int bins, int h, int w,
                              int normalize, float* const* grids, void* stream);
 
+/* Windows BY SPAN of one device-resident recording: job k is the elements [starts[k], ends[k]) of each column (starts, ends: nwin HOST
+ * integers each, 0 <= starts[k] <= ends[k], the columns at least max(ends) elements long), nwin = 1..32.  There is no ordering between
+ * jobs: spans may overlap, nest, repeat or be empty, so windows that slide by less than their length, or pairs of windows at a lag,
+ * are voxelized by one launch sequence.  Everything else is eemflow_voxelize_windows, which is this call with starts = offsets and
+ * ends = offsets + 1: the same kernels (every job's first element and length already travel separately), the same scratch layout, the
+ * banded form, the direct form for grids beyond the LDS layout or under EEM_VOX_DIRECT, the empty window, the same
+ * eemflow_voxelize_last_form text.  grids[k] is bitwise what eemflow_voxelize_many gives for the table eemflow_pack_events_many makes
+ * of span k's slice; two jobs with the same span get the same grid (each job has its own records: a window's votes depend on its own
+ * first and last timestamps).  The grids of a call must not overlap one another.  Stream-ordered, no host synchronisation; a bad
+ * argument is an error return before any launch. */
+int eemflow_voxelize_spans(int nwin, const void* t, const void* x, const void* y, const void* p, const int codes[4], const int64_t* starts,
+                           const int64_t* ends, double scale_a, double scale_b, int relative, int bins, int h, int w, int normalize,
+                           float* const* grids, void* stream);
+
 /* MVSEC ground-truth flow of njobs (1..32) windows by ONE launch, from the device-resident ground-truth stack gt ([nframes][2][h][w]
  * fp32: MVSEC's flow_dist, 20 Hz displacement maps; frame f is the displacement between timestamps f and f + 1).  The host plans each
  * window [start, end] (eemflow_amd.mvsec_raw.MvsecGroundTruth.plan, NumPy float64, the reference's searchsorted and scale factors):
@@ -597,6 +611,13 @@ int eemflow_gt_flow_many(int njobs, const float* gt, int nframes, int h, int w, 
  * Replaces: the event_valid image of loader/MVSEC.py:132-142 (eemflow_amd.mvsec.event_mask), built on the host per sample. */
 int eemflow_event_mask_windows(int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* offsets, int h, int w,
                                float* const* masks, void* stream);
+
+/* The event masks of nwin (1..32) windows BY SPAN of one device-resident recording: window k is the elements [starts[k], ends[k]) of the
+ * columns (starts, ends: nwin HOST integers each, 0 <= starts[k] <= ends[k]; no ordering between windows: they may overlap, nest, repeat
+ * or be empty).  Everything else is eemflow_event_mask_windows, which is this call with starts = offsets, ends = offsets + 1: the same
+ * two launches.  The masks of a call must not overlap one another. */
+int eemflow_event_mask_spans(int nwin, const void* x, const void* y, int code_x, int code_y, const int64_t* starts, const int64_t* ends, int h,
+                             int w, float* const* masks, void* stream);
 
 /* Augmentation of n (1..EEMFLOW_AUGMENT_MAX) training samples of one source size and one output size by ONE launch, written into the
  * batch tensors: vol_old[i], vol_new[i] ([C][H][W] fp32), flow[i] ([2][H][W]; fp64 with flow_f64 != 0, else fp32; a NULL entry, or

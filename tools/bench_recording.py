@@ -17,6 +17,14 @@ Before timing, the fused grid of the first window is held bitwise against the co
 Then (unless --no-model) frames per second of harness.run_recording with a seeded EEMFlow at 1280 x 720 over 32 windows, against
 EEMFlow.forward_stream on the same windows' volumes already resident.
 Writes the lines and one JSON line to --out (default profiles/recording_bench.txt beside this tool) and to stdout.
+--spans: windows by span instead (eemflow_voxelize_spans), written to profiles/spans_bench.txt: at 5 x 260 x 346 with 8e4 events per window and
+5 x 720 x 1280 with 2e6, 32 windows that overlap by 3/4 of their length -
+  spans        all 32 by one call of voxelize_windows(spans=)
+  one_by_one   the same 32 spans, one call of voxelize_windows(offsets) each: all the consecutive-window entry point can do for them
+  consecutive  32 consecutive windows of the same length by one call of voxelize_windows(offsets): the same kernels as `spans`
+then frames per second of MVSEC's dt4 protocol on the synthetic sequence of tests/test_gpu_spans.py (8 samples, 260 x 346, crop 256 x 256):
+harness.run_recording on MvsecRaw.frame_spans(reference_pairs=True) with ground truth and scoring - the loop of `cli mvsec --dt 4
+--reference_pairs` - against MvsecEventFlow_dt4 over files through harness.stream_chunks, scored the same way.
 --kernels-only: just `fused`, `generic` and `device` at 10 windows per call, a few calls (for a `rocprofv3 --kernel-trace --stats` run of its own:
 vox_bin_cols_kernel beside event_pack_kernel + vox_bin_kernel)."""
 import argparse
@@ -68,14 +76,87 @@ def alternate(routes, calls, rounds, per):
     return {name: (statistics.median(v), min(v), max(v)) for name, v in us.items()}
 
 
+SPAN_SIZES = (((5, 260, 346), 80_000), ((5, 720, 1280), 2_000_000))
+
+
+def spans_mode(a, say, res):
+    for (C, H, W), n in SPAN_SIZES:
+        k, stride = 32, n // 4
+        cols = make_columns(4, n, k, H, W)                             # 32 n events: the consecutive windows need them all
+        rec = R.EventRecording(*cols, H, W, device=DEV)
+        spans = rec.sliding_spans(count=n, stride_count=stride)[:k]
+        offsets = rec.window_offsets(count=n)
+        assert spans.shape == (k, 2) and len(offsets) == k + 1 and spans[1, 0] == stride
+        got = R.voxelize_windows(rec, spans=spans[1:2], num_bins=C)[0][0]
+        want = voxelize_many_device(rec.tables(spans=spans[1:2]), C, H, W)[0]
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), "a span's grid is not the composition's, bit for bit"
+        pairs = [[int(s), int(e)] for s, e in spans]
+        routes = {"spans": (lambda: R.voxelize_windows(rec, spans=spans, num_bins=C), 1.0),
+                  "one_by_one": (lambda: [R.voxelize_windows(rec, se, C) for se in pairs], 1.0),
+                  "consecutive": (lambda: R.voxelize_windows(rec, offsets, C), 1.0)}
+        out = alternate(routes, a.calls, a.rounds, k)
+        tag = f"{C}x{H}x{W}_{n:.0e}".replace("+0", "")
+        text = f"{C} x {H} x {W}, {n:.0e} events per window, 32 windows, overlap 3/4:"
+        for name, (med, lo, hi) in out.items():
+            text += f"   {name} {med:8.1f} ({lo:.1f}, {hi:.1f})"
+            res[f"{tag}_{name}_us"] = med
+            res[f"{tag}_{name}_spread_us"] = hi - lo
+        text += f"   one_by_one / spans {out['one_by_one'][0] / out['spans'][0]:5.2f} x   spans / consecutive {out['spans'][0] / out['consecutive'][0]:5.2f} x"
+        res[f"{tag}_one_by_one_over_spans"] = out["one_by_one"][0] / out["spans"][0]
+        res[f"{tag}_spans_over_consecutive"] = out["spans"][0] / out["consecutive"][0]
+        say(text)
+        del rec
+        torch.cuda.empty_cache()
+    if a.no_model:
+        return
+    import pathlib
+    import tempfile
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from mvsec_dt4_sequence import make_sequence                       # the sequence of the dt4 test: raw arrays and the dataset's files
+    from eemflow_amd import EEMFlow, mvsec, mvsec_raw as M
+    from eemflow_amd.metrics import flow_error_sums_many
+    from eemflow_amd.weights import seeded_state_dict
+    with tempfile.TemporaryDirectory() as tmp:
+        s = make_sequence(pathlib.Path(tmp))
+        first, last, crop = s["first"], s["last"], (256, 256)
+        net = EEMFlow("", 5, 5)
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in seeded_state_dict(3).items()})
+        net = net.to(DEV).eval()
+        net.change_imagesize(crop)
+        ds = mvsec.MvsecEventFlow_dt4({"eval_type": "dense", "num_voxel_bins": 5, "sequence": "seqA"}, train=False, root=s["root"], device=DEV,
+                                      valid_time_index={"seqA": [(first, last + 1)]})
+        gt = M.MvsecGroundTruth(s["stack"], s["gt_ts"], device=DEV)
+        raw = M.MvsecRaw(s["events"], s["img_ts"], s["inds"], gt, height=s["h"], width=s["w"], device=DEV)
+        spans, t_spans, lag = raw.frame_spans(first, last, 4, reference_pairs=True)
+
+        def raw_route():
+            for _ in harness.run_recording(net, raw.recording, spans=spans, lag=lag, t_spans=t_spans, gt=gt, crop=crop, chunk=4):
+                pass
+
+        def dataset_route():
+            for _, targets, flows in harness.stream_chunks(ds, net, 4, torch.device(DEV)):
+                flow_error_sums_many([t["flow"].to(DEV)[None].float() for t in targets], flows, None, evaluation_type="dense")
+
+        with torch.no_grad():
+            out = alternate({"raw": (raw_route, 1.0), "dataset": (dataset_route, 1.0)}, 3, a.rounds, len(t_spans))
+    text = f"EEMFlow, MVSEC dt4 protocol, {len(t_spans)} samples of 260 x 346 (crop 256 x 256, 4 windows per call), frames per second:"
+    for name, (med, lo, hi) in out.items():
+        text += f"   {name} {1e6 / med:8.1f} ({1e6 / hi:.1f}, {1e6 / lo:.1f})"
+        res[f"mvsec_dt4_{name}_fps"] = 1e6 / med
+    say(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20, help="calls per timed run (the host route: a fifth of it)")
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "recording_bench.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/recording_bench.txt, or profiles/spans_bench.txt with --spans")
+    ap.add_argument("--spans", action="store_true", help="windows by span: 32 overlapping spans per call against one call each and against consecutive windows")
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--no-model", action="store_true")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "spans_bench.txt" if a.spans else "recording_bench.txt")
     if not torch.cuda.is_available():
         raise SystemExit("bench_recording.py measures on the GPU: no device found")
     lines, res = [], {"calls_per_run": a.calls, "rounds": a.rounds}
@@ -84,10 +165,12 @@ def main():
         print(text, flush=True)
         lines.append(text)
 
-    say(f"tools/bench_recording.py --calls {a.calls} --rounds {a.rounds} (MI355X, one process, routes alternating; us per window, wall clock, "
+    say(f"tools/bench_recording.py{' --spans' if a.spans else ''} --calls {a.calls} --rounds {a.rounds} (MI355X, one process, routes alternating; us per window, wall clock, "
         f"median (min, max) of the rounds)")
     big = None
-    for (C, H, W), n in SIZES:
+    if a.spans:
+        spans_mode(a, say, res)
+    for (C, H, W), n in () if a.spans else SIZES:
         kmax = 10 if a.kernels_only else max(COUNTS)
         cols = make_columns(3, n, kmax, H, W)
         rec = R.EventRecording(*cols, H, W, device=DEV)
@@ -124,7 +207,7 @@ def main():
         if H == 720:
             big = (rec, offsets)
         torch.cuda.empty_cache()
-    if not a.kernels_only and not a.no_model:
+    if not a.kernels_only and not a.no_model and not a.spans:
         from eemflow_amd import EEMFlow
         from eemflow_amd.weights import seeded_state_dict
         rec, offsets = big
